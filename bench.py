@@ -8,8 +8,10 @@ A "step" is one pass of `pairing_batch` over one batch of synthetic (r*G1, s*G2)
   N = 1   BASELINE.json configs[1]: 2^16 independent pairings on one MI355X;
   N > 1   BASELINE.json configs[2]: 2^20 independent pairings sharded over the N GPUs (2^20/N each, contiguous index ranges, no
           data-path collective) - total work fixed, so "scaling": "strong".
-Rank 0 prints ONE JSON line.  The K steps are timed with the library's event profiling OFF; the per-kernel durations behind
-`roofline` come from a separate short profiled pass right after.  Extra objects:
+Rank 0 prints ONE JSON line.  The K steps are timed with the library's event profiling OFF.  A plain run stops there: it prints
+the line (`value`, `ms_per_step`, `config`) and, with --dump-outputs DIR, first writes the Gt values of the last timed step to DIR.
+With --full the default workload's line also carries these objects, measured after the timed steps (the per-kernel durations
+behind `roofline` come from a separate short profiled pass):
   roofline     the dominant kernel's algorithmic 32x32->64 MACs per step / its HIP-event-measured duration, against the
                v_mad_u64_u32 issue peak of the chip MEASURED IN THIS RUN (bn254_ubench_mac32 in the untimed prologue; this path is
                integer-VALU bound, not HBM or MFMA: SURVEY.md 8d); `traffic` is the rocprofv3 HBM byte count per launch taken
@@ -351,6 +353,26 @@ def host_api_rate(gpu_index, Pn, Qn, reps=5):
     e.close()
     return {"value": n / dt, "unit": "pairings/s", "ms_per_call": dt * 1e3, "single_pairing_ms": one * 1e3,
             "what": f"bn254_pairing_batch, {n} pairings per call, pageable numpy buffers: H2D {n * 288 / 1e6:.1f} MB + kernels + D2H {n * 384 / 1e6:.1f} MB; single_pairing_ms: the same call with n = 1"}
+
+
+DUMP_BUDGET = 64_000_000      # bytes of .npy written by --dump-outputs, over all ranks
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BUDGET, seed=0):
+    """--dump-outputs: every (rows, words) uint64 array of `arrays` goes to DIR/<name>.npy as float64 of shape (rows, words, 2), each word
+    split into its low and high 32-bit halves (exact in float64).  When the whole array would not fit in `budget` bytes, a fixed seeded
+    sample of rows is written instead; DIR/<name>_rows.npy (float64) always says which rows of the output the file holds."""
+    import numpy as np
+    d = pathlib.Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    per = budget // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.uint64).reshape(a.shape[0], -1)
+        keep = max(1, min(a.shape[0], (per - 1024) // (a.shape[1] * 16 + 8)))
+        rows = np.arange(a.shape[0]) if keep == a.shape[0] else np.sort(np.random.default_rng(seed).choice(a.shape[0], keep, replace=False))
+        s = a[rows]
+        np.save(d / f"{name}.npy", np.stack([s & np.uint64(0xFFFFFFFF), s >> np.uint64(32)], axis=-1).astype(np.float64))
+        np.save(d / f"{name}_rows.npy", rows.astype(np.float64))
 
 
 def _line(metric, unit, value, world, args, elapsed, scaling, workload, extra=None, cfg=None):
@@ -696,10 +718,17 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=None, help="pairings per GPU per step (default: 2^16 at N = 1, 2^20/N at N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="default workload: after the timed steps also measure the roofline (profiled pass + multiplier peak), power, the `side` "
+                         "configs, the host-buffer rate and the CPU baseline (the --no-* options below skip parts of it); without it the run "
+                         "does only what `value` needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="default workload: write the Gt values of the last timed step to DIR/*.npy (float64, every u64 word as two 32-bit "
+                         "halves; a fixed seeded sample of rows above 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-api", action="store_true")
-    ap.add_argument("--no-power", action="store_true", help="skip the sampled power leg (1.2 s more of the headline step after the timed region)")
-    ap.add_argument("--no-side", action="store_true", help="skip the `side` object (configs[3], configs[4], single-pairing latency) of the default line")
+    ap.add_argument("--no-power", action="store_true", help="--full: skip the sampled power leg (1.2 s more of the headline step after the timed region)")
+    ap.add_argument("--no-side", action="store_true", help="--full: skip the `side` object (configs[3], configs[4], single-pairing latency) of the default line")
     ap.add_argument("--workload", choices=["pairing", "g1mul", "g2mul", "gtpow", "prepared", "product", "product_prepared"], default="pairing",
                     help="pairing: the headline metric (default); the others are side metrics with their own line")
     ap.add_argument("--prepared-mode", choices=["native", "native_per_q", "reference"], default=None,
@@ -708,6 +737,10 @@ def main():
                     help="dist (default, what the driver runs): one process per GPU over torch.distributed/RCCL, inputs resident in HBM; "
                          "multi_c: ONE host process drives all GPUs through bn254_*_multi of the C ABI (host buffers, PCIe inclusive)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.mode != "dist" or args.workload != "pairing"):
+        ap.error("--dump-outputs writes the outputs of the default workload (--workload pairing, --mode dist) only")
 
     if args.mode == "multi_c":
         return bench_multi_c(args)
@@ -779,8 +812,21 @@ def main():
         out = eng.empty(n, 48)
         step = lambda: D.pairing_batch_sharded(eng, P, Q, out)
         elapsed = timed_steps(dist, dev, step, args.steps, args.warmup)          # profiling OFF inside the timed region
+        if args.dump_outputs:                                   # `out` holds the last timed step's Gt values (reference layout, Montgomery limbs)
+            dump_outputs(args.dump_outputs, {"pairing" if world == 1 else f"pairing_rank{rank}": out.cpu().numpy().view(np.uint64)},
+                         budget=DUMP_BUDGET // world)
+        cus = torch.cuda.get_device_properties(dev).multi_processor_count
+        line = _line("BN254 optimal-ate pairings/sec (bit-exact vs ref)", "pairings/s", total * args.steps / elapsed, world, args, elapsed,
+                     scaling, workload, None,
+                     {"pairings_per_gpu": n, "inputs": "r*G1 / s*G2 (Jacobian, z != 1) resident in HBM", "parallelism": f"dp{world} (sharded, no collective)",
+                      "number_system": "exact integer: 9 x 29-bit limbs in u32, v_mad_u64_u32 accumulation, Montgomery radix 2^261",
+                      "mapping": 1,
+                      # the lane-pair kernels are launched in rounds of 256 pairings per CU (two waves on every SIMD): the library
+                      # sizes its sub-launches from the CU count of the device it finds (bn_round_pairs in csrc/bn254_hip.hip)
+                      "cus": cus, "pairings_per_launch": n if n <= 256 * cus else f"equal parts of at most {256 * cus}",
+                      "process_group": (dist.get_backend() if dist.is_initialized() else None)})
 
-        if rank == 0:
+        if rank == 0 and args.full:
             ksteps = min(args.steps, 10)
             # (--batch below the wave-machine thresholds of csrc/bn254_hip.hip: the whole pairing is ONE kernel, "pairing_wave")
             # (--batch in the small / mid-size windows of csrc/bn254_hip.hip: one kernel "pairing_wave", or the four-lane kernels "*_quad")
@@ -788,7 +834,6 @@ def main():
             rf = roofline(eng, stats, n, MAC32_PER_PAIRING, dict(KERNEL_SHARE, final_exp_wave=KERNEL_SHARE["final_exp"], pairing_wave=1.0,
                                                                  miller_quad=KERNEL_SHARE["miller"], final_exp_quad=KERNEL_SHARE["final_exp"]), traffic_key=True, steps=ksteps)
             rf["algorithmic_hbm_bytes_per_launch"] = n * ALGO_BYTES_PER_PAIRING
-            cus = torch.cuda.get_device_properties(dev).multi_processor_count
             if cus != 256:
                 rf["traffic"] = rf["traffic_source"] = None          # the PMC figures in profiles/ were taken on 256 CUs (launch shapes differ elsewhere)
             if rf["traffic"] is not None:
@@ -804,15 +849,7 @@ def main():
                     rf["bound"] = ("valu-int32-mac at the socket power cap (neither hbm nor mfma: SURVEY.md 8d): %.0f W of the %s W cap at sclk %s MHz under these kernels IN THIS RUN "
                                    "(power_W / power_cap_W / sclk_MHz / energy_uJ_per_pairing of this object)"
                                    % (pw["power_W"], "%.0f" % pw["power_cap_W"] if pw["power_cap_W"] else "?", "%.0f" % pw["sclk_MHz"] if pw["sclk_MHz"] else "?"))
-            line = _line("BN254 optimal-ate pairings/sec (bit-exact vs ref)", "pairings/s", total * args.steps / elapsed, world, args, elapsed,
-                         scaling, workload, {"roofline": rf, **({"expected_scaling": expected_scaling("pairing", world, scaling_inputs())} if world > 1 and args.batch is None else {})},
-                         {"pairings_per_gpu": n, "inputs": "r*G1 / s*G2 (Jacobian, z != 1) resident in HBM", "parallelism": f"dp{world} (sharded, no collective)",
-                          "number_system": "exact integer: 9 x 29-bit limbs in u32, v_mad_u64_u32 accumulation, Montgomery radix 2^261",
-                          "mapping": 1,
-                          # the lane-pair kernels are launched in rounds of 256 pairings per CU (two waves on every SIMD): the library
-                          # sizes its sub-launches from the CU count of the device it finds (bn_round_pairs in csrc/bn254_hip.hip)
-                          "cus": cus, "pairings_per_launch": n if n <= 256 * cus else f"equal parts of at most {256 * cus}",
-                          "process_group": (dist.get_backend() if dist.is_initialized() else None)})
+            line.update({"roofline": rf, **({"expected_scaling": expected_scaling("pairing", world, scaling_inputs())} if world > 1 and args.batch is None else {})})
             if world == 1 and args.batch is None:
                 Pn = P.cpu().numpy().view(np.uint64); Qn = Q.cpu().numpy().view(np.uint64)
                 if not args.no_side:
@@ -825,6 +862,7 @@ def main():
                     line["host_api"] = host_api_rate(gpu_index, Pn, Qn)
                 if not args.no_cpu_baseline:
                     line["cpu_baseline"] = cpu_baseline(Pn[:4096], Qn[:4096])
+        if rank == 0:
             print(json.dumps(line), flush=True)
     finally:
         if dist.is_initialized():

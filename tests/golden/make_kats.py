@@ -12,7 +12,8 @@ Sources (reference file:line):
   test_miller_loop      src/groups/mod.rs:522-547
   test_prepared_g2      src/groups/mod.rs:637-762
   test_reduced_pairing  src/groups/mod.rs:773-796
-Only the numbers are kept (no source text).
+Only the numbers are kept (no source text).  Beside them, reference_api.json records names only: the public traits of
+src/lib.rs, the types that implement each, and the inherent `pub fn`s of every type (what the Rust binding's wrappers call).
 """
 import json, re, sys, pathlib
 
@@ -70,6 +71,21 @@ def main():
     dst.write_text(json.dumps(out, indent=1) + "\n")
     print("wrote", dst, dst.stat().st_size, "bytes")
     write_consts()
+    write_api()
+
+
+def write_api():
+    lib = (REF / "lib.rs").read_text()
+    traits = sorted(set(re.findall(r"^pub trait (\w+)", lib, re.M)))
+    impls = re.findall(r"^impl (\w+) for (\w+) \{", lib, re.M)
+    inherent = {}
+    for m in re.finditer(r"^impl (\w+) \{$(.*?)^\}$", lib, re.M | re.S):
+        inherent.setdefault(m.group(1), []).extend(re.findall(r"^    pub fn (\w+)", m.group(2), re.M))
+    api = {"source": "src/lib.rs", "trait_impls": {t: sorted(ty for tr, ty in impls if tr == t) for t in traits},
+           "inherent_fns": {k: sorted(v) for k, v in sorted(inherent.items())}}
+    dst = pathlib.Path(__file__).with_name("reference_api.json")
+    dst.write_text(json.dumps(api, indent=1) + "\n")
+    print("wrote", dst, dst.stat().st_size, "bytes")
 
 
 def limb_arrays(body):

@@ -755,13 +755,40 @@ def test_bench_multi_rank_control_flow(tmp_path):
     env = dict(os.environ, BN254_BENCH_SHARE_GPU="1", BN254_BENCH_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8192"],
+    out = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8192", "--full"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["roofline"]["peak"] > 0 and "frac" in d["roofline"]
+
+
+def test_bench_plain_run_dumps_the_last_step(oracle, tmp_path):
+    """a plain `bench.py` run (no --full) times exactly --steps steps, prints the headline fields and nothing measured after them, and
+    --dump-outputs writes the Gt values of the last step: decoded from the 32-bit halves they equal the oracle's pairings of the
+    synthetic inputs (bn_amd.distributed.synthetic_points, indices [0, n))"""
+    import json, os, pathlib, subprocess, sys
+    from bn_amd import distributed as D
+    root = pathlib.Path(__file__).resolve().parents[1]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "BN254_BENCH_FORCE_DIST")}
+    n = 4096
+    out = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(n),
+                          "--dump-outputs", str(tmp_path / "dump")], env=env, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and abs(d["value"] - n * 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
+    assert d["higher_is_better"] is True and d["unit"] == "pairings/s" and d["dtype"] == "u32"
+    assert not {"roofline", "side", "host_api", "cpu_baseline", "expected_scaling"} & set(d)
+    got = np.load(tmp_path / "dump" / "pairing.npy")
+    assert got.dtype == np.float64 and got.shape == (n, 48, 2)
+    assert np.array_equal(np.load(tmp_path / "dump" / "pairing_rows.npy"), np.arange(n, dtype=np.float64))
+    gt = got[..., 0].astype(np.uint64) | (got[..., 1].astype(np.uint64) << np.uint64(32))
+    P = oracle.g1_mul_batch_jacobian(np.tile(oracle.g1_one(), (n, 1)), D.synthetic_scalars(0, n, 0))
+    Q = oracle.g2_mul_batch_jacobian(np.tile(oracle.g2_one(), (n, 1)), D.synthetic_scalars(0, n, 1))
+    assert np.array_equal(gt, oracle.pairing_batch(P, Q))
 
 
 @pytest.mark.parametrize("workload", ["pairing", "product"])

@@ -235,6 +235,33 @@ def test_bench_relaunches_itself_for_multi_gpu():
     assert out.stderr.count("bench.py needs an MI355X") >= 2 or "local_rank: 1" in out.stderr, out.stderr[-1500:]
 
 
+def test_bench_dump_outputs_is_exact_and_bounded(tmp_path):
+    """bench.py --dump-outputs: u64 words written as float64 32-bit halves decode exactly; an output above the byte budget becomes a fixed
+    seeded sample of rows (the same rows on every run) whose indices are written beside it; the options it needs are checked up front"""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    rng = np.random.default_rng(7)
+    a = rng.integers(0, 2**63, size=(300, 48), dtype=np.int64).view(np.uint64) * np.uint64(2) + np.uint64(1)
+    a[0] = np.uint64(2**64 - 1)
+    bench.dump_outputs(tmp_path / "all", {"pairing": a})
+    got = np.load(tmp_path / "all" / "pairing.npy")
+    assert got.dtype == np.float64 and got.shape == (300, 48, 2)
+    assert np.array_equal(got[..., 0].astype(np.uint64) | (got[..., 1].astype(np.uint64) << np.uint64(32)), a)
+    assert np.array_equal(np.load(tmp_path / "all" / "pairing_rows.npy"), np.arange(300))
+    budget = 100 * (48 * 16 + 8) + 1024
+    for d in ("s1", "s2"):
+        bench.dump_outputs(tmp_path / d, {"pairing": a}, budget=budget)
+    rows = np.load(tmp_path / "s1" / "pairing_rows.npy")
+    assert len(rows) == 100 and np.all(np.diff(rows) > 0) and np.array_equal(rows, np.load(tmp_path / "s2" / "pairing_rows.npy"))
+    s = np.load(tmp_path / "s1" / "pairing.npy")
+    assert np.array_equal(s[..., 0].astype(np.uint64) | (s[..., 1].astype(np.uint64) << np.uint64(32)), a[rows.astype(np.int64)])
+    assert sum(f.stat().st_size for f in (tmp_path / "s1").iterdir()) <= budget
+    assert bench.DUMP_BUDGET <= 64 * 2**20 and 2**16 * (48 * 16 + 8) + 1024 <= bench.DUMP_BUDGET        # the default 2^16 batch is written whole
+    for bad in (["--workload", "g1mul", "--dump-outputs", str(tmp_path)], ["--mode", "multi_c", "--dump-outputs", str(tmp_path)], ["--steps", "0"]):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py")] + bad, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and "error:" in r.stderr, (bad, r.stderr[-500:])
+
+
 def test_scaling_prediction_is_made_of_measurements_only():
     """bench.py's expected_scaling: every number in the prediction comes from a one-GPU bench line (this run's, or the newest
     committed profiles/r*_bench_line.json that carries the four configs[3] shard sizes) - no literals: scaling the inputs scales the outputs, the

@@ -1,6 +1,6 @@
 #!/bin/bash
 # kernel experiments: build_variants/lib_<name>.so from the working tree with extra hipcc flags, then
-#   BN254_LIB_PATH=build_variants/lib_<name>.so python bench.py --no-cpu-baseline --no-host-api
+#   BN254_LIB_PATH=build_variants/lib_<name>.so python bench.py --full --no-cpu-baseline --no-host-api
 # Only the units named in UNITS are recompiled with the flags (default: the lane-pair kernel file, where most experiments are);
 # the other objects come from the last regular build (bn_amd/csrc/build/).
 # usage: [UNITS="bn254_kernels_b bn254_kernels_mul"] tools/build_variant.sh NAME [extra hipcc flags...]

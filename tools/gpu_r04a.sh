@@ -10,7 +10,7 @@ for s in $steps; do
   case $s in
     dfma) timeout 300 build_variants/dfma_experiment > $out/${tag}_dfma.txt 2>&1; echo "dfma rc=$?" | tee -a $out/${tag}_summary.txt; cat $out/${tag}_dfma.txt | tee -a $out/${tag}_summary.txt ;;
     tests) timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "scalar_mul or group_addition or config5 or golden_fixtures or full_size_bilinearity or gt_pow_modes" > $out/${tag}_tests.log 2>&1; echo "tests rc=$?" | tee -a $out/${tag}_summary.txt; tail -3 $out/${tag}_tests.log | tee -a $out/${tag}_summary.txt ;;
-    bench) timeout 600 python bench.py --steps 20 --warmup 3 > $out/${tag}_bench.json 2> $out/${tag}_bench.err; echo "bench rc=$?" | tee -a $out/${tag}_summary.txt; python tools/brief_line.py < $out/${tag}_bench.json | tee -a $out/${tag}_summary.txt ;;
+    bench) timeout 600 python bench.py --full --steps 20 --warmup 3 > $out/${tag}_bench.json 2> $out/${tag}_bench.err; echo "bench rc=$?" | tee -a $out/${tag}_summary.txt; python tools/brief_line.py < $out/${tag}_bench.json | tee -a $out/${tag}_summary.txt ;;
     ab) for r in 1 2; do for lib in main alias; do
           for w in pairing g1mul g2mul gtpow product; do
             extra="--no-cpu-baseline --no-host-api --no-side"

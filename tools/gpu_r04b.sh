@@ -12,16 +12,16 @@ for s in $steps; do
     tests) timeout 2400 python -m pytest tests -m gpu -x -q > $out/${tag}_tests.log 2>&1; echo "tests rc=$?" | tee -a $out/${tag}_summary.txt; tail -15 $out/${tag}_tests.log | tee -a $out/${tag}_summary.txt ;;
     latency) timeout 900 python tools/wave_latency.py > $out/${tag}_latency.json 2> $out/${tag}_latency.err; echo "latency rc=$?" | tee -a $out/${tag}_summary.txt; python -c "
 import json; d=json.load(open('$out/${tag}_latency.json')); print(json.dumps(d['pairing_batch_ms_mid_size'], indent=0))" | tee -a $out/${tag}_summary.txt; tail -3 $out/${tag}_latency.err ;;
-    bench) timeout 900 python bench.py --steps 20 --warmup 3 > $out/${tag}_bench.json 2> $out/${tag}_bench.err; echo "bench rc=$?" | tee -a $out/${tag}_summary.txt; python tools/brief_line.py < $out/${tag}_bench.json | tee -a $out/${tag}_summary.txt
-           timeout 300 python bench.py --batch 8192 --steps 20 --warmup 3 --no-cpu-baseline --no-host-api --no-side > $out/${tag}_bench_8192.json 2>> $out/${tag}_bench.err; python tools/brief_line.py < $out/${tag}_bench_8192.json | tee -a $out/${tag}_summary.txt
+    bench) timeout 900 python bench.py --full --steps 20 --warmup 3 > $out/${tag}_bench.json 2> $out/${tag}_bench.err; echo "bench rc=$?" | tee -a $out/${tag}_summary.txt; python tools/brief_line.py < $out/${tag}_bench.json | tee -a $out/${tag}_summary.txt
+           timeout 300 python bench.py --full --batch 8192 --steps 20 --warmup 3 --no-cpu-baseline --no-host-api --no-side > $out/${tag}_bench_8192.json 2>> $out/${tag}_bench.err; python tools/brief_line.py < $out/${tag}_bench_8192.json | tee -a $out/${tag}_summary.txt
            BN254_BENCH_SHARE_GPU=1 timeout 600 python bench.py --mode multi_c --gpus 2 --steps 3 --warmup 1 > $out/${tag}_bench_multi_c.json 2>> $out/${tag}_bench.err; head -c 1500 $out/${tag}_bench_multi_c.json | tee -a $out/${tag}_summary.txt ;;
     ab) for r in 1 2; do for lib in main alias; do
           echo -n "$lib gtpow " >> $out/${tag}_ab.txt
           BN254_LIB_PATH=$repo/build_variants/lib_$lib.so timeout 300 python bench.py --workload gtpow --steps 10 --warmup 2 2>> $out/${tag}_ab.err | python tools/brief_line.py >> $out/${tag}_ab.txt
         done; done; sort $out/${tag}_ab.txt | tee -a $out/${tag}_summary.txt ;;
     prof) cd /tmp
-          timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats -- python $repo/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-host-api --no-side > $out/${tag}_stats.log 2>&1
-          timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_statsside -- python $repo/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-host-api > $out/${tag}_statsside.log 2>&1
+          timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats -- python $repo/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-host-api --no-side > $out/${tag}_stats.log 2>&1
+          timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_statsside -- python $repo/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-host-api > $out/${tag}_statsside.log 2>&1
           find $out/${tag}_stats -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $out/${tag}_kernel_stats.csv
           find $out/${tag}_statsside -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $out/${tag}_with_side_kernel_stats.csv
           for c in FETCH_SIZE WRITE_SIZE; do

@@ -16,6 +16,6 @@ for l in sys.stdin:
         d=json.loads(l); print('value %.5g ms/step %.4f kernels %s' % (d['value'], d['ms_per_step'], {k: round(v,4) for k,v in d['kernel_ms_per_step'].items()})); break
 else: print('no line')" >> $out/${tag}_ab.txt
         done; done; sort $out/${tag}_ab.txt | tee -a $out/${tag}_summary.txt ;;
-    mid) for n in 8192 16384; do timeout 300 python bench.py --batch $n --steps 20 --warmup 3 --no-cpu-baseline --no-host-api --no-side 2>> $out/${tag}_mid.err | python tools/brief_line.py | tee -a $out/${tag}_summary.txt; done ;;
+    mid) for n in 8192 16384; do timeout 300 python bench.py --full --batch $n --steps 20 --warmup 3 --no-cpu-baseline --no-host-api --no-side 2>> $out/${tag}_mid.err | python tools/brief_line.py | tee -a $out/${tag}_summary.txt; done ;;
   esac
 done

@@ -6,7 +6,7 @@ log=$out/r05_power_probe.txt; : > $log
 sample() { for i in $(seq $2); do echo "== $1 sample $i" >> $log; rocm-smi --showpower --showclocks --showmaxpower --showtemp 2>/dev/null | grep -E "Power|sclk|Temperature \(Sensor (edge|junction)" >> $log; sleep 0.3; done; }
 echo "---- idle" >> $log; sample idle 2
 echo "---- bench.py: 2^16 pairings per step, 1500 steps (Miller + final exponentiation back to back)" >> $log
-python bench.py --steps 1500 --warmup 3 --no-cpu-baseline --no-host-api --no-side > $out/r05_power_bench.json 2>/dev/null &
+python bench.py --full --steps 1500 --warmup 3 --no-cpu-baseline --no-host-api --no-side > $out/r05_power_bench.json 2>/dev/null &
 pid=$!; sleep 6; sample pairing 8; wait $pid
 python tools/brief_line.py < $out/r05_power_bench.json >> $log
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -Ibn_amd/csrc tools/ubench_mix.hip -o /tmp/ubench_mix 2>/dev/null
