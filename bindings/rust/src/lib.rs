@@ -57,6 +57,9 @@ extern "C" {
     fn bn254_pairing_product_prepared_native_multi(m: *mut c_void, p: *const G1, prep: *const c_void, n: usize, out: *mut Gt) -> c_int;
     fn bn254_pairing_batch_multi(m: *mut c_void, p: *const G1, q: *const G2, out: *mut Gt, n: usize) -> c_int;
     fn bn254_pairing_product_multi(m: *mut c_void, p: *const G1, q: *const G2, n: usize, out: *mut Gt) -> c_int;
+    fn bn254_pairing_product_batch(ctx: *mut c_void, p: *const G1, q: *const G2, offsets: *const usize, m: usize, out: *mut Gt) -> c_int;
+    fn bn254_pairing_product_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_q: *const c_void, offsets: *const usize, m: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn bn254_pairing_product_batch_multi(mh: *mut c_void, p: *const G1, q: *const G2, offsets: *const usize, m: usize, out: *mut Gt) -> c_int;
 }
 
 /// One line-function coefficient of a prepared G2 point: the crate's `EllCoeffs { ell_0, ell_vw, ell_vv: Fq2 }` (src/groups/mod.rs:472-476) as the
@@ -123,6 +126,21 @@ pub fn pairing_product(p: &[G1], q: &[G2]) -> Result<Gt, GpuError> {
     let mut out = Gt::one();
     check(unsafe { bn254_pairing_product(std::ptr::null_mut(), p.as_ptr(), q.as_ptr(), p.len(), &mut out) })?;
     Ok(out)
+}
+
+/// `out[j]` = that fold over the pairs `offsets[j]..offsets[j+1]` (CSR segments, `offsets.len()` = m + 1): many independent
+/// multi-pairings in one call, ONE final exponentiation per segment; an empty segment gives `Gt::one()`
+pub fn pairing_product_batch(p: &[G1], q: &[G2], offsets: &[usize]) -> Result<Vec<Gt>, GpuError> {
+    assert_eq!(p.len(), q.len());
+    assert!(!offsets.is_empty() && offsets[offsets.len() - 1] == p.len());
+    let mut out = vec![Gt::one(); offsets.len() - 1];
+    check(unsafe { bn254_pairing_product_batch(std::ptr::null_mut(), p.as_ptr(), q.as_ptr(), offsets.as_ptr(), out.len(), out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// `ok[j]` = (product of segment j == `Gt::one()`): a block of Groth16 / EIP-197-style pairing checks
+pub fn pairing_check_batch(p: &[G1], q: &[G2], offsets: &[usize]) -> Result<Vec<bool>, GpuError> {
+    Ok(pairing_product_batch(p, q, offsets)?.into_iter().map(|g| g == Gt::one()).collect())
 }
 
 /// `out[i] = p[i] * k[i]`, returned normalized (src/lib.rs:88-95): equal to the crate's result under its projective `==`
@@ -376,6 +394,14 @@ impl MultiGpu {
         assert_eq!(p.len(), q.len());
         let mut out = Gt::one();
         check(unsafe { bn254_pairing_product_multi(self.0, p.as_ptr(), q.as_ptr(), p.len(), &mut out) })?;
+        Ok(out)
+    }
+    /// `pairing_product_batch` with the segments sharded over the GPUs (segment j on the GPU whose pair shard holds offsets[j]; no exchange)
+    pub fn pairing_product_batch(&self, p: &[G1], q: &[G2], offsets: &[usize]) -> Result<Vec<Gt>, GpuError> {
+        assert_eq!(p.len(), q.len());
+        assert!(!offsets.is_empty() && offsets[offsets.len() - 1] == p.len());
+        let mut out = vec![Gt::one(); offsets.len() - 1];
+        check(unsafe { bn254_pairing_product_batch_multi(self.0, p.as_ptr(), q.as_ptr(), offsets.as_ptr(), out.len(), out.as_mut_ptr()) })?;
         Ok(out)
     }
 }

@@ -180,6 +180,37 @@ def pairing_product(ps, qs, engine=None):
     return Gt(e.pairing_product(P, Q))
 
 
+def _segment_arrays(segments, qs, offsets):
+    if offsets is not None:                   # (n,12) / (n,24) arrays + CSR offsets
+        return np.asarray(segments, np.uint64).reshape(-1, G1_WORDS), np.asarray(qs, np.uint64).reshape(-1, G2_WORDS), np.asarray(offsets, np.uint64)
+    if qs is not None:
+        raise ValueError("qs is only taken together with offsets")
+    segments = [list(s) for s in segments]
+    offs = np.zeros(len(segments) + 1, np.uint64)
+    offs[1:] = np.cumsum([len(s) for s in segments], dtype=np.uint64) if segments else []
+    pairs = [pq for s in segments for pq in s]
+    P = np.stack([p.limbs for p, _ in pairs]) if pairs else np.zeros((0, G1_WORDS), np.uint64)
+    Q = np.stack([q.limbs for _, q in pairs]) if pairs else np.zeros((0, G2_WORDS), np.uint64)
+    return P, Q, offs
+
+
+def _product_batch_limbs(segments, qs, offsets, engine):
+    P, Q, offs = _segment_arrays(segments, qs, offsets)
+    return (engine or default_engine()).pairing_product_batch(P, Q, offs)
+
+
+def pairing_product_batch(segments, qs=None, offsets=None, engine=None):
+    """[fold(Gt::one(), acc * pairing(p, q)) over the pairs of each segment] (shootout/main.rs:11-16 per segment) with ONE final
+    exponentiation per segment.  segments: a sequence of sequences of (G1, G2) - an empty one gives Gt::one() -, or (n,12) / (n,24) uint64
+    arrays as `segments` / `qs` plus CSR `offsets` (m + 1 entries)."""
+    return [Gt(r) for r in _product_batch_limbs(segments, qs, offsets, engine)]
+
+
+def pairing_check_batch(segments, qs=None, offsets=None, engine=None):
+    """numpy bool array: product of segment j == Gt::one(), compared as canonical limbs - the predicate of a Groth16 / EIP-197-style check"""
+    return (_product_batch_limbs(segments, qs, offsets, engine) == Gt.one().limbs).all(axis=1)
+
+
 class PreparedG2:
     """G2 points prepared once for many pairings (the crate's internal G2Precomp, groups/mod.rs:472-483,557-588, as a device-resident
     native table: Engine.g2_prepare).  One point: shared by every P; several: point i is paired with ps[i]."""

@@ -6,6 +6,7 @@
 // call) and the wire-format kernels (one record per lane).  The pairing and scalar-multiplication kernels live in bn254_kernels_{b,q,w,mul}.hip.
 // (The one-lane-per-pairing kernels of rounds 1-4 - "mapping A", a test double - moved to tests/testdouble/ in round 5.)
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -144,6 +145,7 @@ int bn_get_ctx(bn254_ctx *&ctx) {
 // The ONLY place this library reads its debug environment (BN254_RCCL_PATH, a file path, is read where RCCL is loaded): once per
 // process, into the seed values every new context starts from.
 constexpr size_t BN_LAUNCH_MAX = (size_t)1 << 22;       // units per launch (32-bit word offsets inside a kernel); also the cap of the size options
+constexpr size_t BN_N_MAX = (size_t)1 << 40;            // sanity bound on a batch; launches are cut to size internally
 namespace {
 bool bn_opt_valid(int key, long v);
 struct DebugEnv { long opt[BN254_OPT_COUNT_]; int exchange; bool affinity; };
@@ -360,6 +362,130 @@ int bn_mul_dev(bn254_ctx *ctx, int g, const void *d_p, const void *d_k, void *d_
     });
 }
 
+// ---- batched multi-pairing: m independent products over CSR segments (bn254_pairing_product_batch*)
+// The pairs are cut into chunks of at most one machine round (bn_round_pairs), at the last segment boundary inside the round when there
+// is one; a segment longer than that carries its partial product into the next chunk (value slot 0, in front of the chunk's Miller values).
+// Per chunk: the Miller values (bn_launch_miller, NAF: they only meet a final exponentiation), then the levels of the segmented fold -
+// every lane pair multiplies one piece of at most BN_SEG_FOLD consecutive values (bn254_gt_mul_B<true>); a segment with more values is
+// cut into pieces whose partial products the next level folds, so no lane pair runs a chain longer than BN_SEG_FOLD - 1 products and a
+// segment of L values takes ceil(log_BN_SEG_FOLD L) levels.  The host builds every level's work list up front.
+// Small route: one chunk whose Miller values come from the one-per-wave kernel and at most BN254_OPT_WAVE_FE_MAX segments - the last
+// piece of every segment (at most BN_TAIL_SEG_MAX values; longer segments are first folded down to that) is multiplied AND exponentiated by
+// one wave (bn254_gt_tail_W<true>): a verifier's handful of 4-pair checks is two launches.  Otherwise the last fold level writes every
+// segment's un-exponentiated product to out[j] and bn_launch_final_exp exponentiates the m values in place.
+constexpr size_t BN_SEG_FOLD = 16;          // values per lane-pair piece of the fold: at most 15 products in a row (~20-30 us each)
+constexpr size_t BN_TAIL_SEG_MAX = 16;      // values per wave in the ragged tail: at most 15 wave products (~2.7 us each) before the exponentiation
+int bn_seg_check(const void *p, const void *q, const size_t *offsets, size_t m, const void *out) {
+    if (!offsets || offsets[0] != 0) return BN254_E_BAD_ARG;
+    for (size_t j = 0; j < m; ++j)
+        if (offsets[j + 1] < offsets[j]) return BN254_E_BAD_ARG;
+    const size_t n = offsets[m];
+    return (n > BN_N_MAX || !out || (n && (!p || !q))) ? BN254_E_BAD_ARG : BN254_OK;
+}
+namespace {
+struct SegLaunch { bool tail; size_t first, count; };                                  // a range of the work list: one fold level or the tail
+struct SegChunk { size_t lo, hi; bool carry_out; std::vector<SegLaunch> launches; };   // pairs [lo, hi) and what follows their Miller values
+// partial products ALL fold levels of one chunk write, at most: a segment of L > BN_SEG_FOLD values gives ceil(L / BN_SEG_FOLD) < 2 L / BN_SEG_FOLD
+// partials, so level 0 writes fewer than 2 (chunk_pairs + 1) / BN_SEG_FOLD and every further level fewer than 1/8 of the level before.
+// Every partial of a chunk has a slot of its own (no level reuses another level's slots): a piece may read its inputs several levels
+// after they were written - the ragged tail of the small route reads them only after the deepest level of the plan.
+size_t seg_partials_max(size_t chunk_pairs) { return 4 * (chunk_pairs + 1) / BN_SEG_FOLD + 4; }
+// workspace (in Fq12 values): [carry in][chunk_pairs Miller values][partials of every level][carry out]
+size_t seg_ws_values(size_t chunk_pairs) { return chunk_pairs + 2 + seg_partials_max(chunk_pairs); }
+// false if the partials would not fit their region (cannot happen by the bound above; checked, never written out of bounds)
+bool seg_plan(const size_t *off, size_t m, size_t chunk_pairs, bool small, char *ws, char *d_out, std::vector<BnSegPiece> &pieces, std::vector<SegChunk> &chunks) {
+    const size_t n = off[m], V = sizeof(bn_gt), pb = seg_partials_max(chunk_pairs), last_cap = small ? BN_TAIL_SEG_MAX : BN_SEG_FOLD;
+    char *const part = ws + (chunk_pairs + 1) * V, *const carry_out = ws + (chunk_pairs + 1 + pb) * V;
+    size_t lo = 0, j = 0;
+    bool carry = false;
+    do {
+        size_t hi = std::min(n, lo + chunk_pairs);
+        if (hi < n) {
+            const size_t b = *(std::upper_bound(off, off + m + 1, hi) - 1);          // last segment boundary <= hi
+            if (b > lo) hi = b;
+        }
+        // segments that start in front of hi (the last chunk also takes the empty segments at n)
+        const size_t jend = hi == n ? m : (size_t)(std::lower_bound(off + j, off + m, hi) - off);
+        std::vector<std::vector<BnSegPiece>> lv(1);
+        size_t used = 0;                                                     // partial slots taken in this chunk
+        std::vector<BnSegPiece> tail;
+        SegChunk ch{lo, hi, false, {}};
+        for (size_t jj = j; jj < jend; ++jj) {
+            const bool from_carry = carry && jj == j, to_carry = off[jj + 1] > hi;
+            const size_t a = from_carry ? 0 : off[jj] - lo + 1, b = std::min(off[jj + 1], hi) - lo + 1;      // value slots [a, b)
+            const char *src = ws + a * V;
+            size_t L = b - a, level = 0;
+            while (L > last_cap) {
+                if (lv.size() <= level) lv.emplace_back();
+                char *base = part + used * V;
+                const size_t k = (L + BN_SEG_FOLD - 1) / BN_SEG_FOLD;
+                if (used + k > pb) return false;
+                for (size_t i = 0; i < k; ++i)
+                    lv[level].push_back({(const uint32_t *)(src + i * BN_SEG_FOLD * V), (uint32_t *)(base + i * V), (uint32_t)std::min(BN_SEG_FOLD, L - i * BN_SEG_FOLD), 0u});
+                used += k; src = base; L = k; ++level;
+            }
+            const BnSegPiece last = {(const uint32_t *)src, (uint32_t *)(to_carry ? carry_out : d_out + jj * V), (uint32_t)L, 0u};
+            if (small) tail.push_back(last);
+            else { if (lv.size() <= level) lv.resize(level + 1); lv[level].push_back(last); }
+            ch.carry_out |= to_carry;
+        }
+        for (const auto &l : lv)
+            if (!l.empty()) { ch.launches.push_back({false, pieces.size(), l.size()}); pieces.insert(pieces.end(), l.begin(), l.end()); }
+        if (!tail.empty()) { ch.launches.push_back({true, pieces.size(), tail.size()}); pieces.insert(pieces.end(), tail.begin(), tail.end()); }
+        carry = ch.carry_out;
+        j = carry ? jend - 1 : jend;
+        lo = hi;
+        chunks.push_back(std::move(ch));
+    } while (lo < n);
+    return true;
+}
+}  // namespace
+// out[j] = final_exponentiation(prod of the Miller values of pairs [off[j], off[j+1])) for j < m; off is HOST memory; scratch guard held by the caller
+static int bn_launch_product_batch(bn254_ctx *c, const void *d_p, const void *d_q, const size_t *off, size_t m, void *d_out, hipStream_t s) {
+    const size_t n = off[m];
+    bool ones = n == m;
+    for (size_t j = 0; ones && j < m; ++j) ones = off[j] == j;
+    if (ones) return bn_launch_pairing(c, d_p, d_q, d_out, n, s, nullptr);           // every segment one pair: bn254_pairing_batch's kernels
+    const size_t chunk_pairs = bn_round_pairs(c);
+    const bool small = n <= chunk_pairs && n <= bn_wave_pairing_max(c) && m <= bn_wave_fe_max(c);
+    int rc = c->ws.reserve(seg_ws_values(chunk_pairs) * sizeof(bn_gt)); if (rc) return rc;
+    std::vector<BnSegPiece> pieces;
+    std::vector<SegChunk> chunks;
+    if (!seg_plan(off, m, chunk_pairs, small, (char *)c->ws.p, (char *)d_out, pieces, chunks)) return BN254_E_INTERNAL;
+    // the work lists: ONE copy per call through the context's pinned staging, which is rewritten only after its previous copy completed
+    // (so the caller's `offsets` may be freed as soon as this returns)
+    const size_t bytes = pieces.size() * sizeof(BnSegPiece);
+    if (c->seg_plan_ev) HIP_TRY(hipEventSynchronize(c->seg_plan_ev));
+    else HIP_TRY(hipEventCreateWithFlags(&c->seg_plan_ev, hipEventDisableTiming));
+    if ((rc = c->seg_plan_host.reserve(bytes)) || (rc = c->seg_plan.reserve(bytes))) return rc;
+    memcpy(c->seg_plan_host.p, pieces.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(c->seg_plan.p, c->seg_plan_host.p, bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(c->seg_plan_ev, s));
+    const BnSegPiece *list = (const BnSegPiece *)c->seg_plan.p;
+    const size_t pb = seg_partials_max(chunk_pairs);
+    for (const SegChunk &ch : chunks) {
+        if (ch.hi > ch.lo) {
+            rc = bn_launch_miller(c, (const char *)d_p + ch.lo * sizeof(bn_g1), (const char *)d_q + ch.lo * sizeof(bn_g2), (char *)c->ws.p + sizeof(bn_gt), ch.hi - ch.lo, s, true);
+            if (rc) return rc;
+        }
+        for (const SegLaunch &l : ch.launches) {
+            if (l.tail) {
+                BnScope sc(c, s, "gt_tail_seg");
+                rc = bn254_launch_gt_tail_seg_W(list + l.first, l.count, s);
+            } else {
+                rc = bn_for_parts(l.count, BN_LAUNCH_MAX, [&](size_t lo, size_t cnt) -> int {
+                    BnScope sc(c, s, "gt_segment");
+                    return bn254_launch_gt_fold_seg_B(list + l.first + lo, cnt, s);
+                });
+            }
+            if (rc) return rc;
+        }
+        if (ch.carry_out)                 // the segment that goes on: its partial product becomes value slot 0 of the next chunk
+            HIP_TRY(hipMemcpyAsync(c->ws.p, (char *)c->ws.p + (chunk_pairs + 1 + pb) * sizeof(bn_gt), sizeof(bn_gt), hipMemcpyDeviceToDevice, s));
+    }
+    return small ? BN254_OK : bn_launch_final_exp(c, d_out, d_out, m, s, nullptr);
+}
+
 extern "C" {
 
 int bn254_device_count(void) {
@@ -394,6 +520,8 @@ void bn254_ctx_destroy(bn254_ctx *c) {
     hipDeviceSynchronize();
     for (auto &r : c->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     c->ws.release(); c->exp_tbl.release(); c->pow_tbl.release(); c->miller_state.release(); c->mul_tbl.release();
+    c->seg_plan.release(); c->seg_plan_host.release();
+    if (c->seg_plan_ev) hipEventDestroy(c->seg_plan_ev);
     for (auto &b : c->stage) b.release();
     for (auto &s : c->slot) {
         for (auto &b : s.d_in) b.release();
@@ -443,7 +571,6 @@ int bn254_ctx_get_option_raw(bn254_ctx *ctx, int key, long *value) {
 }
 
 // ---------------------------------------------------------------------------------------------- device-resident API
-constexpr size_t BN_N_MAX = (size_t)1 << 40;          // sanity bound on a batch; launches are cut to size internally
 #define BN_DEV_PROLOGUE(null_check, limit)                                           \
     int rc = bn_get_ctx(ctx); if (rc) return rc;                                     \
     if (n == 0) return BN254_OK;                                                     \
@@ -529,6 +656,16 @@ int bn254_miller_product_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, s
         }
     }
     return bn_launch_product(ctx, ctx->ws.p, nv, d_partial, (char *)ctx->ws.p + fbytes, s);
+}
+int bn254_pairing_product_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, const size_t *offsets, size_t m, void *d_out, void *stream) {
+    if (m == 0) return BN254_OK;
+    if (int e = bn_seg_check(d_p, d_q, offsets, m, d_out)) return e;          // before any device lookup
+    int rc = bn_get_ctx(ctx); if (rc) return rc;
+    BnDeviceGuard dev_guard;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    BnScratchGuard g(ctx, s); if (g.rc) return g.rc;
+    return bn_no_throw([&] { return bn_launch_product_batch(ctx, d_p, d_q, offsets, m, d_out, s); });
 }
 static int mul_dev(bn254_ctx *ctx, int g, const void *d_p, const void *d_k, void *d_out, size_t n, void *stream, int normalize) {
     BN_DEV_PROLOGUE(!d_p || !d_k || !d_out, BN_N_MAX);
@@ -721,6 +858,25 @@ int bn254_pairing_product(bn254_ctx *ctx, const bn_g1 *p, const bn_g2 *q, size_t
     rc = bn254_miller_product_dev(ctx, dp.p, dq.p, n, dpart.p, ctx->stream); if (rc) return rc;
     rc = bn254_final_exp_batch_dev(ctx, dpart.p, dpart.p, 1, ctx->stream); if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, dpart.p, sizeof(bn_gt), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return BN254_OK;
+}
+int bn254_pairing_product_batch(bn254_ctx *ctx, const bn_g1 *p, const bn_g2 *q, const size_t *offsets, size_t m, bn_gt *out) {
+    if (m == 0) return BN254_OK;
+    if (int e = bn_seg_check(p, q, offsets, m, out)) return e;                // before any device lookup
+    const size_t n = offsets[m];
+    bool ones = n == m;
+    for (size_t j = 0; ones && j < m; ++j) ones = offsets[j] == j;
+    if (ones) return bn254_pairing_batch(ctx, p, q, out, n);                 // every segment one pair: the pipelined batch path itself
+    BN_HOST_PROLOGUE();
+    BnBuf &dp = ctx->stage[0], &dq = ctx->stage[1], &dout = ctx->stage[2];
+    if ((rc = dp.reserve(n * sizeof(bn_g1))) || (rc = dq.reserve(n * sizeof(bn_g2))) || (rc = dout.reserve(m * sizeof(bn_gt)))) return rc;
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(dp.p, p, n * sizeof(bn_g1), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(dq.p, q, n * sizeof(bn_g2), hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = bn254_pairing_product_batch_dev(ctx, dp.p, dq.p, offsets, m, dout.p, ctx->stream); if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, dout.p, m * sizeof(bn_gt), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return BN254_OK;
 }

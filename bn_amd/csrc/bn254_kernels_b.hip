@@ -503,13 +503,26 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BN_W
 }
 
 // out[i] = a[i] * b[i]   (Gt * Gt, lib.rs:175-179 -> fq12.rs:295-307)
-__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BN_WAVES, BN_WAVES))) bn254_gt_mul_B(const uint32_t *a, const uint32_t *b, uint32_t *out, uint32_t n) {
+// SEG: one level of the segmented fold of bn254_pairing_product_batch - lane pair i multiplies the pieces[i].cnt consecutive values at
+// pieces[i].src (a serial chain of at most BN_SEG_FOLD values, chosen by the host) into pieces[i].dst; an empty piece writes one.
+// `a`, `b`, `out` unused.  (Both lanes of a pair share the piece, so the DPP exchanges of a product never meet a retired partner.)
+template <bool SEG>
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BN_WAVES, BN_WAVES))) bn254_gt_mul_B(const uint32_t *a, const uint32_t *b, uint32_t *out, uint32_t n, const BnSegPiece *pieces) {
     uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
     uint32_t pair = t >> 1;
     bool live = pair < n;
     if (!live) pair = n - 1;
-    Fq12<F2> r = f12_mul_o(f12_load<F2>(a + 96u * pair), f12_load<F2>(b + 96u * pair));
-    if (live) f12_store(r, out + 96u * pair);
+    if constexpr (SEG) {
+        const BnSegPiece pc = pieces[pair];
+        Fq12<F2> acc = f12_one<F2>();
+        if (pc.cnt) acc = f12_load<F2>(pc.src);
+#pragma unroll 1
+        for (uint32_t j = 1; j < pc.cnt; ++j) acc = f12_mul_o(acc, f12_load<F2>(pc.src + 96u * j));
+        if (live) f12_store(acc, pc.dst);
+    } else {
+        Fq12<F2> r = f12_mul_o(f12_load<F2>(a + 96u * pair), f12_load<F2>(b + 96u * pair));
+        if (live) f12_store(r, out + 96u * pair);
+    }
 }
 // out[i] = a[i] ^ k[i]   (Gt::pow, lib.rs:171 -> fields/mod.rs:35-46: 256 x { res = res^2; if bit { res = a * res } } on the scalar
 // taken out of Montgomery form).  The power is a unique field element, so any addition chain returns the reference's bytes:
@@ -666,7 +679,14 @@ int bn254_launch_miller_native_shared_B(const void *p, const void *table, const 
 }
 int bn254_launch_gt_mul_B(const void *a, const void *b, void *out, size_t n, hipStream_t s) {
     unsigned grid = (unsigned)((2 * n + BLOCK - 1) / BLOCK);
-    hipLaunchKernelGGL(bn254_gt_mul_B, dim3(grid), dim3(BLOCK), 0, s, (const uint32_t *)a, (const uint32_t *)b, (uint32_t *)out, (uint32_t)n);
+    hipLaunchKernelGGL(bn254_gt_mul_B<false>, dim3(grid), dim3(BLOCK), 0, s, (const uint32_t *)a, (const uint32_t *)b, (uint32_t *)out, (uint32_t)n, (const BnSegPiece *)nullptr);
+    return (int)hipGetLastError();
+}
+// one level of the segmented fold: `count` pieces (device memory), one per lane pair
+int bn254_launch_gt_fold_seg_B(const void *pieces, size_t count, hipStream_t s) {
+    unsigned grid = (unsigned)((2 * count + BLOCK - 1) / BLOCK);
+    hipLaunchKernelGGL(bn254_gt_mul_B<true>, dim3(grid), dim3(BLOCK), 0, s, (const uint32_t *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t)count,
+                       (const BnSegPiece *)pieces);
     return (int)hipGetLastError();
 }
 size_t bn254_gt_pow_table_bytes_B(size_t n) {

@@ -90,11 +90,26 @@ __global__ void __launch_bounds__(64) bn254_pairing_W(const uint32_t *g1, const 
 }
 
 // out[b] = in[b*m] * in[b*m + 1] * ... * in[b*m + m-1], then optionally its final exponentiation: the tail of a multi-pairing
-// (the per-GPU partial products of bn254_pairing_product_multi, or the survivors of the product tree), one workgroup per group
-__global__ void __launch_bounds__(64) bn254_gt_tail_W(const uint32_t *in, uint32_t m, uint32_t *out, int final_exp) {
+// (the per-GPU partial products of bn254_pairing_product_multi, or the survivors of the product tree), one workgroup per group.
+// SEG: the ragged form of bn254_pairing_product_batch's small route - workgroup b folds and exponentiates piece b of `pieces`
+// (pieces[b].cnt <= BN_TAIL_SEG_MAX values, chosen by the host) into pieces[b].dst; an empty piece gives one; `in`, `m`, `out` unused.
+template <bool SEG>
+__global__ void __launch_bounds__(64) bn254_gt_tail_W(const uint32_t *in, uint32_t m, uint32_t *out, int final_exp, const BnSegPiece *pieces) {
     __shared__ WaveLds lds;
     WaveDev w = wave_init(lds);
     const uint32_t *src = in + 96u * m * blockIdx.x;
+    uint32_t *dst = out + 96u * blockIdx.x;
+    if constexpr (SEG) {
+        const BnSegPiece pc = pieces[blockIdx.x];
+        src = pc.src; m = pc.cnt; dst = pc.dst;
+        if (m == 0) {                                   // empty segment: Gt::one() (its exponentiation is one)
+            w.sync();
+            w_set_one(w);
+            w.sync();
+            w_store_f12(w, OFF_RES, dst);
+            return;
+        }
+    }
     w_load_f12(w, src, OFF_RES);
     w.sync();
 #pragma unroll 1
@@ -104,7 +119,7 @@ __global__ void __launch_bounds__(64) bn254_gt_tail_W(const uint32_t *in, uint32
         w_run(w, PROG_MUL);
     }
     if (final_exp) w_run(w, PROG_FE);
-    w_store_f12(w, OFF_RES, out + 96u * blockIdx.x);
+    w_store_f12(w, OFF_RES, dst);
 }
 
 // measurement: `iters` runs of one program on one wave (which: 0 cyclotomic squaring = 2 phases, 1 product = 3 phases, 2 slot copy =
@@ -265,7 +280,12 @@ int bn254_launch_pairing_W(const void *p, const void *q, void *out, size_t n, in
     return (int)hipGetLastError();
 }
 int bn254_launch_gt_tail_W(const void *in, size_t groups, unsigned m, void *out, int final_exp, hipStream_t s) {
-    hipLaunchKernelGGL(bn254_gt_tail_W, dim3((unsigned)groups), dim3(64), 0, s, (const uint32_t *)in, m, (uint32_t *)out, final_exp);
+    hipLaunchKernelGGL(bn254_gt_tail_W<false>, dim3((unsigned)groups), dim3(64), 0, s, (const uint32_t *)in, m, (uint32_t *)out, final_exp, (const BnSegPiece *)nullptr);
+    return (int)hipGetLastError();
+}
+// final_exponentiation(fold) of every piece of `pieces` (device memory, `count` entries, each at most BN_TAIL_SEG_MAX values) into its dst
+int bn254_launch_gt_tail_seg_W(const void *pieces, size_t count, hipStream_t s) {
+    hipLaunchKernelGGL(bn254_gt_tail_W<true>, dim3((unsigned)count), dim3(64), 0, s, (const uint32_t *)nullptr, 0u, (uint32_t *)nullptr, 1, (const BnSegPiece *)pieces);
     return (int)hipGetLastError();
 }
 }

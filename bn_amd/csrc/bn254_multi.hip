@@ -490,4 +490,34 @@ int bn254_pairing_product_prepared_native_multi(bn254_multi *m, const bn_g1 *p, 
     return bn_no_throw([&] { return product_multi_impl(m, p, nullptr, prep, n, out); });
 }
 
+// segment j runs on the rank whose pair shard [n*g/G, n*(g+1)/G) holds offsets[j] (offsets[j] == n: the last rank), with all of its pairs -
+// so every rank owns a contiguous run of segments and of pairs; no exchange
+static int product_batch_multi(bn254_multi *mh, const bn_g1 *p, const bn_g2 *q, const size_t *offsets, size_t m, bn_gt *out) {
+    if (m == 0) return BN254_OK;
+    if (int e = bn_seg_check(p, q, offsets, m, out)) return e;            // the segment checks first, as on one device
+    if (!mh) return BN254_E_BAD_ARG;
+    std::lock_guard<std::mutex> lk(mh->mu);
+    const size_t G = mh->ctx.size(), n = offsets[m];
+    std::vector<int> rcs(G, BN254_OK);
+    const std::thread::id caller = std::this_thread::get_id();
+    run_workers((int)G, [&](int g) {
+        BnAffinityScope pin(mh->cpus[(size_t)g], caller);
+        rcs[g] = bn_no_throw([&]() -> int {
+            const size_t j_lo = (size_t)(std::lower_bound(offsets, offsets + m, n * (size_t)g / G) - offsets);
+            const size_t j_hi = (size_t)g + 1 == G ? m : (size_t)(std::lower_bound(offsets, offsets + m, n * ((size_t)g + 1) / G) - offsets);
+            if (j_hi <= j_lo) return BN254_OK;
+            const size_t base = offsets[j_lo];
+            std::vector<size_t> local(j_hi - j_lo + 1);
+            for (size_t j = j_lo; j <= j_hi; ++j) local[j - j_lo] = offsets[j] - base;
+            return bn254_pairing_product_batch(mh->ctx[(size_t)g], p + base, q + base, local.data(), j_hi - j_lo, out + j_lo);
+        });
+    }, true);
+    for (int rc : rcs) if (rc) return rc;
+    return BN254_OK;
+}
+int bn254_pairing_product_batch_multi(bn254_multi *mh, const bn_g1 *p, const bn_g2 *q, const size_t *offsets, size_t m, bn_gt *out) {
+    BnDeviceGuard dev_guard;
+    return bn_no_throw([&] { return product_batch_multi(mh, p, q, offsets, m, out); });
+}
+
 }  // extern "C"

@@ -86,6 +86,9 @@ struct bn254_ctx {
     hipEvent_t scratch_ev = nullptr;    // completion of the last launch that used ws / exp_tbl ...
     hipStream_t scratch_stream = nullptr;   // ... and the stream it ran on
     bool scratch_used = false;
+    BnBuf seg_plan;                     // work lists of the segmented fold (bn254_pairing_product_batch*), device side ...
+    BnBuf seg_plan_host{nullptr, 0, true};  // ... and their pinned staging, rewritten only after seg_plan_ev (its last copy) completed
+    hipEvent_t seg_plan_ev = nullptr;
     BnBuf stage[3];                     // device staging of the small host-buffer entry points
     BnSlot slot[BN_MAX_SLOTS];          // pipelined path (bn254_multi.hip)
     // leases of those slots: a batch of up to one chunk takes ONE of the first two (two callers overlap on the GPU - the number
@@ -166,6 +169,8 @@ int bn_launch_product(bn254_ctx *c, const void *in, size_t n, void *out, void *t
 size_t bn_product_tmp_bytes(const bn254_ctx *c, size_t n);
 // table: the caller's own buffer (pipelined path: the slot's) or NULL for the context's (then under a BnScratchGuard)
 int bn_mul_dev(bn254_ctx *ctx, int g, const void *d_p, const void *d_k, void *d_out, size_t n, hipStream_t s, int normalize, BnBuf *table = nullptr);
+// argument checks of bn254_pairing_product_batch* for m > 0 (CSR offsets, sizes, pointers); no device involved
+int bn_seg_check(const void *p, const void *q, const size_t *offsets, size_t m, const void *out);
 
 extern "C" {
 // bn254_kernels_b.hip
@@ -182,6 +187,7 @@ int bn254_launch_g2_prepare_native_B(const void *q, void *table, void *q_inf, si
 int bn254_launch_miller_native_B(const void *p, const void *table, const void *q_inf, size_t nq, size_t q_lo, int shared, void *f, size_t n, hipStream_t s);
 int bn254_launch_miller_native_shared_B(const void *p, const void *table, const void *q_inf, size_t nq, size_t q_lo, int shared, void *f, size_t n, int m, hipStream_t s);
 int bn254_launch_gt_mul_B(const void *a, const void *b, void *out, size_t n, hipStream_t s);
+int bn254_launch_gt_fold_seg_B(const void *pieces, size_t count, hipStream_t s);
 size_t bn254_gt_pow_table_bytes_B(size_t n);
 int bn254_launch_gt_pow_B(const void *a, const void *k, void *out, size_t n, void *table, int mode, hipStream_t s);
 int bn254_launch_gt_inverse_B(const void *a, void *out, size_t n, hipStream_t s);
@@ -191,6 +197,7 @@ int bn254_launch_wave_ubench_W(int which, int iters, void *out, hipStream_t s);
 int bn254_launch_final_exp_W(const void *f, void *out, size_t n, hipStream_t s);
 int bn254_launch_pairing_W(const void *p, const void *q, void *out, size_t n, int final_exp, hipStream_t s);
 int bn254_launch_gt_tail_W(const void *in, size_t groups, unsigned m, void *out, int final_exp, hipStream_t s);
+int bn254_launch_gt_tail_seg_W(const void *pieces, size_t count, hipStream_t s);
 void bn254_gt_reduce_sizes_W(size_t n, unsigned chunk, unsigned per_wave, size_t *grid, size_t *scratch_bytes, size_t *counter_words);
 int bn254_launch_gt_reduce_W(const void *in, size_t n, unsigned chunk, unsigned per_wave, unsigned bfly, void *scratch, void *counters, void *out, hipStream_t s);
 // bn254_kernels_q.hip: one pairing per quad of lanes (quad.hpp)

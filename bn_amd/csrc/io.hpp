@@ -18,6 +18,13 @@ BN_FN void f12_store(const Fq12<F2> &f, uint32_t *w) {
     f2_store(f.c0.c0, w + 0);  f2_store(f.c0.c1, w + 16); f2_store(f.c0.c2, w + 32);
     f2_store(f.c1.c0, w + 48); f2_store(f.c1.c1, w + 64); f2_store(f.c1.c2, w + 80);
 }
+// one piece of a segmented Fq12 fold (bn254_pairing_product_batch): dst = src[0] * ... * src[cnt-1], or one for cnt == 0.
+// Built on the host, read by bn254_gt_mul_B<true> and bn254_gt_tail_W<true>.
+struct BnSegPiece {
+    const uint32_t *src;
+    uint32_t *dst;
+    uint32_t cnt, pad;
+};
 BN_FN bool words_all_zero(const uint32_t *w, int n) {
     uint32_t o = 0;
     for (int i = 0; i < n; ++i) o |= w[i];

@@ -27,6 +27,24 @@ def _same_len(a, b):
         raise ValueError(f"operands differ in length: {a.shape[0]} vs {b.shape[0]}")
 
 
+def _offsets(offsets):
+    """CSR segment offsets as a C-contiguous size_t array (the C ABI checks their order and start)"""
+    o = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    if o.size == 0:
+        raise ValueError("offsets needs m + 1 >= 1 entries")
+    return o
+
+
+def _segment_args(p, q, offsets):
+    p = _arr(p, G1_WORDS) if len(p) else np.zeros((0, G1_WORDS), np.uint64)
+    q = _arr(q, G2_WORDS) if len(q) else np.zeros((0, G2_WORDS), np.uint64)
+    _same_len(p, q)
+    o = _offsets(offsets)
+    if int(o[-1]) != p.shape[0]:
+        raise ValueError(f"offsets[m] = {int(o[-1])} but {p.shape[0]} pairs were given")
+    return p, q, o, np.empty((o.size - 1, GT_WORDS), np.uint64)
+
+
 class Engine:
     """one context = one GPU (include/bn254_hip.h: bn254_ctx)"""
 
@@ -117,6 +135,13 @@ class Engine:
             raise ValueError("p and q differ in length")
         out = np.empty(GT_WORDS, np.uint64)
         _native.check(self._lib.bn254_pairing_product(self._h, _p(p), _p(q), p.shape[0], _p(out)))
+        return out
+
+    def pairing_product_batch(self, p, q, offsets):
+        """out[j] = fold(Gt::one(), acc * pairing(p[i], q[i])) over i in [offsets[j], offsets[j+1]) -> (m, 48) uint64;
+        ONE final exponentiation per segment (include/bn254_hip.h bn254_pairing_product_batch)"""
+        p, q, o, out = _segment_args(p, q, offsets)
+        _native.check(self._lib.bn254_pairing_product_batch(self._h, _p(p), _p(q), _p(o), o.size - 1, _p(out)))
         return out
 
     def g1_mul_batch(self, p, k):
@@ -287,6 +312,11 @@ class Engine:
     def miller_product_dev(self, d_p, d_q, n, d_partial, stream=0):
         _native.check(self._lib.bn254_miller_product_dev(self._h, d_p, d_q, n, d_partial, stream))
 
+    def pairing_product_batch_dev(self, d_p, d_q, offsets, d_out, stream=0):
+        """device pointers p, q, out (m values); `offsets` is a HOST sequence of m + 1 CSR offsets"""
+        o = _offsets(offsets)
+        _native.check(self._lib.bn254_pairing_product_batch_dev(self._h, d_p, d_q, _p(o), o.size - 1, d_out, stream))
+
     def g2_precompute_dev(self, d_q, d_coeffs, n, stream=0):
         _native.check(self._lib.bn254_g2_precompute_dev(self._h, d_q, d_coeffs, n, stream))
 
@@ -444,6 +474,12 @@ class MultiEngine:
         _same_len(p, q)
         out = np.empty(GT_WORDS, np.uint64)
         _native.check(self._lib.bn254_pairing_product_multi(self._h, _p(p), _p(q), p.shape[0], _p(out)))
+        return out
+
+    def pairing_product_batch(self, p, q, offsets):
+        """Engine.pairing_product_batch with the segments sharded over the ranks (segment j on the rank whose pair shard holds offsets[j])"""
+        p, q, o, out = _segment_args(p, q, offsets)
+        _native.check(self._lib.bn254_pairing_product_batch_multi(self._h, _p(p), _p(q), _p(o), o.size - 1, _p(out)))
         return out
 
     def g2_prepare(self, q):

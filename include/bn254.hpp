@@ -92,6 +92,22 @@ inline Gt pairing_product(const std::vector<G1> &p, const std::vector<G2> &q) {
     check(bn254_pairing_product(nullptr, reinterpret_cast<const bn_g1 *>(p.data()), reinterpret_cast<const bn_g2 *>(q.data()), p.size(), &r.v));
     return r;
 }
+// out[j] = that fold over the pairs [offsets[j], offsets[j+1]) (CSR segments, offsets.size() = m + 1): ONE final exponentiation per segment
+inline std::vector<Gt> pairing_product_batch(const std::vector<G1> &p, const std::vector<G2> &q, const std::vector<size_t> &offsets) {
+    if (p.size() != q.size()) throw std::invalid_argument("pairing_product_batch: length mismatch");
+    if (offsets.empty() || offsets.back() != p.size()) throw std::invalid_argument("pairing_product_batch: offsets must end at the pair count");
+    std::vector<Gt> out(offsets.size() - 1);
+    check(bn254_pairing_product_batch(nullptr, reinterpret_cast<const bn_g1 *>(p.data()), reinterpret_cast<const bn_g2 *>(q.data()), offsets.data(),
+                                      out.size(), reinterpret_cast<bn_gt *>(out.data())));
+    return out;
+}
+// ok[j] = (product of segment j == Gt::one()): the predicate of a block of pairing checks
+inline std::vector<bool> pairing_check_batch(const std::vector<G1> &p, const std::vector<G2> &q, const std::vector<size_t> &offsets) {
+    const std::vector<Gt> r = pairing_product_batch(p, q, offsets);
+    std::vector<bool> ok(r.size());
+    for (size_t j = 0; j < r.size(); ++j) ok[j] = r[j] == Gt::one();
+    return ok;
+}
 
 // G2 points prepared ONCE for many pairings: the device-resident counterpart of the crate's internal G2Precomp (groups/mod.rs:472-483; `precompute`
 // :557-588 runs in the constructor, on the GPU).  One point: shared by every p; several: point i is paired with p[i].
@@ -149,6 +165,15 @@ public:
         Gt r;
         check(bn254_pairing_product_multi(m_, reinterpret_cast<const bn_g1 *>(p.data()), reinterpret_cast<const bn_g2 *>(q.data()), p.size(), &r.v));
         return r;
+    }
+    // bn::pairing_product_batch with the segments sharded over the GPUs (no exchange)
+    std::vector<Gt> pairing_product_batch(const std::vector<G1> &p, const std::vector<G2> &q, const std::vector<size_t> &offsets) {
+        if (p.size() != q.size()) throw std::invalid_argument("pairing_product_batch: length mismatch");
+        if (offsets.empty() || offsets.back() != p.size()) throw std::invalid_argument("pairing_product_batch: offsets must end at the pair count");
+        std::vector<Gt> out(offsets.size() - 1);
+        check(bn254_pairing_product_batch_multi(m_, reinterpret_cast<const bn_g1 *>(p.data()), reinterpret_cast<const bn_g2 *>(q.data()), offsets.data(),
+                                                out.size(), reinterpret_cast<bn_gt *>(out.data())));
+        return out;
     }
 };
 

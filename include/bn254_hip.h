@@ -16,6 +16,7 @@
  * Semantics replaced:
  *   bn254_pairing_batch    out[i] = bn::pairing(p[i], q[i])                         lib.rs:181-183, groups/mod.rs:764-771
  *   bn254_pairing_product  fold(Gt::one(), |acc,(p,q)| acc * pairing(p,q))          shootout/main.rs:11-16, lib.rs:175-179
+ *   bn254_pairing_product_batch  out[j] = that fold over pairs [offsets[j], offsets[j+1])   shootout/main.rs:11-16 per segment, lib.rs:175-183
  *   bn254_g1_mul_batch     out[i] = normalize(p[i] * k[i])                          lib.rs:116-120,88-95, groups/mod.rs:250-270
  *   bn254_g2_mul_batch     same over G2                                             lib.rs:159-163,131-138
  *   bn254_g1/g2_add_batch  out[i] = a[i] + b[i] / a[i] - b[i] (raw Jacobian limbs)       lib.rs:103-114,146-157, groups/mod.rs:275-347
@@ -47,12 +48,14 @@
  *     (a process-wide default context per HIP device).  bn254_pairing_batch and bn254_g{1,2}_mul_batch arbitrate per pipeline
  *     slot: two callers with batches of up to one machine round (256 pairings per CU: 2^16 on an MI355X) run concurrently on two
  *     streams (the number of streams the GPU overlaps without loss), further callers and multi-chunk batches queue; every other
- *     entry point serialises its callers on the context.  Use one context per thread (or bn254_multi_*) for more overlap;
+ *     entry point serialises its callers on the context (bn254_pairing_product_batch too, except when every segment holds one pair: then
+ *     it IS bn254_pairing_batch).  Use one context per thread (or bn254_multi_*) for more overlap;
  *     bn254_ctx_set_option is atomic, but set options before concurrent use: a call in flight may run some
  *     of its launches under the old and some under the new setting (same bytes either way);
  *   - the *_dev entry points are asynchronous on the caller's stream.  Context-owned scratch (the final-exponentiation table,
  *     the product workspace) is ordered across streams with events, so calls on different streams of one context are safe
  *     and serialise on that scratch; the caller still owns the ordering of its OWN buffers between streams.
+ *     bn254_pairing_product_batch_dev reads its HOST `offsets` before it returns (the launches are planned from them).
  */
 #ifndef BN254_HIP_H
 #define BN254_HIP_H
@@ -145,6 +148,21 @@ int bn254_ctx_get_option_raw(bn254_ctx *ctx, int key, long *value);
 /* ctx == NULL uses a process-wide default context on the current HIP device. */
 int bn254_pairing_batch(bn254_ctx *ctx, const bn_g1 *p, const bn_g2 *q, bn_gt *out, size_t n);
 int bn254_pairing_product(bn254_ctx *ctx, const bn_g1 *p, const bn_g2 *q, size_t n, bn_gt *out);
+/* Batched multi-pairing: m independent products in one call - a block of Groth16 / EIP-197-style pairing checks.  Segments are given in
+   CSR form: offsets[0..m] with offsets[0] == 0, non-decreasing, n = offsets[m] pairs, and
+       out[j] = fold(Gt::one(), |acc, i| acc * pairing(p[i], q[i])) over i in [offsets[j], offsets[j+1]),   j < m
+   (shootout/main.rs:11-16 per segment, lib.rs:175-183), bit-identical to that fold.  An empty segment gives Gt::one(); a pair with a point at
+   infinity contributes one (groups/mod.rs:766).  ONE final exponentiation per segment.  Route (the existing thresholds choose it): at most
+   BN254_OPT_WAVE_PAIRING_MAX pairs and BN254_OPT_WAVE_FE_MAX segments - Miller loops one per wave, then one wave per segment folds at most 16
+   values and exponentiates (two launches); otherwise chunks of at most one machine round (BN254_OPT_ROUND_PAIRS pairs, cut at segment
+   boundaries; a longer segment carries its partial product across chunks), a segmented Fq12 fold on lane pairs (pieces of at most 16 values
+   per lane pair, ceil(log16 L) levels for a segment of L values) and the batched final exponentiation of the m values.  Every segment of
+   length 1: exactly bn254_pairing_batch.  Workspace: one round of Miller values plus 24 bytes of work list per segment and per 16 pairs.
+   Made for many short segments: ONE long segment folds on ever fewer lane pairs (5000 pairs: ~0.9 ms of fold) - a caller with a single
+   product, or a few thousand-pair ones, is better served by bn254_pairing_product, whose one-launch product tree needs ~0.1 ms.
+   Errors (BN254_E_BAD_ARG, checked before any device is touched): offsets == NULL with m > 0, offsets[0] != 0, decreasing offsets,
+   n > 2^40, a NULL p / q (n > 0) or out.  m == 0 returns BN254_OK and writes nothing. */
+int bn254_pairing_product_batch(bn254_ctx *ctx, const bn_g1 *p, const bn_g2 *q, const size_t *offsets, size_t m, bn_gt *out);
 int bn254_g1_mul_batch(bn254_ctx *ctx, const bn_g1 *p, const bn_fr *k, bn_g1 *out, size_t n);
 int bn254_g2_mul_batch(bn254_ctx *ctx, const bn_g2 *p, const bn_fr *k, bn_g2 *out, size_t n);
 /* out[i] = a[i] + b[i]  (negate_b != 0: a[i] - b[i] = a[i] + (-b[i])): `Add`/`Sub` of lib.rs:103-114,146-157 over
@@ -227,6 +245,9 @@ int bn254_pairing_batch_multi(bn254_multi *m, const bn_g1 *p, const bn_g2 *q, bn
    un-exponentiated Fq12, ONE all-gather of 384 bytes per rank, world-1 products and a single final exponentiation on rank 0
    (BASELINE configs[3]).  Bit-identical to the fold: the final exponentiation is a homomorphism and Gt values are canonical. */
 int bn254_pairing_product_multi(bn254_multi *m, const bn_g1 *p, const bn_g2 *q, size_t n, bn_gt *out);
+/* bn254_pairing_product_batch over the ranks: segment j runs on the rank whose pair shard [n*g/G, n*(g+1)/G) holds offsets[j]
+   (offsets[j] == n: the last rank), with all of its pairs.  No exchange. */
+int bn254_pairing_product_batch_multi(bn254_multi *mh, const bn_g1 *p, const bn_g2 *q, const size_t *offsets, size_t m, bn_gt *out);
 
 /* native prepared-G2 mode over the GPUs of the handle.  ONE point (nq == 1) is prepared on every rank's GPU and n pairings shard like
    bn254_pairing_batch_multi; nq > 1 points are sharded by the same rule ([nq*g/G, nq*(g+1)/G) on rank g) and then pair with exactly n == nq
@@ -283,6 +304,9 @@ int bn254_gt_product_dev(bn254_ctx *ctx, const void *d_in, size_t n, void *d_out
 int bn254_gt_product_final_exp_dev(bn254_ctx *ctx, const void *d_in, size_t m, void *d_out, void *stream);
 /* local part of a sharded multi-pairing: un-exponentiated product of the Miller values of n pairs -> one Fq12 */
 int bn254_miller_product_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, size_t n, void *d_partial, void *stream);
+/* bn254_pairing_product_batch on device-resident p, q, out; `offsets` (m+1 entries) is HOST memory (the launches are planned from it) and
+   may be freed on return */
+int bn254_pairing_product_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, const size_t *offsets, size_t m, void *d_out, void *stream);
 int bn254_g2_precompute_dev(bn254_ctx *ctx, const void *d_q, void *d_coeffs, size_t n, void *stream);
 int bn254_miller_prepared_dev(bn254_ctx *ctx, const void *d_p, const void *d_coeffs, int shared, void *d_f, size_t n, void *stream);
 /* native prepared-G2 mode on device-resident inputs.  bn254_g2_prepare_dev allocates the handle's table (that part synchronises with the
@@ -315,7 +339,7 @@ int bn254_tile_dev(bn254_ctx *ctx, const void *d_record, size_t record_bytes, si
    accumulated duration and launch count per kernel since the last reset (this is what bench.py's roofline uses). */
 int bn254_profile_enable(bn254_ctx *ctx, int on);
 int bn254_profile_reset(bn254_ctx *ctx);
-/* kernel: "miller", "miller_shared", "miller_wave", "miller_quad", "pairing_wave", "final_exp", "final_exp_wave", "final_exp_quad", "exp_by_neg_z", "gt_product", "gt_tail", "g1_mul", "g2_mul", "gt_mul", "gt_pow", "g2_precompute", "miller_prepared", "g2_prepare_native", "miller_native", "miller_native_shared", "wire_encode", "wire_decode", "gt_inverse", "g1_add", "g2_add".
+/* kernel: "miller", "miller_shared", "miller_wave", "miller_quad", "pairing_wave", "final_exp", "final_exp_wave", "final_exp_quad", "exp_by_neg_z", "gt_product", "gt_tail", "gt_segment", "gt_tail_seg", "g1_mul", "g2_mul", "gt_mul", "gt_pow", "g2_precompute", "miller_prepared", "g2_prepare_native", "miller_native", "miller_native_shared", "wire_encode", "wire_decode", "gt_inverse", "g1_add", "g2_add".
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);
 /* issue-rate ceiling of v_mad_u64_u32 (the 32x32+64 multiply-accumulate every field product is built from) at
