@@ -60,6 +60,12 @@ extern "C" {
     fn bn254_pairing_product_batch(ctx: *mut c_void, p: *const G1, q: *const G2, offsets: *const usize, m: usize, out: *mut Gt) -> c_int;
     fn bn254_pairing_product_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_q: *const c_void, offsets: *const usize, m: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn bn254_pairing_product_batch_multi(mh: *mut c_void, p: *const G1, q: *const G2, offsets: *const usize, m: usize, out: *mut Gt) -> c_int;
+    fn bn254_g1_msm_batch(ctx: *mut c_void, p: *const G1, k: *const Fr, offsets: *const usize, m: usize, out: *mut G1) -> c_int;
+    fn bn254_g2_msm_batch(ctx: *mut c_void, p: *const G2, k: *const Fr, offsets: *const usize, m: usize, out: *mut G2) -> c_int;
+    fn bn254_g1_msm_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_k: *const c_void, offsets: *const usize, m: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn bn254_g2_msm_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_k: *const c_void, offsets: *const usize, m: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn bn254_g1_msm_batch_multi(mh: *mut c_void, p: *const G1, k: *const Fr, offsets: *const usize, m: usize, out: *mut G1) -> c_int;
+    fn bn254_g2_msm_batch_multi(mh: *mut c_void, p: *const G2, k: *const Fr, offsets: *const usize, m: usize, out: *mut G2) -> c_int;
 }
 
 /// One line-function coefficient of a prepared G2 point: the crate's `EllCoeffs { ell_0, ell_vw, ell_vv: Fq2 }` (src/groups/mod.rs:472-476) as the
@@ -155,6 +161,24 @@ pub fn g2_mul_batch(p: &[G2], k: &[Fr]) -> Result<Vec<G2>, GpuError> {
     assert_eq!(p.len(), k.len());
     let mut out = p.to_vec();
     check(unsafe { bn254_g2_mul_batch(std::ptr::null_mut(), p.as_ptr(), k.as_ptr(), out.as_mut_ptr(), p.len()) })?;
+    Ok(out)
+}
+
+/// `out[j]` = normalized sum of `p[i] * k[i]` over the terms `offsets[j]..offsets[j+1]` (CSR segments, `offsets.len()` = m + 1): many
+/// independent multi-scalar multiplications in one call, ONE inversion per segment; an empty or cancelling segment gives `G1::zero()`
+pub fn g1_msm_batch(p: &[G1], k: &[Fr], offsets: &[usize]) -> Result<Vec<G1>, GpuError> {
+    assert_eq!(p.len(), k.len());
+    assert!(!offsets.is_empty() && offsets[offsets.len() - 1] == p.len());
+    let mut out = vec![G1::zero(); offsets.len() - 1];
+    check(unsafe { bn254_g1_msm_batch(std::ptr::null_mut(), p.as_ptr(), k.as_ptr(), offsets.as_ptr(), out.len(), out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+pub fn g2_msm_batch(p: &[G2], k: &[Fr], offsets: &[usize]) -> Result<Vec<G2>, GpuError> {
+    assert_eq!(p.len(), k.len());
+    assert!(!offsets.is_empty() && offsets[offsets.len() - 1] == p.len());
+    let mut out = vec![G2::zero(); offsets.len() - 1];
+    check(unsafe { bn254_g2_msm_batch(std::ptr::null_mut(), p.as_ptr(), k.as_ptr(), offsets.as_ptr(), out.len(), out.as_mut_ptr()) })?;
     Ok(out)
 }
 
@@ -402,6 +426,21 @@ impl MultiGpu {
         assert!(!offsets.is_empty() && offsets[offsets.len() - 1] == p.len());
         let mut out = vec![Gt::one(); offsets.len() - 1];
         check(unsafe { bn254_pairing_product_batch_multi(self.0, p.as_ptr(), q.as_ptr(), offsets.as_ptr(), out.len(), out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+    /// `g1_msm_batch` with the segments sharded over the GPUs (segment j on the GPU whose term shard holds offsets[j]; no exchange)
+    pub fn g1_msm_batch(&self, p: &[G1], k: &[Fr], offsets: &[usize]) -> Result<Vec<G1>, GpuError> {
+        assert_eq!(p.len(), k.len());
+        assert!(!offsets.is_empty() && offsets[offsets.len() - 1] == p.len());
+        let mut out = vec![G1::zero(); offsets.len() - 1];
+        check(unsafe { bn254_g1_msm_batch_multi(self.0, p.as_ptr(), k.as_ptr(), offsets.as_ptr(), out.len(), out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+    pub fn g2_msm_batch(&self, p: &[G2], k: &[Fr], offsets: &[usize]) -> Result<Vec<G2>, GpuError> {
+        assert_eq!(p.len(), k.len());
+        assert!(!offsets.is_empty() && offsets[offsets.len() - 1] == p.len());
+        let mut out = vec![G2::zero(); offsets.len() - 1];
+        check(unsafe { bn254_g2_msm_batch_multi(self.0, p.as_ptr(), k.as_ptr(), offsets.as_ptr(), out.len(), out.as_mut_ptr()) })?;
         Ok(out)
     }
 }

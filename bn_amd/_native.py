@@ -33,6 +33,12 @@ SIGNATURES = {   # name -> argtypes  (every function returns int unless noted)
     "bn254_pairing_product_batch": [_VP, _VP, _VP, _VP, _SZ, _VP],
     "bn254_pairing_product_batch_dev": [_VP, _VP, _VP, _VP, _SZ, _VP, _VP],
     "bn254_pairing_product_batch_multi": [_VP, _VP, _VP, _VP, _SZ, _VP],
+    "bn254_g1_msm_batch": [_VP, _VP, _VP, _VP, _SZ, _VP],
+    "bn254_g2_msm_batch": [_VP, _VP, _VP, _VP, _SZ, _VP],
+    "bn254_g1_msm_batch_dev": [_VP, _VP, _VP, _VP, _SZ, _VP, _VP],
+    "bn254_g2_msm_batch_dev": [_VP, _VP, _VP, _VP, _SZ, _VP, _VP],
+    "bn254_g1_msm_batch_multi": [_VP, _VP, _VP, _VP, _SZ, _VP],
+    "bn254_g2_msm_batch_multi": [_VP, _VP, _VP, _VP, _SZ, _VP],
     "bn254_g1_mul_batch": [_VP, _VP, _VP, _VP, _SZ],
     "bn254_g2_mul_batch": [_VP, _VP, _VP, _VP, _SZ],
     "bn254_g1_add_batch": [_VP, _VP, _VP, _VP, _SZ, C.c_int],

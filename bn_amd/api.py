@@ -107,6 +107,9 @@ class G1(_Point):
         return G1(default_engine().g1_add_batch(self.limbs, o.limbs, negate_b=True)[0])
     def __neg__(self):                    # lib.rs:113-114
         return G1(default_engine().g1_add_batch(G1.zero().limbs, self.limbs, negate_b=True)[0])
+    @staticmethod
+    def msm(points, scalars):             # normalize(sum points[i] * scalars[i]) in one call
+        return g1_msm_batch([list(zip(points, scalars))])[0]
 
 
 _G2_GEN = ((10857046999023057135944570762232829481370756359578518086990519993285655852781,
@@ -136,6 +139,9 @@ class G2(_Point):
         return G2(default_engine().g2_add_batch(self.limbs, o.limbs, negate_b=True)[0])
     def __neg__(self):
         return G2(default_engine().g2_add_batch(G2.zero().limbs, self.limbs, negate_b=True)[0])
+    @staticmethod
+    def msm(points, scalars):
+        return g2_msm_batch([list(zip(points, scalars))])[0]
 
 
 class Gt:
@@ -209,6 +215,34 @@ def pairing_product_batch(segments, qs=None, offsets=None, engine=None):
 def pairing_check_batch(segments, qs=None, offsets=None, engine=None):
     """numpy bool array: product of segment j == Gt::one(), compared as canonical limbs - the predicate of a Groth16 / EIP-197-style check"""
     return (_product_batch_limbs(segments, qs, offsets, engine) == Gt.one().limbs).all(axis=1)
+
+
+def _msm_arrays(group, segments, ks, offsets):
+    if offsets is not None:                   # (n, WORDS) points and (n,4) scalars + CSR offsets
+        return np.asarray(segments, np.uint64).reshape(-1, group.WORDS), np.asarray(ks, np.uint64).reshape(-1, 4), np.asarray(offsets, np.uint64)
+    if ks is not None:
+        raise ValueError("ks is only taken together with offsets")
+    segments = [list(s) for s in segments]
+    offs = np.zeros(len(segments) + 1, np.uint64)
+    offs[1:] = np.cumsum([len(s) for s in segments], dtype=np.uint64) if segments else []
+    terms = [pk for s in segments for pk in s]
+    P = np.stack([p.limbs for p, _ in terms]) if terms else np.zeros((0, group.WORDS), np.uint64)
+    K = np.stack([k.limbs for _, k in terms]) if terms else np.zeros((0, 4), np.uint64)
+    return P, K, offs
+
+
+def g1_msm_batch(segments, ks=None, offsets=None, engine=None):
+    """[normalize(sum of p * k over the terms of each segment)] (lib.rs:103-120,88-95 folded per segment): many independent multi-scalar
+    multiplications in one call, ONE inversion per segment.  segments: a sequence of sequences of (G1, Fr) - an empty one gives G1.zero() -,
+    or (n,12) / (n,4) uint64 arrays as `segments` / `ks` plus CSR `offsets` (m + 1 entries)."""
+    P, K, offs = _msm_arrays(G1, segments, ks, offsets)
+    return [G1(r) for r in (engine or default_engine()).g1_msm_batch(P, K, offs)]
+
+
+def g2_msm_batch(segments, ks=None, offsets=None, engine=None):
+    """the same over G2: (G2, Fr) terms, or (n,24) / (n,4) arrays plus offsets"""
+    P, K, offs = _msm_arrays(G2, segments, ks, offsets)
+    return [G2(r) for r in (engine or default_engine()).g2_msm_batch(P, K, offs)]
 
 
 class PreparedG2:

@@ -389,18 +389,22 @@ struct SegChunk { size_t lo, hi; bool carry_out; std::vector<SegLaunch> launches
 // partials, so level 0 writes fewer than 2 (chunk_pairs + 1) / BN_SEG_FOLD and every further level fewer than 1/8 of the level before.
 // Every partial of a chunk has a slot of its own (no level reuses another level's slots): a piece may read its inputs several levels
 // after they were written - the ragged tail of the small route reads them only after the deepest level of the plan.
-size_t seg_partials_max(size_t chunk_pairs) { return 4 * (chunk_pairs + 1) / BN_SEG_FOLD + 4; }
-// workspace (in Fq12 values): [carry in][chunk_pairs Miller values][partials of every level][carry out]
-size_t seg_ws_values(size_t chunk_pairs) { return chunk_pairs + 2 + seg_partials_max(chunk_pairs); }
+// (`fold` >= 4 values per piece - the multi-scalar multiplications plan with their own width, BN_MSM_FOLD: 2 L / fold (1 + 2 / fold + ...) <= 4 L / fold.)
+size_t seg_partials_max(size_t chunk_pairs, size_t fold = BN_SEG_FOLD) { return 4 * (chunk_pairs + 1) / fold + 4; }
+// workspace (in values: Fq12 here, Jacobian points for the multi-scalar multiplications): [carry in][chunk_pairs values][partials of every level][carry out]
+size_t seg_ws_values(size_t chunk_pairs, size_t fold = BN_SEG_FOLD) { return chunk_pairs + 2 + seg_partials_max(chunk_pairs, fold); }
 // false if the partials would not fit their region (cannot happen by the bound above; checked, never written out of bounds)
-bool seg_plan(const size_t *off, size_t m, size_t chunk_pairs, bool small, char *ws, char *d_out, std::vector<BnSegPiece> &pieces, std::vector<SegChunk> &chunks) {
-    const size_t n = off[m], V = sizeof(bn_gt), pb = seg_partials_max(chunk_pairs), last_cap = small ? BN_TAIL_SEG_MAX : BN_SEG_FOLD;
+// V: bytes per value; fold: values per piece; snap: cut at the last segment boundary inside a chunk (false: every chunk is full, and any
+// segment across a cut carries).  The piece that writes out[j] carries last = 1 (read by the point fold only: it normalises there).
+bool seg_plan(const size_t *off, size_t m, size_t chunk_pairs, bool small, char *ws, char *d_out, std::vector<BnSegPiece> &pieces, std::vector<SegChunk> &chunks,
+              size_t V = sizeof(bn_gt), size_t fold = BN_SEG_FOLD, bool snap = true) {
+    const size_t n = off[m], pb = seg_partials_max(chunk_pairs, fold), last_cap = small ? BN_TAIL_SEG_MAX : fold;
     char *const part = ws + (chunk_pairs + 1) * V, *const carry_out = ws + (chunk_pairs + 1 + pb) * V;
     size_t lo = 0, j = 0;
     bool carry = false;
     do {
         size_t hi = std::min(n, lo + chunk_pairs);
-        if (hi < n) {
+        if (snap && hi < n) {
             const size_t b = *(std::upper_bound(off, off + m + 1, hi) - 1);          // last segment boundary <= hi
             if (b > lo) hi = b;
         }
@@ -418,13 +422,13 @@ bool seg_plan(const size_t *off, size_t m, size_t chunk_pairs, bool small, char 
             while (L > last_cap) {
                 if (lv.size() <= level) lv.emplace_back();
                 char *base = part + used * V;
-                const size_t k = (L + BN_SEG_FOLD - 1) / BN_SEG_FOLD;
+                const size_t k = (L + fold - 1) / fold;
                 if (used + k > pb) return false;
                 for (size_t i = 0; i < k; ++i)
-                    lv[level].push_back({(const uint32_t *)(src + i * BN_SEG_FOLD * V), (uint32_t *)(base + i * V), (uint32_t)std::min(BN_SEG_FOLD, L - i * BN_SEG_FOLD), 0u});
+                    lv[level].push_back({(const uint32_t *)(src + i * fold * V), (uint32_t *)(base + i * V), (uint32_t)std::min(fold, L - i * fold), 0u});
                 used += k; src = base; L = k; ++level;
             }
-            const BnSegPiece last = {(const uint32_t *)src, (uint32_t *)(to_carry ? carry_out : d_out + jj * V), (uint32_t)L, 0u};
+            const BnSegPiece last = {(const uint32_t *)src, (uint32_t *)(to_carry ? carry_out : d_out + jj * V), (uint32_t)L, to_carry ? 0u : 1u};
             if (small) tail.push_back(last);
             else { if (lv.size() <= level) lv.resize(level + 1); lv[level].push_back(last); }
             ch.carry_out |= to_carry;
@@ -440,6 +444,19 @@ bool seg_plan(const size_t *off, size_t m, size_t chunk_pairs, bool small, char 
     return true;
 }
 }  // namespace
+// the work lists: ONE copy per call through the context's pinned staging, which is rewritten only after its previous copy completed
+// (so the caller's `offsets` may be freed as soon as the call returns)
+static int bn_seg_upload(bn254_ctx *c, const std::vector<BnSegPiece> &pieces, hipStream_t s) {
+    int rc;
+    const size_t bytes = pieces.size() * sizeof(BnSegPiece);
+    if (c->seg_plan_ev) HIP_TRY(hipEventSynchronize(c->seg_plan_ev));
+    else HIP_TRY(hipEventCreateWithFlags(&c->seg_plan_ev, hipEventDisableTiming));
+    if ((rc = c->seg_plan_host.reserve(bytes)) || (rc = c->seg_plan.reserve(bytes))) return rc;
+    memcpy(c->seg_plan_host.p, pieces.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(c->seg_plan.p, c->seg_plan_host.p, bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(c->seg_plan_ev, s));
+    return BN254_OK;
+}
 // out[j] = final_exponentiation(prod of the Miller values of pairs [off[j], off[j+1])) for j < m; off is HOST memory; scratch guard held by the caller
 static int bn_launch_product_batch(bn254_ctx *c, const void *d_p, const void *d_q, const size_t *off, size_t m, void *d_out, hipStream_t s) {
     const size_t n = off[m];
@@ -452,15 +469,7 @@ static int bn_launch_product_batch(bn254_ctx *c, const void *d_p, const void *d_
     std::vector<BnSegPiece> pieces;
     std::vector<SegChunk> chunks;
     if (!seg_plan(off, m, chunk_pairs, small, (char *)c->ws.p, (char *)d_out, pieces, chunks)) return BN254_E_INTERNAL;
-    // the work lists: ONE copy per call through the context's pinned staging, which is rewritten only after its previous copy completed
-    // (so the caller's `offsets` may be freed as soon as this returns)
-    const size_t bytes = pieces.size() * sizeof(BnSegPiece);
-    if (c->seg_plan_ev) HIP_TRY(hipEventSynchronize(c->seg_plan_ev));
-    else HIP_TRY(hipEventCreateWithFlags(&c->seg_plan_ev, hipEventDisableTiming));
-    if ((rc = c->seg_plan_host.reserve(bytes)) || (rc = c->seg_plan.reserve(bytes))) return rc;
-    memcpy(c->seg_plan_host.p, pieces.data(), bytes);
-    HIP_TRY(hipMemcpyAsync(c->seg_plan.p, c->seg_plan_host.p, bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(c->seg_plan_ev, s));
+    if ((rc = bn_seg_upload(c, pieces, s))) return rc;
     const BnSegPiece *list = (const BnSegPiece *)c->seg_plan.p;
     const size_t pb = seg_partials_max(chunk_pairs);
     for (const SegChunk &ch : chunks) {
@@ -484,6 +493,57 @@ static int bn_launch_product_batch(bn254_ctx *c, const void *d_p, const void *d_
             HIP_TRY(hipMemcpyAsync(c->ws.p, (char *)c->ws.p + (chunk_pairs + 1 + pb) * sizeof(bn_gt), sizeof(bn_gt), hipMemcpyDeviceToDevice, s));
     }
     return small ? BN254_OK : bn_launch_final_exp(c, d_out, d_out, m, s, nullptr);
+}
+
+// ---- segmented multi-scalar multiplication: out[j] = normalize(sum of p[i] * k[i] over i in [off[j], off[j+1])) (bn254_g{1,2}_msm_batch*)
+// The plan of the batched multi-pairing with points for Fq12 values.  Terms are cut into chunks of at most one sub-launch of the
+// multiplication kernels (BN_MUL_LANES_PER_LAUNCH lanes: 2^20 G1 / 2^19 G2 terms, every launch but the last one full, like bn_mul_dev); a
+// segment that crosses a cut carries its partial sum - Jacobian - into value slot 0 of the next chunk.  Per chunk: the term kernel
+// (bn254_g{1,2}_mul_M<true>: the GLV / GLS chain, NO normalisation) writes Jacobian points to the workspace, then the levels of the segmented
+// fold (bn254_g{1,2}_add_M<true>): every lane (G2: lane pair) adds one piece of at most BN_MSM_FOLD consecutive values with the complete
+// addition, ceil(log_BN_MSM_FOLD L) levels for a segment of L terms, and the piece that completes a segment normalises: one inversion per
+// segment instead of one per term.
+// BN_MSM_FOLD = 4, from the sweep over 4 / 8 / 16 / 32 in profiles/r08_msm.txt (tools/time_msm.py --sweep): a narrow piece keeps more lanes
+// busy and its serial chain short, a wide one saves levels (launches and a round trip of the partial sums through memory) - the fold of
+// 16 x 3001 terms takes 0.27 / 0.37 / 0.49 / 0.74 ms, of 2^14 x 16 terms 0.17 / 0.16 / 0.22 / 0.23 ms.  (seg_partials_max needs >= 4.)
+constexpr size_t BN_MSM_FOLD = 4;
+static_assert(BN_MSM_FOLD >= 4, "seg_partials_max bounds the partial sums for fold widths from 4");
+int bn_msm_check(const void *p, const void *k, const size_t *offsets, size_t m, const void *out) { return bn_seg_check(p, k, offsets, m, out); }
+static bool bn_msm_all_ones(const size_t *off, size_t m) {
+    bool ones = off[m] == m;
+    for (size_t j = 0; ones && j < m; ++j) ones = off[j] == j;
+    return ones;
+}
+// off is HOST memory; scratch guard held by the caller
+static int bn_launch_msm(bn254_ctx *c, int g, const void *d_p, const void *d_k, const size_t *off, size_t m, void *d_out, hipStream_t s) {
+    const size_t n = off[m], V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2);
+    if (bn_msm_all_ones(off, m)) return bn_mul_dev(c, g, d_p, d_k, d_out, n, s, 1);         // every segment one term: bn254_g{1,2}_mul_batch's launches
+    const size_t step = BN_MUL_LANES_PER_LAUNCH / (g == 1 ? 1 : 2), chunk = std::max<size_t>(1, std::min(n, step));
+    int rc;
+    if ((rc = c->ws.reserve(seg_ws_values(chunk, BN_MSM_FOLD) * V)) || (rc = c->mul_tbl.reserve(bn254_mul_table_bytes_M(g, chunk)))) return rc;
+    std::vector<BnSegPiece> pieces;
+    std::vector<SegChunk> chunks;
+    if (!seg_plan(off, m, chunk, false, (char *)c->ws.p, (char *)d_out, pieces, chunks, V, BN_MSM_FOLD, false)) return BN254_E_INTERNAL;
+    if ((rc = bn_seg_upload(c, pieces, s))) return rc;
+    const BnSegPiece *list = (const BnSegPiece *)c->seg_plan.p;
+    const size_t pb = seg_partials_max(chunk, BN_MSM_FOLD);
+    for (const SegChunk &ch : chunks) {
+        if (ch.hi > ch.lo) {
+            BnScope sc(c, s, g == 1 ? "g1_msm_mul" : "g2_msm_mul");
+            rc = bn254_launch_msm_mul_M(g, (const char *)d_p + ch.lo * V, (const char *)d_k + ch.lo * sizeof(bn_fr), (char *)c->ws.p + V, ch.hi - ch.lo, c->mul_tbl.p, s);
+            if (rc) return rc;
+        }
+        for (const SegLaunch &l : ch.launches) {
+            rc = bn_for_parts(l.count, BN_LAUNCH_MAX, [&](size_t lo, size_t cnt) -> int {
+                BnScope sc(c, s, g == 1 ? "g1_msm_fold" : "g2_msm_fold");
+                return bn254_launch_msm_fold_M(g, list + l.first + lo, cnt, s);
+            });
+            if (rc) return rc;
+        }
+        if (ch.carry_out)                 // the segment that goes on: its partial sum becomes value slot 0 of the next chunk
+            HIP_TRY(hipMemcpyAsync(c->ws.p, (char *)c->ws.p + (chunk + 1 + pb) * V, V, hipMemcpyDeviceToDevice, s));
+    }
+    return BN254_OK;
 }
 
 extern "C" {
@@ -676,6 +736,18 @@ int bn254_g1_mul_batch_dev(bn254_ctx *c, const void *p, const void *k, void *o, 
 int bn254_g2_mul_batch_dev(bn254_ctx *c, const void *p, const void *k, void *o, size_t n, void *s) { return mul_dev(c, 2, p, k, o, n, s, 1); }
 int bn254_g1_mul_jacobian_dev(bn254_ctx *c, const void *p, const void *k, void *o, size_t n, void *s) { return mul_dev(c, 1, p, k, o, n, s, 0); }
 int bn254_g2_mul_jacobian_dev(bn254_ctx *c, const void *p, const void *k, void *o, size_t n, void *s) { return mul_dev(c, 2, p, k, o, n, s, 0); }
+static int msm_dev(bn254_ctx *ctx, int g, const void *d_p, const void *d_k, const size_t *offsets, size_t m, void *d_out, void *stream) {
+    if (m == 0) return BN254_OK;
+    if (int e = bn_msm_check(d_p, d_k, offsets, m, d_out)) return e;          // before any device lookup
+    int rc = bn_get_ctx(ctx); if (rc) return rc;
+    BnDeviceGuard dev_guard;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    BnScratchGuard gd(ctx, s); if (gd.rc) return gd.rc;          // workspace, window tables and work list are context-owned scratch
+    return bn_no_throw([&] { return bn_launch_msm(ctx, g, d_p, d_k, offsets, m, d_out, s); });
+}
+int bn254_g1_msm_batch_dev(bn254_ctx *c, const void *p, const void *k, const size_t *offsets, size_t m, void *o, void *s) { return msm_dev(c, 1, p, k, offsets, m, o, s); }
+int bn254_g2_msm_batch_dev(bn254_ctx *c, const void *p, const void *k, const size_t *offsets, size_t m, void *o, void *s) { return msm_dev(c, 2, p, k, offsets, m, o, s); }
 
 int bn254_g2_precompute_dev(bn254_ctx *ctx, const void *d_q, void *d_coeffs, size_t n, void *stream) {
     BN_DEV_PROLOGUE(!d_q || !d_coeffs, 0x7fffffffu / (102 * 48));
@@ -896,6 +968,26 @@ int bn254_g2_mul_batch(bn254_ctx *ctx, const bn_g2 *p, const bn_fr *k, bn_g2 *ou
     HIP_TRY(hipSetDevice(ctx->device));
     return bn_no_throw([&] { return bn_mul_batch_pipelined(ctx, 2, p, k, out, n); });
 }
+static int msm_host(bn254_ctx *ctx, int g, const void *p, const bn_fr *k, const size_t *offsets, size_t m, void *out) {
+    if (m == 0) return BN254_OK;
+    if (int e = bn_msm_check(p, k, offsets, m, out)) return e;                // before any device lookup
+    const size_t n = offsets[m], V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2);
+    if (bn_msm_all_ones(offsets, m))                                          // every segment one term: the pipelined batch path itself
+        return g == 1 ? bn254_g1_mul_batch(ctx, (const bn_g1 *)p, k, (bn_g1 *)out, n) : bn254_g2_mul_batch(ctx, (const bn_g2 *)p, k, (bn_g2 *)out, n);
+    BN_HOST_PROLOGUE();
+    BnBuf &dp = ctx->stage[0], &dk = ctx->stage[1], &dout = ctx->stage[2];
+    if ((rc = dp.reserve(n * V)) || (rc = dk.reserve(n * sizeof(bn_fr))) || (rc = dout.reserve(m * V))) return rc;
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(dp.p, p, n * V, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(dk.p, k, n * sizeof(bn_fr), hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = msm_dev(ctx, g, dp.p, dk.p, offsets, m, dout.p, ctx->stream); if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, dout.p, m * V, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return BN254_OK;
+}
+int bn254_g1_msm_batch(bn254_ctx *ctx, const bn_g1 *p, const bn_fr *k, const size_t *offsets, size_t m, bn_g1 *out) { return msm_host(ctx, 1, p, k, offsets, m, out); }
+int bn254_g2_msm_batch(bn254_ctx *ctx, const bn_g2 *p, const bn_fr *k, const size_t *offsets, size_t m, bn_g2 *out) { return msm_host(ctx, 2, p, k, offsets, m, out); }
 int bn254_g2_precompute(bn254_ctx *ctx, const bn_g2 *q, bn_ell_coeffs *coeffs, size_t n) {
     if (n == 0) return BN254_OK;
     if (!q || !coeffs) return BN254_E_BAD_ARG;

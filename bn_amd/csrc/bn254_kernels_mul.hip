@@ -84,7 +84,8 @@ struct AffTableMem {
 
 // NORMALIZE is a template parameter, i.e. each flavour is its OWN kernel: with a run-time flag the reference chain and the GLV /
 // windowed chain were register-allocated together (round 2: 74 spilled VGPRs in the G1 kernel).
-template <class F, bool NORMALIZE>
+// KEEP_JAC (the term kernels of bn254_g{1,2}_msm_batch): the fast chain WITHOUT jac_normalize - the sum of a segment is normalised once.
+template <class F, bool NORMALIZE, bool KEEP_JAC = false>
 __device__ __forceinline__ Jac<F> run_chain(const Jac<F> &p, const uint32_t *km, uint4 *table, uint32_t lane) {
     uint32_t kw[8], raw[8];
 #pragma unroll
@@ -98,31 +99,41 @@ __device__ __forceinline__ Jac<F> run_chain(const Jac<F> &p, const uint32_t *km,
 #else
         AffTableMem<F> tab = {table + (size_t)lane * AFF_LANE_U4};
 #endif
-        if constexpr (std::is_same<F, FqField>::value) return jac_normalize<F>(scalar_mul_glv(p, raw, tab));      // G1: GLV + signed windows
+        if constexpr (KEEP_JAC) {
+            if constexpr (std::is_same<F, FqField>::value) return scalar_mul_glv(p, raw, tab);
+            else return scalar_mul_gls<F2>(p, raw, tab);
+        } else if constexpr (std::is_same<F, FqField>::value) return jac_normalize<F>(scalar_mul_glv(p, raw, tab));      // G1: GLV + signed windows
         else return jac_normalize<F>(scalar_mul_gls<F2>(p, raw, tab));                                             // G2: GLS, four signed-window streams
     } else {
         return scalar_mul_reference_chain<F>(p, raw);
     }
 }
 
-template <bool NORMALIZE>
+template <bool NORMALIZE, bool KEEP_JAC = false>
 __device__ __forceinline__ void g1_mul_body(const uint32_t *p, const uint32_t *k, uint32_t *out, uint32_t n, uint4 *table) {
     uint32_t idx = blockIdx.x * BLOCK + threadIdx.x;
     if (idx >= n) return;
     const uint32_t *w = p + 24u * idx;
     Jac<FqField> pt = {fe_from_u32x8(w), fe_from_u32x8(w + 8), fe_from_u32x8(w + 16)};
-    Jac<FqField> r = run_chain<FqField, NORMALIZE>(pt, k + 8u * idx, table, idx);
+    Jac<FqField> r = run_chain<FqField, NORMALIZE, KEEP_JAC>(pt, k + 8u * idx, table, idx);
     uint32_t *o = out + 24u * idx;
     fe_to_u32x8(r.x, o); fe_to_u32x8(r.y, o + 8); fe_to_u32x8(r.z, o + 16);
 }
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BN_MUL_WAVES, BN_MUL_WAVES))) bn254_g1_mul_M(const uint32_t *p, const uint32_t *k, uint32_t *out, uint32_t n, uint4 *table) {
     g1_mul_body<true>(p, k, out, n, table);
 }
+// The term kernel of bn254_g1_msm_batch: out[i] = p[i] * k[i] by the same GLV chain, left in JACOBIAN form (any representation of the
+// group element; infinity as z = 0) for the segmented fold below, which normalises once per segment.  A template beside the plain kernel,
+// whose name and body stay as they are.
+template <bool JACOBIAN>
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BN_MUL_WAVES, BN_MUL_WAVES))) bn254_g1_mul_M(const uint32_t *p, const uint32_t *k, uint32_t *out, uint32_t n, uint4 *table) {
+    g1_mul_body<true, JACOBIAN>(p, k, out, n, table);
+}
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BN_MUL_WAVES, BN_MUL_WAVES))) bn254_g1_mul_chain_M(const uint32_t *p, const uint32_t *k, uint32_t *out, uint32_t n) {
     g1_mul_body<false>(p, k, out, n, nullptr);
 }
 
-template <bool NORMALIZE>
+template <bool NORMALIZE, bool KEEP_JAC = false>
 __device__ __forceinline__ void g2_mul_body(const uint32_t *p, const uint32_t *k, uint32_t *out, uint32_t n, uint4 *table) {
     uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
     uint32_t pair = t >> 1;
@@ -131,7 +142,7 @@ __device__ __forceinline__ void g2_mul_body(const uint32_t *p, const uint32_t *k
     const uint32_t *w = p + 48u * pair;
     typedef Fq2Field<F2> F;
     Jac<F> pt = {f2_load((const F2 *)nullptr, w), f2_load((const F2 *)nullptr, w + 16), f2_load((const F2 *)nullptr, w + 32)};
-    Jac<F> r = run_chain<F, NORMALIZE>(pt, k + 8u * pair, table, t);
+    Jac<F> r = run_chain<F, NORMALIZE, KEEP_JAC>(pt, k + 8u * pair, table, t);
     if (live) {
         uint32_t *o = out + 48u * pair;
         f2_store(r.x, o); f2_store(r.y, o + 16); f2_store(r.z, o + 32);
@@ -139,6 +150,11 @@ __device__ __forceinline__ void g2_mul_body(const uint32_t *p, const uint32_t *k
 }
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) bn254_g2_mul_M(const uint32_t *p, const uint32_t *k, uint32_t *out, uint32_t n, uint4 *table) {
     g2_mul_body<true>(p, k, out, n, table);
+}
+// the term kernel of bn254_g2_msm_batch (see bn254_g1_mul_M<JACOBIAN>)
+template <bool JACOBIAN>
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) bn254_g2_mul_M(const uint32_t *p, const uint32_t *k, uint32_t *out, uint32_t n, uint4 *table) {
+    g2_mul_body<true, JACOBIAN>(p, k, out, n, table);
 }
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) bn254_g2_mul_chain_M(const uint32_t *p, const uint32_t *k, uint32_t *out, uint32_t n) {
     g2_mul_body<false>(p, k, out, n, nullptr);
@@ -176,6 +192,42 @@ __global__ void __launch_bounds__(BLOCK) bn254_g2_add_M(const uint32_t *a, const
         f2_store(r.x, o); f2_store(r.y, o + 16); f2_store(r.z, o + 32);
     }
 }
+// One level of the segmented fold of bn254_g{1,2}_msm_batch: lane (G2: lane pair) i adds the pieces[i].cnt consecutive Jacobian points at
+// pieces[i].src in index order - a serial chain chosen by the host (at most BN_MSM_FOLD = 4 values) - into pieces[i].dst; an empty piece is
+// the point at infinity.  The COMPLETE addition: two equal terms of a segment double, P*k + P*(r-k) cancels, and a partial sum at infinity is
+// the left operand of the next addition.  pieces[i].last: the sum of a whole segment, normalised (infinity: G::zero() = (0, 1, 0)).
+// Instances of the names bn254_g{1,2}_add_M beside the plain kernels; `SEG` is always true.
+template <class F, class Load>
+__device__ __forceinline__ Jac<F> msm_fold_body(const BnSegPiece &pc, uint32_t words, Load load) {
+    Jac<F> acc = {F::zero(), F::one(), F::zero()};
+    if (pc.cnt) acc = load(pc.src);
+#pragma unroll 1
+    for (uint32_t j = 1; j < pc.cnt; ++j) {
+        const Jac<F> q = load(pc.src + words * j);
+        acc = jac_add_flags<F>(acc, q, F::is_zero(acc.z), F::is_zero(q.z));
+    }
+    if (pc.last) acc = jac_normalize<F>(acc);
+    return acc;
+}
+template <bool SEG>
+__global__ void __launch_bounds__(BLOCK) bn254_g1_add_M(const BnSegPiece *pieces, uint32_t n) {
+    uint32_t idx = blockIdx.x * BLOCK + threadIdx.x;
+    if (idx >= n) return;
+    const BnSegPiece pc = pieces[idx];
+    Jac<FqField> r = msm_fold_body<FqField>(pc, 24u, [](const uint32_t *w) { return Jac<FqField>{fe_from_u32x8(w), fe_from_u32x8(w + 8), fe_from_u32x8(w + 16)}; });
+    fe_to_u32x8(r.x, pc.dst); fe_to_u32x8(r.y, pc.dst + 8); fe_to_u32x8(r.z, pc.dst + 16);
+}
+template <bool SEG>
+__global__ void __launch_bounds__(BLOCK) bn254_g2_add_M(const BnSegPiece *pieces, uint32_t n) {
+    uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
+    uint32_t pair = t >> 1;
+    bool live = pair < n;
+    if (!live) pair = n - 1;                       // both lanes of a pair share the piece: the DPP exchanges never meet a retired partner
+    typedef Fq2Field<F2> F;
+    const BnSegPiece pc = pieces[pair];
+    Jac<F> r = msm_fold_body<F>(pc, 48u, [](const uint32_t *w) { return Jac<F>{f2_load((const F2 *)nullptr, w), f2_load((const F2 *)nullptr, w + 16), f2_load((const F2 *)nullptr, w + 32)}; });
+    if (live) { f2_store(r.x, pc.dst); f2_store(r.y, pc.dst + 16); f2_store(r.z, pc.dst + 32); }
+}
 }  // namespace
 
 extern "C" {
@@ -204,6 +256,19 @@ int bn254_launch_g2_mul_M(const void *p, const void *k, void *out, size_t n, int
     unsigned grid = (unsigned)((2 * n + BLOCK - 1) / BLOCK);
     if (normalize) hipLaunchKernelGGL(bn254_g2_mul_M, dim3(grid), dim3(BLOCK), 0, s, (const uint32_t *)p, (const uint32_t *)k, (uint32_t *)out, (uint32_t)n, (uint4 *)table);
     else hipLaunchKernelGGL(bn254_g2_mul_chain_M, dim3(grid), dim3(BLOCK), 0, s, (const uint32_t *)p, (const uint32_t *)k, (uint32_t *)out, (uint32_t)n);
+    return (int)hipGetLastError();
+}
+// bn254_g{1,2}_msm_batch: the term kernel (Jacobian results, `table` as above) and one level of the segmented fold (`count` pieces in device memory)
+int bn254_launch_msm_mul_M(int g, const void *p, const void *k, void *out, size_t n, void *table, hipStream_t s) {
+    unsigned grid = (unsigned)(((g == 1 ? n : 2 * n) + BLOCK - 1) / BLOCK);
+    if (g == 1) hipLaunchKernelGGL(bn254_g1_mul_M<true>, dim3(grid), dim3(BLOCK), 0, s, (const uint32_t *)p, (const uint32_t *)k, (uint32_t *)out, (uint32_t)n, (uint4 *)table);
+    else hipLaunchKernelGGL(bn254_g2_mul_M<true>, dim3(grid), dim3(BLOCK), 0, s, (const uint32_t *)p, (const uint32_t *)k, (uint32_t *)out, (uint32_t)n, (uint4 *)table);
+    return (int)hipGetLastError();
+}
+int bn254_launch_msm_fold_M(int g, const void *pieces, size_t count, hipStream_t s) {
+    unsigned grid = (unsigned)(((g == 1 ? count : 2 * count) + BLOCK - 1) / BLOCK);
+    if (g == 1) hipLaunchKernelGGL(bn254_g1_add_M<true>, dim3(grid), dim3(BLOCK), 0, s, (const BnSegPiece *)pieces, (uint32_t)count);
+    else hipLaunchKernelGGL(bn254_g2_add_M<true>, dim3(grid), dim3(BLOCK), 0, s, (const BnSegPiece *)pieces, (uint32_t)count);
     return (int)hipGetLastError();
 }
 }

@@ -492,7 +492,10 @@ int bn254_pairing_product_prepared_native_multi(bn254_multi *m, const bn_g1 *p, 
 
 // segment j runs on the rank whose pair shard [n*g/G, n*(g+1)/G) holds offsets[j] (offsets[j] == n: the last rank), with all of its pairs -
 // so every rank owns a contiguous run of segments and of pairs; no exchange
-static int product_batch_multi(bn254_multi *mh, const bn_g1 *p, const bn_g2 *q, const size_t *offsets, size_t m, bn_gt *out) {
+// (the same rule shards bn254_g{1,2}_msm_batch_multi, terms for pairs)
+// call(ctx, base, local offsets, segments, j_lo): the single-device entry point on terms [base, ...) and segments [j_lo, j_lo + segments)
+typedef std::function<int(bn254_ctx *, size_t, const size_t *, size_t, size_t)> SegCall;
+static int seg_multi(bn254_multi *mh, const void *p, const void *q, const size_t *offsets, size_t m, const void *out, const SegCall &call) {
     if (m == 0) return BN254_OK;
     if (int e = bn_seg_check(p, q, offsets, m, out)) return e;            // the segment checks first, as on one device
     if (!mh) return BN254_E_BAD_ARG;
@@ -509,7 +512,7 @@ static int product_batch_multi(bn254_multi *mh, const bn_g1 *p, const bn_g2 *q, 
             const size_t base = offsets[j_lo];
             std::vector<size_t> local(j_hi - j_lo + 1);
             for (size_t j = j_lo; j <= j_hi; ++j) local[j - j_lo] = offsets[j] - base;
-            return bn254_pairing_product_batch(mh->ctx[(size_t)g], p + base, q + base, local.data(), j_hi - j_lo, out + j_lo);
+            return call(mh->ctx[(size_t)g], base, local.data(), j_hi - j_lo, j_lo);
         });
     }, true);
     for (int rc : rcs) if (rc) return rc;
@@ -517,7 +520,27 @@ static int product_batch_multi(bn254_multi *mh, const bn_g1 *p, const bn_g2 *q, 
 }
 int bn254_pairing_product_batch_multi(bn254_multi *mh, const bn_g1 *p, const bn_g2 *q, const size_t *offsets, size_t m, bn_gt *out) {
     BnDeviceGuard dev_guard;
-    return bn_no_throw([&] { return product_batch_multi(mh, p, q, offsets, m, out); });
+    return bn_no_throw([&] {
+        return seg_multi(mh, p, q, offsets, m, out, [&](bn254_ctx *c, size_t base, const size_t *local, size_t cnt, size_t j_lo) {
+            return bn254_pairing_product_batch(c, p + base, q + base, local, cnt, out + j_lo);
+        });
+    });
+}
+int bn254_g1_msm_batch_multi(bn254_multi *mh, const bn_g1 *p, const bn_fr *k, const size_t *offsets, size_t m, bn_g1 *out) {
+    BnDeviceGuard dev_guard;
+    return bn_no_throw([&] {
+        return seg_multi(mh, p, k, offsets, m, out, [&](bn254_ctx *c, size_t base, const size_t *local, size_t cnt, size_t j_lo) {
+            return bn254_g1_msm_batch(c, p + base, k + base, local, cnt, out + j_lo);
+        });
+    });
+}
+int bn254_g2_msm_batch_multi(bn254_multi *mh, const bn_g2 *p, const bn_fr *k, const size_t *offsets, size_t m, bn_g2 *out) {
+    BnDeviceGuard dev_guard;
+    return bn_no_throw([&] {
+        return seg_multi(mh, p, k, offsets, m, out, [&](bn254_ctx *c, size_t base, const size_t *local, size_t cnt, size_t j_lo) {
+            return bn254_g2_msm_batch(c, p + base, k + base, local, cnt, out + j_lo);
+        });
+    });
 }
 
 }  // extern "C"

@@ -171,6 +171,8 @@ size_t bn_product_tmp_bytes(const bn254_ctx *c, size_t n);
 int bn_mul_dev(bn254_ctx *ctx, int g, const void *d_p, const void *d_k, void *d_out, size_t n, hipStream_t s, int normalize, BnBuf *table = nullptr);
 // argument checks of bn254_pairing_product_batch* for m > 0 (CSR offsets, sizes, pointers); no device involved
 int bn_seg_check(const void *p, const void *q, const size_t *offsets, size_t m, const void *out);
+// the same checks for bn254_g{1,2}_msm_batch* (points, scalars)
+int bn_msm_check(const void *p, const void *k, const size_t *offsets, size_t m, const void *out);
 
 extern "C" {
 // bn254_kernels_b.hip
@@ -210,4 +212,6 @@ int bn254_launch_g1_mul_M(const void *p, const void *k, void *out, size_t n, int
 int bn254_launch_g2_mul_M(const void *p, const void *k, void *out, size_t n, int normalize, void *table, hipStream_t s);
 int bn254_launch_g1_add_M(const void *a, const void *b, void *out, size_t n, int negate_b, hipStream_t s);
 int bn254_launch_g2_add_M(const void *a, const void *b, void *out, size_t n, int negate_b, hipStream_t s);
+int bn254_launch_msm_mul_M(int g, const void *p, const void *k, void *out, size_t n, void *table, hipStream_t s);
+int bn254_launch_msm_fold_M(int g, const void *pieces, size_t count, hipStream_t s);
 }

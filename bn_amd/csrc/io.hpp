@@ -20,10 +20,12 @@ BN_FN void f12_store(const Fq12<F2> &f, uint32_t *w) {
 }
 // one piece of a segmented Fq12 fold (bn254_pairing_product_batch): dst = src[0] * ... * src[cnt-1], or one for cnt == 0.
 // Built on the host, read by bn254_gt_mul_B<true> and bn254_gt_tail_W<true>.
+// The same record drives the segmented point fold of bn254_g{1,2}_msm_batch (bn254_g{1,2}_add_M<true>): dst = src[0] + ... + src[cnt-1]
+// in Jacobian form, or the point at infinity for cnt == 0; `last` != 0 marks the piece that completes a segment, which is normalised.
 struct BnSegPiece {
     const uint32_t *src;
     uint32_t *dst;
-    uint32_t cnt, pad;
+    uint32_t cnt, last;
 };
 BN_FN bool words_all_zero(const uint32_t *w, int n) {
     uint32_t o = 0;

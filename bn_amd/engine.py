@@ -45,6 +45,16 @@ def _segment_args(p, q, offsets):
     return p, q, o, np.empty((o.size - 1, GT_WORDS), np.uint64)
 
 
+def _msm_args(p, k, offsets, words):
+    p = _arr(p, words) if len(p) else np.zeros((0, words), np.uint64)
+    k = _arr(k, 4) if len(k) else np.zeros((0, 4), np.uint64)
+    _same_len(p, k)
+    o = _offsets(offsets)
+    if int(o[-1]) != p.shape[0]:
+        raise ValueError(f"offsets[m] = {int(o[-1])} but {p.shape[0]} terms were given")
+    return p, k, o, np.empty((o.size - 1, words), np.uint64)
+
+
 class Engine:
     """one context = one GPU (include/bn254_hip.h: bn254_ctx)"""
 
@@ -154,6 +164,19 @@ class Engine:
         p = _arr(p, G2_WORDS); k = _arr(k, 4); _same_len(p, k)
         out = np.empty_like(p)
         _native.check(self._lib.bn254_g2_mul_batch(self._h, _p(p), _p(k), _p(out), p.shape[0]))
+        return out
+
+    def g1_msm_batch(self, p, k, offsets):
+        """out[j] = normalize(sum of p[i] * k[i] over i in [offsets[j], offsets[j+1])) -> (m, 12) uint64; an empty or cancelling
+        segment gives G1::zero() = (0, 1, 0); ONE inversion per segment (include/bn254_hip.h bn254_g1_msm_batch)"""
+        p, k, o, out = _msm_args(p, k, offsets, G1_WORDS)
+        _native.check(self._lib.bn254_g1_msm_batch(self._h, _p(p), _p(k), _p(o), o.size - 1, _p(out)))
+        return out
+
+    def g2_msm_batch(self, p, k, offsets):
+        """the same over G2 -> (m, 24) uint64"""
+        p, k, o, out = _msm_args(p, k, offsets, G2_WORDS)
+        _native.check(self._lib.bn254_g2_msm_batch(self._h, _p(p), _p(k), _p(o), o.size - 1, _p(out)))
         return out
 
     def g1_add_batch(self, a, b, negate_b=False):
@@ -331,6 +354,15 @@ class Engine:
         f = self._lib.bn254_g2_mul_batch_dev if normalize else self._lib.bn254_g2_mul_jacobian_dev
         _native.check(f(self._h, d_p, d_k, d_out, n, stream))
 
+    def g1_msm_batch_dev(self, d_p, d_k, offsets, d_out, stream=0):
+        """device pointers p, k, out (m points); `offsets` is a HOST sequence of m + 1 CSR offsets"""
+        o = _offsets(offsets)
+        _native.check(self._lib.bn254_g1_msm_batch_dev(self._h, d_p, d_k, _p(o), o.size - 1, d_out, stream))
+
+    def g2_msm_batch_dev(self, d_p, d_k, offsets, d_out, stream=0):
+        o = _offsets(offsets)
+        _native.check(self._lib.bn254_g2_msm_batch_dev(self._h, d_p, d_k, _p(o), o.size - 1, d_out, stream))
+
     def gt_mul_dev(self, d_a, d_b, d_out, n, stream=0):
         _native.check(self._lib.bn254_gt_mul_batch_dev(self._h, d_a, d_b, d_out, n, stream))
 
@@ -480,6 +512,17 @@ class MultiEngine:
         """Engine.pairing_product_batch with the segments sharded over the ranks (segment j on the rank whose pair shard holds offsets[j])"""
         p, q, o, out = _segment_args(p, q, offsets)
         _native.check(self._lib.bn254_pairing_product_batch_multi(self._h, _p(p), _p(q), _p(o), o.size - 1, _p(out)))
+        return out
+
+    def g1_msm_batch(self, p, k, offsets):
+        """Engine.g1_msm_batch with the segments sharded over the ranks (segment j on the rank whose term shard holds offsets[j])"""
+        p, k, o, out = _msm_args(p, k, offsets, G1_WORDS)
+        _native.check(self._lib.bn254_g1_msm_batch_multi(self._h, _p(p), _p(k), _p(o), o.size - 1, _p(out)))
+        return out
+
+    def g2_msm_batch(self, p, k, offsets):
+        p, k, o, out = _msm_args(p, k, offsets, G2_WORDS)
+        _native.check(self._lib.bn254_g2_msm_batch_multi(self._h, _p(p), _p(k), _p(o), o.size - 1, _p(out)))
         return out
 
     def g2_prepare(self, q):

@@ -101,6 +101,24 @@ inline std::vector<Gt> pairing_product_batch(const std::vector<G1> &p, const std
                                       out.size(), reinterpret_cast<bn_gt *>(out.data())));
     return out;
 }
+// out[j] = normalize(sum of p[i] * k[i] over the terms [offsets[j], offsets[j+1])) (CSR segments, offsets.size() = m + 1): many independent
+// multi-scalar multiplications in one call, ONE inversion per segment; an empty or cancelling segment gives G::zero()
+inline std::vector<G1> g1_msm_batch(const std::vector<G1> &p, const std::vector<Fr> &k, const std::vector<size_t> &offsets) {
+    if (p.size() != k.size()) throw std::invalid_argument("g1_msm_batch: length mismatch");
+    if (offsets.empty() || offsets.back() != p.size()) throw std::invalid_argument("g1_msm_batch: offsets must end at the term count");
+    std::vector<G1> out(offsets.size() - 1);
+    check(bn254_g1_msm_batch(nullptr, reinterpret_cast<const bn_g1 *>(p.data()), reinterpret_cast<const bn_fr *>(k.data()), offsets.data(),
+                             out.size(), reinterpret_cast<bn_g1 *>(out.data())));
+    return out;
+}
+inline std::vector<G2> g2_msm_batch(const std::vector<G2> &p, const std::vector<Fr> &k, const std::vector<size_t> &offsets) {
+    if (p.size() != k.size()) throw std::invalid_argument("g2_msm_batch: length mismatch");
+    if (offsets.empty() || offsets.back() != p.size()) throw std::invalid_argument("g2_msm_batch: offsets must end at the term count");
+    std::vector<G2> out(offsets.size() - 1);
+    check(bn254_g2_msm_batch(nullptr, reinterpret_cast<const bn_g2 *>(p.data()), reinterpret_cast<const bn_fr *>(k.data()), offsets.data(),
+                             out.size(), reinterpret_cast<bn_g2 *>(out.data())));
+    return out;
+}
 // ok[j] = (product of segment j == Gt::one()): the predicate of a block of pairing checks
 inline std::vector<bool> pairing_check_batch(const std::vector<G1> &p, const std::vector<G2> &q, const std::vector<size_t> &offsets) {
     const std::vector<Gt> r = pairing_product_batch(p, q, offsets);
@@ -173,6 +191,23 @@ public:
         std::vector<Gt> out(offsets.size() - 1);
         check(bn254_pairing_product_batch_multi(m_, reinterpret_cast<const bn_g1 *>(p.data()), reinterpret_cast<const bn_g2 *>(q.data()), offsets.data(),
                                                 out.size(), reinterpret_cast<bn_gt *>(out.data())));
+        return out;
+    }
+    // bn::g1_msm_batch / g2_msm_batch with the segments sharded over the GPUs (no exchange)
+    std::vector<G1> g1_msm_batch(const std::vector<G1> &p, const std::vector<Fr> &k, const std::vector<size_t> &offsets) {
+        if (p.size() != k.size()) throw std::invalid_argument("g1_msm_batch: length mismatch");
+        if (offsets.empty() || offsets.back() != p.size()) throw std::invalid_argument("g1_msm_batch: offsets must end at the term count");
+        std::vector<G1> out(offsets.size() - 1);
+        check(bn254_g1_msm_batch_multi(m_, reinterpret_cast<const bn_g1 *>(p.data()), reinterpret_cast<const bn_fr *>(k.data()), offsets.data(),
+                                       out.size(), reinterpret_cast<bn_g1 *>(out.data())));
+        return out;
+    }
+    std::vector<G2> g2_msm_batch(const std::vector<G2> &p, const std::vector<Fr> &k, const std::vector<size_t> &offsets) {
+        if (p.size() != k.size()) throw std::invalid_argument("g2_msm_batch: length mismatch");
+        if (offsets.empty() || offsets.back() != p.size()) throw std::invalid_argument("g2_msm_batch: offsets must end at the term count");
+        std::vector<G2> out(offsets.size() - 1);
+        check(bn254_g2_msm_batch_multi(m_, reinterpret_cast<const bn_g2 *>(p.data()), reinterpret_cast<const bn_fr *>(k.data()), offsets.data(),
+                                       out.size(), reinterpret_cast<bn_g2 *>(out.data())));
         return out;
     }
 };

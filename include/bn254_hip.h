@@ -19,6 +19,9 @@
  *   bn254_pairing_product_batch  out[j] = that fold over pairs [offsets[j], offsets[j+1])   shootout/main.rs:11-16 per segment, lib.rs:175-183
  *   bn254_g1_mul_batch     out[i] = normalize(p[i] * k[i])                          lib.rs:116-120,88-95, groups/mod.rs:250-270
  *   bn254_g2_mul_batch     same over G2                                             lib.rs:159-163,131-138
+ *   bn254_g1_msm_batch     out[j] = normalize(fold(G1::zero(), |acc, i| acc + p[i] * k[i])) over terms [offsets[j], offsets[j+1])
+ *                                                                                    lib.rs:103-120,88-95, groups/mod.rs:250-311
+ *   bn254_g2_msm_batch     same over G2                                             lib.rs:146-163,131-138
  *   bn254_g1/g2_add_batch  out[i] = a[i] + b[i] / a[i] - b[i] (raw Jacobian limbs)       lib.rs:103-114,146-157, groups/mod.rs:275-347
  *   bn254_g2_precompute    coeffs[i][0..102) = q[i].to_affine().precompute().coeffs   groups/mod.rs:557-588 (Q != infinity)
  *   bn254_pairing_prepared_batch  out[i] = final_exponentiation(prepared.miller_loop(p[i]))   groups/mod.rs:486-519,768
@@ -49,13 +52,15 @@
  *     slot: two callers with batches of up to one machine round (256 pairings per CU: 2^16 on an MI355X) run concurrently on two
  *     streams (the number of streams the GPU overlaps without loss), further callers and multi-chunk batches queue; every other
  *     entry point serialises its callers on the context (bn254_pairing_product_batch too, except when every segment holds one pair: then
- *     it IS bn254_pairing_batch).  Use one context per thread (or bn254_multi_*) for more overlap;
+ *     it IS bn254_pairing_batch; likewise bn254_g{1,2}_msm_batch, which are bn254_g{1,2}_mul_batch when every segment holds one term).
+ *     Use one context per thread (or bn254_multi_*) for more overlap;
  *     bn254_ctx_set_option is atomic, but set options before concurrent use: a call in flight may run some
  *     of its launches under the old and some under the new setting (same bytes either way);
  *   - the *_dev entry points are asynchronous on the caller's stream.  Context-owned scratch (the final-exponentiation table,
  *     the product workspace) is ordered across streams with events, so calls on different streams of one context are safe
  *     and serialise on that scratch; the caller still owns the ordering of its OWN buffers between streams.
- *     bn254_pairing_product_batch_dev reads its HOST `offsets` before it returns (the launches are planned from them).
+ *     bn254_pairing_product_batch_dev and bn254_g{1,2}_msm_batch_dev read their HOST `offsets` before they return (the launches are planned
+ *     from them); the term workspace, window tables and work list of bn254_g{1,2}_msm_batch_dev are such context-owned scratch.
  */
 #ifndef BN254_HIP_H
 #define BN254_HIP_H
@@ -165,6 +170,27 @@ int bn254_pairing_product(bn254_ctx *ctx, const bn_g1 *p, const bn_g2 *q, size_t
 int bn254_pairing_product_batch(bn254_ctx *ctx, const bn_g1 *p, const bn_g2 *q, const size_t *offsets, size_t m, bn_gt *out);
 int bn254_g1_mul_batch(bn254_ctx *ctx, const bn_g1 *p, const bn_fr *k, bn_g1 *out, size_t n);
 int bn254_g2_mul_batch(bn254_ctx *ctx, const bn_g2 *p, const bn_fr *k, bn_g2 *out, size_t n);
+/* Segmented multi-scalar multiplication: m independent linear combinations in one call - the IC sums of a block of Groth16 checks, a*P + b*Q,
+   random linear combinations of checks, aggregate keys.  Segments in CSR form: offsets[0..m] with offsets[0] == 0, non-decreasing,
+   n = offsets[m] terms, and
+       out[j] = normalize(fold(G::zero(), |acc, i| acc + p[i] * k[i])) over i in [offsets[j], offsets[j+1]),   j < m
+   (lib.rs:103-120,88-95 for G1, :146-163,131-138 for G2).  Compared after normalize() for the reason given above for scalar multiples, and
+   normalisation makes the image unique: bit-identical to the reference's fold whatever the order of additions.  A sum that is the point at
+   infinity (empty segment, all scalars zero, all points at infinity, terms that cancel) is G::zero() = (0, 1, 0).  Inputs as for
+   bn254_g{1,2}_mul_batch: trusted subgroup points in any Jacobian representation, canonical Montgomery Fr images.
+   How: terms in chunks of one launch of the multiplication kernels (2^20 G1 / 2^19 G2 terms; a segment that crosses a cut carries its partial
+   sum), each term by the GLV / GLS chain WITHOUT normalisation into a context-owned workspace, then a segmented fold with the complete
+   addition (pieces of at most 4 consecutive values per lane / lane pair, ceil(log4 L) levels for a segment of L terms) whose last level
+   normalises: ONE inversion per segment.  Every segment of length 1: exactly bn254_g{1,2}_mul_batch.  Workspace: one chunk of Jacobian
+   terms (96 / 192 bytes each), as much again for partial sums, the window tables of bn254_g{1,2}_mul_batch and 24 bytes of work
+   list per segment and per 4 terms.
+   Made for many short and medium segments (verifier workloads).  There is NO bucket (Pippenger) method here: ONE prover-sized segment
+   (2^20 terms) is computed correctly but at the cost of a full scalar-multiplication chain per term, and its fold levels run on ever
+   fewer lanes.
+   Errors (BN254_E_BAD_ARG, checked before any device is touched): offsets == NULL with m > 0, offsets[0] != 0, decreasing offsets,
+   n > 2^40, a NULL p / k (n > 0) or out.  m == 0 returns BN254_OK and writes nothing. */
+int bn254_g1_msm_batch(bn254_ctx *ctx, const bn_g1 *p, const bn_fr *k, const size_t *offsets, size_t m, bn_g1 *out);
+int bn254_g2_msm_batch(bn254_ctx *ctx, const bn_g2 *p, const bn_fr *k, const size_t *offsets, size_t m, bn_g2 *out);
 /* out[i] = a[i] + b[i]  (negate_b != 0: a[i] - b[i] = a[i] + (-b[i])): `Add`/`Sub` of lib.rs:103-114,146-157 over
    groups/mod.rs:275-347.  The reference's own formulas and branches (zero operands, equal points), so the Jacobian limbs
    returned are the reference's - no normalization involved.  `Neg` is 0 - b. */
@@ -248,6 +274,10 @@ int bn254_pairing_product_multi(bn254_multi *m, const bn_g1 *p, const bn_g2 *q, 
 /* bn254_pairing_product_batch over the ranks: segment j runs on the rank whose pair shard [n*g/G, n*(g+1)/G) holds offsets[j]
    (offsets[j] == n: the last rank), with all of its pairs.  No exchange. */
 int bn254_pairing_product_batch_multi(bn254_multi *mh, const bn_g1 *p, const bn_g2 *q, const size_t *offsets, size_t m, bn_gt *out);
+/* bn254_g{1,2}_msm_batch over the ranks by the same rule: segment j runs on the rank whose TERM shard [n*g/G, n*(g+1)/G) holds offsets[j]
+   (offsets[j] == n: the last rank), with all of its terms.  No exchange. */
+int bn254_g1_msm_batch_multi(bn254_multi *mh, const bn_g1 *p, const bn_fr *k, const size_t *offsets, size_t m, bn_g1 *out);
+int bn254_g2_msm_batch_multi(bn254_multi *mh, const bn_g2 *p, const bn_fr *k, const size_t *offsets, size_t m, bn_g2 *out);
 
 /* native prepared-G2 mode over the GPUs of the handle.  ONE point (nq == 1) is prepared on every rank's GPU and n pairings shard like
    bn254_pairing_batch_multi; nq > 1 points are sharded by the same rule ([nq*g/G, nq*(g+1)/G) on rank g) and then pair with exactly n == nq
@@ -307,6 +337,9 @@ int bn254_miller_product_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, s
 /* bn254_pairing_product_batch on device-resident p, q, out; `offsets` (m+1 entries) is HOST memory (the launches are planned from it) and
    may be freed on return */
 int bn254_pairing_product_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, const size_t *offsets, size_t m, void *d_out, void *stream);
+/* bn254_g{1,2}_msm_batch on device-resident p, k, out (m points); `offsets` (m+1 entries) is HOST memory and may be freed on return */
+int bn254_g1_msm_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, const size_t *offsets, size_t m, void *d_out, void *stream);
+int bn254_g2_msm_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, const size_t *offsets, size_t m, void *d_out, void *stream);
 int bn254_g2_precompute_dev(bn254_ctx *ctx, const void *d_q, void *d_coeffs, size_t n, void *stream);
 int bn254_miller_prepared_dev(bn254_ctx *ctx, const void *d_p, const void *d_coeffs, int shared, void *d_f, size_t n, void *stream);
 /* native prepared-G2 mode on device-resident inputs.  bn254_g2_prepare_dev allocates the handle's table (that part synchronises with the
@@ -339,7 +372,7 @@ int bn254_tile_dev(bn254_ctx *ctx, const void *d_record, size_t record_bytes, si
    accumulated duration and launch count per kernel since the last reset (this is what bench.py's roofline uses). */
 int bn254_profile_enable(bn254_ctx *ctx, int on);
 int bn254_profile_reset(bn254_ctx *ctx);
-/* kernel: "miller", "miller_shared", "miller_wave", "miller_quad", "pairing_wave", "final_exp", "final_exp_wave", "final_exp_quad", "exp_by_neg_z", "gt_product", "gt_tail", "gt_segment", "gt_tail_seg", "g1_mul", "g2_mul", "gt_mul", "gt_pow", "g2_precompute", "miller_prepared", "g2_prepare_native", "miller_native", "miller_native_shared", "wire_encode", "wire_decode", "gt_inverse", "g1_add", "g2_add".
+/* kernel: "miller", "miller_shared", "miller_wave", "miller_quad", "pairing_wave", "final_exp", "final_exp_wave", "final_exp_quad", "exp_by_neg_z", "gt_product", "gt_tail", "gt_segment", "gt_tail_seg", "g1_mul", "g2_mul", "gt_mul", "gt_pow", "g2_precompute", "miller_prepared", "g2_prepare_native", "miller_native", "miller_native_shared", "wire_encode", "wire_decode", "gt_inverse", "g1_add", "g2_add", "g1_msm_mul", "g1_msm_fold", "g2_msm_mul", "g2_msm_fold".
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);
 /* issue-rate ceiling of v_mad_u64_u32 (the 32x32+64 multiply-accumulate every field product is built from) at
