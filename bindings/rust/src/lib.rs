@@ -31,6 +31,8 @@ extern "C" {
     fn bn254_g2_prepared_bytes(prep: *const c_void) -> usize;
     fn bn254_pairing_prepared_native_batch(ctx: *mut c_void, p: *const G1, prep: *const c_void, out: *mut Gt, n: usize) -> c_int;
     fn bn254_pairing_product_prepared_native(ctx: *mut c_void, p: *const G1, prep: *const c_void, n: usize, out: *mut Gt) -> c_int;
+    fn bn254_pairing_product_batch_prepared_native(ctx: *mut c_void, p: *const G1, prep: *const c_void, q_index: *const usize, offsets: *const usize, m: usize, out: *mut Gt) -> c_int;
+    fn bn254_pairing_product_batch_prepared_native_dev(ctx: *mut c_void, d_p: *const c_void, prep: *const c_void, d_q_index: *const c_void, offsets: *const usize, m: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     // wire format of the crate's Encodable / Decodable impls (src/groups/mod.rs:143-205, src/fields/fp.rs:24-36), fixed-size records and the stream
     fn bn254_fr_encode_batch(ctx: *mut c_void, k: *const Fr, out: *mut u8, n: usize) -> c_int;
     fn bn254_fr_decode_batch(ctx: *mut c_void, bytes: *const u8, out: *mut Fr, status: *mut i32, n: usize) -> c_int;
@@ -279,6 +281,20 @@ impl PreparedG2 {
         let mut out = Gt::one();
         check(unsafe { bn254_pairing_product_prepared_native(std::ptr::null_mut(), p.as_ptr(), self.0, p.len(), &mut out) })?;
         Ok(out)
+    }
+    /// `out[j] = fold(Gt::one(), |acc, i| acc * bn::pairing(p[i], q[q_index[i]]))` over the pairs `offsets[j]..offsets[j + 1]`: `pairing_product_batch`
+    /// with the G2 side prepared, ONE final exponentiation per segment.  `q_index: None`: pair `i` uses point `i` (a one-point handle: point 0)
+    pub fn pairing_product_batch(&self, p: &[G1], q_index: Option<&[usize]>, offsets: &[usize]) -> Result<Vec<Gt>, GpuError> {
+        assert!(!offsets.is_empty() && offsets[offsets.len() - 1] == p.len());
+        if let Some(qi) = q_index { assert_eq!(qi.len(), p.len()); }
+        let mut out = vec![Gt::one(); offsets.len() - 1];
+        let qi = q_index.map_or(std::ptr::null(), |q| q.as_ptr());
+        check(unsafe { bn254_pairing_product_batch_prepared_native(std::ptr::null_mut(), p.as_ptr(), self.0, qi, offsets.as_ptr(), out.len(), out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+    /// `ok[j]` = (product of segment j == `Gt::one()`): a block of Groth16 / EIP-197-style checks against prepared points
+    pub fn pairing_check_batch(&self, p: &[G1], q_index: Option<&[usize]>, offsets: &[usize]) -> Result<Vec<bool>, GpuError> {
+        Ok(self.pairing_product_batch(p, q_index, offsets)?.into_iter().map(|g| g == Gt::one()).collect())
     }
 }
 impl Drop for PreparedG2 {

@@ -271,5 +271,33 @@ class PreparedG2:
         P = np.stack([p.limbs for p in ps]) if not isinstance(ps, np.ndarray) else ps
         return Gt(self._e.pairing_product_prepared_native(P, self._h))
 
+    def _product_batch_limbs(self, segments, q_index, offsets):
+        if offsets is not None:                   # (n,12) array + per-pair indices (or None) + CSR offsets
+            P = np.asarray(segments, np.uint64).reshape(-1, G1_WORDS)
+            return self._e.pairing_product_batch_prepared_native(P, self._h, np.asarray(offsets, np.uint64), q_index)
+        if q_index is not None:
+            raise ValueError("q_index is only taken together with offsets (segments carry their indices: (G1, index))")
+        segments = [list(s) for s in segments]
+        offs = np.zeros(len(segments) + 1, np.uint64)
+        offs[1:] = np.cumsum([len(s) for s in segments], dtype=np.uint64) if segments else []
+        pairs = [pi for s in segments for pi in s]
+        n = len(self)
+        for _, i in pairs:
+            if not 0 <= int(i) < n:
+                raise ValueError(f"index {i} names no point of this handle ({n} points)")
+        P = np.stack([p.limbs for p, _ in pairs]) if pairs else np.zeros((0, G1_WORDS), np.uint64)
+        return self._e.pairing_product_batch_prepared_native(P, self._h, offs, np.array([int(i) for _, i in pairs], np.uint64))
+
+    def pairing_product_batch(self, segments, q_index=None, offsets=None):
+        """[fold(Gt::one(), acc * pairing(p, point i of this handle)) over the (p, i) of each segment] with ONE final exponentiation per segment -
+        pairing_product_batch with the G2 side prepared.  segments: a sequence of sequences of (G1, index) - an empty one gives Gt::one() -, or an
+        (n,12) uint64 array as `segments` plus CSR `offsets` (m + 1 entries) and `q_index` (n indices; None: pair i uses point i, every pair
+        point 0 of a one-point handle)."""
+        return [Gt(r) for r in self._product_batch_limbs(segments, q_index, offsets)]
+
+    def pairing_check_batch(self, segments, q_index=None, offsets=None):
+        """numpy bool array: product of segment j == Gt::one() - a block of Groth16 / EIP-197-style checks against prepared points"""
+        return (self._product_batch_limbs(segments, q_index, offsets) == Gt.one().limbs).all(axis=1)
+
     def close(self):
         self._h.close()

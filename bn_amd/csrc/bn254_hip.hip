@@ -446,15 +446,36 @@ bool seg_plan(const size_t *off, size_t m, size_t chunk_pairs, bool small, char 
 }  // namespace
 // the work lists: ONE copy per call through the context's pinned staging, which is rewritten only after its previous copy completed
 // (so the caller's `offsets` may be freed as soon as the call returns)
-static int bn_seg_upload(bn254_ctx *c, const std::vector<BnSegPiece> &pieces, hipStream_t s) {
+// (`miller`: the Miller pieces of bn254_pairing_product_batch_prepared_native, placed behind the fold's pieces in the same copy)
+static int bn_seg_upload(bn254_ctx *c, const std::vector<BnSegPiece> &pieces, hipStream_t s, const std::vector<BnMillerPiece> *miller = nullptr) {
     int rc;
-    const size_t bytes = pieces.size() * sizeof(BnSegPiece);
+    const size_t fold_bytes = pieces.size() * sizeof(BnSegPiece), bytes = fold_bytes + (miller ? miller->size() * sizeof(BnMillerPiece) : 0);
     if (c->seg_plan_ev) HIP_TRY(hipEventSynchronize(c->seg_plan_ev));
     else HIP_TRY(hipEventCreateWithFlags(&c->seg_plan_ev, hipEventDisableTiming));
     if ((rc = c->seg_plan_host.reserve(bytes)) || (rc = c->seg_plan.reserve(bytes))) return rc;
-    memcpy(c->seg_plan_host.p, pieces.data(), bytes);
+    if (fold_bytes) memcpy(c->seg_plan_host.p, pieces.data(), fold_bytes);
+    if (bytes > fold_bytes) memcpy((char *)c->seg_plan_host.p + fold_bytes, miller->data(), bytes - fold_bytes);
     HIP_TRY(hipMemcpyAsync(c->seg_plan.p, c->seg_plan_host.p, bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(c->seg_plan_ev, s));
+    return BN254_OK;
+}
+// what follows the Miller values of one chunk: the levels of its fold (or the ragged tail), then the carry into the next chunk
+static int bn_seg_fold_chunk(bn254_ctx *c, const SegChunk &ch, const BnSegPiece *list, size_t chunk_pairs, size_t pb, hipStream_t s) {
+    int rc;
+    for (const SegLaunch &l : ch.launches) {
+        if (l.tail) {
+            BnScope sc(c, s, "gt_tail_seg");
+            rc = bn254_launch_gt_tail_seg_W(list + l.first, l.count, s);
+        } else {
+            rc = bn_for_parts(l.count, BN_LAUNCH_MAX, [&](size_t lo, size_t cnt) -> int {
+                BnScope sc(c, s, "gt_segment");
+                return bn254_launch_gt_fold_seg_B(list + l.first + lo, cnt, s);
+            });
+        }
+        if (rc) return rc;
+    }
+    if (ch.carry_out)                 // the segment that goes on: its partial product becomes value slot 0 of the next chunk
+        HIP_TRY(hipMemcpyAsync(c->ws.p, (char *)c->ws.p + (chunk_pairs + 1 + pb) * sizeof(bn_gt), sizeof(bn_gt), hipMemcpyDeviceToDevice, s));
     return BN254_OK;
 }
 // out[j] = final_exponentiation(prod of the Miller values of pairs [off[j], off[j+1])) for j < m; off is HOST memory; scratch guard held by the caller
@@ -477,22 +498,90 @@ static int bn_launch_product_batch(bn254_ctx *c, const void *d_p, const void *d_
             rc = bn_launch_miller(c, (const char *)d_p + ch.lo * sizeof(bn_g1), (const char *)d_q + ch.lo * sizeof(bn_g2), (char *)c->ws.p + sizeof(bn_gt), ch.hi - ch.lo, s, true);
             if (rc) return rc;
         }
-        for (const SegLaunch &l : ch.launches) {
-            if (l.tail) {
-                BnScope sc(c, s, "gt_tail_seg");
-                rc = bn254_launch_gt_tail_seg_W(list + l.first, l.count, s);
-            } else {
-                rc = bn_for_parts(l.count, BN_LAUNCH_MAX, [&](size_t lo, size_t cnt) -> int {
-                    BnScope sc(c, s, "gt_segment");
-                    return bn254_launch_gt_fold_seg_B(list + l.first + lo, cnt, s);
-                });
-            }
-            if (rc) return rc;
-        }
-        if (ch.carry_out)                 // the segment that goes on: its partial product becomes value slot 0 of the next chunk
-            HIP_TRY(hipMemcpyAsync(c->ws.p, (char *)c->ws.p + (chunk_pairs + 1 + pb) * sizeof(bn_gt), sizeof(bn_gt), hipMemcpyDeviceToDevice, s));
+        if ((rc = bn_seg_fold_chunk(c, ch, list, chunk_pairs, pb, s))) return rc;
     }
     return small ? BN254_OK : bn_launch_final_exp(c, d_out, d_out, m, s, nullptr);
+}
+
+// ---- batched multi-pairing over prepared points with per-pair indices (bn254_pairing_product_batch_prepared_native*)
+// Every segment of L pairs is cut into ceil(L / 4) PIECES of at most four consecutive pairs; a lane pair runs one piece on ONE Miller accumulator
+// over the native tables (bn254_miller_native_shared4_B<true>: the line products of its pairs, a quarter of the squarings) and writes one
+// un-exponentiated Fq12.  Pieces go out in sub-launches of at most one machine round of lane pairs.
+//   * no segment above four pairs (a block of Groth16 checks): piece j IS segment j (an empty segment is a piece of no pairs, whose four
+//     identity columns give exactly one) - the kernel writes out[j], the final exponentiation runs in place, nothing is folded;
+//   * otherwise the pieces' values are the values of a segmented Fq12 fold whose segment j holds ceil(L_j / 4) of them: the plan of
+//     bn254_pairing_product_batch (seg_plan: chunks of one round of VALUES, carry, levels of BN_SEG_FOLD) over the derived offsets.
+// Small calls (n <= min(the handle's small_max, BN254_OPT_WAVE_PAIRING_MAX)): the general path on the points kept with the handle, gathered by
+// index into the workspace (q_index == NULL: used in place), like the other prepared entry points.
+// d_qi: 64-bit indices in device memory or NULL; off is HOST memory; scratch guard held by the caller.
+static_assert(sizeof(size_t) == sizeof(uint64_t), "q_index travels to the device as 64-bit words");
+static int bn_launch_product_batch_prepared(bn254_ctx *c, const void *d_p, const bn254_g2_prepared *h, const void *d_qi, const size_t *off, size_t m, void *d_out, hipStream_t s) {
+    const size_t n = off[m], chunk_pairs = bn_round_pairs(c);
+    const int shared = h->nq == 1;
+    int rc;
+    const size_t small = h->small_max < bn_wave_pairing_max(c) ? h->small_max : bn_wave_pairing_max(c);
+    if (n <= small) {
+        const void *q = h->q;
+        if (d_qi && n) {
+            const size_t q_at = seg_ws_values(chunk_pairs) * sizeof(bn_gt);          // behind everything bn_launch_product_batch keeps in the workspace
+            if ((rc = c->ws.reserve(q_at + n * sizeof(bn_g2)))) return rc;
+            BnScope sc(c, s, "g2_gather");
+            if ((rc = bn254_launch_gather_K(h->q, shared ? h->small_max : h->nq, sizeof(bn_g2), d_qi, n, (char *)c->ws.p + q_at, s))) return rc;
+            q = (const char *)c->ws.p + q_at;
+        }
+        return bn_launch_product_batch(c, d_p, q, off, m, d_out, s);
+    }
+    size_t longest = 0;
+    for (size_t j = 0; j < m; ++j) longest = std::max(longest, off[j + 1] - off[j]);
+    const bool direct = longest <= 4;
+    // the Miller pieces in launch order, `first` absolute until the sub-launches are cut
+    std::vector<size_t> first;
+    std::vector<BnMillerPiece> mp;
+    std::vector<size_t> voff;                     // derived offsets: values per segment
+    if (direct) {
+        first.reserve(m); mp.reserve(m);
+        for (size_t j = 0; j < m; ++j) { first.push_back(off[j]); mp.push_back({0u, (uint32_t)(off[j + 1] - off[j])}); }
+    } else {
+        voff.assign(m + 1, 0);
+        for (size_t j = 0; j < m; ++j) {
+            const size_t L = off[j + 1] - off[j];
+            for (size_t k = 0; k < L; k += 4) { first.push_back(off[j] + k); mp.push_back({0u, (uint32_t)std::min<size_t>(4, L - k)}); }
+            voff[j + 1] = first.size();
+        }
+    }
+    std::vector<BnSegPiece> pieces;
+    std::vector<SegChunk> chunks;
+    if (direct) chunks.push_back({0, m, false, {}});
+    else {
+        if ((rc = c->ws.reserve(seg_ws_values(chunk_pairs) * sizeof(bn_gt)))) return rc;
+        if (!seg_plan(voff.data(), m, chunk_pairs, false, (char *)c->ws.p, (char *)d_out, pieces, chunks)) return BN254_E_INTERNAL;
+    }
+    // sub-launches: at most one round of lane pairs each, never across a chunk
+    struct Sub { size_t lo, cnt, base; char *out; };
+    std::vector<std::vector<Sub>> subs(chunks.size());
+    for (size_t ci = 0; ci < chunks.size(); ++ci) {
+        const SegChunk &ch = chunks[ci];
+        const size_t step = ch.hi > ch.lo ? bn_sub_launch(c, ch.hi - ch.lo) : 1;
+        for (size_t lo = ch.lo; lo < ch.hi; lo += step) {
+            const size_t cnt = std::min(step, ch.hi - lo), base = first[lo];
+            for (size_t k = lo; k < lo + cnt; ++k) mp[k].first = (uint32_t)(first[k] - base);
+            subs[ci].push_back({lo, cnt, base, direct ? (char *)d_out + lo * sizeof(bn_gt) : (char *)c->ws.p + (1 + lo - ch.lo) * sizeof(bn_gt)});
+        }
+    }
+    if ((rc = bn_seg_upload(c, pieces, s, &mp))) return rc;
+    const BnSegPiece *list = (const BnSegPiece *)c->seg_plan.p;
+    const BnMillerPiece *mlist = (const BnMillerPiece *)((const char *)c->seg_plan.p + pieces.size() * sizeof(BnSegPiece));
+    const size_t pb = seg_partials_max(chunk_pairs);
+    for (size_t ci = 0; ci < chunks.size(); ++ci) {
+        for (const Sub &u : subs[ci]) {
+            BnScope sc(c, s, "miller_native_seg");
+            rc = bn254_launch_miller_native_seg_B((const char *)d_p + u.base * sizeof(bn_g1), h->table, h->inf, h->nq, d_qi && n ? (const char *)d_qi + u.base * sizeof(uint64_t) : nullptr,
+                                                  shared ? 0 : u.base, shared, mlist + u.lo, u.cnt, u.out, s);
+            if (rc) return rc;
+        }
+        if (!direct && (rc = bn_seg_fold_chunk(c, chunks[ci], list, chunk_pairs, pb, s))) return rc;
+    }
+    return bn_launch_final_exp(c, d_out, d_out, m, s, nullptr);
 }
 
 // ---- segmented multi-scalar multiplication: out[j] = normalize(sum of p[i] * k[i] over i in [off[j], off[j+1])) (bn254_g{1,2}_msm_batch*)
@@ -726,6 +815,29 @@ int bn254_pairing_product_batch_dev(bn254_ctx *ctx, const void *d_p, const void 
     hipStream_t s = (hipStream_t)stream;
     BnScratchGuard g(ctx, s); if (g.rc) return g.rc;
     return bn_no_throw([&] { return bn_launch_product_batch(ctx, d_p, d_q, offsets, m, d_out, s); });
+}
+// argument checks of bn254_pairing_product_batch_prepared_native* for m > 0 that need no device: the CSR rules, the handle, and - where the
+// indices are host memory - every index
+// (`indexed`: the pairs carry indices; `q_index`: those indices where the host can read them)
+static int bn_prep_seg_check(const void *p, const bn254_g2_prepared *prep, bool indexed, const size_t *q_index, const size_t *offsets, size_t m, const void *out) {
+    if (int e = bn_seg_check(p, p, offsets, m, out)) return e;
+    if (!prep) return BN254_E_BAD_ARG;
+    const size_t n = offsets[m];
+    if (!indexed) return prep->nq != 1 && n > prep->nq ? BN254_E_BAD_ARG : BN254_OK;
+    for (size_t i = 0; q_index && i < n; ++i)
+        if (q_index[i] >= prep->nq) return BN254_E_BAD_ARG;
+    return BN254_OK;
+}
+int bn254_pairing_product_batch_prepared_native_dev(bn254_ctx *ctx, const void *d_p, const bn254_g2_prepared *prep, const void *d_q_index, const size_t *offsets, size_t m, void *d_out, void *stream) {
+    if (m == 0) return BN254_OK;
+    if (int e = bn_prep_seg_check(d_p, prep, d_q_index != nullptr, nullptr, offsets, m, d_out)) return e;          // before any device lookup
+    int rc = bn_get_ctx(ctx); if (rc) return rc;
+    if (prep->device != ctx->device) return BN254_E_BAD_ARG;
+    BnDeviceGuard dev_guard;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    BnScratchGuard g(ctx, s); if (g.rc) return g.rc;
+    return bn_no_throw([&] { return bn_launch_product_batch_prepared(ctx, d_p, prep, d_q_index, offsets, m, d_out, s); });
 }
 static int mul_dev(bn254_ctx *ctx, int g, const void *d_p, const void *d_k, void *d_out, size_t n, void *stream, int normalize) {
     BN_DEV_PROLOGUE(!d_p || !d_k || !d_out, BN_N_MAX);
@@ -1060,6 +1172,23 @@ int bn254_pairing_product_prepared_native(bn254_ctx *ctx, const bn_g1 *p, const 
     rc = bn254_miller_product_prepared_native_dev(ctx, dp.p, prep, 0, n, dpart.p, ctx->stream); if (rc) return rc;
     rc = bn254_final_exp_batch_dev(ctx, dpart.p, dpart.p, 1, ctx->stream); if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, dpart.p, sizeof(bn_gt), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return BN254_OK;
+}
+int bn254_pairing_product_batch_prepared_native(bn254_ctx *ctx, const bn_g1 *p, const bn254_g2_prepared *prep, const size_t *q_index, const size_t *offsets, size_t m, bn_gt *out) {
+    if (m == 0) return BN254_OK;
+    if (int e = bn_prep_seg_check(p, prep, q_index != nullptr, q_index, offsets, m, out)) return e;                // before any device lookup
+    const size_t n = offsets[m];
+    BN_HOST_PROLOGUE();
+    if (prep->device != ctx->device) return BN254_E_BAD_ARG;
+    BnBuf &dp = ctx->stage[0], &dqi = ctx->stage[1], &dout = ctx->stage[2];
+    if ((rc = dp.reserve(n * sizeof(bn_g1))) || (rc = dqi.reserve(n * sizeof(uint64_t))) || (rc = dout.reserve(m * sizeof(bn_gt)))) return rc;
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(dp.p, p, n * sizeof(bn_g1), hipMemcpyHostToDevice, ctx->stream));
+        if (q_index) HIP_TRY(hipMemcpyAsync(dqi.p, q_index, n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = bn254_pairing_product_batch_prepared_native_dev(ctx, dp.p, prep, q_index ? dqi.p : nullptr, offsets, m, dout.p, ctx->stream); if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, dout.p, m * sizeof(bn_gt), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return BN254_OK;
 }

@@ -432,23 +432,33 @@ __global__ void __launch_bounds__(BLOCK) bn254_native_identity_B(uint4 *table, u
 // ---- the multi-pairing over native tables (pairing.hpp miller_loop_native_shared): M pairs per lane pair on ONE accumulator, pair i of lane pair
 // t is pairing t + i ceil(n / M) of the launch and reads the table of point q_lo + t + i ceil(n / M) (shared: of point 0).  Per pair in LDS: sigma, tau = 18 dwords
 // per lane ([pair][dword][lane]; 18 KB per workgroup at M = 4, eight workgroups per CU = 147 of the 160 KB).  There is no per-step point state.
-template <int M>
+// SEG (the segmented, index-driven instance below): every pair names its own column, so the M column numbers are per-lane STATE - kept in LDS behind
+// the pair's (sigma, tau) record (one more dword per lane and pair: 19 KB per workgroup at M = 4, eight workgroups per CU = 152 of the 160 KB) and
+// read back with the line's sigma; col0, ident, infmask, col_step are unused there (an infinite or missing pair has the identity column stored).
+// The column sits INSIDE its pair's record ([pair][19 dwords][lane]) so that one address register serves both: with the four columns behind the
+// records (a second address per lane) the instance came out at 256 VGPRs + 2 spilled, with this layout at 256 and none (tools/kernel_meta.py).
+template <int M, bool SEG = false>
 struct NativeSharedMem {
     const uint4 *base;
     uint32_t col0, ident, stride, infmask;   // column of pair 0, the identity column (both incl. the lane's parity; shared: col0 for every pair)
     uint32_t *lds;
     int line, cur, col_step;
     mutable Fe xbu, xbv;
-    __device__ __forceinline__ uint32_t col() const { return ((infmask >> cur) & 1u) ? ident : col0 + (uint32_t)(cur * col_step); }
+    static constexpr int REC = SEG ? 19 : 18;   // dwords per pair in LDS: sigma, tau (and the column)
+    __device__ __forceinline__ uint32_t col() const {
+        if constexpr (SEG) return lds[(cur * REC + 18) * BLOCK];
+        else return ((infmask >> cur) & 1u) ? ident : col0 + (uint32_t)(cur * col_step);
+    }
+    __device__ __forceinline__ void st_col(int pair, uint32_t c) const { lds[(pair * REC + 18) * BLOCK] = c; }
     __device__ __forceinline__ Fe ld_lds(int slot) const {
         Fe v;
 #pragma unroll
-        for (int i = 0; i < 9; ++i) v.l[i] = lds[((cur * 2 + slot) * 9 + i) * BLOCK];
+        for (int i = 0; i < 9; ++i) v.l[i] = lds[(cur * REC + slot * 9 + i) * BLOCK];
         return v;
     }
     __device__ __forceinline__ void st_lds(int pair, int slot, const Fe &v) const {
 #pragma unroll
-        for (int i = 0; i < 9; ++i) lds[((pair * 2 + slot) * 9 + i) * BLOCK] = v.l[i];
+        for (int i = 0; i < 9; ++i) lds[(pair * REC + slot * 9 + i) * BLOCK] = v.l[i];
     }
     __device__ __forceinline__ void set_line(int l, int i) { line = l; cur = i; }
     __device__ __forceinline__ Fq2BPrep<Fe> x0() const {
@@ -498,8 +508,57 @@ __device__ __forceinline__ void miller_native_shared_body(const uint32_t *g1, co
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BN_WAVES, BN_WAVES))) bn254_miller_native_shared2_B(const uint32_t *g1, const uint4 *table, uint32_t stride, uint32_t q_lo, int shared, const uint32_t *q_inf, uint32_t *f_out, uint32_t n) {
     miller_native_shared_body<2>(g1, table, stride, q_lo, shared, q_inf, f_out, n);
 }
-__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BN_WAVES, BN_WAVES))) bn254_miller_native_shared4_B(const uint32_t *g1, const uint4 *table, uint32_t stride, uint32_t q_lo, int shared, const uint32_t *q_inf, uint32_t *f_out, uint32_t n) {
-    miller_native_shared_body<4>(g1, table, stride, q_lo, shared, q_inf, f_out, n);
+// ---- the SEGMENTED multi-pairing over native tables (bn254_pairing_product_batch_prepared_native*): many independent products, every pair naming its
+// prepared point by index.  The host cuts every segment into pieces of at most M consecutive pairs (BnMillerPiece); lane pair t takes piece t and
+// writes ONE un-exponentiated Fq12: the product of the piece's Miller values.  Pair `first + i` reads the table of point q_index[first + i]
+// (q_index == NULL: point q_lo + first + i, or point 0 with `shared`); a pair the piece does not have (i >= cnt - a piece of an EMPTY segment has
+// none), a pair with a point at infinity on either side and an index beyond the table's points all take the identity column with sigma = 1,
+// tau = 0, i.e. the factor one - which is also what keeps an out-of-range index of a device-resident q_index inside the table.
+// Coalescing: for a fixed i the lane pairs of a wave should meet ADJACENT columns or ONE column, as in the plain kernel above.  A block of Groth16
+// checks whose per-proof points sit at consecutive indices (pair 0 of check j: point 3 + j) and whose other pairs name the key's three points
+// has exactly that: pair 0 reads a coalesced row, pairs 1-3 are broadcasts out of the L1 / L2.  Arbitrary indices are correct, just slower
+// (every lane pair fetches its own 2 x 16 bytes of a row).
+// `g1`, `q_index`, `f_out` and the pieces' `first` are relative to the sub-launch (32-bit offsets).  A missing pair's P is read from the first 96
+// bytes of the table - always there, never used (its sigma, tau are replaced) - so that both lanes stay active without a valid pair to clamp to.
+template <int M>
+__device__ __forceinline__ void miller_native_seg_body(const uint32_t *g1, const uint4 *table, uint32_t stride, uint32_t q_lo, int shared, const uint32_t *q_inf, uint32_t *f_out, uint32_t n,
+                                                       const uint64_t *q_index, const BnMillerPiece *pieces) {
+    const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
+    const uint32_t lp = t >> 1;
+    const bool live = lp < n;
+    const uint32_t piece = live ? lp : n - 1;                      // lanes beyond the list repeat the last piece (both lanes of a pair stay active for the DPP exchanges)
+    const uint32_t parity = threadIdx.x & 1u, nq = (stride - 2u) >> 1;
+    __shared__ uint32_t park[(M * 2 * 9 + M) * BLOCK];
+    NativeSharedMem<M, true> src = {table, 0u, 0u, stride, 0u, park + threadIdx.x, 0, 0, 0, {}, {}};
+#pragma unroll 1
+    for (int i = 0; i < M; ++i) {
+        const BnMillerPiece pc = pieces[piece];                     // re-read per pair (8 bytes out of the L1): two VGPRs less across the inversion below
+        const bool have = (uint32_t)i < pc.cnt;
+        const uint32_t pair = pc.first + (uint32_t)i;
+        const uint32_t *w1 = have ? g1 + 24u * pair : (const uint32_t *)table;
+        uint32_t qi = nq;
+        if (have) {
+            if (q_index) { const uint64_t v = q_index[pair]; qi = v < (uint64_t)nq ? (uint32_t)v : nq; }
+            else if (shared) qi = 0u;
+            else { const uint64_t v = (uint64_t)q_lo + pair; qi = v < (uint64_t)nq ? (uint32_t)v : nq; }
+        }
+        bool inf = qi >= nq || words_all_zero(w1 + 16, 8);                                 // groups/mod.rs:766
+        inf = inf || q_inf[qi >= nq ? 0u : qi] != 0u;
+        src.st_col(i, (inf ? 2u * nq : 2u * qi) + parity);
+        const PNative<Fe> pn = p_native(f2_scalar_load((const F2 *)nullptr, w1), f2_scalar_load((const F2 *)nullptr, w1 + 8), f2_scalar_load((const F2 *)nullptr, w1 + 16));
+        Fe one, zero;
+        p_native_identity(one, zero);
+        src.st_lds(i, 0, fe_select(inf, pn.sigma, one)); src.st_lds(i, 1, fe_select(inf, pn.tau, zero));
+    }
+    Fq12<F2> f = miller_loop_native_shared<M, F2>(src);
+    if (live) f12_store(f, f_out + 96u * lp);
+}
+// SEG = false: the plain kernel (q_index, pieces unused).  SEG = true: n PIECES, one per lane pair (miller_native_seg_body).
+template <bool SEG>
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(BN_WAVES, BN_WAVES))) bn254_miller_native_shared4_B(const uint32_t *g1, const uint4 *table, uint32_t stride, uint32_t q_lo, int shared, const uint32_t *q_inf, uint32_t *f_out, uint32_t n,
+                                                                                                                                const uint64_t *q_index, const BnMillerPiece *pieces) {
+    if constexpr (SEG) miller_native_seg_body<4>(g1, table, stride, q_lo, shared, q_inf, f_out, n, q_index, pieces);
+    else miller_native_shared_body<4>(g1, table, stride, q_lo, shared, q_inf, f_out, n);
 }
 
 // out[i] = a[i] * b[i]   (Gt * Gt, lib.rs:175-179 -> fq12.rs:295-307)
@@ -673,8 +732,20 @@ int bn254_launch_miller_native_B(const void *p, const void *table, const void *q
 int bn254_launch_miller_native_shared_B(const void *p, const void *table, const void *q_inf, size_t nq, size_t q_lo, int shared, void *f, size_t n, int m, hipStream_t s) {
     const size_t groups = (n + m - 1) / m;
     unsigned grid = (unsigned)((2 * groups + BLOCK - 1) / BLOCK);
-    hipLaunchKernelGGL(m == 4 ? bn254_miller_native_shared4_B : bn254_miller_native_shared2_B, dim3(grid), dim3(BLOCK), 0, s, (const uint32_t *)p, (const uint4 *)table,
-                       (uint32_t)(2 * nq + 2), (uint32_t)q_lo, shared ? 1 : 0, (const uint32_t *)q_inf, (uint32_t *)f, (uint32_t)n);
+    if (m == 4)
+        hipLaunchKernelGGL(bn254_miller_native_shared4_B<false>, dim3(grid), dim3(BLOCK), 0, s, (const uint32_t *)p, (const uint4 *)table, (uint32_t)(2 * nq + 2), (uint32_t)q_lo, shared ? 1 : 0,
+                           (const uint32_t *)q_inf, (uint32_t *)f, (uint32_t)n, (const uint64_t *)nullptr, (const BnMillerPiece *)nullptr);
+    else
+        hipLaunchKernelGGL(bn254_miller_native_shared2_B, dim3(grid), dim3(BLOCK), 0, s, (const uint32_t *)p, (const uint4 *)table, (uint32_t)(2 * nq + 2), (uint32_t)q_lo, shared ? 1 : 0,
+                           (const uint32_t *)q_inf, (uint32_t *)f, (uint32_t)n);
+    return (int)hipGetLastError();
+}
+// the segmented instance: `count` pieces (device memory; `first` relative to p / q_index), one per lane pair, value t -> f[t].  q_index: 64-bit point
+// numbers per pair or NULL (pair i: point q_lo + i, or point 0 with `shared`)
+int bn254_launch_miller_native_seg_B(const void *p, const void *table, const void *q_inf, size_t nq, const void *q_index, size_t q_lo, int shared, const void *pieces, size_t count, void *f, hipStream_t s) {
+    unsigned grid = (unsigned)((2 * count + BLOCK - 1) / BLOCK);
+    hipLaunchKernelGGL(bn254_miller_native_shared4_B<true>, dim3(grid), dim3(BLOCK), 0, s, (const uint32_t *)p, (const uint4 *)table, (uint32_t)(2 * nq + 2), (uint32_t)q_lo, shared ? 1 : 0,
+                       (const uint32_t *)q_inf, (uint32_t *)f, (uint32_t)count, (const uint64_t *)q_index, (const BnMillerPiece *)pieces);
     return (int)hipGetLastError();
 }
 int bn254_launch_gt_mul_B(const void *a, const void *b, void *out, size_t n, hipStream_t s) {

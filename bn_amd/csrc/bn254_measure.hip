@@ -1,5 +1,6 @@
 // Measurement and synthetic-input kernels of the BN254 engine (include/bn254_hip.h "measurement" / "synthetic benchmark inputs"): nothing on
-// the pairing path calls into this unit.
+// the pairing path calls into this unit, except that the record-copy kernel has a gather instance (bn254_launch_gather_K) which the small
+// route of bn254_pairing_product_batch_prepared_native uses to line up the G2 points its pairs name.
 //   * bn254_ubench_mac32(_ex): the v_mad_u64_u32 issue-rate microbenchmark behind bench.py's same-run `roofline.peak` (tools/ubench.hip is the
 //     long form; the multiplier's rate depends on its DATA - profiles/r04_ubench_mad_data_dependence.txt -, hence the operand-width argument:
 //     32 random bits for `peak`, the engine's own 29-bit limbs for `peak_at_kernel_occupancy`);
@@ -84,9 +85,19 @@ __global__ void __launch_bounds__(64) bn254_synthetic_scalars_k(uint64_t lo, uin
     for (int i = 0; i < 8; ++i) out[8u * j + i] = ge ? d[i] : s[i];
 }
 // out[i] = src[0]  (tiles one point/record of `words` u32 over n records: the generator bases of the synthetic inputs)
-__global__ void __launch_bounds__(256) bn254_tile_k(const uint32_t *src, uint32_t words, uint64_t total, uint32_t *out) {
+// GATHER: out[i] = src[index[i]] - record i of the output is record index[i] of the `records` source records, or all zero (for a point: z = 0,
+// the point at infinity) when the index is out of range.  The small route of bn254_pairing_product_batch_prepared_native: the G2 points a
+// handle keeps, gathered by the pairs' indices for the general kernels.
+template <bool GATHER>
+__global__ void __launch_bounds__(256) bn254_tile_k(const uint32_t *src, uint32_t words, uint64_t total, uint32_t *out, const uint64_t *index, uint64_t records) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < total) out[i] = src[i % words];
+    if (i >= total) return;
+    if constexpr (GATHER) {
+        const uint64_t r = index[i / words];
+        out[i] = r < records ? src[r * words + i % words] : 0u;
+    } else {
+        out[i] = src[i % words];
+    }
 }
 
 }  // namespace
@@ -138,7 +149,15 @@ int bn254_tile_dev(bn254_ctx *ctx, const void *d_record, size_t record_bytes, si
     if (!d_record || !d_out || record_bytes == 0 || record_bytes % 4) return BN254_E_BAD_ARG;
     HIP_TRY(hipSetDevice(ctx->device));
     const uint64_t total = (uint64_t)n * (record_bytes / 4);
-    hipLaunchKernelGGL(bn254_tile_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint32_t *)d_record, (uint32_t)(record_bytes / 4), total, (uint32_t *)d_out);
+    hipLaunchKernelGGL(bn254_tile_k<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint32_t *)d_record, (uint32_t)(record_bytes / 4), total, (uint32_t *)d_out,
+                       (const uint64_t *)nullptr, (uint64_t)0);
+    return (int)hipGetLastError();
+}
+// d_out[i] = d_records[d_index[i]] for i < n (records of record_bytes, a multiple of 4; an index >= `records` gives an all-zero record); n * record_bytes / 4 < 2^40
+int bn254_launch_gather_K(const void *d_records, size_t records, size_t record_bytes, const void *d_index, size_t n, void *d_out, hipStream_t s) {
+    const uint64_t total = (uint64_t)n * (record_bytes / 4);
+    hipLaunchKernelGGL(bn254_tile_k<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const uint32_t *)d_records, (uint32_t)(record_bytes / 4), total, (uint32_t *)d_out,
+                       (const uint64_t *)d_index, (uint64_t)records);
     return (int)hipGetLastError();
 }
 

@@ -86,7 +86,7 @@ struct bn254_ctx {
     hipEvent_t scratch_ev = nullptr;    // completion of the last launch that used ws / exp_tbl ...
     hipStream_t scratch_stream = nullptr;   // ... and the stream it ran on
     bool scratch_used = false;
-    BnBuf seg_plan;                     // work lists of the segmented fold (bn254_pairing_product_batch*), device side ...
+    BnBuf seg_plan;                     // work lists of the segmented fold (bn254_pairing_product_batch*, behind them the Miller pieces of ..._prepared_native), device side ...
     BnBuf seg_plan_host{nullptr, 0, true};  // ... and their pinned staging, rewritten only after seg_plan_ev (its last copy) completed
     hipEvent_t seg_plan_ev = nullptr;
     BnBuf stage[3];                     // device staging of the small host-buffer entry points
@@ -188,6 +188,7 @@ int bn254_native_lines_B(void);
 int bn254_launch_g2_prepare_native_B(const void *q, void *table, void *q_inf, size_t nq, hipStream_t s);
 int bn254_launch_miller_native_B(const void *p, const void *table, const void *q_inf, size_t nq, size_t q_lo, int shared, void *f, size_t n, hipStream_t s);
 int bn254_launch_miller_native_shared_B(const void *p, const void *table, const void *q_inf, size_t nq, size_t q_lo, int shared, void *f, size_t n, int m, hipStream_t s);
+int bn254_launch_miller_native_seg_B(const void *p, const void *table, const void *q_inf, size_t nq, const void *q_index, size_t q_lo, int shared, const void *pieces, size_t count, void *f, hipStream_t s);
 int bn254_launch_gt_mul_B(const void *a, const void *b, void *out, size_t n, hipStream_t s);
 int bn254_launch_gt_fold_seg_B(const void *pieces, size_t count, hipStream_t s);
 size_t bn254_gt_pow_table_bytes_B(size_t n);
@@ -214,4 +215,6 @@ int bn254_launch_g1_add_M(const void *a, const void *b, void *out, size_t n, int
 int bn254_launch_g2_add_M(const void *a, const void *b, void *out, size_t n, int negate_b, hipStream_t s);
 int bn254_launch_msm_mul_M(int g, const void *p, const void *k, void *out, size_t n, void *table, hipStream_t s);
 int bn254_launch_msm_fold_M(int g, const void *pieces, size_t count, hipStream_t s);
+// bn254_measure.hip
+int bn254_launch_gather_K(const void *d_records, size_t records, size_t record_bytes, const void *d_index, size_t n, void *d_out, hipStream_t s);
 }

@@ -27,6 +27,12 @@ struct BnSegPiece {
     uint32_t *dst;
     uint32_t cnt, last;
 };
+// one piece of the segmented multi-pairing over prepared points (bn254_pairing_product_batch_prepared_native): `cnt` <= 4 consecutive pairs from
+// pair `first` (relative to the sub-launch) share one Miller accumulator on a lane pair; cnt == 0 (an empty segment) gives one.
+// Built on the host, read by bn254_miller_native_shared4_B<true>.
+struct BnMillerPiece {
+    uint32_t first, cnt;
+};
 BN_FN bool words_all_zero(const uint32_t *w, int n) {
     uint32_t o = 0;
     for (int i = 0; i < n; ++i) o |= w[i];

@@ -234,6 +234,28 @@ class Engine:
         _native.check(self._lib.bn254_pairing_product_prepared_native(self._h, _p(p), prepared._h, p.shape[0], _p(out)))
         return out
 
+    def pairing_product_batch_prepared_native(self, p, prepared, offsets, q_index=None):
+        """out[j] = fold(Gt::one(), acc * pairing(p[i], point q_index[i] of `prepared`)) over i in [offsets[j], offsets[j+1]) -> (m, 48) uint64;
+        ONE final exponentiation per segment (include/bn254_hip.h bn254_pairing_product_batch_prepared_native).  q_index None: pair i uses
+        point i (every pair point 0 of a one-point handle)."""
+        p = _arr(p, G1_WORDS) if len(p) else np.zeros((0, G1_WORDS), np.uint64)
+        o = _offsets(offsets)
+        if int(o[-1]) != p.shape[0]:
+            raise ValueError(f"offsets[m] = {int(o[-1])} but {p.shape[0]} pairs were given")
+        qi = None
+        if q_index is not None:
+            qi = np.ascontiguousarray(q_index, dtype=np.uint64).reshape(-1)
+            if qi.size != p.shape[0]:
+                raise ValueError(f"q_index has {qi.size} entries for {p.shape[0]} pairs")
+        out = np.empty((o.size - 1, GT_WORDS), np.uint64)
+        _native.check(self._lib.bn254_pairing_product_batch_prepared_native(self._h, _p(p), prepared._h, None if qi is None else _p(qi), _p(o), o.size - 1, _p(out)))
+        return out
+
+    def pairing_product_batch_prepared_native_dev(self, d_p, prepared, offsets, d_out, d_q_index=None, stream=0):
+        """device pointers p, out (m values) and q_index (64-bit words, or None); `offsets` is a HOST sequence of m + 1 CSR offsets"""
+        o = _offsets(offsets)
+        _native.check(self._lib.bn254_pairing_product_batch_prepared_native_dev(self._h, d_p, prepared._h, d_q_index, _p(o), o.size - 1, d_out, stream))
+
     def miller_product_prepared_native_dev(self, d_p, prepared, n, d_partial, q_first=0, stream=0):
         _native.check(self._lib.bn254_miller_product_prepared_native_dev(self._h, d_p, prepared._h, q_first, n, d_partial, stream))
 

@@ -4,21 +4,25 @@ A proof (A: G1, B: G2, C: G1) with public inputs a_1 .. a_l is valid when
     e(A, B) = e(alpha, beta) * e(L, gamma) * e(C, delta),        L = IC[0] + sum a_i * IC[i]
 which is checked as  e(A, B) * e(-alpha, beta) * e(-L, gamma) * e(-C, delta) == 1.  A block takes three calls: one segmented multi-scalar
 multiplication for every L (bn_amd.g1_msm_batch, segment j: IC[0] * 1, IC[i] * a_ji), one batched subtraction for the negations and one
-batched multi-pairing check (bn_amd.pairing_check_batch, four pairs per proof)."""
+batched multi-pairing check (bn_amd.pairing_check_batch, four pairs per proof).  With prepared=True the G2 side of the block - the key's beta,
+gamma, delta and every proof's B - is prepared once on the device (Engine.g2_prepare) and the check runs over the native line tables
+(Engine.pairing_product_batch_prepared_native): the four pairs of a proof share one Miller accumulator."""
 import collections
 
 import numpy as np
 
-from .api import Fr, G1, default_engine, pairing_check_batch
+from .api import Fr, G1, Gt, default_engine, pairing_check_batch
 from .engine import G1_WORDS, G2_WORDS
 
 VerifyingKey = collections.namedtuple("VerifyingKey", "alpha_g1 beta_g2 gamma_g2 delta_g2 ic")
 VerifyingKey.__doc__ = "alpha_g1: G1; beta_g2, gamma_g2, delta_g2: G2; ic: l + 1 G1 points for l public inputs"
 
 
-def verify_batch(vk, proofs, public_inputs, engine=None):
+def verify_batch(vk, proofs, public_inputs, engine=None, prepared=False):
     """numpy bool array, one entry per proof.  proofs: sequence of (A: G1, B: G2, C: G1); public_inputs: one sequence of l = len(vk.ic) - 1
-    Fr per proof."""
+    Fr per proof.  prepared: run the pairing checks over ONE prepared handle [beta, gamma, delta, B_0 .. B_{m-1}] (check j: points 3 + j, 0,
+    1, 2), made for this block and closed before returning; same answers.  Worth it for blocks of many thousand proofs (2^16: 0.78 of the
+    default path's kernel time, preparation included); a small block pays ~1.3 ms of preparation for nothing (profiles/r09_product_batch_prepared.txt)."""
     e = engine or default_engine()
     proofs = list(proofs); public_inputs = [list(a) for a in public_inputs]
     m, l = len(proofs), len(vk.ic) - 1
@@ -40,4 +44,13 @@ def verify_batch(vk, proofs, public_inputs, engine=None):
     P[:, 1] = neg[0]; Q[:, 1] = vk.beta_g2.limbs
     P[:, 2] = neg[1:1 + m]; Q[:, 2] = vk.gamma_g2.limbs
     P[:, 3] = neg[1 + m:]; Q[:, 3] = vk.delta_g2.limbs
+    if prepared:
+        q_index = np.empty((m, 4), np.uint64)
+        q_index[:, 0] = 3 + np.arange(m, dtype=np.uint64); q_index[:, 1:] = np.arange(3, dtype=np.uint64)
+        h = e.g2_prepare(np.concatenate([vk.beta_g2.limbs[None], vk.gamma_g2.limbs[None], vk.delta_g2.limbs[None], Q[:, 0]]))
+        try:
+            out = e.pairing_product_batch_prepared_native(P.reshape(-1, G1_WORDS), h, np.arange(m + 1, dtype=np.uint64) * 4, q_index.reshape(-1))
+        finally:
+            h.close()
+        return (out == Gt.one().limbs).all(axis=1)
     return pairing_check_batch(P.reshape(-1, G1_WORDS), Q.reshape(-1, G2_WORDS), offsets=np.arange(m + 1, dtype=np.uint64) * 4, engine=e)

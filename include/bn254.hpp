@@ -152,6 +152,23 @@ public:
         check(bn254_pairing_product_prepared_native(nullptr, reinterpret_cast<const bn_g1 *>(p.data()), h_, p.size(), &r.v));
         return r;
     }
+    // out[j] = fold(Gt::one(), acc * bn::pairing(p[i], point q_index[i])) over the pairs [offsets[j], offsets[j+1]) (CSR segments, offsets.size() = m + 1):
+    // bn::pairing_product_batch with the G2 side prepared, ONE final exponentiation per segment.  q_index empty: pair i uses point i (one prepared point: point 0)
+    std::vector<Gt> pairing_product_batch(const std::vector<G1> &p, const std::vector<size_t> &q_index, const std::vector<size_t> &offsets) const {
+        if (!q_index.empty() && q_index.size() != p.size()) throw std::invalid_argument("pairing_product_batch: one index per pair");
+        if (offsets.empty() || offsets.back() != p.size()) throw std::invalid_argument("pairing_product_batch: offsets must end at the pair count");
+        std::vector<Gt> out(offsets.size() - 1);
+        check(bn254_pairing_product_batch_prepared_native(nullptr, reinterpret_cast<const bn_g1 *>(p.data()), h_, q_index.empty() ? nullptr : q_index.data(), offsets.data(),
+                                                          out.size(), reinterpret_cast<bn_gt *>(out.data())));
+        return out;
+    }
+    // ok[j] = (product of segment j == Gt::one()): a block of Groth16 / EIP-197-style checks against prepared points
+    std::vector<bool> pairing_check_batch(const std::vector<G1> &p, const std::vector<size_t> &q_index, const std::vector<size_t> &offsets) const {
+        const std::vector<Gt> r = pairing_product_batch(p, q_index, offsets);
+        std::vector<bool> ok(r.size());
+        for (size_t j = 0; j < r.size(); ++j) ok[j] = r[j] == Gt::one();
+        return ok;
+    }
 };
 
 // tunables of the default context (BN254_OPT_* of bn254_hip.h; value < 0 restores the default derived from the device)

@@ -17,6 +17,7 @@
  *   bn254_pairing_batch    out[i] = bn::pairing(p[i], q[i])                         lib.rs:181-183, groups/mod.rs:764-771
  *   bn254_pairing_product  fold(Gt::one(), |acc,(p,q)| acc * pairing(p,q))          shootout/main.rs:11-16, lib.rs:175-179
  *   bn254_pairing_product_batch  out[j] = that fold over pairs [offsets[j], offsets[j+1])   shootout/main.rs:11-16 per segment, lib.rs:175-183
+ *   bn254_pairing_product_batch_prepared_native  the same with the G2 side prepared: pair i against point q_index[i] of a bn254_g2_prepared handle
  *   bn254_g1_mul_batch     out[i] = normalize(p[i] * k[i])                          lib.rs:116-120,88-95, groups/mod.rs:250-270
  *   bn254_g2_mul_batch     same over G2                                             lib.rs:159-163,131-138
  *   bn254_g1_msm_batch     out[j] = normalize(fold(G1::zero(), |acc, i| acc + p[i] * k[i])) over terms [offsets[j], offsets[j+1])
@@ -53,6 +54,7 @@
  *     streams (the number of streams the GPU overlaps without loss), further callers and multi-chunk batches queue; every other
  *     entry point serialises its callers on the context (bn254_pairing_product_batch too, except when every segment holds one pair: then
  *     it IS bn254_pairing_batch; likewise bn254_g{1,2}_msm_batch, which are bn254_g{1,2}_mul_batch when every segment holds one term).
+ *     bn254_pairing_product_batch_prepared_native serialises on the context like them; its handle is immutable and shared freely.
  *     Use one context per thread (or bn254_multi_*) for more overlap;
  *     bn254_ctx_set_option is atomic, but set options before concurrent use: a call in flight may run some
  *     of its launches under the old and some under the new setting (same bytes either way);
@@ -60,7 +62,8 @@
  *     the product workspace) is ordered across streams with events, so calls on different streams of one context are safe
  *     and serialise on that scratch; the caller still owns the ordering of its OWN buffers between streams.
  *     bn254_pairing_product_batch_dev and bn254_g{1,2}_msm_batch_dev read their HOST `offsets` before they return (the launches are planned
- *     from them); the term workspace, window tables and work list of bn254_g{1,2}_msm_batch_dev are such context-owned scratch.
+ *     from them), and so does bn254_pairing_product_batch_prepared_native_dev (its `d_q_index` is device memory and read by the kernels only);
+ *     the term workspace, window tables and work list of bn254_g{1,2}_msm_batch_dev are such context-owned scratch.
  */
 #ifndef BN254_HIP_H
 #define BN254_HIP_H
@@ -230,6 +233,30 @@ int bn254_pairing_prepared_native_batch(bn254_ctx *ctx, const bn_g1 *p, const bn
    accumulator per lane pair: over native tables a pair has no per-step point state, so the shared loop is the line products plus a quarter of
    the squarings.  n == 0 gives Gt::one(); a point at infinity on either side contributes one (groups/mod.rs:766). */
 int bn254_pairing_product_prepared_native(bn254_ctx *ctx, const bn_g1 *p, const bn254_g2_prepared *prep, size_t n, bn_gt *out);
+/* Batched multi-pairing over prepared points with per-pair indices: m independent products in one call, every pair naming its prepared point -
+   a block of Groth16 checks whose verifying-key points (and, prepared per block, whose proof points) live in ONE handle.  Segments in CSR form
+   exactly as for bn254_pairing_product_batch (offsets[0] == 0, non-decreasing, n = offsets[m] pairs; an empty segment gives Gt::one();
+   m == 0 returns BN254_OK and writes nothing), and
+       out[j] = fold(Gt::one(), |acc, i| acc * pairing(p[i], point q_index[i] of prep)) over i in [offsets[j], offsets[j+1]),   j < m
+   (shootout/main.rs:11-16 per segment, lib.rs:175-183, with the G2 side prepared), bit-identical to that fold, ONE final exponentiation per
+   segment.  A point at infinity on either side contributes one (groups/mod.rs:766).
+   q_index: n entries, each < count.  (size_t on the host; 64-bit words in device memory for the _dev entry point.)  q_index == NULL keeps the
+   convention of the other prepared entry points: every pair uses point 0 of a one-point handle, pair i uses point i otherwise (n <= count).
+   How: every segment of L pairs is cut into ceil(L / 4) pieces of at most four consecutive pairs; a lane pair runs one piece on ONE Miller
+   accumulator over the native tables (the line products of its pairs, a quarter of the squarings - the loop of
+   bn254_pairing_product_prepared_native) and writes one un-exponentiated value.  When no segment has more than four pairs (the Groth16
+   shape) that value is out[j] and the batched final exponentiation runs in place: nothing is folded.  Otherwise the values go through the
+   segmented fold of bn254_pairing_product_batch (chunks of one machine round of VALUES, pieces of at most 16, carry across chunks).
+   Calls of at most min(12 x CUs, BN254_OPT_WAVE_PAIRING_MAX) pairs are served by bn254_pairing_product_batch's own kernels on the points kept
+   with the handle, gathered by index (same bytes; BN254_OPT_WAVE_PAIRING_MAX = 0 turns that off), as for the other prepared entry points.
+   Layout for speed, not for correctness: for a fixed position i inside the pieces, the lane pairs of a wave should meet ADJACENT points or ONE
+   point - e.g. a block of checks laid out as [3 + j, 0, 1, 2] over a handle [beta, gamma, delta, B_0 .. B_{m-1}]: pair 0 reads adjacent
+   columns, pairs 1-3 are broadcasts.  Arbitrary indices are correct, just slower.
+   Errors (BN254_E_BAD_ARG, checked before any device is touched): everything bn254_pairing_product_batch rejects, prep == NULL,
+   q_index[i] >= count (the caller gets an error, never a wrong product), n > count with q_index == NULL on a handle of several points; then a
+   handle that belongs to another device than the context.  The handle is immutable: any number of threads / streams may share it. */
+int bn254_pairing_product_batch_prepared_native(bn254_ctx *ctx, const bn_g1 *p, const bn254_g2_prepared *prep, const size_t *q_index,
+                                                const size_t *offsets, size_t m, bn_gt *out);
 int bn254_gt_mul_batch(bn254_ctx *ctx, const bn_gt *a, const bn_gt *b, bn_gt *out, size_t n);
 /* Gt::pow (lib.rs:171).  a[i] are Gt VALUES - what the reference's type holds: Gt::one, pairing() and products, powers, inverses of
    such (the Fq12 inside Gt is private and Gt has no decoder), all of order r.  On those the device exponentiates through the
@@ -351,6 +378,12 @@ int bn254_pairing_prepared_native_batch_dev(bn254_ctx *ctx, const void *d_p, con
 /* local part of a multi-pairing over prepared points: un-exponentiated product of the Miller values of p[i] against point q_first + i -> one
    Fq12 (the counterpart of bn254_miller_product_dev; bn254_gt_product_final_exp_dev or bn254_final_exp_batch_dev finishes it) */
 int bn254_miller_product_prepared_native_dev(bn254_ctx *ctx, const void *d_p, const bn254_g2_prepared *prep, size_t q_first, size_t n, void *d_partial, void *stream);
+/* bn254_pairing_product_batch_prepared_native on device-resident p, q_index (n 64-bit words, or NULL) and out; `offsets` (m+1 entries) is HOST
+   memory (the launches are planned from it) and may be freed on return.  d_q_index cannot be read on the host, so it is NOT checked: an index
+   >= count is outside the contract, but memory safe - the kernels map it to the identity record the table ends with (the small route: to the
+   point at infinity), so that pair contributes the factor one. */
+int bn254_pairing_product_batch_prepared_native_dev(bn254_ctx *ctx, const void *d_p, const bn254_g2_prepared *prep, const void *d_q_index,
+                                                    const size_t *offsets, size_t m, void *d_out, void *stream);
 int bn254_gt_mul_batch_dev(bn254_ctx *ctx, const void *d_a, const void *d_b, void *d_out, size_t n, void *stream);
 int bn254_gt_pow_batch_dev(bn254_ctx *ctx, const void *d_a, const void *d_k, void *d_out, size_t n, void *stream);
 int bn254_gt_inverse_batch_dev(bn254_ctx *ctx, const void *d_a, void *d_out, size_t n, void *stream);
@@ -372,7 +405,7 @@ int bn254_tile_dev(bn254_ctx *ctx, const void *d_record, size_t record_bytes, si
    accumulated duration and launch count per kernel since the last reset (this is what bench.py's roofline uses). */
 int bn254_profile_enable(bn254_ctx *ctx, int on);
 int bn254_profile_reset(bn254_ctx *ctx);
-/* kernel: "miller", "miller_shared", "miller_wave", "miller_quad", "pairing_wave", "final_exp", "final_exp_wave", "final_exp_quad", "exp_by_neg_z", "gt_product", "gt_tail", "gt_segment", "gt_tail_seg", "g1_mul", "g2_mul", "gt_mul", "gt_pow", "g2_precompute", "miller_prepared", "g2_prepare_native", "miller_native", "miller_native_shared", "wire_encode", "wire_decode", "gt_inverse", "g1_add", "g2_add", "g1_msm_mul", "g1_msm_fold", "g2_msm_mul", "g2_msm_fold".
+/* kernel: "miller", "miller_shared", "miller_wave", "miller_quad", "pairing_wave", "final_exp", "final_exp_wave", "final_exp_quad", "exp_by_neg_z", "gt_product", "gt_tail", "gt_segment", "gt_tail_seg", "g1_mul", "g2_mul", "gt_mul", "gt_pow", "g2_precompute", "miller_prepared", "g2_prepare_native", "miller_native", "miller_native_shared", "miller_native_seg", "g2_gather", "wire_encode", "wire_decode", "gt_inverse", "g1_add", "g2_add", "g1_msm_mul", "g1_msm_fold", "g2_msm_mul", "g2_msm_fold".
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);
 /* issue-rate ceiling of v_mad_u64_u32 (the 32x32+64 multiply-accumulate every field product is built from) at
