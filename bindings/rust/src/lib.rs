@@ -68,6 +68,12 @@ extern "C" {
     fn bn254_g2_msm_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_k: *const c_void, offsets: *const usize, m: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn bn254_g1_msm_batch_multi(mh: *mut c_void, p: *const G1, k: *const Fr, offsets: *const usize, m: usize, out: *mut G1) -> c_int;
     fn bn254_g2_msm_batch_multi(mh: *mut c_void, p: *const G2, k: *const Fr, offsets: *const usize, m: usize, out: *mut G2) -> c_int;
+    fn bn254_g1_msm(ctx: *mut c_void, p: *const G1, k: *const Fr, n: usize, out: *mut G1) -> c_int;
+    fn bn254_g2_msm(ctx: *mut c_void, p: *const G2, k: *const Fr, n: usize, out: *mut G2) -> c_int;
+    fn bn254_g1_msm_dev(ctx: *mut c_void, d_p: *const c_void, d_k: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn bn254_g2_msm_dev(ctx: *mut c_void, d_p: *const c_void, d_k: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn bn254_g1_msm_multi(mh: *mut c_void, p: *const G1, k: *const Fr, n: usize, out: *mut G1) -> c_int;
+    fn bn254_g2_msm_multi(mh: *mut c_void, p: *const G2, k: *const Fr, n: usize, out: *mut G2) -> c_int;
 }
 
 /// One line-function coefficient of a prepared G2 point: the crate's `EllCoeffs { ell_0, ell_vw, ell_vv: Fq2 }` (src/groups/mod.rs:472-476) as the
@@ -96,6 +102,7 @@ pub const G2_WIRE_BYTES: usize = 129;
 pub enum GpuOption {
     WavePairingMax = 1, WaveFeMax = 2, QuadMax = 3, MillerShared = 4, GtPowMode = 5, ProductChunk = 6, ProductPerWave = 7,
     ProductBfly = 8, RoundPairs = 9, PipelineChunk = 10, PipelineSlots = 11, StreamStopAtError = 12,
+    MsmBucketMin = 13, MsmWindowBits = 14, MsmChunk = 15,
 }
 /// sets an option of the process-wide default context of the current HIP device; `None` restores the default
 pub fn set_option(key: GpuOption, value: Option<i64>) -> Result<(), GpuError> {
@@ -181,6 +188,23 @@ pub fn g2_msm_batch(p: &[G2], k: &[Fr], offsets: &[usize]) -> Result<Vec<G2>, Gp
     assert!(!offsets.is_empty() && offsets[offsets.len() - 1] == p.len());
     let mut out = vec![G2::zero(); offsets.len() - 1];
     check(unsafe { bn254_g2_msm_batch(std::ptr::null_mut(), p.as_ptr(), k.as_ptr(), offsets.as_ptr(), out.len(), out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// the normalized sum of `p[i] * k[i]` over ALL terms: one large multi-scalar multiplication - the bucket (Pippenger) method from
+/// `GpuOption::MsmBucketMin` terms on, below it the one-segment `g1_msm_batch`; the same bytes either way, `G1::zero()` for an empty or
+/// cancelling sum
+pub fn g1_msm(p: &[G1], k: &[Fr]) -> Result<G1, GpuError> {
+    assert_eq!(p.len(), k.len());
+    let mut out = G1::zero();
+    check(unsafe { bn254_g1_msm(std::ptr::null_mut(), p.as_ptr(), k.as_ptr(), p.len(), &mut out) })?;
+    Ok(out)
+}
+
+pub fn g2_msm(p: &[G2], k: &[Fr]) -> Result<G2, GpuError> {
+    assert_eq!(p.len(), k.len());
+    let mut out = G2::zero();
+    check(unsafe { bn254_g2_msm(std::ptr::null_mut(), p.as_ptr(), k.as_ptr(), p.len(), &mut out) })?;
     Ok(out)
 }
 
@@ -457,6 +481,19 @@ impl MultiGpu {
         assert!(!offsets.is_empty() && offsets[offsets.len() - 1] == p.len());
         let mut out = vec![G2::zero(); offsets.len() - 1];
         check(unsafe { bn254_g2_msm_batch_multi(self.0, p.as_ptr(), k.as_ptr(), offsets.as_ptr(), out.len(), out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+    /// `g1_msm` with the terms sharded over the GPUs; GPU 0 adds the partial sums (no device-to-device exchange)
+    pub fn g1_msm(&self, p: &[G1], k: &[Fr]) -> Result<G1, GpuError> {
+        assert_eq!(p.len(), k.len());
+        let mut out = G1::zero();
+        check(unsafe { bn254_g1_msm_multi(self.0, p.as_ptr(), k.as_ptr(), p.len(), &mut out) })?;
+        Ok(out)
+    }
+    pub fn g2_msm(&self, p: &[G2], k: &[Fr]) -> Result<G2, GpuError> {
+        assert_eq!(p.len(), k.len());
+        let mut out = G2::zero();
+        check(unsafe { bn254_g2_msm_multi(self.0, p.as_ptr(), k.as_ptr(), p.len(), &mut out) })?;
         Ok(out)
     }
 }

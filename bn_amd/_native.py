@@ -39,6 +39,12 @@ SIGNATURES = {   # name -> argtypes  (every function returns int unless noted)
     "bn254_g2_msm_batch_dev": [_VP, _VP, _VP, _VP, _SZ, _VP, _VP],
     "bn254_g1_msm_batch_multi": [_VP, _VP, _VP, _VP, _SZ, _VP],
     "bn254_g2_msm_batch_multi": [_VP, _VP, _VP, _VP, _SZ, _VP],
+    "bn254_g1_msm": [_VP, _VP, _VP, _SZ, _VP],
+    "bn254_g2_msm": [_VP, _VP, _VP, _SZ, _VP],
+    "bn254_g1_msm_dev": [_VP, _VP, _VP, _SZ, _VP, _VP],
+    "bn254_g2_msm_dev": [_VP, _VP, _VP, _SZ, _VP, _VP],
+    "bn254_g1_msm_multi": [_VP, _VP, _VP, _SZ, _VP],
+    "bn254_g2_msm_multi": [_VP, _VP, _VP, _SZ, _VP],
     "bn254_g1_mul_batch": [_VP, _VP, _VP, _VP, _SZ],
     "bn254_g2_mul_batch": [_VP, _VP, _VP, _VP, _SZ],
     "bn254_g1_add_batch": [_VP, _VP, _VP, _VP, _SZ, C.c_int],
@@ -205,7 +211,8 @@ def lib():
 
 # BN254_OPT_* of include/bn254_hip.h
 OPTIONS = {"wave_pairing_max": 1, "wave_fe_max": 2, "quad_max": 3, "miller_shared": 4, "gt_pow_mode": 5, "product_chunk": 6,
-           "product_per_wave": 7, "product_bfly": 8, "round_pairs": 9, "pipeline_chunk": 10, "pipeline_slots": 11, "stream_stop_at_error": 12}
+           "product_per_wave": 7, "product_bfly": 8, "round_pairs": 9, "pipeline_chunk": 10, "pipeline_slots": 11, "stream_stop_at_error": 12,
+           "msm_bucket_min": 13, "msm_window_bits": 14, "msm_chunk": 15}
 EXCHANGE = {"auto": -1, "peer": 0, "rccl": 1}
 
 

@@ -109,7 +109,7 @@ class G1(_Point):
         return G1(default_engine().g1_add_batch(G1.zero().limbs, self.limbs, negate_b=True)[0])
     @staticmethod
     def msm(points, scalars):             # normalize(sum points[i] * scalars[i]) in one call
-        return g1_msm_batch([list(zip(points, scalars))])[0]
+        return g1_msm(points, scalars)
 
 
 _G2_GEN = ((10857046999023057135944570762232829481370756359578518086990519993285655852781,
@@ -141,7 +141,7 @@ class G2(_Point):
         return G2(default_engine().g2_add_batch(G2.zero().limbs, self.limbs, negate_b=True)[0])
     @staticmethod
     def msm(points, scalars):
-        return g2_msm_batch([list(zip(points, scalars))])[0]
+        return g2_msm(points, scalars)
 
 
 class Gt:
@@ -243,6 +243,30 @@ def g2_msm_batch(segments, ks=None, offsets=None, engine=None):
     """the same over G2: (G2, Fr) terms, or (n,24) / (n,4) arrays plus offsets"""
     P, K, offs = _msm_arrays(G2, segments, ks, offsets)
     return [G2(r) for r in (engine or default_engine()).g2_msm_batch(P, K, offs)]
+
+
+def _msm1_arrays(group, points, scalars):
+    if isinstance(points, np.ndarray) or isinstance(scalars, np.ndarray):          # (n, WORDS) points and (n, 4) scalars
+        return np.asarray(points, np.uint64).reshape(-1, group.WORDS), np.asarray(scalars, np.uint64).reshape(-1, 4)
+    points, scalars = list(points), list(scalars)
+    if len(points) != len(scalars):
+        raise ValueError("as many scalars as points")
+    P = np.stack([p.limbs for p in points]) if points else np.zeros((0, group.WORDS), np.uint64)
+    K = np.stack([k.limbs for k in scalars]) if scalars else np.zeros((0, 4), np.uint64)
+    return P, K
+
+
+def g1_msm(points, scalars, engine=None):
+    """normalize(sum of points[i] * scalars[i]): ONE large multi-scalar multiplication (bucket method from the option msm_bucket_min terms
+    on; the same bytes as the one-segment g1_msm_batch).  Sequences of G1 / Fr, or (n,12) / (n,4) uint64 arrays; no terms give G1.zero()."""
+    P, K = _msm1_arrays(G1, points, scalars)
+    return G1((engine or default_engine()).g1_msm(P, K))
+
+
+def g2_msm(points, scalars, engine=None):
+    """the same over G2: sequences of G2 / Fr, or (n,24) / (n,4) arrays"""
+    P, K = _msm1_arrays(G2, points, scalars)
+    return G2((engine or default_engine()).g2_msm(P, K))
 
 
 class PreparedG2:

@@ -146,6 +146,10 @@ int bn_get_ctx(bn254_ctx *&ctx) {
 // process, into the seed values every new context starts from.
 constexpr size_t BN_LAUNCH_MAX = (size_t)1 << 22;       // units per launch (32-bit word offsets inside a kernel); also the cap of the size options
 constexpr size_t BN_N_MAX = (size_t)1 << 40;            // sanity bound on a batch; launches are cut to size internally
+// terms from which bn254_g{1,2}_msm take the bucket route while BN254_OPT_MSM_BUCKET_MIN is not set: the smallest measured size from which
+// the route is faster in kernel time than the one-segment bn254_g{1,2}_msm_batch and stays faster above (profiles/r10_msm_bucket.txt: G1
+// 0.73 x at 2^18, 1.06 x at 2^19, 1.33 x at 2^20; G2 0.77 x at 2^17, 1.14 x at 2^18, 1.55 x at 2^19).  bn254_ctx_get_option reports G1's.
+constexpr long BN_MSM_BUCKET_MIN_DEFAULT = (long)1 << 19, BN_MSM_BUCKET_MIN_DEFAULT_G2 = (long)1 << 18;
 namespace {
 bool bn_opt_valid(int key, long v);
 struct DebugEnv { long opt[BN254_OPT_COUNT_]; int exchange; bool affinity; };
@@ -161,7 +165,8 @@ const DebugEnv &bn_debug_env() {
             {"BN254_MILLER_SHARED", BN254_OPT_MILLER_SHARED}, {"BN254_GT_POW_MODE", BN254_OPT_GT_POW_MODE}, {"BN254_PRODUCT_CHUNK", BN254_OPT_PRODUCT_CHUNK},
             {"BN254_PRODUCT_PER_WAVE", BN254_OPT_PRODUCT_PER_WAVE}, {"BN254_PRODUCT_BFLY", BN254_OPT_PRODUCT_BFLY}, {"BN254_ROUND_PAIRS", BN254_OPT_ROUND_PAIRS},
             {"BN254_PIPELINE_CHUNK", BN254_OPT_PIPELINE_CHUNK}, {"BN254_PIPELINE_SLOTS", BN254_OPT_PIPELINE_SLOTS},
-            {"BN254_STREAM_STOP_AT_ERROR", BN254_OPT_STREAM_STOP_AT_ERROR}};
+            {"BN254_STREAM_STOP_AT_ERROR", BN254_OPT_STREAM_STOP_AT_ERROR}, {"BN254_MSM_BUCKET_MIN", BN254_OPT_MSM_BUCKET_MIN},
+            {"BN254_MSM_WINDOW_BITS", BN254_OPT_MSM_WINDOW_BITS}, {"BN254_MSM_CHUNK", BN254_OPT_MSM_CHUNK}};
         for (const auto &v : vars)
             if (const char *e = getenv(v.name)) { const long x = atol(e); if (x >= 0 && bn_opt_valid(v.key, x)) env.opt[v.key] = x; }
         if (const char *e = getenv("BN254_MULTI_AFFINITY")) env.affinity = atoi(e) != 0;
@@ -184,6 +189,9 @@ bool bn_opt_valid(int key, long v) {
         case BN254_OPT_ROUND_PAIRS: case BN254_OPT_PIPELINE_CHUNK: return v >= 1 && v <= (long)BN_LAUNCH_MAX;
         case BN254_OPT_PIPELINE_SLOTS: return v >= 1 && v <= BN_MAX_SLOTS;
         case BN254_OPT_STREAM_STOP_AT_ERROR: return v <= 1;
+        case BN254_OPT_MSM_BUCKET_MIN: return v <= (long)BN_N_MAX + 1;
+        case BN254_OPT_MSM_WINDOW_BITS: return v >= 1 && v <= 16;
+        case BN254_OPT_MSM_CHUNK: return v >= 1 && v <= (long)BN_LAUNCH_MAX;
         default: return false;
     }
 }
@@ -205,7 +213,9 @@ long bn_opt(const bn254_ctx *c, int key) {
         case BN254_OPT_MILLER_SHARED: case BN254_OPT_GT_POW_MODE: case BN254_OPT_STREAM_STOP_AT_ERROR: return 0;
         case BN254_OPT_ROUND_PAIRS: return 256 * cus;
         case BN254_OPT_PIPELINE_SLOTS: return 2;
-        default: return -1;                  // product shape, pipeline chunk: decided per call from the size
+        case BN254_OPT_MSM_BUCKET_MIN: return BN_MSM_BUCKET_MIN_DEFAULT;
+        case BN254_OPT_MSM_CHUNK: return (long)1 << 20;
+        default: return -1;                  // product shape, pipeline chunk, window width of the bucket method: decided per call from the size
     }
 }
 
@@ -635,6 +645,135 @@ static int bn_launch_msm(bn254_ctx *c, int g, const void *d_p, const void *d_k, 
     return BN254_OK;
 }
 
+// ---- one large multi-scalar multiplication: out = normalize(sum of p[i] * k[i] over all n terms) (bn254_g{1,2}_msm*)
+// Below BN254_OPT_MSM_BUCKET_MIN terms: bn_launch_msm on the one segment {0, n}.  From there on the bucket (Pippenger) method with unsigned
+// c-bit windows (BN254_OPT_MSM_WINDOW_BITS; W = ceil(254 / c) windows, 2^c buckets per window of which bucket 0 stays empty), in chunks of at
+// most BN254_OPT_MSM_CHUNK terms.  Per chunk (kernels and their invariants: bn254_kernels_mul.hip):
+//   digits   count the terms per (window, digit), scan the W * 2^c counts, scatter (term index, key) into key order     scope g*_msm_digits
+//   bucket   levels of the accumulation: every lane adds at most MSM_PIECE consecutive entries; a run of one key that ends inside a lane is
+//            added to its bucket, the pieces of a longer run go to the next, eight times shorter level.  The entry count is known on the
+//            device only; the host launches every level for its upper bound W * terms (lanes past the real count retire at once), so
+//            nothing is read back and the call stays asynchronous                                                          scope g*_msm_bucket
+// The buckets collect over the chunks.  Then ONE reduction (scope g*_msm_reduce): groups of 16 consecutive buckets give S = sum B_b and
+// T = sum (b - base) B_b, and the window sums sum_groups (T + base S) weighted by 2^(c w) are the one-segment bn_launch_msm over these
+// 2 * W * 2^c / 16 Jacobian terms with the scalars base * 2^(c w) and 2^(c w) - host-known, built once per window width - which folds,
+// normalises once and writes out.
+// Workspace (context-owned, under the scratch guard), for t = min(n, chunk) terms and V = 96 / 192 bytes per point: W t entries of 8 bytes
+// (index, key), W 2^c counts of 4 bytes and buckets of V bytes, the partial sums of the levels (at most W t / 7 + 64 slots of V + 4 bytes),
+// 2 W 2^c / 16 tail terms of V + 32 bytes.
+namespace {
+const uint64_t BN_FR_MOD64[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};
+// out = (a + b) mod r for a, b < r (r < 2^254: the sum fits four words)
+void bn_fr_add(const uint64_t *a, const uint64_t *b, uint64_t *out) {
+    uint64_t t[4], d[4];
+    unsigned __int128 c = 0;
+    for (int i = 0; i < 4; ++i) { c += (unsigned __int128)a[i] + b[i]; t[i] = (uint64_t)c; c >>= 64; }
+    unsigned __int128 br = 0;
+    for (int i = 0; i < 4; ++i) { const unsigned __int128 x = (unsigned __int128)t[i] - BN_FR_MOD64[i] - br; d[i] = (uint64_t)x; br = (x >> 64) & 1; }
+    for (int i = 0; i < 4; ++i) out[i] = br ? t[i] : d[i];
+}
+constexpr unsigned BN_MSM_GROUP = 16;         // buckets per lane of the reduction: 32 additions in a row, 2^c / 8 tail terms per window
+size_t bn_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// window width by size when BN254_OPT_MSM_WINDOW_BITS is not set: the best measured width per size (profiles/r10_msm_bucket.txt)
+unsigned bn_msm_window_bits(const bn254_ctx *c, int g, size_t n) {
+    const long forced = bn_opt(c, BN254_OPT_MSM_WINDOW_BITS);
+    if (forced >= 1) return (unsigned)forced;
+    (void)g;
+    unsigned lg = 0;
+    while (((size_t)2 << lg) <= n) ++lg;                     // floor(log2 n), 0 for n <= 1
+    // G1 and G2 agree on the best width at every measured size; between neighbouring widths the kernel time differs by a few percent
+    // (the accumulation is bound by its gathers, not by the W additions per term) except where a width leaves a top window of one or
+    // two bits, whose few buckets every term hits (13 at 2^19: 7.3 against 6.6 ms)
+    return lg <= 14 ? 8 : lg == 15 ? 9 : lg <= 17 ? 11 : lg == 18 ? 12 : lg == 19 ? 11 : 14;
+}
+}  // namespace
+void bn_fr_one(bn_fr *out) {                                  // 2^256 mod r: the Montgomery image of one
+    uint64_t x[4] = {1, 0, 0, 0};
+    for (int i = 0; i < 256; ++i) bn_fr_add(x, x, x);
+    memcpy(out->l, x, sizeof x);
+}
+// scratch guard held by the caller
+static int bn_launch_msm_bucket(bn254_ctx *c, int g, const void *d_p, const void *d_k, size_t n, void *d_out, hipStream_t s) {
+    const size_t V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2), L = bn254_msm_piece_M();
+    const unsigned cb = bn_msm_window_bits(c, g, n), W = (254 + cb - 1) / cb, G = std::min(BN_MSM_GROUP, 1u << cb), groups = (1u << cb) / G;
+    const size_t K = (size_t)W << cb, count = (size_t)W * groups;
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, (size_t)bn_opt(c, BN254_OPT_MSM_CHUNK)));
+    const size_t n0max = (size_t)W * chunk;                 // < 254 * 2^22 < 2^32: positions and keys are 32-bit
+    std::vector<size_t> out_slots;                           // slots every level writes, from the upper bound of its entries
+    for (size_t N = n0max;;) {
+        const size_t M = 2 * ((N + L - 1) / L);
+        out_slots.push_back(M);
+        if (N <= L) break;
+        N = M;
+    }
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += bn_align256(bytes); return o; };
+    const size_t o_counts = take(K * 4), o_tiles = take(1024 * 4), o_n0 = take(4), o_idx = take(n0max * 4), o_keys = take(n0max * 4), o_buckets = take(K * V);
+    std::vector<std::pair<size_t, size_t>> o_level;
+    for (size_t M : out_slots) { const size_t a = take(M * V), b = take(M * 4); o_level.push_back({a, b}); }
+    const size_t o_terms = take(2 * count * V);
+    int rc;
+    if ((rc = c->msm_ws.reserve(at))) return rc;
+    char *ws = (char *)c->msm_ws.p;
+    if (c->msm_scal_c != (long)cb) {
+        // the tail's scalars as Montgomery images: S terms of every (window, group), then the T terms
+        std::vector<uint64_t> &h = c->msm_scal_host;
+        HIP_TRY(hipStreamSynchronize(s));                    // the previous image may still be on its way
+        h.assign(2 * count * 4, 0);
+        bn_fr pw; bn_fr_one(&pw);
+        for (unsigned w = 0; w < W; ++w) {
+            uint64_t step[4], acc[4] = {0, 0, 0, 0};
+            memcpy(step, pw.l, sizeof step);
+            for (unsigned b = 1; b < G; b <<= 1) bn_fr_add(step, step, step);                  // G * 2^(c w)
+            for (unsigned q = 0; q < groups; ++q) {
+                memcpy(&h[((size_t)w * groups + q) * 4], acc, sizeof acc);
+                memcpy(&h[(count + (size_t)w * groups + q) * 4], pw.l, sizeof acc);
+                bn_fr_add(acc, step, acc);
+            }
+            for (unsigned b = 0; b < cb; ++b) bn_fr_add(pw.l, pw.l, pw.l);
+        }
+        if ((rc = c->msm_scal.reserve(h.size() * 8))) return rc;
+        c->msm_scal_c = -1;
+        HIP_TRY(hipMemcpyAsync(c->msm_scal.p, h.data(), h.size() * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        c->msm_scal_c = (long)cb;
+    }
+    HIP_TRY(hipMemsetAsync(ws + o_buckets, 0, K * V, s));   // z = 0: every bucket starts as the point at infinity
+    for (size_t lo = 0; lo < n; lo += chunk) {
+        const size_t len = std::min(chunk, n - lo);
+        const char *pk = (const char *)d_k + lo * sizeof(bn_fr), *pp = (const char *)d_p + lo * V;
+        {
+            BnScope sc(c, s, g == 1 ? "g1_msm_digits" : "g2_msm_digits");
+            HIP_TRY(hipMemsetAsync(ws + o_counts, 0, K * 4, s));
+            if ((rc = bn254_launch_msm_digits_M(pk, len, cb, W, ws + o_counts, nullptr, nullptr, 0, s))) return rc;
+            if ((rc = bn254_launch_msm_scan_M(ws + o_counts, K, ws + o_tiles, ws + o_n0, s))) return rc;
+            if ((rc = bn254_launch_msm_digits_M(pk, len, cb, W, ws + o_counts, ws + o_idx, ws + o_keys, 1, s))) return rc;
+        }
+        BnScope sc(c, s, g == 1 ? "g1_msm_bucket" : "g2_msm_bucket");
+        const char *pts = pp, *idx = ws + o_idx, *keys = ws + o_keys;
+        size_t N = (size_t)W * len;
+        for (unsigned level = 0;; ++level) {
+            if (level >= o_level.size()) return BN254_E_INTERNAL;
+            char *opts = ws + o_level[level].first, *okeys = ws + o_level[level].second;
+            if ((rc = bn254_launch_msm_bucket_M(g, pts, idx, keys, ws + o_n0, level, opts, okeys, ws + o_buckets, (N + L - 1) / L, s))) return rc;
+            if (N <= L) break;
+            N = 2 * ((N + L - 1) / L); pts = opts; idx = nullptr; keys = okeys;
+        }
+    }
+    {
+        BnScope sc(c, s, g == 1 ? "g1_msm_reduce" : "g2_msm_reduce");
+        if ((rc = bn254_launch_msm_reduce_M(g, ws + o_buckets, G, groups, cb, count, ws + o_terms, s))) return rc;
+    }
+    const size_t off[2] = {0, 2 * count};
+    return bn_launch_msm(c, g, ws + o_terms, c->msm_scal.p, off, 1, d_out, s);
+}
+// the route of one call: the one-segment launch sequence of bn254_g{1,2}_msm_batch below BN254_OPT_MSM_BUCKET_MIN terms
+static bool bn_msm_bucket_route(const bn254_ctx *c, int g, size_t n) {
+    const long set = c->opt[BN254_OPT_MSM_BUCKET_MIN].load(std::memory_order_relaxed);
+    return n >= (size_t)(set >= 0 ? set : g == 1 ? BN_MSM_BUCKET_MIN_DEFAULT : BN_MSM_BUCKET_MIN_DEFAULT_G2);
+}
+int bn_msm1_check(const void *p, const void *k, size_t n, const void *out) { return (n > BN_N_MAX || !out || (n && (!p || !k))) ? BN254_E_BAD_ARG : BN254_OK; }
+
 extern "C" {
 
 int bn254_device_count(void) {
@@ -669,7 +808,7 @@ void bn254_ctx_destroy(bn254_ctx *c) {
     hipDeviceSynchronize();
     for (auto &r : c->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     c->ws.release(); c->exp_tbl.release(); c->pow_tbl.release(); c->miller_state.release(); c->mul_tbl.release();
-    c->seg_plan.release(); c->seg_plan_host.release();
+    c->seg_plan.release(); c->seg_plan_host.release(); c->msm_ws.release(); c->msm_scal.release();
     if (c->seg_plan_ev) hipEventDestroy(c->seg_plan_ev);
     for (auto &b : c->stage) b.release();
     for (auto &s : c->slot) {
@@ -860,6 +999,22 @@ static int msm_dev(bn254_ctx *ctx, int g, const void *d_p, const void *d_k, cons
 }
 int bn254_g1_msm_batch_dev(bn254_ctx *c, const void *p, const void *k, const size_t *offsets, size_t m, void *o, void *s) { return msm_dev(c, 1, p, k, offsets, m, o, s); }
 int bn254_g2_msm_batch_dev(bn254_ctx *c, const void *p, const void *k, const size_t *offsets, size_t m, void *o, void *s) { return msm_dev(c, 2, p, k, offsets, m, o, s); }
+
+static int msm1_dev(bn254_ctx *ctx, int g, const void *d_p, const void *d_k, size_t n, void *d_out, void *stream) {
+    if (int e = bn_msm1_check(d_p, d_k, n, d_out)) return e;                   // before any device lookup
+    int rc = bn_get_ctx(ctx); if (rc) return rc;
+    BnDeviceGuard dev_guard;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    BnScratchGuard gd(ctx, s); if (gd.rc) return gd.rc;          // every workspace of both routes is context-owned scratch
+    return bn_no_throw([&]() -> int {
+        if (bn_msm_bucket_route(ctx, g, n)) return bn_launch_msm_bucket(ctx, g, d_p, d_k, n, d_out, s);
+        const size_t off[2] = {0, n};
+        return bn_launch_msm(ctx, g, d_p, d_k, off, 1, d_out, s);
+    });
+}
+int bn254_g1_msm_dev(bn254_ctx *c, const void *p, const void *k, size_t n, void *o, void *s) { return msm1_dev(c, 1, p, k, n, o, s); }
+int bn254_g2_msm_dev(bn254_ctx *c, const void *p, const void *k, size_t n, void *o, void *s) { return msm1_dev(c, 2, p, k, n, o, s); }
 
 int bn254_g2_precompute_dev(bn254_ctx *ctx, const void *d_q, void *d_coeffs, size_t n, void *stream) {
     BN_DEV_PROLOGUE(!d_q || !d_coeffs, 0x7fffffffu / (102 * 48));
@@ -1100,6 +1255,29 @@ static int msm_host(bn254_ctx *ctx, int g, const void *p, const bn_fr *k, const 
 }
 int bn254_g1_msm_batch(bn254_ctx *ctx, const bn_g1 *p, const bn_fr *k, const size_t *offsets, size_t m, bn_g1 *out) { return msm_host(ctx, 1, p, k, offsets, m, out); }
 int bn254_g2_msm_batch(bn254_ctx *ctx, const bn_g2 *p, const bn_fr *k, const size_t *offsets, size_t m, bn_g2 *out) { return msm_host(ctx, 2, p, k, offsets, m, out); }
+static int msm1_host_bucket(bn254_ctx *ctx, int g, const void *p, const bn_fr *k, size_t n, void *out) {
+    const size_t V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2);
+    BN_HOST_PROLOGUE();
+    BnBuf &dp = ctx->stage[0], &dk = ctx->stage[1], &dout = ctx->stage[2];
+    if ((rc = dp.reserve(n * V)) || (rc = dk.reserve(n * sizeof(bn_fr))) || (rc = dout.reserve(V))) return rc;
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(dp.p, p, n * V, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(dk.p, k, n * sizeof(bn_fr), hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = msm1_dev(ctx, g, dp.p, dk.p, n, dout.p, ctx->stream); if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, dout.p, V, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return BN254_OK;
+}
+static int msm1_host(bn254_ctx *ctx, int g, const void *p, const bn_fr *k, size_t n, void *out) {
+    if (int e = bn_msm1_check(p, k, n, out)) return e;                         // before any device lookup
+    int rc = bn_get_ctx(ctx); if (rc) return rc;
+    if (bn_msm_bucket_route(ctx, g, n)) return msm1_host_bucket(ctx, g, p, k, n, out);
+    const size_t off[2] = {0, n};
+    return msm_host(ctx, g, p, k, off, 1, out);
+}
+int bn254_g1_msm(bn254_ctx *ctx, const bn_g1 *p, const bn_fr *k, size_t n, bn_g1 *out) { return msm1_host(ctx, 1, p, k, n, out); }
+int bn254_g2_msm(bn254_ctx *ctx, const bn_g2 *p, const bn_fr *k, size_t n, bn_g2 *out) { return msm1_host(ctx, 2, p, k, n, out); }
 int bn254_g2_precompute(bn254_ctx *ctx, const bn_g2 *q, bn_ell_coeffs *coeffs, size_t n) {
     if (n == 0) return BN254_OK;
     if (!q || !coeffs) return BN254_E_BAD_ARG;

@@ -228,6 +228,203 @@ __global__ void __launch_bounds__(BLOCK) bn254_g2_add_M(const BnSegPiece *pieces
     Jac<F> r = msm_fold_body<F>(pc, 48u, [](const uint32_t *w) { return Jac<F>{f2_load((const F2 *)nullptr, w), f2_load((const F2 *)nullptr, w + 16), f2_load((const F2 *)nullptr, w + 32)}; });
     if (live) { f2_store(r.x, pc.dst); f2_store(r.y, pc.dst + 16); f2_store(r.z, pc.dst + 32); }
 }
+
+// ---- bucket (Pippenger) method of bn254_g{1,2}_msm: one large sum (bn254_hip.hip bn_launch_msm_bucket plans the launches)
+// A scalar is cut into W = ceil(254 / c) unsigned c-bit digits; term i belongs to bucket KEY = w * 2^c + digit for every window w whose digit
+// is not zero.  The integer kernels count the terms per key, scan the counts and scatter (term index, key) into key order - a counting sort,
+// arbitrary order inside a key.  Instances of the name bn254_fr_decode_k beside the wire decoder of bn254_hip.hip (they take the canonical
+// integer of a scalar apart); the point kernels below are instances of bn254_g{1,2}_add_M.
+constexpr uint32_t MSM_NONE = 0x7fffffffu;        // key of an unused entry
+constexpr uint32_t MSM_SKIP = 0x80000000u;        // key flag: the entry belongs to the run of its key but carries no point
+constexpr uint32_t MSM_PIECE = 16;                // entries per lane of one accumulation level: the longest serial chain, whatever the data
+constexpr uint32_t MSM_TILE = 1024;               // counts per workgroup of the scan (256 threads x 4)
+
+__device__ __forceinline__ uint32_t msm_digit(const uint32_t *raw, uint32_t w, uint32_t c) {
+    const uint32_t bit = w * c, word = bit >> 5;
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 8; ++i) { if (i == word) lo = raw[i]; if (i == word + 1) hi = raw[i]; }      // selects: `raw` stays in registers
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (bit & 31u)) & ((1u << c) - 1u);
+}
+// COUNT: counts[key] += 1 for every non-zero digit of k[0..n); SCATTER: the same walk, (index, key) written at cursor[key]++ (the scanned counts).
+// When every active lane of a wave holds the same digit (equal scalars: the skew case) one lane adds for all of them; large groups of
+// equal digits inside a wave are served the same way.
+struct MsmDigitsOp {
+    const uint32_t *k; uint32_t n, c, W; uint32_t *counts; uint32_t *idx, *keys; int scatter;
+    __device__ __forceinline__ void operator()() const {
+        const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+        if (i >= n) return;
+        uint32_t kw[8], raw[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) kw[j] = k[8u * i + j];
+        fr_from_mont(kw, raw);
+        const uint64_t active = __ballot(1);
+        const uint32_t lane = __lane_id(), leader = (uint32_t)__ffsll((unsigned long long)active) - 1u;
+        const uint32_t rank = (uint32_t)__popcll(active & ((1ull << lane) - 1ull)), total = (uint32_t)__popcll(active);
+#pragma unroll 1
+        for (uint32_t w = 0; w < W; ++w) {
+            const uint32_t d = msm_digit(raw, w, c), first = (uint32_t)__shfl((int)d, (int)leader);
+            const uint32_t key = (w << c) + d;
+            uint32_t pos = 0;
+            if (__all(d == first)) {                                   // wave-uniform
+                if (d && lane == leader) pos = atomicAdd(&counts[key], total);
+                pos = (uint32_t)__shfl((int)pos, (int)leader) + rank;
+            } else {
+                // lanes that share a digit with the first lane not yet served add through ONE atomic (a short top window has a handful of
+                // buckets that every term hits: 2^20 atomics on three addresses otherwise); after two groups of fewer than three lanes -
+                // the usual case, random digits in a wide window - the rest add for themselves
+                bool done = d == 0;
+                uint64_t rem = __ballot(!done);
+                for (int small = 0; rem && small < 2;) {
+                    const uint32_t lead = (uint32_t)__ffsll((unsigned long long)rem) - 1u, dl = (uint32_t)__shfl((int)d, (int)lead);
+                    const bool mine = !done && d == dl;
+                    const uint64_t m = __ballot(mine);
+                    rem &= ~m;
+                    const uint32_t cnt = (uint32_t)__popcll(m);
+                    if (cnt < 3) { ++small; continue; }
+                    uint32_t base = 0;
+                    if (lane == lead) base = atomicAdd(&counts[(w << c) + dl], cnt);
+                    base = (uint32_t)__shfl((int)base, (int)lead);
+                    if (mine) { pos = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)); done = true; }
+                }
+                if (!done) pos = atomicAdd(&counts[key], 1u);
+            }
+            if (scatter && d) { idx[pos] = i; keys[pos] = key; }
+        }
+    }
+};
+// exclusive scan of `total` counts in place, three launches: mode 0 - the sum of every tile; 1 - ONE workgroup scans the (at most 1024) tile
+// sums and writes the grand total to *n0; 2 - every tile scans its counts from its base
+struct MsmScanOp {
+    uint32_t *counts; uint32_t total; uint32_t *tiles; uint32_t *n0; int mode;
+    __device__ __forceinline__ void operator()() const {
+        __shared__ uint32_t sh[256];
+        const uint32_t t = threadIdx.x;
+        uint32_t *v = mode == 1 ? tiles : counts + (size_t)blockIdx.x * MSM_TILE;
+        const uint32_t len = mode == 1 ? (total + MSM_TILE - 1) / MSM_TILE : min(MSM_TILE, total - blockIdx.x * MSM_TILE);
+        uint32_t x[4], s = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) { x[j] = 4 * t + j < len ? v[4 * t + j] : 0u; s += x[j]; }
+        sh[t] = s;
+        __syncthreads();
+        for (uint32_t off = 1; off < 256; off <<= 1) {
+            const uint32_t a = t >= off ? sh[t - off] : 0u;
+            __syncthreads();
+            sh[t] += a;
+            __syncthreads();
+        }
+        if (mode == 0) { if (t == 255) tiles[blockIdx.x] = sh[255]; return; }
+        uint32_t run = sh[t] - s + (mode == 2 ? tiles[blockIdx.x] : 0u);
+        if (mode == 1 && t == 255) *n0 = sh[255];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) { if (4 * t + j < len) v[4 * t + j] = run; run += x[j]; }
+    }
+};
+template <class Op>
+__global__ void __launch_bounds__(256) bn254_fr_decode_k(Op op) { op(); }
+
+// One level of the bucket accumulation.  The input is a sequence of N entries in key order (level 0: the sorted terms, their points gathered
+// by index; level l > 0: the partial sums level l - 1 wrote); lane (G2: lane pair) i adds the entries [i * MSM_PIECE, (i + 1) * MSM_PIECE) with
+// the complete addition, run by run.  A run of one key that lies inside the lane's entries is complete: buckets[key] += sum (the buckets
+// collect over the chunks of a call).  A run that began before the lane's first entry or goes on behind its last one is a piece of a longer
+// run: its sum becomes an entry of the next level - slot 2i for a run that began earlier, slot 2i + 1 for one that goes on (a run over ALL of
+// the lane's entries takes slot 2i and marks 2i + 1 MSM_SKIP, so that the key's run stays contiguous) - and the next level, eight times
+// shorter, does the same.  So no lane's chain exceeds 2 * MSM_PIECE additions (every entry a run of its own) whatever the scalars are: 2^20 equal scalars are 2^16 lanes of
+// 16 terms, then 2^13, ... - never one chain of 2^20.  N = the level-0 count on the device (*n0) taken through the levels.
+struct MsmAccArgs {
+    const uint32_t *pts, *idx, *keys, *n0;
+    uint32_t level;
+    uint32_t *out_pts, *out_keys, *buckets;
+};
+__device__ __forceinline__ uint32_t msm_level_len(uint32_t n, uint32_t level) {
+    for (uint32_t l = 0; l < level; ++l) n = 2u * ((n + MSM_PIECE - 1) / MSM_PIECE);
+    return n;
+}
+template <class F, uint32_t WORDS, class Load, class Store>
+__device__ __forceinline__ void msm_acc_body(const MsmAccArgs &g, uint32_t i, Load load, Store store) {
+    const uint32_t N = msm_level_len(*g.n0, g.level), a = i * MSM_PIECE;
+    if (a >= N) return;
+    const uint32_t b = min(a + MSM_PIECE, N);
+    const uint32_t prev = a ? g.keys[a - 1] & ~MSM_SKIP : 0xffffffffu, next = b < N ? g.keys[b] & ~MSM_SKIP : 0xffffffffu;
+    g.out_keys[2 * i] = MSM_NONE; g.out_keys[2 * i + 1] = MSM_NONE;
+    Jac<F> acc = {F::zero(), F::one(), F::zero()};
+    uint32_t cur = g.keys[a] & ~MSM_SKIP, j = a;
+    bool first_run = true;
+#pragma unroll 1
+    for (;;) {
+        // one step = at most one addition: an entry joins the run, or a complete run joins its bucket
+        const bool at_end = j >= b;
+        const uint32_t kj = at_end ? 0u : g.keys[j], key = kj & ~MSM_SKIP;
+        const bool flush = at_end || key != cur;
+        const uint32_t *src = nullptr;
+        uint32_t *dst = nullptr;
+        if (flush) {
+            const bool began_earlier = first_run && prev == cur, goes_on = at_end && next == cur;
+            if (cur != MSM_NONE) {
+                if (!began_earlier && !goes_on) { dst = g.buckets + (size_t)cur * WORDS; src = dst; }
+                else {
+                    const uint32_t slot = began_earlier ? 2 * i : 2 * i + 1;
+                    dst = g.out_pts + (size_t)slot * WORDS;
+                    g.out_keys[slot] = cur;
+                    if (began_earlier && goes_on) g.out_keys[2 * i + 1] = cur | MSM_SKIP;
+                }
+            }
+        } else if (!(kj & MSM_SKIP) && key != MSM_NONE) {
+            src = g.pts + (size_t)(g.idx ? g.idx[j] : j) * WORDS;
+        }
+        if (src) {
+            const Jac<F> q = load(src);
+            acc = jac_add_flags<F>(acc, q, F::is_zero(acc.z), F::is_zero(q.z));
+        }
+        if (dst) store(acc, dst);
+        if (at_end) break;
+        if (flush) { first_run = false; acc = {F::zero(), F::one(), F::zero()}; cur = key; }
+        else ++j;
+    }
+}
+// The bucket reduction: lane (lane pair) t = w * groups + g walks the G buckets [base, base + G) of window w from the top with a running sum,
+// two additions per bucket, and leaves S = sum B_b and T = sum (b - base) B_b as two terms of the tail - the one-segment bn254_g{1,2}_msm_batch
+// over 2 * W * groups terms whose scalars the host knows: base * 2^(c w) for S, 2^(c w) for T.
+struct MsmReduceArgs {
+    const uint32_t *buckets; uint32_t G, groups, log2B, count; uint32_t *terms;       // terms: S of every lane, then T of every lane
+};
+template <class F, uint32_t WORDS, class Load, class Store>
+__device__ __forceinline__ void msm_reduce_body(const MsmReduceArgs &g, uint32_t t, Load load, Store store) {
+    const uint32_t w = t / g.groups, base = (w << g.log2B) + (t % g.groups) * g.G;
+    Jac<F> run = {F::zero(), F::one(), F::zero()}, T = run;
+#pragma unroll 1
+    for (uint32_t b = g.G; b-- > 0;) {
+        const Jac<F> q = load(g.buckets + (size_t)(base + b) * WORDS);
+        run = jac_add_flags<F>(run, q, F::is_zero(run.z), F::is_zero(q.z));
+        if (b) T = jac_add_flags<F>(T, run, F::is_zero(T.z), F::is_zero(run.z));
+    }
+    store(run, g.terms + (size_t)t * WORDS);
+    store(T, g.terms + (size_t)(g.count + t) * WORDS);
+}
+struct G1PointIo {
+    __device__ __forceinline__ Jac<FqField> operator()(const uint32_t *w) const { return Jac<FqField>{fe_from_u32x8(w), fe_from_u32x8(w + 8), fe_from_u32x8(w + 16)}; }
+    __device__ __forceinline__ void operator()(const Jac<FqField> &r, uint32_t *o) const { fe_to_u32x8(r.x, o); fe_to_u32x8(r.y, o + 8); fe_to_u32x8(r.z, o + 16); }
+};
+struct G2PointIo {
+    typedef Fq2Field<F2> F;
+    __device__ __forceinline__ Jac<F> operator()(const uint32_t *w) const { return Jac<F>{f2_load((const F2 *)nullptr, w), f2_load((const F2 *)nullptr, w + 16), f2_load((const F2 *)nullptr, w + 32)}; }
+    __device__ __forceinline__ void operator()(const Jac<F> &r, uint32_t *o) const { f2_store(r.x, o); f2_store(r.y, o + 16); f2_store(r.z, o + 32); }
+};
+// `n`: lanes (G2: lane pairs) launched; a lane past the level's entries, or past the reduction's groups, has nothing to do (both lanes of a pair alike)
+__device__ __forceinline__ void msm_point_op(const MsmAccArgs &g, uint32_t i, G1PointIo io) { msm_acc_body<FqField, 24u>(g, i, io, io); }
+__device__ __forceinline__ void msm_point_op(const MsmAccArgs &g, uint32_t i, G2PointIo io) { msm_acc_body<Fq2Field<F2>, 48u>(g, i, io, io); }
+__device__ __forceinline__ void msm_point_op(const MsmReduceArgs &g, uint32_t i, G1PointIo io) { msm_reduce_body<FqField, 24u>(g, i, io, io); }
+__device__ __forceinline__ void msm_point_op(const MsmReduceArgs &g, uint32_t i, G2PointIo io) { msm_reduce_body<Fq2Field<F2>, 48u>(g, i, io, io); }
+template <class Args>
+__global__ void __launch_bounds__(BLOCK) bn254_g1_add_M(Args g, uint32_t n) {
+    const uint32_t idx = blockIdx.x * BLOCK + threadIdx.x;
+    if (idx < n) msm_point_op(g, idx, G1PointIo());
+}
+template <class Args>
+__global__ void __launch_bounds__(BLOCK) bn254_g2_add_M(Args g, uint32_t n) {
+    const uint32_t pair = (blockIdx.x * BLOCK + threadIdx.x) >> 1;
+    if (pair < n) msm_point_op(g, pair, G2PointIo());
+}
 }  // namespace
 
 extern "C" {
@@ -269,6 +466,41 @@ int bn254_launch_msm_fold_M(int g, const void *pieces, size_t count, hipStream_t
     unsigned grid = (unsigned)(((g == 1 ? count : 2 * count) + BLOCK - 1) / BLOCK);
     if (g == 1) hipLaunchKernelGGL(bn254_g1_add_M<true>, dim3(grid), dim3(BLOCK), 0, s, (const BnSegPiece *)pieces, (uint32_t)count);
     else hipLaunchKernelGGL(bn254_g2_add_M<true>, dim3(grid), dim3(BLOCK), 0, s, (const BnSegPiece *)pieces, (uint32_t)count);
+    return (int)hipGetLastError();
+}
+// bn254_g{1,2}_msm, bucket route.  n terms (< 2^32 / W entries in all), window width c, W windows.
+// digits: scatter == 0 counts the terms per key into `counts` (zeroed by the caller); scatter != 0 writes (index, key) at the scanned counts
+int bn254_launch_msm_digits_M(const void *k, size_t n, unsigned c, unsigned W, void *counts, void *idx, void *keys, int scatter, hipStream_t s) {
+    const MsmDigitsOp op = {(const uint32_t *)k, (uint32_t)n, c, W, (uint32_t *)counts, (uint32_t *)idx, (uint32_t *)keys, scatter};
+    hipLaunchKernelGGL(bn254_fr_decode_k<MsmDigitsOp>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, op);
+    return (int)hipGetLastError();
+}
+// counts[0..total) -> their exclusive scan in place, the grand total to *n0; total <= 2^20, `tiles`: 1024 words of scratch
+int bn254_launch_msm_scan_M(void *counts, size_t total, void *tiles, void *n0, hipStream_t s) {
+    const unsigned blocks = (unsigned)((total + MSM_TILE - 1) / MSM_TILE);
+    if (blocks == 0 || blocks > MSM_TILE) return (int)hipErrorInvalidValue;
+    for (int mode = 0; mode < 3; ++mode) {
+        const MsmScanOp op = {(uint32_t *)counts, (uint32_t)total, (uint32_t *)tiles, (uint32_t *)n0, mode};
+        hipLaunchKernelGGL(bn254_fr_decode_k<MsmScanOp>, dim3(mode == 1 ? 1u : blocks), dim3(256), 0, s, op);
+    }
+    return (int)hipGetLastError();
+}
+unsigned bn254_msm_piece_M(void) { return MSM_PIECE; }
+// one accumulation level over `lanes` lanes (G2: lane pairs); idx != NULL only at level 0
+int bn254_launch_msm_bucket_M(int g, const void *pts, const void *idx, const void *keys, const void *n0, unsigned level, void *out_pts, void *out_keys, void *buckets,
+                              size_t lanes, hipStream_t s) {
+    const MsmAccArgs a = {(const uint32_t *)pts, (const uint32_t *)idx, (const uint32_t *)keys, (const uint32_t *)n0, level, (uint32_t *)out_pts, (uint32_t *)out_keys, (uint32_t *)buckets};
+    const unsigned grid = (unsigned)(((g == 1 ? lanes : 2 * lanes) + BLOCK - 1) / BLOCK);
+    if (g == 1) hipLaunchKernelGGL(bn254_g1_add_M<MsmAccArgs>, dim3(grid), dim3(BLOCK), 0, s, a, (uint32_t)lanes);
+    else hipLaunchKernelGGL(bn254_g2_add_M<MsmAccArgs>, dim3(grid), dim3(BLOCK), 0, s, a, (uint32_t)lanes);
+    return (int)hipGetLastError();
+}
+// the bucket reduction: count = W * groups lanes (lane pairs), terms = 2 * count points
+int bn254_launch_msm_reduce_M(int g, const void *buckets, unsigned G, unsigned groups, unsigned c, size_t count, void *terms, hipStream_t s) {
+    const MsmReduceArgs a = {(const uint32_t *)buckets, G, groups, c, (uint32_t)count, (uint32_t *)terms};
+    const unsigned grid = (unsigned)(((g == 1 ? count : 2 * count) + BLOCK - 1) / BLOCK);
+    if (g == 1) hipLaunchKernelGGL(bn254_g1_add_M<MsmReduceArgs>, dim3(grid), dim3(BLOCK), 0, s, a, (uint32_t)count);
+    else hipLaunchKernelGGL(bn254_g2_add_M<MsmReduceArgs>, dim3(grid), dim3(BLOCK), 0, s, a, (uint32_t)count);
     return (int)hipGetLastError();
 }
 }

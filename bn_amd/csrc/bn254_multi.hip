@@ -543,4 +543,39 @@ int bn254_g2_msm_batch_multi(bn254_multi *mh, const bn_g2 *p, const bn_fr *k, co
     });
 }
 
+// One large sum over the ranks: rank g sums its term shard [n*g/G, n*(g+1)/G) with bn254_g{1,2}_msm (normalised; an empty shard gives zero),
+// rank 0 adds the G partial sums as one bn254_g{1,2}_msm_batch segment with scalars one.  Host buffers in, host buffers between: no exchange.
+extern "C++" {
+template <class P, class One, class Sum>
+static int msm1_multi(bn254_multi *mh, const P *p, const bn_fr *k, size_t n, P *out, const One &one_rank, const Sum &sum) {
+    if (int e = bn_msm1_check(p, k, n, out)) return e;                      // the argument checks first, as on one device
+    if (!mh) return BN254_E_BAD_ARG;
+    std::lock_guard<std::mutex> lk(mh->mu);
+    const size_t G = mh->ctx.size();
+    std::vector<int> rcs(G, BN254_OK);
+    std::vector<P> part(G);
+    const std::thread::id caller = std::this_thread::get_id();
+    run_workers((int)G, [&](int g) {
+        BnAffinityScope pin(mh->cpus[(size_t)g], caller);
+        rcs[g] = bn_no_throw([&]() -> int {
+            const size_t lo = n * (size_t)g / G, hi = n * ((size_t)g + 1) / G;
+            return one_rank(mh->ctx[(size_t)g], hi > lo ? p + lo : nullptr, hi > lo ? k + lo : nullptr, hi - lo, &part[(size_t)g]);
+        });
+    }, true);
+    for (int rc : rcs) if (rc) return rc;
+    std::vector<bn_fr> ones(G);
+    for (auto &o : ones) bn_fr_one(&o);
+    const size_t off[2] = {0, G};
+    return sum(mh->ctx[0], part.data(), ones.data(), off, 1, out);
+}
+}  // extern "C++"
+int bn254_g1_msm_multi(bn254_multi *mh, const bn_g1 *p, const bn_fr *k, size_t n, bn_g1 *out) {
+    BnDeviceGuard dev_guard;
+    return bn_no_throw([&] { return msm1_multi(mh, p, k, n, out, bn254_g1_msm, bn254_g1_msm_batch); });
+}
+int bn254_g2_msm_multi(bn254_multi *mh, const bn_g2 *p, const bn_fr *k, size_t n, bn_g2 *out) {
+    BnDeviceGuard dev_guard;
+    return bn_no_throw([&] { return msm1_multi(mh, p, k, n, out, bn254_g2_msm, bn254_g2_msm_batch); });
+}
+
 }  // extern "C"

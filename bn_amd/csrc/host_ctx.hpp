@@ -89,6 +89,10 @@ struct bn254_ctx {
     BnBuf seg_plan;                     // work lists of the segmented fold (bn254_pairing_product_batch*, behind them the Miller pieces of ..._prepared_native), device side ...
     BnBuf seg_plan_host{nullptr, 0, true};  // ... and their pinned staging, rewritten only after seg_plan_ev (its last copy) completed
     hipEvent_t seg_plan_ev = nullptr;
+    BnBuf msm_ws;                       // bucket route of bn254_g{1,2}_msm: counts, sorted indices and keys, buckets, partial sums, tail terms
+    BnBuf msm_scal;                     // ... and the tail's scalars (Montgomery images of 2^(c w) and base * 2^(c w)) for window width msm_scal_c
+    std::vector<uint64_t> msm_scal_host;    // their host image (kept while the copy may be in flight; rebuilt only when the width changes)
+    long msm_scal_c = -1;
     BnBuf stage[3];                     // device staging of the small host-buffer entry points
     BnSlot slot[BN_MAX_SLOTS];          // pipelined path (bn254_multi.hip)
     // leases of those slots: a batch of up to one chunk takes ONE of the first two (two callers overlap on the GPU - the number
@@ -173,6 +177,9 @@ int bn_mul_dev(bn254_ctx *ctx, int g, const void *d_p, const void *d_k, void *d_
 int bn_seg_check(const void *p, const void *q, const size_t *offsets, size_t m, const void *out);
 // the same checks for bn254_g{1,2}_msm_batch* (points, scalars)
 int bn_msm_check(const void *p, const void *k, const size_t *offsets, size_t m, const void *out);
+// argument checks of bn254_g{1,2}_msm* (one sum of n terms); no device involved
+int bn_msm1_check(const void *p, const void *k, size_t n, const void *out);
+void bn_fr_one(bn_fr *out);                                        // the Montgomery image of one
 
 extern "C" {
 // bn254_kernels_b.hip
@@ -215,6 +222,12 @@ int bn254_launch_g1_add_M(const void *a, const void *b, void *out, size_t n, int
 int bn254_launch_g2_add_M(const void *a, const void *b, void *out, size_t n, int negate_b, hipStream_t s);
 int bn254_launch_msm_mul_M(int g, const void *p, const void *k, void *out, size_t n, void *table, hipStream_t s);
 int bn254_launch_msm_fold_M(int g, const void *pieces, size_t count, hipStream_t s);
+int bn254_launch_msm_digits_M(const void *k, size_t n, unsigned c, unsigned W, void *counts, void *idx, void *keys, int scatter, hipStream_t s);
+int bn254_launch_msm_scan_M(void *counts, size_t total, void *tiles, void *n0, hipStream_t s);
+unsigned bn254_msm_piece_M(void);
+int bn254_launch_msm_bucket_M(int g, const void *pts, const void *idx, const void *keys, const void *n0, unsigned level, void *out_pts, void *out_keys, void *buckets,
+                              size_t lanes, hipStream_t s);
+int bn254_launch_msm_reduce_M(int g, const void *buckets, unsigned G, unsigned groups, unsigned c, size_t count, void *terms, hipStream_t s);
 // bn254_measure.hip
 int bn254_launch_gather_K(const void *d_records, size_t records, size_t record_bytes, const void *d_index, size_t n, void *d_out, hipStream_t s);
 }

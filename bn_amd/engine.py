@@ -55,6 +55,13 @@ def _msm_args(p, k, offsets, words):
     return p, k, o, np.empty((o.size - 1, words), np.uint64)
 
 
+def _msm1_args(p, k, words):
+    p = _arr(p, words) if len(p) else np.zeros((0, words), np.uint64)
+    k = _arr(k, 4) if len(k) else np.zeros((0, 4), np.uint64)
+    _same_len(p, k)
+    return p, k, np.empty(words, np.uint64)
+
+
 class Engine:
     """one context = one GPU (include/bn254_hip.h: bn254_ctx)"""
 
@@ -177,6 +184,19 @@ class Engine:
         """the same over G2 -> (m, 24) uint64"""
         p, k, o, out = _msm_args(p, k, offsets, G2_WORDS)
         _native.check(self._lib.bn254_g2_msm_batch(self._h, _p(p), _p(k), _p(o), o.size - 1, _p(out)))
+        return out
+
+    def g1_msm(self, p, k):
+        """normalize(sum of p[i] * k[i] over ALL terms) -> (12,) uint64: one large multi-scalar multiplication, by the bucket method from
+        the option msm_bucket_min terms on; the bytes of g1_msm_batch(p, k, [0, n])[0] (include/bn254_hip.h bn254_g1_msm)"""
+        p, k, out = _msm1_args(p, k, G1_WORDS)
+        _native.check(self._lib.bn254_g1_msm(self._h, _p(p), _p(k), p.shape[0], _p(out)))
+        return out
+
+    def g2_msm(self, p, k):
+        """the same over G2 -> (24,) uint64"""
+        p, k, out = _msm1_args(p, k, G2_WORDS)
+        _native.check(self._lib.bn254_g2_msm(self._h, _p(p), _p(k), p.shape[0], _p(out)))
         return out
 
     def g1_add_batch(self, a, b, negate_b=False):
@@ -385,6 +405,13 @@ class Engine:
         o = _offsets(offsets)
         _native.check(self._lib.bn254_g2_msm_batch_dev(self._h, d_p, d_k, _p(o), o.size - 1, d_out, stream))
 
+    def g1_msm_dev(self, d_p, d_k, n, d_out, stream=0):
+        """device pointers p, k (n terms) and out (ONE point), ordered on `stream`"""
+        _native.check(self._lib.bn254_g1_msm_dev(self._h, d_p, d_k, n, d_out, stream))
+
+    def g2_msm_dev(self, d_p, d_k, n, d_out, stream=0):
+        _native.check(self._lib.bn254_g2_msm_dev(self._h, d_p, d_k, n, d_out, stream))
+
     def gt_mul_dev(self, d_a, d_b, d_out, n, stream=0):
         _native.check(self._lib.bn254_gt_mul_batch_dev(self._h, d_a, d_b, d_out, n, stream))
 
@@ -545,6 +572,17 @@ class MultiEngine:
     def g2_msm_batch(self, p, k, offsets):
         p, k, o, out = _msm_args(p, k, offsets, G2_WORDS)
         _native.check(self._lib.bn254_g2_msm_batch_multi(self._h, _p(p), _p(k), _p(o), o.size - 1, _p(out)))
+        return out
+
+    def g1_msm(self, p, k):
+        """Engine.g1_msm with the terms sharded over the ranks; rank 0 adds the partial sums"""
+        p, k, out = _msm1_args(p, k, G1_WORDS)
+        _native.check(self._lib.bn254_g1_msm_multi(self._h, _p(p), _p(k), p.shape[0], _p(out)))
+        return out
+
+    def g2_msm(self, p, k):
+        p, k, out = _msm1_args(p, k, G2_WORDS)
+        _native.check(self._lib.bn254_g2_msm_multi(self._h, _p(p), _p(k), p.shape[0], _p(out)))
         return out
 
     def g2_prepare(self, q):

@@ -119,6 +119,20 @@ inline std::vector<G2> g2_msm_batch(const std::vector<G2> &p, const std::vector<
                              out.size(), reinterpret_cast<bn_g2 *>(out.data())));
     return out;
 }
+// normalize(sum of p[i] * k[i] over ALL terms): one large multi-scalar multiplication - the bucket (Pippenger) method from
+// BN254_OPT_MSM_BUCKET_MIN terms on, the one-segment g1_msm_batch below it; the same bytes either way
+inline G1 g1_msm(const std::vector<G1> &p, const std::vector<Fr> &k) {
+    if (p.size() != k.size()) throw std::invalid_argument("g1_msm: length mismatch");
+    G1 out;
+    check(bn254_g1_msm(nullptr, reinterpret_cast<const bn_g1 *>(p.data()), reinterpret_cast<const bn_fr *>(k.data()), p.size(), reinterpret_cast<bn_g1 *>(&out)));
+    return out;
+}
+inline G2 g2_msm(const std::vector<G2> &p, const std::vector<Fr> &k) {
+    if (p.size() != k.size()) throw std::invalid_argument("g2_msm: length mismatch");
+    G2 out;
+    check(bn254_g2_msm(nullptr, reinterpret_cast<const bn_g2 *>(p.data()), reinterpret_cast<const bn_fr *>(k.data()), p.size(), reinterpret_cast<bn_g2 *>(&out)));
+    return out;
+}
 // ok[j] = (product of segment j == Gt::one()): the predicate of a block of pairing checks
 inline std::vector<bool> pairing_check_batch(const std::vector<G1> &p, const std::vector<G2> &q, const std::vector<size_t> &offsets) {
     const std::vector<Gt> r = pairing_product_batch(p, q, offsets);
@@ -225,6 +239,19 @@ public:
         std::vector<G2> out(offsets.size() - 1);
         check(bn254_g2_msm_batch_multi(m_, reinterpret_cast<const bn_g2 *>(p.data()), reinterpret_cast<const bn_fr *>(k.data()), offsets.data(),
                                        out.size(), reinterpret_cast<bn_g2 *>(out.data())));
+        return out;
+    }
+    // bn::g1_msm / g2_msm with the terms sharded over the GPUs; GPU 0 adds the partial sums
+    G1 g1_msm(const std::vector<G1> &p, const std::vector<Fr> &k) {
+        if (p.size() != k.size()) throw std::invalid_argument("g1_msm: length mismatch");
+        G1 out;
+        check(bn254_g1_msm_multi(m_, reinterpret_cast<const bn_g1 *>(p.data()), reinterpret_cast<const bn_fr *>(k.data()), p.size(), reinterpret_cast<bn_g1 *>(&out)));
+        return out;
+    }
+    G2 g2_msm(const std::vector<G2> &p, const std::vector<Fr> &k) {
+        if (p.size() != k.size()) throw std::invalid_argument("g2_msm: length mismatch");
+        G2 out;
+        check(bn254_g2_msm_multi(m_, reinterpret_cast<const bn_g2 *>(p.data()), reinterpret_cast<const bn_fr *>(k.data()), p.size(), reinterpret_cast<bn_g2 *>(&out)));
         return out;
     }
 };

@@ -23,6 +23,7 @@
  *   bn254_g1_msm_batch     out[j] = normalize(fold(G1::zero(), |acc, i| acc + p[i] * k[i])) over terms [offsets[j], offsets[j+1])
  *                                                                                    lib.rs:103-120,88-95, groups/mod.rs:250-311
  *   bn254_g2_msm_batch     same over G2                                             lib.rs:146-163,131-138
+ *   bn254_g1_msm / bn254_g2_msm  out[0] = that fold over ALL n terms (one large sum; the bucket method from BN254_OPT_MSM_BUCKET_MIN terms on)
  *   bn254_g1/g2_add_batch  out[i] = a[i] + b[i] / a[i] - b[i] (raw Jacobian limbs)       lib.rs:103-114,146-157, groups/mod.rs:275-347
  *   bn254_g2_precompute    coeffs[i][0..102) = q[i].to_affine().precompute().coeffs   groups/mod.rs:557-588 (Q != infinity)
  *   bn254_pairing_prepared_batch  out[i] = final_exponentiation(prepared.miller_loop(p[i]))   groups/mod.rs:486-519,768
@@ -53,7 +54,8 @@
  *     slot: two callers with batches of up to one machine round (256 pairings per CU: 2^16 on an MI355X) run concurrently on two
  *     streams (the number of streams the GPU overlaps without loss), further callers and multi-chunk batches queue; every other
  *     entry point serialises its callers on the context (bn254_pairing_product_batch too, except when every segment holds one pair: then
- *     it IS bn254_pairing_batch; likewise bn254_g{1,2}_msm_batch, which are bn254_g{1,2}_mul_batch when every segment holds one term).
+ *     it IS bn254_pairing_batch; likewise bn254_g{1,2}_msm_batch, which are bn254_g{1,2}_mul_batch when every segment holds one term;
+ *     bn254_g{1,2}_msm serialise on the context on either route, except for n == 1 below the bucket threshold: bn254_g{1,2}_mul_batch again).
  *     bn254_pairing_product_batch_prepared_native serialises on the context like them; its handle is immutable and shared freely.
  *     Use one context per thread (or bn254_multi_*) for more overlap;
  *     bn254_ctx_set_option is atomic, but set options before concurrent use: a call in flight may run some
@@ -63,7 +65,10 @@
  *     and serialise on that scratch; the caller still owns the ordering of its OWN buffers between streams.
  *     bn254_pairing_product_batch_dev and bn254_g{1,2}_msm_batch_dev read their HOST `offsets` before they return (the launches are planned
  *     from them), and so does bn254_pairing_product_batch_prepared_native_dev (its `d_q_index` is device memory and read by the kernels only);
- *     the term workspace, window tables and work list of bn254_g{1,2}_msm_batch_dev are such context-owned scratch.
+ *     the term workspace, window tables and work list of bn254_g{1,2}_msm_batch_dev are such context-owned scratch, and so is everything
+ *     bn254_g{1,2}_msm_dev keeps (sorted indices, counts, buckets, partial sums, tail terms).  bn254_g{1,2}_msm_dev plans its launches from
+ *     upper bounds and reads nothing back; it synchronises the caller's stream only in a call that changes the window width (the tail's
+ *     scalars are rebuilt and uploaded then), and briefly on the upload of the tail's work list like bn254_g{1,2}_msm_batch_dev.
  */
 #ifndef BN254_HIP_H
 #define BN254_HIP_H
@@ -110,13 +115,13 @@ int bn254_ctx_set_mapping(bn254_ctx *ctx, int mapping);
    Every policy of the host side is a per-context option whose default is derived from the device the context is bound to (its
    compute-unit count, `CUs` below); the call paths read nothing from the environment.  value < 0 restores the default;
    bn254_ctx_get_option reports the EFFECTIVE value - or -1 for the four options whose default is decided PER CALL from the batch
-   size (BN254_OPT_PRODUCT_CHUNK / _PER_WAVE / _BFLY, BN254_OPT_PIPELINE_CHUNK) while none is set explicitly.  The size options
+   size (BN254_OPT_PRODUCT_CHUNK / _PER_WAVE / _BFLY, BN254_OPT_PIPELINE_CHUNK; likewise BN254_OPT_MSM_WINDOW_BITS) while none is set explicitly.  The size options
    (BN254_OPT_WAVE_PAIRING_MAX, _WAVE_FE_MAX, _QUAD_MAX, _ROUND_PAIRS, _PIPELINE_CHUNK) accept at most 2^22: what one launch addresses
    with 32-bit offsets; a value above is rejected with BN254_E_BAD_ARG (larger batches are cut into sub-launches regardless).  ctx == NULL addresses the default context of the current device.  An option
    may be changed at any time; a call in flight may see the old or the new value between two of its launches - harmless, because
    every option selects between kernels that return the same bytes (the one exception is stated at BN254_OPT_GT_POW_MODE).
    For experiments only, the variables BN254_WAVE_PAIRING_MAX, BN254_WAVE_FE_MAX, BN254_QUAD_MAX, BN254_MILLER_SHARED, BN254_GT_POW_MODE,
-   BN254_PRODUCT_CHUNK / _PER_WAVE / _BFLY, BN254_ROUND_PAIRS, BN254_PIPELINE_CHUNK / _SLOTS, BN254_STREAM_STOP_AT_ERROR, BN254_MULTI_EXCHANGE (rccl | peer) and
+   BN254_PRODUCT_CHUNK / _PER_WAVE / _BFLY, BN254_ROUND_PAIRS, BN254_PIPELINE_CHUNK / _SLOTS, BN254_STREAM_STOP_AT_ERROR, BN254_MSM_BUCKET_MIN, BN254_MSM_WINDOW_BITS, BN254_MSM_CHUNK, BN254_MULTI_EXCHANGE (rccl | peer) and
    BN254_MULTI_AFFINITY (0: no thread pinning) are
    read ONCE per process, when the first context is created, and seed the options of every context created afterwards. */
 enum {
@@ -145,7 +150,12 @@ enum {
                                        record (groups/mod.rs:165-175) -: `count` ends WITH the first record whose status is non-zero and
                                        `consumed` behind it (out[] and status[] beyond `count` are unspecified: the batch decoder has
                                        already run over the records that follow); 0 (default): decode every record, report every status */
-    BN254_OPT_COUNT_ = 13
+    BN254_OPT_MSM_BUCKET_MIN = 13,  /* bn254_g{1,2}_msm: terms from which the bucket method runs; below, the one-segment bn254_g{1,2}_msm_batch launches.
+                                       0 = always buckets.  Default: the measured crossover, 2^19 for G1 (the value reported) and 2^18 for G2
+                                       (profiles/r10_msm_bucket.txt) */
+    BN254_OPT_MSM_WINDOW_BITS = 14, /* window width c of the bucket method, 1..16.  Default: by n, the best measured width per size (8 ... 14) */
+    BN254_OPT_MSM_CHUNK = 15,       /* terms per pass of the bucket method, 1..2^22 (positions are 32-bit).  Default 2^20 */
+    BN254_OPT_COUNT_ = 16
 };
 int bn254_ctx_set_option(bn254_ctx *ctx, int key, long value);
 int bn254_ctx_get_option(bn254_ctx *ctx, int key, long *value);
@@ -189,11 +199,25 @@ int bn254_g2_mul_batch(bn254_ctx *ctx, const bn_g2 *p, const bn_fr *k, bn_g2 *ou
    list per segment and per 4 terms.
    Made for many short and medium segments (verifier workloads).  There is NO bucket (Pippenger) method here: ONE prover-sized segment
    (2^20 terms) is computed correctly but at the cost of a full scalar-multiplication chain per term, and its fold levels run on ever
-   fewer lanes.
+   fewer lanes.  One large sum belongs to bn254_g{1,2}_msm below, which has the bucket method.
    Errors (BN254_E_BAD_ARG, checked before any device is touched): offsets == NULL with m > 0, offsets[0] != 0, decreasing offsets,
    n > 2^40, a NULL p / k (n > 0) or out.  m == 0 returns BN254_OK and writes nothing. */
 int bn254_g1_msm_batch(bn254_ctx *ctx, const bn_g1 *p, const bn_fr *k, const size_t *offsets, size_t m, bn_g1 *out);
 int bn254_g2_msm_batch(bn254_ctx *ctx, const bn_g2 *p, const bn_fr *k, const size_t *offsets, size_t m, bn_g2 *out);
+/* One large multi-scalar multiplication: out[0] = normalize(fold(G::zero(), |acc, i| acc + p[i] * k[i])) over all n terms - exactly what
+   bn254_g{1,2}_msm_batch return for the one segment offsets = {0, n}, bit for bit (normalisation makes the image unique).  Inputs as there;
+   n == 0 or a sum at infinity gives G::zero() = (0, 1, 0).
+   Below BN254_OPT_MSM_BUCKET_MIN terms the call IS that one-segment launch sequence.  From there on the bucket (Pippenger) method: the
+   canonical integer of every scalar is cut into W = ceil(254 / c) unsigned c-bit digits (BN254_OPT_MSM_WINDOW_BITS), a counting sort groups
+   the term indices by (window, digit), and the buckets are summed with the complete addition in levels of at most 16 consecutive entries per
+   lane / lane pair - no serial chain depends on the scalars: n equal scalars are n / 16 lanes, then n / 128, ... .  Groups of 16 buckets are
+   reduced by running sums to two points each, and these 2 W 2^c / 16 points, with host-known scalars, are one bn254_g{1,2}_msm_batch segment
+   that folds, normalises once and writes out.  Calls above BN254_OPT_MSM_CHUNK terms run as several passes into the same buckets.
+   Workspace (context-owned), t = min(n, chunk) terms, V = 96 / 192 bytes: 8 W t bytes of (index, key), (4 + V) W 2^c bytes of counts and
+   buckets, at most (V + 4) (W t / 7 + 64) bytes of partial sums, (V + 32) W 2^c / 8 bytes of tail terms, and the workspace of the tail.
+   Errors (BN254_E_BAD_ARG, checked before any device is touched): a NULL p / k with n > 0, a NULL out, n > 2^40. */
+int bn254_g1_msm(bn254_ctx *ctx, const bn_g1 *p, const bn_fr *k, size_t n, bn_g1 *out);
+int bn254_g2_msm(bn254_ctx *ctx, const bn_g2 *p, const bn_fr *k, size_t n, bn_g2 *out);
 /* out[i] = a[i] + b[i]  (negate_b != 0: a[i] - b[i] = a[i] + (-b[i])): `Add`/`Sub` of lib.rs:103-114,146-157 over
    groups/mod.rs:275-347.  The reference's own formulas and branches (zero operands, equal points), so the Jacobian limbs
    returned are the reference's - no normalization involved.  `Neg` is 0 - b. */
@@ -305,6 +329,10 @@ int bn254_pairing_product_batch_multi(bn254_multi *mh, const bn_g1 *p, const bn_
    (offsets[j] == n: the last rank), with all of its terms.  No exchange. */
 int bn254_g1_msm_batch_multi(bn254_multi *mh, const bn_g1 *p, const bn_fr *k, const size_t *offsets, size_t m, bn_g1 *out);
 int bn254_g2_msm_batch_multi(bn254_multi *mh, const bn_g2 *p, const bn_fr *k, const size_t *offsets, size_t m, bn_g2 *out);
+/* bn254_g{1,2}_msm over the ranks: rank g sums its term shard [n*g/G, n*(g+1)/G) (normalised; an empty shard gives zero), then rank 0 adds
+   the G partial sums as one bn254_g{1,2}_msm_batch segment with scalars one.  No device-to-device exchange; same bytes as one device. */
+int bn254_g1_msm_multi(bn254_multi *mh, const bn_g1 *p, const bn_fr *k, size_t n, bn_g1 *out);
+int bn254_g2_msm_multi(bn254_multi *mh, const bn_g2 *p, const bn_fr *k, size_t n, bn_g2 *out);
 
 /* native prepared-G2 mode over the GPUs of the handle.  ONE point (nq == 1) is prepared on every rank's GPU and n pairings shard like
    bn254_pairing_batch_multi; nq > 1 points are sharded by the same rule ([nq*g/G, nq*(g+1)/G) on rank g) and then pair with exactly n == nq
@@ -367,6 +395,10 @@ int bn254_pairing_product_batch_dev(bn254_ctx *ctx, const void *d_p, const void 
 /* bn254_g{1,2}_msm_batch on device-resident p, k, out (m points); `offsets` (m+1 entries) is HOST memory and may be freed on return */
 int bn254_g1_msm_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, const size_t *offsets, size_t m, void *d_out, void *stream);
 int bn254_g2_msm_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, const size_t *offsets, size_t m, void *d_out, void *stream);
+/* bn254_g{1,2}_msm on device-resident p, k (n terms) and out (ONE point), ordered on `stream`.  The bucket route plans from upper bounds: no
+   count is read back; the call synchronises `stream` only when it changes the window width (see Threading above) */
+int bn254_g1_msm_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, size_t n, void *d_out, void *stream);
+int bn254_g2_msm_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, size_t n, void *d_out, void *stream);
 int bn254_g2_precompute_dev(bn254_ctx *ctx, const void *d_q, void *d_coeffs, size_t n, void *stream);
 int bn254_miller_prepared_dev(bn254_ctx *ctx, const void *d_p, const void *d_coeffs, int shared, void *d_f, size_t n, void *stream);
 /* native prepared-G2 mode on device-resident inputs.  bn254_g2_prepare_dev allocates the handle's table (that part synchronises with the
@@ -405,7 +437,7 @@ int bn254_tile_dev(bn254_ctx *ctx, const void *d_record, size_t record_bytes, si
    accumulated duration and launch count per kernel since the last reset (this is what bench.py's roofline uses). */
 int bn254_profile_enable(bn254_ctx *ctx, int on);
 int bn254_profile_reset(bn254_ctx *ctx);
-/* kernel: "miller", "miller_shared", "miller_wave", "miller_quad", "pairing_wave", "final_exp", "final_exp_wave", "final_exp_quad", "exp_by_neg_z", "gt_product", "gt_tail", "gt_segment", "gt_tail_seg", "g1_mul", "g2_mul", "gt_mul", "gt_pow", "g2_precompute", "miller_prepared", "g2_prepare_native", "miller_native", "miller_native_shared", "miller_native_seg", "g2_gather", "wire_encode", "wire_decode", "gt_inverse", "g1_add", "g2_add", "g1_msm_mul", "g1_msm_fold", "g2_msm_mul", "g2_msm_fold".
+/* kernel: "miller", "miller_shared", "miller_wave", "miller_quad", "pairing_wave", "final_exp", "final_exp_wave", "final_exp_quad", "exp_by_neg_z", "gt_product", "gt_tail", "gt_segment", "gt_tail_seg", "g1_mul", "g2_mul", "gt_mul", "gt_pow", "g2_precompute", "miller_prepared", "g2_prepare_native", "miller_native", "miller_native_shared", "miller_native_seg", "g2_gather", "wire_encode", "wire_decode", "gt_inverse", "g1_add", "g2_add", "g1_msm_mul", "g1_msm_fold", "g2_msm_mul", "g2_msm_fold", "g1_msm_digits", "g1_msm_bucket", "g1_msm_reduce", "g2_msm_digits", "g2_msm_bucket", "g2_msm_reduce".
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);
 /* issue-rate ceiling of v_mad_u64_u32 (the 32x32+64 multiply-accumulate every field product is built from) at
