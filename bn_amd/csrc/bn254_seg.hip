@@ -1,0 +1,346 @@
+// Segmented operations of the BN254 engine (include/bn254_hip.h): the batched multi-pairings bn254_pairing_product_batch*, the segmented
+// multi-scalar multiplications bn254_g{1,2}_msm_batch* and the one large sum bn254_g{1,2}_msm* with its bucket route.  Host code only: the
+// plans are host_plan.hpp's, the kernels live in bn254_kernels_{b,w,mul}.hip.  Compiled like every unit (bn254_hip.hip: the flags).
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "host_ctx.hpp"
+
+// ---- one executor for a segmented plan
+// The values (Fq12 / Jacobian points, V bytes each) are cut into chunks of at most `chunk`; a segment that crosses a cut carries its partial
+// result into value slot 0 of the next chunk, in front of that chunk's values.  Per chunk: produce(chunk index, chunk, slot 1, extra) writes
+// the values, then the levels of the segmented fold - every piece folds at most `fold` consecutive values; a segment with more values is cut into
+// pieces whose partial results the next level folds, so no lane runs a chain longer than fold - 1 operations and a segment of L values takes
+// ceil(log_fold L) levels - or, `small`, the ragged tail, then the carry copy.  The host builds every level's work list up front.
+// The work lists: ONE copy per call through the context's pinned staging, which is rewritten only after its previous copy completed (so the
+// caller's `offsets` may be freed as soon as the call returns); cut(chunks) may name Miller pieces to place behind the fold's pieces in the
+// same copy (bn254_pairing_product_batch_prepared_native; `extra`: where they are on the device) or return NULL.
+namespace {
+struct BnSegSpec { size_t V, fold, chunk; bool snap, small; };
+int bn_seg_upload(bn254_ctx *c, const std::vector<BnSegPiece> &pieces, hipStream_t s, const std::vector<BnMillerPiece> *miller) {
+    int rc;
+    const size_t fold_bytes = pieces.size() * sizeof(BnSegPiece), bytes = fold_bytes + (miller ? miller->size() * sizeof(BnMillerPiece) : 0);
+    if (c->seg_plan_ev) HIP_TRY(hipEventSynchronize(c->seg_plan_ev));
+    else HIP_TRY(hipEventCreateWithFlags(&c->seg_plan_ev, hipEventDisableTiming));
+    if ((rc = c->seg_plan_host.reserve(bytes)) || (rc = c->seg_plan.reserve(bytes))) return rc;
+    if (fold_bytes) memcpy(c->seg_plan_host.p, pieces.data(), fold_bytes);
+    if (bytes > fold_bytes) memcpy((char *)c->seg_plan_host.p + fold_bytes, miller->data(), bytes - fold_bytes);
+    HIP_TRY(hipMemcpyAsync(c->seg_plan.p, c->seg_plan_host.p, bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(c->seg_plan_ev, s));
+    return BN254_OK;
+}
+// fold(tail, pieces, count) enqueues one launch over `count` pieces of the device-side work list; off is HOST memory; scratch guard held by the caller
+template <class Cut, class Produce, class Fold>
+int bn_seg_run(bn254_ctx *c, const BnSegSpec &sp, const size_t *off, size_t m, void *d_out, hipStream_t s, Cut cut, Produce produce, Fold fold) {
+    int rc = c->ws.reserve(seg_ws_values(sp.chunk, sp.fold) * sp.V); if (rc) return rc;
+    char *const ws = (char *)c->ws.p;
+    std::vector<BnSegPiece> pieces;
+    std::vector<SegChunk> chunks;
+    if (!seg_plan(off, m, sp.chunk, sp.small, ws, (char *)d_out, pieces, chunks, sp.V, sp.fold, sp.snap)) return BN254_E_INTERNAL;
+    if ((rc = bn_seg_upload(c, pieces, s, cut(chunks)))) return rc;
+    const BnSegPiece *list = (const BnSegPiece *)c->seg_plan.p;
+    const void *extra = list + pieces.size();
+    const size_t carry_slot = sp.chunk + 1 + seg_partials_max(sp.chunk, sp.fold);
+    for (size_t ci = 0; ci < chunks.size(); ++ci) {
+        const SegChunk &ch = chunks[ci];
+        if ((rc = produce(ci, ch, ws + sp.V, extra))) return rc;
+        for (const SegLaunch &l : ch.launches) {
+            if (l.tail) rc = fold(true, list + l.first, l.count);
+            else rc = bn_for_parts(l.count, BN_LAUNCH_MAX, [&](size_t lo, size_t cnt) { return fold(false, list + l.first + lo, cnt); });
+            if (rc) return rc;
+        }
+        if (ch.carry_out)                 // the segment that goes on: its partial result becomes value slot 0 of the next chunk
+            HIP_TRY(hipMemcpyAsync(ws, ws + carry_slot * sp.V, sp.V, hipMemcpyDeviceToDevice, s));
+    }
+    return BN254_OK;
+}
+const auto bn_no_cut = [](const std::vector<SegChunk> &) -> const std::vector<BnMillerPiece> * { return nullptr; };
+// the fold of Fq12 values: lane pairs (bn254_gt_mul_B<true>) or, in the ragged tail, one wave per piece, product and exponentiation (bn254_gt_tail_W<true>)
+auto bn_gt_fold(bn254_ctx *c, hipStream_t s) {
+    return [c, s](bool tail, const BnSegPiece *list, size_t cnt) -> int {
+        BnScope sc(c, s, tail ? "gt_tail_seg" : "gt_segment");
+        return tail ? bn254_launch_gt_tail_seg_W(list, cnt, s) : bn254_launch_gt_fold_seg_B(list, cnt, s);
+    };
+}
+}  // namespace
+
+// ---- batched multi-pairing: m independent products over CSR segments (bn254_pairing_product_batch*)
+// The pairs are cut into chunks of at most one machine round (bn_round_pairs), at the last segment boundary inside the round when there
+// is one.  Per chunk: the Miller values (bn_launch_miller, NAF: they only meet a final exponentiation), then the fold in pieces of BN_SEG_FOLD.
+// Small route: one chunk whose Miller values come from the one-per-wave kernel and at most BN254_OPT_WAVE_FE_MAX segments - the last
+// piece of every segment (at most BN_TAIL_SEG_MAX values; longer segments are first folded down to that) is multiplied AND exponentiated by
+// one wave: a verifier's handful of 4-pair checks is two launches.  Otherwise the last fold level writes every
+// segment's un-exponentiated product to out[j] and bn_launch_final_exp exponentiates the m values in place.
+// out[j] = final_exponentiation(prod of the Miller values of pairs [off[j], off[j+1])) for j < m; off is HOST memory; scratch guard held by the caller
+static int bn_launch_product_batch(bn254_ctx *c, const void *d_p, const void *d_q, const size_t *off, size_t m, void *d_out, hipStream_t s) {
+    const size_t n = off[m];
+    if (bn_seg_all_ones(off, m)) return bn_launch_pairing(c, d_p, d_q, d_out, n, s, nullptr);           // every segment one pair: bn254_pairing_batch's kernels
+    const size_t chunk_pairs = bn_round_pairs(c);
+    const bool small = n <= chunk_pairs && n <= bn_wave_pairing_max(c) && m <= bn_wave_fe_max(c);
+    int rc = bn_seg_run(c, {sizeof(bn_gt), BN_SEG_FOLD, chunk_pairs, true, small}, off, m, d_out, s, bn_no_cut, [&](size_t, const SegChunk &ch, char *values, const void *) -> int {
+        if (ch.hi == ch.lo) return BN254_OK;
+        return bn_launch_miller(c, (const char *)d_p + ch.lo * sizeof(bn_g1), (const char *)d_q + ch.lo * sizeof(bn_g2), values, ch.hi - ch.lo, s, true);
+    }, bn_gt_fold(c, s));
+    if (rc) return rc;
+    return small ? BN254_OK : bn_launch_final_exp(c, d_out, d_out, m, s, nullptr);
+}
+
+// ---- batched multi-pairing over prepared points with per-pair indices (bn254_pairing_product_batch_prepared_native*)
+// Every segment of L pairs is cut into ceil(L / 4) PIECES of at most four consecutive pairs; a lane pair runs one piece on ONE Miller accumulator
+// over the native tables (bn254_miller_native_shared4_B<true>: the line products of its pairs, a quarter of the squarings) and writes one
+// un-exponentiated Fq12.  Pieces go out in sub-launches of at most one machine round of lane pairs (host_plan.hpp miller_cut).
+//   * no segment above four pairs (a block of Groth16 checks): piece j IS segment j (an empty segment is a piece of no pairs, whose four
+//     identity columns give exactly one) - the kernel writes out[j], the final exponentiation runs in place, nothing is folded;
+//   * otherwise the pieces' values are the values of a segmented Fq12 fold whose segment j holds ceil(L_j / 4) of them: the plan of
+//     bn254_pairing_product_batch (chunks of one round of VALUES, carry, levels of BN_SEG_FOLD) over the derived offsets.
+// Small calls (n <= bn_prepared_small_max): the general path on the points kept with the handle, gathered by
+// index into the workspace (q_index == NULL: used in place), like the other prepared entry points.
+// d_qi: 64-bit indices in device memory or NULL; off is HOST memory; scratch guard held by the caller.
+static_assert(sizeof(size_t) == sizeof(uint64_t), "q_index travels to the device as 64-bit words");
+static int bn_launch_product_batch_prepared(bn254_ctx *c, const void *d_p, const bn254_g2_prepared *h, const void *d_qi, const size_t *off, size_t m, void *d_out, hipStream_t s) {
+    const size_t n = off[m], chunk_pairs = bn_round_pairs(c);
+    const int shared = h->nq == 1;
+    int rc;
+    if (n <= bn_prepared_small_max(c, h)) {
+        const void *q = h->q;
+        if (d_qi && n) {
+            const size_t q_at = seg_ws_values(chunk_pairs) * sizeof(bn_gt);          // behind everything bn_launch_product_batch keeps in the workspace
+            if ((rc = c->ws.reserve(q_at + n * sizeof(bn_g2)))) return rc;
+            BnScope sc(c, s, "g2_gather");
+            if ((rc = bn254_launch_gather_K(h->q, shared ? h->small_max : h->nq, sizeof(bn_g2), d_qi, n, (char *)c->ws.p + q_at, s))) return rc;
+            q = (const char *)c->ws.p + q_at;
+        }
+        return bn_launch_product_batch(c, d_p, q, off, m, d_out, s);
+    }
+    const bool direct = bn_seg_longest(off, m) <= 4;
+    MillerCut mc;
+    auto cut = [&](const std::vector<SegChunk> &chunks) {
+        mc = miller_cut(off, m, direct, chunks, [&](size_t count) { return bn_sub_launch(c, count); });
+        return &mc.pieces;
+    };
+    // the sub-launches of chunk `ci` (its pieces start at `chunk_lo`) over the uploaded pieces `mlist`: piece k of the chunk writes values[k]
+    auto miller = [&](size_t ci, size_t chunk_lo, char *values, const void *mlist) -> int {
+        for (size_t i = mc.chunk_subs[ci]; i < mc.chunk_subs[ci + 1]; ++i) {
+            const MillerSub &u = mc.subs[i];
+            BnScope sc(c, s, "miller_native_seg");
+            rc = bn254_launch_miller_native_seg_B((const char *)d_p + u.base * sizeof(bn_g1), h->table, h->inf, h->nq, d_qi && n ? (const char *)d_qi + u.base * sizeof(uint64_t) : nullptr,
+                                                  shared ? 0 : u.base, shared, (const BnMillerPiece *)mlist + u.lo, u.cnt, values + (u.lo - chunk_lo) * sizeof(bn_gt), s);
+            if (rc) return rc;
+        }
+        return BN254_OK;
+    };
+    if (direct) {
+        if ((rc = bn_seg_upload(c, {}, s, cut({{0, m, false, {}}}))) || (rc = miller(0, 0, (char *)d_out, c->seg_plan.p))) return rc;
+    } else {
+        const std::vector<size_t> voff = miller_value_offsets(off, m);
+        rc = bn_seg_run(c, {sizeof(bn_gt), BN_SEG_FOLD, chunk_pairs, true, false}, voff.data(), m, d_out, s, cut,
+                        [&](size_t ci, const SegChunk &ch, char *values, const void *mlist) { return miller(ci, ch.lo, values, mlist); }, bn_gt_fold(c, s));
+        if (rc) return rc;
+    }
+    return bn_launch_final_exp(c, d_out, d_out, m, s, nullptr);
+}
+
+// ---- segmented multi-scalar multiplication: out[j] = normalize(sum of p[i] * k[i] over i in [off[j], off[j+1])) (bn254_g{1,2}_msm_batch*)
+// The plan of the batched multi-pairing with points for Fq12 values.  Terms are cut into chunks of at most one sub-launch of the
+// multiplication kernels (BN_MUL_LANES_PER_LAUNCH lanes: 2^20 G1 / 2^19 G2 terms, every launch but the last one full, like bn_mul_dev); a
+// segment that crosses a cut carries its partial sum - Jacobian - into value slot 0 of the next chunk.  Per chunk: the term kernel
+// (bn254_g{1,2}_mul_M<true>: the GLV / GLS chain, NO normalisation) writes Jacobian points to the workspace, then the levels of the segmented
+// fold (bn254_g{1,2}_add_M<true>): every lane (G2: lane pair) adds one piece of at most BN_MSM_FOLD consecutive values with the complete
+// addition, ceil(log_BN_MSM_FOLD L) levels for a segment of L terms, and the piece that completes a segment normalises: one inversion per
+// segment instead of one per term.
+// BN_MSM_FOLD = 4, from the sweep over 4 / 8 / 16 / 32 in profiles/r08_msm.txt (tools/time_msm.py --sweep): a narrow piece keeps more lanes
+// busy and its serial chain short, a wide one saves levels (launches and a round trip of the partial sums through memory) - the fold of
+// 16 x 3001 terms takes 0.27 / 0.37 / 0.49 / 0.74 ms, of 2^14 x 16 terms 0.17 / 0.16 / 0.22 / 0.23 ms.  (seg_partials_max needs >= 4.)
+constexpr size_t BN_MSM_FOLD = 4;
+static_assert(BN_MSM_FOLD >= 4, "seg_partials_max bounds the partial sums for fold widths from 4");
+// off is HOST memory; scratch guard held by the caller
+static int bn_launch_msm(bn254_ctx *c, int g, const void *d_p, const void *d_k, const size_t *off, size_t m, void *d_out, hipStream_t s) {
+    const size_t n = off[m], V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2);
+    if (bn_seg_all_ones(off, m)) return bn_mul_dev(c, g, d_p, d_k, d_out, n, s, 1);         // every segment one term: bn254_g{1,2}_mul_batch's launches
+    const size_t step = BN_MUL_LANES_PER_LAUNCH / (g == 1 ? 1 : 2), chunk = std::max<size_t>(1, std::min(n, step));
+    int rc = c->mul_tbl.reserve(bn254_mul_table_bytes_M(g, chunk)); if (rc) return rc;
+    return bn_seg_run(c, {V, BN_MSM_FOLD, chunk, false, false}, off, m, d_out, s, bn_no_cut, [&](size_t, const SegChunk &ch, char *values, const void *) -> int {
+        if (ch.hi == ch.lo) return BN254_OK;
+        BnScope sc(c, s, g == 1 ? "g1_msm_mul" : "g2_msm_mul");
+        return bn254_launch_msm_mul_M(g, (const char *)d_p + ch.lo * V, (const char *)d_k + ch.lo * sizeof(bn_fr), values, ch.hi - ch.lo, c->mul_tbl.p, s);
+    }, [&](bool, const BnSegPiece *list, size_t cnt) -> int {
+        BnScope sc(c, s, g == 1 ? "g1_msm_fold" : "g2_msm_fold");
+        return bn254_launch_msm_fold_M(g, list, cnt, s);
+    });
+}
+
+// ---- one large multi-scalar multiplication: out = normalize(sum of p[i] * k[i] over all n terms) (bn254_g{1,2}_msm*)
+// Below BN254_OPT_MSM_BUCKET_MIN terms: bn_launch_msm on the one segment {0, n}.  From there on the bucket (Pippenger) method with unsigned
+// c-bit windows (BN254_OPT_MSM_WINDOW_BITS; W = ceil(254 / c) windows, 2^c buckets per window of which bucket 0 stays empty), in chunks of at
+// most BN254_OPT_MSM_CHUNK terms.  Per chunk (kernels and their invariants: bn254_kernels_mul.hip):
+//   digits   count the terms per (window, digit), scan the W * 2^c counts, scatter (term index, key) into key order     scope g*_msm_digits
+//   bucket   levels of the accumulation: every lane adds at most MSM_PIECE consecutive entries; a run of one key that ends inside a lane is
+//            added to its bucket, the pieces of a longer run go to the next, eight times shorter level.  The entry count is known on the
+//            device only; the host launches every level for its upper bound W * terms (lanes past the real count retire at once), so
+//            nothing is read back and the call stays asynchronous                                                          scope g*_msm_bucket
+// The buckets collect over the chunks.  Then ONE reduction (scope g*_msm_reduce): groups of 16 consecutive buckets give S = sum B_b and
+// T = sum (b - base) B_b, and the window sums sum_groups (T + base S) weighted by 2^(c w) are the one-segment bn_launch_msm over these
+// 2 * W * 2^c / 16 Jacobian terms with the scalars base * 2^(c w) and 2^(c w) - host-known, built once per window width - which folds,
+// normalises once and writes out.
+// Workspace (context-owned, under the scratch guard; host_plan.hpp msm_bucket_plan), for t = min(n, chunk) terms and V = 96 / 192 bytes per
+// point: W t entries of 8 bytes (index, key), W 2^c counts of 4 bytes and buckets of V bytes, the partial sums of the levels (at most
+// W t / 7 + 64 slots of V + 4 bytes), 2 W 2^c / 16 tail terms of V + 32 bytes.
+// scratch guard held by the caller
+static int bn_launch_msm_bucket(bn254_ctx *c, int g, const void *d_p, const void *d_k, size_t n, void *d_out, hipStream_t s) {
+    const size_t V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2), L = bn254_msm_piece_M();
+    const unsigned cb = bn_msm_window_bits(bn_opt(c, BN254_OPT_MSM_WINDOW_BITS), n);
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, (size_t)bn_opt(c, BN254_OPT_MSM_CHUNK)));
+    const MsmBucketPlan bp = msm_bucket_plan(cb, chunk, V, L);
+    int rc;
+    if ((rc = c->msm_ws.reserve(bp.bytes))) return rc;
+    char *ws = (char *)c->msm_ws.p;
+    if (c->msm_scal_c != (long)cb) {
+        std::vector<uint64_t> &h = c->msm_scal_host;
+        HIP_TRY(hipStreamSynchronize(s));                    // the previous image may still be on its way
+        msm_tail_scalars(cb, h);
+        if ((rc = c->msm_scal.reserve(h.size() * 8))) return rc;
+        c->msm_scal_c = -1;
+        HIP_TRY(hipMemcpyAsync(c->msm_scal.p, h.data(), h.size() * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        c->msm_scal_c = (long)cb;
+    }
+    HIP_TRY(hipMemsetAsync(ws + bp.o_buckets, 0, bp.K * V, s));   // z = 0: every bucket starts as the point at infinity
+    rc = bn_for_parts(n, chunk, [&](size_t lo, size_t len) -> int {
+        const char *pk = (const char *)d_k + lo * sizeof(bn_fr), *pp = (const char *)d_p + lo * V;
+        {
+            BnScope sc(c, s, g == 1 ? "g1_msm_digits" : "g2_msm_digits");
+            HIP_TRY(hipMemsetAsync(ws + bp.o_counts, 0, bp.K * 4, s));
+            if ((rc = bn254_launch_msm_digits_M(pk, len, cb, bp.W, ws + bp.o_counts, nullptr, nullptr, 0, s))) return rc;
+            if ((rc = bn254_launch_msm_scan_M(ws + bp.o_counts, bp.K, ws + bp.o_tiles, ws + bp.o_n0, s))) return rc;
+            if ((rc = bn254_launch_msm_digits_M(pk, len, cb, bp.W, ws + bp.o_counts, ws + bp.o_idx, ws + bp.o_keys, 1, s))) return rc;
+        }
+        BnScope sc(c, s, g == 1 ? "g1_msm_bucket" : "g2_msm_bucket");
+        const char *pts = pp, *idx = ws + bp.o_idx, *keys = ws + bp.o_keys;
+        size_t N = (size_t)bp.W * len;
+        for (unsigned level = 0;; ++level) {
+            if (level >= bp.o_level.size()) return BN254_E_INTERNAL;
+            char *opts = ws + bp.o_level[level].first, *okeys = ws + bp.o_level[level].second;
+            if ((rc = bn254_launch_msm_bucket_M(g, pts, idx, keys, ws + bp.o_n0, level, opts, okeys, ws + bp.o_buckets, (N + L - 1) / L, s))) return rc;
+            if (N <= L) return BN254_OK;
+            N = 2 * ((N + L - 1) / L); pts = opts; idx = nullptr; keys = okeys;
+        }
+    });
+    if (rc) return rc;
+    {
+        BnScope sc(c, s, g == 1 ? "g1_msm_reduce" : "g2_msm_reduce");
+        if ((rc = bn254_launch_msm_reduce_M(g, ws + bp.o_buckets, bp.G, bp.groups, cb, bp.count, ws + bp.o_terms, s))) return rc;
+    }
+    const size_t off[2] = {0, 2 * bp.count};
+    return bn_launch_msm(c, g, ws + bp.o_terms, c->msm_scal.p, off, 1, d_out, s);
+}
+// the route of one call: the one-segment launch sequence of bn254_g{1,2}_msm_batch below BN254_OPT_MSM_BUCKET_MIN terms
+static bool bn_msm_bucket_route(const bn254_ctx *c, int g, size_t n) {
+    const long set = c->opt[BN254_OPT_MSM_BUCKET_MIN].load(std::memory_order_relaxed);
+    return n >= (size_t)(set >= 0 ? set : g == 1 ? BN_MSM_BUCKET_MIN_DEFAULT : BN_MSM_BUCKET_MIN_DEFAULT_G2);
+}
+
+// argument checks of bn254_pairing_product_batch_prepared_native* for m > 0 that need no device: the CSR rules, the handle, and - where the
+// indices are host memory - every index
+// (`indexed`: the pairs carry indices; `q_index`: those indices where the host can read them)
+static int bn_prep_seg_check(const void *p, const bn254_g2_prepared *prep, bool indexed, const size_t *q_index, const size_t *offsets, size_t m, const void *out) {
+    if (int e = bn_seg_check(p, p, offsets, m, out)) return e;
+    if (!prep) return BN254_E_BAD_ARG;
+    const size_t n = offsets[m];
+    if (!indexed) return prep->nq != 1 && n > prep->nq ? BN254_E_BAD_ARG : BN254_OK;
+    for (size_t i = 0; q_index && i < n; ++i)
+        if (q_index[i] >= prep->nq) return BN254_E_BAD_ARG;
+    return BN254_OK;
+}
+
+// the *_dev entry points below, after their argument checks: context, device, scratch guard (workspaces, window tables and work lists are
+// context-owned scratch), then fn(stream) with nothing thrown across the ABI
+template <class Fn>
+static int bn_seg_entry(bn254_ctx *&ctx, void *stream, Fn fn) {
+    int rc = bn_get_ctx(ctx); if (rc) return rc;
+    BnDev d(ctx, stream); if (!d.go) return d.rc;
+    BnScratchGuard g(ctx, d.s); if (g.rc) return g.rc;
+    return bn_no_throw([&] { return fn(d.s); });
+}
+
+extern "C" {
+
+// ---------------------------------------------------------------------------------------------- device-resident API
+int bn254_pairing_product_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, const size_t *offsets, size_t m, void *d_out, void *stream) {
+    if (m == 0) return BN254_OK;
+    if (int e = bn_seg_check(d_p, d_q, offsets, m, d_out)) return e;          // before any device lookup
+    return bn_seg_entry(ctx, stream, [&](hipStream_t s) { return bn_launch_product_batch(ctx, d_p, d_q, offsets, m, d_out, s); });
+}
+int bn254_pairing_product_batch_prepared_native_dev(bn254_ctx *ctx, const void *d_p, const bn254_g2_prepared *prep, const void *d_q_index, const size_t *offsets, size_t m, void *d_out, void *stream) {
+    if (m == 0) return BN254_OK;
+    if (int e = bn_prep_seg_check(d_p, prep, d_q_index != nullptr, nullptr, offsets, m, d_out)) return e;          // before any device lookup
+    int rc = bn_get_ctx(ctx); if (rc) return rc;
+    if (prep->device != ctx->device) return BN254_E_BAD_ARG;
+    return bn_seg_entry(ctx, stream, [&](hipStream_t s) { return bn_launch_product_batch_prepared(ctx, d_p, prep, d_q_index, offsets, m, d_out, s); });
+}
+static int msm_dev(bn254_ctx *ctx, int g, const void *d_p, const void *d_k, const size_t *offsets, size_t m, void *d_out, void *stream) {
+    if (m == 0) return BN254_OK;
+    if (int e = bn_msm_check(d_p, d_k, offsets, m, d_out)) return e;          // before any device lookup
+    return bn_seg_entry(ctx, stream, [&](hipStream_t s) { return bn_launch_msm(ctx, g, d_p, d_k, offsets, m, d_out, s); });
+}
+int bn254_g1_msm_batch_dev(bn254_ctx *c, const void *p, const void *k, const size_t *offsets, size_t m, void *o, void *s) { return msm_dev(c, 1, p, k, offsets, m, o, s); }
+int bn254_g2_msm_batch_dev(bn254_ctx *c, const void *p, const void *k, const size_t *offsets, size_t m, void *o, void *s) { return msm_dev(c, 2, p, k, offsets, m, o, s); }
+static int msm1_dev(bn254_ctx *ctx, int g, const void *d_p, const void *d_k, size_t n, void *d_out, void *stream) {
+    if (int e = bn_msm1_check(d_p, d_k, n, d_out)) return e;                   // before any device lookup
+    return bn_seg_entry(ctx, stream, [&](hipStream_t s) -> int {
+        if (bn_msm_bucket_route(ctx, g, n)) return bn_launch_msm_bucket(ctx, g, d_p, d_k, n, d_out, s);
+        const size_t off[2] = {0, n};
+        return bn_launch_msm(ctx, g, d_p, d_k, off, 1, d_out, s);
+    });
+}
+int bn254_g1_msm_dev(bn254_ctx *c, const void *p, const void *k, size_t n, void *o, void *s) { return msm1_dev(c, 1, p, k, n, o, s); }
+int bn254_g2_msm_dev(bn254_ctx *c, const void *p, const void *k, size_t n, void *o, void *s) { return msm1_dev(c, 2, p, k, n, o, s); }
+
+// ---------------------------------------------------------------------------------------------- host-buffer API (BnHost: the context's mutex for the call)
+int bn254_pairing_product_batch(bn254_ctx *ctx, const bn_g1 *p, const bn_g2 *q, const size_t *offsets, size_t m, bn_gt *out) {
+    if (m == 0) return BN254_OK;
+    if (int e = bn_seg_check(p, q, offsets, m, out)) return e;                // before any device lookup
+    const size_t n = offsets[m];
+    if (bn_seg_all_ones(offsets, m)) return bn254_pairing_batch(ctx, p, q, out, n);                 // every segment one pair: the pipelined batch path itself
+    BnHost h(ctx); if (h.rc) return h.rc;
+    return bn_staged(ctx, {p, n * sizeof(bn_g1)}, {q, n * sizeof(bn_g2)}, out, m * sizeof(bn_gt), nullptr, 0,
+                     [&](const BnStaged &d) { return bn254_pairing_product_batch_dev(ctx, d.in[0], d.in[1], offsets, m, d.out, ctx->stream); });
+}
+int bn254_pairing_product_batch_prepared_native(bn254_ctx *ctx, const bn_g1 *p, const bn254_g2_prepared *prep, const size_t *q_index, const size_t *offsets, size_t m, bn_gt *out) {
+    if (m == 0) return BN254_OK;
+    if (int e = bn_prep_seg_check(p, prep, q_index != nullptr, q_index, offsets, m, out)) return e;                // before any device lookup
+    const size_t n = offsets[m];
+    BnHost h(ctx); if (h.rc) return h.rc;
+    if (prep->device != ctx->device) return BN254_E_BAD_ARG;
+    return bn_staged(ctx, {p, n * sizeof(bn_g1)}, {q_index, n * sizeof(uint64_t)}, out, m * sizeof(bn_gt), nullptr, 0,
+                     [&](const BnStaged &d) { return bn254_pairing_product_batch_prepared_native_dev(ctx, d.in[0], prep, d.in[1], offsets, m, d.out, ctx->stream); });
+}
+static int msm_host(bn254_ctx *ctx, int g, const void *p, const bn_fr *k, const size_t *offsets, size_t m, void *out) {
+    if (m == 0) return BN254_OK;
+    if (int e = bn_msm_check(p, k, offsets, m, out)) return e;                // before any device lookup
+    const size_t n = offsets[m], V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2);
+    if (bn_seg_all_ones(offsets, m))                                          // every segment one term: the pipelined batch path itself
+        return g == 1 ? bn254_g1_mul_batch(ctx, (const bn_g1 *)p, k, (bn_g1 *)out, n) : bn254_g2_mul_batch(ctx, (const bn_g2 *)p, k, (bn_g2 *)out, n);
+    BnHost h(ctx); if (h.rc) return h.rc;
+    return bn_staged(ctx, {p, n * V}, {k, n * sizeof(bn_fr)}, out, m * V, nullptr, 0,
+                     [&](const BnStaged &d) { return msm_dev(ctx, g, d.in[0], d.in[1], offsets, m, d.out, ctx->stream); });
+}
+int bn254_g1_msm_batch(bn254_ctx *ctx, const bn_g1 *p, const bn_fr *k, const size_t *offsets, size_t m, bn_g1 *out) { return msm_host(ctx, 1, p, k, offsets, m, out); }
+int bn254_g2_msm_batch(bn254_ctx *ctx, const bn_g2 *p, const bn_fr *k, const size_t *offsets, size_t m, bn_g2 *out) { return msm_host(ctx, 2, p, k, offsets, m, out); }
+static int msm1_host(bn254_ctx *ctx, int g, const void *p, const bn_fr *k, size_t n, void *out) {
+    if (int e = bn_msm1_check(p, k, n, out)) return e;                         // before any device lookup
+    int rc = bn_get_ctx(ctx); if (rc) return rc;
+    if (!bn_msm_bucket_route(ctx, g, n)) {
+        const size_t off[2] = {0, n};
+        return msm_host(ctx, g, p, k, off, 1, out);
+    }
+    const size_t V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2);
+    BnHost h(ctx); if (h.rc) return h.rc;
+    return bn_staged(ctx, {p, n * V}, {k, n * sizeof(bn_fr)}, out, V, nullptr, 0,
+                     [&](const BnStaged &d) { return msm1_dev(ctx, g, d.in[0], d.in[1], n, d.out, ctx->stream); });
+}
+int bn254_g1_msm(bn254_ctx *ctx, const bn_g1 *p, const bn_fr *k, size_t n, bn_g1 *out) { return msm1_host(ctx, 1, p, k, n, out); }
+int bn254_g2_msm(bn254_ctx *ctx, const bn_g2 *p, const bn_fr *k, size_t n, bn_g2 *out) { return msm1_host(ctx, 2, p, k, n, out); }
+
+}  // extern "C"

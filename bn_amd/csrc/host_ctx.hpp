@@ -1,5 +1,7 @@
-// Host-side internals shared by the translation units that implement include/bn254_hip.h (bn254_hip.hip: single-device
-// entry points; bn254_multi.hip: pipelined host-buffer path, multi-device fan-out, RCCL exchange).  Not part of the ABI.
+// Host-side internals shared by the translation units that implement include/bn254_hip.h (bn254_hip.hip: contexts, options, launch
+// policy and the single-device entry points of pairing, Miller loop, final exponentiation and products; bn254_seg.hip: the segmented
+// multi-pairings and the multi-scalar multiplications; bn254_wire.hip: the wire format; bn254_multi.hip: pipelined host-buffer path,
+// multi-device fan-out, RCCL exchange).  The host arithmetic that needs no device is host_plan.hpp.  Not part of the ABI.
 //
 // Concurrency contract (what the header promises and these structures implement):
 //   * any number of host threads may call the HOST-BUFFER entry points of one context - including the process-wide default
@@ -16,11 +18,13 @@
 #include <condition_variable>
 #include <map>
 #include <new>
+#include <optional>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/bn254_hip.h"
+#include "host_plan.hpp"
 
 #define HIP_TRY(expr)                             \
     do {                                          \
@@ -93,7 +97,7 @@ struct bn254_ctx {
     BnBuf msm_scal;                     // ... and the tail's scalars (Montgomery images of 2^(c w) and base * 2^(c w)) for window width msm_scal_c
     std::vector<uint64_t> msm_scal_host;    // their host image (kept while the copy may be in flight; rebuilt only when the width changes)
     long msm_scal_c = -1;
-    BnBuf stage[3];                     // device staging of the small host-buffer entry points
+    BnBuf stage[4];                     // device staging of the small host-buffer entry points (bn_staged: two inputs, two outputs)
     BnSlot slot[BN_MAX_SLOTS];          // pipelined path (bn254_multi.hip)
     // leases of those slots: a batch of up to one chunk takes ONE of the first two (two callers overlap on the GPU - the number
     // of streams the hardware overlaps without loss), a multi-chunk batch takes all of them
@@ -173,13 +177,87 @@ int bn_launch_product(bn254_ctx *c, const void *in, size_t n, void *out, void *t
 size_t bn_product_tmp_bytes(const bn254_ctx *c, size_t n);
 // table: the caller's own buffer (pipelined path: the slot's) or NULL for the context's (then under a BnScratchGuard)
 int bn_mul_dev(bn254_ctx *ctx, int g, const void *d_p, const void *d_k, void *d_out, size_t n, hipStream_t s, int normalize, BnBuf *table = nullptr);
-// argument checks of bn254_pairing_product_batch* for m > 0 (CSR offsets, sizes, pointers); no device involved
-int bn_seg_check(const void *p, const void *q, const size_t *offsets, size_t m, const void *out);
-// the same checks for bn254_g{1,2}_msm_batch* (points, scalars)
-int bn_msm_check(const void *p, const void *k, const size_t *offsets, size_t m, const void *out);
-// argument checks of bn254_g{1,2}_msm* (one sum of n terms); no device involved
-int bn_msm1_check(const void *p, const void *k, size_t n, const void *out);
-void bn_fr_one(bn_fr *out);                                        // the Montgomery image of one
+constexpr size_t BN_LAUNCH_MAX = (size_t)1 << 22;       // units per launch (32-bit word offsets inside a kernel); also the cap of the size options
+// terms from which bn254_g{1,2}_msm take the bucket route while BN254_OPT_MSM_BUCKET_MIN is not set: the smallest measured size from which
+// the route is faster in kernel time than the one-segment bn254_g{1,2}_msm_batch and stays faster above (profiles/r10_msm_bucket.txt: G1
+// 0.73 x at 2^18, 1.06 x at 2^19, 1.33 x at 2^20; G2 0.77 x at 2^17, 1.14 x at 2^18, 1.55 x at 2^19).  bn254_ctx_get_option reports G1's.
+constexpr long BN_MSM_BUCKET_MIN_DEFAULT = (long)1 << 19, BN_MSM_BUCKET_MIN_DEFAULT_G2 = (long)1 << 18;
+// The normalising kernels keep every lane's window table (640 B) in a buffer the sub-launches reuse.  Sub-launches of 2^20 lanes (671 MB; rounds
+// 2-5: 2^18): these kernels run three resident waves per SIMD under plain oldest-first arbitration, a launch ends with every SIMD draining its last
+// wave alone, and that tail is paid once per launch - 2^20 G1 multiplications in ONE launch of 16 waves per SIMD: 91.1 against 86.7 M/s in four
+// launches on the same box, G2 +2 % (profiles/r06_ab_mul_launch_size.txt).
+constexpr size_t BN_MUL_LANES_PER_LAUNCH = (size_t)1 << 20;
+size_t bn_wave_pairing_max(const bn254_ctx *c);                    // BN254_OPT_WAVE_PAIRING_MAX: up to this many pairings per call run one per wave
+size_t bn_wave_fe_max(const bn254_ctx *c);                         // BN254_OPT_WAVE_FE_MAX: the same for final exponentiations
+// calls over a prepared handle of up to this many pairs take the general path on the points kept with the handle
+size_t bn_prepared_small_max(const bn254_ctx *c, const bn254_g2_prepared *prep);
+
+// Prologue of the *_dev entry points: `BnDev d(...); if (!d.go) return d.rc;` makes the context's device current until the entry point
+// returns (the caller's is restored then) and gives the caller's stream.  The second form is the order of the plain batch entry points:
+// context, empty batch (nothing to do: rc = BN254_OK), arguments, device.
+struct BnDev {
+    std::optional<BnDeviceGuard> guard;
+    int rc = BN254_OK;
+    bool go = false;
+    hipStream_t s = nullptr;
+    BnDev() {}
+    BnDev(bn254_ctx *ctx, void *stream) { enter(ctx, (hipStream_t)stream); }
+    BnDev(bn254_ctx *&ctx, void *stream, size_t n, bool bad_arg, size_t limit) {
+        if ((rc = bn_get_ctx(ctx)) || n == 0) return;
+        if (bad_arg || n > limit) { rc = BN254_E_BAD_ARG; return; }
+        enter(ctx, (hipStream_t)stream);
+    }
+    void enter(bn254_ctx *ctx, hipStream_t stream) {
+        guard.emplace();
+        rc = (int)hipSetDevice(ctx->device);
+        go = !rc; s = stream;
+    }
+};
+// Prologue of the host-buffer entry points that lock the context: looks the context up, holds its mutex for the whole call - concurrent
+// callers of one context (in particular of the default context behind ctx == NULL) are serialised, never interleaved on the staging
+// memory -, makes its device current.  `BnHost h(ctx); if (h.rc) return h.rc;`
+struct BnHost {
+    std::unique_lock<std::mutex> lock;
+    BnDev dev;
+    int rc;
+    explicit BnHost(bn254_ctx *&ctx) {
+        if ((rc = bn_get_ctx(ctx))) return;
+        lock = std::unique_lock<std::mutex>(ctx->mu);
+        dev.enter(ctx, ctx->stream);
+        rc = dev.rc;
+    }
+};
+// The body of a host-buffer entry point of the shape copy-in, device calls, copy-out, synchronise, on the context's stream under a BnHost:
+// the inputs (skipped when NULL; nothing copied for zero bytes) are staged in ctx->stage[0..1], body(d) enqueues the work on the staged
+// inputs d.in[] (NULL for a skipped one) and the device buffers d.out / d.out2, then `out` (and `out2` when given) are copied back.
+// On an error the stream is drained first: copies that read or write the caller's buffers may still be in flight.
+struct BnStageIn { const void *p; size_t bytes; };
+struct BnStaged { void *in[2], *out, *out2; };
+template <class Body>
+int bn_staged(bn254_ctx *ctx, BnStageIn in0, BnStageIn in1, void *out, size_t out_bytes, void *out2, size_t out2_bytes, Body body) {
+    const hipStream_t s = ctx->stream;
+    const BnStageIn in[2] = {in0, in1};
+    auto run = [&]() -> int {
+        int rc;
+        BnStaged d = {};
+        for (int i = 0; i < 2; ++i) {
+            if (!in[i].p) continue;
+            if ((rc = ctx->stage[i].reserve(in[i].bytes))) return rc;
+            d.in[i] = ctx->stage[i].p;
+        }
+        if ((rc = ctx->stage[2].reserve(out_bytes)) || (out2 && (rc = ctx->stage[3].reserve(out2_bytes)))) return rc;
+        d.out = ctx->stage[2].p; d.out2 = out2 ? ctx->stage[3].p : nullptr;
+        for (int i = 0; i < 2; ++i)
+            if (d.in[i] && in[i].bytes) HIP_TRY(hipMemcpyAsync(d.in[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, s));
+        if ((rc = body(d))) return rc;
+        HIP_TRY(hipMemcpyAsync(out, d.out, out_bytes, hipMemcpyDeviceToHost, s));
+        if (out2) HIP_TRY(hipMemcpyAsync(out2, d.out2, out2_bytes, hipMemcpyDeviceToHost, s));
+        return (int)hipStreamSynchronize(s);
+    };
+    const int rc = run();
+    if (rc) (void)hipStreamSynchronize(s);
+    return rc;
+}
 
 extern "C" {
 // bn254_kernels_b.hip

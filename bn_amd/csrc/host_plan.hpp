@@ -1,0 +1,232 @@
+// Host arithmetic over sizes and offsets: the argument checks that need no device, the work lists of the segmented folds, the cutting of a
+// prepared batch into Miller pieces, the workspace of the bucket method and its tail scalars.  Plain C++17: nothing here touches a device, so
+// tests/hostsim/ compiles it with g++ and tests/test_host_plan.py replays the plans on the CPU.  (io.hpp: the two records the kernels read.)
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <utility>
+#include <vector>
+
+#include "../../include/bn254_hip.h"
+#include "io.hpp"
+
+using bn254::BnMillerPiece;
+using bn254::BnSegPiece;
+
+constexpr size_t BN_N_MAX = (size_t)1 << 40;            // sanity bound on a batch; launches are cut to size internally
+
+// ---- argument checks (no device involved)
+// bn254_pairing_product_batch* for m > 0: CSR offsets, sizes, pointers
+inline int bn_seg_check(const void *p, const void *q, const size_t *offsets, size_t m, const void *out) {
+    if (!offsets || offsets[0] != 0) return BN254_E_BAD_ARG;
+    for (size_t j = 0; j < m; ++j)
+        if (offsets[j + 1] < offsets[j]) return BN254_E_BAD_ARG;
+    const size_t n = offsets[m];
+    return (n > BN_N_MAX || !out || (n && (!p || !q))) ? BN254_E_BAD_ARG : BN254_OK;
+}
+// the same checks for bn254_g{1,2}_msm_batch* (points, scalars)
+inline int bn_msm_check(const void *p, const void *k, const size_t *offsets, size_t m, const void *out) { return bn_seg_check(p, k, offsets, m, out); }
+// bn254_g{1,2}_msm* (one sum of n terms)
+inline int bn_msm1_check(const void *p, const void *k, size_t n, const void *out) { return (n > BN_N_MAX || !out || (n && (!p || !k))) ? BN254_E_BAD_ARG : BN254_OK; }
+// every segment holds exactly one element: the call is the plain batch operation
+inline bool bn_seg_all_ones(const size_t *off, size_t m) {
+    bool ones = off[m] == m;
+    for (size_t j = 0; ones && j < m; ++j) ones = off[j] == j;
+    return ones;
+}
+inline size_t bn_seg_longest(const size_t *off, size_t m) {
+    size_t longest = 0;
+    for (size_t j = 0; j < m; ++j) longest = std::max(longest, off[j + 1] - off[j]);
+    return longest;
+}
+
+// as few sub-launches as possible with none above one round, all of (nearly) the same size: a ragged tail of a few pairings
+// would cost a whole kernel latency (one wave takes as long as a full machine)
+inline size_t bn_equal_parts(size_t n, size_t round) {
+    const size_t parts = (n + round - 1) / round;
+    return parts <= 1 ? n : ((n + parts - 1) / parts + 31) / 32 * 32;
+}
+
+// sub-launches of at most `step` units: fn(lo, cnt) enqueues one
+template <class Fn>
+int bn_for_parts(size_t n, size_t step, Fn fn) {
+    for (size_t lo = 0; lo < n; lo += step) {
+        int rc = fn(lo, n - lo < step ? n - lo : step);
+        if (rc) return rc;
+    }
+    return BN254_OK;
+}
+
+// ---- the plan of a segmented fold (bn254_seg.hip runs it: Fq12 products of the batched multi-pairings, point sums of the segmented MSM)
+constexpr size_t BN_SEG_FOLD = 16;          // values per lane-pair piece of the fold: at most 15 products in a row (~20-30 us each)
+constexpr size_t BN_TAIL_SEG_MAX = 16;      // values per wave in the ragged tail: at most 15 wave products (~2.7 us each) before the exponentiation
+struct SegLaunch { bool tail; size_t first, count; };                                  // a range of the work list: one fold level or the tail
+struct SegChunk { size_t lo, hi; bool carry_out; std::vector<SegLaunch> launches; };   // values [lo, hi) and what follows them
+// partial products ALL fold levels of one chunk write, at most: a segment of L > BN_SEG_FOLD values gives ceil(L / BN_SEG_FOLD) < 2 L / BN_SEG_FOLD
+// partials, so level 0 writes fewer than 2 (chunk_pairs + 1) / BN_SEG_FOLD and every further level fewer than 1/8 of the level before.
+// Every partial of a chunk has a slot of its own (no level reuses another level's slots): a piece may read its inputs several levels
+// after they were written - the ragged tail of the small route reads them only after the deepest level of the plan.
+// (`fold` >= 4 values per piece - the multi-scalar multiplications plan with their own width, BN_MSM_FOLD: 2 L / fold (1 + 2 / fold + ...) <= 4 L / fold.)
+inline size_t seg_partials_max(size_t chunk_pairs, size_t fold = BN_SEG_FOLD) { return 4 * (chunk_pairs + 1) / fold + 4; }
+// workspace (in values: Fq12, or Jacobian points for the multi-scalar multiplications): [carry in][chunk_pairs values][partials of every level][carry out]
+inline size_t seg_ws_values(size_t chunk_pairs, size_t fold = BN_SEG_FOLD) { return chunk_pairs + 2 + seg_partials_max(chunk_pairs, fold); }
+// false if the partials would not fit their region (cannot happen by the bound above; checked, never written out of bounds)
+// V: bytes per value; fold: values per piece; snap: cut at the last segment boundary inside a chunk (false: every chunk is full, and any
+// segment across a cut carries).  The piece that writes out[j] carries last = 1 (read by the point fold only: it normalises there).
+inline bool seg_plan(const size_t *off, size_t m, size_t chunk_pairs, bool small, char *ws, char *d_out, std::vector<BnSegPiece> &pieces, std::vector<SegChunk> &chunks,
+                     size_t V, size_t fold = BN_SEG_FOLD, bool snap = true) {
+    const size_t n = off[m], pb = seg_partials_max(chunk_pairs, fold), last_cap = small ? BN_TAIL_SEG_MAX : fold;
+    char *const part = ws + (chunk_pairs + 1) * V, *const carry_out = ws + (chunk_pairs + 1 + pb) * V;
+    size_t lo = 0, j = 0;
+    bool carry = false;
+    do {
+        size_t hi = std::min(n, lo + chunk_pairs);
+        if (snap && hi < n) {
+            const size_t b = *(std::upper_bound(off, off + m + 1, hi) - 1);          // last segment boundary <= hi
+            if (b > lo) hi = b;
+        }
+        // segments that start in front of hi (the last chunk also takes the empty segments at n)
+        const size_t jend = hi == n ? m : (size_t)(std::lower_bound(off + j, off + m, hi) - off);
+        std::vector<std::vector<BnSegPiece>> lv(1);
+        size_t used = 0;                                                     // partial slots taken in this chunk
+        std::vector<BnSegPiece> tail;
+        SegChunk ch{lo, hi, false, {}};
+        for (size_t jj = j; jj < jend; ++jj) {
+            const bool from_carry = carry && jj == j, to_carry = off[jj + 1] > hi;
+            const size_t a = from_carry ? 0 : off[jj] - lo + 1, b = std::min(off[jj + 1], hi) - lo + 1;      // value slots [a, b)
+            const char *src = ws + a * V;
+            size_t L = b - a, level = 0;
+            while (L > last_cap) {
+                if (lv.size() <= level) lv.emplace_back();
+                char *base = part + used * V;
+                const size_t k = (L + fold - 1) / fold;
+                if (used + k > pb) return false;
+                for (size_t i = 0; i < k; ++i)
+                    lv[level].push_back({(const uint32_t *)(src + i * fold * V), (uint32_t *)(base + i * V), (uint32_t)std::min(fold, L - i * fold), 0u});
+                used += k; src = base; L = k; ++level;
+            }
+            const BnSegPiece last = {(const uint32_t *)src, (uint32_t *)(to_carry ? carry_out : d_out + jj * V), (uint32_t)L, to_carry ? 0u : 1u};
+            if (small) tail.push_back(last);
+            else { if (lv.size() <= level) lv.resize(level + 1); lv[level].push_back(last); }
+            ch.carry_out |= to_carry;
+        }
+        for (const auto &l : lv)
+            if (!l.empty()) { ch.launches.push_back({false, pieces.size(), l.size()}); pieces.insert(pieces.end(), l.begin(), l.end()); }
+        if (!tail.empty()) { ch.launches.push_back({true, pieces.size(), tail.size()}); pieces.insert(pieces.end(), tail.begin(), tail.end()); }
+        carry = ch.carry_out;
+        j = carry ? jend - 1 : jend;
+        lo = hi;
+        chunks.push_back(std::move(ch));
+    } while (lo < n);
+    return true;
+}
+
+// ---- a prepared batch cut into Miller pieces (bn254_pairing_product_batch_prepared_native*): every segment of L pairs gives ceil(L / 4)
+// pieces of at most four consecutive pairs, or - `direct`: no segment above four pairs - exactly one (an empty segment: a piece of no pairs)
+// derived offsets of the fold over the pieces' values: voff[j + 1] - voff[j] = ceil(L_j / 4)
+inline std::vector<size_t> miller_value_offsets(const size_t *off, size_t m) {
+    std::vector<size_t> voff(m + 1, 0);
+    for (size_t j = 0; j < m; ++j) voff[j + 1] = voff[j] + (off[j + 1] - off[j] + 3) / 4;
+    return voff;
+}
+struct MillerSub { size_t lo, cnt, base; };             // pieces [lo, lo + cnt) of the list; base: the first pair of the sub-launch
+struct MillerCut { std::vector<BnMillerPiece> pieces; std::vector<MillerSub> subs; std::vector<size_t> chunk_subs; };      // subs [chunk_subs[i], chunk_subs[i + 1]): chunk i's
+// the pieces in launch order and their sub-launches: of step(count) pieces for a chunk of `count` (at most one round of lane pairs), never
+// across a chunk; a piece's `first` is relative to its sub-launch.  chunks: piece ranges [lo, hi) (direct: the one chunk {0, m})
+template <class Step>
+MillerCut miller_cut(const size_t *off, size_t m, bool direct, const std::vector<SegChunk> &chunks, Step step) {
+    MillerCut cut;
+    std::vector<size_t> first;                    // absolute until the sub-launches are cut
+    for (size_t j = 0; j < m; ++j) {
+        const size_t L = off[j + 1] - off[j];
+        if (direct) { first.push_back(off[j]); cut.pieces.push_back({0u, (uint32_t)L}); }
+        else for (size_t k = 0; k < L; k += 4) { first.push_back(off[j] + k); cut.pieces.push_back({0u, (uint32_t)std::min<size_t>(4, L - k)}); }
+    }
+    for (const SegChunk &ch : chunks) {
+        cut.chunk_subs.push_back(cut.subs.size());
+        const size_t count = ch.hi - ch.lo;
+        bn_for_parts(count, count ? step(count) : 1, [&](size_t at, size_t cnt) {
+            const size_t lo = ch.lo + at, base = first[lo];
+            for (size_t k = lo; k < lo + cnt; ++k) cut.pieces[k].first = (uint32_t)(first[k] - base);
+            cut.subs.push_back({lo, cnt, base});
+            return 0;
+        });
+    }
+    cut.chunk_subs.push_back(cut.subs.size());
+    return cut;
+}
+
+// ---- bucket (Pippenger) route of bn254_g{1,2}_msm: window width, levels of the accumulation, workspace, tail scalars
+constexpr unsigned BN_MSM_GROUP = 16;         // buckets per lane of the reduction: 32 additions in a row, 2^c / 8 tail terms per window
+inline size_t bn_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// window width by size when BN254_OPT_MSM_WINDOW_BITS is not set (forced < 1): the best measured width per size (profiles/r10_msm_bucket.txt)
+inline unsigned bn_msm_window_bits(long forced, size_t n) {
+    if (forced >= 1) return (unsigned)forced;
+    unsigned lg = 0;
+    while (((size_t)2 << lg) <= n) ++lg;                     // floor(log2 n), 0 for n <= 1
+    // G1 and G2 agree on the best width at every measured size; between neighbouring widths the kernel time differs by a few percent
+    // (the accumulation is bound by its gathers, not by the W additions per term) except where a width leaves a top window of one or
+    // two bits, whose few buckets every term hits (13 at 2^19: 7.3 against 6.6 ms)
+    return lg <= 14 ? 8 : lg == 15 ? 9 : lg <= 17 ? 11 : lg == 18 ? 12 : lg == 19 ? 11 : 14;
+}
+// cb-bit windows over chunks of at most `chunk` terms, V bytes per point, L = bn254_msm_piece_M() entries per lane and level
+struct MsmBucketPlan {
+    unsigned W, G, groups;                       // windows; buckets per group of the reduction; groups per window
+    size_t K, count, n0max;                      // buckets; (window, group) pairs = tail terms / 2; entries of a chunk, at most
+    std::vector<size_t> out_slots;               // slots every level writes, from the upper bound of its entries
+    size_t o_counts, o_tiles, o_n0, o_idx, o_keys, o_buckets, o_terms, bytes;      // 256-byte aligned offsets into the workspace, and its size
+    std::vector<std::pair<size_t, size_t>> o_level;                                // per level: partial sums, their keys
+};
+inline MsmBucketPlan msm_bucket_plan(unsigned cb, size_t chunk, size_t V, size_t L) {
+    MsmBucketPlan p;
+    p.W = (254 + cb - 1) / cb; p.G = std::min(BN_MSM_GROUP, 1u << cb); p.groups = (1u << cb) / p.G;
+    p.K = (size_t)p.W << cb; p.count = (size_t)p.W * p.groups;
+    p.n0max = (size_t)p.W * chunk;                 // < 254 * 2^22 < 2^32: positions and keys are 32-bit
+    for (size_t N = p.n0max;;) {
+        const size_t M = 2 * ((N + L - 1) / L);
+        p.out_slots.push_back(M);
+        if (N <= L) break;
+        N = M;
+    }
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += bn_align256(bytes); return o; };
+    p.o_counts = take(p.K * 4); p.o_tiles = take(1024 * 4); p.o_n0 = take(4); p.o_idx = take(p.n0max * 4); p.o_keys = take(p.n0max * 4); p.o_buckets = take(p.K * V);
+    for (size_t M : p.out_slots) { const size_t a = take(M * V), b = take(M * 4); p.o_level.push_back({a, b}); }
+    p.o_terms = take(2 * p.count * V);
+    p.bytes = at;
+    return p;
+}
+constexpr uint64_t BN_FR_MOD64[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};
+// out = (a + b) mod r for a, b < r (r < 2^254: the sum fits four words)
+inline void bn_fr_add(const uint64_t *a, const uint64_t *b, uint64_t *out) {
+    uint64_t t[4], d[4];
+    unsigned __int128 c = 0;
+    for (int i = 0; i < 4; ++i) { c += (unsigned __int128)a[i] + b[i]; t[i] = (uint64_t)c; c >>= 64; }
+    unsigned __int128 br = 0;
+    for (int i = 0; i < 4; ++i) { const unsigned __int128 x = (unsigned __int128)t[i] - BN_FR_MOD64[i] - br; d[i] = (uint64_t)x; br = (x >> 64) & 1; }
+    for (int i = 0; i < 4; ++i) out[i] = br ? t[i] : d[i];
+}
+inline void bn_fr_one(bn_fr *out) {                           // 2^256 mod r: the Montgomery image of one
+    uint64_t x[4] = {1, 0, 0, 0};
+    for (int i = 0; i < 256; ++i) bn_fr_add(x, x, x);
+    memcpy(out->l, x, sizeof x);
+}
+// the scalars of the tail's 2 * count terms as Montgomery images: base * 2^(c w) for the S term of every (window, group), then 2^(c w) for the T terms
+inline void msm_tail_scalars(unsigned cb, std::vector<uint64_t> &h) {
+    const unsigned W = (254 + cb - 1) / cb, G = std::min(BN_MSM_GROUP, 1u << cb), groups = (1u << cb) / G;
+    const size_t count = (size_t)W * groups;
+    h.assign(2 * count * 4, 0);
+    bn_fr pw; bn_fr_one(&pw);
+    for (unsigned w = 0; w < W; ++w) {
+        uint64_t step[4], acc[4] = {0, 0, 0, 0};
+        memcpy(step, pw.l, sizeof step);
+        for (unsigned b = 1; b < G; b <<= 1) bn_fr_add(step, step, step);                  // G * 2^(c w)
+        for (unsigned q = 0; q < groups; ++q) {
+            memcpy(&h[((size_t)w * groups + q) * 4], acc, sizeof acc);
+            memcpy(&h[(count + (size_t)w * groups + q) * 4], pw.l, sizeof acc);
+            bn_fr_add(acc, step, acc);
+        }
+        for (unsigned b = 0; b < cb; ++b) bn_fr_add(pw.l, pw.l, pw.l);
+    }
+}

@@ -482,3 +482,64 @@ static void hsb_shared(const uint32_t *g1, const uint32_t *g2, uint32_t *o) {
 EXPORT void hsb_pairing_product_shared(int m, const uint32_t *g1, const uint32_t *g2, uint32_t *o) {
     if (m == 2) hsb_shared<2>(g1, g2, o); else hsb_shared<4>(g1, g2, o);
 }
+
+// ---- the host planners (bn_amd/csrc/host_plan.hpp) as flat arrays of 64-bit words; pointers are reported as byte offsets from the
+// workspace base and the output base.  Every export returns 0 when an array is too small (counts[] then holds what it needs).
+#include "../../bn_amd/csrc/host_plan.hpp"
+// pieces: (src offset, dst is out, dst offset, cnt, last); launches: (chunk, tail, first, count); chunks: (lo, hi, carry_out);
+// counts: pieces, launches, chunks, plan ok
+EXPORT int hs_seg_plan(const size_t *off, size_t m, size_t chunk, int small, size_t V, size_t fold, int snap, uint64_t *pieces, uint64_t *launches, uint64_t *chunks,
+                       size_t cap, uint64_t *counts) {
+    char *const ws = (char *)((uintptr_t)1 << 40), *const out = (char *)((uintptr_t)1 << 50);
+    std::vector<BnSegPiece> pc;
+    std::vector<SegChunk> ch;
+    counts[3] = seg_plan(off, m, chunk, small != 0, ws, out, pc, ch, V, fold, snap != 0) ? 1 : 0;
+    size_t nl = 0;
+    for (const SegChunk &c : ch) nl += c.launches.size();
+    counts[0] = pc.size(); counts[1] = nl; counts[2] = ch.size();
+    if (pc.size() > cap || nl > cap || ch.size() > cap) return 0;
+    for (size_t i = 0; i < pc.size(); ++i) {
+        const bool to_out = (const char *)pc[i].dst >= out;
+        const uint64_t row[5] = {(uint64_t)((const char *)pc[i].src - ws), to_out, (uint64_t)((const char *)pc[i].dst - (to_out ? out : ws)), pc[i].cnt, pc[i].last};
+        memcpy(pieces + 5 * i, row, sizeof row);
+    }
+    for (size_t ci = 0, l = 0; ci < ch.size(); ++ci) {
+        chunks[3 * ci] = ch[ci].lo; chunks[3 * ci + 1] = ch[ci].hi; chunks[3 * ci + 2] = ch[ci].carry_out;
+        for (const SegLaunch &s : ch[ci].launches) { const uint64_t row[4] = {ci, s.tail, s.first, s.count}; memcpy(launches + 4 * l++, row, sizeof row); }
+    }
+    return 1;
+}
+EXPORT size_t hs_seg_partials_max(size_t chunk, size_t fold) { return seg_partials_max(chunk, fold); }
+EXPORT size_t hs_seg_tail_max() { return BN_TAIL_SEG_MAX; }
+// voff: m + 1 derived offsets; chunk_ranges: (lo, hi) of every chunk, in pieces; step(count) = bn_equal_parts(count, round);
+// pieces: (first, cnt); subs: (chunk, lo, cnt, base); counts: pieces, subs
+EXPORT int hs_miller_cut(const size_t *off, size_t m, int direct, const size_t *chunk_ranges, size_t nchunks, size_t round, uint64_t *voff, uint64_t *pieces, uint64_t *subs,
+                         size_t cap, uint64_t *counts) {
+    std::vector<SegChunk> ch;
+    for (size_t i = 0; i < nchunks; ++i) ch.push_back({chunk_ranges[2 * i], chunk_ranges[2 * i + 1], false, {}});
+    const std::vector<size_t> vo = miller_value_offsets(off, m);
+    for (size_t j = 0; j <= m; ++j) voff[j] = vo[j];
+    const MillerCut mc = miller_cut(off, m, direct != 0, ch, [&](size_t count) { return bn_equal_parts(count, round); });
+    counts[0] = mc.pieces.size(); counts[1] = mc.subs.size();
+    if (mc.pieces.size() > cap || mc.subs.size() > cap) return 0;
+    for (size_t i = 0; i < mc.pieces.size(); ++i) { pieces[2 * i] = mc.pieces[i].first; pieces[2 * i + 1] = mc.pieces[i].cnt; }
+    for (size_t ci = 0; ci < nchunks; ++ci)
+        for (size_t i = mc.chunk_subs[ci]; i < mc.chunk_subs[ci + 1]; ++i) { const uint64_t row[4] = {ci, mc.subs[i].lo, mc.subs[i].cnt, mc.subs[i].base}; memcpy(subs + 4 * i, row, sizeof row); }
+    return 1;
+}
+// head: W, G, groups, K, count, n0max, o_counts, o_tiles, o_n0, o_idx, o_keys, o_buckets, o_terms, bytes, levels; levels: (out_slots, o_points, o_keys)
+EXPORT int hs_msm_bucket_plan(unsigned cb, size_t chunk, size_t V, size_t L, uint64_t *head, uint64_t *levels, size_t cap) {
+    const MsmBucketPlan p = msm_bucket_plan(cb, chunk, V, L);
+    const uint64_t h[15] = {p.W, p.G, p.groups, p.K, p.count, p.n0max, p.o_counts, p.o_tiles, p.o_n0, p.o_idx, p.o_keys, p.o_buckets, p.o_terms, p.bytes, p.out_slots.size()};
+    memcpy(head, h, sizeof h);
+    if (p.out_slots.size() > cap || p.o_level.size() != p.out_slots.size()) return 0;
+    for (size_t i = 0; i < p.out_slots.size(); ++i) { levels[3 * i] = p.out_slots[i]; levels[3 * i + 1] = p.o_level[i].first; levels[3 * i + 2] = p.o_level[i].second; }
+    return 1;
+}
+EXPORT unsigned hs_msm_window_bits(long forced, size_t n) { return bn_msm_window_bits(forced, n); }
+EXPORT size_t hs_msm_tail_scalars(unsigned cb, uint64_t *out, size_t cap) {           // words written (4 per scalar), or needed
+    std::vector<uint64_t> h;
+    msm_tail_scalars(cb, h);
+    if (h.size() <= cap) memcpy(out, h.data(), h.size() * 8);
+    return h.size();
+}

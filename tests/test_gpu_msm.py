@@ -11,7 +11,7 @@ from conftest import canon_infinity
 pytestmark = pytest.mark.gpu
 
 R = M.R_ORD
-FOLD = 4                                   # BN_MSM_FOLD of bn_amd/csrc/bn254_hip.hip: values per lane (lane pair) and fold level
+FOLD = 4                                   # BN_MSM_FOLD of bn_amd/csrc/bn254_seg.hip: values per lane (lane pair) and fold level
 LONG = 3001                                # "one of a few thousand": six fold levels
 LENGTHS = [0, 1, 2, 3, FOLD - 1, FOLD, FOLD + 1, FOLD * FOLD + 1, LONG]
 STEP = {1: 1 << 20, 2: 1 << 19}            # terms per launch of the term kernel (BN_MUL_LANES_PER_LAUNCH lanes; G2: two lanes per point)

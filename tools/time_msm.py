@@ -6,7 +6,7 @@ buffers on both sides:
 For every shape (segments x terms per segment) both sides are warmed up, then alternate inside the same process; the median wall ms of
 --repeats runs of each, their ratio (the condition is new / composition < 0.97), and the kernel-time split of the new call
 (g*_msm_mul / g*_msm_fold from bn254_kernel_stats) beside g*_mul of bn254_g*_mul_batch_dev on the same terms.
---build-sweep W1,W2,...  (no GPU needed) builds build_variants/lib_msmfold_W.so: the library with BN_MSM_FOLD = W (only bn254_hip.hip is
+--build-sweep W1,W2,...  (no GPU needed) builds build_variants/lib_msmfold_W.so: the library with BN_MSM_FOLD = W (only bn254_seg.hip is
                          recompiled, from a copy with the constant replaced; the other objects come from the last regular build)
 --sweep W1,W2,...        runs the shapes once per such library, each in a child process of its own, and prints one table per width
 usage: tools/time_msm.py [--repeats 7] [--shapes 64x9,16384x16] [--groups 1,2] [--sweep 4,8,16,32]"""
@@ -31,19 +31,19 @@ def build_sweep(widths):
     from bn_amd import _native
     _native.build()
     VARIANTS.mkdir(exist_ok=True)
-    src = (_native.HERE / "csrc" / "bn254_hip.hip").read_text()
+    src = (_native.HERE / "csrc" / "bn254_seg.hip").read_text()
     pat = r"constexpr size_t BN_MSM_FOLD = \d+;"
     assert len(re.findall(pat, src)) == 1
     flags = (_native.OBJ_DIR / "flags.txt").read_text().split()
     for w in widths:
         unit = _native.HERE / "csrc" / f"_msmfold_{w}.hip"            # beside the original: it includes its headers by relative path
-        obj = VARIANTS / f"bn254_hip_msmfold_{w}.o"
+        obj = VARIANTS / f"bn254_seg_msmfold_{w}.o"
         try:
             unit.write_text(re.sub(pat, f"constexpr size_t BN_MSM_FOLD = {w};", src))
             subprocess.check_call(flags + ["-c", str(unit), "-o", str(obj)])
         finally:
             unit.unlink(missing_ok=True)
-        objs = [str(obj if s.stem == "bn254_hip" else _native.OBJ_DIR / (s.stem + ".o")) for s in _native.SOURCES]
+        objs = [str(obj if s.stem == "bn254_seg" else _native.OBJ_DIR / (s.stem + ".o")) for s in _native.SOURCES]
         so = VARIANTS / f"lib_msmfold_{w}.so"
         subprocess.check_call([_native.HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-ldl", "-lpthread", "-o", str(so)])
         obj.unlink()
