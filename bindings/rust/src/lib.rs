@@ -74,6 +74,10 @@ extern "C" {
     fn bn254_g2_msm_dev(ctx: *mut c_void, d_p: *const c_void, d_k: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn bn254_g1_msm_multi(mh: *mut c_void, p: *const G1, k: *const Fr, n: usize, out: *mut G1) -> c_int;
     fn bn254_g2_msm_multi(mh: *mut c_void, p: *const G2, k: *const Fr, n: usize, out: *mut G2) -> c_int;
+    fn bn254_g1_mul_base_batch(ctx: *mut c_void, base: *const G1, k: *const Fr, out: *mut G1, n: usize) -> c_int;
+    fn bn254_g2_mul_base_batch(ctx: *mut c_void, base: *const G2, k: *const Fr, out: *mut G2, n: usize) -> c_int;
+    fn bn254_g1_mul_base_batch_dev(ctx: *mut c_void, base: *const G1, d_k: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_g2_mul_base_batch_dev(ctx: *mut c_void, base: *const G2, d_k: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
 }
 
 /// One line-function coefficient of a prepared G2 point: the crate's `EllCoeffs { ell_0, ell_vw, ell_vv: Fq2 }` (src/groups/mod.rs:472-476) as the
@@ -205,6 +209,21 @@ pub fn g2_msm(p: &[G2], k: &[Fr]) -> Result<G2, GpuError> {
     assert_eq!(p.len(), k.len());
     let mut out = G2::zero();
     check(unsafe { bn254_g2_msm(std::ptr::null_mut(), p.as_ptr(), k.as_ptr(), p.len(), &mut out) })?;
+    Ok(out)
+}
+
+/// `out[i] = (base * k[i]).normalize()`: fixed-base scalar multiplication - many scalars against ONE point (key and SRS generation,
+/// `G::random`).  The same bytes as `g1_mul_batch` on `k.len()` copies of `base`; the context keeps a table of multiples of the four most
+/// recently used bases per group, after which a product is at most 22 mixed additions
+pub fn g1_mul_base(base: &G1, k: &[Fr]) -> Result<Vec<G1>, GpuError> {
+    let mut out = vec![G1::zero(); k.len()];
+    check(unsafe { bn254_g1_mul_base_batch(std::ptr::null_mut(), base, k.as_ptr(), out.as_mut_ptr(), k.len()) })?;
+    Ok(out)
+}
+
+pub fn g2_mul_base(base: &G2, k: &[Fr]) -> Result<Vec<G2>, GpuError> {
+    let mut out = vec![G2::zero(); k.len()];
+    check(unsafe { bn254_g2_mul_base_batch(std::ptr::null_mut(), base, k.as_ptr(), out.as_mut_ptr(), k.len()) })?;
     Ok(out)
 }
 

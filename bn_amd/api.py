@@ -110,6 +110,8 @@ class G1(_Point):
     @staticmethod
     def msm(points, scalars):             # normalize(sum points[i] * scalars[i]) in one call
         return g1_msm(points, scalars)
+    def mul_base(self, scalars):          # [self * k for k in scalars] over ONE cached table of self
+        return g1_mul_base(self, scalars)
 
 
 _G2_GEN = ((10857046999023057135944570762232829481370756359578518086990519993285655852781,
@@ -142,6 +144,8 @@ class G2(_Point):
     @staticmethod
     def msm(points, scalars):
         return g2_msm(points, scalars)
+    def mul_base(self, scalars):
+        return g2_mul_base(self, scalars)
 
 
 class Gt:
@@ -267,6 +271,27 @@ def g2_msm(points, scalars, engine=None):
     """the same over G2: sequences of G2 / Fr, or (n,24) / (n,4) arrays"""
     P, K = _msm1_arrays(G2, points, scalars)
     return G2((engine or default_engine()).g2_msm(P, K))
+
+
+def _scalar_array(scalars):
+    if isinstance(scalars, np.ndarray):
+        return np.asarray(scalars, np.uint64).reshape(-1, 4)
+    scalars = list(scalars)
+    return np.stack([k.limbs for k in scalars]) if scalars else np.zeros((0, 4), np.uint64)
+
+
+def g1_mul_base(base, scalars, engine=None):
+    """[base * k for k in scalars], normalized like `base * k`: fixed-base scalar multiplication - key / SRS generation, many scalars against
+    one generator.  The engine builds a table of multiples of `base` once and keeps it (four bases per group); every product is then at most
+    22 mixed additions.  base: a G1 (or 12 uint64 words); scalars: a sequence of Fr or an (n,4) uint64 array."""
+    b = base.limbs if isinstance(base, G1) else base
+    return [G1(r) for r in (engine or default_engine()).g1_mul_base_batch(b, _scalar_array(scalars))]
+
+
+def g2_mul_base(base, scalars, engine=None):
+    """the same over G2: base a G2 (or 24 uint64 words)"""
+    b = base.limbs if isinstance(base, G2) else base
+    return [G2(r) for r in (engine or default_engine()).g2_mul_base_batch(b, _scalar_array(scalars))]
 
 
 class PreparedG2:

@@ -341,6 +341,12 @@ void bn254_ctx_destroy(bn254_ctx *c) {
     c->ws.release(); c->exp_tbl.release(); c->pow_tbl.release(); c->miller_state.release(); c->mul_tbl.release();
     c->seg_plan.release(); c->seg_plan_host.release(); c->msm_ws.release(); c->msm_scal.release();
     if (c->seg_plan_ev) hipEventDestroy(c->seg_plan_ev);
+    for (auto &bc : c->base_cache) {
+        for (auto &sl : bc.slot) sl.table.release();
+        bc.scal.release();
+    }
+    c->base_stage.release(); c->base_stage_host.release();
+    if (c->base_stage_ev) hipEventDestroy(c->base_stage_ev);
     for (auto &b : c->stage) b.release();
     for (auto &s : c->slot) {
         for (auto &b : s.d_in) b.release();

@@ -410,7 +410,98 @@ struct G2PointIo {
     __device__ __forceinline__ Jac<F> operator()(const uint32_t *w) const { return Jac<F>{f2_load((const F2 *)nullptr, w), f2_load((const F2 *)nullptr, w + 16), f2_load((const F2 *)nullptr, w + 32)}; }
     __device__ __forceinline__ void operator()(const Jac<F> &r, uint32_t *o) const { f2_store(r.x, o); f2_store(r.y, o + 16); f2_store(r.z, o + 32); }
 };
+// ---- fixed-base scalar multiplication of bn254_g{1,2}_mul_base_batch: out[i] = normalize(B * k[i]) for ONE base B per call
+// (bn254_seg.hip bn_launch_mul_base keeps the tables and plans the launches).  The table of a base holds the AFFINE points d * 2^(c w) * B for
+// w < W = ceil(254 / c) and d = 1 .. 2^(c-1), entry (w, d) at index w * 2^(c-1) + d - 1, in the form of AffTableMem: 9 + 9 limbs padded to
+// 80 bytes per lane, read as five 16-byte loads - G1 one such record per entry, G2 two (component c0 for the even lane of a pair, c1 for the
+// odd one).  Word 18 of a record is not zero when the entry is the point at infinity (the base was).
+// The chain: the canonical integer of the scalar is recoded, low window first, into W signed c-bit digits in [-2^(c-1), 2^(c-1)] with a
+// carry (the top window of a scalar below r < 2^254 <= 2^(c W - 1) never carries), and every non-zero digit is ONE mixed addition of the
+// entry |d| of its window, y negated for d < 0 - no doubling, and the accumulator starts at infinity.  The partial sum below window w is
+// smaller than 2^(c w) in absolute value, so it never equals +- the entry of window w as an INTEGER; mod r that argument holds up to the
+// top window only: k = r - 2 (r mod 2^(c (W-1))) recodes (when the low part carries, as it does for c = 8, 10 and 12) to a partial sum -t B and a top entry
+// (r - t) B, the same point.  The additions are therefore the complete ones (jac_madd_signed / jac_madd_flags: equal points double,
+// opposite points and an accumulator at infinity are followed by flags).
+struct BaseMulArgs {
+    const uint32_t *k; uint32_t *out; const uint4 *table; uint32_t c, W;
+};
+template <class F>
+__device__ __forceinline__ Aff<F> base_entry(const uint4 *rec, bool &inf) {
+    uint32_t w[20];
+#pragma unroll
+    for (int g = 0; g < 5; ++g) { const uint4 v = rec[g]; w[4 * g] = v.x; w[4 * g + 1] = v.y; w[4 * g + 2] = v.z; w[4 * g + 3] = v.w; }
+    Aff<F> r;
+    Fe x, y;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { x.l[i] = w[i]; y.l[i] = w[9 + i]; }
+    if constexpr (std::is_same<F, FqField>::value) { r.x = x; r.y = y; } else { r.x.v = x; r.y.v = y; }
+    inf = w[18] != 0;
+    return r;
+}
+// comp: 0 for G1; the lane's component (lane & 1) of a G2 lane pair - both lanes of a pair walk the same digits
+template <class F, uint32_t WORDS, class Store>
+__device__ __forceinline__ void base_mul_body(const BaseMulArgs &g, uint32_t i, uint32_t comp, Store store) {
+    constexpr bool G1 = std::is_same<F, FqField>::value;
+    constexpr uint32_t REC = G1 ? AFF_ENTRY_U4 : 2 * AFF_ENTRY_U4;            // 16-byte groups per table entry
+    uint32_t kw[8], raw[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) kw[j] = g.k[8u * i + j];
+    fr_from_mont(kw, raw);
+    const uint32_t half = 1u << (g.c - 1);
+    Jac<F> acc = {F::zero(), F::one(), F::zero()};
+    bool acc_inf = true;
+    uint32_t carry = 0;
+#pragma unroll 1
+    for (uint32_t w = 0; w < g.W; ++w) {
+        const uint32_t v = msm_digit(raw, w, g.c) + carry;
+        carry = v > half ? 1u : 0u;
+        const uint32_t ad = carry ? (2u * half - v) : v;                      // |digit| <= 2^(c-1)
+        bool e_inf;
+        const Aff<F> q = base_entry<F>(g.table + (size_t)(w * half + (ad ? ad - 1u : 0u)) * REC + comp * AFF_ENTRY_U4, e_inf);
+        const bool q_inf = e_inf || ad == 0;                                  // digit 0: the operand is ignored
+        if constexpr (G1) {
+            acc = jac_madd_signed(acc, q, carry != 0, acc_inf, q_inf);
+        } else {
+            Aff<F> qs = q;
+            qs.y = F::select(carry != 0, q.y, F::template lc3<-1, 0, 0>(q.y, q.y, q.y));
+            acc = jac_madd_flags<F>(acc, qs, acc_inf, q_inf);
+            acc_inf = F::is_zero_std(acc.z);
+        }
+    }
+    store(jac_normalize<F>(acc), g.out + (size_t)i * WORDS);
+}
+// The table build after the shipped normalising kernel (bn254_g{1,2}_mul_M over the tiled base and the host-known scalars d * 2^(c w)):
+// tile - record j of `out` = the one point at `src`; repack - thread t turns component t % comps of the normalised point t / comps into its
+// 80-byte record.  Instances of bn254_fr_decode_k like the other integer kernels of this unit.
+struct BaseTileOp {
+    const uint32_t *src; uint32_t *out; uint32_t words, n;
+    __device__ __forceinline__ void operator()() const {
+        const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+        if (t >= n * words) return;
+        out[t] = src[t % words];
+    }
+};
+struct BaseRepackOp {
+    const uint32_t *pts; uint4 *table; uint32_t comps, n;                     // comps: 1 (G1: 24 words per point) or 2 (G2: 48)
+    __device__ __forceinline__ void operator()() const {
+        const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+        if (t >= n * comps) return;
+        const uint32_t e = t / comps, comp = t % comps;
+        const uint32_t *p = pts + (size_t)e * 24u * comps;
+        const Fe x = fe_from_u32x8(p + 8u * comp), y = fe_from_u32x8(p + 8u * comps + 8u * comp);
+        uint32_t z = 0;
+        for (uint32_t j = 0; j < 8u * comps; ++j) z |= p[16u * comps + j];   // normalised: z is one, or zero at infinity (canonical words)
+        uint32_t w[20];
+        AffTableMem<FqField>::split(x, y, w);
+        w[18] = z == 0 ? 1u : 0u;
+        uint4 *rec = table + (size_t)t * AFF_ENTRY_U4;
+#pragma unroll
+        for (int g = 0; g < 5; ++g) rec[g] = make_uint4(w[4 * g], w[4 * g + 1], w[4 * g + 2], w[4 * g + 3]);
+    }
+};
 // `n`: lanes (G2: lane pairs) launched; a lane past the level's entries, or past the reduction's groups, has nothing to do (both lanes of a pair alike)
+__device__ __forceinline__ void msm_point_op(const BaseMulArgs &g, uint32_t i, G1PointIo io) { base_mul_body<FqField, 24u>(g, i, 0u, io); }
+__device__ __forceinline__ void msm_point_op(const BaseMulArgs &g, uint32_t i, G2PointIo io) { base_mul_body<Fq2Field<F2>, 48u>(g, i, threadIdx.x & 1u, io); }
 __device__ __forceinline__ void msm_point_op(const MsmAccArgs &g, uint32_t i, G1PointIo io) { msm_acc_body<FqField, 24u>(g, i, io, io); }
 __device__ __forceinline__ void msm_point_op(const MsmAccArgs &g, uint32_t i, G2PointIo io) { msm_acc_body<Fq2Field<F2>, 48u>(g, i, io, io); }
 __device__ __forceinline__ void msm_point_op(const MsmReduceArgs &g, uint32_t i, G1PointIo io) { msm_reduce_body<FqField, 24u>(g, i, io, io); }
@@ -501,6 +592,31 @@ int bn254_launch_msm_reduce_M(int g, const void *buckets, unsigned G, unsigned g
     const unsigned grid = (unsigned)(((g == 1 ? count : 2 * count) + BLOCK - 1) / BLOCK);
     if (g == 1) hipLaunchKernelGGL(bn254_g1_add_M<MsmReduceArgs>, dim3(grid), dim3(BLOCK), 0, s, a, (uint32_t)count);
     else hipLaunchKernelGGL(bn254_g2_add_M<MsmReduceArgs>, dim3(grid), dim3(BLOCK), 0, s, a, (uint32_t)count);
+    return (int)hipGetLastError();
+}
+// bn254_g{1,2}_mul_base_batch.  A table: W * 2^(c-1) entries of 80 (G1) / 160 (G2) bytes for c-bit windows, 3 <= c <= 16 (c W > 254).
+size_t bn254_mul_base_table_bytes_M(int g, unsigned c) {
+    return (size_t)((254 + c - 1) / c) * ((size_t)1 << (c - 1)) * (g == 1 ? 1 : 2) * AFF_ENTRY_U4 * sizeof(uint4);
+}
+// out[i] = normalize(base * k[i]) for i < n <= 2^22 over the table of the base
+int bn254_launch_mul_base_M(int g, const void *table, unsigned c, const void *k, void *out, size_t n, hipStream_t s) {
+    const BaseMulArgs a = {(const uint32_t *)k, (uint32_t *)out, (const uint4 *)table, c, (254 + c - 1) / c};
+    const unsigned grid = (unsigned)(((g == 1 ? n : 2 * n) + BLOCK - 1) / BLOCK);
+    if (g == 1) hipLaunchKernelGGL(bn254_g1_add_M<BaseMulArgs>, dim3(grid), dim3(BLOCK), 0, s, a, (uint32_t)n);
+    else hipLaunchKernelGGL(bn254_g2_add_M<BaseMulArgs>, dim3(grid), dim3(BLOCK), 0, s, a, (uint32_t)n);
+    return (int)hipGetLastError();
+}
+// the two ends of a table build: `n` copies of the point at d_base to d_out; the n normalised points at d_pts into the n records of `table`
+int bn254_launch_mul_base_tile_M(int g, const void *d_base, void *d_out, size_t n, hipStream_t s) {
+    const uint32_t words = g == 1 ? 24u : 48u;
+    const BaseTileOp op = {(const uint32_t *)d_base, (uint32_t *)d_out, words, (uint32_t)n};
+    hipLaunchKernelGGL(bn254_fr_decode_k<BaseTileOp>, dim3((unsigned)((n * words + 255) / 256)), dim3(256), 0, s, op);
+    return (int)hipGetLastError();
+}
+int bn254_launch_mul_base_repack_M(int g, const void *d_pts, void *table, size_t n, hipStream_t s) {
+    const uint32_t comps = g == 1 ? 1u : 2u;
+    const BaseRepackOp op = {(const uint32_t *)d_pts, (uint4 *)table, comps, (uint32_t)n};
+    hipLaunchKernelGGL(bn254_fr_decode_k<BaseRepackOp>, dim3((unsigned)((n * comps + 255) / 256)), dim3(256), 0, s, op);
     return (int)hipGetLastError();
 }
 }

@@ -1,5 +1,6 @@
 // Segmented operations of the BN254 engine (include/bn254_hip.h): the batched multi-pairings bn254_pairing_product_batch*, the segmented
-// multi-scalar multiplications bn254_g{1,2}_msm_batch* and the one large sum bn254_g{1,2}_msm* with its bucket route.  Host code only: the
+// multi-scalar multiplications bn254_g{1,2}_msm_batch* and the one large sum bn254_g{1,2}_msm* with its bucket route; the fixed-base scalar multiplication bn254_g{1,2}_mul_base_batch* with its
+// table cache.  Host code only: the
 // plans are host_plan.hpp's, the kernels live in bn254_kernels_{b,w,mul}.hip.  Compiled like every unit (bn254_hip.hip: the flags).
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -241,6 +242,83 @@ static bool bn_msm_bucket_route(const bn254_ctx *c, int g, size_t n) {
     return n >= (size_t)(set >= 0 ? set : g == 1 ? BN_MSM_BUCKET_MIN_DEFAULT : BN_MSM_BUCKET_MIN_DEFAULT_G2);
 }
 
+// ---- fixed-base scalar multiplication: out[i] = normalize(base * k[i]) with ONE base for the whole call (bn254_g{1,2}_mul_base_batch*)
+// Everything bn254_g{1,2}_mul_batch redoes per scalar - GLV / GLS split, window table, ~128 doublings - depends on the base alone.  Here
+// a table of the affine points d * 2^(c w) * base (W = ceil(254 / c) windows, d = 1 .. 2^(c-1); kernels and layout: bn254_kernels_mul.hip
+// BaseMulArgs) turns a multiplication into at most W mixed additions and the normalisation (scope g*_mul_base; sub-launches of at most
+// BN_LAUNCH_MAX scalars).
+// The tables live in the context: BN_BASE_SLOTS per group, least recently used first out, keyed by the caller's bytes of the base (another
+// Jacobian representation of the same point is another key - and gives the same table, the entries are normalised).  EVERY miss builds
+// (scope g*_base_table): the base goes to the device through pinned staging, is tiled, multiplied by the host-known scalars d * 2^(c w) with
+// the shipped normalising kernel bn254_g{1,2}_mul_M and repacked into device limbs; a base at infinity gives a table of flagged entries
+// and every result (0, 1, 0).  Lookup, build and launches run under the caller's scratch guard, which is what orders a rebuild on one
+// stream behind the readers on another.
+namespace {
+std::atomic<unsigned> g_base_window[2];       // measurement only (bn254_mul_base_set_window): 0 = the shipped width
+unsigned bn_base_window(int g) {
+    const unsigned o = g_base_window[g - 1].load(std::memory_order_relaxed);
+    return o ? o : g == 1 ? BN_BASE_WINDOW_G1 : BN_BASE_WINDOW_G2;
+}
+// the scalars of a table build on the device, rebuilt only when the window width changes (as msm_scal)
+int bn_base_scalars(BnBaseCache &bc, unsigned cb, hipStream_t s) {
+    if (bc.scal_c == (long)cb) return BN254_OK;
+    int rc;
+    HIP_TRY(hipStreamSynchronize(s));                        // the previous image may still be on its way
+    base_table_scalars(cb, bc.scal_host);
+    if ((rc = bc.scal.reserve(bc.scal_host.size() * 8))) return rc;
+    bc.scal_c = -1;
+    HIP_TRY(hipMemcpyAsync(bc.scal.p, bc.scal_host.data(), bc.scal_host.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    bc.scal_c = (long)cb;
+    return BN254_OK;
+}
+// the slot that holds the table of `base` (HOST memory, read here), built on `s` if no slot has it; scratch guard held by the caller
+int bn_base_table(bn254_ctx *c, int g, const void *base, hipStream_t s, BnBaseSlot **out) {
+    const size_t V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2);
+    const unsigned cb = bn_base_window(g);
+    BnBaseCache &bc = c->base_cache[g - 1];
+    ++bc.tick;
+    BnBaseSlot *victim = nullptr;
+    for (BnBaseSlot &sl : bc.slot) {
+        if (sl.valid && sl.c == cb && !memcmp(sl.key, base, V)) { sl.used = bc.tick; *out = &sl; return BN254_OK; }
+        if (!victim || (victim->valid && (!sl.valid || sl.used < victim->used))) victim = &sl;
+    }
+    victim->valid = false;
+    int rc;
+    const size_t E = bn_base_entries(cb);
+    if ((rc = bn_base_scalars(bc, cb, s))) return rc;
+    if (c->base_stage_ev) HIP_TRY(hipEventSynchronize(c->base_stage_ev));
+    else HIP_TRY(hipEventCreateWithFlags(&c->base_stage_ev, hipEventDisableTiming));
+    if ((rc = c->base_stage_host.reserve(sizeof(bn_g2))) || (rc = c->base_stage.reserve(sizeof(bn_g2)))) return rc;
+    if ((rc = c->ws.reserve(2 * E * V)) || (rc = c->mul_tbl.reserve(bn254_mul_table_bytes_M(g, E)))) return rc;
+    if ((rc = victim->table.reserve(bn254_mul_base_table_bytes_M(g, cb)))) return rc;
+    memcpy(c->base_stage_host.p, base, V);
+    HIP_TRY(hipMemcpyAsync(c->base_stage.p, c->base_stage_host.p, V, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(c->base_stage_ev, s));
+    char *tiled = (char *)c->ws.p, *pts = tiled + E * V;
+    {
+        BnScope sc(c, s, g == 1 ? "g1_base_table" : "g2_base_table");
+        if ((rc = bn254_launch_mul_base_tile_M(g, c->base_stage.p, tiled, E, s))) return rc;
+        if ((rc = g == 1 ? bn254_launch_g1_mul_M(tiled, bc.scal.p, pts, E, 1, c->mul_tbl.p, s) : bn254_launch_g2_mul_M(tiled, bc.scal.p, pts, E, 1, c->mul_tbl.p, s))) return rc;
+        if ((rc = bn254_launch_mul_base_repack_M(g, pts, victim->table.p, E, s))) return rc;
+    }
+    memcpy(victim->key, base, V);
+    victim->c = cb; victim->used = bc.tick; victim->valid = true;
+    *out = victim;
+    return BN254_OK;
+}
+// base is HOST memory; scratch guard held by the caller
+int bn_launch_mul_base(bn254_ctx *c, int g, const void *base, const void *d_k, void *d_out, size_t n, hipStream_t s) {
+    const size_t V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2);
+    BnBaseSlot *sl = nullptr;
+    int rc = bn_base_table(c, g, base, s, &sl); if (rc) return rc;
+    return bn_for_parts(n, BN_LAUNCH_MAX, [&](size_t lo, size_t cnt) -> int {
+        BnScope sc(c, s, g == 1 ? "g1_mul_base" : "g2_mul_base");
+        return bn254_launch_mul_base_M(g, sl->table.p, sl->c, (const char *)d_k + lo * sizeof(bn_fr), (char *)d_out + lo * V, cnt, s);
+    });
+}
+}  // namespace
+
 // argument checks of bn254_pairing_product_batch_prepared_native* for m > 0 that need no device: the CSR rules, the handle, and - where the
 // indices are host memory - every index
 // (`indexed`: the pairs carry indices; `q_index`: those indices where the host can read them)
@@ -296,6 +374,37 @@ static int msm1_dev(bn254_ctx *ctx, int g, const void *d_p, const void *d_k, siz
 }
 int bn254_g1_msm_dev(bn254_ctx *c, const void *p, const void *k, size_t n, void *o, void *s) { return msm1_dev(c, 1, p, k, n, o, s); }
 int bn254_g2_msm_dev(bn254_ctx *c, const void *p, const void *k, size_t n, void *o, void *s) { return msm1_dev(c, 2, p, k, n, o, s); }
+// order of the checks: empty batch, arguments, then context and device
+static int mul_base_dev(bn254_ctx *ctx, int g, const void *base, const void *d_k, void *d_out, size_t n, void *stream) {
+    if (n == 0) return BN254_OK;
+    if (n > BN_N_MAX || !base || !d_k || !d_out) return BN254_E_BAD_ARG;          // before any device lookup
+    return bn_seg_entry(ctx, stream, [&](hipStream_t s) { return bn_launch_mul_base(ctx, g, base, d_k, d_out, n, s); });
+}
+int bn254_g1_mul_base_batch_dev(bn254_ctx *c, const bn_g1 *base, const void *k, void *o, size_t n, void *s) { return mul_base_dev(c, 1, base, k, o, n, s); }
+int bn254_g2_mul_base_batch_dev(bn254_ctx *c, const bn_g2 *base, const void *k, void *o, size_t n, void *s) { return mul_base_dev(c, 2, base, k, o, n, s); }
+// internal (not in the header; tests and tools/time_mul_base.py): the shipped window width of a group, the device bytes of one table, the
+// slots per group, the scalars a table is built with (returns their count; writes 4 words each when `cap_words` suffices), and - for the
+// width sweep only - a process-wide override of the width (0 restores the shipped one; tables of another width are rebuilt on use)
+unsigned bn254_mul_base_window(int g) { return g == 1 ? BN_BASE_WINDOW_G1 : BN_BASE_WINDOW_G2; }
+size_t bn254_mul_base_table_bytes(int g) { return bn254_mul_base_table_bytes_M(g, bn254_mul_base_window(g)); }
+unsigned bn254_mul_base_slots(void) { return BN_BASE_SLOTS; }
+size_t bn254_mul_base_table_scalars(unsigned c, uint64_t *out, size_t cap_words) {
+    if (c < 3 || c > 16) return 0;
+    size_t count = 0;
+    (void)bn_no_throw([&]() -> int {
+        std::vector<uint64_t> h;
+        base_table_scalars(c, h);
+        if (out && cap_words >= h.size()) memcpy(out, h.data(), h.size() * 8);
+        count = h.size() / 4;
+        return BN254_OK;
+    });
+    return count;
+}
+int bn254_mul_base_set_window(int g, unsigned c) {
+    if ((g != 1 && g != 2) || (c != 0 && (c < 3 || c > 16))) return BN254_E_BAD_ARG;      // c = 2: W c = 254, the top window would carry
+    g_base_window[g - 1].store(c, std::memory_order_relaxed);
+    return BN254_OK;
+}
 
 // ---------------------------------------------------------------------------------------------- host-buffer API (BnHost: the context's mutex for the call)
 int bn254_pairing_product_batch(bn254_ctx *ctx, const bn_g1 *p, const bn_g2 *q, const size_t *offsets, size_t m, bn_gt *out) {
@@ -342,5 +451,15 @@ static int msm1_host(bn254_ctx *ctx, int g, const void *p, const bn_fr *k, size_
 }
 int bn254_g1_msm(bn254_ctx *ctx, const bn_g1 *p, const bn_fr *k, size_t n, bn_g1 *out) { return msm1_host(ctx, 1, p, k, n, out); }
 int bn254_g2_msm(bn254_ctx *ctx, const bn_g2 *p, const bn_fr *k, size_t n, bn_g2 *out) { return msm1_host(ctx, 2, p, k, n, out); }
+static int mul_base_host(bn254_ctx *ctx, int g, const void *base, const bn_fr *k, void *out, size_t n) {
+    if (n == 0) return BN254_OK;
+    if (n > BN_N_MAX || !base || !k || !out) return BN254_E_BAD_ARG;              // before any device lookup
+    const size_t V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2);
+    BnHost h(ctx); if (h.rc) return h.rc;
+    return bn_staged(ctx, {k, n * sizeof(bn_fr)}, {nullptr, 0}, out, n * V, nullptr, 0,
+                     [&](const BnStaged &d) { return mul_base_dev(ctx, g, base, d.in[0], d.out, n, ctx->stream); });
+}
+int bn254_g1_mul_base_batch(bn254_ctx *ctx, const bn_g1 *base, const bn_fr *k, bn_g1 *out, size_t n) { return mul_base_host(ctx, 1, base, k, out, n); }
+int bn254_g2_mul_base_batch(bn254_ctx *ctx, const bn_g2 *base, const bn_fr *k, bn_g2 *out, size_t n) { return mul_base_host(ctx, 2, base, k, out, n); }
 
 }  // extern "C"

@@ -75,6 +75,28 @@ struct BnSlot {
     BnBuf d_in[2], d_out, tbl;
 };
 
+// Fixed-base tables of bn254_g{1,2}_mul_base_batch: per group a small LRU of device tables keyed by the raw bytes of the base they were built
+// from (and the window width).  Context-owned scratch like ws / exp_tbl: looked up, built and read under the BnScratchGuard of the call, so a
+// slot is rebuilt only by a stream that has waited for the last launch that may read it.
+constexpr int BN_BASE_SLOTS = 4;
+// signed window width of the tables, per group: the fastest of the measured 8 / 10 / 12 (profiles/r11_mul_base.txt: G1 2^20 scalars
+// 2.84 / 2.41 / 2.13 ms, G2 2^18 scalars 2.06 / 1.71 / 1.50 ms of kernel time)
+constexpr unsigned BN_BASE_WINDOW_G1 = 12, BN_BASE_WINDOW_G2 = 12;
+struct BnBaseSlot {
+    BnBuf table;                        // W * 2^(c-1) entries of 80 (G1) / 160 (G2) bytes (bn254_kernels_mul.hip BaseMulArgs)
+    unsigned char key[sizeof(bn_g2)];   // the base as the caller passed it: 96 or 192 bytes
+    unsigned c = 0;                     // window width the table was built for
+    bool valid = false;
+    uint64_t used = 0;                  // tick of the last call that used it
+};
+struct BnBaseCache {
+    BnBaseSlot slot[BN_BASE_SLOTS];     // tables are allocated on first use
+    uint64_t tick = 0;
+    BnBuf scal;                         // the scalars d * 2^(c w) the tables are built with, for window width scal_c ...
+    std::vector<uint64_t> scal_host;    // ... and their host image (kept while the copy may be in flight)
+    long scal_c = -1;
+};
+
 struct bn254_ctx {
     int device = 0;
     int cus = 256;                      // compute units of the device (sizes one "round" of the lane-pair kernels: bn_round_pairs)
@@ -97,6 +119,10 @@ struct bn254_ctx {
     BnBuf msm_scal;                     // ... and the tail's scalars (Montgomery images of 2^(c w) and base * 2^(c w)) for window width msm_scal_c
     std::vector<uint64_t> msm_scal_host;    // their host image (kept while the copy may be in flight; rebuilt only when the width changes)
     long msm_scal_c = -1;
+    BnBaseCache base_cache[2];          // bn254_g{1,2}_mul_base_batch: [0] G1, [1] G2
+    BnBuf base_stage;                   // the base of a table build on the device ...
+    BnBuf base_stage_host{nullptr, 0, true};    // ... and its pinned staging, rewritten only after base_stage_ev (its last copy) completed
+    hipEvent_t base_stage_ev = nullptr;
     BnBuf stage[4];                     // device staging of the small host-buffer entry points (bn_staged: two inputs, two outputs)
     BnSlot slot[BN_MAX_SLOTS];          // pipelined path (bn254_multi.hip)
     // leases of those slots: a batch of up to one chunk takes ONE of the first two (two callers overlap on the GPU - the number
@@ -306,6 +332,10 @@ unsigned bn254_msm_piece_M(void);
 int bn254_launch_msm_bucket_M(int g, const void *pts, const void *idx, const void *keys, const void *n0, unsigned level, void *out_pts, void *out_keys, void *buckets,
                               size_t lanes, hipStream_t s);
 int bn254_launch_msm_reduce_M(int g, const void *buckets, unsigned G, unsigned groups, unsigned c, size_t count, void *terms, hipStream_t s);
+size_t bn254_mul_base_table_bytes_M(int g, unsigned c);
+int bn254_launch_mul_base_M(int g, const void *table, unsigned c, const void *k, void *out, size_t n, hipStream_t s);
+int bn254_launch_mul_base_tile_M(int g, const void *d_base, void *d_out, size_t n, hipStream_t s);
+int bn254_launch_mul_base_repack_M(int g, const void *d_pts, void *table, size_t n, hipStream_t s);
 // bn254_measure.hip
 int bn254_launch_gather_K(const void *d_records, size_t records, size_t record_bytes, const void *d_index, size_t n, void *d_out, hipStream_t s);
 }

@@ -1,5 +1,5 @@
 // Host arithmetic over sizes and offsets: the argument checks that need no device, the work lists of the segmented folds, the cutting of a
-// prepared batch into Miller pieces, the workspace of the bucket method and its tail scalars.  Plain C++17: nothing here touches a device, so
+// prepared batch into Miller pieces, the workspace of the bucket method and its tail scalars, the scalars of the fixed-base tables.  Plain C++17: nothing here touches a device, so
 // tests/hostsim/ compiles it with g++ and tests/test_host_plan.py replays the plans on the CPU.  (io.hpp: the two records the kernels read.)
 #pragma once
 #include <algorithm>
@@ -226,6 +226,27 @@ inline void msm_tail_scalars(unsigned cb, std::vector<uint64_t> &h) {
             memcpy(&h[((size_t)w * groups + q) * 4], acc, sizeof acc);
             memcpy(&h[(count + (size_t)w * groups + q) * 4], pw.l, sizeof acc);
             bn_fr_add(acc, step, acc);
+        }
+        for (unsigned b = 0; b < cb; ++b) bn_fr_add(pw.l, pw.l, pw.l);
+    }
+}
+
+// ---- fixed-base scalar multiplication (bn254_g{1,2}_mul_base_batch): the table of a base for signed c-bit windows holds d * 2^(c w) * B for
+// w < W = ceil(254 / c) and d = 1 .. 2^(c-1), entry (w, d) at index w * 2^(c-1) + d - 1
+inline unsigned bn_base_windows(unsigned cb) { return (254 + cb - 1) / cb; }
+inline size_t bn_base_entries(unsigned cb) { return (size_t)bn_base_windows(cb) << (cb - 1); }
+// the scalars the table is built with, in entry order, as Montgomery images: d * 2^(c w) mod r
+inline void base_table_scalars(unsigned cb, std::vector<uint64_t> &h) {
+    const unsigned W = bn_base_windows(cb);
+    const size_t half = (size_t)1 << (cb - 1);
+    h.assign(W * half * 4, 0);
+    bn_fr pw; bn_fr_one(&pw);
+    for (unsigned w = 0; w < W; ++w) {
+        uint64_t acc[4];
+        memcpy(acc, pw.l, sizeof acc);
+        for (size_t d = 1; d <= half; ++d) {
+            memcpy(&h[(w * half + d - 1) * 4], acc, sizeof acc);
+            bn_fr_add(acc, pw.l, acc);
         }
         for (unsigned b = 0; b < cb; ++b) bn_fr_add(pw.l, pw.l, pw.l);
     }

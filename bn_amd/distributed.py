@@ -13,7 +13,7 @@ Anything with the same five methods can be injected (the gloo tests inject an or
 """
 import numpy as np
 
-GT_WORDS = 48
+G1_WORDS, G2_WORDS, GT_WORDS = 12, 24, 48
 
 
 def shard_range(n, rank, world):
@@ -82,6 +82,17 @@ class TorchEngine:
     def g2_mul(self, p, k, normalize=True):
         out = self.torch.empty_like(p)
         self.e.g2_mul_dev(p.data_ptr(), k.data_ptr(), out.data_ptr(), p.shape[0], self._stream(), normalize)
+        return out
+
+    def g1_mul_base(self, base, k):
+        """base: ONE G1 point on the HOST (12 uint64 words, read before the call returns); k: (n,4) device tensor -> (n,12) normalized"""
+        out = self.empty(k.shape[0], G1_WORDS)
+        self.e.g1_mul_base_batch_dev(base, k.data_ptr(), out.data_ptr(), k.shape[0], self._stream())
+        return out
+
+    def g2_mul_base(self, base, k):
+        out = self.empty(k.shape[0], G2_WORDS)
+        self.e.g2_mul_base_batch_dev(base, k.data_ptr(), out.data_ptr(), k.shape[0], self._stream())
         return out
 
     def gt_pow(self, a, k):

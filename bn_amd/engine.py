@@ -173,6 +173,24 @@ class Engine:
         _native.check(self._lib.bn254_g2_mul_batch(self._h, _p(p), _p(k), _p(out), p.shape[0]))
         return out
 
+    def _mul_base(self, fn, base, k, words):
+        base = np.ascontiguousarray(base, dtype=np.uint64).reshape(-1)
+        if base.size != words:
+            raise ValueError(f"base must be ONE point of {words} uint64 words, got {base.size}")
+        k = _arr(k, 4) if len(k) else np.zeros((0, 4), np.uint64)
+        out = np.empty((k.shape[0], words), np.uint64)
+        _native.check(fn(self._h, _p(base), _p(k), _p(out), k.shape[0]))
+        return out
+
+    def g1_mul_base_batch(self, base, k):
+        """out[i] = normalize(base * k[i]) for ONE G1 point `base` (12 words) -> (n, 12) uint64: the bytes of g1_mul_batch on the tiled base,
+        by mixed additions over a per-base table the context caches (include/bn254_hip.h bn254_g1_mul_base_batch)"""
+        return self._mul_base(self._lib.bn254_g1_mul_base_batch, base, k, G1_WORDS)
+
+    def g2_mul_base_batch(self, base, k):
+        """the same over G2 (base: 24 words) -> (n, 24) uint64"""
+        return self._mul_base(self._lib.bn254_g2_mul_base_batch, base, k, G2_WORDS)
+
     def g1_msm_batch(self, p, k, offsets):
         """out[j] = normalize(sum of p[i] * k[i] over i in [offsets[j], offsets[j+1])) -> (m, 12) uint64; an empty or cancelling
         segment gives G1::zero() = (0, 1, 0); ONE inversion per segment (include/bn254_hip.h bn254_g1_msm_batch)"""
@@ -395,6 +413,19 @@ class Engine:
     def g2_mul_dev(self, d_p, d_k, d_out, n, stream=0, normalize=True):
         f = self._lib.bn254_g2_mul_batch_dev if normalize else self._lib.bn254_g2_mul_jacobian_dev
         _native.check(f(self._h, d_p, d_k, d_out, n, stream))
+
+    def g1_mul_base_batch_dev(self, base, d_k, d_out, n, stream=0):
+        """`base` is a HOST point (12 uint64 words), read before the call returns; d_k, d_out device pointers (n records), ordered on `stream`"""
+        base = np.ascontiguousarray(base, dtype=np.uint64).reshape(-1)
+        if base.size != G1_WORDS:
+            raise ValueError(f"base must be ONE point of {G1_WORDS} uint64 words, got {base.size}")
+        _native.check(self._lib.bn254_g1_mul_base_batch_dev(self._h, _p(base), d_k, d_out, n, stream))
+
+    def g2_mul_base_batch_dev(self, base, d_k, d_out, n, stream=0):
+        base = np.ascontiguousarray(base, dtype=np.uint64).reshape(-1)
+        if base.size != G2_WORDS:
+            raise ValueError(f"base must be ONE point of {G2_WORDS} uint64 words, got {base.size}")
+        _native.check(self._lib.bn254_g2_mul_base_batch_dev(self._h, _p(base), d_k, d_out, n, stream))
 
     def g1_msm_batch_dev(self, d_p, d_k, offsets, d_out, stream=0):
         """device pointers p, k, out (m points); `offsets` is a HOST sequence of m + 1 CSR offsets"""

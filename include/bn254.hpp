@@ -133,6 +133,18 @@ inline G2 g2_msm(const std::vector<G2> &p, const std::vector<Fr> &k) {
     check(bn254_g2_msm(nullptr, reinterpret_cast<const bn_g2 *>(p.data()), reinterpret_cast<const bn_fr *>(k.data()), p.size(), reinterpret_cast<bn_g2 *>(&out)));
     return out;
 }
+// out[i] = normalize(base * k[i]): fixed-base scalar multiplication, many scalars against ONE point - the bytes of g1_mul_batch on the tiled
+// base, by mixed additions over a table of multiples of `base` that the context caches (four bases per group)
+inline std::vector<G1> g1_mul_base(const G1 &base, const std::vector<Fr> &k) {
+    std::vector<G1> out(k.size());
+    check(bn254_g1_mul_base_batch(nullptr, reinterpret_cast<const bn_g1 *>(&base), reinterpret_cast<const bn_fr *>(k.data()), reinterpret_cast<bn_g1 *>(out.data()), k.size()));
+    return out;
+}
+inline std::vector<G2> g2_mul_base(const G2 &base, const std::vector<Fr> &k) {
+    std::vector<G2> out(k.size());
+    check(bn254_g2_mul_base_batch(nullptr, reinterpret_cast<const bn_g2 *>(&base), reinterpret_cast<const bn_fr *>(k.data()), reinterpret_cast<bn_g2 *>(out.data()), k.size()));
+    return out;
+}
 // ok[j] = (product of segment j == Gt::one()): the predicate of a block of pairing checks
 inline std::vector<bool> pairing_check_batch(const std::vector<G1> &p, const std::vector<G2> &q, const std::vector<size_t> &offsets) {
     const std::vector<Gt> r = pairing_product_batch(p, q, offsets);

@@ -20,6 +20,8 @@
  *   bn254_pairing_product_batch_prepared_native  the same with the G2 side prepared: pair i against point q_index[i] of a bn254_g2_prepared handle
  *   bn254_g1_mul_batch     out[i] = normalize(p[i] * k[i])                          lib.rs:116-120,88-95, groups/mod.rs:250-270
  *   bn254_g2_mul_batch     same over G2                                             lib.rs:159-163,131-138
+ *   bn254_g1_mul_base_batch / bn254_g2_mul_base_batch  out[i] = normalize(base * k[i]): the same with ONE left operand for the whole batch
+ *                                                                                    (G::random = G::one() * Fr::random(), groups/mod.rs:220-222)
  *   bn254_g1_msm_batch     out[j] = normalize(fold(G1::zero(), |acc, i| acc + p[i] * k[i])) over terms [offsets[j], offsets[j+1])
  *                                                                                    lib.rs:103-120,88-95, groups/mod.rs:250-311
  *   bn254_g2_msm_batch     same over G2                                             lib.rs:146-163,131-138
@@ -56,6 +58,8 @@
  *     entry point serialises its callers on the context (bn254_pairing_product_batch too, except when every segment holds one pair: then
  *     it IS bn254_pairing_batch; likewise bn254_g{1,2}_msm_batch, which are bn254_g{1,2}_mul_batch when every segment holds one term;
  *     bn254_g{1,2}_msm serialise on the context on either route, except for n == 1 below the bucket threshold: bn254_g{1,2}_mul_batch again).
+     bn254_g{1,2}_mul_base_batch serialise on the context as well (they hold its mutex for the call: lookup or build of the base's table,
+     staging, launches, copy back).
  *     bn254_pairing_product_batch_prepared_native serialises on the context like them; its handle is immutable and shared freely.
  *     Use one context per thread (or bn254_multi_*) for more overlap;
  *     bn254_ctx_set_option is atomic, but set options before concurrent use: a call in flight may run some
@@ -69,6 +73,10 @@
  *     bn254_g{1,2}_msm_dev keeps (sorted indices, counts, buckets, partial sums, tail terms).  bn254_g{1,2}_msm_dev plans its launches from
  *     upper bounds and reads nothing back; it synchronises the caller's stream only in a call that changes the window width (the tail's
  *     scalars are rebuilt and uploaded then), and briefly on the upload of the tail's work list like bn254_g{1,2}_msm_batch_dev.
+     The fixed-base tables of bn254_g{1,2}_mul_base_batch_dev are context-owned scratch of the same kind: a table is looked up, built and read
+     under the same event ordering, so a slot is never rebuilt while a launch on another stream may still read it.  The call reads its HOST
+     `base` before it returns (compared with the cached keys; copied to pinned staging on a miss).  It waits on the host only for the copy of
+     the previous miss's base, and - once per context and group - synchronises `stream` when it uploads the scalars the tables are built with.
  */
 #ifndef BN254_HIP_H
 #define BN254_HIP_H
@@ -183,6 +191,24 @@ int bn254_pairing_product(bn254_ctx *ctx, const bn_g1 *p, const bn_g2 *q, size_t
 int bn254_pairing_product_batch(bn254_ctx *ctx, const bn_g1 *p, const bn_g2 *q, const size_t *offsets, size_t m, bn_gt *out);
 int bn254_g1_mul_batch(bn254_ctx *ctx, const bn_g1 *p, const bn_fr *k, bn_g1 *out, size_t n);
 int bn254_g2_mul_batch(bn254_ctx *ctx, const bn_g2 *p, const bn_fr *k, bn_g2 *out, size_t n);
+/* Fixed-base scalar multiplication: out[i] = normalize(base[0] * k[i]) for i < n - key and SRS generation ([tau^i] G), G::random
+   (G::one() * Fr::random(), groups/mod.rs:220-222), Pedersen / ElGamal-style uses of one or two generators.  Bit-identical to
+   bn254_g{1,2}_mul_batch on n copies of `base` with the same k (normalisation makes the image unique).  `base` is ONE point in any Jacobian
+   representation; a base at infinity or k[i] == 0 gives G::zero() = (0, 1, 0); G2 as for bn254_g2_mul_batch: an order-r subgroup point.
+   How: per base a table of the affine multiples d * 2^(12 w) * base, w < 22, d = 1 .. 2048 (signed 12-bit windows, the fastest of the measured
+   8 / 10 / 12; 45 056 entries in the device's 9 x 29-bit limbs: 3 604 480 bytes for G1, 7 208 960 for G2), after which a multiplication is at
+   most 22 mixed additions, no doubling, and the normalisation.  The context keeps the tables of the FOUR most recently used bases per group, keyed by the bytes of `base` as passed (another
+   Jacobian representation of the same point is another key with an equal table): a hit launches the fixed-base kernel alone, a miss first
+   builds the table on the call's stream - the tiled base times the host-known scalars d * 2^(12 w) through the kernel of
+   bn254_g{1,2}_mul_batch, then a repack - and evicts the least recently used slot.  Every miss builds, whatever n is: a call with n = 1 and
+   a new base costs 1.14 ms (G1) / 2.05 ms (G2) of kernel time against 0.85 / 1.07 ms for bn254_g{1,2}_mul_batch at n = 1 (the build is
+   0.93 / 1.80 ms of it), so a caller whose base changes with every call wants bn254_g{1,2}_mul_batch; with the table cached the kernel
+   time is a fifth of the general kernel's: 2^20 G1 scalars 2.17 against 11.42 ms, 2^18 G2 scalars 1.50 against 7.15 ms
+   (profiles/r11_mul_base.txt).
+   Errors (BN254_E_BAD_ARG, checked before any device is touched): a NULL base, k or out with n > 0, n > 2^40.  n == 0 returns BN254_OK and
+   writes nothing.  Threading: see above - the host-buffer entry points hold the context's mutex for the call. */
+int bn254_g1_mul_base_batch(bn254_ctx *ctx, const bn_g1 *base, const bn_fr *k, bn_g1 *out, size_t n);
+int bn254_g2_mul_base_batch(bn254_ctx *ctx, const bn_g2 *base, const bn_fr *k, bn_g2 *out, size_t n);
 /* Segmented multi-scalar multiplication: m independent linear combinations in one call - the IC sums of a block of Groth16 checks, a*P + b*Q,
    random linear combinations of checks, aggregate keys.  Segments in CSR form: offsets[0..m] with offsets[0] == 0, non-decreasing,
    n = offsets[m] terms, and
@@ -421,6 +447,10 @@ int bn254_gt_pow_batch_dev(bn254_ctx *ctx, const void *d_a, const void *d_k, voi
 int bn254_gt_inverse_batch_dev(bn254_ctx *ctx, const void *d_a, void *d_out, size_t n, void *stream);
 int bn254_g1_mul_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, void *d_out, size_t n, void *stream);
 int bn254_g2_mul_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, void *d_out, size_t n, void *stream);
+/* bn254_g{1,2}_mul_base_batch on device-resident k and out (n records), asynchronous on `stream`; `base` is HOST memory (ONE point), read
+   before the call returns (the caller may overwrite it at once) */
+int bn254_g1_mul_base_batch_dev(bn254_ctx *ctx, const bn_g1 *base, const void *d_k, void *d_out, size_t n, void *stream);
+int bn254_g2_mul_base_batch_dev(bn254_ctx *ctx, const bn_g2 *base, const void *d_k, void *d_out, size_t n, void *stream);
 /* raw Jacobian result of the reference's MSB-first double-and-add (what G::random produces, groups/mod.rs:220-222):
    used to generate benchmark inputs with z != 1 on the device */
 int bn254_g1_mul_jacobian_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, void *d_out, size_t n, void *stream);
@@ -437,7 +467,7 @@ int bn254_tile_dev(bn254_ctx *ctx, const void *d_record, size_t record_bytes, si
    accumulated duration and launch count per kernel since the last reset (this is what bench.py's roofline uses). */
 int bn254_profile_enable(bn254_ctx *ctx, int on);
 int bn254_profile_reset(bn254_ctx *ctx);
-/* kernel: "miller", "miller_shared", "miller_wave", "miller_quad", "pairing_wave", "final_exp", "final_exp_wave", "final_exp_quad", "exp_by_neg_z", "gt_product", "gt_tail", "gt_segment", "gt_tail_seg", "g1_mul", "g2_mul", "gt_mul", "gt_pow", "g2_precompute", "miller_prepared", "g2_prepare_native", "miller_native", "miller_native_shared", "miller_native_seg", "g2_gather", "wire_encode", "wire_decode", "gt_inverse", "g1_add", "g2_add", "g1_msm_mul", "g1_msm_fold", "g2_msm_mul", "g2_msm_fold", "g1_msm_digits", "g1_msm_bucket", "g1_msm_reduce", "g2_msm_digits", "g2_msm_bucket", "g2_msm_reduce".
+/* kernel: "miller", "miller_shared", "miller_wave", "miller_quad", "pairing_wave", "final_exp", "final_exp_wave", "final_exp_quad", "exp_by_neg_z", "gt_product", "gt_tail", "gt_segment", "gt_tail_seg", "g1_mul", "g2_mul", "gt_mul", "gt_pow", "g2_precompute", "miller_prepared", "g2_prepare_native", "miller_native", "miller_native_shared", "miller_native_seg", "g2_gather", "wire_encode", "wire_decode", "gt_inverse", "g1_add", "g2_add", "g1_msm_mul", "g1_msm_fold", "g2_msm_mul", "g2_msm_fold", "g1_msm_digits", "g1_msm_bucket", "g1_msm_reduce", "g2_msm_digits", "g2_msm_bucket", "g2_msm_reduce", "g1_mul_base", "g2_mul_base", "g1_base_table", "g2_base_table".
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);
 /* issue-rate ceiling of v_mad_u64_u32 (the 32x32+64 multiply-accumulate every field product is built from) at
