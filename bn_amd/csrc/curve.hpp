@@ -254,7 +254,7 @@ BN_COARSE Jac<FqField> jac_madd_signed(const Jac<FqField> &p, const Aff<FqField>
 // CONJ_EXTRA (G2 only): every entry is rescaled by conj(Zc) as well, so that the common z becomes Zc conj(Zc) = norm(Zc), an element
 // of Fq - the isomorphism (x, y) -> (x s^2, y s^3) commutes with the Frobenius-twist endomorphism psi exactly when s is in Fq.
 // Where the affine window table lives.  Default: a per-lane array (host simulation, one-lane mapping).  The kernels keep it in a
-// buffer laid out [lane][entry][18 dwords padded to 80 bytes] (bn254_kernels_mul.hip AffTableMem): the entry a lane reads depends
+// buffer laid out [lane][entry][18 dwords padded to 80 bytes] (group_ops.hpp AffTableMem): the entry a lane reads depends
 // on ITS digit, and private (scratch) memory is interleaved across lanes dword by dword - a lane-indexed private array makes every
 // dword load of a wave touch up to 64 different 256-byte rows (measured: 32-51 GB of traffic per 2^20 G1 multiplications, 11 % of
 // the kernel's time, profiles/r03m_pmc_side.txt); 80 contiguous bytes per lane cost two cache lines.

@@ -1,0 +1,267 @@
+// The per-lane bodies of the group kernels (bn254_kernels_mul.hip): point I/O, the 80-byte table record, the complete addition, the segmented
+// fold of bn254_g{1,2}_msm_batch, the accumulation levels and the reduction of the bucket method (bn254_g{1,2}_msm) and the fixed-base chain
+// (bn254_g{1,2}_mul_base_batch).  Everything here is pure and takes plain pointers and a lane (G2: lane pair) index, so the host simulation
+// (tests/hostsim/hostsim.cpp) runs the very same bodies over host arrays; what needs a wave, a workgroup or a launch stays in the .hip.
+#pragma once
+#include "curve.hpp"
+#include "io.hpp"
+#include <type_traits>
+
+#if defined(BN_HOSTSIM)
+struct uint4 { uint32_t x, y, z, w; };
+inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return {x, y, z, w}; }
+inline uint32_t min(uint32_t a, uint32_t b) { return a < b ? a : b; }
+#endif
+
+// The argument records of the generic kernels bn254_g{1,2}_add_M<Args>.  They are template arguments of those kernels, so their names are part
+// of the kernels' symbols: they stay in the unnamed namespace, where they were first declared.
+namespace {
+struct MsmAccArgs {          // one accumulation level of the bucket method (msm_acc_body)
+    const uint32_t *pts, *idx, *keys, *n0; uint32_t level; uint32_t *out_pts, *out_keys, *buckets;
+};
+struct MsmReduceArgs {       // the bucket reduction (msm_reduce_body)
+    const uint32_t *buckets; uint32_t G, groups, log2B, count; uint32_t *terms;       // terms: S of every lane, then T of every lane
+};
+struct BaseMulArgs {         // the fixed-base chain (base_mul_body)
+    const uint32_t *k; uint32_t *out; const uint4 *table; uint32_t c, W;
+};
+}  // namespace
+
+namespace bn254 {
+// ---- a Jacobian point <-> its 24 (G1) / 48 (G2) words, for every Fq2 mapping
+template <class F> struct PointIo;
+template <> struct PointIo<FqField> {
+    static constexpr uint32_t WORDS = 24;
+    BN_FN Jac<FqField> operator()(const uint32_t *w) const { return Jac<FqField>{fe_from_u32x8(w), fe_from_u32x8(w + 8), fe_from_u32x8(w + 16)}; }
+    BN_FN void operator()(const Jac<FqField> &r, uint32_t *o) const { fe_to_u32x8(r.x, o); fe_to_u32x8(r.y, o + 8); fe_to_u32x8(r.z, o + 16); }
+};
+template <class F2> struct PointIo<Fq2Field<F2>> {
+    typedef Fq2Field<F2> F;
+    static constexpr uint32_t WORDS = 48;
+    BN_FN Jac<F> operator()(const uint32_t *w) const { return Jac<F>{f2_load((const F2 *)nullptr, w), f2_load((const F2 *)nullptr, w + 16), f2_load((const F2 *)nullptr, w + 32)}; }
+    BN_FN void operator()(const Jac<F> &r, uint32_t *o) const { f2_store(r.x, o); f2_store(r.y, o + 16); f2_store(r.z, o + 32); }
+};
+// the canonical integer of the scalar at k (8 words in Montgomery form)
+BN_FN void fr_load_raw(const uint32_t *k, uint32_t raw[8]) {
+    uint32_t kw[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) kw[i] = k[i];
+    fr_from_mont(kw, raw);
+}
+// ---- the 80-byte record of an affine table entry: the 9 + 9 limbs of (x, y) - Fe, or one lane's components of an Fq2B pair - and two words,
+// read and written as five 16-byte groups.  Word 18 is a flag (the fixed-base tables mark an entry at infinity), word 19 is zero.
+// 16-byte groups per entry: 5 = packed (80 B: an entry may straddle two 128-byte lines; one whole line per entry measured no faster, a
+// prefetch one window ahead 2 % slower: profiles/r04c_ab_g1mul.txt)
+constexpr uint32_t AFF_ENTRY_U4 = 5, AFF_LANE_U4 = 8 * AFF_ENTRY_U4;                 // 80 B per entry, 640 B per lane
+template <class Index>
+BN_FN void aff_record_pack(const Fe &x, const Fe &y, uint32_t flag, uint4 *table, Index entry) {          // record `entry` of `table`
+    uint32_t w[20];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { w[i] = x.l[i]; w[9 + i] = y.l[i]; }
+    w[18] = flag; w[19] = 0;
+    uint4 *rec = table + entry * AFF_ENTRY_U4;
+#pragma unroll
+    for (int g = 0; g < 5; ++g) rec[g] = make_uint4(w[4 * g], w[4 * g + 1], w[4 * g + 2], w[4 * g + 3]);
+}
+BN_FN uint32_t aff_record_unpack(const uint4 *rec, Fe &x, Fe &y) {                  // returns the flag
+    uint32_t w[20];
+#pragma unroll
+    for (int g = 0; g < 5; ++g) { const uint4 v = rec[g]; w[4 * g] = v.x; w[4 * g + 1] = v.y; w[4 * g + 2] = v.z; w[4 * g + 3] = v.w; }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { x.l[i] = w[i]; y.l[i] = w[9 + i]; }
+    BN_SETB(x, 1, 2); BN_SETB(y, 1, 2);                                              // what is packed is a product (fe_mul, fe_from_u32x8)
+    BN_VERIFY(x, "aff_record_unpack"); BN_VERIFY(y, "aff_record_unpack");
+    return w[18];
+}
+// The affine window table of a lane in global memory: [lane][entry 1..8][record] - a lane reads the entry of ITS digit as five 16-byte
+// loads from one or two cache lines (curve.hpp AffTableVars explains why not a private array).
+// G1: (x, y) are Fe; G2 in the lane-pair mapping: this lane's components of (x, y)
+template <class F>
+struct AffTableMem {
+    uint4 *base;             // this lane's 8 entries
+    BN_FN void put(int i, const Aff<F> &v) const {
+        if constexpr (std::is_same<F, FqField>::value) aff_record_pack(v.x, v.y, 0, base, (uint32_t)(i - 1));
+        else aff_record_pack(v.x.v, v.y.v, 0, base, (uint32_t)(i - 1));
+    }
+    BN_FN Aff<F> get(int i) const {
+        const uint4 *e = base + (uint32_t)(i - 1) * AFF_ENTRY_U4;
+        Aff<F> r;
+        if constexpr (std::is_same<F, FqField>::value) aff_record_unpack(e, r.x, r.y);
+        else aff_record_unpack(e, r.x.v, r.y.v);
+        return r;
+    }
+};
+// ---- a[i] + b[i]  (or a[i] - b[i] = a[i] + (-b[i]): lib.rs:103-114,146-157, groups/mod.rs:275-347): the reference's add-2007-bl
+// with its zero / equal-point branches, so the Jacobian limbs returned are the reference's own
+template <class F>
+BN_FN Jac<F> add_body(const Jac<F> &a, Jac<F> b, int negate_b) {
+    const bool bz = F::is_zero(b.z);
+    if (negate_b) b.y = F::select(bz, F::template lc3<-1, 0, 0>(b.y, b.y, b.y), b.y);     // neg(0) = 0 (groups/mod.rs:334-346)
+    return jac_add_flags<F>(a, b, F::is_zero(a.z), bz);
+}
+// One level of the segmented fold of bn254_g{1,2}_msm_batch: lane (G2: lane pair) i adds the pieces[i].cnt consecutive Jacobian points at
+// pieces[i].src in index order - a serial chain chosen by the host (at most BN_MSM_FOLD = 4 values) - into pieces[i].dst; an empty piece is
+// the point at infinity.  The COMPLETE addition: two equal terms of a segment double, P*k + P*(r-k) cancels, and a partial sum at infinity is
+// the left operand of the next addition.  pieces[i].last: the sum of a whole segment, normalised (infinity: G::zero() = (0, 1, 0)).
+// The caller stores the result at pc.dst (a clamped lane pair of G2 computes it and keeps it to itself).
+template <class F>
+BN_FN Jac<F> msm_fold_body(const BnSegPiece &pc) {
+    const PointIo<F> io;
+    Jac<F> acc = {F::zero(), F::one(), F::zero()};
+    if (pc.cnt) acc = io(pc.src);
+#pragma unroll 1
+    for (uint32_t j = 1; j < pc.cnt; ++j) {
+        const Jac<F> q = io(pc.src + PointIo<F>::WORDS * j);
+        acc = jac_add_flags<F>(acc, q, F::is_zero(acc.z), F::is_zero(q.z));
+    }
+    if (pc.last) acc = jac_normalize<F>(acc);
+    return acc;
+}
+// ---- bucket (Pippenger) method of bn254_g{1,2}_msm: one large sum (bn254_hip.hip bn_launch_msm_bucket plans the launches)
+// A scalar is cut into W = ceil(254 / c) unsigned c-bit digits; term i belongs to bucket KEY = w * 2^c + digit for every window w whose digit
+// is not zero.  The integer kernels (bn254_kernels_mul.hip MsmDigitsOp, MsmScanOp) count the terms per key, scan the counts and scatter
+// (term index, key) into key order - a counting sort, arbitrary order inside a key.
+constexpr uint32_t MSM_NONE = 0x7fffffffu;        // key of an unused entry
+constexpr uint32_t MSM_SKIP = 0x80000000u;        // key flag: the entry belongs to the run of its key but carries no point
+constexpr uint32_t MSM_PIECE = 16;                // entries per lane of one accumulation level: the longest serial chain, whatever the data
+constexpr uint32_t MSM_TILE = 1024;               // counts per workgroup of the scan (256 threads x 4)
+BN_FN uint32_t msm_digit(const uint32_t *raw, uint32_t w, uint32_t c) {
+    const uint32_t bit = w * c, word = bit >> 5;
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 8; ++i) { if (i == word) lo = raw[i]; if (i == word + 1) hi = raw[i]; }      // selects: `raw` stays in registers
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (bit & 31u)) & ((1u << c) - 1u);
+}
+// One level of the bucket accumulation.  The input is a sequence of N entries in key order (level 0: the sorted terms, their points gathered
+// by index; level l > 0: the partial sums level l - 1 wrote); lane (G2: lane pair) i adds the entries [i * MSM_PIECE, (i + 1) * MSM_PIECE) with
+// the complete addition, run by run.  A run of one key that lies inside the lane's entries is complete: buckets[key] += sum (the buckets
+// collect over the chunks of a call).  A run that began before the lane's first entry or goes on behind its last one is a piece of a longer
+// run: its sum becomes an entry of the next level - slot 2i for a run that began earlier, slot 2i + 1 for one that goes on (a run over ALL of
+// the lane's entries takes slot 2i and marks 2i + 1 MSM_SKIP, so that the key's run stays contiguous) - and the next level, eight times
+// shorter, does the same.  So no lane's chain exceeds 2 * MSM_PIECE additions (every entry a run of its own) whatever the scalars are: 2^20 equal scalars are 2^16 lanes of
+// 16 terms, then 2^13, ... - never one chain of 2^20.  N = the level-0 count on the device (*n0) taken through the levels.
+// A lane past the level's entries has nothing to do (both lanes of a pair alike).
+BN_FN uint32_t msm_level_len(uint32_t n, uint32_t level) {
+    for (uint32_t l = 0; l < level; ++l) n = 2u * ((n + MSM_PIECE - 1) / MSM_PIECE);
+    return n;
+}
+template <class F>
+BN_FN void msm_acc_body(const MsmAccArgs &g, uint32_t i) {
+    constexpr uint32_t WORDS = PointIo<F>::WORDS;
+    const PointIo<F> io;
+    const uint32_t N = msm_level_len(*g.n0, g.level), a = i * MSM_PIECE;
+    if (a >= N) return;
+    const uint32_t b = min(a + MSM_PIECE, N);
+    const uint32_t prev = a ? g.keys[a - 1] & ~MSM_SKIP : 0xffffffffu, next = b < N ? g.keys[b] & ~MSM_SKIP : 0xffffffffu;
+    g.out_keys[2 * i] = MSM_NONE; g.out_keys[2 * i + 1] = MSM_NONE;
+    Jac<F> acc = {F::zero(), F::one(), F::zero()};
+    uint32_t cur = g.keys[a] & ~MSM_SKIP, j = a;
+    bool first_run = true;
+#pragma unroll 1
+    for (;;) {
+        // one step = at most one addition: an entry joins the run, or a complete run joins its bucket
+        const bool at_end = j >= b;
+        const uint32_t kj = at_end ? 0u : g.keys[j], key = kj & ~MSM_SKIP;
+        const bool flush = at_end || key != cur;
+        const uint32_t *src = nullptr;
+        uint32_t *dst = nullptr;
+        if (flush) {
+            const bool began_earlier = first_run && prev == cur, goes_on = at_end && next == cur;
+            if (cur != MSM_NONE) {
+                if (!began_earlier && !goes_on) { dst = g.buckets + (size_t)cur * WORDS; src = dst; }
+                else {
+                    const uint32_t slot = began_earlier ? 2 * i : 2 * i + 1;
+                    dst = g.out_pts + (size_t)slot * WORDS;
+                    g.out_keys[slot] = cur;
+                    if (began_earlier && goes_on) g.out_keys[2 * i + 1] = cur | MSM_SKIP;
+                }
+            }
+        } else if (!(kj & MSM_SKIP) && key != MSM_NONE) {
+            src = g.pts + (size_t)(g.idx ? g.idx[j] : j) * WORDS;
+        }
+        if (src) {
+            const Jac<F> q = io(src);
+            acc = jac_add_flags<F>(acc, q, F::is_zero(acc.z), F::is_zero(q.z));
+        }
+        if (dst) io(acc, dst);
+        if (at_end) break;
+        if (flush) { first_run = false; acc = {F::zero(), F::one(), F::zero()}; cur = key; }
+        else ++j;
+    }
+}
+// The bucket reduction: lane (lane pair) t = w * groups + g walks the G buckets [base, base + G) of window w from the top with a running sum,
+// two additions per bucket, and leaves S = sum B_b and T = sum (b - base) B_b as two terms of the tail - the one-segment bn254_g{1,2}_msm_batch
+// over 2 * W * groups terms whose scalars the host knows: base * 2^(c w) for S, 2^(c w) for T.
+template <class F>
+BN_FN void msm_reduce_body(const MsmReduceArgs &g, uint32_t t) {
+    constexpr uint32_t WORDS = PointIo<F>::WORDS;
+    const PointIo<F> io;
+    const uint32_t w = t / g.groups, base = (w << g.log2B) + (t % g.groups) * g.G;
+    Jac<F> run = {F::zero(), F::one(), F::zero()}, T = run;
+#pragma unroll 1
+    for (uint32_t b = g.G; b-- > 0;) {
+        const Jac<F> q = io(g.buckets + (size_t)(base + b) * WORDS);
+        run = jac_add_flags<F>(run, q, F::is_zero(run.z), F::is_zero(q.z));
+        if (b) T = jac_add_flags<F>(T, run, F::is_zero(T.z), F::is_zero(run.z));
+    }
+    io(run, g.terms + (size_t)t * WORDS);
+    io(T, g.terms + (size_t)(g.count + t) * WORDS);
+}
+// ---- fixed-base scalar multiplication of bn254_g{1,2}_mul_base_batch: out[i] = normalize(B * k[i]) for ONE base B per call
+// (bn254_seg.hip bn_launch_mul_base keeps the tables and plans the launches).  The table of a base holds the AFFINE points d * 2^(c w) * B for
+// w < W = ceil(254 / c) and d = 1 .. 2^(c-1), entry (w, d) at index w * 2^(c-1) + d - 1, as the records above - G1 one record per entry,
+// G2 two (component c0 for the even lane of a pair, c1 for the odd one).  The flag of a record is not zero when the entry is the point at
+// infinity (the base was).
+// The chain: the canonical integer of the scalar is recoded, low window first, into W signed c-bit digits in [-2^(c-1), 2^(c-1)] with a
+// carry (the top window of a scalar below r < 2^254 <= 2^(c W - 1) never carries), and every non-zero digit is ONE mixed addition of the
+// entry |d| of its window, y negated for d < 0 - no doubling, and the accumulator starts at infinity.  The partial sum below window w is
+// smaller than 2^(c w) in absolute value, so it never equals +- the entry of window w as an INTEGER; mod r that argument holds up to the
+// top window only: k = r - 2 (r mod 2^(c (W-1))) recodes (when the low part carries, as it does for c = 8, 10 and 12) to a partial sum -t B and a top entry
+// (r - t) B, the same point.  The additions are therefore the complete ones (jac_madd_signed / jac_madd_flags: equal points double,
+// opposite points and an accumulator at infinity are followed by flags).
+template <class F>
+BN_FN Aff<F> base_entry(const uint4 *rec, bool &inf) {
+    Aff<F> r;
+    Fe x, y;
+    inf = aff_record_unpack(rec, x, y) != 0;
+    if constexpr (std::is_same<F, FqField>::value) { r.x = x; r.y = y; } else { r.x.v = x; r.y.v = y; }
+    return r;
+}
+// Where a lane finds entry e of the table (the counterpart of AffTableMem / AffTableVars for the window tables): the kernels read ONE record,
+// G1 the entry's only one, a G2 lane the one of its component comp = lane & 1 - both lanes of a pair walk the same digits.  (A simulated
+// lane pair holds both components in one value and fetches both records: tests/hostsim/hostsim.cpp.)  The caller hands in `io` like the table.
+template <class F>
+struct BaseTableMem {
+    static constexpr uint32_t REC = std::is_same<F, FqField>::value ? AFF_ENTRY_U4 : 2 * AFF_ENTRY_U4;            // 16-byte groups per table entry
+    const uint4 *table; uint32_t comp;
+    BN_FN Aff<F> get(uint32_t e, bool &inf) const { return base_entry<F>(table + (size_t)e * REC + comp * AFF_ENTRY_U4, inf); }
+};
+template <class F, class Tab>
+BN_FN void base_mul_body(const BaseMulArgs &g, uint32_t i, Tab tab, PointIo<F> io) {
+    constexpr bool G1 = std::is_same<F, FqField>::value;
+    uint32_t raw[8];
+    fr_load_raw(g.k + 8u * i, raw);
+    const uint32_t half = 1u << (g.c - 1);
+    Jac<F> acc = {F::zero(), F::one(), F::zero()};
+    bool acc_inf = true;
+    uint32_t carry = 0;
+#pragma unroll 1
+    for (uint32_t w = 0; w < g.W; ++w) {
+        const uint32_t v = msm_digit(raw, w, g.c) + carry;
+        carry = v > half ? 1u : 0u;
+        const uint32_t ad = carry ? (2u * half - v) : v;                      // |digit| <= 2^(c-1)
+        bool e_inf;
+        const Aff<F> q = tab.get(w * half + (ad ? ad - 1u : 0u), e_inf);
+        const bool q_inf = e_inf || ad == 0;                                  // digit 0: the operand is ignored
+        if constexpr (G1) {
+            acc = jac_madd_signed(acc, q, carry != 0, acc_inf, q_inf);
+        } else {
+            Aff<F> qs = q;
+            qs.y = F::select(carry != 0, q.y, F::template lc3<-1, 0, 0>(q.y, q.y, q.y));
+            acc = jac_madd_flags<F>(acc, qs, acc_inf, q_inf);
+            acc_inf = F::is_zero_std(acc.z);
+        }
+    }
+    io(jac_normalize<F>(acc), g.out + (size_t)i * io.WORDS);
+}
+}  // namespace bn254

@@ -83,7 +83,7 @@ constexpr int BN_BASE_SLOTS = 4;
 // 2.84 / 2.41 / 2.13 ms, G2 2^18 scalars 2.06 / 1.71 / 1.50 ms of kernel time)
 constexpr unsigned BN_BASE_WINDOW_G1 = 12, BN_BASE_WINDOW_G2 = 12;
 struct BnBaseSlot {
-    BnBuf table;                        // W * 2^(c-1) entries of 80 (G1) / 160 (G2) bytes (bn254_kernels_mul.hip BaseMulArgs)
+    BnBuf table;                        // W * 2^(c-1) entries of 80 (G1) / 160 (G2) bytes (group_ops.hpp base_mul_body)
     unsigned char key[sizeof(bn_g2)];   // the base as the caller passed it: 96 or 192 bytes
     unsigned c = 0;                     // window width the table was built for
     bool valid = false;

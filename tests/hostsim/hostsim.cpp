@@ -6,11 +6,11 @@
 #define BN_HOSTSIM 1
 #include "lanepair.hpp"
 #include "lanequad.hpp"
-#include "../../bn_amd/csrc/io.hpp"
-#include "../../bn_amd/csrc/curve.hpp"
+#include "../../bn_amd/csrc/group_ops.hpp"
 #include "../../bn_amd/csrc/io_wire.hpp"
 #include "../../bn_amd/csrc/quad.hpp"
 #include <cstring>
+#include <vector>
 
 using namespace bn254;
 #define EXPORT extern "C" __attribute__((visibility("default")))
@@ -158,17 +158,79 @@ EXPORT void hsb_pairing(const uint32_t *g1, const uint32_t *g2, uint32_t *o) {
 static F2B ld2b(const uint32_t *w) { return f2_load((F2B *)0, w); }
 static void st2b(const F2B &a, uint32_t *w) { f2_store(a, w); }
 EXPORT void hsb_g2_mul(const uint32_t *p, const uint32_t *k, int normalize, uint32_t *o) { hs_mul_generic<Fq2Field<F2B>, 16>(p, k, o, normalize, ld2b, st2b); }
-// G + G / G - G with the reference's branches (bn254_kernels_mul.hip add_body), G1 one lane and G2 on a lane pair
-template <class F, int W>
-static void hs_add_generic(const uint32_t *a, const uint32_t *b, int negate_b, uint32_t *o, typename F::T (*ld)(const uint32_t *), void (*st)(const typename F::T &, uint32_t *)) {
-    Jac<F> pa = {ld(a), ld(a + W), ld(a + 2 * W)}, pb = {ld(b), ld(b + W), ld(b + 2 * W)};
-    const bool bz = F::is_zero(pb.z);
-    if (negate_b) pb.y = F::select(bz, F::template lc3<-1, 0, 0>(pb.y, pb.y, pb.y), pb.y);
-    Jac<F> r = jac_add_flags<F>(pa, pb, F::is_zero(pa.z), bz);
-    st(r.x, o); st(r.y, o + W); st(r.z, o + 2 * W);
+// ---------------------------------------------------------------- the bodies of the group kernels (bn_amd/csrc/group_ops.hpp): one loop over
+// lanes (G1) or simulated lane pairs (G2) per kernel launch, over host arrays
+typedef FqField G1S;
+typedef Fq2Field<F2B> G2S;
+// G + G / G - G with the reference's branches
+template <class F>
+static void hs_add(const uint32_t *a, const uint32_t *b, int negate_b, uint32_t *o) { const PointIo<F> io; io(add_body<F>(io(a), io(b), negate_b), o); }
+EXPORT void hs_g1_add(const uint32_t *a, const uint32_t *b, int negate_b, uint32_t *o) { hs_add<G1S>(a, b, negate_b, o); }
+EXPORT void hsb_g2_add(const uint32_t *a, const uint32_t *b, int negate_b, uint32_t *o) { hs_add<G2S>(a, b, negate_b, o); }
+// one level of the segmented fold: piece i = (offset of its first point in `src`, in points; cnt; last), its result to point i of `out`
+template <class F>
+static void hs_fold(const uint32_t *src, const uint32_t *pieces, uint32_t n, uint32_t *out) {
+    const uint32_t W = PointIo<F>::WORDS;
+    for (uint32_t i = 0; i < n; ++i) {
+        const BnSegPiece pc = {src + (size_t)pieces[3 * i] * W, out + (size_t)i * W, pieces[3 * i + 1], pieces[3 * i + 2]};
+        PointIo<F>()(msm_fold_body<F>(pc), pc.dst);
+    }
 }
-EXPORT void hs_g1_add(const uint32_t *a, const uint32_t *b, int negate_b, uint32_t *o) { hs_add_generic<FqField, 8>(a, b, negate_b, o, ld1, st1); }
-EXPORT void hsb_g2_add(const uint32_t *a, const uint32_t *b, int negate_b, uint32_t *o) { hs_add_generic<Fq2Field<F2B>, 16>(a, b, negate_b, o, ld2b, st2b); }
+EXPORT void hs_msm_fold(int g, const uint32_t *src, const uint32_t *pieces, uint32_t n, uint32_t *out) { if (g == 1) hs_fold<G1S>(src, pieces, n, out); else hs_fold<G2S>(src, pieces, n, out); }
+EXPORT uint32_t hs_msm_piece() { return MSM_PIECE; }
+EXPORT uint32_t hs_msm_digit(const uint32_t *raw, uint32_t w, uint32_t c) { return msm_digit(raw, w, c); }
+// the accumulation of one chunk as bn_launch_msm_bucket runs it: n0 sorted entries (idx, keys) over `pts`, every level in sequence until one
+// lane covers the level; `buckets` collects.  levels_out: the number of levels run.
+template <class F>
+static void hs_acc(const uint32_t *pts, const uint32_t *idx, const uint32_t *keys, uint32_t n0, uint32_t *buckets, uint32_t *levels_out) {
+    const uint32_t W = PointIo<F>::WORDS;
+    std::vector<uint32_t> in_pts, in_keys(keys, keys + n0), out_pts, out_keys;
+    uint32_t level = 0;
+    for (;; ++level) {
+        const uint32_t N = msm_level_len(n0, level), lanes = (N + MSM_PIECE - 1) / MSM_PIECE;
+        out_pts.assign((size_t)2 * lanes * W, 0u); out_keys.assign((size_t)2 * lanes, 0xdeadbeefu);
+        in_keys.resize(N + 1, MSM_NONE);
+        const MsmAccArgs a = {level ? in_pts.data() : pts, level ? nullptr : idx, in_keys.data(), &n0, level, out_pts.data(), out_keys.data(), buckets};
+        for (uint32_t i = 0; i < lanes + 1; ++i) msm_acc_body<F>(a, i);                 // one lane more than needed: it must retire
+        if (lanes <= 1) break;
+        in_pts.swap(out_pts); in_keys.swap(out_keys);
+    }
+    *levels_out = level + 1;
+}
+EXPORT void hs_msm_acc(int g, const uint32_t *pts, const uint32_t *idx, const uint32_t *keys, uint32_t n0, uint32_t *buckets, uint32_t *levels_out) {
+    if (g == 1) hs_acc<G1S>(pts, idx, keys, n0, buckets, levels_out); else hs_acc<G2S>(pts, idx, keys, n0, buckets, levels_out);
+}
+// the bucket reduction over `count` = W * groups lanes; terms: S of every lane, then T of every lane
+EXPORT void hs_msm_reduce(int g, const uint32_t *buckets, uint32_t G, uint32_t groups, uint32_t log2B, uint32_t count, uint32_t *terms) {
+    const MsmReduceArgs a = {buckets, G, groups, log2B, count, terms};
+    for (uint32_t t = 0; t < count; ++t) { if (g == 1) msm_reduce_body<G1S>(a, t); else msm_reduce_body<G2S>(a, t); }
+}
+// the 80-byte record: pack (9 + 9 limbs, flag) and unpack again; out: 18 limbs, then the flag
+EXPORT void hs_aff_record_roundtrip(const uint32_t *limbs, uint32_t flag, uint32_t *rec, uint32_t *out) {
+    Fe x, y;
+    for (int i = 0; i < 9; ++i) { x.l[i] = limbs[i]; y.l[i] = limbs[9 + i]; }
+    aff_record_pack(x, y, flag, (uint4 *)rec, 0u);
+    Fe u, v;
+    out[18] = aff_record_unpack((const uint4 *)rec, u, v);
+    for (int i = 0; i < 9; ++i) { out[i] = u.l[i]; out[9 + i] = v.l[i]; }
+}
+// record `r` of a fixed-base table from an affine coordinate pair in the reference image (G2: one component of each), flagged when at infinity
+EXPORT void hs_base_record(const uint32_t *x, const uint32_t *y, uint32_t flag, uint32_t *table, uint32_t r) {
+    aff_record_pack(fe_from_u32x8(x), fe_from_u32x8(y), flag, (uint4 *)table, (size_t)r);
+}
+// a simulated lane pair holds both components of an entry: it fetches both records (the kernel's lanes one each, BaseTableMem)
+struct BaseTablePair {
+    const uint4 *table;
+    Aff<G2S> get(uint32_t e, bool &inf) const {
+        bool inf1;
+        const Aff<FqField> c0 = base_entry<FqField>(table + (size_t)e * 2 * AFF_ENTRY_U4, inf), c1 = base_entry<FqField>(table + ((size_t)e * 2 + 1) * AFF_ENTRY_U4, inf1);
+        return {{{{c0.x, c1.x}}}, {{{c0.y, c1.y}}}};
+    }
+};
+EXPORT void hs_mul_base(int g, const uint32_t *table, uint32_t c, const uint32_t *k, uint32_t n, uint32_t *out) {
+    const BaseMulArgs a = {k, out, (const uint4 *)table, c, (254 + c - 1) / c};
+    for (uint32_t i = 0; i < n; ++i) { if (g == 1) base_mul_body<G1S>(a, i, BaseTableMem<G1S>{a.table, 0u}, PointIo<G1S>()); else base_mul_body<G2S>(a, i, BaseTablePair{a.table}, PointIo<G2S>()); }
+}
 // ---------------------------------------------------------------- four lanes per pairing (quad.hpp) on a simulated quad
 typedef Fq2B<FeQ> F2Q;
 EXPORT void hsq_fq12_sqr(const uint32_t *a, uint32_t *o) { q12_store(q12_sqr(q12_load<F2Q>(a)), o); }

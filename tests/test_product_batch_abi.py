@@ -4,9 +4,7 @@ kernel names: bn254_gt_mul_B<true> is the segmented fold, bn254_gt_tail_W<true> 
 import ctypes as C
 import pathlib
 import re
-import subprocess
 import sys
-import tempfile
 
 import pytest
 
@@ -114,21 +112,7 @@ def test_no_segments_is_ok_and_writes_nothing(lib):
 def _instances(so):
     """{full mangled name: vgpr_spill_count} of every kernel in the library's gfx950 code objects"""
     import kernel_meta
-    d = so.read_bytes()
-    offs = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", d)]
-    out = {}
-    with tempfile.TemporaryDirectory() as t:
-        for i, o in enumerate(offs):
-            e = offs[i + 1] if i + 1 < len(offs) else len(d)
-            b = pathlib.Path(t) / f"b{i}.bin"; b.write_bytes(d[o:e])
-            co = pathlib.Path(t) / f"k{i}.co"
-            subprocess.check_call([str(kernel_meta.LLVM / "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                                   f"--input={b}", f"--output={co}", "--unbundle"])
-            txt = subprocess.check_output([str(kernel_meta.LLVM / "llvm-readelf"), "--notes", str(co)], text=True)
-            for blk in txt.split("- .agpr_count")[1:]:
-                name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-                out[name] = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1))
-    return out
+    return {name: m["spill"] for name, m in kernel_meta.instances(so).items()}
 
 
 def test_spill_ceiling_of_every_instance_of_the_fold_kernels():

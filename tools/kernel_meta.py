@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel resource usage (VGPRs, spills, private segment, LDS) of the gfx950 code objects inside a built library.
-usage: tools/kernel_meta.py [path/to/lib.so]      (tests/test_build_quality.py imports kernel_meta())"""
+usage: tools/kernel_meta.py [path/to/lib.so]      (tests/test_build_quality.py imports kernel_meta(), the test_*_abi.py files instances())"""
 import pathlib, re, subprocess, sys, tempfile
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 LLVM = pathlib.Path("/opt/rocm/lib/llvm/bin")
@@ -18,8 +18,8 @@ def short_name(mangled):
     return mangled
 
 
-def kernel_meta(so=None):
-    """{kernel name: {"vgpr", "spill", "private", "lds", "sgpr"}} of every kernel in the library"""
+def instances(so=None):
+    """{mangled kernel name: {"vgpr", "spill", "private", "lds", "sgpr"}} of every kernel instance in the library"""
     so = pathlib.Path(so) if so else ROOT / "bn_amd" / "libbn254_hip.so"
     d = so.read_bytes()
     offs = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", d)]
@@ -33,8 +33,19 @@ def kernel_meta(so=None):
             txt = subprocess.check_output([str(LLVM / "llvm-readelf"), "--notes", str(co)], text=True)
             for blk in txt.split("- .agpr_count")[1:]:
                 g = lambda k: (re.search(r"\." + k + r":\s+(\S+)", blk) or [None, "?"])[1]
-                out[short_name(g("name"))] = {"vgpr": int(g("vgpr_count")), "spill": int(g("vgpr_spill_count")), "private": int(g("private_segment_fixed_size")),
-                                              "lds": int(g("group_segment_fixed_size")), "sgpr": int(g("sgpr_count"))}
+                out[g("name")] = {"vgpr": int(g("vgpr_count")), "spill": int(g("vgpr_spill_count")), "private": int(g("private_segment_fixed_size")),
+                                  "lds": int(g("group_segment_fixed_size")), "sgpr": int(g("sgpr_count"))}
+    return out
+
+
+def kernel_meta(so=None):
+    """{kernel name: {"vgpr", "spill", "private", "lds", "sgpr"}}: the instances of a name (templates beside the plain kernel) folded into
+    one entry that holds the maximum of every figure, so that a ceiling on a name holds for each of its instances"""
+    out = {}
+    for name, m in instances(so).items():
+        cur = out.setdefault(short_name(name), dict(m))
+        for k, v in m.items():
+            cur[k] = max(cur[k], v)
     return out
 
 
