@@ -78,6 +78,14 @@ extern "C" {
     fn bn254_g2_mul_base_batch(ctx: *mut c_void, base: *const G2, k: *const Fr, out: *mut G2, n: usize) -> c_int;
     fn bn254_g1_mul_base_batch_dev(ctx: *mut c_void, base: *const G1, d_k: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_g2_mul_base_batch_dev(ctx: *mut c_void, base: *const G2, d_k: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_g1_normalize_batch(ctx: *mut c_void, p: *const G1, out: *mut G1, n: usize) -> c_int;
+    fn bn254_g2_normalize_batch(ctx: *mut c_void, p: *const G2, out: *mut G2, n: usize) -> c_int;
+    fn bn254_g1_eq_batch(ctx: *mut c_void, a: *const G1, b: *const G1, out: *mut i32, n: usize) -> c_int;
+    fn bn254_g2_eq_batch(ctx: *mut c_void, a: *const G2, b: *const G2, out: *mut i32, n: usize) -> c_int;
+    fn bn254_g1_normalize_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_g2_normalize_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_g1_eq_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_g2_eq_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
 }
 
 /// One line-function coefficient of a prepared G2 point: the crate's `EllCoeffs { ell_0, ell_vw, ell_vv: Fq2 }` (src/groups/mod.rs:472-476) as the
@@ -225,6 +233,36 @@ pub fn g2_mul_base(base: &G2, k: &[Fr]) -> Result<Vec<G2>, GpuError> {
     let mut out = vec![G2::zero(); k.len()];
     check(unsafe { bn254_g2_mul_base_batch(std::ptr::null_mut(), base, k.as_ptr(), out.as_mut_ptr(), k.len()) })?;
     Ok(out)
+}
+
+/// `out[i] = p[i].normalize()` (src/lib.rs:88-95): `(x/z^2, y/z^3, 1)`, the point at infinity as `G1::zero()`; neighbouring points share
+/// one field inversion.  The same bytes as `g1_mul_batch` by `Fr::one()`
+pub fn g1_normalize(p: &[G1]) -> Result<Vec<G1>, GpuError> {
+    let mut out = vec![G1::zero(); p.len()];
+    check(unsafe { bn254_g1_normalize_batch(std::ptr::null_mut(), p.as_ptr(), out.as_mut_ptr(), p.len()) })?;
+    Ok(out)
+}
+
+pub fn g2_normalize(p: &[G2]) -> Result<Vec<G2>, GpuError> {
+    let mut out = vec![G2::zero(); p.len()];
+    check(unsafe { bn254_g2_normalize_batch(std::ptr::null_mut(), p.as_ptr(), out.as_mut_ptr(), p.len()) })?;
+    Ok(out)
+}
+
+/// `out[i] = (a[i] == b[i])` as group elements (`PartialEq for G<P>`, src/groups/mod.rs:83-109), whatever their Jacobian representations;
+/// nothing is normalized
+pub fn g1_eq(a: &[G1], b: &[G1]) -> Result<Vec<bool>, GpuError> {
+    assert_eq!(a.len(), b.len());
+    let mut out = vec![0i32; a.len()];
+    check(unsafe { bn254_g1_eq_batch(std::ptr::null_mut(), a.as_ptr(), b.as_ptr(), out.as_mut_ptr(), a.len()) })?;
+    Ok(out.into_iter().map(|r| r != 0).collect())
+}
+
+pub fn g2_eq(a: &[G2], b: &[G2]) -> Result<Vec<bool>, GpuError> {
+    assert_eq!(a.len(), b.len());
+    let mut out = vec![0i32; a.len()];
+    check(unsafe { bn254_g2_eq_batch(std::ptr::null_mut(), a.as_ptr(), b.as_ptr(), out.as_mut_ptr(), a.len()) })?;
+    Ok(out.into_iter().map(|r| r != 0).collect())
 }
 
 /// `out[i] = a[i] * b[i]` (src/lib.rs:175-179)

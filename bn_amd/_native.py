@@ -51,6 +51,14 @@ SIGNATURES = {   # name -> argtypes  (every function returns int unless noted)
     "bn254_g2_mul_base_batch": [_VP, _VP, _VP, _VP, _SZ],
     "bn254_g1_mul_base_batch_dev": [_VP, _VP, _VP, _VP, _SZ, _VP],
     "bn254_g2_mul_base_batch_dev": [_VP, _VP, _VP, _VP, _SZ, _VP],
+    "bn254_g1_normalize_batch": [_VP, _VP, _VP, _SZ],
+    "bn254_g2_normalize_batch": [_VP, _VP, _VP, _SZ],
+    "bn254_g1_eq_batch": [_VP, _VP, _VP, _VP, _SZ],
+    "bn254_g2_eq_batch": [_VP, _VP, _VP, _VP, _SZ],
+    "bn254_g1_normalize_batch_dev": [_VP, _VP, _VP, _SZ, _VP],
+    "bn254_g2_normalize_batch_dev": [_VP, _VP, _VP, _SZ, _VP],
+    "bn254_g1_eq_batch_dev": [_VP, _VP, _VP, _VP, _SZ, _VP],
+    "bn254_g2_eq_batch_dev": [_VP, _VP, _VP, _VP, _SZ, _VP],
     "bn254_g1_add_batch": [_VP, _VP, _VP, _VP, _SZ, C.c_int],
     "bn254_g2_add_batch": [_VP, _VP, _VP, _VP, _SZ, C.c_int],
     "bn254_fr_encode_batch": [_VP, _VP, _VP, _SZ],

@@ -81,11 +81,11 @@ class _Point:
     def is_zero(self):                    # groups/mod.rs:224-226: z == 0
         return not self.limbs[2 * self.WORDS // 3:].any()
 
-    def __eq__(self, o):                  # projective equality (groups/mod.rs:83-109) via the normalized images
-        return type(o) is type(self) and np.array_equal(self.normalize().limbs, o.normalize().limbs)
+    def __eq__(self, o):                  # projective equality (groups/mod.rs:83-109): one comparison on the GPU, nothing normalized
+        return type(o) is type(self) and bool(self._eq(default_engine())(self.limbs, o.limbs)[0])
 
-    def normalize(self):                  # lib.rs:88-95 / 131-138: multiply by one on the GPU and normalize there
-        return self * Fr.one()
+    def normalize(self):                  # lib.rs:88-95 / 131-138: (x/z^2, y/z^3, 1) on the GPU
+        return type(self)(self._normalize(default_engine())(self.limbs)[0])
 
 
 class G1(_Point):
@@ -99,6 +99,8 @@ class G1(_Point):
         return G1(np.concatenate([np.zeros(4, np.uint64), _one_fq(), np.zeros(4, np.uint64)]))
     @staticmethod
     def random(rng): return G1.one() * Fr.random(rng)        # groups/mod.rs:220-222
+    _eq = staticmethod(lambda e: e.g1_eq)
+    _normalize = staticmethod(lambda e: e.g1_normalize)
     def __mul__(self, k):                 # lib.rs:116-120 (result returned normalized)
         return G1(default_engine().g1_mul_batch(self.limbs, k.limbs)[0])
     def __add__(self, o):                 # lib.rs:103-106 (the reference's Jacobian limbs)
@@ -133,6 +135,8 @@ class G2(_Point):
         return G2(np.concatenate([z, _one_fq(), np.zeros(4, np.uint64), z]))
     @staticmethod
     def random(rng): return G2.one() * Fr.random(rng)
+    _eq = staticmethod(lambda e: e.g2_eq)
+    _normalize = staticmethod(lambda e: e.g2_normalize)
     def __mul__(self, k):
         return G2(default_engine().g2_mul_batch(self.limbs, k.limbs)[0])
     def __add__(self, o):                 # lib.rs:146-149
@@ -292,6 +296,34 @@ def g2_mul_base(base, scalars, engine=None):
     """the same over G2: base a G2 (or 24 uint64 words)"""
     b = base.limbs if isinstance(base, G2) else base
     return [G2(r) for r in (engine or default_engine()).g2_mul_base_batch(b, _scalar_array(scalars))]
+
+
+def _point_array(cls, points):
+    if isinstance(points, np.ndarray):
+        return np.asarray(points, np.uint64).reshape(-1, cls.WORDS)
+    points = list(points)
+    return np.stack([p.limbs for p in points]) if points else np.zeros((0, cls.WORDS), np.uint64)
+
+
+def g1_normalize_batch(points, engine=None):
+    """[p.normalize() for p in points] in one call: (x/z^2, y/z^3, 1), infinity as G1.zero(); neighbouring points share one field
+    inversion.  points: a sequence of G1 or an (n,12) uint64 array."""
+    return [G1(r) for r in (engine or default_engine()).g1_normalize(_point_array(G1, points))]
+
+
+def g2_normalize_batch(points, engine=None):
+    """the same over G2: a sequence of G2 or an (n,24) uint64 array"""
+    return [G2(r) for r in (engine or default_engine()).g2_normalize(_point_array(G2, points))]
+
+
+def g1_eq_batch(a, b, engine=None):
+    """[x == y for x, y in zip(a, b)] in one call, as group elements (any Jacobian representations; nothing is normalized) -> list of bool"""
+    return [bool(r) for r in (engine or default_engine()).g1_eq(_point_array(G1, a), _point_array(G1, b))]
+
+
+def g2_eq_batch(a, b, engine=None):
+    """the same over G2"""
+    return [bool(r) for r in (engine or default_engine()).g2_eq(_point_array(G2, a), _point_array(G2, b))]
 
 
 class PreparedG2:

@@ -265,6 +265,16 @@ template <class F> __device__ __forceinline__ void msm_point_op(const MsmReduceA
 template <class F> __device__ __forceinline__ void msm_point_op(const BaseMulArgs &g, uint32_t i) {
     base_mul_body<F>(g, i, BaseTableMem<F>{g.table, std::is_same<F, G1F>::value ? 0u : threadIdx.x & 1u}, PointIo<F>());
 }
+// the normalisation: lane (lane pair) i owns the run of NORM_RUN points from i * NORM_RUN on; both lanes of a pair walk the same run
+template <class F> __device__ __forceinline__ void msm_point_op(const NormalizeArgs &g, uint32_t i) {
+    normalize_body<F>(g, i, NORM_RUN, PrefixMem<F>{g.prefix, std::is_same<F, G1F>::value ? 0u : threadIdx.x & 1u}, PointIo<F>());
+}
+// the comparison: one int32 per pair of points, stored by the lane (G2: the even lane of the pair)
+template <class F> __device__ __forceinline__ void msm_point_op(const EqArgs &g, uint32_t i) {
+    const PointIo<F> io;
+    const int32_t r = eq_body<F>(io(g.a + (size_t)i * io.WORDS), io(g.b + (size_t)i * io.WORDS));
+    if (std::is_same<F, G1F>::value || !(threadIdx.x & 1u)) g.out[i] = r;
+}
 template <class Args>
 __global__ void __launch_bounds__(BLOCK) bn254_g1_add_M(Args g, uint32_t n) {
     const uint32_t idx = blockIdx.x * BLOCK + threadIdx.x;
@@ -343,6 +353,20 @@ int bn254_launch_mul_base_tile_M(int g, const void *d_base, void *d_out, size_t 
     const BaseTileOp op = {(const uint32_t *)d_base, (uint32_t *)d_out, words, (uint32_t)n};
     hipLaunchKernelGGL(bn254_fr_decode_k<BaseTileOp>, dim3((unsigned)((n * words + 255) / 256)), dim3(256), 0, s, op);
     return (int)hipGetLastError();
+}
+// bn254_g{1,2}_normalize_batch: n points in runs of bn254_normalize_run_M() per lane (lane pair); `prefix`: bn254_normalize_prefix_bytes_M(g, n)
+// bytes of scratch; d_out may be d_p
+unsigned bn254_normalize_run_M(void) { return NORM_RUN; }
+size_t bn254_normalize_prefix_bytes_M(int g, size_t n) { return n * PrefixMem<G1F>::REC * (g == 1 ? 1 : 2) * sizeof(uint4); }
+int bn254_launch_normalize_M(int g, const void *d_p, void *d_out, size_t n, void *prefix, hipStream_t s) {
+    const NormalizeArgs a = {(const uint32_t *)d_p, (uint32_t *)d_out, (uint4 *)prefix, (uint32_t)n};
+    const size_t lanes = (n + NORM_RUN - 1) / NORM_RUN;
+    return launch_group(g, lanes, s, bn254_g1_add_M<NormalizeArgs>, bn254_g2_add_M<NormalizeArgs>, a, (uint32_t)lanes);
+}
+// bn254_g{1,2}_eq_batch: out[i] = 1 when a[i] and b[i] are the same group element, else 0 (n int32)
+int bn254_launch_eq_M(int g, const void *d_a, const void *d_b, void *d_out, size_t n, hipStream_t s) {
+    const EqArgs a = {(const uint32_t *)d_a, (const uint32_t *)d_b, (int32_t *)d_out};
+    return launch_group(g, n, s, bn254_g1_add_M<EqArgs>, bn254_g2_add_M<EqArgs>, a, (uint32_t)n);
 }
 int bn254_launch_mul_base_repack_M(int g, const void *d_pts, void *table, size_t n, hipStream_t s) {
     const uint32_t comps = g == 1 ? 1u : 2u;

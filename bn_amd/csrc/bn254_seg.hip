@@ -1,6 +1,6 @@
 // Segmented operations of the BN254 engine (include/bn254_hip.h): the batched multi-pairings bn254_pairing_product_batch*, the segmented
 // multi-scalar multiplications bn254_g{1,2}_msm_batch* and the one large sum bn254_g{1,2}_msm* with its bucket route; the fixed-base scalar multiplication bn254_g{1,2}_mul_base_batch* with its
-// table cache.  Host code only: the
+// table cache; the batched normalisation bn254_g{1,2}_normalize_batch* and comparison bn254_g{1,2}_eq_batch*.  Host code only: the
 // plans are host_plan.hpp's, the kernels live in bn254_kernels_{b,w,mul}.hip.  Compiled like every unit (bn254_hip.hip: the flags).
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -317,6 +317,29 @@ int bn_launch_mul_base(bn254_ctx *c, int g, const void *base, const void *d_k, v
         return bn254_launch_mul_base_M(g, sl->table.p, sl->c, (const char *)d_k + lo * sizeof(bn_fr), (char *)d_out + lo * V, cnt, s);
     });
 }
+
+// ---- batched normalisation and projective equality (bn254_g{1,2}_normalize_batch*, bn254_g{1,2}_eq_batch*)
+// normalize: sub-launches of at most BN_LAUNCH_MAX points (a multiple of every run length), every lane (G2: lane pair) a run of
+// bn254_normalize_run_M() consecutive points with one inversion (group_ops.hpp normalize_body); the last run of a sub-launch is the short
+// one.  The prefix products of a sub-launch - one field element per point - are context-owned scratch, reused by the next sub-launch on the
+// same stream.  eq: one lane (lane pair) per pair of points, no scratch.
+std::atomic<size_t> g_norm_launch_max;        // tests only (bn254_normalize_set_launch_max): 0 = BN_LAUNCH_MAX
+// scratch guard held by the caller
+int bn_launch_normalize(bn254_ctx *c, int g, const void *d_p, void *d_out, size_t n, hipStream_t s) {
+    const size_t V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2), set = g_norm_launch_max.load(std::memory_order_relaxed), step = set ? set : BN_LAUNCH_MAX;
+    int rc = c->norm_prefix.reserve(bn254_normalize_prefix_bytes_M(g, std::min(n, step))); if (rc) return rc;
+    return bn_for_parts(n, step, [&](size_t lo, size_t cnt) -> int {
+        BnScope sc(c, s, g == 1 ? "g1_normalize" : "g2_normalize");
+        return bn254_launch_normalize_M(g, (const char *)d_p + lo * V, (char *)d_out + lo * V, cnt, c->norm_prefix.p, s);
+    });
+}
+int bn_launch_eq(bn254_ctx *c, int g, const void *d_a, const void *d_b, void *d_out, size_t n, hipStream_t s) {
+    const size_t V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2);
+    return bn_for_parts(n, BN_LAUNCH_MAX, [&](size_t lo, size_t cnt) -> int {
+        BnScope sc(c, s, g == 1 ? "g1_eq" : "g2_eq");
+        return bn254_launch_eq_M(g, (const char *)d_a + lo * V, (const char *)d_b + lo * V, (char *)d_out + lo * sizeof(int32_t), cnt, s);
+    });
+}
 }  // namespace
 
 // argument checks of bn254_pairing_product_batch_prepared_native* for m > 0 that need no device: the CSR rules, the handle, and - where the
@@ -382,6 +405,32 @@ static int mul_base_dev(bn254_ctx *ctx, int g, const void *base, const void *d_k
 }
 int bn254_g1_mul_base_batch_dev(bn254_ctx *c, const bn_g1 *base, const void *k, void *o, size_t n, void *s) { return mul_base_dev(c, 1, base, k, o, n, s); }
 int bn254_g2_mul_base_batch_dev(bn254_ctx *c, const bn_g2 *base, const void *k, void *o, size_t n, void *s) { return mul_base_dev(c, 2, base, k, o, n, s); }
+// order of the checks: empty batch, arguments, then context and device
+static int normalize_dev(bn254_ctx *ctx, int g, const void *d_p, void *d_out, size_t n, void *stream) {
+    if (n == 0) return BN254_OK;
+    if (n > BN_N_MAX || !d_p || !d_out) return BN254_E_BAD_ARG;                    // before any device lookup
+    return bn_seg_entry(ctx, stream, [&](hipStream_t s) { return bn_launch_normalize(ctx, g, d_p, d_out, n, s); });
+}
+int bn254_g1_normalize_batch_dev(bn254_ctx *c, const void *p, void *o, size_t n, void *s) { return normalize_dev(c, 1, p, o, n, s); }
+int bn254_g2_normalize_batch_dev(bn254_ctx *c, const void *p, void *o, size_t n, void *s) { return normalize_dev(c, 2, p, o, n, s); }
+// no context-owned scratch: no scratch guard
+static int eq_dev(bn254_ctx *ctx, int g, const void *d_a, const void *d_b, void *d_out, size_t n, void *stream) {
+    if (n == 0) return BN254_OK;
+    if (n > BN_N_MAX || !d_a || !d_b || !d_out) return BN254_E_BAD_ARG;            // before any device lookup
+    int rc = bn_get_ctx(ctx); if (rc) return rc;
+    BnDev d(ctx, stream); if (!d.go) return d.rc;
+    return bn_no_throw([&] { return bn_launch_eq(ctx, g, d_a, d_b, d_out, n, d.s); });
+}
+int bn254_g1_eq_batch_dev(bn254_ctx *c, const void *a, const void *b, void *o, size_t n, void *s) { return eq_dev(c, 1, a, b, o, n, s); }
+int bn254_g2_eq_batch_dev(bn254_ctx *c, const void *a, const void *b, void *o, size_t n, void *s) { return eq_dev(c, 2, a, b, o, n, s); }
+// internal (not in the header; tests and tools/time_normalize.py): the shipped run length of the normalisation, and an override of its
+// sub-launch size (0 restores BN_LAUNCH_MAX), so that a test reaches the seam between two sub-launches with a handful of points
+unsigned bn254_normalize_run(void) { return bn254_normalize_run_M(); }
+int bn254_normalize_set_launch_max(size_t points) {
+    if (points > BN_LAUNCH_MAX) return BN254_E_BAD_ARG;
+    g_norm_launch_max.store(points, std::memory_order_relaxed);
+    return BN254_OK;
+}
 // internal (not in the header; tests and tools/time_mul_base.py): the shipped window width of a group, the device bytes of one table, the
 // slots per group, the scalars a table is built with (returns their count; writes 4 words each when `cap_words` suffices), and - for the
 // width sweep only - a process-wide override of the width (0 restores the shipped one; tables of another width are rebuilt on use)
@@ -461,5 +510,25 @@ static int mul_base_host(bn254_ctx *ctx, int g, const void *base, const bn_fr *k
 }
 int bn254_g1_mul_base_batch(bn254_ctx *ctx, const bn_g1 *base, const bn_fr *k, bn_g1 *out, size_t n) { return mul_base_host(ctx, 1, base, k, out, n); }
 int bn254_g2_mul_base_batch(bn254_ctx *ctx, const bn_g2 *base, const bn_fr *k, bn_g2 *out, size_t n) { return mul_base_host(ctx, 2, base, k, out, n); }
+static int normalize_host(bn254_ctx *ctx, int g, const void *p, void *out, size_t n) {
+    if (n == 0) return BN254_OK;
+    if (n > BN_N_MAX || !p || !out) return BN254_E_BAD_ARG;                        // before any device lookup
+    const size_t V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2);
+    BnHost h(ctx); if (h.rc) return h.rc;
+    return bn_staged(ctx, {p, n * V}, {nullptr, 0}, out, n * V, nullptr, 0,
+                     [&](const BnStaged &d) { return normalize_dev(ctx, g, d.in[0], d.out, n, ctx->stream); });
+}
+int bn254_g1_normalize_batch(bn254_ctx *ctx, const bn_g1 *p, bn_g1 *out, size_t n) { return normalize_host(ctx, 1, p, out, n); }
+int bn254_g2_normalize_batch(bn254_ctx *ctx, const bn_g2 *p, bn_g2 *out, size_t n) { return normalize_host(ctx, 2, p, out, n); }
+static int eq_host(bn254_ctx *ctx, int g, const void *a, const void *b, int32_t *out, size_t n) {
+    if (n == 0) return BN254_OK;
+    if (n > BN_N_MAX || !a || !b || !out) return BN254_E_BAD_ARG;                  // before any device lookup
+    const size_t V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2);
+    BnHost h(ctx); if (h.rc) return h.rc;
+    return bn_staged(ctx, {a, n * V}, {b, n * V}, out, n * sizeof(int32_t), nullptr, 0,
+                     [&](const BnStaged &d) { return eq_dev(ctx, g, d.in[0], d.in[1], d.out, n, ctx->stream); });
+}
+int bn254_g1_eq_batch(bn254_ctx *ctx, const bn_g1 *a, const bn_g1 *b, int32_t *out, size_t n) { return eq_host(ctx, 1, a, b, out, n); }
+int bn254_g2_eq_batch(bn254_ctx *ctx, const bn_g2 *a, const bn_g2 *b, int32_t *out, size_t n) { return eq_host(ctx, 2, a, b, out, n); }
 
 }  // extern "C"

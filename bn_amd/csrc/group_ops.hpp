@@ -1,6 +1,7 @@
 // The per-lane bodies of the group kernels (bn254_kernels_mul.hip): point I/O, the 80-byte table record, the complete addition, the segmented
-// fold of bn254_g{1,2}_msm_batch, the accumulation levels and the reduction of the bucket method (bn254_g{1,2}_msm) and the fixed-base chain
-// (bn254_g{1,2}_mul_base_batch).  Everything here is pure and takes plain pointers and a lane (G2: lane pair) index, so the host simulation
+// fold of bn254_g{1,2}_msm_batch, the accumulation levels and the reduction of the bucket method (bn254_g{1,2}_msm), the fixed-base chain
+// (bn254_g{1,2}_mul_base_batch), the shared-inversion normalisation (bn254_g{1,2}_normalize_batch) and the projective comparison
+// (bn254_g{1,2}_eq_batch).  Everything here is pure and takes plain pointers and a lane (G2: lane pair) index, so the host simulation
 // (tests/hostsim/hostsim.cpp) runs the very same bodies over host arrays; what needs a wave, a workgroup or a launch stays in the .hip.
 #pragma once
 #include "curve.hpp"
@@ -25,6 +26,12 @@ struct MsmReduceArgs {       // the bucket reduction (msm_reduce_body)
 struct BaseMulArgs {         // the fixed-base chain (base_mul_body)
     const uint32_t *k; uint32_t *out; const uint4 *table; uint32_t c, W;
 };
+struct NormalizeArgs {       // the normalisation with one inversion per run of points (normalize_body); out may be p itself
+    const uint32_t *p; uint32_t *out; uint4 *prefix; uint32_t n;
+};
+struct EqArgs {              // the projective comparison (eq_body)
+    const uint32_t *a, *b; int32_t *out;
+};
 }  // namespace
 
 namespace bn254 {
@@ -34,12 +41,14 @@ template <> struct PointIo<FqField> {
     static constexpr uint32_t WORDS = 24;
     BN_FN Jac<FqField> operator()(const uint32_t *w) const { return Jac<FqField>{fe_from_u32x8(w), fe_from_u32x8(w + 8), fe_from_u32x8(w + 16)}; }
     BN_FN void operator()(const Jac<FqField> &r, uint32_t *o) const { fe_to_u32x8(r.x, o); fe_to_u32x8(r.y, o + 8); fe_to_u32x8(r.z, o + 16); }
+    BN_FN Fe z(const uint32_t *w) const { return fe_from_u32x8(w + 16); }           // the z coordinate alone
 };
 template <class F2> struct PointIo<Fq2Field<F2>> {
     typedef Fq2Field<F2> F;
     static constexpr uint32_t WORDS = 48;
     BN_FN Jac<F> operator()(const uint32_t *w) const { return Jac<F>{f2_load((const F2 *)nullptr, w), f2_load((const F2 *)nullptr, w + 16), f2_load((const F2 *)nullptr, w + 32)}; }
     BN_FN void operator()(const Jac<F> &r, uint32_t *o) const { f2_store(r.x, o); f2_store(r.y, o + 16); f2_store(r.z, o + 32); }
+    BN_FN F2 z(const uint32_t *w) const { return f2_load((const F2 *)nullptr, w + 32); }
 };
 // the canonical integer of the scalar at k (8 words in Montgomery form)
 BN_FN void fr_load_raw(const uint32_t *k, uint32_t raw[8]) {
@@ -263,5 +272,94 @@ BN_FN void base_mul_body(const BaseMulArgs &g, uint32_t i, Tab tab, PointIo<F> i
         }
     }
     io(jac_normalize<F>(acc), g.out + (size_t)i * io.WORDS);
+}
+// ---- normalisation of bn254_g{1,2}_normalize_batch: out[i] = (x / z^2, y / z^3, 1), the point at infinity (z == 0, whatever x and y hold)
+// as G::zero() = (0, 1, 0) - jac_normalize (curve.hpp) with ONE inversion per run of points (Montgomery's trick) instead of one per point.
+// Lane (G2: lane pair) i owns the run of the at most K consecutive points [i K, min(n, (i + 1) K)):
+//   forward    prefix[j] = z'_a z'_(a+1) ... z'_j, with z' = z, or one where z == 0 - a point at infinity must not zero the product of its run
+//   inversion  of the run's product (safegcd, fe_inverse)
+//   backward   j from the run's end: 1 / z_j = inv * prefix[j - 1], inv *= z'_j, the point from (1 / z_j)^2 and (1 / z_j)^3, (0, 1, 0) selected
+//              where z == 0
+// 3 products per point on top of the 4 of jac_normalize, and 1 / K of an inversion.  The prefix products live in memory - one field element
+// per point, `prefix`: scratch of the caller -, not in registers: K live field elements are 9 K VGPRs of a kernel that may not spill, and
+// the loops need no unrolling.  The backward pass reads point j completely before it writes out[j], and no lane reads
+// another lane's points, so out may be p.  The inverse of a field element is unique and the stores are canonical: the bytes do not depend
+// on K, and they are those of jac_normalize.
+// A prefix record: the 9 limbs of the product (a product: normalized, below 2q) in three 16-byte groups; a G2 point has two, component c0
+// for the even lane of the pair and c1 for the odd one, like the table records above.
+constexpr uint32_t NORM_PREFIX_U4 = 3;
+constexpr uint32_t NORM_RUN = 8;                  // points per inversion, one constant for both groups: of 1 / 4 / 8 / 16 the fastest for G2, within 4 % of 16 for G1 (profiles/r12_normalize.txt)
+BN_FN void prefix_record_put(const Fe &a, uint4 *rec) {
+    rec[0] = make_uint4(a.l[0], a.l[1], a.l[2], a.l[3]); rec[1] = make_uint4(a.l[4], a.l[5], a.l[6], a.l[7]); rec[2] = make_uint4(a.l[8], 0, 0, 0);
+}
+BN_FN Fe prefix_record_get(const uint4 *rec) {
+    const uint4 u = rec[0], v = rec[1], w = rec[2];
+    Fe a;
+    a.l[0] = u.x; a.l[1] = u.y; a.l[2] = u.z; a.l[3] = u.w; a.l[4] = v.x; a.l[5] = v.y; a.l[6] = v.z; a.l[7] = v.w; a.l[8] = w.x;
+    BN_SETB(a, 1, 2);                                                                // what is stored is a product (fe_mul, fe_from_u32x8)
+    BN_VERIFY(a, "prefix_record_get");
+    return a;
+}
+// Where a lane keeps the prefix product of point j (the counterpart of BaseTableMem): G1 the one record of the point, a G2 lane the record of
+// its component comp = lane & 1.  (A simulated lane pair holds both components in one value and keeps both records:
+// tests/hostsim/hostsim_normalize.cpp.)
+template <class F>
+struct PrefixMem {
+    static constexpr uint32_t REC = std::is_same<F, FqField>::value ? NORM_PREFIX_U4 : 2 * NORM_PREFIX_U4;        // 16-byte groups per point
+    uint4 *base; uint32_t comp;
+    BN_FN void put(uint32_t j, const typename F::T &a) const {
+        if constexpr (std::is_same<F, FqField>::value) prefix_record_put(a, base + (size_t)j * REC);
+        else prefix_record_put(a.v, base + (size_t)j * REC + comp * NORM_PREFIX_U4);
+    }
+    BN_FN typename F::T get(uint32_t j) const {
+        typename F::T r;
+        if constexpr (std::is_same<F, FqField>::value) r = prefix_record_get(base + (size_t)j * REC);
+        else r.v = prefix_record_get(base + (size_t)j * REC + comp * NORM_PREFIX_U4);
+        return r;
+    }
+};
+template <class F, class Pre>
+BN_FN void normalize_body(const NormalizeArgs &g, uint32_t i, uint32_t K, Pre pre, PointIo<F> io) {
+    using T = typename F::T;
+    const uint32_t a = i * K;
+    if (a >= g.n) return;
+    const uint32_t b = min(a + K, g.n);
+    T acc = F::one();
+#pragma unroll 1
+    for (uint32_t j = a; j < b; ++j) {
+        const T z = io.z(g.p + (size_t)j * io.WORDS);                                // a product: is_zero_std applies
+        const T zs = F::select(F::is_zero_std(z), z, F::one());
+        acc = j == a ? zs : F::mul(acc, zs);
+        if (j + 1 < b) pre.put(j, acc);
+    }
+    T inv = F::inverse(acc);
+#pragma unroll 1
+    for (uint32_t j = b; j-- > a;) {
+        const Jac<F> p = io(g.p + (size_t)j * io.WORDS);
+        const bool inf = F::is_zero_std(p.z);
+        T zi = inv;
+        if (j > a) {
+            zi = F::mul(inv, pre.get(j - 1));
+            inv = F::mul(inv, F::select(inf, p.z, F::one()));
+        }
+        const T zi2 = F::sqr(zi);
+        Jac<F> r = {F::mul(p.x, zi2), F::mul(p.y, F::mul(zi2, zi)), F::one()};
+        r.x = F::select(inf, r.x, F::zero()); r.y = F::select(inf, r.y, F::one()); r.z = F::select(inf, r.z, F::zero());
+        io(r, g.out + (size_t)j * io.WORDS);
+    }
+}
+// ---- a[i] == b[i] as group elements (PartialEq for G<P>, groups/mod.rs:83-109): both at infinity - equal; exactly one - not; otherwise
+// x1 z2^2 == x2 z1^2 and y1 z2^3 == y2 z1^3.  Two squarings and six products, no inversion.  The two sides are lazy residues (below 2q), so
+// what is compared with zero is their fully reduced difference (the equal-point test of jac_add_flags), never the limbs of the two products.
+template <class F>
+BN_FN int32_t eq_body(const Jac<F> &p, const Jac<F> &q) {
+    using T = typename F::T;
+    const bool pz = F::is_zero_std(p.z), qz = F::is_zero_std(q.z);                   // loaded coordinates are products
+    const T z1s = F::sqr(p.z), z2s = F::sqr(q.z);
+    const T u1 = F::mul(p.x, z2s), u2 = F::mul(q.x, z1s);
+    const T s1 = F::mul(p.y, F::mul(q.z, z2s)), s2 = F::mul(q.y, F::mul(p.z, z1s));
+    const T h = F::template lc3<1, -1, 0>(u2, u1, u1), sd = F::template lc3<1, -1, 0>(s2, s1, s1);
+    const bool same = F::is_zero_std(h) && F::is_zero_std(sd);
+    return (pz || qz) ? (pz && qz ? 1 : 0) : (same ? 1 : 0);
 }
 }  // namespace bn254

@@ -120,6 +120,7 @@ struct bn254_ctx {
     std::vector<uint64_t> msm_scal_host;    // their host image (kept while the copy may be in flight; rebuilt only when the width changes)
     long msm_scal_c = -1;
     BnBaseCache base_cache[2];          // bn254_g{1,2}_mul_base_batch: [0] G1, [1] G2
+    BnBuf norm_prefix;                  // bn254_g{1,2}_normalize_batch: the prefix products of one sub-launch (48 / 96 bytes per point)
     BnBuf base_stage;                   // the base of a table build on the device ...
     BnBuf base_stage_host{nullptr, 0, true};    // ... and its pinned staging, rewritten only after base_stage_ev (its last copy) completed
     hipEvent_t base_stage_ev = nullptr;
@@ -336,6 +337,10 @@ size_t bn254_mul_base_table_bytes_M(int g, unsigned c);
 int bn254_launch_mul_base_M(int g, const void *table, unsigned c, const void *k, void *out, size_t n, hipStream_t s);
 int bn254_launch_mul_base_tile_M(int g, const void *d_base, void *d_out, size_t n, hipStream_t s);
 int bn254_launch_mul_base_repack_M(int g, const void *d_pts, void *table, size_t n, hipStream_t s);
+unsigned bn254_normalize_run_M(void);
+size_t bn254_normalize_prefix_bytes_M(int g, size_t n);
+int bn254_launch_normalize_M(int g, const void *d_p, void *d_out, size_t n, void *prefix, hipStream_t s);
+int bn254_launch_eq_M(int g, const void *d_a, const void *d_b, void *d_out, size_t n, hipStream_t s);
 // bn254_measure.hip
 int bn254_launch_gather_K(const void *d_records, size_t records, size_t record_bytes, const void *d_index, size_t n, void *d_out, hipStream_t s);
 }

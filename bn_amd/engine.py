@@ -191,6 +191,38 @@ class Engine:
         """the same over G2 (base: 24 words) -> (n, 24) uint64"""
         return self._mul_base(self._lib.bn254_g2_mul_base_batch, base, k, G2_WORDS)
 
+    def _normalize(self, fn, p, words):
+        p = _arr(p, words) if len(p) else np.zeros((0, words), np.uint64)
+        out = np.empty_like(p)
+        _native.check(fn(self._h, _p(p), _p(out), p.shape[0]))
+        return out
+
+    def g1_normalize(self, p):
+        """out[i] = (x/z^2, y/z^3, 1) of the G1 point p[i], infinity (z == 0) as (0, 1, 0) -> (n, 12) uint64: the bytes of g1_mul_batch by
+        Fr::one(), with one field inversion per run of points (include/bn254_hip.h bn254_g1_normalize_batch)"""
+        return self._normalize(self._lib.bn254_g1_normalize_batch, p, G1_WORDS)
+
+    def g2_normalize(self, p):
+        """the same over G2 -> (n, 24) uint64"""
+        return self._normalize(self._lib.bn254_g2_normalize_batch, p, G2_WORDS)
+
+    def _eq(self, fn, a, b, words):
+        a = _arr(a, words) if len(a) else np.zeros((0, words), np.uint64)
+        b = _arr(b, words) if len(b) else np.zeros((0, words), np.uint64)
+        _same_len(a, b)
+        out = np.empty(a.shape[0], np.int32)
+        _native.check(fn(self._h, _p(a), _p(b), _p(out), a.shape[0]))
+        return out != 0
+
+    def g1_eq(self, a, b):
+        """out[i] = (a[i] == b[i]) as group elements, whatever their Jacobian representations -> (n,) bool; no inversion
+        (include/bn254_hip.h bn254_g1_eq_batch)"""
+        return self._eq(self._lib.bn254_g1_eq_batch, a, b, G1_WORDS)
+
+    def g2_eq(self, a, b):
+        """the same over G2"""
+        return self._eq(self._lib.bn254_g2_eq_batch, a, b, G2_WORDS)
+
     def g1_msm_batch(self, p, k, offsets):
         """out[j] = normalize(sum of p[i] * k[i] over i in [offsets[j], offsets[j+1])) -> (m, 12) uint64; an empty or cancelling
         segment gives G1::zero() = (0, 1, 0); ONE inversion per segment (include/bn254_hip.h bn254_g1_msm_batch)"""
@@ -413,6 +445,20 @@ class Engine:
     def g2_mul_dev(self, d_p, d_k, d_out, n, stream=0, normalize=True):
         f = self._lib.bn254_g2_mul_batch_dev if normalize else self._lib.bn254_g2_mul_jacobian_dev
         _native.check(f(self._h, d_p, d_k, d_out, n, stream))
+
+    def g1_normalize_dev(self, d_p, d_out, n, stream=0):
+        """device pointers p, out (n points; out may be p), ordered on `stream`"""
+        _native.check(self._lib.bn254_g1_normalize_batch_dev(self._h, d_p, d_out, n, stream))
+
+    def g2_normalize_dev(self, d_p, d_out, n, stream=0):
+        _native.check(self._lib.bn254_g2_normalize_batch_dev(self._h, d_p, d_out, n, stream))
+
+    def g1_eq_dev(self, d_a, d_b, d_out, n, stream=0):
+        """device pointers a, b (n points) and out (n int32: 1 or 0), ordered on `stream`"""
+        _native.check(self._lib.bn254_g1_eq_batch_dev(self._h, d_a, d_b, d_out, n, stream))
+
+    def g2_eq_dev(self, d_a, d_b, d_out, n, stream=0):
+        _native.check(self._lib.bn254_g2_eq_batch_dev(self._h, d_a, d_b, d_out, n, stream))
 
     def g1_mul_base_batch_dev(self, base, d_k, d_out, n, stream=0):
         """`base` is a HOST point (12 uint64 words), read before the call returns; d_k, d_out device pointers (n records), ordered on `stream`"""

@@ -45,7 +45,9 @@ struct G1 {
     G1 operator+(const G1 &o) const { G1 r; check(bn254_g1_add_batch(nullptr, &v, &o.v, &r.v, 1, 0)); return r; }     // lib.rs:103-106
     G1 operator-(const G1 &o) const { G1 r; check(bn254_g1_add_batch(nullptr, &v, &o.v, &r.v, 1, 1)); return r; }     // lib.rs:108-111
     G1 operator-() const { return zero() - *this; }                                                                  // lib.rs:113-114
-    void normalize() { *this = *this * Fr::one(); }                          // lib.rs:88-95
+    void normalize() { check(bn254_g1_normalize_batch(nullptr, &v, &v, 1)); }                                        // lib.rs:88-95 (in place)
+    bool operator==(const G1 &o) const { int32_t r = 0; check(bn254_g1_eq_batch(nullptr, &v, &o.v, &r, 1)); return r != 0; }   // groups/mod.rs:83-109
+    bool operator!=(const G1 &o) const { return !(*this == o); }
 };
 struct G2 {
     bn_g2 v;
@@ -62,7 +64,9 @@ struct G2 {
     G2 operator+(const G2 &o) const { G2 r; check(bn254_g2_add_batch(nullptr, &v, &o.v, &r.v, 1, 0)); return r; }
     G2 operator-(const G2 &o) const { G2 r; check(bn254_g2_add_batch(nullptr, &v, &o.v, &r.v, 1, 1)); return r; }
     G2 operator-() const { return zero() - *this; }
-    void normalize() { *this = *this * Fr::one(); }
+    void normalize() { check(bn254_g2_normalize_batch(nullptr, &v, &v, 1)); }                                        // lib.rs:131-138 (in place)
+    bool operator==(const G2 &o) const { int32_t r = 0; check(bn254_g2_eq_batch(nullptr, &v, &o.v, &r, 1)); return r != 0; }
+    bool operator!=(const G2 &o) const { return !(*this == o); }
 };
 struct Gt {
     bn_gt v;
@@ -144,6 +148,30 @@ inline std::vector<G2> g2_mul_base(const G2 &base, const std::vector<Fr> &k) {
     std::vector<G2> out(k.size());
     check(bn254_g2_mul_base_batch(nullptr, reinterpret_cast<const bn_g2 *>(&base), reinterpret_cast<const bn_fr *>(k.data()), reinterpret_cast<bn_g2 *>(out.data()), k.size()));
     return out;
+}
+// out[i] = p[i].normalize() = (x/z^2, y/z^3, 1), infinity as G::zero(): neighbouring points share one field inversion
+inline std::vector<G1> g1_normalize(const std::vector<G1> &p) {
+    std::vector<G1> out(p.size());
+    check(bn254_g1_normalize_batch(nullptr, reinterpret_cast<const bn_g1 *>(p.data()), reinterpret_cast<bn_g1 *>(out.data()), p.size()));
+    return out;
+}
+inline std::vector<G2> g2_normalize(const std::vector<G2> &p) {
+    std::vector<G2> out(p.size());
+    check(bn254_g2_normalize_batch(nullptr, reinterpret_cast<const bn_g2 *>(p.data()), reinterpret_cast<bn_g2 *>(out.data()), p.size()));
+    return out;
+}
+// out[i] = (a[i] == b[i]) as group elements, whatever their Jacobian representations (groups/mod.rs:83-109): nothing is normalized
+inline std::vector<bool> g1_eq(const std::vector<G1> &a, const std::vector<G1> &b) {
+    if (a.size() != b.size()) throw std::invalid_argument("g1_eq: length mismatch");
+    std::vector<int32_t> r(a.size());
+    check(bn254_g1_eq_batch(nullptr, reinterpret_cast<const bn_g1 *>(a.data()), reinterpret_cast<const bn_g1 *>(b.data()), r.data(), a.size()));
+    return std::vector<bool>(r.begin(), r.end());
+}
+inline std::vector<bool> g2_eq(const std::vector<G2> &a, const std::vector<G2> &b) {
+    if (a.size() != b.size()) throw std::invalid_argument("g2_eq: length mismatch");
+    std::vector<int32_t> r(a.size());
+    check(bn254_g2_eq_batch(nullptr, reinterpret_cast<const bn_g2 *>(a.data()), reinterpret_cast<const bn_g2 *>(b.data()), r.data(), a.size()));
+    return std::vector<bool>(r.begin(), r.end());
 }
 // ok[j] = (product of segment j == Gt::one()): the predicate of a block of pairing checks
 inline std::vector<bool> pairing_check_batch(const std::vector<G1> &p, const std::vector<G2> &q, const std::vector<size_t> &offsets) {
