@@ -86,6 +86,16 @@ extern "C" {
     fn bn254_g2_normalize_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_g1_eq_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_g2_eq_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_fr_add_batch(ctx: *mut c_void, a: *const Fr, b: *const Fr, out: *mut Fr, n: usize, negate_b: c_int) -> c_int;
+    fn bn254_fr_mul_batch(ctx: *mut c_void, a: *const Fr, b: *const Fr, out: *mut Fr, n: usize) -> c_int;
+    fn bn254_fr_inverse_batch(ctx: *mut c_void, a: *const Fr, out: *mut Fr, ok: *mut i32, n: usize) -> c_int;
+    fn bn254_fr_pow_batch(ctx: *mut c_void, a: *const Fr, e: *const Fr, out: *mut Fr, n: usize) -> c_int;
+    fn bn254_fr_interpret_batch(ctx: *mut c_void, bytes: *const u8, out: *mut Fr, n: usize) -> c_int;
+    fn bn254_fr_add_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_out: *mut c_void, n: usize, negate_b: c_int, stream: *mut c_void) -> c_int;
+    fn bn254_fr_mul_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_fr_inverse_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_out: *mut c_void, d_ok: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_fr_pow_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_e: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_fr_interpret_batch_dev(ctx: *mut c_void, d_in: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
 }
 
 /// One line-function coefficient of a prepared G2 point: the crate's `EllCoeffs { ell_0, ell_vw, ell_vv: Fq2 }` (src/groups/mod.rs:472-476) as the
@@ -263,6 +273,53 @@ pub fn g2_eq(a: &[G2], b: &[G2]) -> Result<Vec<bool>, GpuError> {
     let mut out = vec![0i32; a.len()];
     check(unsafe { bn254_g2_eq_batch(std::ptr::null_mut(), a.as_ptr(), b.as_ptr(), out.as_mut_ptr(), a.len()) })?;
     Ok(out.into_iter().map(|r| r != 0).collect())
+}
+
+/// `out[i] = a[i] + b[i]` in the scalar field (src/lib.rs:33-37), for arrays of scalars that feed `g1_msm`, `g1_mul_base`, `Gt::pow` ...
+pub fn fr_add(a: &[Fr], b: &[Fr]) -> Result<Vec<Fr>, GpuError> {
+    assert_eq!(a.len(), b.len());
+    let mut out = vec![Fr::zero(); a.len()];
+    check(unsafe { bn254_fr_add_batch(std::ptr::null_mut(), a.as_ptr(), b.as_ptr(), out.as_mut_ptr(), a.len(), 0) })?;
+    Ok(out)
+}
+
+/// `out[i] = a[i] - b[i]` (src/lib.rs:39-41); `-b` is `fr_sub(&zeros, b)` (src/lib.rs:43-47)
+pub fn fr_sub(a: &[Fr], b: &[Fr]) -> Result<Vec<Fr>, GpuError> {
+    assert_eq!(a.len(), b.len());
+    let mut out = vec![Fr::zero(); a.len()];
+    check(unsafe { bn254_fr_add_batch(std::ptr::null_mut(), a.as_ptr(), b.as_ptr(), out.as_mut_ptr(), a.len(), 1) })?;
+    Ok(out)
+}
+
+/// `out[i] = a[i] * b[i]` (src/lib.rs:49-53)
+pub fn fr_mul(a: &[Fr], b: &[Fr]) -> Result<Vec<Fr>, GpuError> {
+    assert_eq!(a.len(), b.len());
+    let mut out = vec![Fr::zero(); a.len()];
+    check(unsafe { bn254_fr_mul_batch(std::ptr::null_mut(), a.as_ptr(), b.as_ptr(), out.as_mut_ptr(), a.len()) })?;
+    Ok(out)
+}
+
+/// `out[i] = a[i].inverse()` (src/lib.rs:25): `None` for a zero element; neighbouring elements share one exponentiation
+pub fn fr_inverse(a: &[Fr]) -> Result<Vec<Option<Fr>>, GpuError> {
+    let mut out = vec![Fr::zero(); a.len()];
+    let mut ok = vec![0i32; a.len()];
+    check(unsafe { bn254_fr_inverse_batch(std::ptr::null_mut(), a.as_ptr(), out.as_mut_ptr(), ok.as_mut_ptr(), a.len()) })?;
+    Ok(out.into_iter().zip(ok).map(|(x, k)| if k != 0 { Some(x) } else { None }).collect())
+}
+
+/// `out[i] = a[i].pow(e[i])` (src/lib.rs:23); `0^0` is one
+pub fn fr_pow(a: &[Fr], e: &[Fr]) -> Result<Vec<Fr>, GpuError> {
+    assert_eq!(a.len(), e.len());
+    let mut out = vec![Fr::zero(); a.len()];
+    check(unsafe { bn254_fr_pow_batch(std::ptr::null_mut(), a.as_ptr(), e.as_ptr(), out.as_mut_ptr(), a.len()) })?;
+    Ok(out)
+}
+
+/// `out[i] = Fr::interpret(&bufs[i])` (src/lib.rs:27-29): 64 bytes as a big-endian 512-bit integer, mod r
+pub fn fr_interpret(bufs: &[[u8; 64]]) -> Result<Vec<Fr>, GpuError> {
+    let mut out = vec![Fr::zero(); bufs.len()];
+    check(unsafe { bn254_fr_interpret_batch(std::ptr::null_mut(), bufs.as_ptr() as *const u8, out.as_mut_ptr(), bufs.len()) })?;
+    Ok(out)
 }
 
 /// `out[i] = a[i] * b[i]` (src/lib.rs:175-179)

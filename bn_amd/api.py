@@ -2,8 +2,9 @@
 the GPU engine adds (pairing_batch / pairing_product; the reference only has the fold of shootout/main.rs:11-16).
 
 Values are immutable wrappers around the reference's memory images (Montgomery u64 limbs).  Group and pairing arithmetic
-runs on the GPU through the C ABI; only the scalar field Fr (lib.rs:15-53, "host-side convenience" in SURVEY.md) is plain
-Python integer arithmetic.  No CPU fallback for anything that touches a curve point or a Gt."""
+runs on the GPU through the C ABI; the operators of a single scalar Fr (lib.rs:15-53, "host-side convenience" in SURVEY.md) are plain
+Python integer arithmetic, ARRAYS of scalars have the batch functions fr_*_batch, which run on the GPU like everything else.  No CPU
+fallback for anything that touches a curve point or a Gt."""
 import numpy as np
 
 from .engine import Engine, G1_WORDS, G2_WORDS, GT_WORDS
@@ -51,6 +52,12 @@ class Fr:
     @staticmethod
     def random(rng):                      # uniform mod r from 512 bits, like arith.rs:195-198
         return Fr(int.from_bytes(rng.bytes(64), "little"))
+    @staticmethod
+    def interpret(buf):                   # lib.rs:27-29 -> arith.rs:90-97: 64 bytes as a big-endian 512-bit integer, mod r
+        buf = bytes(buf)
+        if len(buf) != 64:
+            raise ValueError("Fr.interpret takes exactly 64 bytes")
+        return Fr(int.from_bytes(buf, "big"))
     @staticmethod
     def from_limbs(l):
         return Fr(sum(int(x) << (64 * i) for i, x in enumerate(l)) * pow(_MONT, -1, R_MOD))
@@ -324,6 +331,48 @@ def g1_eq_batch(a, b, engine=None):
 def g2_eq_batch(a, b, engine=None):
     """the same over G2"""
     return [bool(r) for r in (engine or default_engine()).g2_eq(_point_array(G2, a), _point_array(G2, b))]
+
+
+def fr_add_batch(a, b, engine=None):
+    """[x + y for x, y in zip(a, b)] on the GPU in one call.  Here and below: sequences of Fr, or (n,4) uint64 arrays of Montgomery limbs."""
+    return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_add_batch(_scalar_array(a), _scalar_array(b))]
+
+
+def fr_sub_batch(a, b, engine=None):
+    """[x - y for x, y in zip(a, b)]"""
+    return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_add_batch(_scalar_array(a), _scalar_array(b), negate_b=True)]
+
+
+def fr_neg_batch(a, engine=None):
+    """[-x for x in a]: 0 - x (lib.rs:43-47)"""
+    A = _scalar_array(a)
+    return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_add_batch(np.zeros_like(A), A, negate_b=True)]
+
+
+def fr_mul_batch(a, b, engine=None):
+    """[x * y for x, y in zip(a, b)]"""
+    return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_mul_batch(_scalar_array(a), _scalar_array(b))]
+
+
+def fr_pow_batch(a, e, engine=None):
+    """[x.pow(y) for x, y in zip(a, e)] (lib.rs:23); 0^0 is one"""
+    return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_pow_batch(_scalar_array(a), _scalar_array(e))]
+
+
+def fr_inverse_batch(a, engine=None):
+    """[x.inverse() for x in a] (lib.rs:25): a list of Fr, None where x is zero; neighbouring elements share one exponentiation"""
+    out, ok = (engine or default_engine()).fr_inverse_batch(_scalar_array(a))
+    return [Fr.from_limbs(r) if k else None for r, k in zip(out, ok)]
+
+
+def fr_interpret_batch(bufs, engine=None):
+    """[Fr.interpret(b) for b in bufs] (lib.rs:27-29): a sequence of 64-byte buffers, or an (n,64) uint8 array"""
+    if not isinstance(bufs, np.ndarray):
+        bufs = [bytes(b) for b in bufs]
+        if any(len(b) != 64 for b in bufs):
+            raise ValueError("Fr.interpret takes exactly 64 bytes")
+        bufs = np.frombuffer(b"".join(bufs), np.uint8).reshape(-1, 64)
+    return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_interpret_batch(bufs)]
 
 
 class PreparedG2:

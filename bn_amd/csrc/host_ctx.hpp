@@ -121,6 +121,7 @@ struct bn254_ctx {
     long msm_scal_c = -1;
     BnBaseCache base_cache[2];          // bn254_g{1,2}_mul_base_batch: [0] G1, [1] G2
     BnBuf norm_prefix;                  // bn254_g{1,2}_normalize_batch: the prefix products of one sub-launch (48 / 96 bytes per point)
+    BnBuf fr_prefix;                    // bn254_fr_inverse_batch: the prefix products of one sub-launch (32 bytes per element)
     BnBuf base_stage;                   // the base of a table build on the device ...
     BnBuf base_stage_host{nullptr, 0, true};    // ... and its pinned staging, rewritten only after base_stage_ev (its last copy) completed
     hipEvent_t base_stage_ev = nullptr;

@@ -223,6 +223,42 @@ class Engine:
         """the same over G2"""
         return self._eq(self._lib.bn254_g2_eq_batch, a, b, G2_WORDS)
 
+    # ---- the scalar field on the device (include/bn254_hip.h bn254_fr_*_batch): (n,4) uint64 Montgomery images in, the same out
+    def _fr2(self, fn, a, b, *tail):
+        a = _arr(a, 4) if len(a) else np.zeros((0, 4), np.uint64)
+        b = _arr(b, 4) if len(b) else np.zeros((0, 4), np.uint64)
+        _same_len(a, b)
+        out = np.empty_like(a)
+        _native.check(fn(self._h, _p(a), _p(b), _p(out), a.shape[0], *tail))
+        return out
+
+    def fr_add_batch(self, a, b, negate_b=False):
+        """out[i] = a[i] + b[i] (negate_b: a[i] - b[i]) mod r -> (n, 4) uint64"""
+        return self._fr2(self._lib.bn254_fr_add_batch, a, b, 1 if negate_b else 0)
+
+    def fr_mul_batch(self, a, b):
+        """out[i] = a[i] * b[i] mod r -> (n, 4) uint64"""
+        return self._fr2(self._lib.bn254_fr_mul_batch, a, b)
+
+    def fr_pow_batch(self, a, e):
+        """out[i] = a[i]^(the canonical integer of e[i]) -> (n, 4) uint64; 0^0 = 1"""
+        return self._fr2(self._lib.bn254_fr_pow_batch, a, e)
+
+    def fr_inverse_batch(self, a):
+        """(out, ok): out[i] = a[i]^-1 and ok[i] True, or Fr::zero() and False where a[i] is zero -> (n, 4) uint64, (n,) bool; neighbouring
+        elements share one exponentiation (include/bn254_hip.h bn254_fr_inverse_batch)"""
+        a = _arr(a, 4) if len(a) else np.zeros((0, 4), np.uint64)
+        out = np.empty_like(a); ok = np.empty(a.shape[0], np.int32)
+        _native.check(self._lib.bn254_fr_inverse_batch(self._h, _p(a), _p(out), _p(ok), a.shape[0]))
+        return out, ok != 0
+
+    def fr_interpret_batch(self, buf):
+        """out[i] = the 64-byte record i of `buf` as a big-endian 512-bit integer, mod r (Fr::interpret, lib.rs:27-29) -> (n, 4) uint64"""
+        b = np.ascontiguousarray(buf, np.uint8).reshape(-1, 64)
+        out = np.empty((b.shape[0], 4), np.uint64)
+        _native.check(self._lib.bn254_fr_interpret_batch(self._h, _p(b), _p(out), b.shape[0]))
+        return out
+
     def g1_msm_batch(self, p, k, offsets):
         """out[j] = normalize(sum of p[i] * k[i] over i in [offsets[j], offsets[j+1])) -> (m, 12) uint64; an empty or cancelling
         segment gives G1::zero() = (0, 1, 0); ONE inversion per segment (include/bn254_hip.h bn254_g1_msm_batch)"""
@@ -459,6 +495,24 @@ class Engine:
 
     def g2_eq_dev(self, d_a, d_b, d_out, n, stream=0):
         _native.check(self._lib.bn254_g2_eq_batch_dev(self._h, d_a, d_b, d_out, n, stream))
+
+    def fr_add_batch_dev(self, d_a, d_b, d_out, n, negate_b=False, stream=0):
+        """device pointers a, b, out (n records of 32 bytes; out may be a or b), ordered on `stream`"""
+        _native.check(self._lib.bn254_fr_add_batch_dev(self._h, d_a, d_b, d_out, n, 1 if negate_b else 0, stream))
+
+    def fr_mul_batch_dev(self, d_a, d_b, d_out, n, stream=0):
+        _native.check(self._lib.bn254_fr_mul_batch_dev(self._h, d_a, d_b, d_out, n, stream))
+
+    def fr_pow_batch_dev(self, d_a, d_e, d_out, n, stream=0):
+        _native.check(self._lib.bn254_fr_pow_batch_dev(self._h, d_a, d_e, d_out, n, stream))
+
+    def fr_inverse_batch_dev(self, d_a, d_out, d_ok, n, stream=0):
+        """d_ok: n int32 (1 / 0), or None"""
+        _native.check(self._lib.bn254_fr_inverse_batch_dev(self._h, d_a, d_out, d_ok, n, stream))
+
+    def fr_interpret_batch_dev(self, d_in, d_out, n, stream=0):
+        """d_in: 64 n bytes, d_out: n records"""
+        _native.check(self._lib.bn254_fr_interpret_batch_dev(self._h, d_in, d_out, n, stream))
 
     def g1_mul_base_batch_dev(self, base, d_k, d_out, n, stream=0):
         """`base` is a HOST point (12 uint64 words), read before the call returns; d_k, d_out device pointers (n records), ordered on `stream`"""

@@ -6,12 +6,15 @@ which is checked as  e(A, B) * e(-alpha, beta) * e(-L, gamma) * e(-C, delta) == 
 multiplication for every L (bn_amd.g1_msm_batch, segment j: IC[0] * 1, IC[i] * a_ji), one batched subtraction for the negations and one
 batched multi-pairing check (bn_amd.pairing_check_batch, four pairs per proof).  With prepared=True the G2 side of the block - the key's beta,
 gamma, delta and every proof's B - is prepared once on the device (Engine.g2_prepare) and the check runs over the native line tables
-(Engine.pairing_product_batch_prepared_native): the four pairs of a proof share one Miller accumulator."""
+(Engine.pairing_product_batch_prepared_native): the four pairs of a proof share one Miller accumulator.
+
+verify_aggregate answers for the whole block at once: a random linear combination of the m checks is ONE multi-pairing of m + 3 pairs."""
 import collections
+import secrets
 
 import numpy as np
 
-from .api import Fr, G1, Gt, default_engine, pairing_check_batch
+from .api import Fr, G1, Gt, R_MOD, default_engine, pairing_check_batch
 from .engine import G1_WORDS, G2_WORDS
 
 VerifyingKey = collections.namedtuple("VerifyingKey", "alpha_g1 beta_g2 gamma_g2 delta_g2 ic")
@@ -54,3 +57,45 @@ def verify_batch(vk, proofs, public_inputs, engine=None, prepared=False):
             h.close()
         return (out == Gt.one().limbs).all(axis=1)
     return pairing_check_batch(P.reshape(-1, G1_WORDS), Q.reshape(-1, G2_WORDS), offsets=np.arange(m + 1, dtype=np.uint64) * 4, engine=e)
+
+
+def _block_args(vk, proofs, public_inputs):
+    proofs = list(proofs); public_inputs = [list(a) for a in public_inputs]
+    m, l = len(proofs), len(vk.ic) - 1
+    if len(public_inputs) != m:
+        raise ValueError(f"{m} proofs but {len(public_inputs)} sets of public inputs")
+    if any(len(a) != l for a in public_inputs):
+        raise ValueError(f"every proof takes {l} public inputs (len(vk.ic) - 1)")
+    return proofs, public_inputs, m, l
+
+
+def verify_aggregate(vk, proofs, public_inputs, engine=None, rng=None):
+    """ONE bool for the whole block: with random 128-bit r_j,
+        prod_j [e(A_j, B_j) e(-alpha, beta) e(-L_j, gamma) e(-C_j, delta)]^(r_j) == 1
+    evaluated as the multi-pairing  prod_j e(r_j A_j, B_j) * e(-(sum r_j) alpha, beta) * e(-sum_j r_j L_j, gamma) * e(-sum_j r_j C_j, delta):
+    m + 3 Miller loops and one final exponentiation where verify_batch runs 4 m and m.  The scaled A_j are one g1_mul_batch, the products
+    r_j * a_ji (a_j0 = 1) one fr_mul_batch, the three sums one g1_msm_batch of three segments, their negation one g1_add_batch.
+    A block that holds a bad proof is accepted with probability about 2^-128 (the r_j are drawn from `secrets`); the answer does not say
+    WHICH proof failed - verify_batch does.  rng: tests only - an object with .bytes(n) (numpy Generator) that makes the r_j reproducible.
+    An empty block is True.  Arguments as for verify_batch, and rejected like there before any device call."""
+    proofs, public_inputs, m, l = _block_args(vk, proofs, public_inputs)
+    if m == 0:
+        return True
+    e = engine or default_engine()
+    draw = (lambda: int.from_bytes(rng.bytes(16), "little")) if rng is not None else (lambda: secrets.randbits(128))
+    r = [Fr(draw()) for _ in range(m)]
+    R = np.stack([x.limbs for x in r])
+    A = e.g1_mul_batch(np.stack([a.limbs for a, _, _ in proofs]), R)
+    one = Fr.one().limbs
+    inputs = np.stack([one if i == 0 else a[i - 1].limbs for a in public_inputs for i in range(l + 1)])
+    ra = e.fr_mul_batch(np.repeat(R, l + 1, axis=0), inputs)
+    ic = np.stack([p.limbs for p in vk.ic])
+    C = np.stack([c.limbs for _, _, c in proofs])
+    rsum = Fr(sum(x.v for x in r) % R_MOD).limbs
+    n1 = m * (l + 1)
+    sums = e.g1_msm_batch(np.concatenate([vk.alpha_g1.limbs[None], np.tile(ic, (m, 1)), C]), np.concatenate([rsum[None], ra, R]),
+                          np.array([0, 1, 1 + n1, 1 + n1 + m], np.uint64))
+    neg = e.g1_add_batch(np.tile(G1.zero().limbs, (3, 1)), sums, negate_b=True)
+    P = np.concatenate([A, neg])
+    Q = np.concatenate([np.stack([b.limbs for _, b, _ in proofs]), vk.beta_g2.limbs[None], vk.gamma_g2.limbs[None], vk.delta_g2.limbs[None]])
+    return bool(np.array_equal(e.pairing_product(P, Q), Gt.one().limbs))

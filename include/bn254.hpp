@@ -9,9 +9,11 @@
 //   Gt::one(), a == b              lib.rs:169     bn::Gt::one(), a == b   (canonical limbs: memcmp)
 //   (fold of shootout/main.rs)                    bn::pairing_batch(...), bn::pairing_product(...)
 #pragma once
+#include <array>
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "bn254_hip.h"
@@ -158,6 +160,33 @@ inline std::vector<G1> g1_normalize(const std::vector<G1> &p) {
 inline std::vector<G2> g2_normalize(const std::vector<G2> &p) {
     std::vector<G2> out(p.size());
     check(bn254_g2_normalize_batch(nullptr, reinterpret_cast<const bn_g2 *>(p.data()), reinterpret_cast<bn_g2 *>(out.data()), p.size()));
+    return out;
+}
+// The crate's Fr operations (lib.rs:15-53) over arrays of scalars, on the device: out[i] = a[i] + b[i], a[i] - b[i], a[i] * b[i],
+// a[i].pow(e[i]) (0^0 is one), Fr::interpret of 64-byte records, and a[i].inverse() as (values, ok) with Fr::zero() / false for a zero element
+inline std::vector<Fr> fr_binary(int (*fn)(bn254_ctx *, const bn_fr *, const bn_fr *, bn_fr *, size_t), const std::vector<Fr> &a, const std::vector<Fr> &b) {
+    if (a.size() != b.size()) throw std::invalid_argument("fr batch: length mismatch");
+    std::vector<Fr> out(a.size());
+    check(fn(nullptr, reinterpret_cast<const bn_fr *>(a.data()), reinterpret_cast<const bn_fr *>(b.data()), reinterpret_cast<bn_fr *>(out.data()), a.size()));
+    return out;
+}
+inline std::vector<Fr> fr_add(const std::vector<Fr> &a, const std::vector<Fr> &b) {
+    return fr_binary([](bn254_ctx *c, const bn_fr *x, const bn_fr *y, bn_fr *o, size_t n) { return bn254_fr_add_batch(c, x, y, o, n, 0); }, a, b);
+}
+inline std::vector<Fr> fr_sub(const std::vector<Fr> &a, const std::vector<Fr> &b) {
+    return fr_binary([](bn254_ctx *c, const bn_fr *x, const bn_fr *y, bn_fr *o, size_t n) { return bn254_fr_add_batch(c, x, y, o, n, 1); }, a, b);
+}
+inline std::vector<Fr> fr_mul(const std::vector<Fr> &a, const std::vector<Fr> &b) { return fr_binary(bn254_fr_mul_batch, a, b); }
+inline std::vector<Fr> fr_pow(const std::vector<Fr> &a, const std::vector<Fr> &e) { return fr_binary(bn254_fr_pow_batch, a, e); }
+inline std::pair<std::vector<Fr>, std::vector<bool>> fr_inverse(const std::vector<Fr> &a) {
+    std::vector<Fr> out(a.size());
+    std::vector<int32_t> ok(a.size());
+    check(bn254_fr_inverse_batch(nullptr, reinterpret_cast<const bn_fr *>(a.data()), reinterpret_cast<bn_fr *>(out.data()), ok.data(), a.size()));
+    return {out, std::vector<bool>(ok.begin(), ok.end())};
+}
+inline std::vector<Fr> fr_interpret(const std::vector<std::array<uint8_t, 64>> &bufs) {
+    std::vector<Fr> out(bufs.size());
+    check(bn254_fr_interpret_batch(nullptr, reinterpret_cast<const uint8_t *>(bufs.data()), reinterpret_cast<bn_fr *>(out.data()), bufs.size()));
     return out;
 }
 // out[i] = (a[i] == b[i]) as group elements, whatever their Jacobian representations (groups/mod.rs:83-109): nothing is normalized

@@ -30,6 +30,13 @@
  *   bn254_g1_normalize_batch / bn254_g2_normalize_batch  out[i] = p[i].normalize() = (x/z^2, y/z^3, 1), infinity as G::zero()
  *                                                                                    lib.rs:88-95,131-138, groups/mod.rs:113-130
  *   bn254_g1_eq_batch / bn254_g2_eq_batch  out[i] = (a[i] == b[i]) as 1 / 0           PartialEq for G<P>, groups/mod.rs:83-109
+ *   bn254_fr_add_batch     out[i] = a[i] + b[i] / a[i] - b[i]                            lib.rs:33-47 (Add, Sub, Neg = 0 - b), fields/fp.rs:131-167
+ *   bn254_fr_mul_batch     out[i] = a[i] * b[i]                                          lib.rs:49-53, fields/fp.rs:169-177
+ *   bn254_fr_inverse_batch out[i] = a[i].inverse(): Option<Fr> as ok[i] = 1, or 0 with Fr::zero()   lib.rs:25, fields/fp.rs:107-115
+ *   bn254_fr_pow_batch     out[i] = a[i].pow(e[i])                                       lib.rs:23, fields/mod.rs:35-46
+ *   bn254_fr_interpret_batch  out[i] = Fr::interpret(&in[64 i .. 64 i + 64])             lib.rs:27-29, fields/fp.rs:72-74, arith.rs:90-97
+ *   bn254_fr_add_batch_dev / bn254_fr_mul_batch_dev / bn254_fr_inverse_batch_dev / bn254_fr_pow_batch_dev / bn254_fr_interpret_batch_dev
+ *                          the same five on device-resident arrays, asynchronous on the caller's stream
  *   bn254_g2_precompute    coeffs[i][0..102) = q[i].to_affine().precompute().coeffs   groups/mod.rs:557-588 (Q != infinity)
  *   bn254_pairing_prepared_batch  out[i] = final_exponentiation(prepared.miller_loop(p[i]))   groups/mod.rs:486-519,768
  *   bn254_gt_mul_batch     out[i] = a[i] * b[i]                                     lib.rs:175-179, fields/fq12.rs:295-307
@@ -64,6 +71,7 @@
      bn254_g{1,2}_mul_base_batch serialise on the context as well (they hold its mutex for the call: lookup or build of the base's table,
      staging, launches, copy back).
      bn254_g{1,2}_normalize_batch and bn254_g{1,2}_eq_batch serialise on the context in the same way (its mutex for the call).
+     bn254_fr_{add,mul,inverse,pow,interpret}_batch serialise on the context in the same way (its mutex for the whole call).
  *     bn254_pairing_product_batch_prepared_native serialises on the context like them; its handle is immutable and shared freely.
  *     Use one context per thread (or bn254_multi_*) for more overlap;
  *     bn254_ctx_set_option is atomic, but set options before concurrent use: a call in flight may run some
@@ -83,6 +91,8 @@
      the previous miss's base, and - once per context and group - synchronises `stream` when it uploads the scalars the tables are built with.
      bn254_g{1,2}_normalize_batch_dev keep the prefix products of a sub-launch in context-owned scratch under the same event ordering;
      bn254_g{1,2}_eq_batch_dev use no scratch.  Neither reads anything back nor waits on the host.
+     bn254_fr_inverse_batch_dev keeps the prefix products of a sub-launch in context-owned scratch under the same event ordering;
+     bn254_fr_{add,mul,pow,interpret}_batch_dev use no scratch.  None of the five waits on anything or reads anything back.
  */
 #ifndef BN254_HIP_H
 #define BN254_HIP_H
@@ -347,6 +357,32 @@ int bn254_gt_mul_batch(bn254_ctx *ctx, const bn_gt *a, const bn_gt *b, bn_gt *ou
 int bn254_gt_pow_batch(bn254_ctx *ctx, const bn_gt *a, const bn_fr *k, bn_gt *out, size_t n);
 /* out[i] = a[i]^-1 in Fq12 (Gt::inverse, lib.rs:172 -> fields/fq12.rs:284-292); a[i] must be non-zero, as every Gt value is */
 int bn254_gt_inverse_batch(bn254_ctx *ctx, const bn_gt *a, bn_gt *out, size_t n);
+/* Batched scalar-field arithmetic - the crate's Fr (lib.rs:15-53) for ARRAYS of scalars: the powers of tau of a bn254_g{1,2}_mul_base_batch
+   call, the products r_j * a_ji of a random linear combination of checks, Lagrange denominators, whatever feeds bn254_g{1,2}_msm*,
+   bn254_g{1,2}_mul_base_batch or bn254_gt_pow_batch.  Inputs are canonical Montgomery images (< r), the bytes the reference keeps; outputs
+   are canonical, hence unique, hence the reference's bytes whichever algorithm computes them.  A non-canonical input is outside the
+   contract but memory safe.  `out` may be exactly `a` or exactly `b` (partial overlap is outside the contract).
+   add: a + b, or a - b when negate_b != 0; `Neg` is 0 - b, as for bn254_g1_add_batch.
+   inverse: Option<Fr> - ok[i] = 1 and out[i] = a[i]^-1, or ok[i] = 0 and out[i] = Fr::zero() for a[i] == 0; ok may be NULL.  One
+   exponentiation by r - 2 is shared by a run of 8 consecutive elements (Montgomery's trick: prefix products - one in place of a zero
+   element -, one a^(r-2), a backward pass): 3 products per element and an eighth of an exponentiation; a zero does not disturb its
+   neighbours, and the bytes do not depend on the run length.
+   pow: a^(canonical integer of e) (fields/mod.rs:35-46 through lib.rs:23) by a fixed, data-independent 2-bit window over the 254 bits of
+   the exponent; 0^0 = 1 (the reference's loop starts from one and sees no bit), 0^e = 0 for e > 0.
+   interpret: every 64-byte record as a big-endian 512-bit integer hi * 2^256 + lo, reduced mod r by two Montgomery products (lo by R^2,
+   hi by R^3) and one addition.
+   One element per lane as eight 32-bit words in radix 2^256 (the ABI bytes: nothing is converted), word-serial Montgomery products of
+   v_mad_u64_u32, records moved as 16-byte loads and stores (device pointers of the _dev twins: 16-byte aligned).  The run length 8 and
+   the 2-bit window are defaults chosen WITHOUT a measurement: tools/time_fr.py times run lengths 1 / 4 / 8 / 16 and windows of
+   1 / 2 / 4 bits in one process and writes profiles/r13_fr.txt, which is not in the tree yet.
+   Errors (BN254_E_BAD_ARG, checked before any device is touched): a NULL input or output with n > 0 (ok excepted), n > 2^40.  n == 0
+   returns BN254_OK and writes nothing.  Batches run as sub-launches of at most 2^22 elements.  Threading: see above - the host-buffer
+   entry points hold the context's mutex for the whole call. */
+int bn254_fr_add_batch(bn254_ctx *ctx, const bn_fr *a, const bn_fr *b, bn_fr *out, size_t n, int negate_b);
+int bn254_fr_mul_batch(bn254_ctx *ctx, const bn_fr *a, const bn_fr *b, bn_fr *out, size_t n);
+int bn254_fr_inverse_batch(bn254_ctx *ctx, const bn_fr *a, bn_fr *out, int32_t *ok, size_t n);
+int bn254_fr_pow_batch(bn254_ctx *ctx, const bn_fr *a, const bn_fr *e, bn_fr *out, size_t n);
+int bn254_fr_interpret_batch(bn254_ctx *ctx, const uint8_t *in, bn_fr *out, size_t n);
 
 /* ---- one node, several GPUs (north_star: independent batches shard across the GPUs; ONE exchange for the multi-pairing) --- */
 /* `devices[0..ndev)`: HIP device index of every rank (NULL = 0..ndev-1).  One context and one host thread per rank.  A device may
@@ -484,6 +520,14 @@ int bn254_g1_normalize_batch_dev(bn254_ctx *ctx, const void *d_p, void *d_out, s
 int bn254_g2_normalize_batch_dev(bn254_ctx *ctx, const void *d_p, void *d_out, size_t n, void *stream);
 int bn254_g1_eq_batch_dev(bn254_ctx *ctx, const void *d_a, const void *d_b, void *d_out, size_t n, void *stream);
 int bn254_g2_eq_batch_dev(bn254_ctx *ctx, const void *d_a, const void *d_b, void *d_out, size_t n, void *stream);
+/* bn254_fr_{add,mul,inverse,pow,interpret}_batch on device-resident arrays (n records of 32 bytes; d_in of interpret: 64 n bytes; d_ok of
+   inverse: n int32, or NULL), asynchronous on `stream`.  d_out may be exactly d_a or d_b.  inverse keeps its prefix products in
+   context-owned scratch (see Threading); the others use none. */
+int bn254_fr_add_batch_dev(bn254_ctx *ctx, const void *d_a, const void *d_b, void *d_out, size_t n, int negate_b, void *stream);
+int bn254_fr_mul_batch_dev(bn254_ctx *ctx, const void *d_a, const void *d_b, void *d_out, size_t n, void *stream);
+int bn254_fr_inverse_batch_dev(bn254_ctx *ctx, const void *d_a, void *d_out, void *d_ok, size_t n, void *stream);
+int bn254_fr_pow_batch_dev(bn254_ctx *ctx, const void *d_a, const void *d_e, void *d_out, size_t n, void *stream);
+int bn254_fr_interpret_batch_dev(bn254_ctx *ctx, const void *d_in, void *d_out, size_t n, void *stream);
 /* raw Jacobian result of the reference's MSB-first double-and-add (what G::random produces, groups/mod.rs:220-222):
    used to generate benchmark inputs with z != 1 on the device */
 int bn254_g1_mul_jacobian_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, void *d_out, size_t n, void *stream);
@@ -500,7 +544,7 @@ int bn254_tile_dev(bn254_ctx *ctx, const void *d_record, size_t record_bytes, si
    accumulated duration and launch count per kernel since the last reset (this is what bench.py's roofline uses). */
 int bn254_profile_enable(bn254_ctx *ctx, int on);
 int bn254_profile_reset(bn254_ctx *ctx);
-/* kernel: "miller", "miller_shared", "miller_wave", "miller_quad", "pairing_wave", "final_exp", "final_exp_wave", "final_exp_quad", "exp_by_neg_z", "gt_product", "gt_tail", "gt_segment", "gt_tail_seg", "g1_mul", "g2_mul", "gt_mul", "gt_pow", "g2_precompute", "miller_prepared", "g2_prepare_native", "miller_native", "miller_native_shared", "miller_native_seg", "g2_gather", "wire_encode", "wire_decode", "gt_inverse", "g1_add", "g2_add", "g1_msm_mul", "g1_msm_fold", "g2_msm_mul", "g2_msm_fold", "g1_msm_digits", "g1_msm_bucket", "g1_msm_reduce", "g2_msm_digits", "g2_msm_bucket", "g2_msm_reduce", "g1_mul_base", "g2_mul_base", "g1_base_table", "g2_base_table", "g1_normalize", "g2_normalize", "g1_eq", "g2_eq".
+/* kernel: "miller", "miller_shared", "miller_wave", "miller_quad", "pairing_wave", "final_exp", "final_exp_wave", "final_exp_quad", "exp_by_neg_z", "gt_product", "gt_tail", "gt_segment", "gt_tail_seg", "g1_mul", "g2_mul", "gt_mul", "gt_pow", "g2_precompute", "miller_prepared", "g2_prepare_native", "miller_native", "miller_native_shared", "miller_native_seg", "g2_gather", "wire_encode", "wire_decode", "fr_add", "fr_mul", "fr_inverse", "fr_pow", "fr_interpret", "gt_inverse", "g1_add", "g2_add", "g1_msm_mul", "g1_msm_fold", "g2_msm_mul", "g2_msm_fold", "g1_msm_digits", "g1_msm_bucket", "g1_msm_reduce", "g2_msm_digits", "g2_msm_bucket", "g2_msm_reduce", "g1_mul_base", "g2_mul_base", "g1_base_table", "g2_base_table", "g1_normalize", "g2_normalize", "g1_eq", "g2_eq".
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);
 /* issue-rate ceiling of v_mad_u64_u32 (the 32x32+64 multiply-accumulate every field product is built from) at
