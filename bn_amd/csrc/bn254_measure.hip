@@ -5,13 +5,14 @@
 //     long form; the multiplier's rate depends on its DATA - profiles/r04_ubench_mad_data_dependence.txt -, hence the operand-width argument:
 //     32 random bits for `peak`, the engine's own 29-bit limbs for `peak_at_kernel_occupancy`);
 //   * bn254_synthetic_scalars_dev: the on-device generator of the synthetic Fr scalars (SplitMix64 -> 512 bits -> mod r -> Montgomery form),
-//     word for word bn_amd.distributed.synthetic_scalars;
+//     word for word bn_amd.distributed.synthetic_scalars; the kernel is a launch of fr_ops.hpp's fr_synthetic_body, which the host
+//     simulation runs too - this unit has no Fr arithmetic of its own;
 //   * bn254_tile_dev: one record repeated n times (the generator bases the scalars multiply).
 #include <cstdint>
 #include <mutex>
 
+#include "fr_ops.hpp"
 #include "host_ctx.hpp"
-#include "bn254_constants.hpp"
 
 namespace {
 
@@ -32,57 +33,10 @@ __global__ void __launch_bounds__(256) bn254_ubench_mad_k(uint32_t *out, uint32_
     if (s == 0x1234567) out[threadIdx.x] = (uint32_t)s;
 }
 
-// ---- Fr (8 x u32, Montgomery radix 2^256) just for the scalar generator: CIOS product, result < r
-__device__ void fr_mont_mul(const uint32_t *a, const uint32_t *b, uint32_t *out) {
-    using namespace bn254;
-    uint32_t t[10] = {};
-    for (int i = 0; i < 8; ++i) {
-        uint64_t c = 0;
-        for (int j = 0; j < 8; ++j) { uint64_t x = (uint64_t)a[j] * b[i] + t[j] + c; t[j] = (uint32_t)x; c = x >> 32; }
-        uint64_t x = (uint64_t)t[8] + c; t[8] = (uint32_t)x; t[9] = (uint32_t)(x >> 32);
-        uint32_t mq = t[0] * k::FR_INV32;
-        c = ((uint64_t)mq * k::FR_MOD32[0] + t[0]) >> 32;
-        for (int j = 1; j < 8; ++j) { uint64_t y = (uint64_t)mq * k::FR_MOD32[j] + t[j] + c; t[j - 1] = (uint32_t)y; c = y >> 32; }
-        x = (uint64_t)t[8] + c; t[7] = (uint32_t)x;
-        t[8] = t[9] + (uint32_t)(x >> 32);
-        t[9] = 0;
-    }
-    // t < 2r: one conditional subtraction
-    uint32_t d[8];
-    int64_t br = 0;
-    for (int i = 0; i < 8; ++i) { int64_t s = (int64_t)t[i] - (int64_t)k::FR_MOD32[i] + br; d[i] = (uint32_t)s; br = s >> 32; }
-    const bool ge = (t[8] != 0) || (br == 0);
-    for (int i = 0; i < 8; ++i) out[i] = ge ? d[i] : t[i];
-}
-__device__ uint64_t splitmix64_next(uint64_t &state) {
-    state += 0x9E3779B97F4A7C15ull;
-    uint64_t z = state;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 // out[j] = Montgomery image of (512-bit SplitMix64 draw of stream 2*(lo+j)+which) mod r   (bn_amd.distributed.synthetic_scalars)
 __global__ void __launch_bounds__(64) bn254_synthetic_scalars_k(uint64_t lo, uint32_t n, uint32_t which, uint64_t seed, uint32_t *out) {
-    using namespace bn254;
     const uint32_t j = blockIdx.x * 64 + threadIdx.x;
-    if (j >= n) return;
-    uint64_t state = seed + (((lo + j) * 2 + which) << 32);
-    uint32_t w[16];
-    for (int i = 0; i < 8; ++i) { uint64_t z = splitmix64_next(state); w[2 * i] = (uint32_t)z; w[2 * i + 1] = (uint32_t)(z >> 32); }
-    uint32_t r2[8], r3[8], a[8], b[8];
-    for (int i = 0; i < 8; ++i) r2[i] = k::FR_R2_32[i];
-    fr_mont_mul(r2, r2, r3);                    // R^3 mod r
-    fr_mont_mul(w, r2, a);                      // low half  * R     (operand < 2^256, result < r)
-    fr_mont_mul(w + 8, r3, b);                  // high half * R^2 = high * 2^256 * R
-    uint32_t s[9];
-    uint64_t c = 0;
-    for (int i = 0; i < 8; ++i) { uint64_t x = (uint64_t)a[i] + b[i] + c; s[i] = (uint32_t)x; c = x >> 32; }
-    s[8] = (uint32_t)c;
-    uint32_t d[8];
-    int64_t br = 0;
-    for (int i = 0; i < 8; ++i) { int64_t t = (int64_t)s[i] - (int64_t)k::FR_MOD32[i] + br; d[i] = (uint32_t)t; br = t >> 32; }
-    const bool ge = (s[8] != 0) || (br == 0);
-    for (int i = 0; i < 8; ++i) out[8u * j + i] = ge ? d[i] : s[i];
+    if (j < n) bn254::fr_synthetic_body(seed, lo, j, which, out);
 }
 // out[i] = src[0]  (tiles one point/record of `words` u32 over n records: the generator bases of the synthetic inputs)
 // GATHER: out[i] = src[index[i]] - record i of the output is record index[i] of the `records` source records, or all zero (for a point: z = 0,

@@ -10,6 +10,7 @@
 //   * the caller may normalize (x/z^2, y/z^3, 1) - the parity definition for `g*_mul_batch`.
 #pragma once
 #include "pairing.hpp"
+#include "fr.hpp"
 
 namespace bn254 {
 
@@ -284,40 +285,6 @@ BN_FN typename F::T table_to_common_z(const Jac<F> *tab, Tab &aff) {
 }
 template <class F>
 BN_FN Jac<F> jac_add(const Jac<F> &p, const Jac<F> &q) { return jac_add_flags(p, q, F::is_zero(p.z), F::is_zero(q.z)); }
-
-// Fr out of Montgomery form (fields/fp.rs:15-22: multiply by 1): 8 x u32 words, word-serial Montgomery reduction mod r
-BN_FN void fr_from_mont(const uint32_t *km, uint32_t *raw) {
-    uint32_t t[9];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t[i] = km[i];
-    t[8] = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        uint32_t m = t[0] * k::FR_INV32;
-        uint64_t c = ((uint64_t)m * k::FR_MOD32[0] + t[0]) >> 32;
-#pragma unroll
-        for (int j = 1; j < 8; ++j) {
-            uint64_t x = (uint64_t)m * k::FR_MOD32[j] + t[j] + c;
-            t[j - 1] = (uint32_t)x;
-            c = x >> 32;
-        }
-        uint64_t x = (uint64_t)t[8] + c;
-        t[7] = (uint32_t)x;
-        t[8] = (uint32_t)(x >> 32);
-    }
-    // t < 2r; one conditional subtraction
-    uint32_t d[8];
-    int64_t br = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        int64_t s = (int64_t)t[i] - (int64_t)k::FR_MOD32[i] + br;
-        d[i] = (uint32_t)s;
-        br = s >> 32;
-    }
-    bool ge = (t[8] != 0) || (br == 0);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) raw[i] = ge ? d[i] : t[i];
-}
 
 // groups/mod.rs:250-270: res = 0; for bits MSB->LSB { if found { res = 2 res }; if bit { found = true; res = res + p } }.
 // Per-lane scalars differ, so `found`/`bit` are per-lane predicates applied by selects; the op sequence each lane's result

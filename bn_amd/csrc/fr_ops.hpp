@@ -1,16 +1,15 @@
-// The per-lane bodies of the scalar-field kernels (bn254_fr.hip): bn254_fr_{add,mul,inverse,pow,interpret}_batch.  One Fr per lane as eight
-// u32 words in Montgomery radix 2^256 - the bytes of the C ABI, so nothing is converted on the way in or out - and every result canonical
-// (< r), hence unique: the bytes are the reference's whichever algorithm computes them (fields/fp.rs, arith.rs:183-279).  Everything here is
-// pure and takes plain pointers and an element (inverse: run) index, so the host simulation (tests/hostsim/hostsim_fr.cpp) runs the very same
-// bodies over host arrays.  The Fq machinery (fe.hpp's 29-bit limbs, generated for q) is not used: fe.hpp is included for BN_FN and k:: only.
+// The per-lane bodies of the scalar-field kernels (bn254_fr.hip): bn254_fr_{add,mul,inverse,pow,interpret}_batch, and of the generator of
+// the synthetic benchmark scalars (bn254_measure.hip).  One Fr per lane as eight u32 words in Montgomery radix 2^256 - the bytes of the C
+// ABI, so nothing is converted on the way in or out - and every result canonical (< r), hence unique: the bytes are the reference's whichever
+// algorithm computes them (fields/fp.rs, arith.rs:183-279).  The arithmetic itself is fr.hpp; here are the moves between memory and
+// registers, pow, and the bodies.  Everything is pure and takes plain pointers and an element (inverse: run) index, so the host simulation
+// (tests/hostsim/hostsim_fr.cpp) runs the very same bodies over host arrays.
 #pragma once
 #include <stddef.h>
-#include "fe.hpp"
+#include "fr.hpp"
 
 namespace bn254 {
 
-BN254_CONSTANT uint32_t FR_ONE_32[8] = {0x4ffffffbu, 0xac96341cu, 0x9f60cd29u, 0x36fc7695u, 0x7879462eu, 0x666ea36fu, 0x9a07df2fu, 0x0e0a77c1u};     // 2^256 mod r: Fr::one()
-BN254_CONSTANT uint32_t FR_R3_32[8] = {0xb4bf0040u, 0x5e94d8e1u, 0x1cfbb6b8u, 0x2a489cbeu, 0xa19fcfedu, 0x893cc664u, 0x7fcc657cu, 0x0cf8594bu};      // 2^768 mod r
 BN254_CONSTANT uint32_t FR_MINUS_2_32[8] = {0xefffffffu, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u}; // r - 2 (raw): the Fermat exponent
 constexpr int FR_BITS = 254;                 // bits of r: a canonical exponent has no bit above
 // The shipped choices (plain constants - the library has no compile switch for them; bn254_fr.hip carries a run-time override for the
@@ -18,21 +17,6 @@ constexpr int FR_BITS = 254;                 // bits of r: a canonical exponent 
 constexpr int FR_POW_WINDOW = 2;
 constexpr uint32_t FR_INV_RUN = 8;
 
-struct Fr { uint32_t w[8]; };
-
-BN_FN Fr fr_const(const uint32_t *c) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r.w[i] = c[i];
-    return r;
-}
-BN_FN Fr fr_zero() {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r.w[i] = 0u;
-    return r;
-}
-BN_FN Fr fr_one() { return fr_const(FR_ONE_32); }
 // record `i` of an array of 32-byte records, as two 16-byte moves
 BN_FN Fr fr_load(const uint32_t *p, size_t i) {
     Fr r;
@@ -52,87 +36,11 @@ BN_FN void fr_store(const Fr &a, uint32_t *p, size_t i) {
     ((uint4 *)p)[2 * i + 1] = make_uint4(a.w[4], a.w[5], a.w[6], a.w[7]);
 #endif
 }
-BN_FN bool fr_is_zero(const Fr &a) {
-    uint32_t o = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o |= a.w[i];
-    return o == 0;
-}
-BN_FN Fr fr_select(bool take_b, const Fr &a, const Fr &b) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r.w[i] = take_b ? b.w[i] : a.w[i];
-    return r;
-}
-// t (eight words and a carry word) -> t - r when t >= r.  For t < 2 r the result is canonical.
-BN_FN Fr fr_reduce_once(const uint32_t *t, uint32_t top) {
-    uint32_t d[8];
-    int64_t br = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int64_t v = (int64_t)t[i] - (int64_t)k::FR_MOD32[i] + br;
-        d[i] = (uint32_t)v; br = v >> 32;
-    }
-    const bool ge = top != 0 || br == 0;
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r.w[i] = ge ? d[i] : t[i];
-    return r;
-}
-// a + b mod r
-BN_FN Fr fr_add(const Fr &a, const Fr &b) {
-    uint32_t t[8];
-    uint64_t c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { c += (uint64_t)a.w[i] + b.w[i]; t[i] = (uint32_t)c; c >>= 32; }
-    return fr_reduce_once(t, (uint32_t)c);
-}
-// a - b mod r: r is added back when the difference borrows
-BN_FN Fr fr_sub(const Fr &a, const Fr &b) {
-    uint32_t t[8];
-    int64_t br = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { const int64_t v = (int64_t)a.w[i] - (int64_t)b.w[i] + br; t[i] = (uint32_t)v; br = v >> 32; }
-    const uint32_t mask = br ? 0xffffffffu : 0u;
-    Fr r;
-    uint64_t c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { c += (uint64_t)t[i] + (k::FR_MOD32[i] & mask); r.w[i] = (uint32_t)c; c >>= 32; }
-    return r;
-}
-// a * b / 2^256 mod r, word-serial (CIOS): per word of a, one row of eight products into t and one row of eight products m * r that
-// clears the low word - 128 multiply-adds of the shape (uint64_t)x * y + z, and eight low products for m.  One operand canonical (< r)
-// keeps t below 2 r, so the one conditional subtraction gives the canonical result; the other may be any 256-bit value.
-BN_FN Fr fr_mul(const Fr &a, const Fr &b) {
-    uint32_t t[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) t[i] = 0u;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        uint64_t c = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const uint64_t x = (uint64_t)a.w[i] * b.w[j] + t[j] + c;
-            t[j] = (uint32_t)x; c = x >> 32;
-        }
-        const uint64_t top = (uint64_t)t[8] + c;                          // < 2^33
-        const uint32_t m = t[0] * k::FR_INV32;
-        c = ((uint64_t)m * k::FR_MOD32[0] + t[0]) >> 32;
-#pragma unroll
-        for (int j = 1; j < 8; ++j) {
-            const uint64_t y = (uint64_t)m * k::FR_MOD32[j] + t[j] + c;
-            t[j - 1] = (uint32_t)y; c = y >> 32;
-        }
-        const uint64_t y = top + c;
-        t[7] = (uint32_t)y; t[8] = (uint32_t)(y >> 32);
-    }
-    return fr_reduce_once(t, t[8]);
-}
 // the canonical integer of a Montgomery image: a / 2^256 mod r
 BN_FN Fr fr_raw(const Fr &a) {
-    Fr one = fr_zero();
-    one.w[0] = 1u;
-    return fr_mul(a, one);
+    Fr r;
+    fr_from_mont(a.w, r.w);
+    return r;
 }
 // digit w (WB bits, WB divides 32) of the integer e
 template <int WB>
@@ -185,8 +93,7 @@ BN_FN void fr_pow_body(const uint32_t *a, const uint32_t *e, uint32_t *out, size
     const Fr x = fr_load(a, i), y = fr_raw(fr_load(e, i));
     fr_store(fr_pow_raw<WB>(x, y), out, i);
 }
-// lib.rs:27-29 over arith.rs:90-97: record i of 64 bytes as a big-endian 512-bit integer hi * 2^256 + lo, mod r.  lo * R^2 / R = lo * R and
-// hi * R^3 / R = (hi * 2^256) * R are both canonical (R^2, R^3 are), so their sum needs one subtraction.
+// lib.rs:27-29 over arith.rs:90-97: record i of 64 bytes as a big-endian 512-bit integer hi * 2^256 + lo, mod r
 BN_FN void fr_interpret_body(const uint8_t *in, uint32_t *out, size_t i) {
     Fr hi, lo;
 #if defined(BN_HOSTSIM)
@@ -202,7 +109,23 @@ BN_FN void fr_interpret_body(const uint8_t *in, uint32_t *out, size_t i) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) { hi.w[7 - j] = __builtin_bswap32(b[j]); lo.w[7 - j] = __builtin_bswap32(b[8 + j]); }
 #endif
-    fr_store(fr_add(fr_mul(lo, fr_const(k::FR_R2_32)), fr_mul(hi, fr_const(FR_R3_32))), out, i);
+    fr_store(fr_from_wide(lo, hi), out, i);
+}
+// element j of bn254_synthetic_scalars_dev: the 512-bit SplitMix64 draw of stream 2 * (lo + j) + which (eight outputs, least significant
+// first, each as two words), mod r - bn_amd.distributed.synthetic_scalars word for word
+BN_FN void fr_synthetic_body(uint64_t seed, uint64_t lo, uint32_t j, uint32_t which, uint32_t *out) {
+    uint64_t state = seed + (((lo + j) * 2 + which) << 32);
+    Fr half[2];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        state += 0x9E3779B97F4A7C15ull;
+        uint64_t z = state;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        z ^= z >> 31;
+        half[i >> 2].w[2 * (i & 3)] = (uint32_t)z; half[i >> 2].w[2 * (i & 3) + 1] = (uint32_t)(z >> 32);
+    }
+    fr_store(fr_from_wide(half[0], half[1]), out, j);
 }
 // Option<Fr> inverse of the run of K consecutive elements [lane * K, min(n, (lane + 1) * K)) with ONE exponentiation (Montgomery's trick):
 // forward, the product of the elements in front of each one (one in place of a zero element) goes to `prefix`; the run's product is raised

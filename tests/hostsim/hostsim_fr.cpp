@@ -1,4 +1,5 @@
-// TEST INFRASTRUCTURE - host simulation of the bodies of bn254_fr_{add,mul,inverse,pow,interpret}_batch (bn_amd/csrc/fr_ops.hpp) compiled
+// TEST INFRASTRUCTURE - host simulation of the bodies of bn254_fr_{add,mul,inverse,pow,interpret}_batch and of the synthetic-scalar generator
+// (bn_amd/csrc/fr_ops.hpp over the arithmetic of fr.hpp) compiled
 // with g++ for the CPU: the very code the kernels run, one loop over lanes per launch, over host arrays, for ANY run length K of the
 // inversion and every window width of pow the library carries.  Never loaded by the product (bn_amd/); not a CPU fallback.
 #define BN_HOSTSIM 1
@@ -28,6 +29,10 @@ EXPORT int hsf_pow(const uint32_t *a, const uint32_t *e, uint32_t n, uint32_t wb
 }
 EXPORT void hsf_interpret(const uint8_t *in, uint32_t n, uint32_t *out) {
     for (uint32_t i = 0; i < n; ++i) fr_interpret_body(in, out, i);
+}
+// one launch of bn254_synthetic_scalars_k: elements lo .. lo + n of stream `which`
+EXPORT void hsf_synthetic(uint64_t seed, uint64_t lo, uint32_t n, uint32_t which, uint32_t *out) {
+    for (uint32_t j = 0; j < n; ++j) fr_synthetic_body(seed, lo, j, which, out);
 }
 // runs of K: ceil(n / K) lanes and one more, which must retire; the prefix scratch holds exactly K * lanes records (std::vector::at would
 // throw past them) and is filled with a pattern no product can be; ok may be NULL

@@ -267,7 +267,7 @@ def test_sub_launches_with_small_rounds(oracle, eng):
 def test_decoders_at_the_modulus_limits(oracle, eng):
     """the batch decoders on coordinates at the exact limits - x or y = q - 1 (on the curve: the largest-x point, y = q - 1 on the point
     with y^2 = 1) against = q and the generator shifted by q; G2 coordinates q^2 - 1 (c1 = c0 = q - 1) against q^2 and a valid point
-    with a coordinate + q^2; Fr r - 1 against r - record by record, status and output equal to the oracle's"""
+    with a coordinate + q^2; Fr 0, 1, r - 2 and r - 1 against r, r + 1 and 2^256 - 1 - record by record, status and output equal to the oracle's"""
     Q, R = M.Q, M.R_ORD
     (xe, ye), (xe2, ye2) = E.edge_g1_affine()[2:]
     (x1, _), _ = E.g1_points_with_y_one()
@@ -290,10 +290,10 @@ def test_decoders_at_the_modulus_limits(oracle, eng):
         rc, want = oracle.g2_decode(rec)
         assert s2[i] == rc and np.array_equal(d2[i], want if rc == 0 else oracle.g2_zero()), (i, s2[i], rc)
     assert s2[0] == 0 and list(s2[3:7]) == [2, 2, 2, 2] and s2[1] != 2 and s2[2] != 2
-    fr = [R - 1, R, R + 1, (1 << 256) - 1, 0, R - 2]
+    fr = [R - 1, R, R + 1, (1 << 256) - 1, 0, R - 2, 1]
     b = np.stack([np.frombuffer(v.to_bytes(32, "big"), np.uint8) for v in fr])
     dk, sk = eng.fr_decode_batch(b)
     for i in range(len(fr)):
         rc, want = oracle.fr_decode(b[i])
         assert sk[i] == rc and np.array_equal(dk[i], want), (i, sk[i], rc)
-    assert list(sk) == [0, 1, 1, 1, 0, 0] and np.array_equal(dk[0], oracle.fp_from_int(FR, R - 1))
+    assert list(sk) == [0, 1, 1, 1, 0, 0, 0] and np.array_equal(dk[0], oracle.fp_from_int(FR, R - 1))

@@ -1,6 +1,7 @@
-"""The bodies of bn254_fr_{add,mul,inverse,pow,interpret}_batch (bn_amd/csrc/fr_ops.hpp) on the CPU: tests/hostsim/hostsim_fr.cpp runs the
-kernels' own code over host arrays, for every run length of the inversion and every window width of pow the library can be built with,
-against Python integers (tests/fr_cases.py).  The inputs are those of tests/test_gpu_fr.py at n <= 40."""
+"""The bodies of bn254_fr_{add,mul,inverse,pow,interpret}_batch and of the synthetic-scalar generator (bn_amd/csrc/fr_ops.hpp over fr.hpp) on
+the CPU: tests/hostsim/hostsim_fr.cpp runs the kernels' own code over host arrays, for every run length of the inversion and every window
+width of pow the library can be built with, against Python integers (tests/fr_cases.py).  The inputs are those of tests/test_gpu_fr.py at
+n <= 40."""
 import ctypes as C
 import pathlib
 import subprocess
@@ -121,3 +122,33 @@ def test_interpret_against_the_model(sim):
     sim.hsf_interpret(buf.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_uint32(N), _p(out))
     assert np.array_equal(out, FC.rows([v % FC.R for v in ints]))
     assert not out[0].any() and not out[2].any()                               # 0 and r are zero
+
+
+def _raw_rows(values):
+    """256-bit integers as they are (no reduction, no Montgomery form) -> (n, 4) uint64"""
+    return np.array([[(v >> (64 * j)) & ((1 << 64) - 1) for j in range(4)] for v in values], np.uint64)
+
+
+def test_mul_with_a_non_canonical_left_operand(sim):
+    """fr_mul's precondition (fr.hpp): ONE operand below r is enough, the other may be any 256-bit value - what wire decode of a rejected
+    record and both halves of fr_from_wide rely on.  a * b / 2^256 mod r from Python integers, canonical"""
+    left = [FC.R, FC.R + 1, 1 << 255, (1 << 256) - 1]
+    right = [0, 1, FC.MONT % FC.R, FC.MONT * FC.MONT % FC.R, FC.R - 1]
+    a = [x for x in left for _ in right]; b = [y for _ in left for y in right]
+    n = len(a)
+    out = np.full((n, 4), 0x5a5a5a5a5a5a5a5a, np.uint64)
+    sim.hsf_mul(_p(_raw_rows(a)), _p(_raw_rows(b)), C.c_uint32(n), _p(out))
+    inv = pow(FC.MONT, -1, FC.R)
+    want = _raw_rows([x * y * inv % FC.R for x, y in zip(a, b)])
+    assert np.array_equal(out, want), np.nonzero((out != want).any(axis=1))[0]
+
+
+@pytest.mark.parametrize("which", [0, 1])
+def test_synthetic_scalars_equal_the_numpy_generator(sim, which):
+    """fr_synthetic_body (the body of bn254_synthetic_scalars_k) == bn_amd.distributed.synthetic_scalars word for word"""
+    from bn_amd import distributed as D
+    for lo, hi in ((0, 40), (1 << 24, (1 << 24) + 40), ((1 << 25) - 3, (1 << 25) + 3)):
+        out = np.full((hi - lo, 4), 0x5a5a5a5a5a5a5a5a, np.uint64)
+        sim.hsf_synthetic(C.c_uint64(D.SEED), C.c_uint64(lo), C.c_uint32(hi - lo), C.c_uint32(which), _p(out))
+        want = D.synthetic_scalars(lo, hi, which)
+        assert np.array_equal(out, want), (which, lo, np.nonzero((out != want).any(axis=1))[0])
