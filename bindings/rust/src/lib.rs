@@ -91,11 +91,14 @@ extern "C" {
     fn bn254_fr_inverse_batch(ctx: *mut c_void, a: *const Fr, out: *mut Fr, ok: *mut i32, n: usize) -> c_int;
     fn bn254_fr_pow_batch(ctx: *mut c_void, a: *const Fr, e: *const Fr, out: *mut Fr, n: usize) -> c_int;
     fn bn254_fr_interpret_batch(ctx: *mut c_void, bytes: *const u8, out: *mut Fr, n: usize) -> c_int;
+    fn bn254_fr_root_of_unity(log_n: c_int, out: *mut Fr) -> c_int;
+    fn bn254_fr_ntt_batch(ctx: *mut c_void, input: *const Fr, out: *mut Fr, log_n: c_int, count: usize, inverse: c_int, shift: *const Fr) -> c_int;
     fn bn254_fr_add_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_out: *mut c_void, n: usize, negate_b: c_int, stream: *mut c_void) -> c_int;
     fn bn254_fr_mul_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_inverse_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_out: *mut c_void, d_ok: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_pow_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_e: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_interpret_batch_dev(ctx: *mut c_void, d_in: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_fr_ntt_batch_dev(ctx: *mut c_void, d_in: *const c_void, d_out: *mut c_void, log_n: c_int, count: usize, inverse: c_int, shift: *const Fr, stream: *mut c_void) -> c_int;
 }
 
 /// One line-function coefficient of a prepared G2 point: the crate's `EllCoeffs { ell_0, ell_vw, ell_vv: Fq2 }` (src/groups/mod.rs:472-476) as the
@@ -319,6 +322,23 @@ pub fn fr_pow(a: &[Fr], e: &[Fr]) -> Result<Vec<Fr>, GpuError> {
 pub fn fr_interpret(bufs: &[[u8; 64]]) -> Result<Vec<Fr>, GpuError> {
     let mut out = vec![Fr::zero(); bufs.len()];
     check(unsafe { bn254_fr_interpret_batch(std::ptr::null_mut(), bufs.as_ptr() as *const u8, out.as_mut_ptr(), bufs.len()) })?;
+    Ok(out)
+}
+
+/// `w_n` for `n = 2^log_n` (0..=28): `w_28^(2^(28 - log_n))` with `w_28 = 5^((r-1)/2^28)`, ark-bn254's root.  Host only.
+pub fn fr_root_of_unity(log_n: u32) -> Result<Fr, GpuError> {
+    let mut out = Fr::zero();
+    check(unsafe { bn254_fr_root_of_unity(log_n as c_int, &mut out) })?;
+    Ok(out)
+}
+
+/// `values.len() / 2^log_n` number-theoretic transforms of `2^log_n` elements each, natural order in and out.  Forward: the polynomial with
+/// coefficients `values` evaluated at `shift * w_n^k`; inverse: the coefficients back from such evaluations.  `shift`: `None` for one.
+pub fn fr_ntt(values: &[Fr], log_n: u32, inverse: bool, shift: Option<&Fr>) -> Result<Vec<Fr>, GpuError> {
+    assert!(log_n <= 24 && values.len() % (1usize << log_n) == 0);
+    let mut out = vec![Fr::zero(); values.len()];
+    let sh = shift.map_or(std::ptr::null(), |s| s as *const Fr);
+    check(unsafe { bn254_fr_ntt_batch(std::ptr::null_mut(), values.as_ptr(), out.as_mut_ptr(), log_n as c_int, values.len() >> log_n, inverse as c_int, sh) })?;
     Ok(out)
 }
 

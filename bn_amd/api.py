@@ -59,6 +59,11 @@ class Fr:
             raise ValueError("Fr.interpret takes exactly 64 bytes")
         return Fr(int.from_bytes(buf, "big"))
     @staticmethod
+    def root_of_unity(log_n):             # w_n for n = 2^log_n: w_28^(2^(28 - log_n)), w_28 = 5^((r-1)/2^28) - ark-bn254's root; the domains nest
+        if not 0 <= log_n <= 28:
+            raise ValueError("r - 1 is divisible by 2^28 and no higher power of two")
+        return Fr(pow(5, (R_MOD - 1) >> log_n, R_MOD))
+    @staticmethod
     def from_limbs(l):
         return Fr(sum(int(x) << (64 * i) for i, x in enumerate(l)) * pow(_MONT, -1, R_MOD))
     @property
@@ -373,6 +378,47 @@ def fr_interpret_batch(bufs, engine=None):
             raise ValueError("Fr.interpret takes exactly 64 bytes")
         bufs = np.frombuffer(b"".join(bufs), np.uint8).reshape(-1, 64)
     return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_interpret_batch(bufs)]
+
+
+def _shift_limbs(shift):
+    if shift is None:
+        return None
+    shift = shift if isinstance(shift, Fr) else Fr(shift)
+    if shift.is_zero():
+        raise ValueError("the coset shift must be non-zero")
+    return shift.limbs
+
+
+def fr_ntt_batch(rows, inverse=False, shift=None, engine=None):
+    """one transform per row, all in ONE call: rows is a sequence of equally long sequences of Fr (length n a power of two) or a (count, n, 4)
+    uint64 array.  See fr_ntt."""
+    if isinstance(rows, np.ndarray):
+        if rows.ndim != 3 or rows.shape[2] != 4:
+            raise ValueError("an array of transforms is (count, n, 4) uint64")
+        count, n = rows.shape[0], rows.shape[1]
+        flat = np.asarray(rows, np.uint64).reshape(-1, 4)
+    else:
+        rows = [r if isinstance(r, np.ndarray) else list(r) for r in rows]
+        count, n = len(rows), (len(rows[0]) if rows else 1)
+        if any(len(r) != n for r in rows):
+            raise ValueError("every transform of a batch has the same length")
+        flat = np.concatenate([_scalar_array(r) for r in rows]) if rows else np.zeros((0, 4), np.uint64)
+    if n < 1 or n & (n - 1):
+        raise ValueError(f"the length of a transform must be a power of two, got {n}")
+    sh = _shift_limbs(shift)
+    if count == 0:
+        return []
+    out = (engine or default_engine()).fr_ntt_batch(flat, n.bit_length() - 1, inverse, sh)
+    return [[Fr.from_limbs(r) for r in out[t * n:(t + 1) * n]] for t in range(count)]
+
+
+def fr_ntt(values, inverse=False, shift=None, engine=None):
+    """The number-theoretic transform of `values` (a sequence of Fr or an (n,4) uint64 array; n = 2^log_n, else ValueError) over the subgroup
+    generated by w = Fr.root_of_unity(log_n), natural order in and out -> list of Fr.  Forward: out[k] = sum_j values[j] (shift w^k)^j, the
+    polynomial with these coefficients evaluated on the coset shift * H; inverse: out[j] = shift^-j n^-1 sum_k values[k] w^(-j k), the
+    coefficients back from such evaluations.  shift: an Fr or an integer, None for 1."""
+    A = _scalar_array(values)
+    return fr_ntt_batch(A.reshape(1, -1, 4), inverse, shift, engine)[0]
 
 
 class PreparedG2:

@@ -122,6 +122,11 @@ struct bn254_ctx {
     BnBaseCache base_cache[2];          // bn254_g{1,2}_mul_base_batch: [0] G1, [1] G2
     BnBuf norm_prefix;                  // bn254_g{1,2}_normalize_batch: the prefix products of one sub-launch (48 / 96 bytes per point)
     BnBuf fr_prefix;                    // bn254_fr_inverse_batch: the prefix products of one sub-launch (32 bytes per element)
+    BnBuf ntt_tbl;                      // bn254_fr_ntt_batch: two table pairs of 2 * 2^12 Fr (ntt_ops.hpp) - the powers of w_24, built once, ...
+    bool ntt_root_ready = false;
+    uint64_t ntt_shift_key[5] = {};     // ... and the powers of the coset shift the second pair was built for (forward: the shift; inverse: shift and size)
+    bool ntt_shift_valid = false;
+    BnBuf ntt_ws;                       // the arrays between the passes of one group of transforms (one, or two for an odd number of passes in place)
     BnBuf base_stage;                   // the base of a table build on the device ...
     BnBuf base_stage_host{nullptr, 0, true};    // ... and its pinned staging, rewritten only after base_stage_ev (its last copy) completed
     hipEvent_t base_stage_ev = nullptr;

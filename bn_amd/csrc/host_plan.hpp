@@ -251,3 +251,114 @@ inline void base_table_scalars(unsigned cb, std::vector<uint64_t> &h) {
         for (unsigned b = 0; b < cb; ++b) bn_fr_add(pw.l, pw.l, pw.l);
     }
 }
+
+// ---- number-theoretic transforms over Fr (bn254_fr_ntt_batch): the handful of field operations the HOST needs per call - the root of a size,
+// the inverse of the coset shift, n^-1 - as Montgomery images, and the cut of a transform into passes
+constexpr uint64_t BN_FR_INV64 = 0xc2e1f593efffffffull;                // -r^-1 mod 2^64
+// the Montgomery image of w_28 = 5^((r-1)/2^28) = 19103219067921713944291392827692070036145651957329286315305642004821462161904 (ark-bn254's root)
+constexpr uint64_t BN_FR_ROOT28[4] = {0x636e735580d13d9cull, 0xa22bf3742445ffd6ull, 0x56452ac01eb203d8ull, 0x1860ef942963f9e7ull};
+constexpr uint64_t BN_FR_MINUS_2[4] = {0x43e1f593efffffffull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};   // r - 2 (raw)
+constexpr int BN_NTT_ROOT_LOG = 28;
+// out = a * b / 2^256 mod r for a canonical b (a: any four words), word-serial like fr.hpp's fr_mul; out may be a or b
+inline void bn_fr_mul(const uint64_t *a, const uint64_t *b, uint64_t *out) {
+    uint64_t t[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 4; ++i) {
+        unsigned __int128 c = 0;
+        for (int j = 0; j < 4; ++j) { c += (unsigned __int128)a[i] * b[j] + t[j]; t[j] = (uint64_t)c; c >>= 64; }
+        c += t[4]; t[4] = (uint64_t)c; t[5] = (uint64_t)(c >> 64);
+        const uint64_t m = t[0] * BN_FR_INV64;
+        c = ((unsigned __int128)m * BN_FR_MOD64[0] + t[0]) >> 64;
+        for (int j = 1; j < 4; ++j) { c += (unsigned __int128)m * BN_FR_MOD64[j] + t[j]; t[j - 1] = (uint64_t)c; c >>= 64; }
+        c += t[4]; t[3] = (uint64_t)c; t[4] = t[5] + (uint64_t)(c >> 64);
+    }
+    uint64_t d[4];
+    unsigned __int128 br = 0;
+    for (int i = 0; i < 4; ++i) { const unsigned __int128 x = (unsigned __int128)t[i] - BN_FR_MOD64[i] - br; d[i] = (uint64_t)x; br = (x >> 64) & 1; }
+    const bool ge = t[4] != 0 || br == 0;
+    for (int i = 0; i < 4; ++i) out[i] = ge ? d[i] : t[i];
+}
+// out = a^e for the 256-bit integer e (four words, least significant first)
+inline void bn_fr_pow(const uint64_t *a, const uint64_t *e, uint64_t *out) {
+    bn_fr acc; bn_fr_one(&acc);
+    for (int bit = 255; bit >= 0; --bit) {
+        bn_fr_mul(acc.l, acc.l, acc.l);
+        if ((e[bit >> 6] >> (bit & 63)) & 1) bn_fr_mul(acc.l, a, acc.l);
+    }
+    memcpy(out, acc.l, sizeof acc.l);
+}
+inline void bn_fr_inverse(const uint64_t *a, uint64_t *out) { bn_fr_pow(a, BN_FR_MINUS_2, out); }
+// 2^-k as a Montgomery image: the n^-1 of an inverse transform of n = 2^k elements
+constexpr uint64_t BN_FR_HALF[4] = {0x783c14d81ffffffeull, 0xaf982f6f0c8d1eddull, 0x8f5f7492fcfd4f45ull, 0x1f37631a3d9cbfacull};   // (r + 1) / 2
+inline void bn_fr_inv_pow2(unsigned k, bn_fr *out) {
+    bn_fr_one(out);
+    for (unsigned i = 0; i < k; ++i) bn_fr_mul(out->l, BN_FR_HALF, out->l);
+}
+inline bool bn_fr_is_zero(const uint64_t *a) { return (a[0] | a[1] | a[2] | a[3]) == 0; }
+// w_n for n = 2^log_n: w_28^(2^(28 - log_n)), so the domains of all sizes nest
+inline int bn_fr_root(int log_n, bn_fr *out) {
+    if (log_n < 0 || log_n > BN_NTT_ROOT_LOG || !out) return BN254_E_BAD_ARG;
+    memcpy(out->l, BN_FR_ROOT28, sizeof out->l);
+    for (int i = log_n; i < BN_NTT_ROOT_LOG; ++i) bn_fr_mul(out->l, out->l, out->l);
+    return BN254_OK;
+}
+// A transform of n = 2^log_n over tiles of 2^T elements is P = ceil(log_n / T) passes (one for log_n == 0) of t_0 >= t_1 >= .. radix-2 stages
+// with t_0 + .. = log_n, as even as they come.  Pass i is the step of a Stockham autosort that splits the current length n_i = 2^(log_m + t)
+// into 2^t sub-transforms of length 2^log_m each, the data already interleaved at stride 2^log_s: log_s + t + log_m = log_n.
+struct BnNttPass { unsigned t, log_m, log_s; };
+constexpr unsigned BN_NTT_PASSES_MAX = 24;
+inline unsigned bn_ntt_plan(unsigned log_n, unsigned T, BnNttPass *pass) {
+    const unsigned P = log_n ? (log_n + T - 1) / T : 1, base = log_n / P, rem = log_n % P;
+    unsigned done = 0;
+    for (unsigned i = 0; i < P; ++i) {
+        const unsigned t = base + (i < rem ? 1u : 0u);
+        pass[i] = BnNttPass{t, log_n - done - t, done};
+        done += t;
+    }
+    return P;
+}
+// The launches of a call: groups of whole transforms of at most `step` elements (a larger transform is a group of its own); per group the
+// passes one after the other, each as sub-launches of at most `step` elements cut between small transforms (whole workgroups of
+// C = 2^(T - t) of them where a sub-launch holds that many).  A pass reads one array and writes another: the last writes OUT, the ones before
+// alternate between WS0 and OUT, and pass 0 reads IN - so an odd number (> 1) of passes in place would have pass 0 write what it still
+// reads, and writes WS1 instead.  A single pass is in place by construction (a workgroup reads all of its transforms before it writes).
+enum BnNttBuf { BN_NTT_IN, BN_NTT_OUT, BN_NTT_WS0, BN_NTT_WS1 };
+struct BnNttRun {
+    unsigned P; BnNttPass pass[BN_NTT_PASSES_MAX];
+    size_t per_group;                   // transforms per group
+    size_t most;                        // elements of the largest group: the size of one workspace array
+    unsigned ws_bufs;                   // workspace arrays of `most` elements the call needs: 0, 1 or 2
+};
+inline BnNttRun bn_ntt_run(unsigned log_n, unsigned T, size_t count, size_t step, bool in_place) {
+    BnNttRun r;
+    r.P = bn_ntt_plan(log_n, T, r.pass);
+    r.per_group = std::max<size_t>(1, step >> log_n);
+    r.most = std::min(count, r.per_group) << log_n;
+    r.ws_bufs = r.P < 2 ? 0u : (in_place && (r.P & 1) ? 2u : 1u);
+    return r;
+}
+// one sub-launch: pass `i` of the group over small transforms [lo, lo + n) in `blocks` workgroups; pre: inputs times the shift's powers
+// (forward coset, first pass); post: last pass of an inverse - 1 outputs times n^-1, 2 times n^-1 s^-index
+struct BnNttStep { unsigned i; BnNttPass g; BnNttBuf src, dst; unsigned pre, post; size_t lo, n, blocks; };
+// the sub-launches of one group of `cnt` transforms, in order: fn(step) enqueues one
+template <class Fn>
+int bn_ntt_group(const BnNttRun &r, unsigned log_n, unsigned T, size_t cnt, size_t step, bool in_place, bool shift, bool inverse, Fn fn) {
+    BnNttBuf src = BN_NTT_IN;
+    for (unsigned i = 0; i < r.P; ++i) {
+        BnNttStep s;
+        s.i = i; s.g = r.pass[i]; s.src = src;
+        s.dst = ((r.P - 1 - i) & 1) ? BN_NTT_WS0 : BN_NTT_OUT;
+        if (i == 0 && r.P > 1 && s.dst == BN_NTT_OUT && in_place) s.dst = BN_NTT_WS1;
+        s.pre = (i == 0 && shift && !inverse) ? 1u : 0u;
+        s.post = (i == r.P - 1 && inverse) ? (shift ? 2u : 1u) : 0u;
+        const size_t tiles = cnt << (log_n - s.g.t), C = (size_t)1 << (T - s.g.t);
+        size_t per_launch = std::max<size_t>(1, step >> s.g.t);
+        if (per_launch >= C) per_launch -= per_launch % C;
+        const int rc = bn_for_parts(tiles, per_launch, [&](size_t lo, size_t n) -> int {
+            s.lo = lo; s.n = n; s.blocks = (n + C - 1) / C;
+            return fn(s);
+        });
+        if (rc) return rc;
+        src = s.dst;
+    }
+    return BN254_OK;
+}

@@ -27,6 +27,26 @@ def _same_len(a, b):
         raise ValueError(f"operands differ in length: {a.shape[0]} vs {b.shape[0]}")
 
 
+def _ntt_count(rows, log_n):
+    """transforms in an array of `rows` elements"""
+    if not 0 <= log_n <= 24:
+        raise ValueError(f"log_n must be 0..24, got {log_n}")
+    if rows % (1 << log_n):
+        raise ValueError(f"{rows} elements are not whole transforms of 2^{log_n}")
+    return rows >> log_n
+
+
+def _ntt_shift(shift):
+    """the coset shift as one C-contiguous scalar of 4 uint64 words, or None (NULL).  The CALLER keeps the returned array alive for the length
+    of the C call and takes its address there: a converted copy (a list, another dtype, a strided view) belongs to nobody else"""
+    if shift is None:
+        return None
+    shift = np.ascontiguousarray(shift, dtype=np.uint64).reshape(-1)
+    if shift.size != 4:
+        raise ValueError(f"shift must be ONE scalar of 4 uint64 words, got {shift.size}")
+    return shift
+
+
 def _offsets(offsets):
     """CSR segment offsets as a C-contiguous size_t array (the C ABI checks their order and start)"""
     o = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
@@ -257,6 +277,17 @@ class Engine:
         b = np.ascontiguousarray(buf, np.uint8).reshape(-1, 64)
         out = np.empty((b.shape[0], 4), np.uint64)
         _native.check(self._lib.bn254_fr_interpret_batch(self._h, _p(b), _p(out), b.shape[0]))
+        return out
+
+    def fr_ntt_batch(self, a, log_n, inverse=False, shift=None):
+        """len(a) / 2^log_n number-theoretic transforms of 2^log_n elements each, natural order in and out -> (len(a), 4) uint64.  Forward:
+        the polynomial with coefficients a evaluated at shift * w^k; inverse: back to the coefficients.  shift: ONE scalar (4 uint64 words,
+        non-zero) or None for 1 (include/bn254_hip.h bn254_fr_ntt_batch)"""
+        a = _arr(a, 4) if len(a) else np.zeros((0, 4), np.uint64)
+        count = _ntt_count(a.shape[0], log_n)
+        out = np.empty_like(a)
+        shift = _ntt_shift(shift)                                  # held here until the call has returned
+        _native.check(self._lib.bn254_fr_ntt_batch(self._h, _p(a), _p(out), log_n, count, 1 if inverse else 0, None if shift is None else _p(shift)))
         return out
 
     def g1_msm_batch(self, p, k, offsets):
@@ -513,6 +544,12 @@ class Engine:
     def fr_interpret_batch_dev(self, d_in, d_out, n, stream=0):
         """d_in: 64 n bytes, d_out: n records"""
         _native.check(self._lib.bn254_fr_interpret_batch_dev(self._h, d_in, d_out, n, stream))
+
+    def fr_ntt_batch_dev(self, d_in, d_out, log_n, count, inverse=False, shift=None, stream=0):
+        """device pointers in, out (count * 2^log_n records of 32 bytes; out may be in), ordered on `stream`; `shift` is a HOST scalar (4 uint64
+        words) or None, read before the call returns"""
+        shift = _ntt_shift(shift)                                  # held here until the call has returned (it reads the shift before it does)
+        _native.check(self._lib.bn254_fr_ntt_batch_dev(self._h, d_in, d_out, log_n, count, 1 if inverse else 0, None if shift is None else _p(shift), stream))
 
     def g1_mul_base_batch_dev(self, base, d_k, d_out, n, stream=0):
         """`base` is a HOST point (12 uint64 words), read before the call returns; d_k, d_out device pointers (n records), ordered on `stream`"""

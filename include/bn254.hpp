@@ -189,6 +189,21 @@ inline std::vector<Fr> fr_interpret(const std::vector<std::array<uint8_t, 64>> &
     check(bn254_fr_interpret_batch(nullptr, reinterpret_cast<const uint8_t *>(bufs.data()), reinterpret_cast<bn_fr *>(out.data()), bufs.size()));
     return out;
 }
+// w_n for n = 2^log_n (0..28): w_28^(2^(28 - log_n)), w_28 = 5^((r-1)/2^28); computed on the host
+inline Fr fr_root_of_unity(int log_n) {
+    Fr out;
+    check(bn254_fr_root_of_unity(log_n, reinterpret_cast<bn_fr *>(&out)));
+    return out;
+}
+// values.size() / 2^log_n number-theoretic transforms of 2^log_n elements each, natural order in and out.  Forward: the polynomial with
+// coefficients `values` evaluated at shift * w_n^k; inverse: the coefficients back from such evaluations.  shift: nullptr for one.
+inline std::vector<Fr> fr_ntt(const std::vector<Fr> &values, int log_n, bool inverse = false, const Fr *shift = nullptr) {
+    if (log_n < 0 || log_n > BN254_NTT_LOG_MAX || values.size() % (size_t(1) << log_n)) throw std::invalid_argument("fr_ntt: not whole transforms of 2^log_n");
+    std::vector<Fr> out(values.size());
+    check(bn254_fr_ntt_batch(nullptr, reinterpret_cast<const bn_fr *>(values.data()), reinterpret_cast<bn_fr *>(out.data()), log_n, values.size() >> log_n, inverse ? 1 : 0,
+                             reinterpret_cast<const bn_fr *>(shift)));
+    return out;
+}
 // out[i] = (a[i] == b[i]) as group elements, whatever their Jacobian representations (groups/mod.rs:83-109): nothing is normalized
 inline std::vector<bool> g1_eq(const std::vector<G1> &a, const std::vector<G1> &b) {
     if (a.size() != b.size()) throw std::invalid_argument("g1_eq: length mismatch");

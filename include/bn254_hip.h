@@ -37,6 +37,9 @@
  *   bn254_fr_interpret_batch  out[i] = Fr::interpret(&in[64 i .. 64 i + 64])             lib.rs:27-29, fields/fp.rs:72-74, arith.rs:90-97
  *   bn254_fr_add_batch_dev / bn254_fr_mul_batch_dev / bn254_fr_inverse_batch_dev / bn254_fr_pow_batch_dev / bn254_fr_interpret_batch_dev
  *                          the same five on device-resident arrays, asynchronous on the caller's stream
+ *   bn254_fr_ntt_batch     out[t n + k] = sum_j in[t n + j] s^j w_n^(j k), or the inverse map: the polynomial <-> its evaluations over the subgroup of
+ *                          order n = 2^log_n (on the coset s H); no counterpart in the reference - the convention is ark-bn254's root of unity
+ *   bn254_fr_ntt_batch_dev the same on device-resident arrays, asynchronous on the caller's stream; bn254_fr_root_of_unity  w_n, on the host
  *   bn254_g2_precompute    coeffs[i][0..102) = q[i].to_affine().precompute().coeffs   groups/mod.rs:557-588 (Q != infinity)
  *   bn254_pairing_prepared_batch  out[i] = final_exponentiation(prepared.miller_loop(p[i]))   groups/mod.rs:486-519,768
  *   bn254_gt_mul_batch     out[i] = a[i] * b[i]                                     lib.rs:175-179, fields/fq12.rs:295-307
@@ -72,6 +75,8 @@
      staging, launches, copy back).
      bn254_g{1,2}_normalize_batch and bn254_g{1,2}_eq_batch serialise on the context in the same way (its mutex for the call).
      bn254_fr_{add,mul,inverse,pow,interpret}_batch serialise on the context in the same way (its mutex for the whole call).
+     bn254_fr_ntt_batch serialises on the context in the same way (its mutex for the whole call); bn254_fr_root_of_unity touches no
+     context and no device.
  *     bn254_pairing_product_batch_prepared_native serialises on the context like them; its handle is immutable and shared freely.
  *     Use one context per thread (or bn254_multi_*) for more overlap;
  *     bn254_ctx_set_option is atomic, but set options before concurrent use: a call in flight may run some
@@ -93,6 +98,9 @@
      bn254_g{1,2}_eq_batch_dev use no scratch.  Neither reads anything back nor waits on the host.
      bn254_fr_inverse_batch_dev keeps the prefix products of a sub-launch in context-owned scratch under the same event ordering;
      bn254_fr_{add,mul,pow,interpret}_batch_dev use no scratch.  None of the five waits on anything or reads anything back.
+     bn254_fr_ntt_batch_dev keeps its twiddle tables and the arrays between its passes in context-owned scratch under the same event
+     ordering: a table is built, rebuilt (the shift's) and read only by a stream that has waited for the last launch that may read it.  It
+     reads its HOST `shift` before it returns (the few field operations on it run on the host), waits on nothing and reads nothing back.
  */
 #ifndef BN254_HIP_H
 #define BN254_HIP_H
@@ -383,6 +391,40 @@ int bn254_fr_mul_batch(bn254_ctx *ctx, const bn_fr *a, const bn_fr *b, bn_fr *ou
 int bn254_fr_inverse_batch(bn254_ctx *ctx, const bn_fr *a, bn_fr *out, int32_t *ok, size_t n);
 int bn254_fr_pow_batch(bn254_ctx *ctx, const bn_fr *a, const bn_fr *e, bn_fr *out, size_t n);
 int bn254_fr_interpret_batch(bn254_ctx *ctx, const uint8_t *in, bn_fr *out, size_t n);
+/* Number-theoretic transforms over Fr: `count` transforms of n = 2^log_n elements each (log_n 0 .. BN254_NTT_LOG_MAX), transform t in
+   records [t n, (t + 1) n), natural order in and out - what moves a polynomial between its coefficients and its evaluations over the
+   subgroup H of order n of Fr*, plain and on a coset: the quotient (a b - c) / Z_H of a Groth16 prover, the inverse transform in front of
+   a KZG / PLONK commitment by bn254_g1_msm.
+   Root: w_n = w_28^(2^(28 - log_n)) with w_28 = 5^((r-1)/2^28) = 19103219067921713944291392827692070036145651957329286315305642004821462161904
+   (r - 1 is divisible by 2^28; 5 is a quadratic non-residue, so w_28^(2^27) = r - 1) - the convention of arkworks' ark-bn254.  Every size
+   uses this ONE root, so the domains of different sizes nest.  bn254_fr_root_of_unity writes w_n as a Montgomery image (log_n 0 .. 28;
+   host only: it touches no context and no device).
+   forward (inverse == 0):  out[t n + k] = sum_j in[t n + j] s^j w_n^(j k)              - the polynomial with coefficients `in` at s w_n^k
+   inverse (inverse != 0):  out[t n + j] = s^-j n^-1 sum_k in[t n + k] w_n^(-j k)       - the coefficients back from such evaluations
+   s is the coset shift: `shift` is ONE element in HOST memory in both forms, read before the call returns (like `base` of
+   bn254_g1_mul_base_batch_dev), NULL for s = 1.  Inputs are canonical Montgomery images; every output is canonical, hence unique, hence
+   independent of the algorithm.  `out` may be exactly `in` (partial overlap is outside the contract).
+   How: a transform is ceil(log_n / T) passes over global memory with T = 9: a workgroup of 256 lanes holds a tile of 2^T elements (16 KiB)
+   in LDS, beside the up to 2^(T-1) stage twiddles of its pass (8 KiB), and runs up to T radix-2 stages on it.  A pass is a step of a Stockham autosort, so no pass reverses bits in global memory; the
+   stages of a transform are split evenly over its passes (2^20: 7 + 7 + 6, 2^24: 8 + 8 + 8), and a tile of a pass of t < T stages is 2^(T - t) small
+   transforms whose rows are runs of adjacent records.  The coset powers and n^-1 are folded into the first and the last pass.  Twiddles
+   are factored: w_24^i and w_24^(2^12 i) for i < 2^12 serve every size and both directions (a stage's twiddle is one load - a workgroup copies those of its pass to LDS once -; the twiddle
+   between two passes is two loads and one product more per element), and a second pair of the same shape holds the powers of the last
+   shift used (rebuilt when the shift changes, or - for an inverse transform, whose pair carries n^-1 - the size or the direction).  Both are built on the device on first use and kept: 512 KiB per context.
+   A transform of more than one pass also keeps one array of the size of a group of transforms (up to 2^22 elements, or one larger
+   transform: 512 MB at 2^24) per context, two for an odd number of passes in place.  A full table of 16 n bytes was not built or measured.
+   Measured on an MI355X (tools/time_ntt.py; the full table is profiles/r14_ntt.txt): one forward transform of 2^20 takes 0.255 ms of
+   kernel time and one of 2^24 4.0 ms, about 6 x the device-to-device copies of their passes and 3 - 4 x the time of their Montgomery
+   products at the measured multiply-add rate, so neither floor is near.  Tile logs 8 / 9 / 10 / 11 take 0.286 / 0.256 / 0.262 / 0.252 ms
+   at 2^20 and 4.33 / 3.76 / 3.75 / 4.24 ms at 2^24.  By the rule that the fastest at 2^20 ships it would be 11 (1.4 % ahead of 9); 9 ships
+   instead, because 11 is 13 % slower at 2^24 and needs 80 KiB of LDS per workgroup, more than a kernel gets without asking for it.
+   Errors (BN254_E_BAD_ARG, checked before any device is touched): log_n < 0 or > BN254_NTT_LOG_MAX (> 28 for bn254_fr_root_of_unity), a
+   NULL `in` or `out` with count > 0 (a NULL `out` of bn254_fr_root_of_unity), count 2^log_n > 2^40, a `shift` that is Fr::zero().
+   count == 0 returns BN254_OK and writes nothing.  Calls run as sub-launches of at most 2^22 elements.  Threading: see above - the
+   host-buffer entry point holds the context's mutex for the whole call. */
+#define BN254_NTT_LOG_MAX 24
+int bn254_fr_root_of_unity(int log_n, bn_fr *out);
+int bn254_fr_ntt_batch(bn254_ctx *ctx, const bn_fr *in, bn_fr *out, int log_n, size_t count, int inverse, const bn_fr *shift);
 
 /* ---- one node, several GPUs (north_star: independent batches shard across the GPUs; ONE exchange for the multi-pairing) --- */
 /* `devices[0..ndev)`: HIP device index of every rank (NULL = 0..ndev-1).  One context and one host thread per rank.  A device may
@@ -528,6 +570,10 @@ int bn254_fr_mul_batch_dev(bn254_ctx *ctx, const void *d_a, const void *d_b, voi
 int bn254_fr_inverse_batch_dev(bn254_ctx *ctx, const void *d_a, void *d_out, void *d_ok, size_t n, void *stream);
 int bn254_fr_pow_batch_dev(bn254_ctx *ctx, const void *d_a, const void *d_e, void *d_out, size_t n, void *stream);
 int bn254_fr_interpret_batch_dev(bn254_ctx *ctx, const void *d_in, void *d_out, size_t n, void *stream);
+/* bn254_fr_ntt_batch on device-resident arrays (count 2^log_n records of 32 bytes, 16-byte aligned), asynchronous on `stream`; d_out may
+   be exactly d_in; `shift` is HOST memory (one element or NULL), read before the call returns.  Tables and the arrays between the passes
+   are context-owned scratch (see Threading). */
+int bn254_fr_ntt_batch_dev(bn254_ctx *ctx, const void *d_in, void *d_out, int log_n, size_t count, int inverse, const bn_fr *shift, void *stream);
 /* raw Jacobian result of the reference's MSB-first double-and-add (what G::random produces, groups/mod.rs:220-222):
    used to generate benchmark inputs with z != 1 on the device */
 int bn254_g1_mul_jacobian_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, void *d_out, size_t n, void *stream);
@@ -546,6 +592,7 @@ int bn254_tile_dev(bn254_ctx *ctx, const void *d_record, size_t record_bytes, si
 int bn254_profile_enable(bn254_ctx *ctx, int on);
 int bn254_profile_reset(bn254_ctx *ctx);
 /* kernel: "miller", "miller_shared", "miller_wave", "miller_quad", "pairing_wave", "final_exp", "final_exp_wave", "final_exp_quad", "exp_by_neg_z", "gt_product", "gt_tail", "gt_segment", "gt_tail_seg", "g1_mul", "g2_mul", "gt_mul", "gt_pow", "g2_precompute", "miller_prepared", "g2_prepare_native", "miller_native", "miller_native_shared", "miller_native_seg", "g2_gather", "wire_encode", "wire_decode", "fr_add", "fr_mul", "fr_inverse", "fr_pow", "fr_interpret", "gt_inverse", "g1_add", "g2_add", "g1_msm_mul", "g1_msm_fold", "g2_msm_mul", "g2_msm_fold", "g1_msm_digits", "g1_msm_bucket", "g1_msm_reduce", "g2_msm_digits", "g2_msm_bucket", "g2_msm_reduce", "g1_mul_base", "g2_mul_base", "g1_base_table", "g2_base_table", "g1_normalize", "g2_normalize", "g1_eq", "g2_eq".
+   and, of bn254_fr_ntt_batch: "ntt" (the passes), "ntt_table" (the builds of the twiddle tables).
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);
 /* issue-rate ceiling of v_mad_u64_u32 (the 32x32+64 multiply-accumulate every field product is built from) at
