@@ -93,12 +93,14 @@ extern "C" {
     fn bn254_fr_interpret_batch(ctx: *mut c_void, bytes: *const u8, out: *mut Fr, n: usize) -> c_int;
     fn bn254_fr_root_of_unity(log_n: c_int, out: *mut Fr) -> c_int;
     fn bn254_fr_ntt_batch(ctx: *mut c_void, input: *const Fr, out: *mut Fr, log_n: c_int, count: usize, inverse: c_int, shift: *const Fr) -> c_int;
+    fn bn254_fr_dot_batch(ctx: *mut c_void, coeff: *const Fr, index: *const u64, x: *const Fr, nx: usize, offsets: *const usize, m: usize, out: *mut Fr) -> c_int;
     fn bn254_fr_add_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_out: *mut c_void, n: usize, negate_b: c_int, stream: *mut c_void) -> c_int;
     fn bn254_fr_mul_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_inverse_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_out: *mut c_void, d_ok: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_pow_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_e: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_interpret_batch_dev(ctx: *mut c_void, d_in: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_ntt_batch_dev(ctx: *mut c_void, d_in: *const c_void, d_out: *mut c_void, log_n: c_int, count: usize, inverse: c_int, shift: *const Fr, stream: *mut c_void) -> c_int;
+    fn bn254_fr_dot_batch_dev(ctx: *mut c_void, d_coeff: *const c_void, d_index: *const c_void, d_x: *const c_void, nx: usize, offsets: *const usize, m: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
 }
 
 /// One line-function coefficient of a prepared G2 point: the crate's `EllCoeffs { ell_0, ell_vw, ell_vv: Fq2 }` (src/groups/mod.rs:472-476) as the
@@ -339,6 +341,19 @@ pub fn fr_ntt(values: &[Fr], log_n: u32, inverse: bool, shift: Option<&Fr>) -> R
     let mut out = vec![Fr::zero(); values.len()];
     let sh = shift.map_or(std::ptr::null(), |s| s as *const Fr);
     check(unsafe { bn254_fr_ntt_batch(std::ptr::null_mut(), values.as_ptr(), out.as_mut_ptr(), log_n as c_int, values.len() >> log_n, inverse as c_int, sh) })?;
+    Ok(out)
+}
+
+/// `out[j] = sum of coeff[t] * x[index[t]] over t in offsets[j]..offsets[j + 1]`: a sparse matrix in CSR form (`offsets`, `index`, `coeff`)
+/// times the vector `x` - the witness map of an R1CS.  `index`: `None` for `x[t]`, a plain segmented inner product (`x.len() == coeff.len()`).
+/// An empty segment gives `Fr::zero()`; an index `>= x.len()` is an error, never a wrong sum.
+pub fn fr_dot(coeff: &[Fr], index: Option<&[u64]>, x: &[Fr], offsets: &[usize]) -> Result<Vec<Fr>, GpuError> {
+    assert!(!offsets.is_empty() && *offsets.last().unwrap() == coeff.len());
+    assert!(index.map_or(x.len() == coeff.len(), |i| i.len() == coeff.len()));
+    let m = offsets.len() - 1;
+    let mut out = vec![Fr::zero(); m];
+    let idx = index.map_or(std::ptr::null(), |i| i.as_ptr());
+    check(unsafe { bn254_fr_dot_batch(std::ptr::null_mut(), coeff.as_ptr(), idx, x.as_ptr(), x.len(), offsets.as_ptr(), m, out.as_mut_ptr()) })?;
     Ok(out)
 }
 

@@ -380,6 +380,16 @@ def fr_interpret_batch(bufs, engine=None):
     return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_interpret_batch(bufs)]
 
 
+def fr_dot_batch(coeff, x, offsets, index=None, engine=None):
+    """[sum(coeff[t] * x[index[t]] for t in range(offsets[j], offsets[j + 1])) for j in range(m)] -> list of Fr: a sparse matrix in CSR form
+    (offsets, index, coeff) times the vector x, all rows in ONE call.  index None: x[t], a plain segmented inner product.  coeff and x are
+    sequences of Fr or (n,4) uint64 arrays; an empty segment gives zero.  ValueError for offsets that do not start at 0, decrease or end
+    elsewhere than at len(coeff), for an index of another length or with an entry >= len(x), and for len(x) != len(coeff) without an index."""
+    from .engine import _dot_args
+    args = _dot_args(_scalar_array(coeff), _scalar_array(x), offsets, index)
+    return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_dot_batch(args[0], args[1], args[2], args[3])]
+
+
 def _shift_limbs(shift):
     if shift is None:
         return None

@@ -1,5 +1,5 @@
 // Host arithmetic over sizes and offsets: the argument checks that need no device, the work lists of the segmented folds, the cutting of a
-// prepared batch into Miller pieces, the workspace of the bucket method and its tail scalars, the scalars of the fixed-base tables.  Plain C++17: nothing here touches a device, so
+// prepared batch into Miller pieces, the workspace of the bucket method and its tail scalars, the scalars of the fixed-base tables, the passes of a transform, the pieces of a sparse linear map.  Plain C++17: nothing here touches a device, so
 // tests/hostsim/ compiles it with g++ and tests/test_host_plan.py replays the plans on the CPU.  (io.hpp: the two records the kernels read.)
 #pragma once
 #include <algorithm>
@@ -361,4 +361,57 @@ int bn_ntt_group(const BnNttRun &r, unsigned log_n, unsigned T, size_t cnt, size
         src = s.dst;
     }
     return BN254_OK;
+}
+
+// ---- sparse linear maps over Fr (bn254_fr_dot_batch): the argument checks and the work list
+// CSR offsets, sizes and pointers as for the other segmented calls; without an index the terms meet x one to one, so nx must be n
+inline int bn_dot_check(const void *coeff, bool has_index, const void *x, size_t nx, const size_t *offsets, size_t m, const void *out) {
+    const int rc = bn_seg_check(coeff, x, offsets, m, out);
+    if (rc) return rc;
+    return (!has_index && nx != offsets[m]) ? BN254_E_BAD_ARG : BN254_OK;
+}
+// the host-buffer form reads its index: the caller gets an error, never a wrong sum
+inline int bn_dot_check_index(const uint64_t *index, size_t n, size_t nx) {
+    for (size_t t = 0; index && t < n; ++t)
+        if (index[t] >= nx) return BN254_E_BAD_ARG;
+    return BN254_OK;
+}
+// Every segment of L terms is cut into k = ceil(L / P) pieces of at most P consecutive terms, one lane each (level 0: products and sums).
+// k <= 1: the piece writes out[j] (an empty segment: a piece of no terms, which writes zero).  Otherwise the pieces write k partial sums to
+// scratch slots of their own, and fold levels of at most F consecutive slots per lane (additions only) follow until one value is left, which
+// goes to out[j]: ceil(log_F k) levels.  No slot is written twice, so a level may run as any number of sub-launches in any order after the
+// level before it.  Slots: k (1 + 1/F + 1/F^2 + ..) + levels < 2 k + 64 per folded segment, fewer than 2 n / P + 64 m in all.
+struct BnDotLevel { size_t first, count; };                 // a range of the work list
+struct BnDotPlan {
+    std::vector<bn254::BnDotPiece> pieces;                  // level after level
+    std::vector<BnDotLevel> levels;                         // [0]: the product level (one piece per segment at least), then the fold levels
+    size_t slots = 0;                                       // scratch records of 32 bytes
+};
+inline bn254::BnDotPiece bn_dot_piece(uint64_t first, size_t len, bool to_out, uint64_t dst) {
+    return {first | (uint64_t)len << 48 | (uint64_t)(to_out ? 1 : 0) << 63, dst};
+}
+inline BnDotPlan bn_dot_plan(const size_t *off, size_t m, size_t P, size_t F) {
+    BnDotPlan plan;
+    std::vector<std::vector<bn254::BnDotPiece>> lv(1);
+    lv[0].reserve(m + off[m] / P);
+    for (size_t j = 0; j < m; ++j) {
+        const size_t L = off[j + 1] - off[j];
+        if (L <= P) { lv[0].push_back(bn_dot_piece(off[j], L, true, j)); continue; }
+        size_t k = (L + P - 1) / P, src = plan.slots, level = 1;
+        for (size_t i = 0; i < k; ++i) lv[0].push_back(bn_dot_piece(off[j] + i * P, std::min(P, L - i * P), false, src + i));
+        plan.slots += k;
+        for (; k > F; ++level) {
+            const size_t k2 = (k + F - 1) / F, dst = plan.slots;
+            if (lv.size() <= level) lv.emplace_back();
+            for (size_t i = 0; i < k2; ++i) lv[level].push_back(bn_dot_piece(src + i * F, std::min(F, k - i * F), false, dst + i));
+            plan.slots += k2; src = dst; k = k2;
+        }
+        if (lv.size() <= level) lv.emplace_back();
+        lv[level].push_back(bn_dot_piece(src, k, true, j));
+    }
+    for (const auto &l : lv) {
+        plan.levels.push_back({plan.pieces.size(), l.size()});
+        plan.pieces.insert(plan.pieces.end(), l.begin(), l.end());
+    }
+    return plan;
 }

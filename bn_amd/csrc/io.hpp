@@ -33,6 +33,17 @@ struct BnSegPiece {
 struct BnMillerPiece {
     uint32_t first, cnt;
 };
+// one piece of a sparse linear map over Fr (bn254_fr_dot_batch): `len` consecutive terms from term `first` on - or, in a fold level, `len`
+// consecutive partial sums from scratch slot `first` on - are summed into record `dst` of the output (`to_out`) or of the scratch; len == 0
+// (an empty segment) gives zero.  Two words: src = first (48 bits) | len << 48 (15 bits) | to_out << 63.  Built on the host
+// (host_plan.hpp bn_dot_plan), read by the bodies of dot_ops.hpp.
+struct BnDotPiece {
+    uint64_t src, dst;
+};
+constexpr uint32_t BN_DOT_LEN_MAX = 0x7fffu;
+BN_FN uint64_t dot_piece_first(const BnDotPiece &p) { return p.src & (((uint64_t)1 << 48) - 1); }
+BN_FN uint32_t dot_piece_len(const BnDotPiece &p) { return (uint32_t)(p.src >> 48) & BN_DOT_LEN_MAX; }
+BN_FN bool dot_piece_to_out(const BnDotPiece &p) { return (p.src >> 63) != 0; }
 BN_FN bool words_all_zero(const uint32_t *w, int n) {
     uint32_t o = 0;
     for (int i = 0; i < n; ++i) o |= w[i];

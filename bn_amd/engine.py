@@ -55,6 +55,29 @@ def _offsets(offsets):
     return o
 
 
+def _dot_args(coeff, x, offsets, index):
+    """the operands of fr_dot_batch, checked the way the C ABI checks them (it answers BN254_E_BAD_ARG; here the caller learns which one):
+    (coeff, x, offsets, index or None) as C-contiguous arrays"""
+    coeff = _arr(coeff, 4) if len(coeff) else np.zeros((0, 4), np.uint64)
+    x = _arr(x, 4) if len(x) else np.zeros((0, 4), np.uint64)
+    o = _offsets(offsets)
+    n, nx = coeff.shape[0], x.shape[0]
+    if int(o[0]) != 0 or (o.size > 1 and bool((o[1:] < o[:-1]).any())):
+        raise ValueError("offsets must start at 0 and never decrease")
+    if int(o[-1]) != n:
+        raise ValueError(f"offsets[m] = {int(o[-1])} but {n} terms were given")
+    if index is None:
+        if nx != n:
+            raise ValueError(f"without an index the terms meet x one to one: {n} terms vs {nx} elements of x")
+        return coeff, x, o, None
+    index = np.asarray(index)
+    if index.ndim != 1 or index.shape[0] != n:
+        raise ValueError(f"index holds {index.shape} entries but {n} terms were given")
+    if n and (index.dtype.kind not in "iu" or int(index.min()) < 0 or int(index.max()) >= nx):
+        raise ValueError(f"an index is out of range: x holds {nx} elements")
+    return coeff, x, o, np.ascontiguousarray(index, dtype=np.uint64)
+
+
 def _segment_args(p, q, offsets):
     p = _arr(p, G1_WORDS) if len(p) else np.zeros((0, G1_WORDS), np.uint64)
     q = _arr(q, G2_WORDS) if len(q) else np.zeros((0, G2_WORDS), np.uint64)
@@ -288,6 +311,15 @@ class Engine:
         out = np.empty_like(a)
         shift = _ntt_shift(shift)                                  # held here until the call has returned
         _native.check(self._lib.bn254_fr_ntt_batch(self._h, _p(a), _p(out), log_n, count, 1 if inverse else 0, None if shift is None else _p(shift)))
+        return out
+
+    def fr_dot_batch(self, coeff, x, offsets, index=None):
+        """out[j] = sum of coeff[t] * x[index[t]] over t in [offsets[j], offsets[j+1]) -> (m, 4) uint64: a sparse matrix in CSR form times the
+        vector x.  index None: x[t], a plain segmented inner product (len(x) == len(coeff)).  An empty segment gives zero
+        (include/bn254_hip.h bn254_fr_dot_batch)"""
+        coeff, x, o, index = _dot_args(coeff, x, offsets, index)
+        out = np.empty((o.size - 1, 4), np.uint64)
+        _native.check(self._lib.bn254_fr_dot_batch(self._h, _p(coeff), None if index is None else _p(index), _p(x), x.shape[0], _p(o), o.size - 1, _p(out)))
         return out
 
     def g1_msm_batch(self, p, k, offsets):
@@ -550,6 +582,15 @@ class Engine:
         words) or None, read before the call returns"""
         shift = _ntt_shift(shift)                                  # held here until the call has returned (it reads the shift before it does)
         _native.check(self._lib.bn254_fr_ntt_batch_dev(self._h, d_in, d_out, log_n, count, 1 if inverse else 0, None if shift is None else _p(shift), stream))
+
+    def fr_dot_batch_dev(self, d_coeff, d_index, d_x, nx, offsets, m, d_out, stream=0):
+        """device pointers coeff (offsets[m] records of 32 bytes), index (as many 64-bit words, or None), x (nx records), out (m records),
+        ordered on `stream`; `offsets` is a HOST sequence of m + 1 CSR offsets, read before the call returns.  The index is not checked here:
+        an entry >= nx contributes zero"""
+        o = _offsets(offsets)
+        if o.size != m + 1:
+            raise ValueError(f"{m} segments need {m + 1} offsets, got {o.size}")
+        _native.check(self._lib.bn254_fr_dot_batch_dev(self._h, d_coeff, d_index, d_x, nx, _p(o), m, d_out, stream))
 
     def g1_mul_base_batch_dev(self, base, d_k, d_out, n, stream=0):
         """`base` is a HOST point (12 uint64 words), read before the call returns; d_k, d_out device pointers (n records), ordered on `stream`"""

@@ -14,7 +14,8 @@ import secrets
 
 import numpy as np
 
-from .api import Fr, G1, Gt, R_MOD, default_engine, pairing_check_batch
+from . import poly
+from .api import Fr, G1, G2, Gt, R_MOD, _scalar_array, default_engine, pairing_check_batch
 from .engine import G1_WORDS, G2_WORDS
 
 VerifyingKey = collections.namedtuple("VerifyingKey", "alpha_g1 beta_g2 gamma_g2 delta_g2 ic")
@@ -99,3 +100,173 @@ def verify_aggregate(vk, proofs, public_inputs, engine=None, rng=None):
     P = np.concatenate([A, neg])
     Q = np.concatenate([np.stack([b.limbs for _, b, _ in proofs]), vk.beta_g2.limbs[None], vk.gamma_g2.limbs[None], vk.delta_g2.limbs[None]])
     return bool(np.array_equal(e.pairing_product(P, Q), Gt.one().limbs))
+
+
+# ---- proving: a rank-1 constraint system, its witness map, a development setup and the prover, from calls the engine already has
+R1CS = collections.namedtuple("R1CS", "num_public num_variables a b c")
+R1CS.__doc__ = """num_public: l public inputs; num_variables: columns, the length of z = (1, public_1 .. public_l, private ...) with z[0] = 1;
+a, b, c: the three matrices, each a CSR triple (offsets, index, coeff) over num_variables columns - offsets of rows + 1 entries, index and coeff
+(Fr values or an (nnz,4) uint64 array) of offsets[rows] entries - with the same number of rows.  z satisfies the system when
+(a z)[j] * (b z)[j] == (c z)[j] for every row j."""
+ProvingKey = collections.namedtuple("ProvingKey", "alpha_g1 beta_g1 beta_g2 delta_g1 delta_g2 a_query b_g1_query b_g2_query l_query h_query")
+ProvingKey.__doc__ = """alpha_g1, beta_g1, delta_g1: G1; beta_g2, delta_g2: G2; the queries are normalized points as uint64 arrays, ready for
+the multi-scalar multiplications: a_query (num_variables, 12) = u_i(tau) G1, b_g1_query (num_variables, 12) and b_g2_query (num_variables, 24)
+= v_i(tau) G, l_query (num_variables - l - 1, 12) = ((beta u_i + alpha v_i + w_i) / delta) G1 for the private variables, h_query (n - 1, 12) =
+(tau^k (tau^n - 1) / delta) G1 with n the domain size."""
+_MONT = (1 << 256) % R_MOD
+_M64 = (1 << 64) - 1
+
+
+def _limbs(values):
+    """integers mod r -> (len, 4) uint64 Montgomery images"""
+    out = np.zeros((len(values), 4), np.uint64)
+    for i, v in enumerate(values):
+        m = v % R_MOD * _MONT % R_MOD
+        out[i] = [(m >> (64 * j)) & _M64 for j in range(4)]
+    return out
+
+
+def _draw(rng):
+    """one scalar from 64 bytes of rng (an object with .bytes(n), e.g. a numpy Generator): little endian, mod r"""
+    return int.from_bytes(rng.bytes(64), "little") % R_MOD
+
+
+def _matrices(r1cs):
+    """the three CSR triples as arrays, checked: [(offsets uint64, index uint64, coeff (nnz,4))] and the common number of rows"""
+    out = []
+    nv = int(r1cs.num_variables)
+    if not 0 <= int(r1cs.num_public) < nv:
+        raise ValueError(f"{r1cs.num_public} public inputs do not fit {nv} variables (z[0] is the constant one)")
+    for name, (offsets, index, coeff) in zip("abc", (r1cs.a, r1cs.b, r1cs.c)):
+        o = np.asarray(offsets, np.uint64).reshape(-1)
+        i = np.asarray(index, np.uint64).reshape(-1)
+        c = _scalar_array(coeff)
+        if o.size == 0 or int(o[0]) != 0 or bool((o[1:] < o[:-1]).any()) or int(o[-1]) != i.size or c.shape[0] != i.size:
+            raise ValueError(f"matrix {name} is no CSR triple: offsets start at 0, never decrease and end at len(index) == len(coeff)")
+        if i.size and int(i.max()) >= nv:
+            raise ValueError(f"matrix {name} names column {int(i.max())} but the system has {nv} variables")
+        out.append((o, i, c))
+    rows = out[0][0].size - 1
+    if any(o.size - 1 != rows for o, _, _ in out):
+        raise ValueError("the three matrices differ in their number of rows")
+    return out, rows
+
+
+def _assignment(r1cs, z):
+    Z = _scalar_array(z)
+    if Z.shape[0] != int(r1cs.num_variables):
+        raise ValueError(f"the assignment holds {Z.shape[0]} values but the system has {r1cs.num_variables} variables")
+    if Z.shape[0] == 0 or not np.array_equal(Z[0], Fr.one().limbs):
+        raise ValueError("z[0] is the constant one")
+    return Z
+
+
+def _stacked(mats):
+    """three CSR matrices as one: the rows of b behind those of a, those of c behind b's"""
+    offsets = [np.zeros(1, np.uint64)]
+    at = 0
+    for o, _, _ in mats:
+        offsets.append(o[1:] + np.uint64(at))
+        at += int(o[-1])
+    return np.concatenate(offsets), np.concatenate([i for _, i, _ in mats]), np.concatenate([c for _, _, c in mats])
+
+
+def _domain(rows):
+    """log2 of the next power of two >= rows (at least 1: the quotient needs a domain)"""
+    return max(1, (rows - 1).bit_length())
+
+
+def witness_map(r1cs, z, engine=None):
+    """(a_evals, b_evals, c_evals): the products A z, B z, C z of the three matrices with the assignment z (a sequence of Fr or a
+    (num_variables, 4) uint64 array), each as an (n, 4) uint64 array padded with zero rows to the domain size n, the next power of two >= rows
+    (0 * 0 = 0 keeps A B = C on the whole domain) - the evaluations poly.quotient takes.  The three matrices are stacked and run as ONE sparse
+    matrix-vector product of 3 * rows segments.  ValueError, before any device call, for matrices that are no CSR triples over
+    num_variables columns or differ in their rows, for len(z) != num_variables and for z[0] != 1."""
+    mats, rows = _matrices(r1cs)
+    Z = _assignment(r1cs, z)
+    offsets, index, coeff = _stacked(mats)
+    out = (engine or default_engine()).fr_dot_batch(coeff, Z, offsets, index)
+    n = 1 << _domain(rows)
+    evals = np.zeros((3, n, 4), np.uint64)
+    evals[:, :rows] = out.reshape(3, rows, 4)
+    return evals[0], evals[1], evals[2]
+
+
+def _transposed(o, i, c, nv):
+    """the CSR triple of the transposed matrix: nv rows whose indices are the rows of the original"""
+    row_of = np.repeat(np.arange(o.size - 1, dtype=np.uint64), np.diff(o).astype(np.int64))
+    order = np.argsort(i, kind="stable")
+    counts = np.bincount(i.astype(np.int64), minlength=nv)
+    return np.concatenate([np.zeros(1, np.uint64), np.cumsum(counts).astype(np.uint64)]), row_of[order], c[order]
+
+
+def setup(r1cs, rng, engine=None):
+    """(ProvingKey, VerifyingKey) of the system from a trapdoor (alpha, beta, gamma, delta, tau) drawn from rng - FOR TESTS AND DEVELOPMENT
+    ONLY: whoever knows the trapdoor forges proofs, and this function knows it.  A ceremony that nobody can reconstruct is out of scope.
+    rng: an object with .bytes(n) (a numpy Generator).  The five scalars are drawn in that order, each as 64 bytes little endian mod r, and
+    drawn again while zero (tau: while tau^n == 1, where the domain's vanishing polynomial is zero).
+    With n the domain size (the next power of two >= rows) and H its subgroup: the Lagrange values L_j(tau), j < n, are the inverse transform
+    of (tau^k)_k; u_i(tau) = sum_j A[j,i] L_j(tau) and likewise v_i, w_i for B, C are ONE sparse matrix-vector product over the three
+    transposed matrices (transposed with numpy on the host); the combinations (beta u_i + alpha v_i + w_i) / gamma for i <= l, / delta for
+    i > l, and tau^k (tau^n - 1) / delta for k <= n - 2, are batched field arithmetic; every group element is a fixed-base multiple of the
+    generator (one call per group)."""
+    mats, rows = _matrices(r1cs)
+    e = engine or default_engine()
+    nv, l = int(r1cs.num_variables), int(r1cs.num_public)
+    log_n = _domain(rows)
+    n = 1 << log_n
+    trap = []
+    while len(trap) < 5:
+        v = _draw(rng)
+        if v and not (len(trap) == 4 and pow(v, n, R_MOD) == 1):
+            trap.append(v)
+    alpha, beta, gamma, delta, tau = trap
+    powers = [1]
+    for _ in range(n - 1):
+        powers.append(powers[-1] * tau % R_MOD)
+    P = _limbs(powers)
+    lagrange = e.fr_ntt_batch(P, log_n, inverse=True)
+    offsets, index, coeff = _stacked([_transposed(o, i, c, nv) for o, i, c in mats])
+    uvw = e.fr_dot_batch(coeff, lagrange, offsets, index)
+    u, v, w = uvw[:nv], uvw[nv:2 * nv], uvw[2 * nv:]
+    scaled = e.fr_mul_batch(uvw[:2 * nv], np.repeat(_limbs([beta, alpha]), nv, axis=0))
+    k = e.fr_add_batch(e.fr_add_batch(scaled[:nv], scaled[nv:]), w)
+    inv_gamma, inv_delta = pow(gamma, -1, R_MOD), pow(delta, -1, R_MOD)
+    t_over_delta = (pow(tau, n, R_MOD) - 1) * inv_delta % R_MOD
+    tail = e.fr_mul_batch(np.concatenate([k, P[:n - 1]]),
+                          np.concatenate([np.repeat(_limbs([inv_gamma, inv_delta]), [l + 1, nv - l - 1], axis=0), np.tile(_limbs([t_over_delta]), (n - 1, 1))]))
+    g1 = e.g1_mul_base_batch(G1.one().limbs, np.concatenate([_limbs([alpha, beta, delta]), u, v, tail]))
+    g2 = e.g2_mul_base_batch(G2.one().limbs, np.concatenate([_limbs([beta, gamma, delta]), v]))
+    kq = g1[3 + 2 * nv:3 + 3 * nv]
+    pk = ProvingKey(G1(g1[0]), G1(g1[1]), G2(g2[0]), G1(g1[2]), G2(g2[2]), g1[3:3 + nv], g1[3 + nv:3 + 2 * nv], g2[3:], kq[l + 1:], g1[3 + 3 * nv:])
+    vk = VerifyingKey(G1(g1[0]), G2(g2[0]), G2(g2[1]), G2(g2[2]), [G1(r) for r in kq[:l + 1]])
+    return pk, vk
+
+
+def prove(pk, r1cs, z, rng, engine=None):
+    """The proof (A: G1, B: G2, C: G1) that the prover knows an assignment z = (1, public_1 .. public_l, private ...) of the system, for the
+    keys of setup(); verify_batch(vk, [proof], [z[1:l + 1]]) accepts it.  With h = poly.quotient(*witness_map(r1cs, z)) and r, s drawn from
+    rng (in that order, 64 bytes each, little endian mod r):
+        A = alpha + sum z_i a_query_i + r delta
+        B = beta + sum z_i b_g2_query_i + s delta                          (in G2; the same sum in G1 is B1)
+        C = sum_{i>l} z_i l_query_i + sum_k h_k h_query_k + s A + r B1 - r s delta
+    The five sums are multi-scalar multiplications, four in G1 and one in G2; what remains - a handful of terms per output - is one segmented
+    multi-scalar multiplication per group.  It is NOT checked that z satisfies the system: an assignment that does not yields a proof that
+    does not verify (the quotient is then the quotient of nothing).  ValueError, before any device call, when len(z) != num_variables or
+    z[0] != 1."""
+    Z = _assignment(r1cs, z)
+    e = engine or default_engine()
+    l = int(r1cs.num_public)
+    a_evals, b_evals, c_evals = witness_map(r1cs, Z, engine=e)
+    h = poly.quotient(a_evals, b_evals, c_evals, engine=e)
+    H = np.stack([x.limbs for x in h[:-1]])
+    r, s = _draw(rng), _draw(rng)
+    sum_a, sum_b1 = e.g1_msm(pk.a_query, Z), e.g1_msm(pk.b_g1_query, Z)
+    sum_l, sum_h = e.g1_msm(pk.l_query, Z[l + 1:]), e.g1_msm(pk.h_query, H)
+    sum_b2 = e.g2_msm(pk.b_g2_query, Z)
+    # s A + r B1 - r s delta = s alpha + s sum_a + r beta + r sum_b1 + r s delta
+    points = np.stack([pk.alpha_g1.limbs, sum_a, pk.delta_g1.limbs,
+                       sum_l, sum_h, pk.alpha_g1.limbs, sum_a, pk.beta_g1.limbs, sum_b1, pk.delta_g1.limbs])
+    ac = e.g1_msm_batch(points, _limbs([1, 1, r, 1, 1, s, s, r, r, r * s]), np.array([0, 3, 10], np.uint64))
+    b = e.g2_msm_batch(np.stack([pk.beta_g2.limbs, sum_b2, pk.delta_g2.limbs]), _limbs([1, 1, s]), np.array([0, 3], np.uint64))
+    return G1(ac[0]), G2(b[0]), G1(ac[1])

@@ -204,6 +204,16 @@ inline std::vector<Fr> fr_ntt(const std::vector<Fr> &values, int log_n, bool inv
                              reinterpret_cast<const bn_fr *>(shift)));
     return out;
 }
+// out[j] = sum of coeff[t] * x[index[t]] over t in [offsets[j], offsets[j+1]): a sparse matrix in CSR form times the vector x - the witness
+// map of an R1CS.  index: nullptr for x[t], a plain segmented inner product (x.size() == coeff.size()).  An empty segment gives Fr::zero().
+inline std::vector<Fr> fr_dot(const std::vector<Fr> &coeff, const std::vector<uint64_t> *index, const std::vector<Fr> &x, const std::vector<size_t> &offsets) {
+    if (offsets.empty() || offsets.back() != coeff.size() || (index ? index->size() != coeff.size() : x.size() != coeff.size()))
+        throw std::invalid_argument("fr_dot: offsets, index and coeff disagree in length");
+    std::vector<Fr> out(offsets.size() - 1);
+    check(bn254_fr_dot_batch(nullptr, reinterpret_cast<const bn_fr *>(coeff.data()), index ? index->data() : nullptr, reinterpret_cast<const bn_fr *>(x.data()), x.size(),
+                             offsets.data(), out.size(), reinterpret_cast<bn_fr *>(out.data())));
+    return out;
+}
 // out[i] = (a[i] == b[i]) as group elements, whatever their Jacobian representations (groups/mod.rs:83-109): nothing is normalized
 inline std::vector<bool> g1_eq(const std::vector<G1> &a, const std::vector<G1> &b) {
     if (a.size() != b.size()) throw std::invalid_argument("g1_eq: length mismatch");

@@ -40,6 +40,9 @@
  *   bn254_fr_ntt_batch     out[t n + k] = sum_j in[t n + j] s^j w_n^(j k), or the inverse map: the polynomial <-> its evaluations over the subgroup of
  *                          order n = 2^log_n (on the coset s H); no counterpart in the reference - the convention is ark-bn254's root of unity
  *   bn254_fr_ntt_batch_dev the same on device-resident arrays, asynchronous on the caller's stream; bn254_fr_root_of_unity  w_n, on the host
+ *   bn254_fr_dot_batch     out[j] = sum of coeff[t] * x[index[t]] over t in [offsets[j], offsets[j+1]): a sparse matrix in CSR form times a vector over Fr
+ *                          (lib.rs:33-53 Add and Mul, folded per row); no counterpart in the reference - the witness map of an R1CS
+ *   bn254_fr_dot_batch_dev the same on device-resident coeff, index, x and out, asynchronous on the caller's stream
  *   bn254_g2_precompute    coeffs[i][0..102) = q[i].to_affine().precompute().coeffs   groups/mod.rs:557-588 (Q != infinity)
  *   bn254_pairing_prepared_batch  out[i] = final_exponentiation(prepared.miller_loop(p[i]))   groups/mod.rs:486-519,768
  *   bn254_gt_mul_batch     out[i] = a[i] * b[i]                                     lib.rs:175-179, fields/fq12.rs:295-307
@@ -77,6 +80,7 @@
      bn254_fr_{add,mul,inverse,pow,interpret}_batch serialise on the context in the same way (its mutex for the whole call).
      bn254_fr_ntt_batch serialises on the context in the same way (its mutex for the whole call); bn254_fr_root_of_unity touches no
      context and no device.
+     bn254_fr_dot_batch serialises on the context in the same way (its mutex for the whole call).
  *     bn254_pairing_product_batch_prepared_native serialises on the context like them; its handle is immutable and shared freely.
  *     Use one context per thread (or bn254_multi_*) for more overlap;
  *     bn254_ctx_set_option is atomic, but set options before concurrent use: a call in flight may run some
@@ -101,6 +105,9 @@
      bn254_fr_ntt_batch_dev keeps its twiddle tables and the arrays between its passes in context-owned scratch under the same event
      ordering: a table is built, rebuilt (the shift's) and read only by a stream that has waited for the last launch that may read it.  It
      reads its HOST `shift` before it returns (the few field operations on it run on the host), waits on nothing and reads nothing back.
+     bn254_fr_dot_batch_dev reads its HOST `offsets` before it returns (the launches are planned from them; its `d_index` is device memory and
+     read by the kernels only); its work list and partial sums are context-owned scratch under the same event ordering.  It waits on the
+     host only for the upload of the previous work list that went through the same pinned staging, and reads nothing back.
  */
 #ifndef BN254_HIP_H
 #define BN254_HIP_H
@@ -425,6 +432,32 @@ int bn254_fr_interpret_batch(bn254_ctx *ctx, const uint8_t *in, bn_fr *out, size
 #define BN254_NTT_LOG_MAX 24
 int bn254_fr_root_of_unity(int log_n, bn_fr *out);
 int bn254_fr_ntt_batch(bn254_ctx *ctx, const bn_fr *in, bn_fr *out, int log_n, size_t count, int inverse, const bn_fr *shift);
+/* Sparse linear maps over Fr: m dot products in one call - a sparse matrix in CSR form times a vector.  The witness map of an R1CS (the rows
+   of A, B, C against the assignment z, in front of the quotient of bn254_fr_ntt_batch), the same transposed for a setup
+   (u_i(tau) = sum_j A[j,i] L_j(tau)), and, without an index, segmented inner products: a polynomial against a vector of powers, plain sums
+   (coeff = Fr::one()), Lagrange interpolation.  Segments in CSR form exactly as for bn254_g1_msm_batch: offsets[0..m] with offsets[0] == 0,
+   non-decreasing, n = offsets[m] terms, and
+       out[j] = sum over t in [offsets[j], offsets[j+1]) of coeff[t] * x[index[t]],   j < m
+   with x of nx elements and index of n entries, each < nx.  index == NULL means x[t]: a plain segmented inner product, and nx must then equal
+   n.  An empty segment gives Fr::zero().  Inputs are canonical Montgomery images; every output is canonical, hence unique, hence independent of
+   the order in which the terms are added.  `out` may not overlap any input.  `offsets` is HOST memory.
+   How: the host cuts every segment into pieces of at most 4 consecutive terms and a lane runs one piece - two 16-byte loads for coeff[t], two
+   for x[index[t]], a Montgomery product and an addition per term -, so no lane's chain depends on the data: one row of 2^22 terms is 2^20
+   lanes, not one.  A segment of at most 4 terms writes out[j] directly; a longer one writes partial sums to context-owned scratch, which
+   fold levels of at most 16 per lane (additions only) reduce to one value: ceil(log16(ceil(L / 4))) levels for a segment of L terms.  The
+   work list (16 bytes per piece: one per segment at least, one per 4 terms) is built on the host and uploaded with the call; levels run as
+   sub-launches of at most 2^22 lanes.  Measured on an MI355X (tools/time_dot.py, medians of 5, one process; the full table is
+   profiles/r15_dot.txt), kernel time for piece lengths 4 / 8 / 16 / 32: 0.251 / 0.276 / 0.312 / 0.322 ms on an R1CS-like call (786 432 rows of
+   1..6 terms, every 1024th of 4096: 5.9 M terms gathered from 2^18 elements), 0.205 / 0.222 / 0.183 / 0.136 ms on ONE segment of 2^22 terms
+   without an index, 0.127 / 0.143 / 0.166 / 0.125 ms on 2^10 rows of 2^12 terms.  The rule was fixed before measuring - the fastest on the
+   R1CS-like call ships -, so the piece length is 4; on the one long segment it is 51 % behind the best there (32), whose partial sums are an
+   eighth as many.  The shipped call takes 1.40 / 2.04 / 1.12 x a device-to-device copy of the bytes it must move and 2.4 / 2.8 / 1.8 x
+   bn254_fr_mul_batch_dev on as many pre-gathered terms (which sums nothing).  The fan 16 was not swept.  A variant that accumulates
+   unreduced products and reduces once per four terms was not built.
+   Errors (BN254_E_BAD_ARG, checked before any device is touched): offsets == NULL with m > 0, offsets[0] != 0, decreasing offsets,
+   n > 2^40, a NULL coeff / x (n > 0) or out, index == NULL with nx != n, an index[t] >= nx (the caller gets an error, never a wrong sum).
+   m == 0 returns BN254_OK and writes nothing.  Threading: see above - the host-buffer entry point holds the context's mutex for the whole call. */
+int bn254_fr_dot_batch(bn254_ctx *ctx, const bn_fr *coeff, const uint64_t *index, const bn_fr *x, size_t nx, const size_t *offsets, size_t m, bn_fr *out);
 
 /* ---- one node, several GPUs (north_star: independent batches shard across the GPUs; ONE exchange for the multi-pairing) --- */
 /* `devices[0..ndev)`: HIP device index of every rank (NULL = 0..ndev-1).  One context and one host thread per rank.  A device may
@@ -574,6 +607,12 @@ int bn254_fr_interpret_batch_dev(bn254_ctx *ctx, const void *d_in, void *d_out, 
    be exactly d_in; `shift` is HOST memory (one element or NULL), read before the call returns.  Tables and the arrays between the passes
    are context-owned scratch (see Threading). */
 int bn254_fr_ntt_batch_dev(bn254_ctx *ctx, const void *d_in, void *d_out, int log_n, size_t count, int inverse, const bn_fr *shift, void *stream);
+/* bn254_fr_dot_batch on device-resident coeff (n records of 32 bytes, 16-byte aligned), d_index (n 64-bit words, or NULL), x (nx records) and
+   out (m records); `offsets` (m+1 entries) is HOST memory (the launches are planned from it) and may be freed on return.  d_index cannot be
+   read on the host, so it is NOT checked: an index >= nx is outside the contract, but memory safe - the kernel compares it before it loads
+   anything through it, so that term contributes zero.  Work list and partial sums are context-owned scratch (see Threading). */
+int bn254_fr_dot_batch_dev(bn254_ctx *ctx, const void *d_coeff, const void *d_index, const void *d_x, size_t nx, const size_t *offsets, size_t m, void *d_out,
+                           void *stream);
 /* raw Jacobian result of the reference's MSB-first double-and-add (what G::random produces, groups/mod.rs:220-222):
    used to generate benchmark inputs with z != 1 on the device */
 int bn254_g1_mul_jacobian_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, void *d_out, size_t n, void *stream);
@@ -592,6 +631,7 @@ int bn254_tile_dev(bn254_ctx *ctx, const void *d_record, size_t record_bytes, si
 int bn254_profile_enable(bn254_ctx *ctx, int on);
 int bn254_profile_reset(bn254_ctx *ctx);
 /* kernel: "miller", "miller_shared", "miller_wave", "miller_quad", "pairing_wave", "final_exp", "final_exp_wave", "final_exp_quad", "exp_by_neg_z", "gt_product", "gt_tail", "gt_segment", "gt_tail_seg", "g1_mul", "g2_mul", "gt_mul", "gt_pow", "g2_precompute", "miller_prepared", "g2_prepare_native", "miller_native", "miller_native_shared", "miller_native_seg", "g2_gather", "wire_encode", "wire_decode", "fr_add", "fr_mul", "fr_inverse", "fr_pow", "fr_interpret", "gt_inverse", "g1_add", "g2_add", "g1_msm_mul", "g1_msm_fold", "g2_msm_mul", "g2_msm_fold", "g1_msm_digits", "g1_msm_bucket", "g1_msm_reduce", "g2_msm_digits", "g2_msm_bucket", "g2_msm_reduce", "g1_mul_base", "g2_mul_base", "g1_base_table", "g2_base_table", "g1_normalize", "g2_normalize", "g1_eq", "g2_eq".
+   of bn254_fr_dot_batch: "fr_dot" (the pieces: products and sums), "fr_dot_fold" (the levels over the partial sums);
    and, of bn254_fr_ntt_batch: "ntt" (the passes), "ntt_table" (the builds of the twiddle tables).
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);
