@@ -94,6 +94,7 @@ extern "C" {
     fn bn254_fr_root_of_unity(log_n: c_int, out: *mut Fr) -> c_int;
     fn bn254_fr_ntt_batch(ctx: *mut c_void, input: *const Fr, out: *mut Fr, log_n: c_int, count: usize, inverse: c_int, shift: *const Fr) -> c_int;
     fn bn254_fr_dot_batch(ctx: *mut c_void, coeff: *const Fr, index: *const u64, x: *const Fr, nx: usize, offsets: *const usize, m: usize, out: *mut Fr) -> c_int;
+    fn bn254_fr_scan_batch(ctx: *mut c_void, a: *const Fr, b: *const Fr, init: *const Fr, offsets: *const usize, m: usize, flags: c_int, out: *mut Fr) -> c_int;
     fn bn254_fr_add_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_out: *mut c_void, n: usize, negate_b: c_int, stream: *mut c_void) -> c_int;
     fn bn254_fr_mul_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_inverse_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_out: *mut c_void, d_ok: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
@@ -101,6 +102,7 @@ extern "C" {
     fn bn254_fr_interpret_batch_dev(ctx: *mut c_void, d_in: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_ntt_batch_dev(ctx: *mut c_void, d_in: *const c_void, d_out: *mut c_void, log_n: c_int, count: usize, inverse: c_int, shift: *const Fr, stream: *mut c_void) -> c_int;
     fn bn254_fr_dot_batch_dev(ctx: *mut c_void, d_coeff: *const c_void, d_index: *const c_void, d_x: *const c_void, nx: usize, offsets: *const usize, m: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn bn254_fr_scan_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_init: *const c_void, offsets: *const usize, m: usize, flags: c_int, d_out: *mut c_void, stream: *mut c_void) -> c_int;
 }
 
 /// One line-function coefficient of a prepared G2 point: the crate's `EllCoeffs { ell_0, ell_vw, ell_vv: Fq2 }` (src/groups/mod.rs:472-476) as the
@@ -354,6 +356,26 @@ pub fn fr_dot(coeff: &[Fr], index: Option<&[u64]>, x: &[Fr], offsets: &[usize]) 
     let mut out = vec![Fr::zero(); m];
     let idx = index.map_or(std::ptr::null(), |i| i.as_ptr());
     check(unsafe { bn254_fr_dot_batch(std::ptr::null_mut(), coeff.as_ptr(), idx, x.as_ptr(), x.len(), offsets.as_ptr(), m, out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// Flags of [`fr_scan`] (the header's `BN254_SCAN_*`): from each segment's last term to its first; `out[t]` is the value BEFORE term `t`;
+/// `a` holds one factor per segment.
+pub const SCAN_REVERSE: c_int = 1;
+pub const SCAN_EXCLUSIVE: c_int = 2;
+pub const SCAN_A_PER_SEGMENT: c_int = 4;
+
+/// `out[t] = a[t] * prev + b[t]` over the terms of every segment `offsets[j]..offsets[j + 1]` in order, `prev = out[t - 1]` or `init[j]` at the
+/// segment's first term: segmented prefix sums (`a`: `None`), prefix products (`b`: `None`), powers and Horner's rule (`SCAN_A_PER_SEGMENT`).
+/// `init`: `None` for `Fr::zero()` with `b`, `Fr::one()` without.  One output per term; an empty segment writes nothing.
+pub fn fr_scan(a: Option<&[Fr]>, b: Option<&[Fr]>, init: Option<&[Fr]>, offsets: &[usize], flags: c_int) -> Result<Vec<Fr>, GpuError> {
+    assert!(!offsets.is_empty() && (a.is_some() || b.is_some()));
+    let (m, n) = (offsets.len() - 1, *offsets.last().unwrap());
+    assert!(b.map_or(true, |v| v.len() == n) && init.map_or(true, |v| v.len() == m));
+    assert!(a.map_or(true, |v| v.len() == if flags & SCAN_A_PER_SEGMENT != 0 { m } else { n }));
+    let mut out = vec![Fr::zero(); n];
+    let ptr = |v: Option<&[Fr]>| v.map_or(std::ptr::null(), |s| s.as_ptr());
+    check(unsafe { bn254_fr_scan_batch(std::ptr::null_mut(), ptr(a), ptr(b), ptr(init), offsets.as_ptr(), m, flags, out.as_mut_ptr()) })?;
     Ok(out)
 }
 

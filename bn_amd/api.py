@@ -390,6 +390,21 @@ def fr_dot_batch(coeff, x, offsets, index=None, engine=None):
     return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_dot_batch(args[0], args[1], args[2], args[3])]
 
 
+def fr_scan_batch(a, b, offsets, init=None, reverse=False, exclusive=False, a_per_segment=False, engine=None):
+    """The first-order linear recurrence over every segment, all segments in ONE call -> list of len(terms) Fr:
+        out[t] = a[t] * prev + b[t],   prev = out[t-1], or init[j] at the first term of segment j = [offsets[j], offsets[j+1])
+    a None: every a[t] is one (segmented prefix sums); b None: every b[t] is zero (segmented prefix products); init None: zero with b, one
+    without.  reverse: each segment from its last term to its first; exclusive: out[t] = prev (the first term gets init[j], the total is
+    not written); a_per_segment: a holds one factor per segment (powers, Horner's rule).  a, b, init are sequences of Fr or (n,4) uint64
+    arrays.  ValueError, before any device call, naming the operand: a and b both None, offsets that do not start at 0 or decrease, a, b or
+    init of the wrong length."""
+    from .engine import _scan_args
+    rows = lambda v: None if v is None else _scalar_array(v)
+    args = _scan_args(rows(a), rows(b), offsets, rows(init), a_per_segment)
+    out = (engine or default_engine()).fr_scan_batch(args[0], args[1], args[2], args[3], reverse=reverse, exclusive=exclusive, a_per_segment=a_per_segment)
+    return [Fr.from_limbs(r) for r in out]
+
+
 def _shift_limbs(shift):
     if shift is None:
         return None

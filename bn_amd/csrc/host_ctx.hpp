@@ -112,7 +112,7 @@ struct bn254_ctx {
     hipEvent_t scratch_ev = nullptr;    // completion of the last launch that used ws / exp_tbl ...
     hipStream_t scratch_stream = nullptr;   // ... and the stream it ran on
     bool scratch_used = false;
-    BnBuf seg_plan;                     // work lists of the segmented fold (bn254_pairing_product_batch*, behind them the Miller pieces of ..._prepared_native) and of bn254_fr_dot_batch, device side ...
+    BnBuf seg_plan;                     // work lists of the segmented fold (bn254_pairing_product_batch*, behind them the Miller pieces of ..._prepared_native) and of bn254_fr_dot_batch and bn254_fr_scan_batch, device side ...
     BnBuf seg_plan_host{nullptr, 0, true};  // ... and their pinned staging, rewritten only after seg_plan_ev (its last copy) completed
     hipEvent_t seg_plan_ev = nullptr;
     BnBuf msm_ws;                       // bucket route of bn254_g{1,2}_msm: counts, sorted indices and keys, buckets, partial sums, tail terms
@@ -128,6 +128,7 @@ struct bn254_ctx {
     bool ntt_shift_valid = false;
     BnBuf ntt_ws;                       // the arrays between the passes of one group of transforms (one, or two for an odd number of passes in place)
     BnBuf dot_ws;                       // bn254_fr_dot_batch: the partial sums of the segments longer than one piece (32 bytes each; its work list travels through seg_plan)
+    BnBuf scan_ws;                      // bn254_fr_scan_batch: per scratch slot of its plan a map (A, B) and a carry, three arrays of 32-byte records (its work list travels through seg_plan)
     BnBuf base_stage;                   // the base of a table build on the device ...
     BnBuf base_stage_host{nullptr, 0, true};    // ... and its pinned staging, rewritten only after base_stage_ev (its last copy) completed
     hipEvent_t base_stage_ev = nullptr;

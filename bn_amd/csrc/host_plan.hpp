@@ -1,5 +1,5 @@
 // Host arithmetic over sizes and offsets: the argument checks that need no device, the work lists of the segmented folds, the cutting of a
-// prepared batch into Miller pieces, the workspace of the bucket method and its tail scalars, the scalars of the fixed-base tables, the passes of a transform, the pieces of a sparse linear map.  Plain C++17: nothing here touches a device, so
+// prepared batch into Miller pieces, the workspace of the bucket method and its tail scalars, the scalars of the fixed-base tables, the passes of a transform, the pieces of a sparse linear map, the levels of a segmented scan.  Plain C++17: nothing here touches a device, so
 // tests/hostsim/ compiles it with g++ and tests/test_host_plan.py replays the plans on the CPU.  (io.hpp: the two records the kernels read.)
 #pragma once
 #include <algorithm>
@@ -413,5 +413,74 @@ inline BnDotPlan bn_dot_plan(const size_t *off, size_t m, size_t P, size_t F) {
         plan.levels.push_back({plan.pieces.size(), l.size()});
         plan.pieces.insert(plan.pieces.end(), l.begin(), l.end());
     }
+    return plan;
+}
+
+// ---- segmented scans over Fr (bn254_fr_scan_batch): the argument checks and the work list
+constexpr unsigned BN_SCAN_FLAGS_ALL = BN254_SCAN_REVERSE | BN254_SCAN_EXCLUSIVE | BN254_SCAN_A_PER_SEGMENT;
+// one operand at least, known flags, CSR offsets as for the other segmented calls, an output.  init is optional, so nothing is asked of it.
+inline int bn_scan_check(const void *a, const void *b, const size_t *offsets, size_t m, unsigned flags, const void *out) {
+    if ((!a && !b) || (flags & ~BN_SCAN_FLAGS_ALL) || !offsets || offsets[0] != 0) return BN254_E_BAD_ARG;
+    for (size_t j = 0; j < m; ++j)
+        if (offsets[j + 1] < offsets[j]) return BN254_E_BAD_ARG;
+    return (offsets[m] > BN_N_MAX || !out) ? BN254_E_BAD_ARG : BN254_OK;
+}
+// Every segment of L > 0 terms is cut into k = ceil(L / P) pieces of at most P consecutive terms, in the order of the recurrence (REVERSE:
+// piece 0 holds the LAST terms and every piece walks downwards), one lane each in the APPLY level.  k == 1: the piece is "direct" - it starts
+// from init[j] and needs nothing else.  Otherwise the pieces own scratch slots base .. base + k - 1 (the slot of a piece holds its map and
+// the value in front of it), and the segment takes part in
+//   REDUCE   once, over the work list of the apply level (a direct piece returns at once): every piece writes its map;
+//   UP       u(k) levels, u(k) = the number of times k -> ceil(k / F) is taken while k > F (max(0, ceil(log_F k) - 1)): a lane composes at most F
+//            consecutive maps of the level below into a slot of its own;
+//   DOWN     u(k) + 1 levels: at the top ONE lane walks the at most F maps that are left from init[j]; below it a lane per slot of the level
+//            above walks that slot's at most F children from the slot's carry;
+//   APPLY    once.
+// So a segment of L <= P terms is one level and a longer one 2 u(ceil(L / P)) + 3; a call runs the levels of its longest segment, shorter
+// segments simply have no piece in the deeper ones.  No map and no carry is written twice, and a level reads only what earlier levels wrote,
+// so a level may run as any number of sub-launches in any order after the level before it.  Slots: k (1 + 1/F + 1/F^2 + ..) + u < 2 k + 64
+// per long segment, fewer than 2 n / P + 64 m in all; an empty segment has no piece at all.
+enum BnScanKind { BN_SCAN_REDUCE, BN_SCAN_UP, BN_SCAN_DOWN, BN_SCAN_APPLY };
+struct BnScanLevel { BnScanKind kind; size_t first, count; };       // a range of the work list
+struct BnScanPlan {
+    std::vector<bn254::BnScanPiece> pieces;                 // the apply level (shared with reduce), then the up levels, then the down levels
+    std::vector<BnScanLevel> levels;                        // in launch order
+    size_t slots = 0;                                       // scratch slots: a map (A, B) and a carry each
+};
+inline bn254::BnScanPiece bn_scan_piece(uint64_t first, size_t len, bool flag, uint64_t seg, uint64_t slot) {
+    return {first | (uint64_t)len << 48 | (uint64_t)(flag ? 1 : 0) << 63, seg, slot};
+}
+inline BnScanPlan bn_scan_plan(const size_t *off, size_t m, size_t P, size_t F, bool reverse) {
+    BnScanPlan plan;
+    std::vector<bn254::BnScanPiece> apply;
+    std::vector<std::vector<bn254::BnScanPiece>> up, down;
+    apply.reserve(m + off[m] / P);
+    for (size_t j = 0; j < m; ++j) {
+        const size_t L = off[j + 1] - off[j];
+        if (L == 0) continue;
+        const size_t start = reverse ? off[j + 1] - 1 : off[j];
+        if (L <= P) { apply.push_back(bn_scan_piece(start, L, true, j, 0)); continue; }
+        size_t k = (L + P - 1) / P;
+        std::vector<std::pair<size_t, size_t>> lv{{plan.slots, k}};               // (first slot, count) of every level of this segment's tree
+        for (size_t i = 0; i < k; ++i) apply.push_back(bn_scan_piece(reverse ? start - i * P : start + i * P, std::min(P, L - i * P), false, j, plan.slots + i));
+        plan.slots += k;
+        for (size_t level = 0; k > F; ++level) {
+            const size_t k2 = (k + F - 1) / F, src = lv.back().first, dst = plan.slots;
+            if (up.size() <= level) up.emplace_back();
+            for (size_t i = 0; i < k2; ++i) up[level].push_back(bn_scan_piece(src + i * F, std::min(F, k - i * F), false, j, dst + i));
+            plan.slots += k2; lv.push_back({dst, k2}); k = k2;
+        }
+        if (down.size() < lv.size()) down.resize(lv.size());
+        down[0].push_back(bn_scan_piece(lv.back().first, lv.back().second, true, j, 0));
+        for (size_t d = 1; d < lv.size(); ++d) {
+            const auto parent = lv[lv.size() - d], child = lv[lv.size() - 1 - d];
+            for (size_t i = 0; i < parent.second; ++i) down[d].push_back(bn_scan_piece(child.first + i * F, std::min(F, child.second - i * F), false, j, parent.first + i));
+        }
+    }
+    plan.pieces = std::move(apply);
+    const size_t lanes = plan.pieces.size();
+    if (!down.empty()) plan.levels.push_back({BN_SCAN_REDUCE, 0, lanes});
+    for (const auto &l : up) { plan.levels.push_back({BN_SCAN_UP, plan.pieces.size(), l.size()}); plan.pieces.insert(plan.pieces.end(), l.begin(), l.end()); }
+    for (const auto &l : down) { plan.levels.push_back({BN_SCAN_DOWN, plan.pieces.size(), l.size()}); plan.pieces.insert(plan.pieces.end(), l.begin(), l.end()); }
+    plan.levels.push_back({BN_SCAN_APPLY, 0, lanes});
     return plan;
 }

@@ -44,6 +44,18 @@ constexpr uint32_t BN_DOT_LEN_MAX = 0x7fffu;
 BN_FN uint64_t dot_piece_first(const BnDotPiece &p) { return p.src & (((uint64_t)1 << 48) - 1); }
 BN_FN uint32_t dot_piece_len(const BnDotPiece &p) { return (uint32_t)(p.src >> 48) & BN_DOT_LEN_MAX; }
 BN_FN bool dot_piece_to_out(const BnDotPiece &p) { return (p.src >> 63) != 0; }
+// one piece of a segmented scan over Fr (bn254_fr_scan_batch).  Three words: src = first (48 bits) | len << 48 (15 bits) | flag << 63, the
+// segment, a scratch slot.  In the apply level (which the reduce level shares): `len` consecutive terms of segment `seg` from term `first` on
+// (REVERSE: downwards), whose map goes to, and whose carry comes from, slot `slot`; flag: the piece is its whole segment and starts from
+// init[seg].  In an up level: the maps of slots [first, first + len) composed into `slot`.  In a down level: the carries of slots
+// [first, first + len) from the carry of `slot`, or - flag - from init[seg].  Built on the host (host_plan.hpp bn_scan_plan), read by the
+// bodies of scan_ops.hpp.
+struct BnScanPiece {
+    uint64_t src, seg, slot;
+};
+BN_FN uint64_t scan_piece_first(const BnScanPiece &p) { return p.src & (((uint64_t)1 << 48) - 1); }
+BN_FN uint32_t scan_piece_len(const BnScanPiece &p) { return (uint32_t)(p.src >> 48) & BN_DOT_LEN_MAX; }
+BN_FN bool scan_piece_flag(const BnScanPiece &p) { return (p.src >> 63) != 0; }
 BN_FN bool words_all_zero(const uint32_t *w, int n) {
     uint32_t o = 0;
     for (int i = 0; i < n; ++i) o |= w[i];

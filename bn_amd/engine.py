@@ -78,6 +78,33 @@ def _dot_args(coeff, x, offsets, index):
     return coeff, x, o, np.ascontiguousarray(index, dtype=np.uint64)
 
 
+SCAN_REVERSE, SCAN_EXCLUSIVE, SCAN_A_PER_SEGMENT = 1, 2, 4           # BN254_SCAN_* of include/bn254_hip.h
+
+
+def _scan_flags(reverse, exclusive, a_per_segment):
+    return (SCAN_REVERSE if reverse else 0) | (SCAN_EXCLUSIVE if exclusive else 0) | (SCAN_A_PER_SEGMENT if a_per_segment else 0)
+
+
+def _scan_args(a, b, offsets, init, a_per_segment):
+    """the operands of fr_scan_batch, checked the way the C ABI checks them (it answers BN254_E_BAD_ARG; here the caller learns which one):
+    (a or None, b or None, offsets, init or None) as C-contiguous arrays"""
+    if a is None and b is None:
+        raise ValueError("a and b are both None: the recurrence out[t] = a[t] * prev + b[t] needs one of them")
+    rows = lambda v: None if v is None else (_arr(v, 4) if len(v) else np.zeros((0, 4), np.uint64))
+    a, b, init = rows(a), rows(b), rows(init)
+    o = _offsets(offsets)
+    if int(o[0]) != 0 or (o.size > 1 and bool((o[1:] < o[:-1]).any())):
+        raise ValueError("offsets must start at 0 and never decrease")
+    m, n = o.size - 1, int(o[-1])
+    if b is not None and b.shape[0] != n:
+        raise ValueError(f"b holds {b.shape[0]} terms but offsets[m] = {n}")
+    if a is not None and a.shape[0] != (m if a_per_segment else n):
+        raise ValueError(f"a holds {a.shape[0]} records but " + (f"a_per_segment takes one for each of the {m} segments" if a_per_segment else f"offsets[m] = {n}"))
+    if init is not None and init.shape[0] != m:
+        raise ValueError(f"init holds {init.shape[0]} values but there are {m} segments")
+    return a, b, o, init
+
+
 def _segment_args(p, q, offsets):
     p = _arr(p, G1_WORDS) if len(p) else np.zeros((0, G1_WORDS), np.uint64)
     q = _arr(q, G2_WORDS) if len(q) else np.zeros((0, G2_WORDS), np.uint64)
@@ -320,6 +347,17 @@ class Engine:
         coeff, x, o, index = _dot_args(coeff, x, offsets, index)
         out = np.empty((o.size - 1, 4), np.uint64)
         _native.check(self._lib.bn254_fr_dot_batch(self._h, _p(coeff), None if index is None else _p(index), _p(x), x.shape[0], _p(o), o.size - 1, _p(out)))
+        return out
+
+    def fr_scan_batch(self, a, b, offsets, init=None, reverse=False, exclusive=False, a_per_segment=False):
+        """out[t] = a[t] * prev + b[t] over the terms of every segment [offsets[j], offsets[j+1]) in order, prev = out[t-1] or init[j] at the
+        segment's first term -> (n, 4) uint64.  a None: prefix sums; b None: prefix products; init None: zero with b, one without.
+        reverse: from each segment's last term to its first; exclusive: out[t] = prev; a_per_segment: a holds one factor per segment
+        (include/bn254_hip.h bn254_fr_scan_batch)"""
+        a, b, o, init = _scan_args(a, b, offsets, init, a_per_segment)
+        out = np.empty((int(o[-1]), 4), np.uint64)
+        opt = lambda v: None if v is None else _p(v)
+        _native.check(self._lib.bn254_fr_scan_batch(self._h, opt(a), opt(b), opt(init), _p(o), o.size - 1, _scan_flags(reverse, exclusive, a_per_segment), _p(out)))
         return out
 
     def g1_msm_batch(self, p, k, offsets):
@@ -591,6 +629,15 @@ class Engine:
         if o.size != m + 1:
             raise ValueError(f"{m} segments need {m + 1} offsets, got {o.size}")
         _native.check(self._lib.bn254_fr_dot_batch_dev(self._h, d_coeff, d_index, d_x, nx, _p(o), m, d_out, stream))
+
+    def fr_scan_batch_dev(self, d_a, d_b, d_init, offsets, m, d_out, reverse=False, exclusive=False, a_per_segment=False, stream=0):
+        """device pointers a, b (offsets[m] records of 32 bytes; a_per_segment: a has m; either may be None), init (m records, or None) and
+        out (offsets[m] records; may be d_a or d_b), ordered on `stream`; `offsets` is a HOST sequence of m + 1 CSR offsets, read before the
+        call returns"""
+        o = _offsets(offsets)
+        if o.size != m + 1:
+            raise ValueError(f"{m} segments need {m + 1} offsets, got {o.size}")
+        _native.check(self._lib.bn254_fr_scan_batch_dev(self._h, d_a, d_b, d_init, _p(o), m, _scan_flags(reverse, exclusive, a_per_segment), d_out, stream))
 
     def g1_mul_base_batch_dev(self, base, d_k, d_out, n, stream=0):
         """`base` is a HOST point (12 uint64 words), read before the call returns; d_k, d_out device pointers (n records), ordered on `stream`"""

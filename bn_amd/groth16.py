@@ -206,7 +206,7 @@ def setup(r1cs, rng, engine=None):
     rng: an object with .bytes(n) (a numpy Generator).  The five scalars are drawn in that order, each as 64 bytes little endian mod r, and
     drawn again while zero (tau: while tau^n == 1, where the domain's vanishing polynomial is zero).
     With n the domain size (the next power of two >= rows) and H its subgroup: the Lagrange values L_j(tau), j < n, are the inverse transform
-    of (tau^k)_k; u_i(tau) = sum_j A[j,i] L_j(tau) and likewise v_i, w_i for B, C are ONE sparse matrix-vector product over the three
+    of (tau^k)_k, which are ONE scan (poly.powers); u_i(tau) = sum_j A[j,i] L_j(tau) and likewise v_i, w_i for B, C are ONE sparse matrix-vector product over the three
     transposed matrices (transposed with numpy on the host); the combinations (beta u_i + alpha v_i + w_i) / gamma for i <= l, / delta for
     i > l, and tau^k (tau^n - 1) / delta for k <= n - 2, are batched field arithmetic; every group element is a fixed-base multiple of the
     generator (one call per group)."""
@@ -221,10 +221,7 @@ def setup(r1cs, rng, engine=None):
         if v and not (len(trap) == 4 and pow(v, n, R_MOD) == 1):
             trap.append(v)
     alpha, beta, gamma, delta, tau = trap
-    powers = [1]
-    for _ in range(n - 1):
-        powers.append(powers[-1] * tau % R_MOD)
-    P = _limbs(powers)
+    P = poly.powers(Fr(tau), n, engine=e, limbs=True)
     lagrange = e.fr_ntt_batch(P, log_n, inverse=True)
     offsets, index, coeff = _stacked([_transposed(o, i, c, nv) for o, i, c in mats])
     uvw = e.fr_dot_batch(coeff, lagrange, offsets, index)

@@ -214,6 +214,19 @@ inline std::vector<Fr> fr_dot(const std::vector<Fr> &coeff, const std::vector<ui
                              offsets.data(), out.size(), reinterpret_cast<bn_fr *>(out.data())));
     return out;
 }
+// out[t] = a[t] * prev + b[t] over the terms of every segment [offsets[j], offsets[j+1]) in order, prev = out[t-1] or init[j] at the segment's
+// first term: segmented prefix sums (a: nullptr), prefix products (b: nullptr), powers and Horner's rule (BN254_SCAN_A_PER_SEGMENT: a holds
+// one factor per segment).  init: nullptr for Fr::zero() with b, Fr::one() without.  flags: BN254_SCAN_*.  One output per term.
+inline std::vector<Fr> fr_scan(const std::vector<Fr> *a, const std::vector<Fr> *b, const std::vector<Fr> *init, const std::vector<size_t> &offsets, unsigned flags = 0) {
+    if (offsets.empty() || (!a && !b)) throw std::invalid_argument("fr_scan: no offsets, or neither a nor b");
+    const size_t m = offsets.size() - 1, n = offsets.back();
+    if ((b && b->size() != n) || (init && init->size() != m) || (a && a->size() != ((flags & BN254_SCAN_A_PER_SEGMENT) ? m : n)))
+        throw std::invalid_argument("fr_scan: offsets, a, b and init disagree in length");
+    std::vector<Fr> out(n);
+    auto ptr = [](const std::vector<Fr> *v) { return v ? reinterpret_cast<const bn_fr *>(v->data()) : nullptr; };
+    check(bn254_fr_scan_batch(nullptr, ptr(a), ptr(b), ptr(init), offsets.data(), m, flags, reinterpret_cast<bn_fr *>(out.data())));
+    return out;
+}
 // out[i] = (a[i] == b[i]) as group elements, whatever their Jacobian representations (groups/mod.rs:83-109): nothing is normalized
 inline std::vector<bool> g1_eq(const std::vector<G1> &a, const std::vector<G1> &b) {
     if (a.size() != b.size()) throw std::invalid_argument("g1_eq: length mismatch");

@@ -43,6 +43,9 @@
  *   bn254_fr_dot_batch     out[j] = sum of coeff[t] * x[index[t]] over t in [offsets[j], offsets[j+1]): a sparse matrix in CSR form times a vector over Fr
  *                          (lib.rs:33-53 Add and Mul, folded per row); no counterpart in the reference - the witness map of an R1CS
  *   bn254_fr_dot_batch_dev the same on device-resident coeff, index, x and out, asynchronous on the caller's stream
+ *   bn254_fr_scan_batch    out[t] = a[t] * out[t-1] + b[t] over the terms of every segment, from init[j]: segmented prefix sums, prefix products, powers and
+ *                          Horner's rule over Fr (lib.rs:33-53 Add and Mul, chained per segment); no counterpart in the reference
+ *   bn254_fr_scan_batch_dev the same on device-resident a, b, init and out, asynchronous on the caller's stream
  *   bn254_g2_precompute    coeffs[i][0..102) = q[i].to_affine().precompute().coeffs   groups/mod.rs:557-588 (Q != infinity)
  *   bn254_pairing_prepared_batch  out[i] = final_exponentiation(prepared.miller_loop(p[i]))   groups/mod.rs:486-519,768
  *   bn254_gt_mul_batch     out[i] = a[i] * b[i]                                     lib.rs:175-179, fields/fq12.rs:295-307
@@ -81,6 +84,7 @@
      bn254_fr_ntt_batch serialises on the context in the same way (its mutex for the whole call); bn254_fr_root_of_unity touches no
      context and no device.
      bn254_fr_dot_batch serialises on the context in the same way (its mutex for the whole call).
+     bn254_fr_scan_batch serialises on the context in the same way (its mutex for the whole call).
  *     bn254_pairing_product_batch_prepared_native serialises on the context like them; its handle is immutable and shared freely.
  *     Use one context per thread (or bn254_multi_*) for more overlap;
  *     bn254_ctx_set_option is atomic, but set options before concurrent use: a call in flight may run some
@@ -108,6 +112,9 @@
      bn254_fr_dot_batch_dev reads its HOST `offsets` before it returns (the launches are planned from them; its `d_index` is device memory and
      read by the kernels only); its work list and partial sums are context-owned scratch under the same event ordering.  It waits on the
      host only for the upload of the previous work list that went through the same pinned staging, and reads nothing back.
+     bn254_fr_scan_batch_dev reads its HOST `offsets` before it returns in the same way; its work list, the maps of its pieces and their
+     carries are context-owned scratch under the same event ordering, and it too waits on the host only for the previous upload through the
+     pinned staging and reads nothing back.
  */
 #ifndef BN254_HIP_H
 #define BN254_HIP_H
@@ -458,6 +465,38 @@ int bn254_fr_ntt_batch(bn254_ctx *ctx, const bn_fr *in, bn_fr *out, int log_n, s
    n > 2^40, a NULL coeff / x (n > 0) or out, index == NULL with nx != n, an index[t] >= nx (the caller gets an error, never a wrong sum).
    m == 0 returns BN254_OK and writes nothing.  Threading: see above - the host-buffer entry point holds the context's mutex for the whole call. */
 int bn254_fr_dot_batch(bn254_ctx *ctx, const bn_fr *coeff, const uint64_t *index, const bn_fr *x, size_t nx, const size_t *offsets, size_t m, bn_fr *out);
+/* Segmented scans over Fr: the first-order linear recurrence, every segment in one call.  Segments in CSR form exactly as for
+   bn254_fr_dot_batch: offsets[0..m] with offsets[0] == 0, non-decreasing, n = offsets[m] terms; `out` has n records, one per term.  For the
+   terms t of segment j, in order,
+       out[t] = a[t] * prev + b[t],   prev = out[t-1], or init[j] at the segment's first term.
+   a == NULL: every a[t] is one - segmented prefix sums, and no product is executed.  b == NULL: every b[t] is zero - segmented prefix
+   products.  Both NULL: BN254_E_BAD_ARG.  init == NULL: Fr::zero() when b is given, Fr::one() when it is not; otherwise m records.
+   flags:
+     BN254_SCAN_REVERSE        the recurrence runs from each segment's last term to its first (prev = out[t+1]): the forward scan of the
+                               reversed segment, reversed
+     BN254_SCAN_EXCLUSIVE      out[t] = prev, the value BEFORE term t is applied: the first term gets init[j], the segment's total is not written
+     BN254_SCAN_A_PER_SEGMENT  a has m records and a[j] multiplies every term of segment j: powers (b == NULL, EXCLUSIVE, init one), Horner's
+                               rule and the division by X - z (REVERSE, b the coefficients), many polynomials at many points
+   Any other bit: BN254_E_BAD_ARG.  Inputs are canonical Montgomery images; every product and sum is canonical, hence the bytes are those of
+   the integer recurrence however the work is cut.  An empty segment writes nothing.  `out` may be exactly `a` or exactly `b` (a term is
+   read before its output is written) - except `a` with BN254_SCAN_A_PER_SEGMENT, whose m records are not the n of `out`.  `offsets` is HOST
+   memory.
+   How: a term is the affine map y -> a y + b, and composing such maps is associative, so no lane's chain depends on the data and no
+   workgroup waits for another.  The host cuts every segment into pieces of at most P = 32 consecutive terms.  A segment of at most P terms
+   is one lane, one pass, straight to out.  A longer one takes: reduce - a lane per piece composes its terms into the piece's map (A, B), two
+   products per term (one without b, none without a); up levels - a lane composes at most F = 16 consecutive maps into one, until at most F
+   are left; down levels - a lane takes the value in front of its group (at the top init[j]) and walks its at most F maps, leaving the
+   value in front of every child; apply - a lane per piece runs the recurrence from the value in front of it, one product per term.  With
+   u = max(0, ceil(log16(ceil(L / 32))) - 1) that is 1 + u + (u + 1) + 1 = 2 u + 3 levels for a segment of L > 32 terms, ordered by the stream;
+   every level runs as sub-launches of at most 2^22 lanes.  The work list (24 bytes per piece) is built on the host and uploaded with the
+   call; maps and carries (96 bytes per piece and per group) are context-owned scratch.  Timings: profiles/r16_scan.txt (tools/time_scan.py).
+   Errors (BN254_E_BAD_ARG, checked before any device is touched): a and b both NULL, an unknown flag, offsets == NULL, offsets[0] != 0,
+   decreasing offsets, n > 2^40, a NULL out.  m == 0 returns BN254_OK before anything is looked at, n == 0 after these checks; neither touches a
+   device.  Threading: see above - the host-buffer entry point holds the context's mutex for the whole call. */
+#define BN254_SCAN_REVERSE 1
+#define BN254_SCAN_EXCLUSIVE 2
+#define BN254_SCAN_A_PER_SEGMENT 4
+int bn254_fr_scan_batch(bn254_ctx *ctx, const bn_fr *a, const bn_fr *b, const bn_fr *init, const size_t *offsets, size_t m, unsigned int flags, bn_fr *out);
 
 /* ---- one node, several GPUs (north_star: independent batches shard across the GPUs; ONE exchange for the multi-pairing) --- */
 /* `devices[0..ndev)`: HIP device index of every rank (NULL = 0..ndev-1).  One context and one host thread per rank.  A device may
@@ -613,6 +652,12 @@ int bn254_fr_ntt_batch_dev(bn254_ctx *ctx, const void *d_in, void *d_out, int lo
    anything through it, so that term contributes zero.  Work list and partial sums are context-owned scratch (see Threading). */
 int bn254_fr_dot_batch_dev(bn254_ctx *ctx, const void *d_coeff, const void *d_index, const void *d_x, size_t nx, const size_t *offsets, size_t m, void *d_out,
                            void *stream);
+/* bn254_fr_scan_batch on device-resident a, b (n records of 32 bytes, 16-byte aligned; with BN254_SCAN_A_PER_SEGMENT a has m), init (m records,
+   or NULL) and out (n records; may be exactly d_a or d_b as above); `offsets` (m+1 entries) is HOST memory - the only thing the call reads:
+   the launches are planned from it - and may be freed on return.  It waits for nothing and reads nothing back.  Work list, maps and
+   carries are context-owned scratch (see Threading). */
+int bn254_fr_scan_batch_dev(bn254_ctx *ctx, const void *d_a, const void *d_b, const void *d_init, const size_t *offsets, size_t m, unsigned int flags, void *d_out,
+                            void *stream);
 /* raw Jacobian result of the reference's MSB-first double-and-add (what G::random produces, groups/mod.rs:220-222):
    used to generate benchmark inputs with z != 1 on the device */
 int bn254_g1_mul_jacobian_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, void *d_out, size_t n, void *stream);
@@ -632,6 +677,7 @@ int bn254_profile_enable(bn254_ctx *ctx, int on);
 int bn254_profile_reset(bn254_ctx *ctx);
 /* kernel: "miller", "miller_shared", "miller_wave", "miller_quad", "pairing_wave", "final_exp", "final_exp_wave", "final_exp_quad", "exp_by_neg_z", "gt_product", "gt_tail", "gt_segment", "gt_tail_seg", "g1_mul", "g2_mul", "gt_mul", "gt_pow", "g2_precompute", "miller_prepared", "g2_prepare_native", "miller_native", "miller_native_shared", "miller_native_seg", "g2_gather", "wire_encode", "wire_decode", "fr_add", "fr_mul", "fr_inverse", "fr_pow", "fr_interpret", "gt_inverse", "g1_add", "g2_add", "g1_msm_mul", "g1_msm_fold", "g2_msm_mul", "g2_msm_fold", "g1_msm_digits", "g1_msm_bucket", "g1_msm_reduce", "g2_msm_digits", "g2_msm_bucket", "g2_msm_reduce", "g1_mul_base", "g2_mul_base", "g1_base_table", "g2_base_table", "g1_normalize", "g2_normalize", "g1_eq", "g2_eq".
    of bn254_fr_dot_batch: "fr_dot" (the pieces: products and sums), "fr_dot_fold" (the levels over the partial sums);
+   of bn254_fr_scan_batch: "fr_scan" (the apply level, direct segments among it), "fr_scan_reduce" (the maps of the pieces), "fr_scan_up", "fr_scan_down" (the levels over the maps);
    and, of bn254_fr_ntt_batch: "ntt" (the passes), "ntt_table" (the builds of the twiddle tables).
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);
