@@ -95,6 +95,9 @@ extern "C" {
     fn bn254_fr_ntt_batch(ctx: *mut c_void, input: *const Fr, out: *mut Fr, log_n: c_int, count: usize, inverse: c_int, shift: *const Fr) -> c_int;
     fn bn254_fr_dot_batch(ctx: *mut c_void, coeff: *const Fr, index: *const u64, x: *const Fr, nx: usize, offsets: *const usize, m: usize, out: *mut Fr) -> c_int;
     fn bn254_fr_scan_batch(ctx: *mut c_void, a: *const Fr, b: *const Fr, init: *const Fr, offsets: *const usize, m: usize, flags: c_int, out: *mut Fr) -> c_int;
+    fn bn254_fr_mle_eq(ctx: *mut c_void, z: *const Fr, nv: c_int, out: *mut Fr) -> c_int;
+    fn bn254_fr_mle_fold(ctx: *mut c_void, input: *const Fr, len: usize, r: *const Fr, out: *mut Fr) -> c_int;
+    fn bn254_fr_sumcheck_round(ctx: *mut c_void, tables: *const Fr, n: usize, k: usize, group_offsets: *const usize, group_tables: *const u64, group_coeff: *const Fr, g: usize, degree: c_int, out: *mut Fr) -> c_int;
     fn bn254_fr_add_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_out: *mut c_void, n: usize, negate_b: c_int, stream: *mut c_void) -> c_int;
     fn bn254_fr_mul_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_inverse_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_out: *mut c_void, d_ok: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
@@ -103,6 +106,9 @@ extern "C" {
     fn bn254_fr_ntt_batch_dev(ctx: *mut c_void, d_in: *const c_void, d_out: *mut c_void, log_n: c_int, count: usize, inverse: c_int, shift: *const Fr, stream: *mut c_void) -> c_int;
     fn bn254_fr_dot_batch_dev(ctx: *mut c_void, d_coeff: *const c_void, d_index: *const c_void, d_x: *const c_void, nx: usize, offsets: *const usize, m: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn bn254_fr_scan_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_init: *const c_void, offsets: *const usize, m: usize, flags: c_int, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn bn254_fr_mle_eq_dev(ctx: *mut c_void, d_z: *const c_void, nv: c_int, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn bn254_fr_mle_fold_dev(ctx: *mut c_void, d_in: *const c_void, len: usize, r: *const Fr, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn bn254_fr_sumcheck_round_dev(ctx: *mut c_void, d_tables: *const c_void, n: usize, k: usize, group_offsets: *const usize, group_tables: *const u64, group_coeff: *const Fr, g: usize, degree: c_int, d_out: *mut c_void, stream: *mut c_void) -> c_int;
 }
 
 /// One line-function coefficient of a prepared G2 point: the crate's `EllCoeffs { ell_0, ell_vw, ell_vv: Fq2 }` (src/groups/mod.rs:472-476) as the
@@ -376,6 +382,38 @@ pub fn fr_scan(a: Option<&[Fr]>, b: Option<&[Fr]>, init: Option<&[Fr]>, offsets:
     let mut out = vec![Fr::zero(); n];
     let ptr = |v: Option<&[Fr]>| v.map_or(std::ptr::null(), |s| s.as_ptr());
     check(unsafe { bn254_fr_scan_batch(std::ptr::null_mut(), ptr(a), ptr(b), ptr(init), offsets.as_ptr(), m, flags, out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// The table of `eq(z, .)` over the hypercube of `z.len()` variables: `out[i] = prod_j (if bit j of i { z[j] } else { 1 - z[j] })`, `2^z.len()`
+/// values; no variables give `[Fr::one()]`.
+pub fn fr_mle_eq(z: &[Fr]) -> Result<Vec<Fr>, GpuError> {
+    assert!(z.len() <= 30);
+    let mut out = vec![Fr::zero(); 1usize << z.len()];
+    check(unsafe { bn254_fr_mle_eq(std::ptr::null_mut(), z.as_ptr(), z.len() as c_int, out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// `out[i] = a[i] + r * (a[i + a.len() / 2] - a[i])`: the multilinear table `a` (index `i` is the point whose variable `j` is bit `j` of `i`) with
+/// its MOST significant variable bound to `r`.  `k` tables stored index-major (`a[i * k + j]`) are folded by the one call.
+pub fn fr_mle_fold(a: &[Fr], r: &Fr) -> Result<Vec<Fr>, GpuError> {
+    assert!(a.len() % 2 == 0);
+    let mut out = vec![Fr::zero(); a.len() / 2];
+    check(unsafe { bn254_fr_mle_fold(std::ptr::null_mut(), a.as_ptr(), a.len(), r as *const Fr, out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// The round polynomial of a sumcheck at `t = 0 ..= degree`: `out[t] = sum over i < n / 2 and the groups c of group_coeff[c] * prod over j in
+/// group c of (T_j[i] + t * (T_j[i + n / 2] - T_j[i]))` with `T_j[i] = tables[i * k + j]`, `n = tables.len() / k`.  Group `c` holds the table
+/// numbers `group_tables[group_offsets[c]..group_offsets[c + 1]]` (1 to `degree` of them, a table may repeat).
+pub fn fr_sumcheck_round(tables: &[Fr], k: usize, group_offsets: &[usize], group_tables: &[u64], group_coeff: &[Fr], degree: usize) -> Result<Vec<Fr>, GpuError> {
+    assert!(k >= 1 && tables.len() % (2 * k) == 0 && !group_offsets.is_empty());
+    let g = group_offsets.len() - 1;
+    assert!(group_coeff.len() == g && *group_offsets.last().unwrap() == group_tables.len());
+    let mut out = vec![Fr::zero(); degree + 1];
+    check(unsafe {
+        bn254_fr_sumcheck_round(std::ptr::null_mut(), tables.as_ptr(), tables.len() / k, k, group_offsets.as_ptr(), group_tables.as_ptr(), group_coeff.as_ptr(), g, degree as c_int, out.as_mut_ptr())
+    })?;
     Ok(out)
 }
 

@@ -405,6 +405,40 @@ def fr_scan_batch(a, b, offsets, init=None, reverse=False, exclusive=False, a_pe
     return [Fr.from_limbs(r) for r in out]
 
 
+def fr_mle_eq(z, engine=None):
+    """The table of eq(z, .) over the hypercube of nv = len(z) variables -> list of 2^nv Fr: out[i] = prod_j (z[j] if bit j of i else 1 - z[j]), the
+    multilinear polynomial that is one at the point z of the hypercube and zero at every other.  z: a sequence of Fr or an (nv,4) uint64
+    array; no variables give [Fr.one()].  ValueError for more than 30 variables."""
+    from .engine import _mle_eq_args
+    Z = _mle_eq_args(_scalar_array(z))
+    return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_mle_eq(Z)]
+
+
+def fr_mle_fold(a, r, engine=None):
+    """[a[i] + r * (a[i + len(a) // 2] - a[i]) for i in range(len(a) // 2)] -> list of Fr: the multilinear table a with its MOST significant
+    variable bound to r.  a: a sequence of Fr or an (n,4) uint64 array, n even; r: an Fr.  ValueError for an odd length."""
+    from .engine import _mle_fold_args
+    A, rr = _mle_fold_args(_scalar_array(a), r)
+    return [Fr.from_limbs(x) for x in (engine or default_engine()).fr_mle_fold(A, rr)]
+
+
+def fr_sumcheck_round(tables, groups, degree=None, engine=None):
+    """The round polynomial of a sumcheck over sum_c coeff_c * prod_{j in group c} T_j, at t = 0 .. degree -> list of degree + 1 Fr:
+        out[t] = sum over i < n / 2 and the groups c of coeff_c * prod_j (T_j[i] + t * (T_j[i + n / 2] - T_j[i]))
+    - the most significant variable is the one the round binds, and out[0] + out[1] is the sum over all n indices.  tables: a sequence of k
+    tables of n Fr each, or an (n, k, 4) uint64 array with table j at index i in [i, j]; groups: a list of (coeff, [table numbers]), a table
+    may repeat within a group; degree: None for the longest group.  ValueError, before any device call, naming the operand: an odd n or
+    n < 2, more than 16 tables or groups, a group that is empty, longer than the degree or names a table that is not there."""
+    from .engine import _sumcheck_args
+    if not isinstance(tables, np.ndarray):
+        cols = [_scalar_array(t) for t in tables]
+        if len({c.shape[0] for c in cols}) > 1:
+            raise ValueError(f"tables differ in length: {[c.shape[0] for c in cols]}")
+        tables = np.stack(cols, axis=1) if cols else np.zeros((0, 0, 4), np.uint64)
+    t, _, _, _, degree = _sumcheck_args(tables, groups, degree)
+    return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_sumcheck_round(t, groups, degree)]
+
+
 def _shift_limbs(shift):
     if shift is None:
         return None

@@ -1,0 +1,173 @@
+// Multilinear tables and sumcheck rounds over Fr on the device (include/bn254_hip.h bn254_fr_mle_eq, bn254_fr_mle_fold, bn254_fr_sumcheck_round and
+// their _dev twins): the kernels - instances of bn254_fr_decode_k<Op> like the other integer kernels, one lane of the bodies of mle_ops.hpp
+// each -, the levels host_plan.hpp's bn_sumcheck_plan computes as sub-launches, and the six entry points.
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+
+#include "mle_ops.hpp"
+#include "host_ctx.hpp"
+
+using namespace bn254;
+
+namespace {
+constexpr unsigned MLE_BLOCK = 256;
+
+// lanes [lo, lo + n) of a call: a sub-launch
+struct FrMleEqOp {
+    const uint32_t *z; uint32_t nv; uint32_t *out; uint64_t lo; uint32_t n;
+    __device__ __forceinline__ void operator()() const {
+        const uint32_t i = blockIdx.x * MLE_BLOCK + threadIdx.x;
+        if (i < n) fr_mle_eq_body(z, nv, out, lo + i);
+    }
+};
+struct FrMleFoldOp {
+    const uint32_t *in; Fr r; uint32_t *out; uint64_t half, lo; uint32_t n;
+    __device__ __forceinline__ void operator()() const {
+        const uint32_t i = blockIdx.x * MLE_BLOCK + threadIdx.x;
+        if (i < n) fr_mle_fold_body(in, r, out, half, lo + i);
+    }
+};
+template <int D>
+struct FrSumcheckRoundOp {
+    const uint32_t *tables; uint64_t h; uint32_t k; BnSumcheckDesc desc; uint64_t lanes; uint32_t *dst; uint64_t lo; uint32_t n;
+    __device__ __forceinline__ void operator()() const {
+        const uint32_t i = blockIdx.x * MLE_BLOCK + threadIdx.x;
+        if (i < n) fr_sumcheck_round_body<D>(tables, h, k, desc, lanes, dst, lo + i);
+    }
+};
+struct FrSumcheckSumOp {
+    const uint32_t *src; uint64_t cnt; uint32_t F; uint32_t *dst; uint64_t lo; uint32_t n;
+    __device__ __forceinline__ void operator()() const {
+        const uint32_t i = blockIdx.x * MLE_BLOCK + threadIdx.x;
+        if (i < n) fr_sumcheck_sum_body(src, cnt, F, dst, lo + i);
+    }
+};
+template <class Op>
+__global__ void __launch_bounds__(MLE_BLOCK) bn254_fr_decode_k(Op op) { op(); }
+
+template <class Op>
+int mle_launch(const Op &op, size_t lanes, hipStream_t s) {
+    hipLaunchKernelGGL(bn254_fr_decode_k<Op>, dim3((unsigned)((lanes + MLE_BLOCK - 1) / MLE_BLOCK)), dim3(MLE_BLOCK), 0, s, op);
+    return (int)hipGetLastError();
+}
+
+// tests and tools/time_mle.py only: the sub-launch size (0 = BN_LAUNCH_MAX) and the piece length the sweep times (0 = the shipped constant)
+std::atomic<size_t> g_mle_launch_max;
+std::atomic<unsigned> g_sumcheck_piece;
+size_t mle_step() { const size_t set = g_mle_launch_max.load(std::memory_order_relaxed); return set ? set : BN_LAUNCH_MAX; }
+unsigned sumcheck_piece() { const unsigned set = g_sumcheck_piece.load(std::memory_order_relaxed); return set ? set : FR_SUMCHECK_PIECE; }
+
+int eq_run(bn254_ctx *c, const void *d_z, int nv, void *d_out, hipStream_t s) {
+    return bn_for_parts((size_t)1 << nv, mle_step(), [&](size_t lo, size_t cnt) -> int {
+        BnScope sc(c, s, "fr_mle_eq");
+        return mle_launch(FrMleEqOp{(const uint32_t *)d_z, (uint32_t)nv, (uint32_t *)d_out, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
+    });
+}
+int fold_run(bn254_ctx *c, const void *d_in, size_t len, const bn_fr *r, void *d_out, hipStream_t s) {
+    Fr rr;
+    memcpy(rr.w, r->l, sizeof rr.w);
+    return bn_for_parts(len / 2, mle_step(), [&](size_t lo, size_t cnt) -> int {
+        BnScope sc(c, s, "fr_mle_fold");
+        return mle_launch(FrMleFoldOp{(const uint32_t *)d_in, rr, (uint32_t *)d_out, (uint64_t)(len / 2), (uint64_t)lo, (uint32_t)cnt}, cnt, s);
+    });
+}
+template <int D>
+int round_launch(const uint32_t *tables, size_t h, size_t k, const BnSumcheckDesc &desc, size_t lanes, uint32_t *dst, size_t lo, size_t cnt, hipStream_t s) {
+    return mle_launch(FrSumcheckRoundOp<D>{tables, (uint64_t)h, (uint32_t)k, desc, (uint64_t)lanes, dst, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
+}
+// scratch guard held by the caller.  The round kernel, then the sum levels in the plan's order, each as sub-launches of at most mle_step()
+// lanes; the stream orders them.
+int round_run(bn254_ctx *c, const void *d_tables, size_t n, size_t k, const BnSumcheckDesc &desc, int degree, void *d_out, hipStream_t s) {
+    const size_t h = n / 2;
+    const BnSumcheckPlan plan = bn_sumcheck_plan(h, (unsigned)degree, sumcheck_piece(), FR_SUMCHECK_FAN);
+    int rc = c->mle_ws.reserve(plan.slots * sizeof(bn_fr)); if (rc) return rc;
+    uint32_t *const ws = (uint32_t *)c->mle_ws.p, *const out = (uint32_t *)d_out;
+    const uint32_t *tables = (const uint32_t *)d_tables;
+    rc = bn_for_parts(plan.lanes, mle_step(), [&](size_t lo, size_t cnt) -> int {
+        BnScope sc(c, s, "fr_sumcheck_round");
+        uint32_t *dst = plan.levels.empty() ? out : ws;
+        switch (degree) {
+        case 1: return round_launch<1>(tables, h, k, desc, plan.lanes, dst, lo, cnt, s);
+        case 2: return round_launch<2>(tables, h, k, desc, plan.lanes, dst, lo, cnt, s);
+        case 3: return round_launch<3>(tables, h, k, desc, plan.lanes, dst, lo, cnt, s);
+        default: return round_launch<4>(tables, h, k, desc, plan.lanes, dst, lo, cnt, s);
+        }
+    });
+    if (rc) return rc;
+    for (const BnSumcheckLevel &lv : plan.levels) {
+        rc = bn_for_parts(lv.lanes, mle_step(), [&](size_t lo, size_t cnt) -> int {
+            BnScope sc(c, s, "fr_sumcheck_sum");
+            return mle_launch(FrSumcheckSumOp{ws + 8 * lv.src, (uint64_t)lv.cnt, FR_SUMCHECK_FAN, lv.to_out ? out : ws + 8 * lv.dst, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
+        });
+        if (rc) return rc;
+    }
+    return BN254_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// order of the checks everywhere: arguments (nothing of them touches a device), then context and device; nothing waits, nothing is read back
+int bn254_fr_mle_eq_dev(bn254_ctx *ctx, const void *d_z, int nv, void *d_out, void *stream) {
+    int rc = bn_mle_eq_check(d_z, nv, d_out); if (rc) return rc;
+    if ((rc = bn_get_ctx(ctx))) return rc;
+    BnDev d(ctx, stream); if (!d.go) return d.rc;
+    return bn_no_throw([&] { return eq_run(ctx, d_z, nv, d_out, d.s); });
+}
+int bn254_fr_mle_eq(bn254_ctx *ctx, const bn_fr *z, int nv, bn_fr *out) {
+    int rc = bn_mle_eq_check(z, nv, out); if (rc) return rc;
+    BnHost h(ctx); if (h.rc) return h.rc;
+    return bn_staged(ctx, {z, (size_t)nv * sizeof(bn_fr)}, {nullptr, 0}, out, sizeof(bn_fr) << nv, nullptr, 0,
+                     [&](const BnStaged &d) { return bn254_fr_mle_eq_dev(ctx, d.in[0], nv, d.out, ctx->stream); });
+}
+int bn254_fr_mle_fold_dev(bn254_ctx *ctx, const void *d_in, size_t len, const bn_fr *r, void *d_out, void *stream) {
+    if (len == 0) return BN254_OK;
+    int rc = bn_mle_fold_check(d_in, len, r, d_out); if (rc) return rc;
+    if ((rc = bn_get_ctx(ctx))) return rc;
+    BnDev d(ctx, stream); if (!d.go) return d.rc;
+    return bn_no_throw([&] { return fold_run(ctx, d_in, len, r, d_out, d.s); });
+}
+int bn254_fr_mle_fold(bn254_ctx *ctx, const bn_fr *in, size_t len, const bn_fr *r, bn_fr *out) {
+    if (len == 0) return BN254_OK;
+    int rc = bn_mle_fold_check(in, len, r, out); if (rc) return rc;
+    BnHost h(ctx); if (h.rc) return h.rc;
+    return bn_staged(ctx, {in, len * sizeof(bn_fr)}, {nullptr, 0}, out, len / 2 * sizeof(bn_fr), nullptr, 0,
+                     [&](const BnStaged &d) { return bn254_fr_mle_fold_dev(ctx, d.in[0], len, r, d.out, ctx->stream); });
+}
+int bn254_fr_sumcheck_round_dev(bn254_ctx *ctx, const void *d_tables, size_t n, size_t k, const size_t *group_offsets, const uint64_t *group_tables, const bn_fr *group_coeff,
+                                size_t g, int degree, void *d_out, void *stream) {
+    BnSumcheckDesc desc;
+    int rc = bn_sumcheck_check(d_tables, n, k, group_offsets, group_tables, group_coeff, g, degree, d_out, &desc); if (rc) return rc;      // before any device lookup
+    if ((rc = bn_get_ctx(ctx))) return rc;
+    BnDev d(ctx, stream); if (!d.go) return d.rc;
+    BnScratchGuard guard(ctx, d.s); if (guard.rc) return guard.rc;
+    return bn_no_throw([&] { return round_run(ctx, d_tables, n, k, desc, degree, d_out, d.s); });
+}
+int bn254_fr_sumcheck_round(bn254_ctx *ctx, const bn_fr *tables, size_t n, size_t k, const size_t *group_offsets, const uint64_t *group_tables, const bn_fr *group_coeff, size_t g,
+                            int degree, bn_fr *out) {
+    BnSumcheckDesc desc;
+    int rc = bn_sumcheck_check(tables, n, k, group_offsets, group_tables, group_coeff, g, degree, out, &desc); if (rc) return rc;          // before any device lookup
+    BnHost h(ctx); if (h.rc) return h.rc;
+    return bn_staged(ctx, {tables, n * k * sizeof(bn_fr)}, {nullptr, 0}, out, (size_t)(degree + 1) * sizeof(bn_fr), nullptr, 0, [&](const BnStaged &d) {
+        return bn254_fr_sumcheck_round_dev(ctx, d.in[0], n, k, group_offsets, group_tables, group_coeff, g, degree, d.out, ctx->stream);
+    });
+}
+
+// internal (not in the header; tests and tools/time_mle.py): the shipped piece length and fan of the round, an override of the sub-launch
+// size of all three calls (0 restores BN_LAUNCH_MAX) so that a test reaches the seam between two sub-launches with a handful of lanes, and
+// - for the sweep only - a process-wide override of the piece length (0 restores the shipped one; same bytes whatever is set)
+unsigned bn254_fr_sumcheck_piece(void) { return FR_SUMCHECK_PIECE; }
+unsigned bn254_fr_sumcheck_fan(void) { return FR_SUMCHECK_FAN; }
+int bn254_fr_mle_set_launch_max(size_t lanes) {
+    if (lanes > BN_LAUNCH_MAX) return BN254_E_BAD_ARG;
+    g_mle_launch_max.store(lanes, std::memory_order_relaxed);
+    return BN254_OK;
+}
+int bn254_fr_sumcheck_set_piece(unsigned P) {
+    if (P > 64) return BN254_E_BAD_ARG;
+    g_sumcheck_piece.store(P, std::memory_order_relaxed);
+    return BN254_OK;
+}
+
+}  // extern "C"

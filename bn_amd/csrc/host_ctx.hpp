@@ -129,6 +129,7 @@ struct bn254_ctx {
     BnBuf ntt_ws;                       // the arrays between the passes of one group of transforms (one, or two for an odd number of passes in place)
     BnBuf dot_ws;                       // bn254_fr_dot_batch: the partial sums of the segments longer than one piece (32 bytes each; its work list travels through seg_plan)
     BnBuf scan_ws;                      // bn254_fr_scan_batch: per scratch slot of its plan a map (A, B) and a carry, three arrays of 32-byte records (its work list travels through seg_plan)
+    BnBuf mle_ws;                       // bn254_fr_sumcheck_round: the partial sums of the round kernel's lanes and of the sum levels, [t][lane] per level (32 bytes each)
     BnBuf base_stage;                   // the base of a table build on the device ...
     BnBuf base_stage_host{nullptr, 0, true};    // ... and its pinned staging, rewritten only after base_stage_ev (its last copy) completed
     hipEvent_t base_stage_ev = nullptr;

@@ -1,5 +1,5 @@
 // Host arithmetic over sizes and offsets: the argument checks that need no device, the work lists of the segmented folds, the cutting of a
-// prepared batch into Miller pieces, the workspace of the bucket method and its tail scalars, the scalars of the fixed-base tables, the passes of a transform, the pieces of a sparse linear map, the levels of a segmented scan.  Plain C++17: nothing here touches a device, so
+// prepared batch into Miller pieces, the workspace of the bucket method and its tail scalars, the scalars of the fixed-base tables, the passes of a transform, the pieces of a sparse linear map, the levels of a segmented scan and of a sumcheck round.  Plain C++17: nothing here touches a device, so
 // tests/hostsim/ compiles it with g++ and tests/test_host_plan.py replays the plans on the CPU.  (io.hpp: the two records the kernels read.)
 #pragma once
 #include <algorithm>
@@ -482,5 +482,59 @@ inline BnScanPlan bn_scan_plan(const size_t *off, size_t m, size_t P, size_t F, 
     for (const auto &l : up) { plan.levels.push_back({BN_SCAN_UP, plan.pieces.size(), l.size()}); plan.pieces.insert(plan.pieces.end(), l.begin(), l.end()); }
     for (const auto &l : down) { plan.levels.push_back({BN_SCAN_DOWN, plan.pieces.size(), l.size()}); plan.pieces.insert(plan.pieces.end(), l.begin(), l.end()); }
     plan.levels.push_back({BN_SCAN_APPLY, 0, lanes});
+    return plan;
+}
+
+// ---- multilinear tables and sumcheck rounds over Fr (bn254_fr_mle_eq, bn254_fr_mle_fold, bn254_fr_sumcheck_round): the argument checks and the levels
+inline int bn_mle_eq_check(const void *z, int nv, const void *out) { return (nv < 0 || nv > BN254_MLE_VARS_MAX || !out || (nv && !z)) ? BN254_E_BAD_ARG : BN254_OK; }
+// for len > 0: an even number of records, one challenge
+inline int bn_mle_fold_check(const void *in, size_t len, const void *r, const void *out) { return ((len & 1) || len > BN_N_MAX || !in || !r || !out) ? BN254_E_BAD_ARG : BN254_OK; }
+// sizes, pointers and the groups in CSR form (offsets[0] == 0, every group of 1 .. degree table numbers below k); fills the record the
+// round kernel reads.  group_coeff: g Montgomery images of four 64-bit limbs, copied as eight 32-bit words.
+inline int bn_sumcheck_check(const void *tables, size_t n, size_t k, const size_t *offsets, const uint64_t *group_tables, const bn_fr *coeff, size_t g, int degree, const void *out,
+                             bn254::BnSumcheckDesc *desc) {
+    static_assert(BN254_SUMCHECK_GROUPS_MAX == bn254::BN_SUMCHECK_GROUPS && BN254_SUMCHECK_DEGREE_MAX == bn254::BN_SUMCHECK_FACTORS && BN254_SUMCHECK_TABLES_MAX <= 256,
+                  "io.hpp BnSumcheckDesc mirrors the header's limits");
+    if (!tables || !offsets || !group_tables || !coeff || !out) return BN254_E_BAD_ARG;
+    if (n < 2 || (n & 1) || k < 1 || k > BN254_SUMCHECK_TABLES_MAX || g < 1 || g > BN254_SUMCHECK_GROUPS_MAX || degree < 1 || degree > BN254_SUMCHECK_DEGREE_MAX) return BN254_E_BAD_ARG;
+    if (n > BN_N_MAX / k || offsets[0] != 0) return BN254_E_BAD_ARG;
+    memset(desc, 0, sizeof *desc);
+    desc->groups = (uint32_t)g;
+    for (size_t c = 0; c < g; ++c) {
+        if (offsets[c + 1] <= offsets[c] || offsets[c + 1] - offsets[c] > (size_t)degree) return BN254_E_BAD_ARG;
+        desc->len[c] = (uint8_t)(offsets[c + 1] - offsets[c]);
+        for (size_t f = 0; f < desc->len[c]; ++f) {
+            const uint64_t j = group_tables[offsets[c] + f];
+            if (j >= k) return BN254_E_BAD_ARG;
+            desc->table[c][f] = (uint8_t)j;
+        }
+        memcpy(desc->coeff[c], coeff[c].l, sizeof desc->coeff[c]);
+    }
+    return BN254_OK;
+}
+// A round over h = n / 2 indices: lanes = ceil(h / P) lanes of the round kernel, lane l summing the indices l, l + lanes, .. (at most P).  One
+// lane writes out and that is all.  Otherwise the lanes write (degree + 1) * lanes partial sums, laid out [t][lane], to the front of the scratch, and sum
+// levels follow: a level over cnt sums per t has (degree + 1) * ceil(cnt / F) lanes and writes as many sums, [t][lane] again, behind its
+// input - the last level (ceil(cnt / F) == 1) to out instead.  ceil(log_F lanes) levels; slots: (degree + 1) * lanes * (1 + 1/F + ..) < 2 (degree + 1) * lanes.
+// No slot is written twice, so a level may run as any number of sub-launches in any order after the level before it.
+struct BnSumcheckLevel { size_t cnt, lanes, src, dst; bool to_out; };        // src, dst: first scratch slot
+struct BnSumcheckPlan {
+    size_t lanes = 0;                                       // of the round kernel
+    std::vector<BnSumcheckLevel> levels;                    // the sum levels, in launch order
+    size_t slots = 0;                                       // scratch records of 32 bytes
+};
+inline BnSumcheckPlan bn_sumcheck_plan(size_t h, unsigned degree, size_t P, size_t F) {
+    BnSumcheckPlan plan;
+    plan.lanes = (h + P - 1) / P;
+    if (plan.lanes <= 1) return plan;
+    const size_t T = degree + 1;
+    size_t cnt = plan.lanes, src = 0;
+    plan.slots = T * cnt;
+    for (;;) {
+        const size_t cnt2 = (cnt + F - 1) / F;
+        plan.levels.push_back({cnt, T * cnt2, src, plan.slots, cnt2 == 1});
+        if (cnt2 == 1) break;
+        src = plan.slots; plan.slots += T * cnt2; cnt = cnt2;
+    }
     return plan;
 }

@@ -56,6 +56,16 @@ struct BnScanPiece {
 BN_FN uint64_t scan_piece_first(const BnScanPiece &p) { return p.src & (((uint64_t)1 << 48) - 1); }
 BN_FN uint32_t scan_piece_len(const BnScanPiece &p) { return (uint32_t)(p.src >> 48) & BN_DOT_LEN_MAX; }
 BN_FN bool scan_piece_flag(const BnScanPiece &p) { return (p.src >> 63) != 0; }
+// the products of one sumcheck round (bn254_fr_sumcheck_round): `groups` groups, group c = coeff[c] (eight words, a Montgomery image) times
+// the len[c] tables table[c][0 .. len[c]).  The same for every lane: it travels as a kernel argument.  Built on the host
+// (host_plan.hpp bn_sumcheck_desc, which checks the bounds), read by the round body of mle_ops.hpp.
+constexpr uint32_t BN_SUMCHECK_GROUPS = 16, BN_SUMCHECK_FACTORS = 4;
+struct BnSumcheckDesc {
+    uint32_t coeff[BN_SUMCHECK_GROUPS][8];
+    uint8_t table[BN_SUMCHECK_GROUPS][BN_SUMCHECK_FACTORS];
+    uint8_t len[BN_SUMCHECK_GROUPS];
+    uint32_t groups;
+};
 BN_FN bool words_all_zero(const uint32_t *w, int n) {
     uint32_t o = 0;
     for (int i = 0; i < n; ++i) o |= w[i];

@@ -1,0 +1,99 @@
+// The per-lane bodies of the multilinear kernels over Fr (bn254_mle.hip): bn254_fr_mle_eq, bn254_fr_mle_fold, bn254_fr_sumcheck_round and
+// their _dev twins.  A multilinear table of nv variables is 2^nv records; the record at index i is the value at the point whose variable j is
+// bit j of i.  Several tables of one sumcheck are stored index-major: tables[i * k + j] is table j at index i.
+//   eq      out[i] = prod_{j < nv} (bit j of i ? z[j] : 1 - z[j]): one lane per element, nv products, whatever the data
+//   fold    out[i] = in[i] + r * (in[i + half] - in[i]): binds the MOST significant variable; lane i alone touches records i and i + half
+//   round   for t = 0 .. D:  sum over i < h, over the groups c, of coeff[c] * prod_{j in group c} (T_j[i] + t (T_j[i + h] - T_j[i])).
+//           There are `lanes` = ceil(h / P) lanes and lane l sums the at most P indices l, l + lanes, l + 2 lanes, .. below h, so that the lanes of
+//           a wave read neighbouring rows; its D + 1 sums go to part[t * lanes + l] - or, with one lane, straight to out[t]
+//   sum     levels of fan F over the partial sums (additions only), laid out [t][piece] before and after; the last level writes out[t]
+// so the length of a lane's serial chain is a constant of the plan, never a property of the data, and no lane waits for another: the order
+// between the levels is the order of the launches on their stream.  Every product and every sum is canonical (fr.hpp), hence the bytes are
+// those of the Python-integer sums however the indices are dealt out.  Everything is pure and takes plain pointers and a lane index, so the
+// host simulation (tests/hostsim/hostsim_mle.cpp) runs the very same bodies over host arrays.
+#pragma once
+#include "fr_ops.hpp"
+#include "io.hpp"
+
+namespace bn254 {
+
+// The shipped choices (plain constants; bn254_mle.hip carries a run-time override of the piece length for the sweep of tools/time_mle.py
+// only).  Indices per lane of the round kernel: the rule fixed before measuring is "the fastest of 4 / 8 / 16 / 32 on four tables of 2^22
+// entries at degree 3 ships"; that is 16 (0.668 / 0.629 / 0.612 / 0.770 ms, profiles/r17_mle.txt), which is also the fastest on one table of
+// 2^24 entries and three times behind 4 on four tables of 2^16, where 2048 lanes leave most of the machine idle.  Partial sums per lane of a
+// sum level: not swept.
+constexpr uint32_t FR_SUMCHECK_PIECE = 16;
+constexpr uint32_t FR_SUMCHECK_FAN = 16;
+
+BN_FN void fr_mle_eq_body(const uint32_t *z, uint32_t nv, uint32_t *out, size_t i) {
+    const Fr one = fr_one();
+    Fr acc = one;
+#pragma unroll 1
+    for (uint32_t j = 0; j < nv; ++j) {
+        const Fr zj = fr_load(z, j);
+        acc = fr_mul(acc, fr_select(((i >> j) & 1) != 0, fr_sub(one, zj), zj));
+    }
+    fr_store(acc, out, i);
+}
+// out may be in: both records are read before record i is written, and no other lane touches either
+BN_FN void fr_mle_fold_body(const uint32_t *in, const Fr &r, uint32_t *out, size_t half, size_t i) {
+    const Fr lo = fr_load(in, i), hi = fr_load(in, i + half);
+    fr_store(fr_add(lo, fr_mul(fr_sub(hi, lo), r)), out, i);
+}
+
+// Lane `lane` of the round kernel.  The factors of a group are walked one at a time: v = lo, d = hi - lo, and per t (unrolled: acc and prod
+// have compile-time indices and stay in registers) prod[t] *= v, v += d - the values at t = 0, 1, 2, .. cost additions only.  The
+// coefficient goes into the first factor's v and d: two products per group and index, not D + 1.  dst: part, or out when lanes == 1.
+template <int D>
+BN_FN void fr_sumcheck_round_body(const uint32_t *tables, uint64_t h, uint32_t k, const BnSumcheckDesc &desc, uint64_t lanes, uint32_t *dst, uint64_t lane) {
+    Fr acc[D + 1];
+#pragma unroll
+    for (int t = 0; t <= D; ++t) acc[t] = fr_zero();
+#pragma unroll 1
+    for (uint64_t i = lane; i < h; i += lanes) {
+        const uint64_t row_lo = i * k, row_hi = (i + h) * k;
+#pragma unroll 1
+        for (uint32_t c = 0; c < desc.groups; ++c) {
+            Fr prod[D + 1];
+            {
+                const uint32_t j = desc.table[c][0];
+                const Fr co = fr_const(desc.coeff[c]), lo = fr_load(tables, row_lo + j), hi = fr_load(tables, row_hi + j);
+                Fr v = fr_mul(lo, co);
+                const Fr d = fr_mul(fr_sub(hi, lo), co);
+#pragma unroll
+                for (int t = 0; t <= D; ++t) {
+                    prod[t] = v;
+                    if (t < D) v = fr_add(v, d);
+                }
+            }
+#pragma unroll 1
+            for (uint32_t f = 1; f < desc.len[c]; ++f) {
+                const uint32_t j = desc.table[c][f];
+                const Fr lo = fr_load(tables, row_lo + j), hi = fr_load(tables, row_hi + j);
+                Fr v = lo;
+                const Fr d = fr_sub(hi, lo);
+#pragma unroll
+                for (int t = 0; t <= D; ++t) {
+                    prod[t] = fr_mul(prod[t], v);
+                    if (t < D) v = fr_add(v, d);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t <= D; ++t) acc[t] = fr_add(acc[t], prod[t]);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t <= D; ++t) fr_store(acc[t], dst, t * lanes + lane);     // one lane: record t of out
+}
+// Lane `lane` of a sum level over `cnt` partial sums per t: with cnt2 = ceil(cnt / F), lane = t * cnt2 + i adds src[t * cnt + i F ..] (at most
+// F of them) into dst[t * cnt2 + i]; the last level has cnt2 == 1 and its dst is out.  src and dst are different ranges of the scratch.
+BN_FN void fr_sumcheck_sum_body(const uint32_t *src, uint64_t cnt, uint32_t F, uint32_t *dst, uint64_t lane) {
+    const uint64_t cnt2 = (cnt + F - 1) / F, t = lane / cnt2, i = lane % cnt2, first = i * F;
+    const uint32_t len = (uint32_t)(cnt - first < F ? cnt - first : F);
+    Fr acc = fr_zero();
+#pragma unroll 1
+    for (uint32_t j = 0; j < len; ++j) acc = fr_add(acc, fr_load(src, t * cnt + first + j));
+    fr_store(acc, dst, lane);
+}
+
+}  // namespace bn254

@@ -105,6 +105,65 @@ def _scan_args(a, b, offsets, init, a_per_segment):
     return a, b, o, init
 
 
+MLE_VARS_MAX, SUMCHECK_DEGREE_MAX, SUMCHECK_TABLES_MAX, SUMCHECK_GROUPS_MAX = 30, 4, 16, 16       # BN254_MLE_* / BN254_SUMCHECK_* of include/bn254_hip.h
+
+
+def _fr_point(v, name):
+    """one field element (anything with .limbs, or four uint64 words) as a C-contiguous array of 4 words"""
+    v = np.ascontiguousarray(getattr(v, "limbs", v), dtype=np.uint64).reshape(-1)
+    if v.size != 4:
+        raise ValueError(f"{name} must be ONE scalar of 4 uint64 words, got {v.size}")
+    return v
+
+
+def _mle_eq_args(z):
+    z = _arr(z, 4) if len(z) else np.zeros((0, 4), np.uint64)
+    if z.shape[0] > MLE_VARS_MAX:
+        raise ValueError(f"z holds {z.shape[0]} variables, at most {MLE_VARS_MAX} are supported")
+    return z
+
+
+def _mle_fold_args(a, r):
+    """(a as a C-contiguous (rows, .., 4) array, r): the fold pairs row i with row i + rows / 2, whatever lies between the first axis and the limbs"""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    if a.ndim < 2 or a.shape[-1] != 4:
+        raise ValueError(f"a must have shape (rows, .., 4) uint64, got {a.shape}")
+    if a.shape[0] % 2:
+        raise ValueError(f"a holds {a.shape[0]} rows: a fold needs an even number")
+    return a, _fr_point(r, "r")
+
+
+def _sumcheck_args(tables, groups, degree):
+    """the operands of fr_sumcheck_round, checked the way the C ABI checks them (it answers BN254_E_BAD_ARG; here the caller learns which one):
+    (tables as (n, k, 4), group offsets, table numbers, coefficients as (g, 4), degree)"""
+    t = np.ascontiguousarray(tables, dtype=np.uint64)
+    if t.ndim == 2 and t.shape[1] == 4:                            # one table
+        t = t.reshape(t.shape[0], 1, 4)
+    if t.ndim != 3 or t.shape[2] != 4:
+        raise ValueError(f"tables must have shape (n, k, 4) uint64, got {t.shape}")
+    n, k = t.shape[0], t.shape[1]
+    if n < 2 or n % 2:
+        raise ValueError(f"tables hold {n} indices: a round needs an even number, 2 at least")
+    if not 1 <= k <= SUMCHECK_TABLES_MAX:
+        raise ValueError(f"tables hold {k} tables per index, 1..{SUMCHECK_TABLES_MAX} are supported")
+    groups = list(groups)
+    if not 1 <= len(groups) <= SUMCHECK_GROUPS_MAX:
+        raise ValueError(f"groups holds {len(groups)} products, 1..{SUMCHECK_GROUPS_MAX} are supported")
+    members = [[int(j) for j in g[1]] for g in groups]
+    if degree is None:
+        degree = max(len(m) for m in members)
+    if not 1 <= degree <= SUMCHECK_DEGREE_MAX:
+        raise ValueError(f"degree must be 1..{SUMCHECK_DEGREE_MAX}, got {degree}")
+    for c, m in enumerate(members):
+        if not 1 <= len(m) <= degree:
+            raise ValueError(f"groups[{c}] holds {len(m)} tables, 1..{degree} (the degree) are allowed")
+        if min(m) < 0 or max(m) >= k:
+            raise ValueError(f"groups[{c}] names table {max(m) if max(m) >= k else min(m)} but tables holds {k}")
+    coeff = np.stack([_fr_point(g[0], f"the coefficient of groups[{c}]") for c, g in enumerate(groups)])
+    off = np.concatenate([[0], np.cumsum([len(m) for m in members])]).astype(np.uint64)
+    return t, off, np.array([j for m in members for j in m], np.uint64), coeff, degree
+
+
 def _segment_args(p, q, offsets):
     p = _arr(p, G1_WORDS) if len(p) else np.zeros((0, G1_WORDS), np.uint64)
     q = _arr(q, G2_WORDS) if len(q) else np.zeros((0, G2_WORDS), np.uint64)
@@ -358,6 +417,33 @@ class Engine:
         out = np.empty((int(o[-1]), 4), np.uint64)
         opt = lambda v: None if v is None else _p(v)
         _native.check(self._lib.bn254_fr_scan_batch(self._h, opt(a), opt(b), opt(init), _p(o), o.size - 1, _scan_flags(reverse, exclusive, a_per_segment), _p(out)))
+        return out
+
+    def fr_mle_eq(self, z):
+        """the table of eq(z, .) over the hypercube of nv = len(z) variables -> (2^nv, 4) uint64: out[i] = prod_j (bit j of i ? z[j] : 1 - z[j]);
+        no variables give [one] (include/bn254_hip.h bn254_fr_mle_eq)"""
+        z = _mle_eq_args(z)
+        out = np.empty((1 << z.shape[0], 4), np.uint64)
+        _native.check(self._lib.bn254_fr_mle_eq(self._h, _p(z), z.shape[0], _p(out)))
+        return out
+
+    def fr_mle_fold(self, a, r):
+        """out[i] = a[i] + r * (a[i + rows/2] - a[i]) -> (rows/2, .., 4) uint64: binds the MOST significant variable of a multilinear table to r.
+        a: (rows, 4), or (rows, k, 4) - k tables stored index-major, all folded at once; r: ONE scalar (an Fr or 4 uint64 words)
+        (include/bn254_hip.h bn254_fr_mle_fold)"""
+        a, r = _mle_fold_args(a, r)
+        out = np.empty((a.shape[0] // 2,) + a.shape[1:], np.uint64)
+        _native.check(self._lib.bn254_fr_mle_fold(self._h, _p(a), a.size // 4, _p(r), _p(out)))
+        return out
+
+    def fr_sumcheck_round(self, tables, groups, degree=None):
+        """the round polynomial of sum_c coeff_c * prod_{j in group c} T_j at t = 0 .. degree -> (degree + 1, 4) uint64:
+        out[t] = sum over i < n/2 and the groups of coeff_c * prod_j (T_j[i] + t * (T_j[i + n/2] - T_j[i])).  tables: (n, k, 4), table j at index i
+        in tables[i, j]; groups: a list of (coeff, [table numbers]); degree: None for the longest group
+        (include/bn254_hip.h bn254_fr_sumcheck_round)"""
+        t, off, members, coeff, degree = _sumcheck_args(tables, groups, degree)
+        out = np.empty((degree + 1, 4), np.uint64)
+        _native.check(self._lib.bn254_fr_sumcheck_round(self._h, _p(t), t.shape[0], t.shape[1], _p(off), _p(members), _p(coeff), off.size - 1, degree, _p(out)))
         return out
 
     def g1_msm_batch(self, p, k, offsets):
@@ -638,6 +724,28 @@ class Engine:
         if o.size != m + 1:
             raise ValueError(f"{m} segments need {m + 1} offsets, got {o.size}")
         _native.check(self._lib.bn254_fr_scan_batch_dev(self._h, d_a, d_b, d_init, _p(o), m, _scan_flags(reverse, exclusive, a_per_segment), d_out, stream))
+
+    def fr_mle_eq_dev(self, d_z, nv, d_out, stream=0):
+        """device pointers z (nv records of 32 bytes) and out (2^nv records), ordered on `stream`"""
+        _native.check(self._lib.bn254_fr_mle_eq_dev(self._h, d_z, nv, d_out, stream))
+
+    def fr_mle_fold_dev(self, d_in, length, r, d_out, stream=0):
+        """device pointers in (`length` records of 32 bytes) and out (length / 2 records; may be d_in: the upper half is then left as it was),
+        ordered on `stream`; `r` is a HOST scalar (an Fr or 4 uint64 words), read before the call returns"""
+        r = _fr_point(r, "r")                                      # held here until the call has returned
+        _native.check(self._lib.bn254_fr_mle_fold_dev(self._h, d_in, length, _p(r), d_out, stream))
+
+    def fr_sumcheck_round_dev(self, d_tables, n, k, groups, d_out, degree=None, stream=0):
+        """device pointers tables (n * k records of 32 bytes, table j at index i in record i * k + j) and out (degree + 1 records), ordered on
+        `stream`; `groups` is a HOST list of (coeff, [table numbers]), read before the call returns.  Returns the degree it ran with"""
+        members = [[int(j) for j in g[1]] for g in groups]
+        if degree is None:
+            degree = max((len(m) for m in members), default=0)
+        coeff = np.stack([_fr_point(g[0], f"the coefficient of groups[{c}]") for c, g in enumerate(groups)]) if members else np.zeros((0, 4), np.uint64)
+        off = np.concatenate([[0], np.cumsum([len(m) for m in members])]).astype(np.uint64)
+        flat = np.array([j for m in members for j in m] or [0], np.uint64)
+        _native.check(self._lib.bn254_fr_sumcheck_round_dev(self._h, d_tables, n, k, _p(off), _p(flat), _p(coeff), len(members), degree, d_out, stream))
+        return degree
 
     def g1_mul_base_batch_dev(self, base, d_k, d_out, n, stream=0):
         """`base` is a HOST point (12 uint64 words), read before the call returns; d_k, d_out device pointers (n records), ordered on `stream`"""

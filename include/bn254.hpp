@@ -227,6 +227,33 @@ inline std::vector<Fr> fr_scan(const std::vector<Fr> *a, const std::vector<Fr> *
     check(bn254_fr_scan_batch(nullptr, ptr(a), ptr(b), ptr(init), offsets.data(), m, flags, reinterpret_cast<bn_fr *>(out.data())));
     return out;
 }
+// the table of eq(z, .) over the hypercube of z.size() variables: out[i] = prod_j (bit j of i ? z[j] : 1 - z[j]); no variables give {one}
+inline std::vector<Fr> fr_mle_eq(const std::vector<Fr> &z) {
+    if (z.size() > BN254_MLE_VARS_MAX) throw std::invalid_argument("fr_mle_eq: too many variables");
+    std::vector<Fr> out(size_t(1) << z.size());
+    check(bn254_fr_mle_eq(nullptr, reinterpret_cast<const bn_fr *>(z.data()), int(z.size()), reinterpret_cast<bn_fr *>(out.data())));
+    return out;
+}
+// out[i] = a[i] + r * (a[i + a.size() / 2] - a[i]): the multilinear table a with its MOST significant variable bound to r; k tables stored
+// index-major (a[i * k + j]) are folded by the one call
+inline std::vector<Fr> fr_mle_fold(const std::vector<Fr> &a, const Fr &r) {
+    if (a.size() % 2) throw std::invalid_argument("fr_mle_fold: an odd length");
+    std::vector<Fr> out(a.size() / 2);
+    check(bn254_fr_mle_fold(nullptr, reinterpret_cast<const bn_fr *>(a.data()), a.size(), reinterpret_cast<const bn_fr *>(&r), reinterpret_cast<bn_fr *>(out.data())));
+    return out;
+}
+// the round polynomial of a sumcheck at t = 0 .. degree: out[t] = sum over i < n / 2 and the groups c of group_coeff[c] * prod over j in group c
+// of (T_j[i] + t * (T_j[i + n / 2] - T_j[i])), T_j[i] = tables[i * k + j], n = tables.size() / k; group c holds the table numbers
+// group_tables[group_offsets[c] .. group_offsets[c + 1])
+inline std::vector<Fr> fr_sumcheck_round(const std::vector<Fr> &tables, size_t k, const std::vector<size_t> &group_offsets, const std::vector<uint64_t> &group_tables,
+                                         const std::vector<Fr> &group_coeff, int degree) {
+    if (k == 0 || tables.size() % (2 * k) || group_offsets.empty() || group_coeff.size() != group_offsets.size() - 1 || group_offsets.back() != group_tables.size() || degree < 1)
+        throw std::invalid_argument("fr_sumcheck_round: tables, k and the groups disagree");
+    std::vector<Fr> out(size_t(degree) + 1);
+    check(bn254_fr_sumcheck_round(nullptr, reinterpret_cast<const bn_fr *>(tables.data()), tables.size() / k, k, group_offsets.data(), group_tables.data(),
+                                  reinterpret_cast<const bn_fr *>(group_coeff.data()), group_coeff.size(), degree, reinterpret_cast<bn_fr *>(out.data())));
+    return out;
+}
 // out[i] = (a[i] == b[i]) as group elements, whatever their Jacobian representations (groups/mod.rs:83-109): nothing is normalized
 inline std::vector<bool> g1_eq(const std::vector<G1> &a, const std::vector<G1> &b) {
     if (a.size() != b.size()) throw std::invalid_argument("g1_eq: length mismatch");

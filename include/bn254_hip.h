@@ -46,6 +46,10 @@
  *   bn254_fr_scan_batch    out[t] = a[t] * out[t-1] + b[t] over the terms of every segment, from init[j]: segmented prefix sums, prefix products, powers and
  *                          Horner's rule over Fr (lib.rs:33-53 Add and Mul, chained per segment); no counterpart in the reference
  *   bn254_fr_scan_batch_dev the same on device-resident a, b, init and out, asynchronous on the caller's stream
+ *   bn254_fr_mle_eq        out[i] = prod_j (bit j of i ? z[j] : 1 - z[j]): the table of eq(z, .) over the hypercube of nv variables (lib.rs:33-53 Sub and Mul);
+ *                          bn254_fr_mle_fold  out[i] = in[i] + r * (in[i + len/2] - in[i]): binds the most significant variable of a multilinear table;
+ *                          bn254_fr_sumcheck_round  the round polynomial of a sum of products of tables at t = 0 .. degree; none has a counterpart in the reference
+ *   bn254_fr_mle_eq_dev / bn254_fr_mle_fold_dev / bn254_fr_sumcheck_round_dev  the same three on device-resident tables, asynchronous on the caller's stream
  *   bn254_g2_precompute    coeffs[i][0..102) = q[i].to_affine().precompute().coeffs   groups/mod.rs:557-588 (Q != infinity)
  *   bn254_pairing_prepared_batch  out[i] = final_exponentiation(prepared.miller_loop(p[i]))   groups/mod.rs:486-519,768
  *   bn254_gt_mul_batch     out[i] = a[i] * b[i]                                     lib.rs:175-179, fields/fq12.rs:295-307
@@ -85,6 +89,7 @@
      context and no device.
      bn254_fr_dot_batch serialises on the context in the same way (its mutex for the whole call).
      bn254_fr_scan_batch serialises on the context in the same way (its mutex for the whole call).
+     bn254_fr_mle_eq, bn254_fr_mle_fold and bn254_fr_sumcheck_round serialise on the context in the same way (its mutex for the whole call).
  *     bn254_pairing_product_batch_prepared_native serialises on the context like them; its handle is immutable and shared freely.
  *     Use one context per thread (or bn254_multi_*) for more overlap;
  *     bn254_ctx_set_option is atomic, but set options before concurrent use: a call in flight may run some
@@ -115,6 +120,10 @@
      bn254_fr_scan_batch_dev reads its HOST `offsets` before it returns in the same way; its work list, the maps of its pieces and their
      carries are context-owned scratch under the same event ordering, and it too waits on the host only for the previous upload through the
      pinned staging and reads nothing back.
+     bn254_fr_mle_eq_dev and bn254_fr_mle_fold_dev use no scratch; bn254_fr_mle_fold_dev reads its HOST `r` and bn254_fr_sumcheck_round_dev its HOST
+     group description before they return (both travel as kernel arguments: nothing is uploaded).  The partial sums of
+     bn254_fr_sumcheck_round_dev are context-owned scratch under the same event ordering.  None of the three waits on anything or reads
+     anything back.
  */
 #ifndef BN254_HIP_H
 #define BN254_HIP_H
@@ -497,6 +506,44 @@ int bn254_fr_dot_batch(bn254_ctx *ctx, const bn_fr *coeff, const uint64_t *index
 #define BN254_SCAN_EXCLUSIVE 2
 #define BN254_SCAN_A_PER_SEGMENT 4
 int bn254_fr_scan_batch(bn254_ctx *ctx, const bn_fr *a, const bn_fr *b, const bn_fr *init, const size_t *offsets, size_t m, unsigned int flags, bn_fr *out);
+/* Multilinear tables and sumcheck rounds over Fr: what Spartan, HyperPlonk, GKR and lookup arguments need of a prover.  A multilinear table of
+   nv variables is 2^nv records; the record at index i is the value at the point of the hypercube whose variable j is bit j of i.  Several
+   tables of one sumcheck are stored index-major: tables[i * k + j] is table j at index i (in numpy an (n, k, 4) array), so that ONE fold of
+   len = n k records folds all k tables in place and a lane of the round kernel finds its k operands in one contiguous run.  Sumcheck round
+   s (from 0) binds variable nv - 1 - s, so the evaluation point has point[j] = challenge[nv - 1 - j].  Inputs are canonical Montgomery
+   images; every product and sum is canonical, hence the bytes are those of the integer model however the work is cut.
+   bn254_fr_mle_eq: out[i] = prod_{j < nv} (bit j of i ? z[j] : 1 - z[j]) for i < 2^nv, the table of eq(z, .); nv == 0 writes Fr::one().  One lane
+   per element and nv products per lane whatever the data: no chain depends on it.
+   bn254_fr_mle_fold: out[i] = in[i] + r * (in[i + len/2] - in[i]) for i < len/2 - the MOST significant variable is bound to r.  `r` is ONE element
+   in HOST memory.  `out` may be exactly `in` (lane i alone reads its two records and writes record i); the upper half is then left as it
+   was.  len == 0 returns BN254_OK and writes nothing; an odd len is BN254_E_BAD_ARG.
+   bn254_fr_sumcheck_round: with h = n / 2 and g groups in CSR form over group_tables (group_offsets[0] == 0, increasing; group c holds the 1 to
+   `degree` table numbers group_tables[group_offsets[c] .. group_offsets[c+1]), each < k; a table may repeat within a group), for t = 0 .. degree
+       out[t] = sum_{i < h} sum_{c < g} group_coeff[c] * prod_{j in group c} (T_j[i] + t * (T_j[i + h] - T_j[i])),   T_j[i] = tables[i k + j].
+   `out` has degree + 1 records; out[0] + out[1] is the sum over all n indices.  n need not be a power of two.  The group description
+   (group_offsets, group_tables, group_coeff) is HOST memory.
+   How: the round kernel has ceil(h / 16) lanes; lane l sums the at most P = 16 indices l, l + lanes, .. into degree + 1 accumulators that stay in
+   registers (the kernel is compiled once per degree).  Per group and index it walks the factors one at a time: v = T_j[i], d = T_j[i + h] - T_j[i],
+   and per t a product by v and v += d - the values at t = 0, 1, .. cost additions only, and no product or interpolated table is ever written
+   to memory.  The coefficient is multiplied into the first factor's v and d.  A call of h <= P writes out directly; otherwise the lanes write
+   partial sums, laid out [t][lane], to context-owned scratch and sum levels of at most F = 16 per lane (additions only) reduce them:
+   ceil(log16(ceil(h / 16))) levels, ordered by the stream, every level as sub-launches of at most 2^22 lanes.  No atomics, no workgroup waits
+   for another, no LDS.  Measured on an MI355X (tools/time_mle.py, kernel ms, medians of 5; profiles/r17_mle.txt): four tables of 2^22 entries at
+   degree 3 take 0.668 / 0.629 / 0.612 / 0.770 ms at P = 4 / 8 / 16 / 32 - the fastest ships, by a rule fixed before measuring -, which is 1.04 x
+   bn254_fr_mul_batch_dev on the 16 products per index the round executes and 2.6 x faster than the same round from existing calls.
+   Errors (BN254_E_BAD_ARG, checked before any device is touched): eq - nv outside 0 .. BN254_MLE_VARS_MAX, a NULL out, a NULL z with nv > 0;
+   fold - an odd len, len > 2^40, a NULL in, r or out; round - n odd or below 2, k outside 1 .. BN254_SUMCHECK_TABLES_MAX, g outside
+   1 .. BN254_SUMCHECK_GROUPS_MAX, degree outside 1 .. BN254_SUMCHECK_DEGREE_MAX, an empty group or one longer than degree, a table number >= k,
+   group_offsets[0] != 0, a NULL pointer, n k > 2^40.  Threading: see above - the host-buffer entry points hold the context's mutex for the
+   whole call. */
+#define BN254_MLE_VARS_MAX 30
+#define BN254_SUMCHECK_DEGREE_MAX 4
+#define BN254_SUMCHECK_TABLES_MAX 16
+#define BN254_SUMCHECK_GROUPS_MAX 16
+int bn254_fr_mle_eq(bn254_ctx *ctx, const bn_fr *z, int nv, bn_fr *out);
+int bn254_fr_mle_fold(bn254_ctx *ctx, const bn_fr *in, size_t len, const bn_fr *r, bn_fr *out);
+int bn254_fr_sumcheck_round(bn254_ctx *ctx, const bn_fr *tables, size_t n, size_t k, const size_t *group_offsets, const uint64_t *group_tables, const bn_fr *group_coeff, size_t g,
+                            int degree, bn_fr *out);
 
 /* ---- one node, several GPUs (north_star: independent batches shard across the GPUs; ONE exchange for the multi-pairing) --- */
 /* `devices[0..ndev)`: HIP device index of every rank (NULL = 0..ndev-1).  One context and one host thread per rank.  A device may
@@ -658,6 +705,14 @@ int bn254_fr_dot_batch_dev(bn254_ctx *ctx, const void *d_coeff, const void *d_in
    carries are context-owned scratch (see Threading). */
 int bn254_fr_scan_batch_dev(bn254_ctx *ctx, const void *d_a, const void *d_b, const void *d_init, const size_t *offsets, size_t m, unsigned int flags, void *d_out,
                             void *stream);
+/* bn254_fr_mle_eq / bn254_fr_mle_fold / bn254_fr_sumcheck_round on device-resident records of 32 bytes, 16-byte aligned, asynchronous on `stream`:
+   d_z (nv records) and d_out (2^nv); d_in (len records) and d_out (len / 2; may be exactly d_in); d_tables (n k records) and d_out (degree + 1).
+   `r` of the fold and the group description of the round are HOST memory, read before the call returns, and may be freed then.  None
+   waits for anything or reads anything back; the partial sums of the round are context-owned scratch (see Threading). */
+int bn254_fr_mle_eq_dev(bn254_ctx *ctx, const void *d_z, int nv, void *d_out, void *stream);
+int bn254_fr_mle_fold_dev(bn254_ctx *ctx, const void *d_in, size_t len, const bn_fr *r, void *d_out, void *stream);
+int bn254_fr_sumcheck_round_dev(bn254_ctx *ctx, const void *d_tables, size_t n, size_t k, const size_t *group_offsets, const uint64_t *group_tables, const bn_fr *group_coeff,
+                                size_t g, int degree, void *d_out, void *stream);
 /* raw Jacobian result of the reference's MSB-first double-and-add (what G::random produces, groups/mod.rs:220-222):
    used to generate benchmark inputs with z != 1 on the device */
 int bn254_g1_mul_jacobian_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, void *d_out, size_t n, void *stream);
@@ -678,6 +733,7 @@ int bn254_profile_reset(bn254_ctx *ctx);
 /* kernel: "miller", "miller_shared", "miller_wave", "miller_quad", "pairing_wave", "final_exp", "final_exp_wave", "final_exp_quad", "exp_by_neg_z", "gt_product", "gt_tail", "gt_segment", "gt_tail_seg", "g1_mul", "g2_mul", "gt_mul", "gt_pow", "g2_precompute", "miller_prepared", "g2_prepare_native", "miller_native", "miller_native_shared", "miller_native_seg", "g2_gather", "wire_encode", "wire_decode", "fr_add", "fr_mul", "fr_inverse", "fr_pow", "fr_interpret", "gt_inverse", "g1_add", "g2_add", "g1_msm_mul", "g1_msm_fold", "g2_msm_mul", "g2_msm_fold", "g1_msm_digits", "g1_msm_bucket", "g1_msm_reduce", "g2_msm_digits", "g2_msm_bucket", "g2_msm_reduce", "g1_mul_base", "g2_mul_base", "g1_base_table", "g2_base_table", "g1_normalize", "g2_normalize", "g1_eq", "g2_eq".
    of bn254_fr_dot_batch: "fr_dot" (the pieces: products and sums), "fr_dot_fold" (the levels over the partial sums);
    of bn254_fr_scan_batch: "fr_scan" (the apply level, direct segments among it), "fr_scan_reduce" (the maps of the pieces), "fr_scan_up", "fr_scan_down" (the levels over the maps);
+   of bn254_fr_mle_eq, bn254_fr_mle_fold and bn254_fr_sumcheck_round: "fr_mle_eq", "fr_mle_fold", "fr_sumcheck_round" (the lanes over the indices), "fr_sumcheck_sum" (the levels over the partial sums);
    and, of bn254_fr_ntt_batch: "ntt" (the passes), "ntt_table" (the builds of the twiddle tables).
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);
