@@ -98,6 +98,9 @@ extern "C" {
     fn bn254_fr_mle_eq(ctx: *mut c_void, z: *const Fr, nv: c_int, out: *mut Fr) -> c_int;
     fn bn254_fr_mle_fold(ctx: *mut c_void, input: *const Fr, len: usize, r: *const Fr, out: *mut Fr) -> c_int;
     fn bn254_fr_sumcheck_round(ctx: *mut c_void, tables: *const Fr, n: usize, k: usize, group_offsets: *const usize, group_tables: *const u64, group_coeff: *const Fr, g: usize, degree: c_int, out: *mut Fr) -> c_int;
+    fn bn254_fr_poseidon_batch(ctx: *mut c_void, input: *const Fr, arity: c_int, out: *mut Fr, n: usize) -> c_int;
+    fn bn254_fr_poseidon_permute_batch(ctx: *mut c_void, input: *const Fr, t: c_int, out: *mut Fr, n: usize) -> c_int;
+    fn bn254_fr_merkle_tree(ctx: *mut c_void, leaves: *const Fr, log_n: c_int, nodes: *mut Fr) -> c_int;
     fn bn254_fr_add_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_out: *mut c_void, n: usize, negate_b: c_int, stream: *mut c_void) -> c_int;
     fn bn254_fr_mul_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_inverse_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_out: *mut c_void, d_ok: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
@@ -109,6 +112,9 @@ extern "C" {
     fn bn254_fr_mle_eq_dev(ctx: *mut c_void, d_z: *const c_void, nv: c_int, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn bn254_fr_mle_fold_dev(ctx: *mut c_void, d_in: *const c_void, len: usize, r: *const Fr, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn bn254_fr_sumcheck_round_dev(ctx: *mut c_void, d_tables: *const c_void, n: usize, k: usize, group_offsets: *const usize, group_tables: *const u64, group_coeff: *const Fr, g: usize, degree: c_int, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn bn254_fr_poseidon_batch_dev(ctx: *mut c_void, d_in: *const c_void, arity: c_int, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_fr_poseidon_permute_batch_dev(ctx: *mut c_void, d_in: *const c_void, t: c_int, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_fr_merkle_tree_dev(ctx: *mut c_void, d_leaves: *const c_void, log_n: c_int, d_nodes: *mut c_void, stream: *mut c_void) -> c_int;
 }
 
 /// One line-function coefficient of a prepared G2 point: the crate's `EllCoeffs { ell_0, ell_vw, ell_vv: Fq2 }` (src/groups/mod.rs:472-476) as the
@@ -415,6 +421,33 @@ pub fn fr_sumcheck_round(tables: &[Fr], k: usize, group_offsets: &[usize], group
         bn254_fr_sumcheck_round(std::ptr::null_mut(), tables.as_ptr(), tables.len() / k, k, group_offsets.as_ptr(), group_tables.as_ptr(), group_coeff.as_ptr(), g, degree as c_int, out.as_mut_ptr())
     })?;
     Ok(out)
+}
+
+/// `out[i] = Poseidon(input[i * arity .. (i + 1) * arity])`: the circomlib / iden3 hash over `Fr` (x^5, `t = arity + 1`, `R_F = 8`,
+/// `R_P = 56 / 57 / 56 / 60`), element 0 of the permutation of `[0, x_1, .., x_arity]`; `arity` is 1 to 4.
+pub fn fr_poseidon(input: &[Fr], arity: usize) -> Result<Vec<Fr>, GpuError> {
+    assert!((1..=4).contains(&arity) && input.len() % arity == 0);
+    let n = input.len() / arity;
+    let mut out = vec![Fr::zero(); n];
+    check(unsafe { bn254_fr_poseidon_batch(std::ptr::null_mut(), input.as_ptr(), arity as c_int, out.as_mut_ptr(), n) })?;
+    Ok(out)
+}
+
+/// The Poseidon permutation itself on `states.len() / t` states of `t` elements each, `t` 2 to 5.
+pub fn fr_poseidon_permute(states: &[Fr], t: usize) -> Result<Vec<Fr>, GpuError> {
+    assert!((2..=5).contains(&t) && states.len() % t == 0);
+    let mut out = vec![Fr::zero(); states.len()];
+    check(unsafe { bn254_fr_poseidon_permute_batch(std::ptr::null_mut(), states.as_ptr(), t as c_int, out.as_mut_ptr(), states.len() / t) })?;
+    Ok(out)
+}
+
+/// The `n - 1` inner nodes of the binary Poseidon tree over `n = 2^k` leaves, level by level: the `n / 2` parents of the leaves first, the root
+/// last; parent `i` of a level is `hash(child[2 i], child[2 i + 1])`.  One leaf gives no node.
+pub fn fr_merkle_tree(leaves: &[Fr]) -> Result<Vec<Fr>, GpuError> {
+    assert!(leaves.len().is_power_of_two() && leaves.len() <= 1 << 24);
+    let mut nodes = vec![Fr::zero(); leaves.len() - 1];
+    check(unsafe { bn254_fr_merkle_tree(std::ptr::null_mut(), leaves.as_ptr(), leaves.len().trailing_zeros() as c_int, nodes.as_mut_ptr()) })?;
+    Ok(nodes)
 }
 
 /// `out[i] = a[i] * b[i]` (src/lib.rs:175-179)

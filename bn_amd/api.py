@@ -439,6 +439,42 @@ def fr_sumcheck_round(tables, groups, degree=None, engine=None):
     return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_sumcheck_round(t, groups, degree)]
 
 
+def _poseidon_rows(rows):
+    """rows of Fr (a sequence of equally long sequences) or an (n, width, 4) uint64 array -> the array"""
+    if isinstance(rows, np.ndarray):
+        return rows
+    rows = [_scalar_array(r) for r in rows]
+    if len({r.shape[0] for r in rows}) > 1:
+        raise ValueError(f"rows differ in length: {sorted({r.shape[0] for r in rows})}")
+    return np.stack(rows) if rows else np.zeros((0, 1, 4), np.uint64)
+
+
+def fr_poseidon_batch(inputs, engine=None):
+    """[Poseidon(*row) for row in inputs] -> list of Fr: the circomlib / iden3 hash over Fr (x^5, t = arity + 1, R_F = 8, R_P = 56 / 57 / 56 / 60),
+    element 0 of the permutation of [0, *row]; one GPU lane per hash.  inputs: rows of 1 .. 4 Fr each, all of one length, or an
+    (n, arity, 4) uint64 array.  ValueError for another arity."""
+    from .engine import _poseidon_args, POSEIDON_ARITY_MAX
+    x = _poseidon_args(_poseidon_rows(inputs), "inputs", 1, POSEIDON_ARITY_MAX, "arity")
+    return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_poseidon_batch(x)]
+
+
+def fr_poseidon_permute_batch(states, engine=None):
+    """[permute(state) for state in states] -> list of lists of Fr: the Poseidon permutation itself on states of t = 2 .. 5 Fr each (or an
+    (n, t, 4) uint64 array).  ValueError for another width."""
+    from .engine import _poseidon_args, POSEIDON_ARITY_MAX
+    x = _poseidon_args(_poseidon_rows(states), "states", 2, POSEIDON_ARITY_MAX + 1, "t")
+    return [[Fr.from_limbs(r) for r in st] for st in (engine or default_engine()).fr_poseidon_permute_batch(x)]
+
+
+def fr_merkle_tree(leaves, engine=None):
+    """the n - 1 inner nodes of the binary Poseidon tree over n = 2^k leaves -> list of Fr, level by level: the n / 2 parents of the leaves
+    first, the root last; parent i of a level is hash(child[2 i], child[2 i + 1]).  One call, one launch per level.  leaves: a sequence of Fr
+    or an (n, 4) uint64 array.  ValueError unless n is a power of two (one leaf gives [])."""
+    from .engine import _merkle_args
+    x, _ = _merkle_args(_scalar_array(leaves))
+    return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_merkle_tree(x)]
+
+
 def _shift_limbs(shift):
     if shift is None:
         return None

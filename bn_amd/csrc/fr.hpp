@@ -111,6 +111,57 @@ BN_FN Fr fr_mul(const Fr &a, const Fr &b) {
     }
     return fr_reduce_once(t, t[8]);
 }
+// sum_k a[k] * b[k] / 2^256 mod r for T <= 5 pairs with ONE reduction: per word, T rows of eight products into t and then the one row m * r
+// that clears the low word - 8 T + 8 multiply-adds per word where T calls of fr_mul take 16 T.
+// PRECONDITION: every a[k] and every b[k] is canonical (< r).  Then sum a b <= 5 (r - 1)^2 < 2^256 r because 5 r < 2^256, so the rows leave
+// (sum a b + M r) / 2^256 < 2 r and the one conditional subtraction gives the canonical result.  On the way, after every word,
+// t < t_before / 2^32 + 5 r + r, which stays below 6 r (1 + 2^-31) < 2^257: the carry word holds 0 or 1; inside a word the carries of
+// the T rows are summed in 64 bits.  The bound-enforcing host simulation (BN_BOUNDS) checks the precondition, the carry word after every word and
+// t < 2 r at the end.
+template <int T>
+BN_FN Fr fr_dot(const Fr (&a)[T], const uint32_t (*b)[8]) {
+    static_assert(T >= 1 && T <= 5, "5 r < 2^256 < 6 r");
+#if defined(BN_BOUNDS)
+    for (int q = 0; q < T; ++q) BN_REQUIRE(fr_lt_r(a[q].w) && fr_lt_r(b[q]), "fr_dot takes canonical operands");
+#endif
+    uint32_t t[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) t[i] = 0u;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        uint64_t top = t[8];
+#pragma unroll
+        for (int q = 0; q < T; ++q) {
+            uint64_t c = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const uint64_t x = (uint64_t)a[q].w[i] * b[q][j] + t[j] + c;
+                t[j] = (uint32_t)x; c = x >> 32;
+            }
+            top += c;                                                       // < 1 + 5 * 2^32
+        }
+        const uint32_t m = t[0] * k::FR_INV32;
+        uint64_t c = ((uint64_t)m * k::FR_MOD32[0] + t[0]) >> 32;
+#pragma unroll
+        for (int j = 1; j < 8; ++j) {
+            const uint64_t y = (uint64_t)m * k::FR_MOD32[j] + t[j] + c;
+            t[j - 1] = (uint32_t)y; c = y >> 32;
+        }
+        const uint64_t y = top + c;
+        t[7] = (uint32_t)y; t[8] = (uint32_t)(y >> 32);
+#if defined(BN_BOUNDS)
+        BN_REQUIRE((y >> 32) <= 1, "fr_dot: the running value left 2^257");
+#endif
+    }
+#if defined(BN_BOUNDS)
+    {   // t < 2 r: t - r < r
+        uint32_t d[8]; int64_t br = 0;
+        for (int i = 0; i < 8; ++i) { const int64_t v = (int64_t)t[i] - (int64_t)k::FR_MOD32[i] + br; d[i] = (uint32_t)v; br = v >> 32; }
+        BN_REQUIRE(t[8] == 0 ? (br != 0 || fr_lt_r(d)) : (br != 0 && fr_lt_r(d)), "fr_dot: the sum before the subtraction is not below 2 r");
+    }
+#endif
+    return fr_reduce_once(t, t[8]);
+}
 // Fr out of Montgomery form (fields/fp.rs:15-22: multiply by 1): 8 x u32 words, word-serial Montgomery reduction mod r
 BN_FN void fr_from_mont(const uint32_t *km, uint32_t *raw) {
     uint32_t t[9];

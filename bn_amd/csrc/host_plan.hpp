@@ -538,3 +538,28 @@ inline BnSumcheckPlan bn_sumcheck_plan(size_t h, unsigned degree, size_t P, size
     }
     return plan;
 }
+
+// ---- Poseidon hashes and Merkle trees over Fr (bn254_fr_poseidon_batch, bn254_fr_poseidon_permute_batch, bn254_fr_merkle_tree): the argument checks and the levels
+// n states of t records (a hash of arity t - 1 reads n * (t - 1) of them: the bound is taken on n * t either way); n == 0 is answered before
+inline int bn_poseidon_check(const void *in, int t, const void *out, size_t n) {
+    if (t < 2 || t > BN254_POSEIDON_ARITY_MAX + 1) return BN254_E_BAD_ARG;
+    return (n > BN_N_MAX / (size_t)t || !in || !out) ? BN254_E_BAD_ARG : BN254_OK;
+}
+inline int bn_merkle_check(const void *leaves, int log_n, const void *nodes) {
+    if (log_n < 0 || log_n > BN254_MERKLE_LOG_MAX) return BN254_E_BAD_ARG;
+    return (log_n > 0 && (!leaves || !nodes)) ? BN254_E_BAD_ARG : BN254_OK;
+}
+// The tree over n = 2^log_n leaves: log_n levels, level l (from 0) of n >> (l + 1) parents.  Level 0 reads the leaves, level l > 0 the nodes
+// from `src`; every level writes the nodes from `dst`, behind the level before it, so the root is node n - 2 and no record is written twice.
+// `parts`: the sub-launches of at most `step` lanes the level is cut into.
+struct BnMerkleLevel { size_t cnt, src, dst, parts; bool from_leaves; };
+inline std::vector<BnMerkleLevel> bn_merkle_plan(int log_n, size_t step) {
+    std::vector<BnMerkleLevel> levels;
+    size_t src = 0, dst = 0;
+    for (int l = 0; l < log_n; ++l) {
+        const size_t cnt = (size_t)1 << (log_n - 1 - l);
+        levels.push_back({cnt, src, dst, (cnt + step - 1) / step, l == 0});
+        src = dst; dst += cnt;
+    }
+    return levels;
+}

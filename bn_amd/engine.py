@@ -108,6 +108,32 @@ def _scan_args(a, b, offsets, init, a_per_segment):
 MLE_VARS_MAX, SUMCHECK_DEGREE_MAX, SUMCHECK_TABLES_MAX, SUMCHECK_GROUPS_MAX = 30, 4, 16, 16       # BN254_MLE_* / BN254_SUMCHECK_* of include/bn254_hip.h
 
 
+POSEIDON_ARITY_MAX, MERKLE_LOG_MAX = 4, 24                  # BN254_POSEIDON_ARITY_MAX / BN254_MERKLE_LOG_MAX of include/bn254_hip.h
+
+
+def _poseidon_args(x, name, lo, hi, what):
+    """rows of records as a C-contiguous (n, width, 4) array, lo <= width <= hi"""
+    x = np.ascontiguousarray(x, dtype=np.uint64)
+    if x.ndim == 2 and x.shape[1] == 4:                            # one record per row
+        x = x.reshape(x.shape[0], 1, 4)
+    if x.ndim != 3 or x.shape[2] != 4:
+        raise ValueError(f"{name} must have shape (n, {what}, 4) uint64, got {x.shape}")
+    if not lo <= x.shape[1] <= hi:
+        raise ValueError(f"{name} holds {x.shape[1]} records per row, {what} = {lo}..{hi} are supported")
+    return x
+
+
+def _merkle_args(leaves):
+    """(leaves as a C-contiguous (n, 4) array, log2 n)"""
+    x = _arr(leaves, 4) if len(leaves) else np.zeros((0, 4), np.uint64)
+    n = x.shape[0]
+    if n == 0 or n & (n - 1):
+        raise ValueError(f"leaves holds {n} records: a tree needs a power of two, one at least")
+    if n > 1 << MERKLE_LOG_MAX:
+        raise ValueError(f"leaves holds {n} records, at most 2^{MERKLE_LOG_MAX} are supported")
+    return x, n.bit_length() - 1
+
+
 def _fr_point(v, name):
     """one field element (anything with .limbs, or four uint64 words) as a C-contiguous array of 4 words"""
     v = np.ascontiguousarray(getattr(v, "limbs", v), dtype=np.uint64).reshape(-1)
@@ -446,6 +472,31 @@ class Engine:
         _native.check(self._lib.bn254_fr_sumcheck_round(self._h, _p(t), t.shape[0], t.shape[1], _p(off), _p(members), _p(coeff), off.size - 1, degree, _p(out)))
         return out
 
+    def fr_poseidon_batch(self, x):
+        """out[i] = Poseidon(x[i, 0], .., x[i, arity - 1]) -> (n, 4) uint64: the circomlib / iden3 hash over Fr, element 0 of the permutation of
+        [0, x[i, 0], ..].  x: (n, arity, 4), arity 1 .. 4 (include/bn254_hip.h bn254_fr_poseidon_batch)"""
+        x = _poseidon_args(x, "x", 1, POSEIDON_ARITY_MAX, "arity")
+        out = np.empty((x.shape[0], 4), np.uint64)
+        _native.check(self._lib.bn254_fr_poseidon_batch(self._h, _p(x), x.shape[1], _p(out), x.shape[0]))
+        return out
+
+    def fr_poseidon_permute_batch(self, states):
+        """out[i] = the Poseidon permutation of the state states[i] -> (n, t, 4) uint64.  states: (n, t, 4), t 2 .. 5
+        (include/bn254_hip.h bn254_fr_poseidon_permute_batch)"""
+        x = _poseidon_args(states, "states", 2, POSEIDON_ARITY_MAX + 1, "t")
+        out = np.empty_like(x)
+        _native.check(self._lib.bn254_fr_poseidon_permute_batch(self._h, _p(x), x.shape[1], _p(out), x.shape[0]))
+        return out
+
+    def fr_merkle_tree(self, leaves):
+        """the n - 1 inner nodes of the binary Poseidon tree over n = 2^k leaves -> (n - 1, 4) uint64, level by level: the n / 2 parents of the
+        leaves, the n / 4 parents of those, .. the root last; parent i of a level is hash(child[2 i], child[2 i + 1]).  One leaf gives no
+        node (include/bn254_hip.h bn254_fr_merkle_tree)"""
+        x, log_n = _merkle_args(leaves)
+        out = np.empty((x.shape[0] - 1, 4), np.uint64)
+        _native.check(self._lib.bn254_fr_merkle_tree(self._h, _p(x), log_n, _p(out) if log_n else None))
+        return out
+
     def g1_msm_batch(self, p, k, offsets):
         """out[j] = normalize(sum of p[i] * k[i] over i in [offsets[j], offsets[j+1])) -> (m, 12) uint64; an empty or cancelling
         segment gives G1::zero() = (0, 1, 0); ONE inversion per segment (include/bn254_hip.h bn254_g1_msm_batch)"""
@@ -746,6 +797,19 @@ class Engine:
         flat = np.array([j for m in members for j in m] or [0], np.uint64)
         _native.check(self._lib.bn254_fr_sumcheck_round_dev(self._h, d_tables, n, k, _p(off), _p(flat), _p(coeff), len(members), degree, d_out, stream))
         return degree
+
+    def fr_poseidon_batch_dev(self, d_in, arity, d_out, n, stream=0):
+        """device pointers in (n * arity records of 32 bytes, row-major) and out (n records; must not overlap in), ordered on `stream`"""
+        _native.check(self._lib.bn254_fr_poseidon_batch_dev(self._h, d_in, arity, d_out, n, stream))
+
+    def fr_poseidon_permute_batch_dev(self, d_in, t, d_out, n, stream=0):
+        """device pointers in and out (n states of t records of 32 bytes each; out may be exactly in), ordered on `stream`"""
+        _native.check(self._lib.bn254_fr_poseidon_permute_batch_dev(self._h, d_in, t, d_out, n, stream))
+
+    def fr_merkle_tree_dev(self, d_leaves, log_n, d_nodes, stream=0):
+        """device pointers leaves (2^log_n records of 32 bytes) and nodes (2^log_n - 1 records, level by level, the root last; must not overlap
+        leaves), ordered on `stream`: one launch per level"""
+        _native.check(self._lib.bn254_fr_merkle_tree_dev(self._h, d_leaves, log_n, d_nodes, stream))
 
     def g1_mul_base_batch_dev(self, base, d_k, d_out, n, stream=0):
         """`base` is a HOST point (12 uint64 words), read before the call returns; d_k, d_out device pointers (n records), ordered on `stream`"""

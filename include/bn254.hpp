@@ -254,6 +254,30 @@ inline std::vector<Fr> fr_sumcheck_round(const std::vector<Fr> &tables, size_t k
                                   reinterpret_cast<const bn_fr *>(group_coeff.data()), group_coeff.size(), degree, reinterpret_cast<bn_fr *>(out.data())));
     return out;
 }
+// out[i] = Poseidon(in[i * arity .. (i + 1) * arity)): the circomlib / iden3 hash over Fr, element 0 of the permutation of {0, x_1, .., x_arity}
+inline std::vector<Fr> fr_poseidon(const std::vector<Fr> &in, int arity) {
+    if (arity < 1 || arity > BN254_POSEIDON_ARITY_MAX || in.size() % size_t(arity)) throw std::invalid_argument("fr_poseidon: arity and the inputs disagree");
+    std::vector<Fr> out(in.size() / size_t(arity));
+    check(bn254_fr_poseidon_batch(nullptr, reinterpret_cast<const bn_fr *>(in.data()), arity, reinterpret_cast<bn_fr *>(out.data()), out.size()));
+    return out;
+}
+// the Poseidon permutation on states.size() / t states of t elements each, t = 2 .. 5
+inline std::vector<Fr> fr_poseidon_permute(const std::vector<Fr> &states, int t) {
+    if (t < 2 || t > BN254_POSEIDON_ARITY_MAX + 1 || states.size() % size_t(t)) throw std::invalid_argument("fr_poseidon_permute: t and the states disagree");
+    std::vector<Fr> out(states.size());
+    check(bn254_fr_poseidon_permute_batch(nullptr, reinterpret_cast<const bn_fr *>(states.data()), t, reinterpret_cast<bn_fr *>(out.data()), states.size() / size_t(t)));
+    return out;
+}
+// the n - 1 inner nodes of the binary Poseidon tree over n = 2^k leaves, level by level, the root last; one leaf gives no node
+inline std::vector<Fr> fr_merkle_tree(const std::vector<Fr> &leaves) {
+    const size_t n = leaves.size();
+    int log_n = 0;
+    while ((size_t(1) << log_n) < n) ++log_n;
+    if (n == 0 || (size_t(1) << log_n) != n || log_n > BN254_MERKLE_LOG_MAX) throw std::invalid_argument("fr_merkle_tree: the leaves are not a power of two");
+    std::vector<Fr> nodes(n - 1);
+    check(bn254_fr_merkle_tree(nullptr, reinterpret_cast<const bn_fr *>(leaves.data()), log_n, reinterpret_cast<bn_fr *>(nodes.data())));
+    return nodes;
+}
 // out[i] = (a[i] == b[i]) as group elements, whatever their Jacobian representations (groups/mod.rs:83-109): nothing is normalized
 inline std::vector<bool> g1_eq(const std::vector<G1> &a, const std::vector<G1> &b) {
     if (a.size() != b.size()) throw std::invalid_argument("g1_eq: length mismatch");

@@ -50,6 +50,10 @@
  *                          bn254_fr_mle_fold  out[i] = in[i] + r * (in[i + len/2] - in[i]): binds the most significant variable of a multilinear table;
  *                          bn254_fr_sumcheck_round  the round polynomial of a sum of products of tables at t = 0 .. degree; none has a counterpart in the reference
  *   bn254_fr_mle_eq_dev / bn254_fr_mle_fold_dev / bn254_fr_sumcheck_round_dev  the same three on device-resident tables, asynchronous on the caller's stream
+ *   bn254_fr_poseidon_batch  out[i] = Poseidon(in[i * arity .. (i + 1) * arity)), the circomlib / iden3 instance over Fr (x^5, t = arity + 1, R_F = 8, R_P = 56 / 57 / 56 / 60);
+ *                          bn254_fr_poseidon_permute_batch  the permutation itself on n states of t records;  bn254_fr_merkle_tree  every node of the binary
+ *                          tree of hash(left, right) over 2^log_n leaves; none has a counterpart in the reference
+ *   bn254_fr_poseidon_batch_dev / bn254_fr_poseidon_permute_batch_dev / bn254_fr_merkle_tree_dev  the same three on device-resident records, asynchronous on the caller's stream
  *   bn254_g2_precompute    coeffs[i][0..102) = q[i].to_affine().precompute().coeffs   groups/mod.rs:557-588 (Q != infinity)
  *   bn254_pairing_prepared_batch  out[i] = final_exponentiation(prepared.miller_loop(p[i]))   groups/mod.rs:486-519,768
  *   bn254_gt_mul_batch     out[i] = a[i] * b[i]                                     lib.rs:175-179, fields/fq12.rs:295-307
@@ -90,6 +94,7 @@
      bn254_fr_dot_batch serialises on the context in the same way (its mutex for the whole call).
      bn254_fr_scan_batch serialises on the context in the same way (its mutex for the whole call).
      bn254_fr_mle_eq, bn254_fr_mle_fold and bn254_fr_sumcheck_round serialise on the context in the same way (its mutex for the whole call).
+     bn254_fr_poseidon_batch, bn254_fr_poseidon_permute_batch and bn254_fr_merkle_tree serialise on the context in the same way (its mutex for the whole call).
  *     bn254_pairing_product_batch_prepared_native serialises on the context like them; its handle is immutable and shared freely.
  *     Use one context per thread (or bn254_multi_*) for more overlap;
  *     bn254_ctx_set_option is atomic, but set options before concurrent use: a call in flight may run some
@@ -124,6 +129,9 @@
      group description before they return (both travel as kernel arguments: nothing is uploaded).  The partial sums of
      bn254_fr_sumcheck_round_dev are context-owned scratch under the same event ordering.  None of the three waits on anything or reads
      anything back.
+     bn254_fr_poseidon_batch_dev, bn254_fr_poseidon_permute_batch_dev and bn254_fr_merkle_tree_dev use no scratch and no host operand: the levels of a
+     tree are launches in stream order that read what the level before wrote into the caller's `nodes`.  None of the three waits on anything
+     or reads anything back, so any number of threads may issue them on one context, each on its own stream and buffers.
  */
 #ifndef BN254_HIP_H
 #define BN254_HIP_H
@@ -544,6 +552,36 @@ int bn254_fr_mle_eq(bn254_ctx *ctx, const bn_fr *z, int nv, bn_fr *out);
 int bn254_fr_mle_fold(bn254_ctx *ctx, const bn_fr *in, size_t len, const bn_fr *r, bn_fr *out);
 int bn254_fr_sumcheck_round(bn254_ctx *ctx, const bn_fr *tables, size_t n, size_t k, const size_t *group_offsets, const uint64_t *group_tables, const bn_fr *group_coeff, size_t g,
                             int degree, bn_fr *out);
+/* Poseidon hashes and Merkle trees over Fr: the hash that lives in the field - Semaphore / Tornado style membership trees, circom's
+   poseidon.circom, iden3 sparse trees, witness generation for a circuit that hashes, in-circuit Fiat-Shamir.  The instance is circomlib's:
+   S-box x^5, state width t = arity + 1 for arity 1 .. 4, R_F = 8 full rounds (four in front, four behind) around R_P = 56 / 57 / 56 / 60 partial rounds
+   for t = 2 / 3 / 4 / 5; round constants and the Cauchy matrix from the Grain LFSR of the Poseidon paper (bn_amd/poseidon.py derives them,
+   bn_amd/csrc/poseidon_constants.hpp is generated from it; hash(1, 2) = 7853200120776062878684798364095072458815029376092732009249414926327459813530).  One round: s[i] += C[round * t + i]; s[i] = s[i]^5 for every i (full round) or for i = 0 only (partial round);
+   new[i] = sum_j M[i][j] * s[j].  hash(x_1 .. x_arity) = permute([0, x_1, .., x_arity])[0].  Inputs are canonical Montgomery images; outputs are
+   canonical, hence the bytes are those of the integer model.
+   bn254_fr_poseidon_batch: `in` holds n * arity records, row-major; out[i] = hash(in[i * arity], .., in[i * arity + arity - 1]).  `out` must not overlap `in`.
+   bn254_fr_poseidon_permute_batch: n states of t records each, t = 2 .. 5; out[i * t .. i * t + t) = permute(in[i * t .. i * t + t)).  `out` may be
+   exactly `in` (a lane reads its t records before it writes them); any other overlap is undefined.
+   bn254_fr_merkle_tree: with n = 2^log_n leaves, `nodes` receives the n - 1 inner nodes level by level: first the n / 2 parents of the leaves, then
+   the n / 4 parents of those, and so on until the root, nodes[n - 2].  Parent i of a level is hash(child[2 i], child[2 i + 1]) (t = 3).
+   log_n == 0 writes nothing (the leaf is the root).  `nodes` must not overlap `leaves`.
+   How: one lane per permutation, one kernel instance per width; the state stays in registers, the loop over the rounds is not unrolled and
+   the constants are addressed by the round counter alone.  The plain schedule (t^2 products per partial round) is what runs.  A tree is one
+   launch per level in stream order, every launch cut into sub-launches of at most 2^22 lanes; no workgroup waits for another, no atomics, no
+   LDS, no scratch.  The top levels of a tree are single lanes running a chain of about 830 dependent products each.
+   Measured on an MI355X (tools/time_poseidon.py, kernel ms, medians of 5; profiles/r18_poseidon.txt): 2^20 hashes of arity 1 / 2 / 3 / 4 take
+   4.7968 / 7.1311 / 10.1963 / 15.2952 ms, 0.46 x bn254_fr_mul_batch_dev on the 828 products of the plain schedule at arity 2; ONE hash of arity 2 takes
+   0.7967 ms; a tree of 2^20 leaves 20.1076 ms, of which the seven levels of at most 64 hashes take 5.4096 ms.  A matrix row is one product-sum with a
+   single reduction (fr.hpp fr_dot) - by a rule fixed before measuring, 7.1201 against 9.5540 ms on 2^20 hashes of arity 2.
+   n == 0 returns BN254_OK and writes nothing.
+   Errors (BN254_E_BAD_ARG, checked before any device is touched): arity outside 1 .. BN254_POSEIDON_ARITY_MAX; t outside 2 .. 5; log_n outside
+   0 .. BN254_MERKLE_LOG_MAX; a NULL pointer with work to do; n * t > 2^40.  Threading: see above - the host-buffer entry points hold the context's
+   mutex for the whole call. */
+#define BN254_POSEIDON_ARITY_MAX 4
+#define BN254_MERKLE_LOG_MAX 24
+int bn254_fr_poseidon_batch(bn254_ctx *ctx, const bn_fr *in, int arity, bn_fr *out, size_t n);
+int bn254_fr_poseidon_permute_batch(bn254_ctx *ctx, const bn_fr *in, int t, bn_fr *out, size_t n);
+int bn254_fr_merkle_tree(bn254_ctx *ctx, const bn_fr *leaves, int log_n, bn_fr *nodes);
 
 /* ---- one node, several GPUs (north_star: independent batches shard across the GPUs; ONE exchange for the multi-pairing) --- */
 /* `devices[0..ndev)`: HIP device index of every rank (NULL = 0..ndev-1).  One context and one host thread per rank.  A device may
@@ -713,6 +751,12 @@ int bn254_fr_mle_eq_dev(bn254_ctx *ctx, const void *d_z, int nv, void *d_out, vo
 int bn254_fr_mle_fold_dev(bn254_ctx *ctx, const void *d_in, size_t len, const bn_fr *r, void *d_out, void *stream);
 int bn254_fr_sumcheck_round_dev(bn254_ctx *ctx, const void *d_tables, size_t n, size_t k, const size_t *group_offsets, const uint64_t *group_tables, const bn_fr *group_coeff,
                                 size_t g, int degree, void *d_out, void *stream);
+/* bn254_fr_poseidon_batch / bn254_fr_poseidon_permute_batch / bn254_fr_merkle_tree on device-resident records of 32 bytes, 16-byte aligned, asynchronous on
+   `stream`: d_in (n * arity records) and d_out (n); d_in and d_out (n * t each; d_out may be exactly d_in); d_leaves (2^log_n) and d_nodes
+   (2^log_n - 1).  No host operand, no scratch; none waits for anything or reads anything back. */
+int bn254_fr_poseidon_batch_dev(bn254_ctx *ctx, const void *d_in, int arity, void *d_out, size_t n, void *stream);
+int bn254_fr_poseidon_permute_batch_dev(bn254_ctx *ctx, const void *d_in, int t, void *d_out, size_t n, void *stream);
+int bn254_fr_merkle_tree_dev(bn254_ctx *ctx, const void *d_leaves, int log_n, void *d_nodes, void *stream);
 /* raw Jacobian result of the reference's MSB-first double-and-add (what G::random produces, groups/mod.rs:220-222):
    used to generate benchmark inputs with z != 1 on the device */
 int bn254_g1_mul_jacobian_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, void *d_out, size_t n, void *stream);
@@ -734,6 +778,7 @@ int bn254_profile_reset(bn254_ctx *ctx);
    of bn254_fr_dot_batch: "fr_dot" (the pieces: products and sums), "fr_dot_fold" (the levels over the partial sums);
    of bn254_fr_scan_batch: "fr_scan" (the apply level, direct segments among it), "fr_scan_reduce" (the maps of the pieces), "fr_scan_up", "fr_scan_down" (the levels over the maps);
    of bn254_fr_mle_eq, bn254_fr_mle_fold and bn254_fr_sumcheck_round: "fr_mle_eq", "fr_mle_fold", "fr_sumcheck_round" (the lanes over the indices), "fr_sumcheck_sum" (the levels over the partial sums);
+   of bn254_fr_poseidon_batch, bn254_fr_poseidon_permute_batch and bn254_fr_merkle_tree: "fr_poseidon", "fr_poseidon_permute", "fr_merkle_level" (one scope per level, or per sub-launch of it);
    and, of bn254_fr_ntt_batch: "ntt" (the passes), "ntt_table" (the builds of the twiddle tables).
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);
