@@ -98,6 +98,7 @@ extern "C" {
     fn bn254_fr_mle_eq(ctx: *mut c_void, z: *const Fr, nv: c_int, out: *mut Fr) -> c_int;
     fn bn254_fr_mle_fold(ctx: *mut c_void, input: *const Fr, len: usize, r: *const Fr, out: *mut Fr) -> c_int;
     fn bn254_fr_sumcheck_round(ctx: *mut c_void, tables: *const Fr, n: usize, k: usize, group_offsets: *const usize, group_tables: *const u64, group_coeff: *const Fr, g: usize, degree: c_int, out: *mut Fr) -> c_int;
+    fn bn254_fr_mle_quotients(ctx: *mut c_void, a: *const Fr, nv: c_int, z: *const Fr, out: *mut Fr) -> c_int;
     fn bn254_fr_poseidon_batch(ctx: *mut c_void, input: *const Fr, arity: c_int, out: *mut Fr, n: usize) -> c_int;
     fn bn254_fr_poseidon_permute_batch(ctx: *mut c_void, input: *const Fr, t: c_int, out: *mut Fr, n: usize) -> c_int;
     fn bn254_fr_merkle_tree(ctx: *mut c_void, leaves: *const Fr, log_n: c_int, nodes: *mut Fr) -> c_int;
@@ -112,6 +113,7 @@ extern "C" {
     fn bn254_fr_mle_eq_dev(ctx: *mut c_void, d_z: *const c_void, nv: c_int, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn bn254_fr_mle_fold_dev(ctx: *mut c_void, d_in: *const c_void, len: usize, r: *const Fr, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn bn254_fr_sumcheck_round_dev(ctx: *mut c_void, d_tables: *const c_void, n: usize, k: usize, group_offsets: *const usize, group_tables: *const u64, group_coeff: *const Fr, g: usize, degree: c_int, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn bn254_fr_mle_quotients_dev(ctx: *mut c_void, d_a: *const c_void, nv: c_int, z: *const Fr, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn bn254_fr_poseidon_batch_dev(ctx: *mut c_void, d_in: *const c_void, arity: c_int, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_poseidon_permute_batch_dev(ctx: *mut c_void, d_in: *const c_void, t: c_int, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_merkle_tree_dev(ctx: *mut c_void, d_leaves: *const c_void, log_n: c_int, d_nodes: *mut c_void, stream: *mut c_void) -> c_int;
@@ -420,6 +422,16 @@ pub fn fr_sumcheck_round(tables: &[Fr], k: usize, group_offsets: &[usize], group
     check(unsafe {
         bn254_fr_sumcheck_round(std::ptr::null_mut(), tables.as_ptr(), tables.len() / k, k, group_offsets.as_ptr(), group_tables.as_ptr(), group_coeff.as_ptr(), g, degree as c_int, out.as_mut_ptr())
     })?;
+    Ok(out)
+}
+
+/// The quotients of a multilinear opening of the table `a` (`2^z.len()` values) at `z`, in heap order: `out[0] = f(z)` and `out[2^j + i] = q_j[i]`
+/// with `f(x) - f(z) = sum_j (x_j - z_j) q_j(x_0 .. x_{j-1})` - from `t = a`, for `j = nv - 1` down to `0`, `q_j[i] = t[i + 2^j] - t[i]` and
+/// `t[i] += z[j] * q_j[i]`.  The field work of a multilinear KZG opening.
+pub fn fr_mle_quotients(a: &[Fr], z: &[Fr]) -> Result<Vec<Fr>, GpuError> {
+    assert!(z.len() <= 30 && a.len() == 1usize << z.len());
+    let mut out = vec![Fr::zero(); a.len()];
+    check(unsafe { bn254_fr_mle_quotients(std::ptr::null_mut(), a.as_ptr(), z.len() as c_int, z.as_ptr(), out.as_mut_ptr()) })?;
     Ok(out)
 }
 

@@ -439,6 +439,15 @@ def fr_sumcheck_round(tables, groups, degree=None, engine=None):
     return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_sumcheck_round(t, groups, degree)]
 
 
+def fr_mle_quotients(a, z, engine=None):
+    """The quotients of the multilinear table a at the point z -> list of len(a) Fr in heap order: out[0] = f(z) and out[2^j + i] = q_j[i] for
+    j < nv, i < 2^j, with f(x) - f(z) = sum_j (x_j - z_j) q_j(x_0 .. x_{j-1}): from t = a, for j = nv - 1 down to 0, q_j[i] = t[i + 2^j] - t[i] and
+    t[i] += z[j] * q_j[i].  a: a sequence of 2^nv Fr or an (n,4) uint64 array; z: nv Fr.  ValueError unless len(a) == 2^len(z) <= 2^30."""
+    from .engine import _mle_quotients_args
+    A, Z = _mle_quotients_args(_scalar_array(a), _scalar_array(z))
+    return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_mle_quotients(A, Z)]
+
+
 def _poseidon_rows(rows):
     """rows of Fr (a sequence of equally long sequences) or an (n, width, 4) uint64 array -> the array"""
     if isinstance(rows, np.ndarray):

@@ -1,6 +1,7 @@
-// Multilinear tables and sumcheck rounds over Fr on the device (include/bn254_hip.h bn254_fr_mle_eq, bn254_fr_mle_fold, bn254_fr_sumcheck_round and
-// their _dev twins): the kernels - instances of bn254_fr_decode_k<Op> like the other integer kernels, one lane of the bodies of mle_ops.hpp
-// each -, the levels host_plan.hpp's bn_sumcheck_plan computes as sub-launches, and the six entry points.
+// Multilinear tables and sumcheck rounds over Fr on the device (include/bn254_hip.h bn254_fr_mle_eq, bn254_fr_mle_fold, bn254_fr_sumcheck_round,
+// bn254_fr_mle_quotients and their _dev twins): the kernels - instances of bn254_fr_decode_k<Op> like the other integer kernels, one lane of the
+// bodies of mle_ops.hpp each -, the levels host_plan.hpp's bn_sumcheck_plan and the passes its bn_mle_quotients_plan compute as sub-launches,
+// and the eight entry points.
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -43,6 +44,15 @@ struct FrSumcheckSumOp {
         if (i < n) fr_sumcheck_sum_body(src, cnt, F, dst, lo + i);
     }
 };
+// a pass of RHO levels over the working table of 2^m records: zz[k] = z[m - 1 - k], by value like the fold's r
+template <int RHO>
+struct FrMleQuotOp {
+    const uint32_t *src; Fr zz[RHO]; uint32_t m; uint32_t *fold_dst, *out; uint64_t lo; uint32_t n;
+    __device__ __forceinline__ void operator()() const {
+        const uint32_t i = blockIdx.x * MLE_BLOCK + threadIdx.x;
+        if (i < n) fr_mle_quotients_body<RHO>(src, zz, m, fold_dst, out, lo + i);
+    }
+};
 template <class Op>
 __global__ void __launch_bounds__(MLE_BLOCK) bn254_fr_decode_k(Op op) { op(); }
 
@@ -52,10 +62,12 @@ int mle_launch(const Op &op, size_t lanes, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
-// tests and tools/time_mle.py only: the sub-launch size (0 = BN_LAUNCH_MAX) and the piece length the sweep times (0 = the shipped constant)
+// tests and tools/time_mle.py, tools/time_mle_open.py only: the sub-launch size (0 = BN_LAUNCH_MAX), the piece length and the levels per
+// quotient pass the sweeps time (0 = the shipped constants)
 std::atomic<size_t> g_mle_launch_max;
-std::atomic<unsigned> g_sumcheck_piece;
+std::atomic<unsigned> g_sumcheck_piece, g_mle_quot_levels;
 size_t mle_step() { const size_t set = g_mle_launch_max.load(std::memory_order_relaxed); return set ? set : BN_LAUNCH_MAX; }
+unsigned quot_levels() { const unsigned set = g_mle_quot_levels.load(std::memory_order_relaxed); return set ? set : FR_MLE_QUOT_LEVELS; }
 unsigned sumcheck_piece() { const unsigned set = g_sumcheck_piece.load(std::memory_order_relaxed); return set ? set : FR_SUMCHECK_PIECE; }
 
 int eq_run(bn254_ctx *c, const void *d_z, int nv, void *d_out, hipStream_t s) {
@@ -99,6 +111,36 @@ int round_run(bn254_ctx *c, const void *d_tables, size_t n, size_t k, const BnSu
         rc = bn_for_parts(lv.lanes, mle_step(), [&](size_t lo, size_t cnt) -> int {
             BnScope sc(c, s, "fr_sumcheck_sum");
             return mle_launch(FrSumcheckSumOp{ws + 8 * lv.src, (uint64_t)lv.cnt, FR_SUMCHECK_FAN, lv.to_out ? out : ws + 8 * lv.dst, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
+        });
+        if (rc) return rc;
+    }
+    return BN254_OK;
+}
+template <int RHO>
+int quot_launch(const uint32_t *src, const bn_fr *z, unsigned m, uint32_t *fold_dst, uint32_t *out, size_t lo, size_t cnt, hipStream_t s) {
+    FrMleQuotOp<RHO> op{src, {}, (uint32_t)m, fold_dst, out, (uint64_t)lo, (uint32_t)cnt};
+    for (int k = 0; k < RHO; ++k) memcpy(op.zz[k].w, z[m - 1 - k].l, sizeof op.zz[k].w);
+    return mle_launch(op, cnt, s);
+}
+// scratch guard held by the caller.  The passes in the plan's order, each as sub-launches of at most mle_step() lanes; the stream orders
+// them.  The first reads a and leaves the folded table in the scratch, the later ones run in place there; a is never written.
+int quotients_run(bn254_ctx *c, const void *d_a, int nv, const bn_fr *z, void *d_out, hipStream_t s) {
+    uint32_t *const out = (uint32_t *)d_out;
+    if (nv == 0) return (int)hipMemcpyAsync(out, d_a, sizeof(bn_fr), hipMemcpyDeviceToDevice, s);
+    const BnMleQuotPlan plan = bn_mle_quotients_plan((unsigned)nv, quot_levels());
+    int rc = c->mle_ws.reserve(plan.slots * sizeof(bn_fr)); if (rc) return rc;
+    uint32_t *const ws = (uint32_t *)c->mle_ws.p;
+    for (const BnMleQuotPass &ps : plan.passes) {
+        const uint32_t *src = ps.first ? (const uint32_t *)d_a : ws;
+        uint32_t *fold_dst = ps.last ? out : ws;
+        rc = bn_for_parts(ps.lanes, mle_step(), [&](size_t lo, size_t cnt) -> int {
+            BnScope sc(c, s, FR_MLE_QUOT_SCOPE);
+            switch (ps.levels) {
+            case 1: return quot_launch<1>(src, z, ps.vars, fold_dst, out, lo, cnt, s);
+            case 2: return quot_launch<2>(src, z, ps.vars, fold_dst, out, lo, cnt, s);
+            case 3: return quot_launch<3>(src, z, ps.vars, fold_dst, out, lo, cnt, s);
+            default: return quot_launch<4>(src, z, ps.vars, fold_dst, out, lo, cnt, s);
+            }
         });
         if (rc) return rc;
     }
@@ -153,6 +195,20 @@ int bn254_fr_sumcheck_round(bn254_ctx *ctx, const bn_fr *tables, size_t n, size_
         return bn254_fr_sumcheck_round_dev(ctx, d.in[0], n, k, group_offsets, group_tables, group_coeff, g, degree, d.out, ctx->stream);
     });
 }
+// z is HOST memory in both forms: its records travel as kernel arguments.  out must not overlap a.
+int bn254_fr_mle_quotients_dev(bn254_ctx *ctx, const void *d_a, int nv, const bn_fr *z, void *d_out, void *stream) {
+    int rc = bn_mle_quotients_check(d_a, nv, z, d_out); if (rc) return rc;
+    if ((rc = bn_get_ctx(ctx))) return rc;
+    BnDev d(ctx, stream); if (!d.go) return d.rc;
+    BnScratchGuard guard(ctx, d.s); if (guard.rc) return guard.rc;
+    return bn_no_throw([&] { return quotients_run(ctx, d_a, nv, z, d_out, d.s); });
+}
+int bn254_fr_mle_quotients(bn254_ctx *ctx, const bn_fr *a, int nv, const bn_fr *z, bn_fr *out) {
+    int rc = bn_mle_quotients_check(a, nv, z, out); if (rc) return rc;
+    BnHost h(ctx); if (h.rc) return h.rc;
+    return bn_staged(ctx, {a, sizeof(bn_fr) << nv}, {nullptr, 0}, out, sizeof(bn_fr) << nv, nullptr, 0,
+                     [&](const BnStaged &d) { return bn254_fr_mle_quotients_dev(ctx, d.in[0], nv, z, d.out, ctx->stream); });
+}
 
 // internal (not in the header; tests and tools/time_mle.py): the shipped piece length and fan of the round, an override of the sub-launch
 // size of all three calls (0 restores BN_LAUNCH_MAX) so that a test reaches the seam between two sub-launches with a handful of lanes, and
@@ -162,6 +218,14 @@ unsigned bn254_fr_sumcheck_fan(void) { return FR_SUMCHECK_FAN; }
 int bn254_fr_mle_set_launch_max(size_t lanes) {
     if (lanes > BN_LAUNCH_MAX) return BN254_E_BAD_ARG;
     g_mle_launch_max.store(lanes, std::memory_order_relaxed);
+    return BN254_OK;
+}
+// the shipped levels per quotient pass and - for the sweep of tools/time_mle_open.py only - a process-wide override (0 restores the shipped
+// one; same bytes whatever is set)
+unsigned bn254_fr_mle_quotients_levels(void) { return FR_MLE_QUOT_LEVELS; }
+int bn254_fr_mle_quotients_set_levels(unsigned rho) {
+    if (rho > FR_MLE_QUOT_LEVELS_MAX) return BN254_E_BAD_ARG;
+    g_mle_quot_levels.store(rho, std::memory_order_relaxed);
     return BN254_OK;
 }
 int bn254_fr_sumcheck_set_piece(unsigned P) {

@@ -1,5 +1,5 @@
 // Host arithmetic over sizes and offsets: the argument checks that need no device, the work lists of the segmented folds, the cutting of a
-// prepared batch into Miller pieces, the workspace of the bucket method and its tail scalars, the scalars of the fixed-base tables, the passes of a transform, the pieces of a sparse linear map, the levels of a segmented scan and of a sumcheck round.  Plain C++17: nothing here touches a device, so
+// prepared batch into Miller pieces, the workspace of the bucket method and its tail scalars, the scalars of the fixed-base tables, the passes of a transform, the pieces of a sparse linear map, the levels of a segmented scan and of a sumcheck round, the passes of the quotients of a multilinear opening.  Plain C++17: nothing here touches a device, so
 // tests/hostsim/ compiles it with g++ and tests/test_host_plan.py replays the plans on the CPU.  (io.hpp: the two records the kernels read.)
 #pragma once
 #include <algorithm>
@@ -536,6 +536,35 @@ inline BnSumcheckPlan bn_sumcheck_plan(size_t h, unsigned degree, size_t P, size
         if (cnt2 == 1) break;
         src = plan.slots; plan.slots += T * cnt2; cnt = cnt2;
     }
+    return plan;
+}
+
+// ---- the quotients of a multilinear opening (bn254_fr_mle_quotients): the argument check and the passes
+// a and out hold 2^nv records of 32 bytes each and must not overlap (a pass reads a while the quotients of its levels are written)
+inline int bn_mle_quotients_check(const void *a, int nv, const void *z, const void *out) {
+    if (nv < 0 || nv > BN254_MLE_VARS_MAX || !a || !out || (nv && !z)) return BN254_E_BAD_ARG;
+    const uintptr_t pa = (uintptr_t)a, po = (uintptr_t)out, bytes = (uintptr_t)sizeof(bn_fr) << nv;
+    return (pa < po ? po - pa < bytes : pa - po < bytes) ? BN254_E_BAD_ARG : BN254_OK;
+}
+// The nv levels of a call run as passes of `rho` levels each, the full ones first, and the remainder nv mod rho last, on the small table.  A
+// pass of `levels` levels over the working table of 2^vars records has lanes = 2^(vars - levels) lanes; lane i reads the records i + c * lanes,
+// c < 2^levels, writes the quotient of level k (k < levels, variable j = vars - 1 - k) at index i + c * lanes, c < 2^(levels - 1 - k), to record
+// 2^j + i + c * lanes of the output, and record i of the folded table.  The first pass reads `a` and writes the folded table to the scratch
+// (`slots` records: its lanes); the later ones read the scratch and write it in place.  The last pass has one lane and its folded record is
+// record 0 of the output.  nv == 0 has no pass: the one record is copied.
+struct BnMleQuotPass { unsigned levels, vars; size_t lanes; bool first, last; };
+struct BnMleQuotPlan {
+    std::vector<BnMleQuotPass> passes;
+    size_t slots = 0;                                       // scratch records of 32 bytes
+};
+inline BnMleQuotPlan bn_mle_quotients_plan(unsigned nv, unsigned rho) {
+    BnMleQuotPlan plan;
+    for (unsigned vars = nv; vars > 0;) {
+        const unsigned levels = vars >= rho ? rho : vars;
+        plan.passes.push_back({levels, vars, (size_t)1 << (vars - levels), vars == nv, vars == levels});
+        vars -= levels;
+    }
+    if (!plan.passes.empty()) plan.slots = plan.passes[0].lanes;
     return plan;
 }
 

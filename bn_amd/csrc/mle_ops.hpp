@@ -1,5 +1,5 @@
-// The per-lane bodies of the multilinear kernels over Fr (bn254_mle.hip): bn254_fr_mle_eq, bn254_fr_mle_fold, bn254_fr_sumcheck_round and
-// their _dev twins.  A multilinear table of nv variables is 2^nv records; the record at index i is the value at the point whose variable j is
+// The per-lane bodies of the multilinear kernels over Fr (bn254_mle.hip): bn254_fr_mle_eq, bn254_fr_mle_fold, bn254_fr_sumcheck_round,
+// bn254_fr_mle_quotients and their _dev twins.  A multilinear table of nv variables is 2^nv records; the record at index i is the value at the point whose variable j is
 // bit j of i.  Several tables of one sumcheck are stored index-major: tables[i * k + j] is table j at index i.
 //   eq      out[i] = prod_{j < nv} (bit j of i ? z[j] : 1 - z[j]): one lane per element, nv products, whatever the data
 //   fold    out[i] = in[i] + r * (in[i + half] - in[i]): binds the MOST significant variable; lane i alone touches records i and i + half
@@ -7,10 +7,13 @@
 //           There are `lanes` = ceil(h / P) lanes and lane l sums the at most P indices l, l + lanes, l + 2 lanes, .. below h, so that the lanes of
 //           a wave read neighbouring rows; its D + 1 sums go to part[t * lanes + l] - or, with one lane, straight to out[t]
 //   sum     levels of fan F over the partial sums (additions only), laid out [t][piece] before and after; the last level writes out[t]
+//   quotients  the nv tables q_j of an opening at z, f(x) - f(z) = sum_j (x_j - z_j) q_j(x_0 .. x_{j-1}): from t = a, for j = nv - 1 down to 0 with
+//           half = 2^j, q_j[i] = t[i + half] - t[i] and t[i] += z[j] q_j[i] - the fold by z[j], whose difference is kept.  One launch does RHO of
+//           these levels in registers: a pass over a table of L records has L / 2^RHO lanes and lane i holds the records i + c L / 2^RHO
 // so the length of a lane's serial chain is a constant of the plan, never a property of the data, and no lane waits for another: the order
 // between the levels is the order of the launches on their stream.  Every product and every sum is canonical (fr.hpp), hence the bytes are
 // those of the Python-integer sums however the indices are dealt out.  Everything is pure and takes plain pointers and a lane index, so the
-// host simulation (tests/hostsim/hostsim_mle.cpp) runs the very same bodies over host arrays.
+// host simulation (tests/hostsim/hostsim_mle.cpp, hostsim_mle_open.cpp) runs the very same bodies over host arrays.
 #pragma once
 #include "fr_ops.hpp"
 #include "io.hpp"
@@ -24,6 +27,14 @@ namespace bn254 {
 // sum level: not swept.
 constexpr uint32_t FR_SUMCHECK_PIECE = 16;
 constexpr uint32_t FR_SUMCHECK_FAN = 16;
+// Levels per launch of the quotient kernel, one of 1 / 2 / 3 / 4 (bn254_mle.hip carries a run-time override for the sweep of
+// tools/time_mle_open.py only).  The rule fixed before measuring: the fastest on one table of 2^22 records ships, an instance that spills
+// being out of the sweep.  None spills (52 / 86 / 150 / 265 registers) and 2 is the fastest (0.224 / 0.158 / 0.177 / 0.233 ms,
+// profiles/r19_mle_open.txt), at 2^16 and 2^20 records as well.  Why the larger instances lose was not investigated.
+constexpr uint32_t FR_MLE_QUOT_LEVELS = 2;
+constexpr uint32_t FR_MLE_QUOT_LEVELS_MAX = 4;
+// the profile scope of the quotient passes (a constant here: bn254_mle.hip names its scopes through it)
+constexpr char FR_MLE_QUOT_SCOPE[] = "fr_mle_quotients";
 
 BN_FN void fr_mle_eq_body(const uint32_t *z, uint32_t nv, uint32_t *out, size_t i) {
     const Fr one = fr_one();
@@ -39,6 +50,36 @@ BN_FN void fr_mle_eq_body(const uint32_t *z, uint32_t nv, uint32_t *out, size_t 
 BN_FN void fr_mle_fold_body(const uint32_t *in, const Fr &r, uint32_t *out, size_t half, size_t i) {
     const Fr lo = fr_load(in, i), hi = fr_load(in, i + half);
     fr_store(fr_add(lo, fr_mul(fr_sub(hi, lo), r)), out, i);
+}
+// one level over the 2 HC records a lane has left, record pair C and the pairs after it.  A recursion over template arguments, not a loop:
+// every index into v is a constant whatever the unroller's budget makes of eight products in a row, so v stays in registers
+template <int HC, int C = 0>
+BN_FN void fr_mle_quotients_level(Fr *v, const Fr &zk, uint32_t *out, size_t at, size_t S) {
+    if constexpr (C < HC) {
+        const Fr q = fr_sub(v[C + HC], v[C]);
+        fr_store(q, out, at + C * S);
+        v[C] = fr_add(v[C], fr_mul(q, zk));
+        fr_mle_quotients_level<HC, C + 1>(v, zk, out, at, S);
+    }
+}
+// Lane i of a quotient pass of RHO levels over a table of 2^m records at src (m >= RHO), S = 2^(m - RHO) lanes.  The lane loads the 2^RHO
+// records i + c S - all of them before it stores anything - and level k binds variable j = m - 1 - k by zz[k] = z[j]: among the 2^(RHO - k)
+// records left, c and c + 2^(RHO - 1 - k) are index i + c S and its partner half = 2^j above.  The difference is q_j[i + c S], record
+// 2^j + i + c S of the heap `out`; the sum is the folded record.  After RHO levels record i of the folded table goes to fold_dst[i] - the
+// working table, which may be src (no other lane touches the records of this one), or, in the last pass (S == 1), out itself: record 0.
+// At every load and store the lanes of a wave touch neighbouring records.
+template <int RHO>
+BN_FN void fr_mle_quotients_body(const uint32_t *src, const Fr *zz, uint32_t m, uint32_t *fold_dst, uint32_t *out, size_t i) {
+    static_assert(RHO >= 1 && RHO <= (int)FR_MLE_QUOT_LEVELS_MAX, "one instance per number of levels");
+    const size_t S = (size_t)1 << (m - RHO), top = (size_t)1 << (m - 1);
+    Fr v[1 << RHO];
+#pragma unroll
+    for (int c = 0; c < (1 << RHO); ++c) v[c] = fr_load(src, i + c * S);
+    fr_mle_quotients_level<(1 << (RHO - 1))>(v, zz[0], out, top + i, S);
+    if constexpr (RHO > 1) fr_mle_quotients_level<(1 << (RHO - 2))>(v, zz[1], out, (top >> 1) + i, S);
+    if constexpr (RHO > 2) fr_mle_quotients_level<(1 << (RHO - 3))>(v, zz[2], out, (top >> 2) + i, S);
+    if constexpr (RHO > 3) fr_mle_quotients_level<(1 << (RHO - 4))>(v, zz[3], out, (top >> 3) + i, S);
+    fr_store(v[0], fold_dst, i);
 }
 
 // Lane `lane` of the round kernel.  The factors of a group are walked one at a time: v = lo, d = hi - lo, and per t (unrolled: acc and prod

@@ -159,6 +159,15 @@ def _mle_fold_args(a, r):
     return a, _fr_point(r, "r")
 
 
+def _mle_quotients_args(a, z):
+    """(a as a C-contiguous (2^nv, 4) array, z as (nv, 4)): the table of a multilinear polynomial and a point of as many variables"""
+    z = _mle_eq_args(z)
+    a = _arr(a, 4) if len(a) else np.zeros((0, 4), np.uint64)
+    if a.shape[0] != 1 << z.shape[0]:
+        raise ValueError(f"a holds {a.shape[0]} values but z has {z.shape[0]} variables: 2^{z.shape[0]} are needed")
+    return a, z
+
+
 def _sumcheck_args(tables, groups, degree):
     """the operands of fr_sumcheck_round, checked the way the C ABI checks them (it answers BN254_E_BAD_ARG; here the caller learns which one):
     (tables as (n, k, 4), group offsets, table numbers, coefficients as (g, 4), degree)"""
@@ -470,6 +479,15 @@ class Engine:
         t, off, members, coeff, degree = _sumcheck_args(tables, groups, degree)
         out = np.empty((degree + 1, 4), np.uint64)
         _native.check(self._lib.bn254_fr_sumcheck_round(self._h, _p(t), t.shape[0], t.shape[1], _p(off), _p(members), _p(coeff), off.size - 1, degree, _p(out)))
+        return out
+
+    def fr_mle_quotients(self, a, z):
+        """the quotients of the multilinear table a (2^nv records) at the point z (nv records) -> (2^nv, 4) uint64 in heap order: out[0] = f(z) and
+        out[2^j + i] = q_j[i], where f(x) - f(z) = sum_j (x_j - z_j) q_j(x_0 .. x_{j-1}) - from t = a, for j = nv - 1 down to 0,
+        q_j[i] = t[i + 2^j] - t[i] and t[i] += z[j] * q_j[i] (include/bn254_hip.h bn254_fr_mle_quotients)"""
+        a, z = _mle_quotients_args(a, z)
+        out = np.empty_like(a)
+        _native.check(self._lib.bn254_fr_mle_quotients(self._h, _p(a), z.shape[0], _p(z), _p(out)))
         return out
 
     def fr_poseidon_batch(self, x):
@@ -797,6 +815,12 @@ class Engine:
         flat = np.array([j for m in members for j in m] or [0], np.uint64)
         _native.check(self._lib.bn254_fr_sumcheck_round_dev(self._h, d_tables, n, k, _p(off), _p(flat), _p(coeff), len(members), degree, d_out, stream))
         return degree
+
+    def fr_mle_quotients_dev(self, d_a, z, d_out, stream=0):
+        """device pointers a and out (2^nv records of 32 bytes each; out must not overlap a, which is never written), ordered on `stream`; `z`
+        is a HOST array of nv scalars, read before the call returns"""
+        z = _mle_eq_args(z)                                        # held here until the call has returned
+        _native.check(self._lib.bn254_fr_mle_quotients_dev(self._h, d_a, z.shape[0], _p(z), d_out, stream))
 
     def fr_poseidon_batch_dev(self, d_in, arity, d_out, n, stream=0):
         """device pointers in (n * arity records of 32 bytes, row-major) and out (n records; must not overlap in), ordered on `stream`"""

@@ -6,6 +6,8 @@ lookup arguments.  Round s (from 0) binds variable nv - 1 - s: the prover sends 
 the verifier checks g_s(0) + g_s(1) against the running value (the claim at first), draws r_s, and moves the running value to g_s(r_s).  After
 nv rounds the running value must be the expression at the tables' values at the point, point[j] = r_{nv-1-j}; the prover sends those k
 values (`finals`) and the CALLER checks them against their own commitments or tables (mle.evaluate) - verify only checks that they fit.
+Against commitments that check is bn_amd.mkzg: the prover opens every committed table at the point (mkzg.open) and the verifier accepts
+finals[j] with mkzg.verify against the commitment of table j.
 
 prove uses the host-buffer calls, as kzg and groth16 do: the tables go up once per round for the round polynomial and once for the fold,
 halving every round - about four times their bytes in total over a proof, twice per call kind.  A resident prover is the two _dev calls

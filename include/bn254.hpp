@@ -254,6 +254,14 @@ inline std::vector<Fr> fr_sumcheck_round(const std::vector<Fr> &tables, size_t k
                                   reinterpret_cast<const bn_fr *>(group_coeff.data()), group_coeff.size(), degree, reinterpret_cast<bn_fr *>(out.data())));
     return out;
 }
+// the quotients of a multilinear opening of the table a (2^z.size() values) at z, in heap order: out[0] = f(z) and out[2^j + i] = q_j[i] with
+// f(x) - f(z) = sum_j (x_j - z_j) q_j(x_0 .. x_{j-1}); the field work of a multilinear KZG opening
+inline std::vector<Fr> fr_mle_quotients(const std::vector<Fr> &a, const std::vector<Fr> &z) {
+    if (z.size() > BN254_MLE_VARS_MAX || a.size() != size_t(1) << z.size()) throw std::invalid_argument("fr_mle_quotients: the table holds 2^z.size() values");
+    std::vector<Fr> out(a.size());
+    check(bn254_fr_mle_quotients(nullptr, reinterpret_cast<const bn_fr *>(a.data()), int(z.size()), reinterpret_cast<const bn_fr *>(z.data()), reinterpret_cast<bn_fr *>(out.data())));
+    return out;
+}
 // out[i] = Poseidon(in[i * arity .. (i + 1) * arity)): the circomlib / iden3 hash over Fr, element 0 of the permutation of {0, x_1, .., x_arity}
 inline std::vector<Fr> fr_poseidon(const std::vector<Fr> &in, int arity) {
     if (arity < 1 || arity > BN254_POSEIDON_ARITY_MAX || in.size() % size_t(arity)) throw std::invalid_argument("fr_poseidon: arity and the inputs disagree");

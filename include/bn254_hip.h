@@ -50,6 +50,9 @@
  *                          bn254_fr_mle_fold  out[i] = in[i] + r * (in[i + len/2] - in[i]): binds the most significant variable of a multilinear table;
  *                          bn254_fr_sumcheck_round  the round polynomial of a sum of products of tables at t = 0 .. degree; none has a counterpart in the reference
  *   bn254_fr_mle_eq_dev / bn254_fr_mle_fold_dev / bn254_fr_sumcheck_round_dev  the same three on device-resident tables, asynchronous on the caller's stream
+ *   bn254_fr_mle_quotients  out[0] = f(z) and out[2^j + i] = q_j[i], the nv quotient tables of f(x) - f(z) = sum_j (x_j - z_j) q_j(x_0 .. x_{j-1}) for the multilinear
+ *                          table f: the field work of a multilinear KZG (PST) opening; no counterpart in the reference
+ *   bn254_fr_mle_quotients_dev  the same on a device-resident table, asynchronous on the caller's stream
  *   bn254_fr_poseidon_batch  out[i] = Poseidon(in[i * arity .. (i + 1) * arity)), the circomlib / iden3 instance over Fr (x^5, t = arity + 1, R_F = 8, R_P = 56 / 57 / 56 / 60);
  *                          bn254_fr_poseidon_permute_batch  the permutation itself on n states of t records;  bn254_fr_merkle_tree  every node of the binary
  *                          tree of hash(left, right) over 2^log_n leaves; none has a counterpart in the reference
@@ -94,6 +97,7 @@
      bn254_fr_dot_batch serialises on the context in the same way (its mutex for the whole call).
      bn254_fr_scan_batch serialises on the context in the same way (its mutex for the whole call).
      bn254_fr_mle_eq, bn254_fr_mle_fold and bn254_fr_sumcheck_round serialise on the context in the same way (its mutex for the whole call).
+     bn254_fr_mle_quotients serialises on the context in the same way (its mutex for the whole call).
      bn254_fr_poseidon_batch, bn254_fr_poseidon_permute_batch and bn254_fr_merkle_tree serialise on the context in the same way (its mutex for the whole call).
  *     bn254_pairing_product_batch_prepared_native serialises on the context like them; its handle is immutable and shared freely.
  *     Use one context per thread (or bn254_multi_*) for more overlap;
@@ -129,6 +133,9 @@
      group description before they return (both travel as kernel arguments: nothing is uploaded).  The partial sums of
      bn254_fr_sumcheck_round_dev are context-owned scratch under the same event ordering.  None of the three waits on anything or reads
      anything back.
+     bn254_fr_mle_quotients_dev reads its HOST `z` before it returns (the challenges of a pass travel as kernel arguments: nothing is
+     uploaded).  The working table between its passes is context-owned scratch under the same event ordering - the buffer the partial sums
+     of bn254_fr_sumcheck_round_dev use, so the two serialise on it across streams.  It waits on nothing and reads nothing back.
      bn254_fr_poseidon_batch_dev, bn254_fr_poseidon_permute_batch_dev and bn254_fr_merkle_tree_dev use no scratch and no host operand: the levels of a
      tree are launches in stream order that read what the level before wrote into the caller's `nodes`.  None of the three waits on anything
      or reads anything back, so any number of threads may issue them on one context, each on its own stream and buffers.
@@ -552,6 +559,28 @@ int bn254_fr_mle_eq(bn254_ctx *ctx, const bn_fr *z, int nv, bn_fr *out);
 int bn254_fr_mle_fold(bn254_ctx *ctx, const bn_fr *in, size_t len, const bn_fr *r, bn_fr *out);
 int bn254_fr_sumcheck_round(bn254_ctx *ctx, const bn_fr *tables, size_t n, size_t k, const size_t *group_offsets, const uint64_t *group_tables, const bn_fr *group_coeff, size_t g,
                             int degree, bn_fr *out);
+/* The quotients of a multilinear opening: the prover's field work of a multilinear KZG (PST) commitment.  Conventions are those of the
+   multilinear calls above: index i is the point whose variable j is bit j of i, the MOST significant variable is bound first, everything is
+   canonical, so the bytes are those of the integer model however the work is cut.  For a table `a` of n = 2^nv records and a point z[0 .. nv),
+   start with t = a; for j = nv - 1 down to 0, with half = 2^j,
+       q_j[i] = t[i + half] - t[i]   and   t[i] = t[i] + z[j] * q_j[i]   for i < half,
+   so that f(x) - f(z) = sum_j (x_j - z_j) q_j(x_0 .. x_{j-1}) for the multilinear f with the values a.  `out` has n records in heap order:
+   out[0] = f(z), the one record left, and out[2^j + i] = q_j[i] for j < nv, i < 2^j - the layout in which segment [2^j, 2^(j+1)) meets level j of a
+   reference string without a copy.  nv == 0 copies the record to out[0].  `z` is HOST memory.  `a` is never written; `out` must NOT overlap `a`
+   (aliasing is not supported: a pass still reads `a` while quotients are written).
+   How: one launch does rho = 2 levels in registers.  A pass over a table of L records has L / 2^rho lanes; lane i loads the 2^rho records
+   i + c L / 2^rho - all before it writes anything -, does rho levels on them, stores its 2^rho - 1 quotient records to their heap positions and its
+   one folded record to position i of the working table; neighbouring lanes touch neighbouring records at every load and store.  So rho levels
+   cost one read and one write of the level's bytes.  A call is ceil(nv / rho) launches ordered by the stream: the full passes first, the
+   remainder of nv mod rho levels last, on the small table; the first pass reads `a` and writes the working table to context-owned scratch
+   (2^(nv - rho) records: a quarter of the table), the later ones run in place there; every pass is cut into sub-launches of at most 2^22 lanes.  No LDS, no atomics,
+   no workgroup waits on another, and a lane's serial chain is a constant of the plan.  Measured on an MI355X (tools/time_mle_open.py, kernel ms,
+   medians of 5; profiles/r19_mle_open.txt): one table of 2^22 records takes 0.224 / 0.158 / 0.177 / 0.233 ms at rho = 1 / 2 / 3 / 4 (52 / 86 / 150 / 265
+   registers, none spills) - the fastest ships, by a rule fixed before measuring -, which is 3.97 x a device-to-device copy of the 2 n records
+   the call must move and 2.51 x faster than the same quotients from bn254_fr_add_batch_dev and bn254_fr_mle_fold_dev (2 nv launches).
+   Errors (BN254_E_BAD_ARG, checked before any device is touched): nv outside 0 .. BN254_MLE_VARS_MAX, a NULL a or out, a NULL z with nv > 0,
+   out overlapping a.  Threading: see above - the host-buffer entry point holds the context's mutex for the whole call. */
+int bn254_fr_mle_quotients(bn254_ctx *ctx, const bn_fr *a, int nv, const bn_fr *z, bn_fr *out);
 /* Poseidon hashes and Merkle trees over Fr: the hash that lives in the field - Semaphore / Tornado style membership trees, circom's
    poseidon.circom, iden3 sparse trees, witness generation for a circuit that hashes, in-circuit Fiat-Shamir.  The instance is circomlib's:
    S-box x^5, state width t = arity + 1 for arity 1 .. 4, R_F = 8 full rounds (four in front, four behind) around R_P = 56 / 57 / 56 / 60 partial rounds
@@ -751,6 +780,10 @@ int bn254_fr_mle_eq_dev(bn254_ctx *ctx, const void *d_z, int nv, void *d_out, vo
 int bn254_fr_mle_fold_dev(bn254_ctx *ctx, const void *d_in, size_t len, const bn_fr *r, void *d_out, void *stream);
 int bn254_fr_sumcheck_round_dev(bn254_ctx *ctx, const void *d_tables, size_t n, size_t k, const size_t *group_offsets, const uint64_t *group_tables, const bn_fr *group_coeff,
                                 size_t g, int degree, void *d_out, void *stream);
+/* bn254_fr_mle_quotients on device-resident records of 32 bytes, 16-byte aligned, asynchronous on `stream`: d_a and d_out hold 2^nv records each and
+   must not overlap; d_a is never written.  `z` (nv records) is HOST memory, read before the call returns, and may be freed then.  The call
+   waits for nothing and reads nothing back; the working table between its passes is context-owned scratch (see Threading). */
+int bn254_fr_mle_quotients_dev(bn254_ctx *ctx, const void *d_a, int nv, const bn_fr *z, void *d_out, void *stream);
 /* bn254_fr_poseidon_batch / bn254_fr_poseidon_permute_batch / bn254_fr_merkle_tree on device-resident records of 32 bytes, 16-byte aligned, asynchronous on
    `stream`: d_in (n * arity records) and d_out (n); d_in and d_out (n * t each; d_out may be exactly d_in); d_leaves (2^log_n) and d_nodes
    (2^log_n - 1).  No host operand, no scratch; none waits for anything or reads anything back. */
@@ -778,6 +811,7 @@ int bn254_profile_reset(bn254_ctx *ctx);
    of bn254_fr_dot_batch: "fr_dot" (the pieces: products and sums), "fr_dot_fold" (the levels over the partial sums);
    of bn254_fr_scan_batch: "fr_scan" (the apply level, direct segments among it), "fr_scan_reduce" (the maps of the pieces), "fr_scan_up", "fr_scan_down" (the levels over the maps);
    of bn254_fr_mle_eq, bn254_fr_mle_fold and bn254_fr_sumcheck_round: "fr_mle_eq", "fr_mle_fold", "fr_sumcheck_round" (the lanes over the indices), "fr_sumcheck_sum" (the levels over the partial sums);
+   of bn254_fr_mle_quotients: "fr_mle_quotients" (one scope per pass, or per sub-launch of it);
    of bn254_fr_poseidon_batch, bn254_fr_poseidon_permute_batch and bn254_fr_merkle_tree: "fr_poseidon", "fr_poseidon_permute", "fr_merkle_level" (one scope per level, or per sub-launch of it);
    and, of bn254_fr_ntt_batch: "ntt" (the passes), "ntt_table" (the builds of the twiddle tables).
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
