@@ -98,6 +98,7 @@ extern "C" {
     fn bn254_fr_mle_eq(ctx: *mut c_void, z: *const Fr, nv: c_int, out: *mut Fr) -> c_int;
     fn bn254_fr_mle_fold(ctx: *mut c_void, input: *const Fr, len: usize, r: *const Fr, out: *mut Fr) -> c_int;
     fn bn254_fr_sumcheck_round(ctx: *mut c_void, tables: *const Fr, n: usize, k: usize, group_offsets: *const usize, group_tables: *const u64, group_coeff: *const Fr, g: usize, degree: c_int, out: *mut Fr) -> c_int;
+    fn bn254_fr_sumcheck_fold_round(ctx: *mut c_void, tables: *const Fr, n: usize, k: usize, r: *const Fr, group_offsets: *const usize, group_tables: *const u64, group_coeff: *const Fr, g: usize, degree: c_int, folded: *mut Fr, out: *mut Fr) -> c_int;
     fn bn254_fr_mle_quotients(ctx: *mut c_void, a: *const Fr, nv: c_int, z: *const Fr, out: *mut Fr) -> c_int;
     fn bn254_fr_poseidon_batch(ctx: *mut c_void, input: *const Fr, arity: c_int, out: *mut Fr, n: usize) -> c_int;
     fn bn254_fr_poseidon_permute_batch(ctx: *mut c_void, input: *const Fr, t: c_int, out: *mut Fr, n: usize) -> c_int;
@@ -113,6 +114,7 @@ extern "C" {
     fn bn254_fr_mle_eq_dev(ctx: *mut c_void, d_z: *const c_void, nv: c_int, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn bn254_fr_mle_fold_dev(ctx: *mut c_void, d_in: *const c_void, len: usize, r: *const Fr, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn bn254_fr_sumcheck_round_dev(ctx: *mut c_void, d_tables: *const c_void, n: usize, k: usize, group_offsets: *const usize, group_tables: *const u64, group_coeff: *const Fr, g: usize, degree: c_int, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn bn254_fr_sumcheck_fold_round_dev(ctx: *mut c_void, d_tables: *const c_void, n: usize, k: usize, r: *const Fr, group_offsets: *const usize, group_tables: *const u64, group_coeff: *const Fr, g: usize, degree: c_int, d_folded: *mut c_void, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn bn254_fr_mle_quotients_dev(ctx: *mut c_void, d_a: *const c_void, nv: c_int, z: *const Fr, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn bn254_fr_poseidon_batch_dev(ctx: *mut c_void, d_in: *const c_void, arity: c_int, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_poseidon_permute_batch_dev(ctx: *mut c_void, d_in: *const c_void, t: c_int, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
@@ -423,6 +425,22 @@ pub fn fr_sumcheck_round(tables: &[Fr], k: usize, group_offsets: &[usize], group
         bn254_fr_sumcheck_round(std::ptr::null_mut(), tables.as_ptr(), tables.len() / k, k, group_offsets.as_ptr(), group_tables.as_ptr(), group_coeff.as_ptr(), g, degree as c_int, out.as_mut_ptr())
     })?;
     Ok(out)
+}
+
+/// `fr_mle_fold` of the `k` index-major tables by `r` and `fr_sumcheck_round` of the folded tables in one pass over them: `(folded, out)` with
+/// `folded[i * k + j] = T_j[i] + r * (T_j[i + n / 2] - T_j[i])` (`n / 2 * k` values, `n = tables.len() / k` a multiple of 4) and `out` the
+/// `degree + 1` values of the round polynomial over `folded` - what a sumcheck prover does between two challenges.
+pub fn fr_sumcheck_fold_round(tables: &[Fr], k: usize, r: &Fr, group_offsets: &[usize], group_tables: &[u64], group_coeff: &[Fr], degree: usize) -> Result<(Vec<Fr>, Vec<Fr>), GpuError> {
+    assert!(k >= 1 && tables.len() % (4 * k) == 0 && !group_offsets.is_empty());
+    let g = group_offsets.len() - 1;
+    assert!(group_coeff.len() == g && *group_offsets.last().unwrap() == group_tables.len());
+    let mut folded = vec![Fr::zero(); tables.len() / 2];
+    let mut out = vec![Fr::zero(); degree + 1];
+    check(unsafe {
+        bn254_fr_sumcheck_fold_round(std::ptr::null_mut(), tables.as_ptr(), tables.len() / k, k, r as *const Fr, group_offsets.as_ptr(), group_tables.as_ptr(), group_coeff.as_ptr(), g, degree as c_int,
+                                     folded.as_mut_ptr(), out.as_mut_ptr())
+    })?;
+    Ok((folded, out))
 }
 
 /// The quotients of a multilinear opening of the table `a` (`2^z.len()` values) at `z`, in heap order: `out[0] = f(z)` and `out[2^j + i] = q_j[i]`

@@ -82,6 +82,8 @@ SIGNATURES = {   # name -> argtypes  (every function returns int unless noted)
     "bn254_fr_mle_fold_dev": [_VP, _VP, _SZ, _VP, _VP, _VP],
     "bn254_fr_sumcheck_round": [_VP, _VP, _SZ, _SZ, _VP, _VP, _VP, _SZ, C.c_int, _VP],
     "bn254_fr_sumcheck_round_dev": [_VP, _VP, _SZ, _SZ, _VP, _VP, _VP, _SZ, C.c_int, _VP, _VP],
+    "bn254_fr_sumcheck_fold_round": [_VP, _VP, _SZ, _SZ, _VP, _VP, _VP, _VP, _SZ, C.c_int, _VP, _VP],
+    "bn254_fr_sumcheck_fold_round_dev": [_VP, _VP, _SZ, _SZ, _VP, _VP, _VP, _VP, _SZ, C.c_int, _VP, _VP, _VP],
     "bn254_fr_mle_quotients": [_VP, _VP, C.c_int, _VP, _VP],
     "bn254_fr_mle_quotients_dev": [_VP, _VP, C.c_int, _VP, _VP, _VP],
     "bn254_fr_poseidon_batch": [_VP, _VP, C.c_int, _VP, _SZ],

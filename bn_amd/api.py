@@ -439,6 +439,24 @@ def fr_sumcheck_round(tables, groups, degree=None, engine=None):
     return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_sumcheck_round(t, groups, degree)]
 
 
+def fr_sumcheck_fold_round(tables, r, groups, degree=None, engine=None):
+    """fr_mle_fold of every table by r, then fr_sumcheck_round of the folded tables, in ONE pass over them -> (folded, out): folded is the
+    (n / 2, k, 4) uint64 array of the tables with their most significant variable bound to r, out the list of degree + 1 Fr of the round
+    polynomial over the folded tables - what a sumcheck prover does between two challenges.  tables, groups and degree as in
+    fr_sumcheck_round; r: an Fr.  ValueError, before any device call, for what fr_sumcheck_round rejects and for an n that is no multiple of 4."""
+    from .engine import _fold_round_rows, _fr_point, _sumcheck_args
+    if not isinstance(tables, np.ndarray):
+        cols = [_scalar_array(t) for t in tables]
+        if len({c.shape[0] for c in cols}) > 1:
+            raise ValueError(f"tables differ in length: {[c.shape[0] for c in cols]}")
+        tables = np.stack(cols, axis=1) if cols else np.zeros((0, 0, 4), np.uint64)
+    t, _, _, _, degree = _sumcheck_args(tables, groups, degree)
+    _fold_round_rows(t.shape[0])
+    rr = _fr_point(r, "r")
+    folded, out = (engine or default_engine()).fr_sumcheck_fold_round(t, rr, groups, degree)
+    return folded, [Fr.from_limbs(x) for x in out]
+
+
 def fr_mle_quotients(a, z, engine=None):
     """The quotients of the multilinear table a at the point z -> list of len(a) Fr in heap order: out[0] = f(z) and out[2^j + i] = q_j[i] for
     j < nv, i < 2^j, with f(x) - f(z) = sum_j (x_j - z_j) q_j(x_0 .. x_{j-1}): from t = a, for j = nv - 1 down to 0, q_j[i] = t[i + 2^j] - t[i] and

@@ -1,7 +1,7 @@
 // Multilinear tables and sumcheck rounds over Fr on the device (include/bn254_hip.h bn254_fr_mle_eq, bn254_fr_mle_fold, bn254_fr_sumcheck_round,
-// bn254_fr_mle_quotients and their _dev twins): the kernels - instances of bn254_fr_decode_k<Op> like the other integer kernels, one lane of the
-// bodies of mle_ops.hpp each -, the levels host_plan.hpp's bn_sumcheck_plan and the passes its bn_mle_quotients_plan compute as sub-launches,
-// and the eight entry points.
+// bn254_fr_sumcheck_fold_round, bn254_fr_mle_quotients and their _dev twins): the kernels - instances of bn254_fr_decode_k<Op> like the other
+// integer kernels, one lane of the bodies of mle_ops.hpp each -, the levels host_plan.hpp's bn_sumcheck_plan and the passes its
+// bn_mle_quotients_plan compute as sub-launches, and the ten entry points.
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -37,6 +37,15 @@ struct FrSumcheckRoundOp {
         if (i < n) fr_sumcheck_round_body<D>(tables, h, k, desc, lanes, dst, lo + i);
     }
 };
+// the fused fold-then-round kernel: r by value like the fold's
+template <int D>
+struct FrSumcheckFoldRoundOp {
+    const uint32_t *tables; Fr r; uint32_t *folded; uint64_t h2; uint32_t k; BnSumcheckDesc desc; uint64_t lanes; uint32_t *dst; uint64_t lo; uint32_t n;
+    __device__ __forceinline__ void operator()() const {
+        const uint32_t i = blockIdx.x * MLE_BLOCK + threadIdx.x;
+        if (i < n) fr_sumcheck_fold_round_body<D>(tables, r, folded, h2, k, desc, lanes, dst, lo + i);
+    }
+};
 struct FrSumcheckSumOp {
     const uint32_t *src; uint64_t cnt; uint32_t F; uint32_t *dst; uint64_t lo; uint32_t n;
     __device__ __forceinline__ void operator()() const {
@@ -62,13 +71,18 @@ int mle_launch(const Op &op, size_t lanes, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
-// tests and tools/time_mle.py, tools/time_mle_open.py only: the sub-launch size (0 = BN_LAUNCH_MAX), the piece length and the levels per
-// quotient pass the sweeps time (0 = the shipped constants)
+// tests and tools/time_mle.py, tools/time_mle_open.py, tools/time_fold_round.py only: the sub-launch size (0 = BN_LAUNCH_MAX), the piece
+// lengths and the levels per quotient pass the sweeps time (0 = the shipped constants and, for the fused call, the adaptive choice)
 std::atomic<size_t> g_mle_launch_max;
-std::atomic<unsigned> g_sumcheck_piece, g_mle_quot_levels;
+std::atomic<unsigned> g_sumcheck_piece, g_sumcheck_fold_piece, g_mle_quot_levels;
 size_t mle_step() { const size_t set = g_mle_launch_max.load(std::memory_order_relaxed); return set ? set : BN_LAUNCH_MAX; }
 unsigned quot_levels() { const unsigned set = g_mle_quot_levels.load(std::memory_order_relaxed); return set ? set : FR_MLE_QUOT_LEVELS; }
 unsigned sumcheck_piece() { const unsigned set = g_sumcheck_piece.load(std::memory_order_relaxed); return set ? set : FR_SUMCHECK_PIECE; }
+// an override holds at every size; otherwise the shipped piece, halved while the lanes do not fill a device of `cus` compute units
+unsigned sumcheck_fold_piece(size_t h2, size_t cus) {
+    const unsigned set = g_sumcheck_fold_piece.load(std::memory_order_relaxed);
+    return set ? set : (unsigned)bn_sumcheck_fold_piece(h2, FR_SUMCHECK_FOLD_PIECE, bn_sumcheck_fold_fill(cus));
+}
 
 int eq_run(bn254_ctx *c, const void *d_z, int nv, void *d_out, hipStream_t s) {
     return bn_for_parts((size_t)1 << nv, mle_step(), [&](size_t lo, size_t cnt) -> int {
@@ -88,23 +102,15 @@ template <int D>
 int round_launch(const uint32_t *tables, size_t h, size_t k, const BnSumcheckDesc &desc, size_t lanes, uint32_t *dst, size_t lo, size_t cnt, hipStream_t s) {
     return mle_launch(FrSumcheckRoundOp<D>{tables, (uint64_t)h, (uint32_t)k, desc, (uint64_t)lanes, dst, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
 }
-// scratch guard held by the caller.  The round kernel, then the sum levels in the plan's order, each as sub-launches of at most mle_step()
-// lanes; the stream orders them.
-int round_run(bn254_ctx *c, const void *d_tables, size_t n, size_t k, const BnSumcheckDesc &desc, int degree, void *d_out, hipStream_t s) {
-    const size_t h = n / 2;
-    const BnSumcheckPlan plan = bn_sumcheck_plan(h, (unsigned)degree, sumcheck_piece(), FR_SUMCHECK_FAN);
+// scratch guard held by the caller.  The lanes of `plan` through launch(dst, lo, cnt) under `scope` - the round kernel or the fused one -,
+// then the sum levels in the plan's order, each as sub-launches of at most mle_step() lanes; the stream orders them.
+template <class Launch>
+int levels_run(bn254_ctx *c, const BnSumcheckPlan &plan, const char *scope, void *d_out, hipStream_t s, Launch launch) {
     int rc = c->mle_ws.reserve(plan.slots * sizeof(bn_fr)); if (rc) return rc;
     uint32_t *const ws = (uint32_t *)c->mle_ws.p, *const out = (uint32_t *)d_out;
-    const uint32_t *tables = (const uint32_t *)d_tables;
     rc = bn_for_parts(plan.lanes, mle_step(), [&](size_t lo, size_t cnt) -> int {
-        BnScope sc(c, s, "fr_sumcheck_round");
-        uint32_t *dst = plan.levels.empty() ? out : ws;
-        switch (degree) {
-        case 1: return round_launch<1>(tables, h, k, desc, plan.lanes, dst, lo, cnt, s);
-        case 2: return round_launch<2>(tables, h, k, desc, plan.lanes, dst, lo, cnt, s);
-        case 3: return round_launch<3>(tables, h, k, desc, plan.lanes, dst, lo, cnt, s);
-        default: return round_launch<4>(tables, h, k, desc, plan.lanes, dst, lo, cnt, s);
-        }
+        BnScope sc(c, s, scope);
+        return launch(plan.levels.empty() ? out : ws, lo, cnt);
     });
     if (rc) return rc;
     for (const BnSumcheckLevel &lv : plan.levels) {
@@ -115,6 +121,41 @@ int round_run(bn254_ctx *c, const void *d_tables, size_t n, size_t k, const BnSu
         if (rc) return rc;
     }
     return BN254_OK;
+}
+int round_run(bn254_ctx *c, const void *d_tables, size_t n, size_t k, const BnSumcheckDesc &desc, int degree, void *d_out, hipStream_t s) {
+    const size_t h = n / 2;
+    const BnSumcheckPlan plan = bn_sumcheck_plan(h, (unsigned)degree, sumcheck_piece(), FR_SUMCHECK_FAN);
+    const uint32_t *tables = (const uint32_t *)d_tables;
+    return levels_run(c, plan, "fr_sumcheck_round", d_out, s, [&](uint32_t *dst, size_t lo, size_t cnt) -> int {
+        switch (degree) {
+        case 1: return round_launch<1>(tables, h, k, desc, plan.lanes, dst, lo, cnt, s);
+        case 2: return round_launch<2>(tables, h, k, desc, plan.lanes, dst, lo, cnt, s);
+        case 3: return round_launch<3>(tables, h, k, desc, plan.lanes, dst, lo, cnt, s);
+        default: return round_launch<4>(tables, h, k, desc, plan.lanes, dst, lo, cnt, s);
+        }
+    });
+}
+template <int D>
+int fold_round_launch(const uint32_t *tables, const Fr &r, uint32_t *folded, size_t h2, size_t k, const BnSumcheckDesc &desc, size_t lanes, uint32_t *dst, size_t lo, size_t cnt,
+                      hipStream_t s) {
+    return mle_launch(FrSumcheckFoldRoundOp<D>{tables, r, folded, (uint64_t)h2, (uint32_t)k, desc, (uint64_t)lanes, dst, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
+}
+// scratch guard held by the caller.  The fused kernel over the n / 4 indices of the round that follows the fold, then the round's own sum levels.
+int fold_round_run(bn254_ctx *c, const void *d_tables, size_t n, size_t k, const bn_fr *r, const BnSumcheckDesc &desc, int degree, void *d_folded, void *d_out, hipStream_t s) {
+    const size_t h2 = n / 4;
+    const BnSumcheckPlan plan = bn_sumcheck_plan(h2, (unsigned)degree, sumcheck_fold_piece(h2, (size_t)c->cus), FR_SUMCHECK_FAN);
+    const uint32_t *tables = (const uint32_t *)d_tables;
+    uint32_t *folded = (uint32_t *)d_folded;
+    Fr rr;
+    memcpy(rr.w, r->l, sizeof rr.w);
+    return levels_run(c, plan, FR_SUMCHECK_FOLD_ROUND_SCOPE, d_out, s, [&](uint32_t *dst, size_t lo, size_t cnt) -> int {
+        switch (degree) {
+        case 1: return fold_round_launch<1>(tables, rr, folded, h2, k, desc, plan.lanes, dst, lo, cnt, s);
+        case 2: return fold_round_launch<2>(tables, rr, folded, h2, k, desc, plan.lanes, dst, lo, cnt, s);
+        case 3: return fold_round_launch<3>(tables, rr, folded, h2, k, desc, plan.lanes, dst, lo, cnt, s);
+        default: return fold_round_launch<4>(tables, rr, folded, h2, k, desc, plan.lanes, dst, lo, cnt, s);
+        }
+    });
 }
 template <int RHO>
 int quot_launch(const uint32_t *src, const bn_fr *z, unsigned m, uint32_t *fold_dst, uint32_t *out, size_t lo, size_t cnt, hipStream_t s) {
@@ -195,6 +236,26 @@ int bn254_fr_sumcheck_round(bn254_ctx *ctx, const bn_fr *tables, size_t n, size_
         return bn254_fr_sumcheck_round_dev(ctx, d.in[0], n, k, group_offsets, group_tables, group_coeff, g, degree, d.out, ctx->stream);
     });
 }
+// r and the groups are HOST memory in both forms.  d_folded may be exactly d_tables: the kernel runs in place, the upper half is left as it was
+int bn254_fr_sumcheck_fold_round_dev(bn254_ctx *ctx, const void *d_tables, size_t n, size_t k, const bn_fr *r, const size_t *group_offsets, const uint64_t *group_tables,
+                                     const bn_fr *group_coeff, size_t g, int degree, void *d_folded, void *d_out, void *stream) {
+    BnSumcheckDesc desc;
+    int rc = bn_sumcheck_fold_check(d_tables, n, k, r, group_offsets, group_tables, group_coeff, g, degree, d_folded, d_out, &desc); if (rc) return rc;      // before any device lookup
+    if ((rc = bn_get_ctx(ctx))) return rc;
+    BnDev d(ctx, stream); if (!d.go) return d.rc;
+    BnScratchGuard guard(ctx, d.s); if (guard.rc) return guard.rc;
+    return bn_no_throw([&] { return fold_round_run(ctx, d_tables, n, k, r, desc, degree, d_folded, d_out, d.s); });
+}
+// the staged copy is folded out of place on the device; with folded == tables only the lower half of the caller's array is written back
+int bn254_fr_sumcheck_fold_round(bn254_ctx *ctx, const bn_fr *tables, size_t n, size_t k, const bn_fr *r, const size_t *group_offsets, const uint64_t *group_tables,
+                                 const bn_fr *group_coeff, size_t g, int degree, bn_fr *folded, bn_fr *out) {
+    BnSumcheckDesc desc;
+    int rc = bn_sumcheck_fold_check(tables, n, k, r, group_offsets, group_tables, group_coeff, g, degree, folded, out, &desc); if (rc) return rc;            // before any device lookup
+    BnHost h(ctx); if (h.rc) return h.rc;
+    return bn_staged(ctx, {tables, n * k * sizeof(bn_fr)}, {nullptr, 0}, folded, n / 2 * k * sizeof(bn_fr), out, (size_t)(degree + 1) * sizeof(bn_fr), [&](const BnStaged &d) {
+        return bn254_fr_sumcheck_fold_round_dev(ctx, d.in[0], n, k, r, group_offsets, group_tables, group_coeff, g, degree, d.out, d.out2, ctx->stream);
+    });
+}
 // z is HOST memory in both forms: its records travel as kernel arguments.  out must not overlap a.
 int bn254_fr_mle_quotients_dev(bn254_ctx *ctx, const void *d_a, int nv, const bn_fr *z, void *d_out, void *stream) {
     int rc = bn_mle_quotients_check(d_a, nv, z, d_out); if (rc) return rc;
@@ -233,5 +294,14 @@ int bn254_fr_sumcheck_set_piece(unsigned P) {
     g_sumcheck_piece.store(P, std::memory_order_relaxed);
     return BN254_OK;
 }
+// the shipped piece length of the fused fold-then-round kernel, a process-wide override of it for the sweep of tools/time_fold_round.py and
+// the tests (0 restores the adaptive choice; same bytes whatever is set), and the piece a call over h2 indices runs with on `cus` compute units
+unsigned bn254_fr_sumcheck_fold_piece(void) { return FR_SUMCHECK_FOLD_PIECE; }
+int bn254_fr_sumcheck_fold_set_piece(unsigned P) {
+    if (P > 64) return BN254_E_BAD_ARG;
+    g_sumcheck_fold_piece.store(P, std::memory_order_relaxed);
+    return BN254_OK;
+}
+unsigned bn254_fr_sumcheck_fold_piece_for(size_t h2, size_t cus) { return sumcheck_fold_piece(h2, cus); }
 
 }  // extern "C"

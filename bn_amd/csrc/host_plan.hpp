@@ -1,5 +1,5 @@
 // Host arithmetic over sizes and offsets: the argument checks that need no device, the work lists of the segmented folds, the cutting of a
-// prepared batch into Miller pieces, the workspace of the bucket method and its tail scalars, the scalars of the fixed-base tables, the passes of a transform, the pieces of a sparse linear map, the levels of a segmented scan and of a sumcheck round, the passes of the quotients of a multilinear opening.  Plain C++17: nothing here touches a device, so
+// prepared batch into Miller pieces, the workspace of the bucket method and its tail scalars, the scalars of the fixed-base tables, the passes of a transform, the pieces of a sparse linear map, the levels of a segmented scan and of a sumcheck round, the check and piece length of the fused fold-then-round call, the passes of the quotients of a multilinear opening.  Plain C++17: nothing here touches a device, so
 // tests/hostsim/ compiles it with g++ and tests/test_host_plan.py replays the plans on the CPU.  (io.hpp: the two records the kernels read.)
 #pragma once
 #include <algorithm>
@@ -537,6 +537,33 @@ inline BnSumcheckPlan bn_sumcheck_plan(size_t h, unsigned degree, size_t P, size
         src = plan.slots; plan.slots += T * cnt2; cnt = cnt2;
     }
     return plan;
+}
+
+// ---- the fused fold-then-round call (bn254_fr_sumcheck_fold_round): the argument check and the indices per lane
+inline bool bn_ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb ? pb - pa < a_bytes : pa - pb < b_bytes;
+}
+// n = 4 h2 rows of k tables are folded to n / 2 rows, and the round runs over those: everything bn_sumcheck_check rejects for
+// (n / 2, k, groups, degree), a whole number of row quadruples, one challenge, n k within the limit.  `folded` (n / 2 * k records) may be
+// exactly `tables` (n k records) and must not overlap it otherwise; `out` (degree + 1 records) must overlap neither.
+inline int bn_sumcheck_fold_check(const void *tables, size_t n, size_t k, const void *r, const size_t *offsets, const uint64_t *group_tables, const bn_fr *coeff, size_t g, int degree,
+                                  const void *folded, const void *out, bn254::BnSumcheckDesc *desc) {
+    if (n < 4 || (n & 3) || !r || !folded) return BN254_E_BAD_ARG;
+    const int rc = bn_sumcheck_check(tables, n / 2, k, offsets, group_tables, coeff, g, degree, out, desc); if (rc) return rc;
+    if (n > BN_N_MAX / k) return BN254_E_BAD_ARG;
+    const size_t table_bytes = n * k * sizeof(bn_fr), out_bytes = (size_t)(degree + 1) * sizeof(bn_fr);
+    if (folded != tables && bn_ranges_overlap(tables, table_bytes, folded, table_bytes / 2)) return BN254_E_BAD_ARG;
+    if (bn_ranges_overlap(tables, table_bytes, out, out_bytes) || bn_ranges_overlap(folded, table_bytes / 2, out, out_bytes)) return BN254_E_BAD_ARG;
+    return BN254_OK;
+}
+// Indices per lane of the fused kernel over h2 indices: the shipped P, halved down to 4 while its ceil(h2 / P) lanes are fewer than `fill` -
+// the lanes that occupy every SIMD with the two waves these kernels hold from degree 2 on, cus * 4 SIMDs * 64 lanes * 2.  A prover walks
+// through every size, and below `fill` lanes a long piece only leaves compute units idle.  The bytes do not depend on P.
+inline size_t bn_sumcheck_fold_fill(size_t cus) { return cus * 4 * 64 * 2; }
+inline size_t bn_sumcheck_fold_piece(size_t h2, size_t P, size_t fill) {
+    while (P > 4 && (h2 + P - 1) / P < fill) P /= 2;
+    return P;
 }
 
 // ---- the quotients of a multilinear opening (bn254_fr_mle_quotients): the argument check and the passes

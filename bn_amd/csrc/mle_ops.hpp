@@ -1,11 +1,14 @@
 // The per-lane bodies of the multilinear kernels over Fr (bn254_mle.hip): bn254_fr_mle_eq, bn254_fr_mle_fold, bn254_fr_sumcheck_round,
-// bn254_fr_mle_quotients and their _dev twins.  A multilinear table of nv variables is 2^nv records; the record at index i is the value at the point whose variable j is
-// bit j of i.  Several tables of one sumcheck are stored index-major: tables[i * k + j] is table j at index i.
+// bn254_fr_sumcheck_fold_round, bn254_fr_mle_quotients and their _dev twins.  A multilinear table of nv variables is 2^nv records; the record
+// at index i is the value at the point whose variable j is bit j of i.  Several tables of one sumcheck are stored index-major: tables[i * k + j] is table j at index i.
 //   eq      out[i] = prod_{j < nv} (bit j of i ? z[j] : 1 - z[j]): one lane per element, nv products, whatever the data
 //   fold    out[i] = in[i] + r * (in[i + half] - in[i]): binds the MOST significant variable; lane i alone touches records i and i + half
 //   round   for t = 0 .. D:  sum over i < h, over the groups c, of coeff[c] * prod_{j in group c} (T_j[i] + t (T_j[i + h] - T_j[i])).
 //           There are `lanes` = ceil(h / P) lanes and lane l sums the at most P indices l, l + lanes, l + 2 lanes, .. below h, so that the lanes of
 //           a wave read neighbouring rows; its D + 1 sums go to part[t * lanes + l] - or, with one lane, straight to out[t]
+//   fold_round  the fold of n = 4 h2 rows by r and the round over the 2 h2 folded rows in one pass: the round's lanes over h2 indices; for
+//           index i a lane folds rows (i, i + 2 h2) and (i + h2, i + 3 h2) of all k tables into rows i and i + h2 of the folded array, then
+//           sums the groups over these two rows.  The folded array may be the tables: rows i and i + h2 belong to that lane alone
 //   sum     levels of fan F over the partial sums (additions only), laid out [t][piece] before and after; the last level writes out[t]
 //   quotients  the nv tables q_j of an opening at z, f(x) - f(z) = sum_j (x_j - z_j) q_j(x_0 .. x_{j-1}): from t = a, for j = nv - 1 down to 0 with
 //           half = 2^j, q_j[i] = t[i + half] - t[i] and t[i] += z[j] q_j[i] - the fold by z[j], whose difference is kept.  One launch does RHO of
@@ -13,7 +16,7 @@
 // so the length of a lane's serial chain is a constant of the plan, never a property of the data, and no lane waits for another: the order
 // between the levels is the order of the launches on their stream.  Every product and every sum is canonical (fr.hpp), hence the bytes are
 // those of the Python-integer sums however the indices are dealt out.  Everything is pure and takes plain pointers and a lane index, so the
-// host simulation (tests/hostsim/hostsim_mle.cpp, hostsim_mle_open.cpp) runs the very same bodies over host arrays.
+// host simulation (tests/hostsim/hostsim_mle.cpp, hostsim_mle_open.cpp, hostsim_fold_round.cpp) runs the very same bodies over host arrays.
 #pragma once
 #include "fr_ops.hpp"
 #include "io.hpp"
@@ -35,6 +38,13 @@ constexpr uint32_t FR_MLE_QUOT_LEVELS = 2;
 constexpr uint32_t FR_MLE_QUOT_LEVELS_MAX = 4;
 // the profile scope of the quotient passes (a constant here: bn254_mle.hip names its scopes through it)
 constexpr char FR_MLE_QUOT_SCOPE[] = "fr_mle_quotients";
+// Indices per lane of the fused fold-then-round kernel (bn254_fr_sumcheck_fold_round; bn254_mle.hip carries a run-time override for the sweep
+// of tools/time_fold_round.py and the tests).  The rule fixed before measuring is the round's: the fastest of 4 / 8 / 16 on four tables of
+// 2^22 entries at degree 3 ships; that is 8 (0.605 / 0.595 / 0.671 ms, profiles/r20_fold_round.txt).  Below that size host_plan.hpp's
+// bn_sumcheck_fold_piece halves it while the lanes do not fill the machine: 0.175 against 0.312 ms on four tables of 2^16, and at no swept size
+// slower than the fixed 8, so the adaptive choice ships.
+constexpr uint32_t FR_SUMCHECK_FOLD_PIECE = 8;
+constexpr char FR_SUMCHECK_FOLD_ROUND_SCOPE[] = "fr_sumcheck_fold_round";
 
 BN_FN void fr_mle_eq_body(const uint32_t *z, uint32_t nv, uint32_t *out, size_t i) {
     const Fr one = fr_one();
@@ -82,17 +92,22 @@ BN_FN void fr_mle_quotients_body(const uint32_t *src, const Fr *zz, uint32_t m, 
     fr_store(v[0], fold_dst, i);
 }
 
-// Lane `lane` of the round kernel.  The factors of a group are walked one at a time: v = lo, d = hi - lo, and per t (unrolled: acc and prod
-// have compile-time indices and stay in registers) prod[t] *= v, v += d - the values at t = 0, 1, 2, .. cost additions only.  The
-// coefficient goes into the first factor's v and d: two products per group and index, not D + 1.  dst: part, or out when lanes == 1.
-template <int D>
-BN_FN void fr_sumcheck_round_body(const uint32_t *tables, uint64_t h, uint32_t k, const BnSumcheckDesc &desc, uint64_t lanes, uint32_t *dst, uint64_t lane) {
+// Lane `lane` of a round over h indices of `tables` - the round kernel's and, with a fold in front of every index, the fused kernel's.
+// pre(row_lo, row_hi) runs once per index before its rows are read: nothing for the round, the fold of the two rows for the fused call - the
+// one function both bodies call, so the group walk exists once.  The factors of a group are walked one at a time: v = lo, d = hi - lo, and
+// per t (unrolled: acc and prod have compile-time indices and stay in registers) prod[t] *= v, v += d - the values at t = 0, 1, 2, .. cost
+// additions only.  The coefficient goes into the first factor's v and d: two products per group and index, not D + 1.  dst: part, or out
+// when lanes == 1.
+template <int D, class Pre>
+BN_FN void fr_sumcheck_lane(const uint32_t *tables, uint64_t h, uint32_t k, const BnSumcheckDesc &desc, uint64_t lanes, uint32_t *dst, uint64_t lane,
+                            const Pre &pre) {
     Fr acc[D + 1];
 #pragma unroll
     for (int t = 0; t <= D; ++t) acc[t] = fr_zero();
 #pragma unroll 1
     for (uint64_t i = lane; i < h; i += lanes) {
         const uint64_t row_lo = i * k, row_hi = (i + h) * k;
+        pre(row_lo, row_hi);
 #pragma unroll 1
         for (uint32_t c = 0; c < desc.groups; ++c) {
             Fr prod[D + 1];
@@ -125,6 +140,28 @@ BN_FN void fr_sumcheck_round_body(const uint32_t *tables, uint64_t h, uint32_t k
     }
 #pragma unroll
     for (int t = 0; t <= D; ++t) fr_store(acc[t], dst, t * lanes + lane);     // one lane: record t of out
+}
+template <int D>
+BN_FN void fr_sumcheck_round_body(const uint32_t *tables, uint64_t h, uint32_t k, const BnSumcheckDesc &desc, uint64_t lanes, uint32_t *dst, uint64_t lane) {
+    fr_sumcheck_lane<D>(tables, h, k, desc, lanes, dst, lane, [](uint64_t, uint64_t) {});
+}
+// Lane `lane` of the fused fold-then-round kernel over n = 4 h2 rows of k tables: the round's mapping over the h2 indices of the round that
+// follows the fold.  For index i the lane first folds rows (i, i + 2 h2) and (i + h2, i + 3 h2) of every one of the k tables by r - two
+// products per table, the fold's own - into rows i and i + h2 of `folded`, then walks the groups over those two rows: it reads back what it
+// has just written itself, which program order makes visible.  No other lane reads or writes rows i and i + h2 of either array and rows
+// >= 2 h2 are only read, so `folded` may be `tables` and no lane waits for another.  dst: part, or out when lanes == 1.
+template <int D>
+BN_FN void fr_sumcheck_fold_round_body(const uint32_t *tables, const Fr &r, uint32_t *folded, uint64_t h2, uint32_t k, const BnSumcheckDesc &desc, uint64_t lanes, uint32_t *dst,
+                                       uint64_t lane) {
+    const uint64_t up = 2 * h2 * k;
+    fr_sumcheck_lane<D>(folded, h2, k, desc, lanes, dst, lane, [&](uint64_t row_lo, uint64_t row_hi) {
+#pragma unroll 1
+        for (uint32_t j = 0; j < k; ++j) {
+            const Fr a0 = fr_load(tables, row_lo + j), a1 = fr_load(tables, row_hi + j), a2 = fr_load(tables, row_lo + up + j), a3 = fr_load(tables, row_hi + up + j);
+            fr_store(fr_add(a0, fr_mul(fr_sub(a2, a0), r)), folded, row_lo + j);
+            fr_store(fr_add(a1, fr_mul(fr_sub(a3, a1), r)), folded, row_hi + j);
+        }
+    });
 }
 // Lane `lane` of a sum level over `cnt` partial sums per t: with cnt2 = ceil(cnt / F), lane = t * cnt2 + i adds src[t * cnt + i F ..] (at most
 // F of them) into dst[t * cnt2 + i]; the last level has cnt2 == 1 and its dst is out.  src and dst are different ranges of the scratch.

@@ -199,6 +199,12 @@ def _sumcheck_args(tables, groups, degree):
     return t, off, np.array([j for m in members for j in m], np.uint64), coeff, degree
 
 
+def _fold_round_rows(n):
+    """the fused fold-then-round call folds n rows to n / 2 and the round pairs those: whole quadruples of rows"""
+    if n < 4 or n % 4:
+        raise ValueError(f"tables hold {n} indices: a fold and a round need a multiple of 4")
+
+
 def _segment_args(p, q, offsets):
     p = _arr(p, G1_WORDS) if len(p) else np.zeros((0, G1_WORDS), np.uint64)
     q = _arr(q, G2_WORDS) if len(q) else np.zeros((0, G2_WORDS), np.uint64)
@@ -480,6 +486,19 @@ class Engine:
         out = np.empty((degree + 1, 4), np.uint64)
         _native.check(self._lib.bn254_fr_sumcheck_round(self._h, _p(t), t.shape[0], t.shape[1], _p(off), _p(members), _p(coeff), off.size - 1, degree, _p(out)))
         return out
+
+    def fr_sumcheck_fold_round(self, tables, r, groups, degree=None):
+        """fr_mle_fold of the (n, k, 4) tables by r and fr_sumcheck_round of the folded tables in ONE pass -> (folded, out): folded is (n/2, k, 4),
+        folded[i] = tables[i] + r * (tables[i + n/2] - tables[i]); out is (degree + 1, 4), the round polynomial of the folded tables - the bytes of
+        the two calls.  n must be a multiple of 4; every table is folded, also one no group names
+        (include/bn254_hip.h bn254_fr_sumcheck_fold_round)"""
+        t, off, members, coeff, degree = _sumcheck_args(tables, groups, degree)
+        _fold_round_rows(t.shape[0])
+        r = _fr_point(r, "r")
+        folded = np.empty((t.shape[0] // 2,) + t.shape[1:], np.uint64)
+        out = np.empty((degree + 1, 4), np.uint64)
+        _native.check(self._lib.bn254_fr_sumcheck_fold_round(self._h, _p(t), t.shape[0], t.shape[1], _p(r), _p(off), _p(members), _p(coeff), off.size - 1, degree, _p(folded), _p(out)))
+        return folded, out
 
     def fr_mle_quotients(self, a, z):
         """the quotients of the multilinear table a (2^nv records) at the point z (nv records) -> (2^nv, 4) uint64 in heap order: out[0] = f(z) and
@@ -814,6 +833,21 @@ class Engine:
         off = np.concatenate([[0], np.cumsum([len(m) for m in members])]).astype(np.uint64)
         flat = np.array([j for m in members for j in m] or [0], np.uint64)
         _native.check(self._lib.bn254_fr_sumcheck_round_dev(self._h, d_tables, n, k, _p(off), _p(flat), _p(coeff), len(members), degree, d_out, stream))
+        return degree
+
+    def fr_sumcheck_fold_round_dev(self, d_tables, n, k, r, groups, d_folded, d_out, degree=None, stream=0):
+        """device pointers tables (n * k records of 32 bytes, table j at index i in record i * k + j; n a multiple of 4), folded (n / 2 * k records;
+        may be d_tables: the call then runs in place and rows [n/2, n) are left as they were) and out (degree + 1 records), ordered on `stream`;
+        `r` (an Fr or 4 uint64 words) and `groups`, a list of (coeff, [table numbers]), are HOST values, read before the call returns.  Returns
+        the degree it ran with"""
+        members = [[int(j) for j in g[1]] for g in groups]
+        if degree is None:
+            degree = max((len(m) for m in members), default=0)
+        r = _fr_point(r, "r")                                      # held here until the call has returned
+        coeff = np.stack([_fr_point(g[0], f"the coefficient of groups[{c}]") for c, g in enumerate(groups)]) if members else np.zeros((0, 4), np.uint64)
+        off = np.concatenate([[0], np.cumsum([len(m) for m in members])]).astype(np.uint64)
+        flat = np.array([j for m in members for j in m] or [0], np.uint64)
+        _native.check(self._lib.bn254_fr_sumcheck_fold_round_dev(self._h, d_tables, n, k, _p(r), _p(off), _p(flat), _p(coeff), len(members), degree, d_folded, d_out, stream))
         return degree
 
     def fr_mle_quotients_dev(self, d_a, z, d_out, stream=0):

@@ -10,9 +10,19 @@ Against commitments that check is bn_amd.mkzg: the prover opens every committed 
 finals[j] with mkzg.verify against the commitment of table j.
 
 prove uses the host-buffer calls, as kzg and groth16 do: the tables go up once per round for the round polynomial and once for the fold,
-halving every round - about four times their bytes in total over a proof, twice per call kind.  A resident prover is the two _dev calls
-(Engine.fr_sumcheck_round_dev, Engine.fr_mle_fold_dev in place) on ONE device buffer.  Not built: a fused fold-then-round call, which would
-read the tables once per round instead of twice, and a factored eq table (low bits times high bits, as the transform's twiddles)."""
+halving every round - about four times their bytes in total over a proof, twice per call kind.  prove_resident is the resident prover, on
+ONE device buffer: the tables go up once, round 0 is Engine.fr_sumcheck_round_dev, every later round ONE Engine.fr_sumcheck_fold_round_dev in place
+- the fused fold-then-round call, which folds by the challenge just drawn and sums the next round polynomial in one pass over the tables -
+and one Engine.fr_mle_fold_dev leaves the finals; per round only degree + 1 records come down.  Same proof, byte for byte.
+Measured at nv = 20 over four tables at degree 3 (tools/time_fold_round.py, profiles/r20_fold_round.txt; medians of 5): prove_resident takes
+3.49 ms of kernel time and 7.3 ms of wall time, the same loop with the two _dev calls per round 7.00 and 10.5 ms, prove 7.12 and 146 ms.  The
+rule fixed before measuring - the fused call ships if the [min, max] of its whole-proof kernel time lies wholly below the two-call loop's -
+came out for the fused call (2.01 x).  The gain is in the small rounds, where the fused call takes 4 indices per lane instead of the round's
+fixed 16 and is one launch fewer (2.0 to 2.2 x from 2^16 to 2^20 entries); on tables of 2^22 entries it is 0.92 x the two calls: it runs at
+1.31 x the plain batched product on its products, so there the tables' second trip was never the cost.
+Not built: folding inside the factor walk of the fused fold-then-round call (the folded records would not come back through the cache, for
+two more products per factor occurrence), a factored eq table (low bits times high bits, as the transform's twiddles), a device-side
+transcript."""
 import collections
 import hashlib
 
@@ -89,6 +99,68 @@ def prove(tables, groups, transcript=None, engine=None):
         T = e.fr_mle_fold(T, r.limbs)
         rounds.append(g); challenges.append(r)
     return Proof(claim, rounds, [Fr.from_limbs(x) for x in T[0]]), challenges[::-1]
+
+
+# What prove_resident runs between two challenges: the fused bn254_fr_sumcheck_fold_round_dev, or bn254_fr_mle_fold_dev in place followed by
+# bn254_fr_sumcheck_round_dev.  The rule was fixed before measuring (tools/time_fold_round.py, profiles/r20_fold_round.txt): the fused call if
+# the [min, max] of its whole-proof kernel time at nv = 20 lies wholly below that of the two-call loop.  It does: 3.49 ms [3.43 3.57]
+# against 7.00 ms [6.86 7.05].
+FUSED = True
+
+
+def prove_resident(tables, groups, transcript=None, engine=None):
+    """prove on ONE device buffer: the same arguments, the same (Proof, point), byte for byte, for the same transcript.  The (n, k) array goes up
+    once, into a torch tensor on the engine's device that also holds the degree + 1 records of a round; round 0 is fr_sumcheck_round_dev,
+    rounds 1 .. nv - 1 are fr_sumcheck_fold_round_dev in place (the fold by the challenge just drawn and the next round polynomial in one pass
+    - or, with FUSED off, fr_mle_fold_dev in place and fr_sumcheck_round_dev), and one fr_mle_fold_dev leaves the finals.  Per round only the
+    degree + 1 records the transcript absorbs come down."""
+    return _prove_resident(tables, groups, transcript, engine, FUSED)
+
+
+def _prove_resident(tables, groups, transcript, engine, fused):
+    import torch
+    if not isinstance(tables, np.ndarray):
+        tables = np.stack([_scalar_array(t) for t in tables], axis=1)
+    gs, degree = _groups(groups)
+    limb_groups = [(c.limbs, m) for c, m in gs]
+    T, _, _, _, degree = _sumcheck_args(tables, limb_groups, degree)
+    n, k = T.shape[0], T.shape[1]
+    nv = n.bit_length() - 1
+    if n != 1 << nv:
+        raise ValueError(f"tables hold {n} indices: a power of two is needed")
+    e = engine or default_engine()
+    tr = transcript or Transcript("bn_amd.sumcheck")
+    dev = torch.device("cuda", e.device)
+    buf = torch.empty((n * k + degree + 1) * 4, dtype=torch.int64, device=dev)          # the tables, then the records of a round
+    buf[:n * k * 4].copy_(torch.from_numpy(T.reshape(-1).view(np.int64)))
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    d_tables, d_out = buf.data_ptr(), buf.data_ptr() + 32 * n * k
+
+    def down(first, count):
+        """records [first, first + count) of the buffer as Fr; the copy is ordered on the stream and waits for it"""
+        words = buf[first * 4:(first + count) * 4].cpu().numpy().view(np.uint64).reshape(count, 4)
+        return [Fr.from_limbs(x) for x in words]
+
+    e.fr_sumcheck_round_dev(d_tables, n, k, limb_groups, d_out, degree, stream)
+    g = down(n * k, degree + 1)
+    claim = g[0] + g[1]
+    _absorb_statement(tr, nv, k, degree, gs, claim)
+    rounds, challenges = [], []
+    for s in range(nv):
+        tr.absorb(g)
+        r = tr.challenge()
+        rounds.append(g); challenges.append(r)
+        rows = n >> s                                                                    # before the fold by r
+        if s == nv - 1:
+            e.fr_mle_fold_dev(d_tables, rows * k, r.limbs, d_tables, stream)
+        elif fused:
+            e.fr_sumcheck_fold_round_dev(d_tables, rows, k, r.limbs, limb_groups, d_tables, d_out, degree, stream)
+        else:
+            e.fr_mle_fold_dev(d_tables, rows * k, r.limbs, d_tables, stream)
+            e.fr_sumcheck_round_dev(d_tables, rows // 2, k, limb_groups, d_out, degree, stream)
+        if s < nv - 1:
+            g = down(n * k, degree + 1)
+    return Proof(claim, rounds, down(0, k)), challenges[::-1]
 
 
 def _at(values, r):

@@ -254,6 +254,20 @@ inline std::vector<Fr> fr_sumcheck_round(const std::vector<Fr> &tables, size_t k
                                   reinterpret_cast<const bn_fr *>(group_coeff.data()), group_coeff.size(), degree, reinterpret_cast<bn_fr *>(out.data())));
     return out;
 }
+// fr_mle_fold of the k index-major tables by r and fr_sumcheck_round of the folded tables in one pass: {folded, out} with
+// folded[i * k + j] = T_j[i] + r * (T_j[i + n / 2] - T_j[i]) (n = tables.size() / k, a multiple of 4) and out the degree + 1 values of the round
+// polynomial over folded - what a sumcheck prover does between two challenges
+inline std::pair<std::vector<Fr>, std::vector<Fr>> fr_sumcheck_fold_round(const std::vector<Fr> &tables, size_t k, const Fr &r, const std::vector<size_t> &group_offsets,
+                                                                          const std::vector<uint64_t> &group_tables, const std::vector<Fr> &group_coeff, int degree) {
+    if (k == 0 || tables.empty() || tables.size() % (4 * k) || group_offsets.empty() || group_coeff.size() != group_offsets.size() - 1 || group_offsets.back() != group_tables.size() ||
+        degree < 1)
+        throw std::invalid_argument("fr_sumcheck_fold_round: tables, k and the groups disagree");
+    std::vector<Fr> folded(tables.size() / 2), out(size_t(degree) + 1);
+    check(bn254_fr_sumcheck_fold_round(nullptr, reinterpret_cast<const bn_fr *>(tables.data()), tables.size() / k, k, reinterpret_cast<const bn_fr *>(&r), group_offsets.data(),
+                                       group_tables.data(), reinterpret_cast<const bn_fr *>(group_coeff.data()), group_coeff.size(), degree, reinterpret_cast<bn_fr *>(folded.data()),
+                                       reinterpret_cast<bn_fr *>(out.data())));
+    return {std::move(folded), std::move(out)};
+}
 // the quotients of a multilinear opening of the table a (2^z.size() values) at z, in heap order: out[0] = f(z) and out[2^j + i] = q_j[i] with
 // f(x) - f(z) = sum_j (x_j - z_j) q_j(x_0 .. x_{j-1}); the field work of a multilinear KZG opening
 inline std::vector<Fr> fr_mle_quotients(const std::vector<Fr> &a, const std::vector<Fr> &z) {

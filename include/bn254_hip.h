@@ -50,6 +50,9 @@
  *                          bn254_fr_mle_fold  out[i] = in[i] + r * (in[i + len/2] - in[i]): binds the most significant variable of a multilinear table;
  *                          bn254_fr_sumcheck_round  the round polynomial of a sum of products of tables at t = 0 .. degree; none has a counterpart in the reference
  *   bn254_fr_mle_eq_dev / bn254_fr_mle_fold_dev / bn254_fr_sumcheck_round_dev  the same three on device-resident tables, asynchronous on the caller's stream
+ *   bn254_fr_sumcheck_fold_round  bn254_fr_mle_fold of all the tables of a sumcheck by r and bn254_fr_sumcheck_round of the folded tables in one pass: the step
+ *                          of a prover between two challenges; no counterpart in the reference
+ *   bn254_fr_sumcheck_fold_round_dev  the same on device-resident tables, in place if asked, asynchronous on the caller's stream
  *   bn254_fr_mle_quotients  out[0] = f(z) and out[2^j + i] = q_j[i], the nv quotient tables of f(x) - f(z) = sum_j (x_j - z_j) q_j(x_0 .. x_{j-1}) for the multilinear
  *                          table f: the field work of a multilinear KZG (PST) opening; no counterpart in the reference
  *   bn254_fr_mle_quotients_dev  the same on a device-resident table, asynchronous on the caller's stream
@@ -97,6 +100,7 @@
      bn254_fr_dot_batch serialises on the context in the same way (its mutex for the whole call).
      bn254_fr_scan_batch serialises on the context in the same way (its mutex for the whole call).
      bn254_fr_mle_eq, bn254_fr_mle_fold and bn254_fr_sumcheck_round serialise on the context in the same way (its mutex for the whole call).
+     bn254_fr_sumcheck_fold_round serialises on the context in the same way (its mutex for the whole call).
      bn254_fr_mle_quotients serialises on the context in the same way (its mutex for the whole call).
      bn254_fr_poseidon_batch, bn254_fr_poseidon_permute_batch and bn254_fr_merkle_tree serialise on the context in the same way (its mutex for the whole call).
  *     bn254_pairing_product_batch_prepared_native serialises on the context like them; its handle is immutable and shared freely.
@@ -133,6 +137,9 @@
      group description before they return (both travel as kernel arguments: nothing is uploaded).  The partial sums of
      bn254_fr_sumcheck_round_dev are context-owned scratch under the same event ordering.  None of the three waits on anything or reads
      anything back.
+     bn254_fr_sumcheck_fold_round_dev reads its HOST `r` and group description before it returns (kernel arguments again); its partial sums are
+     the scratch of bn254_fr_sumcheck_round_dev under the same event ordering, so the two serialise on it across streams.  It waits on
+     nothing and reads nothing back.
      bn254_fr_mle_quotients_dev reads its HOST `z` before it returns (the challenges of a pass travel as kernel arguments: nothing is
      uploaded).  The working table between its passes is context-owned scratch under the same event ordering - the buffer the partial sums
      of bn254_fr_sumcheck_round_dev use, so the two serialise on it across streams.  It waits on nothing and reads nothing back.
@@ -559,6 +566,36 @@ int bn254_fr_mle_eq(bn254_ctx *ctx, const bn_fr *z, int nv, bn_fr *out);
 int bn254_fr_mle_fold(bn254_ctx *ctx, const bn_fr *in, size_t len, const bn_fr *r, bn_fr *out);
 int bn254_fr_sumcheck_round(bn254_ctx *ctx, const bn_fr *tables, size_t n, size_t k, const size_t *group_offsets, const uint64_t *group_tables, const bn_fr *group_coeff, size_t g,
                             int degree, bn_fr *out);
+/* The fold of one sumcheck round and the round polynomial of the next in ONE pass over the tables: what a prover does between two challenges.
+   Conventions are those of the multilinear calls above (index-major tables[i * k + j], the MOST significant variable bound first, groups in
+   CSR form in HOST memory, `r` ONE element in HOST memory).  For n a multiple of 4,
+       folded  receives the n / 2 * k records bn254_fr_mle_fold(tables, n k, r) writes: folded[i k + j] = T_j[i] + r * (T_j[i + n/2] - T_j[i]),
+       out     receives the degree + 1 records bn254_fr_sumcheck_round(folded, n / 2, k, groups .., degree) writes.
+   Everything is canonical, so the bytes ARE those of the two calls and of the integer model however the work is cut.  Every one of the k tables
+   is folded, also one that no group names.  `folded` may be exactly `tables`, in both forms: rows [n/2, n) are then left as they were.  Any
+   other overlap of `folded` with `tables`, and `out` overlapping either, is BN254_E_BAD_ARG.
+   How: the round's mapping over the h2 = n / 4 indices of the round that follows the fold - ceil(h2 / P) lanes, lane l takes the indices l,
+   l + lanes, .. .  For index i a lane first walks the k tables: it loads the four records of rows i, i + h2, i + 2 h2, i + 3 h2 and stores
+   a0 + r (a2 - a0) to row i and a1 + r (a3 - a1) to row i + h2 of `folded` - two products per table, the fold's own; then it runs the
+   round's group walk over rows i and i + h2 of `folded`, reading back what it has just written itself.  Rows i and i + h2 belong to that lane
+   alone, which is why in place is safe and no lane waits for another.  One launch reads n k records and writes n k / 2 where the two calls
+   move 2 n k.  Partial sums and sum levels are the round's own (context-owned scratch, fan 16, sub-launches of at most 2^22 lanes).  No LDS,
+   no atomics.  Indices per lane: P = 8 at full size (the fastest of 4 / 8 / 16 on four tables of 2^22 entries at degree 3, a rule fixed before
+   measuring), halved down to 4 while ceil(h2 / P) is below compute units * 4 * 64 * 2 lanes - the lanes that give every SIMD the two waves
+   these kernels hold -, because a prover walks through every size.
+   Measured on an MI355X (tools/time_fold_round.py, kernel ms, medians of 5; profiles/r20_fold_round.txt): four tables of 2^22 entries at
+   degree 3 take 0.605 / 0.595 / 0.671 ms at P = 4 / 8 / 16 - the fastest ships -, which is 3.60 x a device-to-device copy of the 1.5 n k records the
+   call must move and 1.31 x bn254_fr_mul_batch_dev on the 24 products per index it executes: the product floor is the nearer one.  At that
+   size the fusion itself does not pay: bn254_fr_mle_fold_dev in place and bn254_fr_sumcheck_round_dev take 0.545 ms together (0.92 x, ranges
+   apart; one table of 2^24 at degree 1: 0.346 against 0.333 ms).  At 2^16 / 2^18 / 2^20 entries, where the piece has shrunk to 4, the call takes
+   0.175 / 0.188 / 0.213 ms against 0.393 / 0.406 / 0.433 ms of the two calls (2.24 / 2.16 / 2.03 x) and against 0.312 / 0.324 / 0.330 ms at the fixed
+   P = 8, and the kernel time of a whole proof of 20 variables falls from 7.00 to 3.49 ms (2.01 x).  188 / 242 / 238 / 254 registers at degree
+   1 / 2 / 3 / 4, no spill, two waves per SIMD.
+   Errors (BN254_E_BAD_ARG, checked before any device is touched): n not a multiple of 4 or below 4, a NULL r or folded, everything
+   bn254_fr_sumcheck_round rejects for (n / 2, k, groups, degree), n k > 2^40, the overlaps above.  Threading: as bn254_fr_sumcheck_round - the
+   host-buffer entry point holds the context's mutex for the whole call. */
+int bn254_fr_sumcheck_fold_round(bn254_ctx *ctx, const bn_fr *tables, size_t n, size_t k, const bn_fr *r, const size_t *group_offsets, const uint64_t *group_tables,
+                                 const bn_fr *group_coeff, size_t g, int degree, bn_fr *folded, bn_fr *out);
 /* The quotients of a multilinear opening: the prover's field work of a multilinear KZG (PST) commitment.  Conventions are those of the
    multilinear calls above: index i is the point whose variable j is bit j of i, the MOST significant variable is bound first, everything is
    canonical, so the bytes are those of the integer model however the work is cut.  For a table `a` of n = 2^nv records and a point z[0 .. nv),
@@ -780,6 +817,11 @@ int bn254_fr_mle_eq_dev(bn254_ctx *ctx, const void *d_z, int nv, void *d_out, vo
 int bn254_fr_mle_fold_dev(bn254_ctx *ctx, const void *d_in, size_t len, const bn_fr *r, void *d_out, void *stream);
 int bn254_fr_sumcheck_round_dev(bn254_ctx *ctx, const void *d_tables, size_t n, size_t k, const size_t *group_offsets, const uint64_t *group_tables, const bn_fr *group_coeff,
                                 size_t g, int degree, void *d_out, void *stream);
+/* bn254_fr_sumcheck_fold_round on device-resident records of 32 bytes, 16-byte aligned, asynchronous on `stream`: d_tables holds n k records,
+   d_folded n / 2 * k (it may be exactly d_tables: the call then runs in place and rows [n/2, n) are left as they were), d_out degree + 1.  `r`
+   and the group description are HOST memory, read before the call returns.  Scratch and ordering are bn254_fr_sumcheck_round_dev's. */
+int bn254_fr_sumcheck_fold_round_dev(bn254_ctx *ctx, const void *d_tables, size_t n, size_t k, const bn_fr *r, const size_t *group_offsets, const uint64_t *group_tables,
+                                     const bn_fr *group_coeff, size_t g, int degree, void *d_folded, void *d_out, void *stream);
 /* bn254_fr_mle_quotients on device-resident records of 32 bytes, 16-byte aligned, asynchronous on `stream`: d_a and d_out hold 2^nv records each and
    must not overlap; d_a is never written.  `z` (nv records) is HOST memory, read before the call returns, and may be freed then.  The call
    waits for nothing and reads nothing back; the working table between its passes is context-owned scratch (see Threading). */
@@ -812,6 +854,7 @@ int bn254_profile_reset(bn254_ctx *ctx);
    of bn254_fr_scan_batch: "fr_scan" (the apply level, direct segments among it), "fr_scan_reduce" (the maps of the pieces), "fr_scan_up", "fr_scan_down" (the levels over the maps);
    of bn254_fr_mle_eq, bn254_fr_mle_fold and bn254_fr_sumcheck_round: "fr_mle_eq", "fr_mle_fold", "fr_sumcheck_round" (the lanes over the indices), "fr_sumcheck_sum" (the levels over the partial sums);
    of bn254_fr_mle_quotients: "fr_mle_quotients" (one scope per pass, or per sub-launch of it);
+   of bn254_fr_sumcheck_fold_round: "fr_sumcheck_fold_round" (the lanes over the indices; the levels over its partial sums run under the round's scope for them);
    of bn254_fr_poseidon_batch, bn254_fr_poseidon_permute_batch and bn254_fr_merkle_tree: "fr_poseidon", "fr_poseidon_permute", "fr_merkle_level" (one scope per level, or per sub-launch of it);
    and, of bn254_fr_ntt_batch: "ntt" (the passes), "ntt_table" (the builds of the twiddle tables).
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */

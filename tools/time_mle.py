@@ -235,7 +235,7 @@ def main():
     say("sumcheck.prove, nv = %d (%d rounds, %d + %d calls)        | wall ms %s" % (nvp, nvp, nvp, nvp, fmt(p)))
     say("the integer model prover at nv = %d                        | wall ms %9.1f (one run) | EXTRAPOLATED per element to nv = %d: %.0f ms, %.0f x the GPU prover"
         % (nvm, model, nvp, model * (1 << (nvp - nvm)), model * (1 << (nvp - nvm)) / statistics.median(p)))
-    say("   not built: a fused fold-then-round call (the tables would be read once per round, not twice), a factored eq table (low bits times high bits), a sweep of the fan")
+    say("   not built here: a factored eq table (low bits times high bits), a sweep of the fan; the fused fold-then-round call and the resident prover are timed by tools/time_fold_round.py")
 
 
 if __name__ == "__main__":
