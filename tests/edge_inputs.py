@@ -1,12 +1,14 @@
-"""TEST INFRASTRUCTURE - edge inputs for the group kernels (G1/G2 mul, group addition, Gt::pow, the wire decoders).
+"""TEST INFRASTRUCTURE - edge inputs for the group kernels (G1/G2 mul, group addition, Gt::pow, the wire decoders) and the Fq12 tower.
 
 Plain Python on oracle/bn_model.py and the oracle's limb format (numpy uint64 Montgomery limbs, the reference's #[repr(C)] layouts).
-Three families:
+Four families:
   * edge REPRESENTATIONS: the same group element as (X z^2, Y z^3, Z z) for z at the edges of Fq / Fq2 (rescale_g1 / rescale_g2);
   * edge POINTS: the G1 points with the smallest and largest x, k G2 for k in {1, r - 1, q mod r};
   * crafted SCALARS that drive the GLV split of G1 mul (curve.hpp glv_decompose) and the GLS split of G2 mul and Gt::pow
     (gls_decompose) to their largest parts and through their sign patterns, built from the lattice bases that
-    tools/gen_device_constants.py wrote into bn_amd/csrc/bn254_constants.hpp.
+    tools/gen_device_constants.py wrote into bn_amd/csrc/bn254_constants.hpp;
+  * edge Fq12 ELEMENTS (edge_fq12) with their images in the cyclotomic subgroup and in the order-r subgroup: coefficients 0, q - 1 and
+    equal ones, subfield elements, single slots - what the tower, the final exponentiation and the Gt operations are fed.
 """
 import pathlib
 import re
@@ -271,3 +273,68 @@ def g2_record(x, y, tag=4):
 
 def fq2_packed(c):
     return c[1] * Q + c[0]
+
+
+# ---------------------------------------------------------------------------------------------- edge Fq12 elements
+# the coefficient pool of tests/test_hostsim.py's EDGE: 0 and q - 1, their neighbours, the middle, a single high bit, a full low 29-bit
+# limb, the lowest bit of the top limb of the 9 x 29-bit form, and R mod q
+FQ12_POOL = [0, 1, 2, Q - 1, Q - 2, (Q - 1) // 2, 1 << 253, (1 << 29) - 1, 1 << 232, M.MONT_R % Q]
+GT_EDGE_SCALARS = [0, 1, 2, 15, 16, R - 1, (1 << 253) + 12345]
+_FQ12_CACHE = {}
+
+
+def edge_fq12_ints():
+    """ordered {name: [12 integers]} - 64 NON-ZERO Fq12 elements, coefficients in the order oracle.fq12_from_ints takes (slots 0..5 are
+    c0 = three Fq2, slots 6..11 are c1).  Equal coefficients make the signed Karatsuba differences of the tower vanish, 0 against q - 1
+    drives them to either extreme, subfield elements and single slots leave most partial products zero.  (-1 is there twice: under its
+    own name and as the first of the twelve single slots.)"""
+    z, m = 0, Q - 1
+    e = {"one": [1] + [z] * 11, "-1": [m] + [z] * 11, "all q-1": [m] * 12, "all 1": [1] * 12,
+         "0,q-1 x6": [z, m] * 6, "q-1,0 x6": [m, z] * 6, "c0 only": [m] * 6 + [z] * 6, "c1 only": [z] * 6 + [m] * 6,
+         "w": [z] * 6 + [1] + [z] * 5}
+    for s in range(12):
+        e["q-1 in slot %d" % s] = [m if i == s else z for i in range(12)]
+    e["fq2 subfield"] = [m, Q - 2] + [z] * 10
+    e["all (q-1)/2"] = [(Q - 1) // 2] * 12
+    e["all 2^253"] = [1 << 253] * 12
+    rng = np.random.default_rng(20260)
+    while len(e) < 64:
+        c = [FQ12_POOL[i] for i in rng.integers(0, len(FQ12_POOL), 12)]
+        if any(c):
+            e["pool draw %d" % (len(e) - 24)] = c
+    return e
+
+
+def edge_fq12(oracle):
+    """ordered {name: (48,) uint64}: edge_fq12_ints() as the oracle's Montgomery limbs"""
+    if "fq12" not in _FQ12_CACHE:
+        _FQ12_CACHE["fq12"] = {k: oracle.fq12_from_ints(v) for k, v in edge_fq12_ints().items()}
+    return _FQ12_CACHE["fq12"]
+
+
+def edge_cyclotomic(oracle):
+    """the easy part of the final exponentiation of every edge element, in order: elements of the cyclotomic subgroup, generally NOT of
+    order r"""
+    if "cyc" not in _FQ12_CACHE:
+        _FQ12_CACHE["cyc"] = [oracle.fq12_final_exp_first_chunk(a) for a in edge_fq12(oracle).values()]
+    return _FQ12_CACHE["cyc"]
+
+
+def edge_gt(oracle):
+    """the final exponentiation of every edge element, in order: elements whose order divides r"""
+    if "gt" not in _FQ12_CACHE:
+        _FQ12_CACHE["gt"] = [oracle.fq12_final_exponentiation(a) for a in edge_fq12(oracle).values()]
+    return _FQ12_CACHE["gt"]
+
+
+def edge_partners(n=64):
+    """the index of the second operand for every edge element: a fixed seeded draw, never the element itself (a * b is not the square)"""
+    idx = np.random.default_rng(20261).integers(0, n, n)
+    return [int(j) if int(j) != i else (i + 1) % n for i, j in enumerate(idx)]
+
+
+def oracle_is_cyclotomic(oracle, a):
+    """a^(q^4 - q^2 + 1) == 1 as frob^4(a) * a == frob^2(a), computed with the oracle: what pairing.hpp gt_is_cyclotomic evaluates"""
+    f2 = oracle.fq12_frobenius_map(a, 2)
+    f4 = oracle.fq12_frobenius_map(f2, 2)
+    return np.array_equal(oracle.fq12_mul(f4, a), f2)

@@ -162,3 +162,32 @@ def test_crafted_scalars_through_the_device_chains(oracle, hs):
         want = canon_infinity(oracle.g2_normalize(oracle.g2_mul(q, k)))
         assert np.array_equal(hs.call("hs_g2_mul_gls", q, k, out_words=48), want), kv
         assert np.array_equal(hs.call("hsb_g2_mul_gls", q, k, out_words=48), want), kv
+
+
+def test_edge_fq12_set(oracle):
+    """the 64 edge Fq12 elements are what their names say (checked with the independent big-integer model), non-zero and distinct but for -1, which the list holds twice; their
+    easy-part images are cyclotomic, their final exponentiations have an order dividing r, and the Fq6-subfield elements map to one"""
+    ints = E.edge_fq12_ints()
+    edge = E.edge_fq12(oracle)
+    assert len(ints) == 64 and list(edge) == list(ints)
+    # (the list names -1 twice: on its own and as the first of the twelve single slots; everything else is distinct)
+    assert ints["-1"] == ints["q-1 in slot 0"] and len({tuple(v) for v in ints.values()}) == 63
+    assert all(len(v) == 12 and any(v) and all(0 <= c < M.Q for c in v) for v in ints.values())
+    assert all(c in E.FQ12_POOL for nm, v in ints.items() if nm.startswith("pool draw") for c in v)
+    assert sum(nm.startswith("pool draw") for nm in ints) == 40 and sum(nm.startswith("q-1 in slot") for nm in ints) == 12
+    m1 = ints["-1"]
+    assert m1 == [M.Q - 1] + [0] * 11 and ints["w"][6] == 1 and sum(ints["w"]) == 1 and ints["c0 only"] == [M.Q - 1] * 6 + [0] * 6
+    f12 = lambda v: (((v[0], v[1]), (v[2], v[3]), (v[4], v[5])), ((v[6], v[7]), (v[8], v[9]), (v[10], v[11])))
+    flat = lambda x: [c for h in x for f2 in h for c in f2]
+    assert flat(M.f12_mul(f12(m1), f12(m1))) == ints["one"] and flat(M.f12_mul(f12(ints["w"]), f12(ints["w"]))) == [0, 0, 1, 0] + [0] * 8   # w^2 = v
+    for nm, a in edge.items():
+        assert oracle.fq12_to_ints(a) == ints[nm], nm
+    one = oracle.fq12_one()
+    rm1 = oracle.fp_from_int(FR, M.R_ORD - 1)
+    for nm, c, g in zip(edge, E.edge_cyclotomic(oracle), E.edge_gt(oracle)):
+        assert E.oracle_is_cyclotomic(oracle, c), nm
+        assert np.array_equal(oracle.fq12_mul(oracle.gt_pow(g, rm1), g), one), nm                       # g^r == 1
+    gt = dict(zip(edge, E.edge_gt(oracle)))
+    assert np.array_equal(gt["c0 only"], one) and np.array_equal(gt["-1"], one) and not np.array_equal(gt["all q-1"], one)
+    p = E.edge_partners()
+    assert len(p) == 64 and all(0 <= j < 64 and j != i for i, j in enumerate(p))

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import bn_model as M
+import edge_inputs as E
 import hostsim_lib
 from conftest import canon_infinity
 from bn_oracle import FQ, FR
@@ -530,3 +531,101 @@ def test_quad_mapping_on_simulated_quad(oracle, hs, kats):
     assert np.array_equal(hs.call("hsq_pairing", oracle.g1_zero(), Q, 1, out_words=96), one)
     assert np.array_equal(hs.call("hsq_pairing", P, oracle.g2_zero(), 1, out_words=96), one)
     assert np.array_equal(hs.call("hsq_pairing", oracle.g1_one(), oracle.g2_one(), 1, out_words=96), oracle.pairing(oracle.g1_one(), oracle.g2_one()))
+
+
+# ------------------------------------------------------------------------------------------------ the tower at edge elements
+# tests/edge_inputs.py edge_fq12: 64 non-zero Fq12 elements with coefficients 0, q - 1, equal ones, subfield elements and single slots, their
+# images in the cyclotomic subgroup (edge_cyclotomic) and in the order-r subgroup (edge_gt).  Every bound of the lazy number system is
+# enforced (a violation aborts the process), every result is compared bit for bit with the oracle.
+
+
+def _line(b):
+    """the first three Fq2 of an Fq12 as a sparse line (ell_0, ell_vw, ell_vv)"""
+    return b[:8], b[8:16], b[16:24]
+
+
+@pytest.mark.parametrize("pre", ["hs_", "hsb_"])
+def test_tower_ops_on_edge_elements(oracle, hs, pre):
+    """tower.hpp on one lane (hs_) and on a lane pair (hsb_): product by another edge element and by itself, square, Granger-Scott
+    square (fq12.rs:178-227 as written: arbitrary input), inverse, the three Frobenius maps, the sparse line product"""
+    names, elems = list(E.edge_fq12(oracle)), list(E.edge_fq12(oracle).values())
+    for i, j in enumerate(E.edge_partners()):
+        a, b, nm = elems[i], elems[j], names[i]
+        assert np.array_equal(hs.call(pre + "fq12_mul", a, b, out_words=96), oracle.fq12_mul(a, b)), (nm, names[j])
+        assert np.array_equal(hs.call(pre + "fq12_mul", a, a, out_words=96), oracle.fq12_mul(a, a)), nm
+        assert np.array_equal(hs.call(pre + "fq12_sqr", a, out_words=96), oracle.fq12_sqr(a)), nm
+        assert np.array_equal(hs.call(pre + "fq12_cyclotomic_sqr", a, out_words=96), oracle.fq12_cyclotomic_squared(a)), nm
+        assert np.array_equal(hs.call(pre + "fq12_inverse", a, out_words=96), oracle.fq12_inverse(a)), nm
+        for p in (1, 2, 3):
+            assert np.array_equal(hs.call(pre + "fq12_frobenius", a, p, out_words=96), oracle.fq12_frobenius_map(a, p)), (nm, p)
+        assert np.array_equal(hs.call(pre + "fq12_mul_by_024", a, *_line(b), out_words=96), oracle.fq12_mul_by_024(a, *_line(b))), (nm, names[j])
+
+
+def test_quad_tower_ops_on_edge_elements(oracle, hs):
+    """quad.hpp (four lanes: the lower lane pair holds c0, the upper c1) on the same elements: square, product by b and by conj(b),
+    Granger-Scott square, inverse, Frobenius maps and the sparse line product, each against the oracle itself"""
+    names, elems = list(E.edge_fq12(oracle)), list(E.edge_fq12(oracle).values())
+    cyc = E.edge_cyclotomic(oracle)
+    for i, j in enumerate(E.edge_partners()):
+        a, b, nm = elems[i], elems[j], names[i]
+        assert np.array_equal(hs.call("hsq_fq12_sqr", a, out_words=96), oracle.fq12_sqr(a)), nm
+        assert np.array_equal(hs.call("hsq_fq12_mul", a, b, 0, out_words=96), oracle.fq12_mul(a, b)), (nm, names[j])
+        assert np.array_equal(hs.call("hsq_fq12_mul", a, a, 0, out_words=96), oracle.fq12_mul(a, a)), nm
+        assert np.array_equal(hs.call("hsq_fq12_mul", a, b, 1, out_words=96), oracle.fq12_mul(a, oracle.fq12_unitary_inverse(b))), (nm, names[j])
+        assert np.array_equal(hs.call("hsq_fq12_cyclotomic_sqr", a, out_words=96), oracle.fq12_cyclotomic_squared(a)), nm
+        assert np.array_equal(hs.call("hsq_fq12_cyclotomic_sqr", cyc[i], out_words=96), oracle.fq12_sqr(cyc[i])), nm     # a true square there
+        assert np.array_equal(hs.call("hsq_fq12_inverse", a, out_words=96), oracle.fq12_inverse(a)), nm
+        for p in (1, 2, 3):
+            assert np.array_equal(hs.call("hsq_fq12_frobenius", a, p, out_words=96), oracle.fq12_frobenius_map(a, p)), (nm, p)
+        assert np.array_equal(hs.call("hsq_fq12_mul_by_024", a, *_line(b), out_words=96), oracle.fq12_mul_by_024(a, *_line(b))), (nm, names[j])
+
+
+@pytest.mark.parametrize("fn", ["hs_final_exponentiation", "hsb_final_exponentiation", "hsq_final_exponentiation"])
+def test_final_exponentiation_on_edge_elements(oracle, hs, fn):
+    """fq12.rs:41-88 through the one-lane, lane-pair and four-lane code on every edge element; an element of the Fq6 subfield is fixed
+    by frob^6, so the easy part already maps it to one"""
+    edge, want = E.edge_fq12(oracle), E.edge_gt(oracle)
+    got = {nm: hs.call(fn, a, out_words=96) for nm, a in edge.items()}
+    for (nm, g), w in zip(got.items(), want):
+        assert np.array_equal(g, w), nm
+    one = oracle.fq12_one()
+    assert np.array_equal(got["c0 only"], one) and np.array_equal(got["-1"], one)
+
+
+def _cycled_scalars(oracle, n):
+    return [oracle.fp_from_int(FR, E.GT_EDGE_SCALARS[i % len(E.GT_EDGE_SCALARS)]) for i in range(n)]
+
+
+def test_gt_pow_general_chain_on_edge_elements(oracle, hs):
+    """the windowed general chain of bn254_gt_pow_B and the chain the kernel picks by itself (membership test first) on every edge
+    element, edge scalars cycled over them"""
+    edge = E.edge_fq12(oracle)
+    for (nm, a), k in zip(edge.items(), _cycled_scalars(oracle, len(edge))):
+        want = oracle.gt_pow(a, k)
+        assert np.array_equal(hs.call("hsb_gt_pow", a, k, out_words=96), want), nm
+        assert np.array_equal(hs.call("hsb_gt_pow_auto", a, k, out_words=96), want), nm
+
+
+def test_gt_pow_cyclotomic_chains_on_edge_elements(oracle, hs):
+    """the membership test on the cyclotomic images (1) and on -1 and `all q-1` (0, as the oracle's own frob^4(a) a == frob^2(a) says),
+    the one-dimensional signed-window chain on the cyclotomic images (order generally not r) and the Frobenius decomposition on the
+    order-r images"""
+    edge, cyc, gt = E.edge_fq12(oracle), E.edge_cyclotomic(oracle), E.edge_gt(oracle)
+    U32 = hostsim_lib._U32P
+    for nm, c in zip(edge, cyc):
+        assert E.oracle_is_cyclotomic(oracle, c) and hs.lib.hsb_gt_is_cyclotomic(c.ctypes.data_as(U32)) == 1, nm
+    for nm in ("-1", "all q-1"):
+        assert not E.oracle_is_cyclotomic(oracle, edge[nm])
+        assert hs.lib.hsb_gt_is_cyclotomic(edge[nm].ctypes.data_as(U32)) == 0, nm
+    for nm, c, g, k in zip(edge, cyc, gt, _cycled_scalars(oracle, len(edge))):
+        assert np.array_equal(hs.call("hsb_gt_pow_cyclotomic", c, k, out_words=96), oracle.gt_pow(c, k)), nm
+        assert np.array_equal(hs.call("hsb_gt_pow_gls", g, k, out_words=96), oracle.gt_pow(g, k)), nm
+
+
+def test_exp_by_neg_z_on_edge_elements(oracle, hs):
+    """fq12.rs:229-246 as written (any Fq12: off the subgroup the result belongs to this operation sequence) on the edge elements, and
+    the signed-digit schedule of the final exponentiation on their cyclotomic images, where both are a^-u"""
+    edge, cyc = E.edge_fq12(oracle), E.edge_cyclotomic(oracle)
+    for (nm, a), c in zip(edge.items(), cyc):
+        assert np.array_equal(hs.call("hs_fq12_exp_by_neg_z", a, out_words=96), oracle.fq12_exp_by_neg_z(a)), nm
+        assert np.array_equal(hs.call("hs_fq12_exp_by_neg_z_naf", c, out_words=96), oracle.fq12_exp_by_neg_z(c)), nm

@@ -129,3 +129,43 @@ def test_wave_pairing_in_host_simulation(oracle, hs, kats):
     k1 = oracle.fp_from_decimal(FR, kats["test_reduced_pairing"]["k1"]); k2 = oracle.fp_from_decimal(FR, kats["test_reduced_pairing"]["k2"])
     gt = hs.call("hsw_pairing", 1, oracle.g1_mul(oracle.g1_one(), k1), oracle.g2_mul(oracle.g2_one(), k2), out_words=96)
     assert oracle.fq12_to_ints(gt) == [int(x) for x in kats["test_reduced_pairing"]["expected"]]
+
+
+# ------------------------------------------------------------------------------------------------ the programs at edge elements
+def test_wave_products_and_frobenius_on_edge_elements(oracle, hs):
+    """MUL, MULC and FROB1..3 on the 64 edge elements of tests/edge_inputs.py (coefficients 0, q - 1, equal ones, subfield elements,
+    single slots), the second operand another edge element by a seeded index, bounds enforced"""
+    import edge_inputs as E
+    names, elems = list(E.edge_fq12(oracle)), list(E.edge_fq12(oracle).values())
+    z = np.zeros(48, np.uint64)
+    for i, j in enumerate(E.edge_partners()):
+        a, b, nm = elems[i], elems[j], names[i]
+        assert np.array_equal(hs.call("hsw_run", 0, a, b, out_words=96), oracle.fq12_mul(a, b)), (nm, names[j])
+        assert np.array_equal(hs.call("hsw_run", 1, a, b, out_words=96), oracle.fq12_mul(a, oracle.fq12_unitary_inverse(b))), (nm, names[j])
+        for P in (1, 2, 3):
+            assert np.array_equal(hs.call("hsw_run", 2 + P, a, z, out_words=96), oracle.fq12_frobenius_map(a, P)), (nm, P)
+
+
+def test_wave_easy_part_and_cyclotomic_squarings_on_edge_elements(oracle, hs):
+    """EASY against fq12_final_exp_first_chunk, then CYC and the fused CYC5 on its output"""
+    import edge_inputs as E
+    z = np.zeros(48, np.uint64)
+    for (nm, a), c in zip(E.edge_fq12(oracle).items(), E.edge_cyclotomic(oracle)):
+        assert np.array_equal(hs.call("hsw_run", 6, a, z, out_words=96), c), nm
+        c2 = oracle.fq12_cyclotomic_squared(c)
+        assert np.array_equal(hs.call("hsw_run", 2, c, z, out_words=96), c2), nm
+        c32 = c2
+        for _ in range(4): c32 = oracle.fq12_cyclotomic_squared(c32)
+        assert np.array_equal(hs.call("hsw_run", 9, c, z, out_words=96), c32), nm
+
+
+def test_wave_final_exponentiation_on_edge_elements(oracle, hs):
+    """FE (the program bn254_final_exp_W interprets) on every edge element; the Fq6-subfield elements give one"""
+    import edge_inputs as E
+    z = np.zeros(48, np.uint64)
+    edge = E.edge_fq12(oracle)
+    got = {nm: hs.call("hsw_run", 8, a, z, out_words=96) for nm, a in edge.items()}
+    for (nm, g), w in zip(got.items(), E.edge_gt(oracle)):
+        assert np.array_equal(g, w), nm
+    one = oracle.fq12_one()
+    assert np.array_equal(got["c0 only"], one) and np.array_equal(got["-1"], one)
