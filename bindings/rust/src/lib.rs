@@ -21,6 +21,15 @@ extern "C" {
     fn bn254_g1_decode_batch(ctx: *mut c_void, bytes: *const u8, out: *mut G1, status: *mut i32, n: usize) -> c_int;
     fn bn254_g2_decode_batch(ctx: *mut c_void, bytes: *const u8, out: *mut G2, status: *mut i32, n: usize) -> c_int;
     fn bn254_gt_inverse_batch(ctx: *mut c_void, a: *const Gt, out: *mut Gt, n: usize) -> c_int;
+    // compressed encodings (x and a sign bit; format: BN254_COMPRESSED_ARK = 0, BN254_COMPRESSED_GNARK = 1)
+    fn bn254_g1_compress_batch(ctx: *mut c_void, p: *const G1, format: c_int, out: *mut u8, n: usize) -> c_int;
+    fn bn254_g2_compress_batch(ctx: *mut c_void, p: *const G2, format: c_int, out: *mut u8, n: usize) -> c_int;
+    fn bn254_g1_decompress_batch(ctx: *mut c_void, bytes: *const u8, format: c_int, out: *mut G1, status: *mut i32, n: usize) -> c_int;
+    fn bn254_g2_decompress_batch(ctx: *mut c_void, bytes: *const u8, format: c_int, out: *mut G2, status: *mut i32, n: usize) -> c_int;
+    fn bn254_g1_compress_batch_dev(ctx: *mut c_void, d_p: *const c_void, format: c_int, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_g2_compress_batch_dev(ctx: *mut c_void, d_p: *const c_void, format: c_int, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_g1_decompress_batch_dev(ctx: *mut c_void, d_in: *const c_void, format: c_int, d_out: *mut c_void, d_status: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_g2_decompress_batch_dev(ctx: *mut c_void, d_in: *const c_void, format: c_int, d_out: *mut c_void, d_status: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     // prepared-G2 mode (the crate's internal G2Precomp, src/groups/mod.rs:472-483): 102 line coefficients per Q, then many P against them
     fn bn254_g2_precompute(ctx: *mut c_void, q: *const G2, coeffs: *mut EllCoeffs, n: usize) -> c_int;
     fn bn254_pairing_prepared_batch(ctx: *mut c_void, p: *const G1, coeffs: *const EllCoeffs, shared: c_int, out: *mut Gt, n: usize) -> c_int;
@@ -527,6 +536,52 @@ pub fn g1_decode_batch(records: &[u8]) -> Result<Vec<Result<G1, i32>>, GpuError>
     let n = records.len() / G1_WIRE_BYTES;
     let (mut out, mut status) = (vec![G1::zero(); n], vec![0i32; n]);
     check(unsafe { bn254_g1_decode_batch(std::ptr::null_mut(), records.as_ptr(), out.as_mut_ptr(), status.as_mut_ptr(), n) })?;
+    Ok(out.into_iter().zip(status).map(|(p, s)| if s == 0 { Ok(p) } else { Err(s) }).collect())
+}
+
+/// The byte layout of a compressed point: x and one sign bit, 32 bytes for G1 and 64 for G2.  Laid out as ark-serialize / gnark-crypto
+/// describe; not checked against those libraries here.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum CompressedFormat {
+    /// little endian, G2 as c0 then c1, flags in the top two bits of the last byte (bit 7 sign, bit 6 infinity)
+    Ark,
+    /// big endian, G2 as c1 then c0, flags in the top two bits of the first byte (10 sign 0, 11 sign 1, 01 infinity)
+    Gnark,
+}
+
+impl CompressedFormat {
+    fn code(self) -> c_int { match self { CompressedFormat::Ark => 0, CompressedFormat::Gnark => 1 } }
+    pub const fn g1_bytes() -> usize { 32 }
+    pub const fn g2_bytes() -> usize { 64 }
+}
+
+/// 32 bytes per point, canonical: any Jacobian form of a point gives the same bytes
+pub fn g1_compress_batch(p: &[G1], format: CompressedFormat) -> Result<Vec<u8>, GpuError> {
+    let mut out = vec![0u8; p.len() * CompressedFormat::g1_bytes()];
+    check(unsafe { bn254_g1_compress_batch(std::ptr::null_mut(), p.as_ptr(), format.code(), out.as_mut_ptr(), p.len()) })?;
+    Ok(out)
+}
+
+pub fn g2_compress_batch(p: &[G2], format: CompressedFormat) -> Result<Vec<u8>, GpuError> {
+    let mut out = vec![0u8; p.len() * CompressedFormat::g2_bytes()];
+    check(unsafe { bn254_g2_compress_batch(std::ptr::null_mut(), p.as_ptr(), format.code(), out.as_mut_ptr(), p.len()) })?;
+    Ok(out)
+}
+
+/// `Err(code)` per record, checked in this order: 3 invalid flags, 1 x not below the modulus, 4 no point has this x, 5 not in the subgroup (G2)
+pub fn g1_decompress_batch(records: &[u8], format: CompressedFormat) -> Result<Vec<Result<G1, i32>>, GpuError> {
+    assert_eq!(records.len() % CompressedFormat::g1_bytes(), 0);
+    let n = records.len() / CompressedFormat::g1_bytes();
+    let (mut out, mut status) = (vec![G1::zero(); n], vec![0i32; n]);
+    check(unsafe { bn254_g1_decompress_batch(std::ptr::null_mut(), records.as_ptr(), format.code(), out.as_mut_ptr(), status.as_mut_ptr(), n) })?;
+    Ok(out.into_iter().zip(status).map(|(p, s)| if s == 0 { Ok(p) } else { Err(s) }).collect())
+}
+
+pub fn g2_decompress_batch(records: &[u8], format: CompressedFormat) -> Result<Vec<Result<G2, i32>>, GpuError> {
+    assert_eq!(records.len() % CompressedFormat::g2_bytes(), 0);
+    let n = records.len() / CompressedFormat::g2_bytes();
+    let (mut out, mut status) = (vec![G2::zero(); n], vec![0i32; n]);
+    check(unsafe { bn254_g2_decompress_batch(std::ptr::null_mut(), records.as_ptr(), format.code(), out.as_mut_ptr(), status.as_mut_ptr(), n) })?;
     Ok(out.into_iter().zip(status).map(|(p, s)| if s == 0 { Ok(p) } else { Err(s) }).collect())
 }
 

@@ -104,6 +104,14 @@ SIGNATURES = {   # name -> argtypes  (every function returns int unless noted)
     "bn254_g2_encode_stream": [_VP, _VP, _SZ, _VP, _SZ, C.POINTER(_SZ)],
     "bn254_g1_decode_stream": [_VP, _VP, _SZ, _VP, _VP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)],
     "bn254_g2_decode_stream": [_VP, _VP, _SZ, _VP, _VP, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)],
+    "bn254_g1_compress_batch": [_VP, _VP, C.c_int, _VP, _SZ],
+    "bn254_g2_compress_batch": [_VP, _VP, C.c_int, _VP, _SZ],
+    "bn254_g1_decompress_batch": [_VP, _VP, C.c_int, _VP, _VP, _SZ],
+    "bn254_g2_decompress_batch": [_VP, _VP, C.c_int, _VP, _VP, _SZ],
+    "bn254_g1_compress_batch_dev": [_VP, _VP, C.c_int, _VP, _SZ, _VP],
+    "bn254_g2_compress_batch_dev": [_VP, _VP, C.c_int, _VP, _SZ, _VP],
+    "bn254_g1_decompress_batch_dev": [_VP, _VP, C.c_int, _VP, _VP, _SZ, _VP],
+    "bn254_g2_decompress_batch_dev": [_VP, _VP, C.c_int, _VP, _VP, _SZ, _VP],
     "bn254_g2_precompute": [_VP, _VP, _VP, _SZ],
     "bn254_pairing_prepared_batch": [_VP, _VP, _VP, C.c_int, _VP, _SZ],
     "bn254_g2_precompute_dev": [_VP, _VP, _VP, _SZ, _VP],

@@ -126,6 +126,11 @@ class G1(_Point):
         return g1_msm(points, scalars)
     def mul_base(self, scalars):          # [self * k for k in scalars] over ONE cached table of self
         return g1_mul_base(self, scalars)
+    def to_compressed(self, format="ark"):    # 32 bytes: x and the sign of y
+        return g1_compress_batch([self], format)[0]
+    @staticmethod
+    def from_compressed(b, format="ark"):     # DecodeError for a record that is rejected
+        return _one_decompressed(g1_decompress_batch, b, format)
 
 
 _G2_GEN = ((10857046999023057135944570762232829481370756359578518086990519993285655852781,
@@ -162,6 +167,11 @@ class G2(_Point):
         return g2_msm(points, scalars)
     def mul_base(self, scalars):
         return g2_mul_base(self, scalars)
+    def to_compressed(self, format="ark"):    # 64 bytes
+        return g2_compress_batch([self], format)[0]
+    @staticmethod
+    def from_compressed(b, format="ark"):
+        return _one_decompressed(g2_decompress_batch, b, format)
 
 
 class Gt:
@@ -315,6 +325,65 @@ def _point_array(cls, points):
         return np.asarray(points, np.uint64).reshape(-1, cls.WORDS)
     points = list(points)
     return np.stack([p.limbs for p in points]) if points else np.zeros((0, cls.WORDS), np.uint64)
+
+
+DECODE_STATUS = {0: "ok", 1: "a coordinate is not below the field modulus", 2: "an Fq2 coordinate is not below the squared modulus", 3: "invalid flags or leading byte",
+                 4: "no point of the curve has this x", 5: "the point is not in the subgroup"}
+
+
+class DecodeError(ValueError):
+    """a record the decoder rejected; .status is the decoder's number (DECODE_STATUS)"""
+    def __init__(self, status):
+        self.status = int(status)
+        super().__init__(f"decode status {self.status}: {DECODE_STATUS.get(self.status, 'unknown')}")
+
+
+def _records(b, size):
+    """bytes (one record or many), a sequence of bytes objects or a uint8 array -> (n, size) uint8"""
+    if isinstance(b, (bytes, bytearray, memoryview)):
+        a = np.frombuffer(bytes(b), np.uint8)
+    elif isinstance(b, np.ndarray):
+        a = np.ascontiguousarray(b, np.uint8).reshape(-1)
+    else:
+        a = np.frombuffer(b"".join(bytes(r) for r in b), np.uint8)
+    if a.size % size:
+        raise ValueError(f"{a.size} bytes are not whole records of {size}")
+    return a.reshape(-1, size)
+
+
+def _one_decompressed(fn, b, format):
+    points, status = fn(b, format)
+    if len(points) != 1:
+        raise ValueError(f"one record is expected, got {len(points)}")
+    if status[0]:
+        raise DecodeError(status[0])
+    return points[0]
+
+
+def g1_compress_batch(points, format="ark", engine=None):
+    """[32 bytes per point]: x and the sign of y in the layout `format` ("ark": little endian, flags in the last byte; "gnark": big endian,
+    flags in the first).  points: a sequence of G1 (any Jacobian form) or an (n,12) uint64 array."""
+    return [r.tobytes() for r in (engine or default_engine()).g1_compress_batch(_point_array(G1, points), format)]
+
+
+def g2_compress_batch(points, format="ark", engine=None):
+    """the same over G2: 64 bytes per point"""
+    return [r.tobytes() for r in (engine or default_engine()).g2_compress_batch(_point_array(G2, points), format)]
+
+
+def g1_decompress_batch(b, format="ark", engine=None):
+    """(points, status): b is bytes of whole 32-byte records, a sequence of records or a uint8 array.  status[i] (int32): 0 ok, 3 invalid
+    flags, 1 x not below q, 4 no point has this x; a rejected record is G1.zero()."""
+    rec = _records(b, 32)
+    p, st = (engine or default_engine()).g1_decompress_batch(rec, format)
+    return [G1(r) for r in p], st
+
+
+def g2_decompress_batch(b, format="ark", engine=None):
+    """the same over G2: 64-byte records; status 5 for a point of the twist outside the subgroup"""
+    rec = _records(b, 64)
+    p, st = (engine or default_engine()).g2_decompress_batch(rec, format)
+    return [G2(r) for r in p], st
 
 
 def g1_normalize_batch(points, engine=None):

@@ -1,12 +1,16 @@
 // The wire format of the BN254 engine (include/bn254_hip.h; io_wire.hpp): encode / decode kernels, one record per lane, their host-buffer
-// entry points, and the byte streams of variable-length records built on them.  Compiled like every unit (bn254_hip.hip: the flags).
+// entry points, the byte streams of variable-length records built on them, and the compressed encodings (io_compress.hpp): their kernels are
+// template instances of bn254_fr_decode_k<Op> and - G2 decompression, which carries the subgroup chain - of bn254_g2_decode_k<Op>.
+// Compiled like every unit (bn254_hip.hip: the flags).
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstring>
 #include <vector>
 
 #include "curve.hpp"
 #include "io.hpp"
 #include "io_wire.hpp"
+#include "io_compress.hpp"
 #include "host_ctx.hpp"
 
 using namespace bn254;
@@ -60,6 +64,48 @@ __global__ void __launch_bounds__(BLOCK) bn254_fr_decode_k(const uint8_t *in, ui
     for (int i = 0; i < 32; ++i) b[i] = in[32u * idx + i];
     status[idx] = fr_decode_record(b, out + 8u * idx);
 }
+
+// compressed encodings (io_compress.hpp): lanes [lo, lo + n) of a call, one record per lane
+struct G1CompressOp {
+    const uint32_t *p; uint8_t *out; uint64_t lo; uint32_t n; int format;
+    __device__ __forceinline__ void operator()() const {
+        const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+        if (i >= n) return;
+        uint32_t w[24];
+        for (int j = 0; j < 24; ++j) w[j] = p[24 * (lo + i) + j];
+        g1_compress_record(w, format, out + BN254_G1_COMPRESSED_BYTES * (lo + i));
+    }
+};
+struct G2CompressOp {
+    const uint32_t *p; uint8_t *out; uint64_t lo; uint32_t n; int format;
+    __device__ __forceinline__ void operator()() const {
+        const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+        if (i >= n) return;
+        uint32_t w[48];
+        for (int j = 0; j < 48; ++j) w[j] = p[48 * (lo + i) + j];
+        g2_compress_record(w, format, out + BN254_G2_COMPRESSED_BYTES * (lo + i));
+    }
+};
+struct G1DecompressOp {
+    const uint8_t *in; uint32_t *out; int32_t *status; uint64_t lo; uint32_t n; int format;
+    __device__ __forceinline__ void operator()() const {
+        const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+        if (i >= n) return;
+        status[lo + i] = g1_decompress_record(in + BN254_G1_COMPRESSED_BYTES * (lo + i), format, out + 24 * (lo + i));
+    }
+};
+struct G2DecompressOp {
+    const uint8_t *in; uint32_t *out; int32_t *status; uint64_t lo; uint32_t n; int format;
+    __device__ __forceinline__ void operator()() const {
+        const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+        if (i >= n) return;
+        status[lo + i] = g2_decompress_record(in + BN254_G2_COMPRESSED_BYTES * (lo + i), format, out + 48 * (lo + i));
+    }
+};
+template <class Op>
+__global__ void __launch_bounds__(BLOCK) bn254_fr_decode_k(Op op) { op(); }
+template <class Op>
+__global__ void __launch_bounds__(BLOCK) bn254_g2_decode_k(Op op) { op(); }
 
 }  // namespace
 
@@ -146,5 +192,67 @@ int bn254_g1_decode_stream(bn254_ctx *ctx, const uint8_t *in, size_t len, bn_g1 
 int bn254_g2_decode_stream(bn254_ctx *ctx, const uint8_t *in, size_t len, bn_g2 *out, int32_t *status, size_t max_points, size_t *count, size_t *consumed) {
     return stream_decode(ctx, 2, in, len, out, status, max_points, count, consumed);
 }
+
+}  // extern "C"
+
+// ---- compressed encodings -------------------------------------------------------------------------------------------------------
+namespace {
+constexpr size_t WIRE_N_MAX = 0x7fffffffu / 129;            // the wire layer's limit on the records of one call
+// tests only: the sub-launch size (0 = BN_LAUNCH_MAX)
+std::atomic<size_t> g_compress_launch_max;
+size_t compress_step() { const size_t set = g_compress_launch_max.load(std::memory_order_relaxed); return set ? set : BN_LAUNCH_MAX; }
+
+// arguments only: nothing here touches a device.  1 = nothing to do
+int compress_check(int format, const void *in, const void *out, const void *status, bool decompress, size_t n) {
+    if (format != BN254_COMPRESSED_ARK && format != BN254_COMPRESSED_GNARK) return BN254_E_BAD_ARG;
+    if (n == 0) return 1;
+    return (!in || !out || (decompress && !status) || n > WIRE_N_MAX) ? BN254_E_BAD_ARG : BN254_OK;
+}
+int compress_run(bn254_ctx *ctx, int g, bool decompress, const void *d_in, int format, void *d_out, void *d_status, size_t n, hipStream_t s) {
+    return bn_for_parts(n, compress_step(), [&](size_t lo, size_t cnt) -> int {
+        BnScope sc(ctx, s, decompress ? (g == 1 ? "g1_decompress" : "g2_decompress") : (g == 1 ? "g1_compress" : "g2_compress"));
+        const dim3 grid((unsigned)((cnt + BLOCK - 1) / BLOCK)), block(BLOCK);
+        if (!decompress && g == 1) hipLaunchKernelGGL(bn254_fr_decode_k<G1CompressOp>, grid, block, 0, s, G1CompressOp{(const uint32_t *)d_in, (uint8_t *)d_out, (uint64_t)lo, (uint32_t)cnt, format});
+        if (!decompress && g == 2) hipLaunchKernelGGL(bn254_fr_decode_k<G2CompressOp>, grid, block, 0, s, G2CompressOp{(const uint32_t *)d_in, (uint8_t *)d_out, (uint64_t)lo, (uint32_t)cnt, format});
+        if (decompress && g == 1) hipLaunchKernelGGL(bn254_fr_decode_k<G1DecompressOp>, grid, block, 0, s, G1DecompressOp{(const uint8_t *)d_in, (uint32_t *)d_out, (int32_t *)d_status, (uint64_t)lo, (uint32_t)cnt, format});
+        if (decompress && g == 2) hipLaunchKernelGGL(bn254_g2_decode_k<G2DecompressOp>, grid, block, 0, s, G2DecompressOp{(const uint8_t *)d_in, (uint32_t *)d_out, (int32_t *)d_status, (uint64_t)lo, (uint32_t)cnt, format});
+        return (int)hipGetLastError();
+    });
+}
+// order of the checks: arguments, then context and device; nothing waits, nothing is read back
+int compress_dev(bn254_ctx *ctx, int g, bool decompress, const void *d_in, int format, void *d_out, void *d_status, size_t n, void *stream) {
+    int rc = compress_check(format, d_in, d_out, d_status, decompress, n); if (rc) return rc == 1 ? BN254_OK : rc;
+    if ((rc = bn_get_ctx(ctx))) return rc;
+    BnDev d(ctx, stream); if (!d.go) return d.rc;
+    return bn_no_throw([&] { return compress_run(ctx, g, decompress, d_in, format, d_out, d_status, n, d.s); });
+}
+int compress_host(bn254_ctx *ctx, int g, bool decompress, const void *in, int format, void *out, int32_t *status, size_t n) {
+    int rc = compress_check(format, in, out, status, decompress, n); if (rc) return rc == 1 ? BN254_OK : rc;
+    BnHost h(ctx); if (h.rc) return h.rc;
+    const size_t ps = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2), rs = g == 1 ? BN254_G1_COMPRESSED_BYTES : BN254_G2_COMPRESSED_BYTES;
+    return bn_staged(ctx, {in, n * (decompress ? rs : ps)}, {nullptr, 0}, out, n * (decompress ? ps : rs), decompress ? status : nullptr, n * sizeof(int32_t),
+                     [&](const BnStaged &d) { return compress_run(ctx, g, decompress, d.in[0], format, d.out, d.out2, n, ctx->stream); });
+}
+}  // namespace
+
+extern "C" {
+
+int bn254_g1_compress_batch(bn254_ctx *ctx, const bn_g1 *p, int format, uint8_t *out, size_t n) { return compress_host(ctx, 1, false, p, format, out, nullptr, n); }
+int bn254_g2_compress_batch(bn254_ctx *ctx, const bn_g2 *p, int format, uint8_t *out, size_t n) { return compress_host(ctx, 2, false, p, format, out, nullptr, n); }
+int bn254_g1_decompress_batch(bn254_ctx *ctx, const uint8_t *in, int format, bn_g1 *out, int32_t *status, size_t n) { return compress_host(ctx, 1, true, in, format, out, status, n); }
+int bn254_g2_decompress_batch(bn254_ctx *ctx, const uint8_t *in, int format, bn_g2 *out, int32_t *status, size_t n) { return compress_host(ctx, 2, true, in, format, out, status, n); }
+int bn254_g1_compress_batch_dev(bn254_ctx *ctx, const void *d_p, int format, void *d_out, size_t n, void *stream) { return compress_dev(ctx, 1, false, d_p, format, d_out, nullptr, n, stream); }
+int bn254_g2_compress_batch_dev(bn254_ctx *ctx, const void *d_p, int format, void *d_out, size_t n, void *stream) { return compress_dev(ctx, 2, false, d_p, format, d_out, nullptr, n, stream); }
+int bn254_g1_decompress_batch_dev(bn254_ctx *ctx, const void *d_in, int format, void *d_out, void *d_status, size_t n, void *stream) { return compress_dev(ctx, 1, true, d_in, format, d_out, d_status, n, stream); }
+int bn254_g2_decompress_batch_dev(bn254_ctx *ctx, const void *d_in, int format, void *d_out, void *d_status, size_t n, void *stream) { return compress_dev(ctx, 2, true, d_in, format, d_out, d_status, n, stream); }
+
+// internal (not in the header; tests and tools/time_compress.py): an override of the sub-launch size of the eight calls above (0 restores
+// BN_LAUNCH_MAX) so that a test reaches the seam between two sub-launches with a handful of records, and which chain form the square roots run
+int bn254_compress_set_launch_max(size_t lanes) {
+    if (lanes > BN_LAUNCH_MAX) return BN254_E_BAD_ARG;
+    g_compress_launch_max.store(lanes, std::memory_order_relaxed);
+    return BN254_OK;
+}
+int bn254_compress_sqrt_window(void) { return BN254_SQRT_WINDOW; }
 
 }  // extern "C"

@@ -135,13 +135,9 @@ BN_FN void g2_encode_record(const uint32_t *p, uint8_t *out) {
     fq2a_encode(a.x, buf + 1); fq2a_encode(a.y, buf + 65);
     for (int i = 0; i < 129; ++i) out[i] = (inf && i > 0) ? 0 : buf[i];
 }
-BN_FN int g2_decode_record(const uint8_t *in, uint32_t *out) {
-    uint8_t tag = in[0];
-    Fq2A x, y;
-    bool okx = fq2a_decode(in + 1, x), oky = fq2a_decode(in + 65, y);
-    int status = WIRE_OK;
+// p * (-1) + p == 0   (groups/mod.rs:183-194): the scalar r - 1 is the same for every lane, so its bits drive uniform branches
+BN_FN bool g2_in_subgroup(const Fq2A &x, const Fq2A &y) {
     using F = Fq2Field<Fq2A>;
-    // p * (-1) + p == 0   (groups/mod.rs:183-194): the scalar r - 1 is the same for every lane, so its bits drive uniform branches
     Jac<F> p = {x, y, F::one()};
     Jac<F> acc = p;
 #pragma unroll 1
@@ -150,7 +146,15 @@ BN_FN int g2_decode_record(const uint8_t *in, uint32_t *out) {
         if ((k::R_MINUS_1[i >> 6] >> (i & 63)) & 1) acc = jac_add_flags(acc, p, false, false);
     }
     Jac<F> sum = jac_add_flags(acc, p, false, false);
-    if (!F::is_zero(sum.z)) status = WIRE_E_NOT_IN_SUBGROUP;
+    return F::is_zero(sum.z);
+}
+BN_FN int g2_decode_record(const uint8_t *in, uint32_t *out) {
+    uint8_t tag = in[0];
+    Fq2A x, y;
+    bool okx = fq2a_decode(in + 1, x), oky = fq2a_decode(in + 65, y);
+    int status = WIRE_OK;
+    using F = Fq2Field<Fq2A>;
+    if (!g2_in_subgroup(x, y)) status = WIRE_E_NOT_IN_SUBGROUP;
     Fq2A rhs = f2_lc3<1, 1, 0>(f2_mul(f2_sqr(x), x), f2_const((const Fq2A *)nullptr, k::G2_B), x);
     if (!f2_is_zero(f2_lc3<1, -1, 0>(f2_sqr(y), rhs, y))) status = WIRE_E_NOT_ON_CURVE;
     if (!oky) status = WIRE_E_NOT_LESS_THAN_MODULUS_SQUARED;

@@ -22,6 +22,19 @@ def _p(a):
     return C.c_void_p(a.ctypes.data)
 
 
+COMPRESSED_FORMATS = {"ark": 0, "gnark": 1}          # BN254_COMPRESSED_* of include/bn254_hip.h
+G1_COMPRESSED_BYTES, G2_COMPRESSED_BYTES = 32, 64
+
+
+def compressed_format(fmt):
+    """"ark" / "gnark" -> the header's number (numbers pass through: the library rejects the unknown ones)"""
+    if isinstance(fmt, str):
+        if fmt not in COMPRESSED_FORMATS:
+            raise ValueError(f"unknown compressed format {fmt!r}: {sorted(COMPRESSED_FORMATS)} are defined")
+        return COMPRESSED_FORMATS[fmt]
+    return int(fmt)
+
+
 def _same_len(a, b):
     if a.shape[0] != b.shape[0]:
         raise ValueError(f"operands differ in length: {a.shape[0]} vs {b.shape[0]}")
@@ -673,6 +686,43 @@ class Engine:
         b = np.ascontiguousarray(b, np.uint8).reshape(-1, 129); n = b.shape[0]
         out = np.empty((n, G2_WORDS), np.uint64); st = np.empty(n, np.int32)
         _native.check(self._lib.bn254_g2_decode_batch(self._h, _p(b), _p(out), _p(st), n)); return out, st
+
+    # ---- compressed encodings (x and a sign bit: G1 32 bytes, G2 64 bytes; format "ark" or "gnark")
+    def _compress(self, fn, p, words, rec, fmt):
+        p = _arr(p, words); out = np.empty((p.shape[0], rec), np.uint8)
+        _native.check(fn(self._h, _p(p), compressed_format(fmt), _p(out), p.shape[0])); return out
+
+    def _decompress(self, fn, b, words, rec, fmt):
+        b = np.ascontiguousarray(b, np.uint8).reshape(-1, rec); n = b.shape[0]
+        out = np.empty((n, words), np.uint64); st = np.empty(n, np.int32)
+        _native.check(fn(self._h, _p(b), compressed_format(fmt), _p(out), _p(st), n)); return out, st
+
+    def g1_compress_batch(self, p, format="ark"):
+        """(n,12) uint64 points (any Jacobian form) -> (n,32) uint8 canonical records"""
+        return self._compress(self._lib.bn254_g1_compress_batch, p, G1_WORDS, G1_COMPRESSED_BYTES, format)
+
+    def g2_compress_batch(self, p, format="ark"):
+        return self._compress(self._lib.bn254_g2_compress_batch, p, G2_WORDS, G2_COMPRESSED_BYTES, format)
+
+    def g1_decompress_batch(self, b, format="ark"):
+        """records -> (points (x, y, 1), int32 status: 0 ok, 3 flags, 1 range, 4 no such point, 5 not in the subgroup); rejected -> G::zero()"""
+        return self._decompress(self._lib.bn254_g1_decompress_batch, b, G1_WORDS, G1_COMPRESSED_BYTES, format)
+
+    def g2_decompress_batch(self, b, format="ark"):
+        return self._decompress(self._lib.bn254_g2_decompress_batch, b, G2_WORDS, G2_COMPRESSED_BYTES, format)
+
+    def g1_compress_batch_dev(self, d_p, d_out, n, format="ark", stream=0):
+        _native.check(self._lib.bn254_g1_compress_batch_dev(self._h, d_p, compressed_format(format), d_out, n, stream))
+
+    def g2_compress_batch_dev(self, d_p, d_out, n, format="ark", stream=0):
+        _native.check(self._lib.bn254_g2_compress_batch_dev(self._h, d_p, compressed_format(format), d_out, n, stream))
+
+    def g1_decompress_batch_dev(self, d_in, d_out, d_status, n, format="ark", stream=0):
+        """device pointers: records, points and n int32 statuses"""
+        _native.check(self._lib.bn254_g1_decompress_batch_dev(self._h, d_in, compressed_format(format), d_out, d_status, n, stream))
+
+    def g2_decompress_batch_dev(self, d_in, d_out, d_status, n, format="ark", stream=0):
+        _native.check(self._lib.bn254_g2_decompress_batch_dev(self._h, d_in, compressed_format(format), d_out, d_status, n, stream))
 
     # ---- the crate's variable-length byte stream (infinity = the lone byte 0)
     def _encode_stream(self, fn, p, rec):

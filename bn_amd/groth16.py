@@ -60,6 +60,46 @@ def verify_batch(vk, proofs, public_inputs, engine=None, prepared=False):
     return pairing_check_batch(P.reshape(-1, G1_WORDS), Q.reshape(-1, G2_WORDS), offsets=np.arange(m + 1, dtype=np.uint64) * 4, engine=e)
 
 
+def encode_proofs(proofs, format="ark", engine=None):
+    """bytes: A | B | C per proof in the compressed layout `format` ("ark" or "gnark"), 32 + 64 + 32 = 128 bytes each - one G1 call over the
+    2 m points A_0, C_0, A_1, ... and one G2 call"""
+    e = engine or default_engine()
+    proofs = list(proofs)
+    m = len(proofs)
+    if m == 0:
+        return b""
+    ac = e.g1_compress_batch(np.stack([p.limbs for a, _, c in proofs for p in (a, c)]), format).reshape(m, 2, 32)
+    b = e.g2_compress_batch(np.stack([b.limbs for _, b, _ in proofs]), format)
+    return np.concatenate([ac[:, 0], b, ac[:, 1]], axis=1).tobytes()
+
+
+def decode_proofs(blob, format="ark", engine=None):
+    """(proofs, status): the proofs of encode_proofs' bytes as (A: G1, B: G2, C: G1) and an (m, 3) int32 array of the decoder's statuses for A,
+    B, C (0 ok, 3 flags, 1 range, 4 no such point, 5 not in the subgroup); a rejected point is the group's zero.  ValueError unless the blob is
+    whole 128-byte records."""
+    e = engine or default_engine()
+    raw = np.frombuffer(bytes(blob), np.uint8)
+    if raw.size % 128:
+        raise ValueError(f"{raw.size} bytes are not whole proofs of 128")
+    rec = raw.reshape(-1, 128)
+    m = rec.shape[0]
+    if m == 0:
+        return [], np.zeros((0, 3), np.int32)
+    ac, st_ac = e.g1_decompress_batch(np.ascontiguousarray(rec[:, [*range(32), *range(96, 128)]]).reshape(2 * m, 32), format)
+    b, st_b = e.g2_decompress_batch(np.ascontiguousarray(rec[:, 32:96]), format)
+    st_ac = st_ac.reshape(m, 2)
+    status = np.stack([st_ac[:, 0], st_b, st_ac[:, 1]], axis=1).astype(np.int32)
+    return [(G1(ac[2 * j]), G2(b[j]), G1(ac[2 * j + 1])) for j in range(m)], status
+
+
+def verify_batch_compressed(vk, blob, public_inputs, format="ark", engine=None, prepared=False):
+    """verify_batch over encode_proofs' bytes: the proofs are decompressed on the device (two calls), verified, and a proof with any non-zero
+    decode status is False whatever the pairing check of its zeroed points says"""
+    proofs, status = decode_proofs(blob, format, engine=engine)
+    ok = verify_batch(vk, proofs, public_inputs, engine=engine, prepared=prepared)
+    return ok & (status == 0).all(axis=1)
+
+
 def _block_args(vk, proofs, public_inputs):
     proofs = list(proofs); public_inputs = [list(a) for a in public_inputs]
     m, l = len(proofs), len(vk.ic) - 1

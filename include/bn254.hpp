@@ -300,6 +300,34 @@ inline std::vector<Fr> fr_merkle_tree(const std::vector<Fr> &leaves) {
     check(bn254_fr_merkle_tree(nullptr, reinterpret_cast<const bn_fr *>(leaves.data()), log_n, reinterpret_cast<bn_fr *>(nodes.data())));
     return nodes;
 }
+// Compressed encodings: x and one sign bit, 32 bytes per G1 and 64 per G2 point, in the layout `format` (BN254_COMPRESSED_ARK or
+// BN254_COMPRESSED_GNARK: laid out as ark-serialize / gnark-crypto describe; not checked against those libraries here).  compress takes any
+// Jacobian form and writes canonical bytes; decompress returns (x, y, 1) and one status per record (0 ok, 3 flags, 1 range, 4 no such point,
+// 5 not in the subgroup), a rejected record as G::zero()
+inline std::vector<uint8_t> g1_compress(const std::vector<G1> &p, int format = BN254_COMPRESSED_ARK) {
+    std::vector<uint8_t> out(p.size() * BN254_G1_COMPRESSED_BYTES);
+    check(bn254_g1_compress_batch(nullptr, reinterpret_cast<const bn_g1 *>(p.data()), format, out.data(), p.size()));
+    return out;
+}
+inline std::vector<uint8_t> g2_compress(const std::vector<G2> &p, int format = BN254_COMPRESSED_ARK) {
+    std::vector<uint8_t> out(p.size() * BN254_G2_COMPRESSED_BYTES);
+    check(bn254_g2_compress_batch(nullptr, reinterpret_cast<const bn_g2 *>(p.data()), format, out.data(), p.size()));
+    return out;
+}
+inline std::vector<G1> g1_decompress(const std::vector<uint8_t> &records, std::vector<int32_t> &status, int format = BN254_COMPRESSED_ARK) {
+    if (records.size() % BN254_G1_COMPRESSED_BYTES) throw std::invalid_argument("g1_decompress: not whole records of 32 bytes");
+    std::vector<G1> out(records.size() / BN254_G1_COMPRESSED_BYTES);
+    status.assign(out.size(), 0);
+    check(bn254_g1_decompress_batch(nullptr, records.data(), format, reinterpret_cast<bn_g1 *>(out.data()), status.data(), out.size()));
+    return out;
+}
+inline std::vector<G2> g2_decompress(const std::vector<uint8_t> &records, std::vector<int32_t> &status, int format = BN254_COMPRESSED_ARK) {
+    if (records.size() % BN254_G2_COMPRESSED_BYTES) throw std::invalid_argument("g2_decompress: not whole records of 64 bytes");
+    std::vector<G2> out(records.size() / BN254_G2_COMPRESSED_BYTES);
+    status.assign(out.size(), 0);
+    check(bn254_g2_decompress_batch(nullptr, records.data(), format, reinterpret_cast<bn_g2 *>(out.data()), status.data(), out.size()));
+    return out;
+}
 // out[i] = (a[i] == b[i]) as group elements, whatever their Jacobian representations (groups/mod.rs:83-109): nothing is normalized
 inline std::vector<bool> g1_eq(const std::vector<G1> &a, const std::vector<G1> &b) {
     if (a.size() != b.size()) throw std::invalid_argument("g1_eq: length mismatch");

@@ -60,6 +60,9 @@
  *                          bn254_fr_poseidon_permute_batch  the permutation itself on n states of t records;  bn254_fr_merkle_tree  every node of the binary
  *                          tree of hash(left, right) over 2^log_n leaves; none has a counterpart in the reference
  *   bn254_fr_poseidon_batch_dev / bn254_fr_poseidon_permute_batch_dev / bn254_fr_merkle_tree_dev  the same three on device-resident records, asynchronous on the caller's stream
+ *   bn254_g{1,2}_compress_batch / bn254_g{1,2}_decompress_batch  points <-> x and one sign bit (32 / 64 bytes) in the byte layouts ark-serialize and gnark-crypto
+ *                          describe; decompression recovers y by a square root on the device and checks curve and subgroup; no counterpart in the reference
+ *   bn254_g{1,2}_compress_batch_dev / bn254_g{1,2}_decompress_batch_dev  the same four on device-resident records, asynchronous on the caller's stream
  *   bn254_g2_precompute    coeffs[i][0..102) = q[i].to_affine().precompute().coeffs   groups/mod.rs:557-588 (Q != infinity)
  *   bn254_pairing_prepared_batch  out[i] = final_exponentiation(prepared.miller_loop(p[i]))   groups/mod.rs:486-519,768
  *   bn254_gt_mul_batch     out[i] = a[i] * b[i]                                     lib.rs:175-179, fields/fq12.rs:295-307
@@ -103,6 +106,7 @@
      bn254_fr_sumcheck_fold_round serialises on the context in the same way (its mutex for the whole call).
      bn254_fr_mle_quotients serialises on the context in the same way (its mutex for the whole call).
      bn254_fr_poseidon_batch, bn254_fr_poseidon_permute_batch and bn254_fr_merkle_tree serialise on the context in the same way (its mutex for the whole call).
+     bn254_g{1,2}_compress_batch and bn254_g{1,2}_decompress_batch serialise on the context in the same way (its mutex for the whole call).
  *     bn254_pairing_product_batch_prepared_native serialises on the context like them; its handle is immutable and shared freely.
  *     Use one context per thread (or bn254_multi_*) for more overlap;
  *     bn254_ctx_set_option is atomic, but set options before concurrent use: a call in flight may run some
@@ -146,6 +150,8 @@
      bn254_fr_poseidon_batch_dev, bn254_fr_poseidon_permute_batch_dev and bn254_fr_merkle_tree_dev use no scratch and no host operand: the levels of a
      tree are launches in stream order that read what the level before wrote into the caller's `nodes`.  None of the three waits on anything
      or reads anything back, so any number of threads may issue them on one context, each on its own stream and buffers.
+     bn254_g{1,2}_compress_batch_dev and bn254_g{1,2}_decompress_batch_dev use no scratch and no host operand either, wait on nothing and read
+     nothing back (d_status stays on the device): any number of threads may issue them on one context, each on its own stream and buffers.
  */
 #ifndef BN254_HIP_H
 #define BN254_HIP_H
@@ -728,6 +734,34 @@ int bn254_g2_encode_stream(bn254_ctx *ctx, const bn_g2 *p, size_t n, uint8_t *ou
 int bn254_g1_decode_stream(bn254_ctx *ctx, const uint8_t *in, size_t len, bn_g1 *out, int32_t *status, size_t max_points, size_t *count, size_t *consumed);
 int bn254_g2_decode_stream(bn254_ctx *ctx, const uint8_t *in, size_t len, bn_g2 *out, int32_t *status, size_t max_points, size_t *count, size_t *consumed);
 
+/* Compressed encodings: x and one sign bit, 32 bytes for G1 and 64 for G2, one record per lane.  Two byte layouts, laid out as ark-serialize /
+   gnark-crypto describe; not checked against those libraries here.
+     BN254_COMPRESSED_ARK    little-endian integers; G2 is x.c0 then x.c1; the top two bits of the LAST byte are flags: bit 7 = sign(y),
+                             bit 6 = infinity (that one flag and zeros everywhere else); both set is invalid
+     BN254_COMPRESSED_GNARK  big-endian integers; G2 is x.c1 then x.c0; the top two bits of the FIRST byte: 10 = sign(y) 0, 11 = sign(y) 1,
+                             01 = infinity (all other bits zero), 00 = invalid
+   sign(y) = 1 iff y > -y as canonical integers; in Fq2 c1 is compared first and c0 only when c1 == 0.
+   compress takes any Jacobian point, normalises as bn254_g{1,2}_encode_batch does and writes canonical bytes.  decompress recovers y with one
+   (G1) or two (G2) fixed exponentiations by (q - 3) / 4 - the same chain in every lane - and reports status[i] with the numbers of the wire
+   format above, checked in this order: 3 = invalid flags or an infinity record with other bits set, 1 = a coordinate component is not below q,
+   4 = x^3 + b is not a square, 5 = not in the subgroup (G2 only), 0 = ok.  A rejected record decodes to G::zero(); an accepted one to the bytes
+   bn254_g{1,2}_decode_batch gives for the uncompressed record of the same point, so decompress(compress(p)) == decode(encode(p)) and
+   compress(decompress(b)) == b for every accepted b.  An unknown format, a NULL pointer with n > 0 or n above the wire format's limit
+   (0x7fffffff / 129 records) is BN254_E_BAD_ARG before any device is touched; n == 0 succeeds.  The _dev forms take device pointers (d_status
+   too) and enqueue on `stream`: compressed proofs go up once and can feed bn254_pairing_product_batch_dev without coming back. */
+#define BN254_COMPRESSED_ARK 0
+#define BN254_COMPRESSED_GNARK 1
+#define BN254_G1_COMPRESSED_BYTES 32
+#define BN254_G2_COMPRESSED_BYTES 64
+int bn254_g1_compress_batch(bn254_ctx *ctx, const bn_g1 *p, int format, uint8_t *out, size_t n);
+int bn254_g2_compress_batch(bn254_ctx *ctx, const bn_g2 *p, int format, uint8_t *out, size_t n);
+int bn254_g1_decompress_batch(bn254_ctx *ctx, const uint8_t *in, int format, bn_g1 *out, int32_t *status, size_t n);
+int bn254_g2_decompress_batch(bn254_ctx *ctx, const uint8_t *in, int format, bn_g2 *out, int32_t *status, size_t n);
+int bn254_g1_compress_batch_dev(bn254_ctx *ctx, const void *d_p, int format, void *d_out, size_t n, void *stream);
+int bn254_g2_compress_batch_dev(bn254_ctx *ctx, const void *d_p, int format, void *d_out, size_t n, void *stream);
+int bn254_g1_decompress_batch_dev(bn254_ctx *ctx, const void *d_in, int format, void *d_out, void *d_status, size_t n, void *stream);
+int bn254_g2_decompress_batch_dev(bn254_ctx *ctx, const void *d_in, int format, void *d_out, void *d_status, size_t n, void *stream);
+
 /* ---- device-resident entry points (inputs/outputs already in HBM; `stream` is a hipStream_t or NULL) ------------------ */
 /* Same layouts (array of structs) in device memory.  Asynchronous on `stream`; the caller synchronises. */
 int bn254_pairing_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, void *d_out, size_t n, void *stream);
@@ -856,6 +890,7 @@ int bn254_profile_reset(bn254_ctx *ctx);
    of bn254_fr_mle_quotients: "fr_mle_quotients" (one scope per pass, or per sub-launch of it);
    of bn254_fr_sumcheck_fold_round: "fr_sumcheck_fold_round" (the lanes over the indices; the levels over its partial sums run under the round's scope for them);
    of bn254_fr_poseidon_batch, bn254_fr_poseidon_permute_batch and bn254_fr_merkle_tree: "fr_poseidon", "fr_poseidon_permute", "fr_merkle_level" (one scope per level, or per sub-launch of it);
+   of bn254_g{1,2}_compress_batch and bn254_g{1,2}_decompress_batch: "g1_compress", "g2_compress", "g1_decompress", "g2_decompress" (one scope per sub-launch);
    and, of bn254_fr_ntt_batch: "ntt" (the passes), "ntt_table" (the builds of the twiddle tables).
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);

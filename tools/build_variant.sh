@@ -3,6 +3,7 @@
 #   BN254_LIB_PATH=build_variants/lib_<name>.so python bench.py --full --no-cpu-baseline --no-host-api
 # Only the units named in UNITS are recompiled with the flags (default: the lane-pair kernel file, where most experiments are);
 # the other objects come from the last regular build (bn_amd/csrc/build/).
+# (the two chains of the compressed encodings' square roots: UNITS=bn254_wire tools/build_variant.sh sqrt_plain -DBN254_SQRT_WINDOW=0, ... sqrt_window -DBN254_SQRT_WINDOW=1)
 # usage: [UNITS="bn254_kernels_b bn254_kernels_mul"] tools/build_variant.sh NAME [extra hipcc flags...]
 set -e
 cd "$(dirname "$0")/.."
