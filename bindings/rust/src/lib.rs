@@ -30,6 +30,13 @@ extern "C" {
     fn bn254_g2_compress_batch_dev(ctx: *mut c_void, d_p: *const c_void, format: c_int, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_g1_decompress_batch_dev(ctx: *mut c_void, d_in: *const c_void, format: c_int, d_out: *mut c_void, d_status: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_g2_decompress_batch_dev(ctx: *mut c_void, d_in: *const c_void, format: c_int, d_out: *mut c_void, d_status: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    // hash to G1 (RFC 9380: SvdW map, SHA-256 XMD); `dst` is a host pointer in the _dev form too
+    fn bn254_g1_map_to_curve_batch(ctx: *mut c_void, u: *const u8, out: *mut G1, n: usize) -> c_int;
+    fn bn254_g1_hash_to_curve_uniform_batch(ctx: *mut c_void, uniform: *const u8, out: *mut G1, n: usize) -> c_int;
+    fn bn254_g1_hash_to_curve_batch(ctx: *mut c_void, msgs: *const u8, msg_len: usize, dst: *const u8, dst_len: usize, out: *mut G1, n: usize) -> c_int;
+    fn bn254_g1_map_to_curve_batch_dev(ctx: *mut c_void, d_u: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_g1_hash_to_curve_uniform_batch_dev(ctx: *mut c_void, d_uniform: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_g1_hash_to_curve_batch_dev(ctx: *mut c_void, d_msgs: *const c_void, msg_len: usize, dst: *const u8, dst_len: usize, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     // prepared-G2 mode (the crate's internal G2Precomp, src/groups/mod.rs:472-483): 102 line coefficients per Q, then many P against them
     fn bn254_g2_precompute(ctx: *mut c_void, q: *const G2, coeffs: *mut EllCoeffs, n: usize) -> c_int;
     fn bn254_pairing_prepared_batch(ctx: *mut c_void, p: *const G1, coeffs: *const EllCoeffs, shared: c_int, out: *mut Gt, n: usize) -> c_int;
@@ -583,6 +590,36 @@ pub fn g2_decompress_batch(records: &[u8], format: CompressedFormat) -> Result<V
     let (mut out, mut status) = (vec![G2::zero(); n], vec![0i32; n]);
     check(unsafe { bn254_g2_decompress_batch(std::ptr::null_mut(), records.as_ptr(), format.code(), out.as_mut_ptr(), status.as_mut_ptr(), n) })?;
     Ok(out.into_iter().zip(status).map(|(p, s)| if s == 0 { Ok(p) } else { Err(s) }).collect())
+}
+
+// bytes per field element of hash_to_field (L of RFC 9380) and per record of the uniform call: BN254_H2C_FIELD_BYTES, BN254_H2C_UNIFORM_BYTES
+const H2C_FIELD_BYTES: usize = 48;
+const H2C_UNIFORM_BYTES: usize = 96;
+
+/// map_to_curve of RFC 9380 (Shallue-van de Woestijne, Z = 1) on every 48-byte big-endian integer of `u`, taken mod q: (x, y, 1), never infinity.
+/// The map's constants are derived from the RFC's formulas; not checked against gnark-crypto or any other library.
+pub fn g1_map_to_curve_batch(u: &[u8]) -> Result<Vec<G1>, GpuError> {
+    assert_eq!(u.len() % H2C_FIELD_BYTES, 0);
+    let mut out = vec![G1::zero(); u.len() / H2C_FIELD_BYTES];
+    check(unsafe { bn254_g1_map_to_curve_batch(std::ptr::null_mut(), u.as_ptr(), out.as_mut_ptr(), out.len()) })?;
+    Ok(out)
+}
+
+/// hash_to_curve from 96 uniform bytes per record: map(u0) + map(u1), normalised (G1::zero() when the two maps cancel)
+pub fn g1_hash_to_curve_uniform_batch(uniform: &[u8]) -> Result<Vec<G1>, GpuError> {
+    assert_eq!(uniform.len() % H2C_UNIFORM_BYTES, 0);
+    let mut out = vec![G1::zero(); uniform.len() / H2C_UNIFORM_BYTES];
+    check(unsafe { bn254_g1_hash_to_curve_uniform_batch(std::ptr::null_mut(), uniform.as_ptr(), out.as_mut_ptr(), out.len()) })?;
+    Ok(out)
+}
+
+/// hash_to_curve of `n` messages of `msg_len` bytes each, back to back in `msgs` (`msg_len` may be 0), with expand_message_xmd over SHA-256 on
+/// the device; `dst` holds 1 .. 255 bytes
+pub fn g1_hash_to_curve_batch(msgs: &[u8], msg_len: usize, n: usize, dst: &[u8]) -> Result<Vec<G1>, GpuError> {
+    assert_eq!(msgs.len(), n * msg_len);
+    let mut out = vec![G1::zero(); n];
+    check(unsafe { bn254_g1_hash_to_curve_batch(std::ptr::null_mut(), msgs.as_ptr(), msg_len, dst.as_ptr(), dst.len(), out.as_mut_ptr(), n) })?;
+    Ok(out)
 }
 
 /// `q.to_affine().precompute()` for every q (src/groups/mod.rs:557-588; q must not be infinity): 102 coefficients per point, in schedule order

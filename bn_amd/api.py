@@ -126,6 +126,9 @@ class G1(_Point):
         return g1_msm(points, scalars)
     def mul_base(self, scalars):          # [self * k for k in scalars] over ONE cached table of self
         return g1_mul_base(self, scalars)
+    @staticmethod
+    def hash(msg, dst):                   # hash_to_curve of RFC 9380 (SvdW, SHA-256 XMD) under the tag dst
+        return g1_hash_to_curve_batch([msg], dst)[0]
     def to_compressed(self, format="ark"):    # 32 bytes: x and the sign of y
         return g1_compress_batch([self], format)[0]
     @staticmethod
@@ -384,6 +387,34 @@ def g2_decompress_batch(b, format="ark", engine=None):
     rec = _records(b, 64)
     p, st = (engine or default_engine()).g2_decompress_batch(rec, format)
     return [G2(r) for r in p], st
+
+
+def g1_map_to_curve_batch(us, engine=None):
+    """[map_to_curve(u) for u in us], the Shallue-van de Woestijne map of RFC 9380: never the point at infinity.  us: a sequence of integers
+    below 2^384 (taken mod q) or an (n,48) uint8 array of big-endian integers."""
+    if not isinstance(us, np.ndarray):
+        us = list(us)
+        us = np.stack([np.frombuffer(int(u).to_bytes(48, "big"), np.uint8) for u in us]) if us else np.zeros((0, 48), np.uint8)
+    return [G1(r) for r in (engine or default_engine()).g1_map_to_curve_batch(us)]
+
+
+def _hash_to_curve_limbs(msgs, dst, engine):
+    """(n,12) uint64: messages of one length take the device's SHA-256, mixed lengths are expanded with hashlib and take the uniform call"""
+    from . import hash_to_curve as h2c
+    dst = h2c.h2c_dst(dst)
+    if not isinstance(msgs, np.ndarray):
+        msgs = [bytes(m) for m in msgs]
+    e = engine or default_engine()
+    arr = h2c.message_array(msgs)
+    if arr is not None:
+        return e.g1_hash_to_curve_batch(arr, dst)
+    return e.g1_hash_to_curve_uniform_batch(h2c.uniform_bytes(msgs, dst))
+
+
+def g1_hash_to_curve_batch(msgs, dst, engine=None):
+    """[hash_to_curve(m) for m in msgs] (RFC 9380, random-oracle variant: SHA-256 XMD, two SvdW maps, one sum) under the domain separation
+    tag dst (1 .. 255 bytes).  msgs: a sequence of bytes or an (n, msg_len) uint8 array."""
+    return [G1(r) for r in _hash_to_curve_limbs(msgs, dst, engine)]
 
 
 def g1_normalize_batch(points, engine=None):

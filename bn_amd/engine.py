@@ -35,6 +35,17 @@ def compressed_format(fmt):
     return int(fmt)
 
 
+H2C_FIELD_BYTES, H2C_UNIFORM_BYTES, H2C_DST_MAX = 48, 96, 255       # BN254_H2C_* of include/bn254_hip.h
+
+
+def h2c_dst(dst):
+    """the domain separation tag as bytes, 1 .. 255 of them (the RFC's rule for hashing longer tags is not built)"""
+    dst = bytes(dst)
+    if not 0 < len(dst) <= H2C_DST_MAX:
+        raise ValueError(f"a domain separation tag has 1 .. {H2C_DST_MAX} bytes, got {len(dst)}")
+    return dst
+
+
 def _same_len(a, b):
     if a.shape[0] != b.shape[0]:
         raise ValueError(f"operands differ in length: {a.shape[0]} vs {b.shape[0]}")
@@ -723,6 +734,37 @@ class Engine:
 
     def g2_decompress_batch_dev(self, d_in, d_out, d_status, n, format="ark", stream=0):
         _native.check(self._lib.bn254_g2_decompress_batch_dev(self._h, d_in, compressed_format(format), d_out, d_status, n, stream))
+
+    # ---- hash to G1 (RFC 9380: the SvdW map, hash_to_curve from uniform bytes, and behind SHA-256 XMD on the device)
+    def g1_map_to_curve_batch(self, u):
+        """(n,48) uint8 big-endian integers (taken mod q) -> (n,12) uint64 points (x, y, 1)"""
+        u = np.ascontiguousarray(u, np.uint8).reshape(-1, H2C_FIELD_BYTES); out = np.empty((u.shape[0], G1_WORDS), np.uint64)
+        _native.check(self._lib.bn254_g1_map_to_curve_batch(self._h, _p(u), _p(out), u.shape[0])); return out
+
+    def g1_hash_to_curve_uniform_batch(self, uniform):
+        """(n,96) uint8 uniform bytes -> (n,12) uint64: map(u0) + map(u1), normalised"""
+        b = np.ascontiguousarray(uniform, np.uint8).reshape(-1, H2C_UNIFORM_BYTES); out = np.empty((b.shape[0], G1_WORDS), np.uint64)
+        _native.check(self._lib.bn254_g1_hash_to_curve_uniform_batch(self._h, _p(b), _p(out), b.shape[0])); return out
+
+    def g1_hash_to_curve_batch(self, msgs, dst):
+        """(n,msg_len) uint8 messages of one length and a tag of 1 .. 255 bytes -> (n,12) uint64: hash_to_curve with SHA-256 XMD on the device"""
+        msgs = np.ascontiguousarray(msgs, np.uint8)
+        if msgs.ndim != 2:
+            raise ValueError(f"msgs must be an (n, msg_len) uint8 array, got shape {msgs.shape}")
+        dst = h2c_dst(dst); n, ml = msgs.shape
+        out = np.empty((n, G1_WORDS), np.uint64)
+        _native.check(self._lib.bn254_g1_hash_to_curve_batch(self._h, _p(msgs) if msgs.size else None, ml, dst, len(dst), _p(out), n)); return out
+
+    def g1_map_to_curve_batch_dev(self, d_u, d_out, n, stream=0):
+        _native.check(self._lib.bn254_g1_map_to_curve_batch_dev(self._h, d_u, d_out, n, stream))
+
+    def g1_hash_to_curve_uniform_batch_dev(self, d_uniform, d_out, n, stream=0):
+        _native.check(self._lib.bn254_g1_hash_to_curve_uniform_batch_dev(self._h, d_uniform, d_out, n, stream))
+
+    def g1_hash_to_curve_batch_dev(self, d_msgs, msg_len, dst, d_out, n, stream=0):
+        """device pointers for messages and points; `dst` is host bytes (it travels as a kernel argument)"""
+        dst = h2c_dst(dst)
+        _native.check(self._lib.bn254_g1_hash_to_curve_batch_dev(self._h, d_msgs, msg_len, dst, len(dst), d_out, n, stream))
 
     # ---- the crate's variable-length byte stream (infinity = the lone byte 0)
     def _encode_stream(self, fn, p, rec):

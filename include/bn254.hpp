@@ -328,6 +328,28 @@ inline std::vector<G2> g2_decompress(const std::vector<uint8_t> &records, std::v
     check(bn254_g2_decompress_batch(nullptr, records.data(), format, reinterpret_cast<bn_g2 *>(out.data()), status.data(), out.size()));
     return out;
 }
+// Hash to G1 (RFC 9380): the Shallue-van de Woestijne map on 48-byte big-endian integers taken mod q, hash_to_curve = map(u0) + map(u1) from 96
+// uniform bytes per record, and the same behind expand_message_xmd over SHA-256 on the device for n messages of one length.  The map's
+// constants are derived from the RFC's formulas; not checked against gnark-crypto or any other library.  Results are (x, y, 1), or G::zero()
+// where the two maps of a hash cancel
+inline std::vector<G1> g1_map_to_curve(const std::vector<uint8_t> &u) {
+    if (u.size() % BN254_H2C_FIELD_BYTES) throw std::invalid_argument("g1_map_to_curve: not whole elements of 48 bytes");
+    std::vector<G1> out(u.size() / BN254_H2C_FIELD_BYTES);
+    check(bn254_g1_map_to_curve_batch(nullptr, u.data(), reinterpret_cast<bn_g1 *>(out.data()), out.size()));
+    return out;
+}
+inline std::vector<G1> g1_hash_to_curve_uniform(const std::vector<uint8_t> &uniform) {
+    if (uniform.size() % BN254_H2C_UNIFORM_BYTES) throw std::invalid_argument("g1_hash_to_curve_uniform: not whole records of 96 bytes");
+    std::vector<G1> out(uniform.size() / BN254_H2C_UNIFORM_BYTES);
+    check(bn254_g1_hash_to_curve_uniform_batch(nullptr, uniform.data(), reinterpret_cast<bn_g1 *>(out.data()), out.size()));
+    return out;
+}
+inline std::vector<G1> g1_hash_to_curve(const std::vector<uint8_t> &msgs, size_t msg_len, size_t n, const std::vector<uint8_t> &dst) {
+    if (msgs.size() != n * msg_len) throw std::invalid_argument("g1_hash_to_curve: msgs is not n messages of msg_len bytes");
+    std::vector<G1> out(n);
+    check(bn254_g1_hash_to_curve_batch(nullptr, msgs.data(), msg_len, dst.data(), dst.size(), reinterpret_cast<bn_g1 *>(out.data()), n));
+    return out;
+}
 // out[i] = (a[i] == b[i]) as group elements, whatever their Jacobian representations (groups/mod.rs:83-109): nothing is normalized
 inline std::vector<bool> g1_eq(const std::vector<G1> &a, const std::vector<G1> &b) {
     if (a.size() != b.size()) throw std::invalid_argument("g1_eq: length mismatch");

@@ -63,6 +63,12 @@
  *   bn254_g{1,2}_compress_batch / bn254_g{1,2}_decompress_batch  points <-> x and one sign bit (32 / 64 bytes) in the byte layouts ark-serialize and gnark-crypto
  *                          describe; decompression recovers y by a square root on the device and checks curve and subgroup; no counterpart in the reference
  *   bn254_g{1,2}_compress_batch_dev / bn254_g{1,2}_decompress_batch_dev  the same four on device-resident records, asynchronous on the caller's stream
+ *   bn254_g1_map_to_curve_batch  out[i] = map_to_curve(u[i] mod q), the Shallue-van de Woestijne map of RFC 9380 for y^2 = x^3 + 3 (Z = 1);
+ *                          bn254_g1_hash_to_curve_uniform_batch  out[i] = map(u0) + map(u1) over 96 uniform bytes (hash_to_field with L = 48), normalised;
+ *                          bn254_g1_hash_to_curve_batch  the same behind expand_message_xmd over SHA-256 on the device, one message per lane; none has a
+ *                          counterpart in the reference
+ *   bn254_g1_map_to_curve_batch_dev / bn254_g1_hash_to_curve_uniform_batch_dev / bn254_g1_hash_to_curve_batch_dev  the same three on device-resident records,
+ *                          asynchronous on the caller's stream
  *   bn254_g2_precompute    coeffs[i][0..102) = q[i].to_affine().precompute().coeffs   groups/mod.rs:557-588 (Q != infinity)
  *   bn254_pairing_prepared_batch  out[i] = final_exponentiation(prepared.miller_loop(p[i]))   groups/mod.rs:486-519,768
  *   bn254_gt_mul_batch     out[i] = a[i] * b[i]                                     lib.rs:175-179, fields/fq12.rs:295-307
@@ -107,6 +113,8 @@
      bn254_fr_mle_quotients serialises on the context in the same way (its mutex for the whole call).
      bn254_fr_poseidon_batch, bn254_fr_poseidon_permute_batch and bn254_fr_merkle_tree serialise on the context in the same way (its mutex for the whole call).
      bn254_g{1,2}_compress_batch and bn254_g{1,2}_decompress_batch serialise on the context in the same way (its mutex for the whole call).
+     bn254_g1_map_to_curve_batch, bn254_g1_hash_to_curve_uniform_batch and bn254_g1_hash_to_curve_batch serialise on the context in the same way (its
+     mutex for the whole call).
  *     bn254_pairing_product_batch_prepared_native serialises on the context like them; its handle is immutable and shared freely.
  *     Use one context per thread (or bn254_multi_*) for more overlap;
  *     bn254_ctx_set_option is atomic, but set options before concurrent use: a call in flight may run some
@@ -152,6 +160,10 @@
      or reads anything back, so any number of threads may issue them on one context, each on its own stream and buffers.
      bn254_g{1,2}_compress_batch_dev and bn254_g{1,2}_decompress_batch_dev use no scratch and no host operand either, wait on nothing and read
      nothing back (d_status stays on the device): any number of threads may issue them on one context, each on its own stream and buffers.
+     bn254_g1_map_to_curve_batch_dev, bn254_g1_hash_to_curve_uniform_batch_dev and bn254_g1_hash_to_curve_batch_dev use no scratch either: one launch
+     per sub-launch does the field reduction, both maps, the sum and the normalisation.  bn254_g1_hash_to_curve_batch_dev reads its HOST `dst`
+     before it returns (the tag travels as a kernel argument: nothing is uploaded).  None of the three waits on anything or reads anything
+     back, so any number of threads may issue them on one context, each on its own stream and buffers.
  */
 #ifndef BN254_HIP_H
 #define BN254_HIP_H
@@ -762,6 +774,33 @@ int bn254_g2_compress_batch_dev(bn254_ctx *ctx, const void *d_p, int format, voi
 int bn254_g1_decompress_batch_dev(bn254_ctx *ctx, const void *d_in, int format, void *d_out, void *d_status, size_t n, void *stream);
 int bn254_g2_decompress_batch_dev(bn254_ctx *ctx, const void *d_in, int format, void *d_out, void *d_status, size_t n, void *stream);
 
+/* Hash to G1 (RFC 9380), one record per lane.  The constants below were derived from the RFC's formulas (Z by its find_z_svdw search); they are
+   not checked against gnark-crypto or any other library.
+     map_to_curve   the Shallue-van de Woestijne map with Z = 1, c1 = g(Z) = 4, c2 = -Z / 2, c3 = sqrt(-g(Z) 3 Z^2) with sgn0(c3) = 0,
+                    c4 = -4 g(Z) / (3 Z^2), computed in the RFC's order; sgn0(a) is the canonical integer of a mod 2 (not the y > -y rule of the
+                    compressed encodings), inv0(0) = 0, zero counts as a square.  u[i] is 48 big-endian bytes, any value below 2^384, taken
+                    mod q.  out[i] = (x, y, 1) in canonical Montgomery words; the map never gives the point at infinity.
+     uniform        record i is 96 bytes: u0 = bytes [0, 48), u1 = bytes [48, 96) (hash_to_field with L = 48).  out[i] = map(u0) + map(u1) by the
+                    complete addition - equal points double - normalised: (x, y, 1), or G::zero() = (0, 1, 0) when the two maps cancel.
+                    The cofactor is 1: nothing is cleared.
+     messages       n messages of msg_len bytes each, back to back; record i is hash_to_curve(msg i) with the 96 uniform bytes from
+                    expand_message_xmd(msg, dst, 96) over SHA-256, computed on the device.  msg_len == 0 is allowed (msgs may then be NULL).
+                    Messages of different lengths go through the uniform call after a host-side expansion.  `dst` is a HOST pointer in both
+                    forms (1 .. BN254_H2C_DST_MAX bytes; the RFC's rule for hashing longer tags is not built).
+   A NULL pointer with work to do, dst_len == 0 or dst_len > BN254_H2C_DST_MAX, msg_len > 2^20, n > 2^40 or n * msg_len > 2^40 is
+   BN254_E_BAD_ARG before any device is touched; n == 0 succeeds.  Calls run as sub-launches of at most 2^22 records.  The _dev forms take
+   device pointers (dst excepted) and enqueue on `stream`: the points can feed bn254_g1_mul_batch_dev or bn254_pairing_product_batch_dev without
+   coming back.  Threading: see above. */
+#define BN254_H2C_FIELD_BYTES 48
+#define BN254_H2C_UNIFORM_BYTES 96
+#define BN254_H2C_DST_MAX 255
+int bn254_g1_map_to_curve_batch(bn254_ctx *ctx, const uint8_t *u, bn_g1 *out, size_t n);
+int bn254_g1_hash_to_curve_uniform_batch(bn254_ctx *ctx, const uint8_t *uniform, bn_g1 *out, size_t n);
+int bn254_g1_hash_to_curve_batch(bn254_ctx *ctx, const uint8_t *msgs, size_t msg_len, const uint8_t *dst, size_t dst_len, bn_g1 *out, size_t n);
+int bn254_g1_map_to_curve_batch_dev(bn254_ctx *ctx, const void *d_u, void *d_out, size_t n, void *stream);
+int bn254_g1_hash_to_curve_uniform_batch_dev(bn254_ctx *ctx, const void *d_uniform, void *d_out, size_t n, void *stream);
+int bn254_g1_hash_to_curve_batch_dev(bn254_ctx *ctx, const void *d_msgs, size_t msg_len, const uint8_t *dst, size_t dst_len, void *d_out, size_t n, void *stream);
+
 /* ---- device-resident entry points (inputs/outputs already in HBM; `stream` is a hipStream_t or NULL) ------------------ */
 /* Same layouts (array of structs) in device memory.  Asynchronous on `stream`; the caller synchronises. */
 int bn254_pairing_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, void *d_out, size_t n, void *stream);
@@ -891,6 +930,7 @@ int bn254_profile_reset(bn254_ctx *ctx);
    of bn254_fr_sumcheck_fold_round: "fr_sumcheck_fold_round" (the lanes over the indices; the levels over its partial sums run under the round's scope for them);
    of bn254_fr_poseidon_batch, bn254_fr_poseidon_permute_batch and bn254_fr_merkle_tree: "fr_poseidon", "fr_poseidon_permute", "fr_merkle_level" (one scope per level, or per sub-launch of it);
    of bn254_g{1,2}_compress_batch and bn254_g{1,2}_decompress_batch: "g1_compress", "g2_compress", "g1_decompress", "g2_decompress" (one scope per sub-launch);
+   of bn254_g1_map_to_curve_batch, bn254_g1_hash_to_curve_uniform_batch and bn254_g1_hash_to_curve_batch: "g1_map_to_curve", "g1_hash_to_curve", "g1_hash_to_curve_msg" (one scope per sub-launch);
    and, of bn254_fr_ntt_batch: "ntt" (the passes), "ntt_table" (the builds of the twiddle tables).
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);
