@@ -1,11 +1,11 @@
 // The scalar field on the device (include/bn254_hip.h bn254_fr_{add,mul,inverse,pow,interpret}_batch and their _dev twins): the kernels -
-// instances of bn254_fr_decode_k<Op> like the other integer kernels, one element (inverse: one run of elements) per lane over the bodies of
-// fr_ops.hpp -, their sub-launches, and the ten entry points.
+// Ops of lane_launch.hpp's bn254_fr_decode_k like the other integer kernels, one element (inverse: one run of elements) per lane over the
+// bodies of fr_ops.hpp -, their sub-launches, and the ten entry points.
 #include <algorithm>
-#include <atomic>
 
 #include "fr_ops.hpp"
 #include "host_ctx.hpp"
+#include "lane_launch.hpp"
 
 using namespace bn254;
 
@@ -48,73 +48,52 @@ struct FrInverseOp {
         fr_inverse_body<FR_POW_WINDOW>(a, out, ok, prefix, n, blockIdx.x * FR_BLOCK + threadIdx.x, lanes, K);
     }
 };
-template <class Op>
-__global__ void __launch_bounds__(FR_BLOCK) bn254_fr_decode_k(Op op) { op(); }
-
-template <class Op>
-int fr_launch(const Op &op, size_t lanes, hipStream_t s) {
-    hipLaunchKernelGGL(bn254_fr_decode_k<Op>, dim3((unsigned)((lanes + FR_BLOCK - 1) / FR_BLOCK)), dim3(FR_BLOCK), 0, s, op);
-    return (int)hipGetLastError();
-}
-
-// tests and tools/time_fr.py only: the sub-launch size (0 = BN_LAUNCH_MAX), and the variants the sweep times (0 = the shipped constants)
-std::atomic<size_t> g_fr_launch_max;
-std::atomic<unsigned> g_fr_inverse_run, g_fr_pow_window;
-size_t fr_step() { const size_t set = g_fr_launch_max.load(std::memory_order_relaxed); return set ? set : BN_LAUNCH_MAX; }
-unsigned fr_run() { const unsigned set = g_fr_inverse_run.load(std::memory_order_relaxed); return set ? set : FR_INV_RUN; }
-unsigned fr_window() { const unsigned set = g_fr_pow_window.load(std::memory_order_relaxed); return set ? set : (unsigned)FR_POW_WINDOW; }
+// tests and tools/time_fr.py only: the sub-launch size, and the variants the sweep times
+BnLaunchMax g_fr_launch_max;
+BnOverride<unsigned> g_fr_inverse_run, g_fr_pow_window;
 
 enum FrKind { FR_ADD, FR_SUB, FR_MUL, FR_POW };
 const char *const FR_SCOPE[] = {"fr_add", "fr_add", "fr_mul", "fr_pow"};
-// out[i] = a[i] op b[i]: sub-launches of at most fr_step() elements
+// out[i] = a[i] op b[i]: sub-launches of at most g_fr_launch_max.step() elements
 int fr_launch_binary(bn254_ctx *c, FrKind kind, const void *d_a, const void *d_b, void *d_out, size_t n, hipStream_t s) {
-    const unsigned wb = fr_window();
-    return bn_for_parts(n, fr_step(), [&](size_t lo, size_t cnt) -> int {
+    const unsigned wb = g_fr_pow_window.get(FR_POW_WINDOW);
+    return bn_for_parts(n, g_fr_launch_max.step(), [&](size_t lo, size_t cnt) -> int {
         const uint32_t *a = (const uint32_t *)d_a + 8 * lo, *b = (const uint32_t *)d_b + 8 * lo;
         uint32_t *out = (uint32_t *)d_out + 8 * lo;
         BnScope sc(c, s, FR_SCOPE[kind]);
         switch (kind) {
-        case FR_ADD: case FR_SUB: return fr_launch(FrAddOp{a, b, out, (uint32_t)cnt, kind == FR_SUB}, cnt, s);
-        case FR_MUL: return fr_launch(FrMulOp{a, b, out, (uint32_t)cnt}, cnt, s);
+        case FR_ADD: case FR_SUB: return bn_lane_launch<FR_BLOCK>(FrAddOp{a, b, out, (uint32_t)cnt, kind == FR_SUB}, cnt, s);
+        case FR_MUL: return bn_lane_launch<FR_BLOCK>(FrMulOp{a, b, out, (uint32_t)cnt}, cnt, s);
         default:
-            if (wb == 1) return fr_launch(FrPowOp<1>{a, b, out, (uint32_t)cnt}, cnt, s);
-            if (wb == 4) return fr_launch(FrPowOp<4>{a, b, out, (uint32_t)cnt}, cnt, s);
-            return fr_launch(FrPowOp<2>{a, b, out, (uint32_t)cnt}, cnt, s);
+            if (wb == 1) return bn_lane_launch<FR_BLOCK>(FrPowOp<1>{a, b, out, (uint32_t)cnt}, cnt, s);
+            if (wb == 4) return bn_lane_launch<FR_BLOCK>(FrPowOp<4>{a, b, out, (uint32_t)cnt}, cnt, s);
+            return bn_lane_launch<FR_BLOCK>(FrPowOp<2>{a, b, out, (uint32_t)cnt}, cnt, s);
         }
     });
 }
 int fr_launch_interpret(bn254_ctx *c, const void *d_in, void *d_out, size_t n, hipStream_t s) {
-    return bn_for_parts(n, fr_step(), [&](size_t lo, size_t cnt) -> int {
+    return bn_for_parts(n, g_fr_launch_max.step(), [&](size_t lo, size_t cnt) -> int {
         BnScope sc(c, s, "fr_interpret");
-        return fr_launch(FrInterpretOp{(const uint8_t *)d_in + 64 * lo, (uint32_t *)d_out + 8 * lo, (uint32_t)cnt}, cnt, s);
+        return bn_lane_launch<FR_BLOCK>(FrInterpretOp{(const uint8_t *)d_in + 64 * lo, (uint32_t *)d_out + 8 * lo, (uint32_t)cnt}, cnt, s);
     });
 }
 // scratch guard held by the caller: the prefix products of one sub-launch (K * lanes records of 32 bytes) are context-owned
 int fr_launch_inverse(bn254_ctx *c, const void *d_a, void *d_out, void *d_ok, size_t n, hipStream_t s) {
-    const size_t step = fr_step(), K = fr_run(), most = std::min(n, step);
+    const size_t step = g_fr_launch_max.step(), K = g_fr_inverse_run.get(FR_INV_RUN), most = std::min(n, step);
     int rc = c->fr_prefix.reserve(((most + K - 1) / K) * K * sizeof(bn_fr)); if (rc) return rc;
     return bn_for_parts(n, step, [&](size_t lo, size_t cnt) -> int {
         const size_t lanes = (cnt + K - 1) / K;
         BnScope sc(c, s, "fr_inverse");
-        return fr_launch(FrInverseOp{(const uint32_t *)d_a + 8 * lo, (uint32_t *)d_out + 8 * lo, d_ok ? (int32_t *)d_ok + lo : nullptr, (uint32_t *)c->fr_prefix.p,
+        return bn_lane_launch<FR_BLOCK>(FrInverseOp{(const uint32_t *)d_a + 8 * lo, (uint32_t *)d_out + 8 * lo, d_ok ? (int32_t *)d_ok + lo : nullptr, (uint32_t *)c->fr_prefix.p,
                                      (uint32_t)cnt, (uint32_t)lanes, (uint32_t)K}, lanes, s);
     });
 }
 
-// the _dev prologue after the argument checks: context, device, then the launches (nothing waits, nothing is read back)
-template <class Fn>
-int fr_entry(bn254_ctx *&ctx, void *stream, bool scratch, Fn fn) {
-    int rc = bn_get_ctx(ctx); if (rc) return rc;
-    BnDev d(ctx, stream); if (!d.go) return d.rc;
-    if (!scratch) return bn_no_throw([&] { return fn(d.s); });
-    BnScratchGuard g(ctx, d.s); if (g.rc) return g.rc;
-    return bn_no_throw([&] { return fn(d.s); });
-}
 // order of the checks: empty batch, arguments, then context and device
 int fr_binary_dev(bn254_ctx *ctx, FrKind kind, const void *d_a, const void *d_b, void *d_out, size_t n, void *stream) {
     if (n == 0) return BN254_OK;
     if (n > BN_N_MAX || !d_a || !d_b || !d_out) return BN254_E_BAD_ARG;            // before any device lookup
-    return fr_entry(ctx, stream, false, [&](hipStream_t s) { return fr_launch_binary(ctx, kind, d_a, d_b, d_out, n, s); });
+    return bn_dev_entry(ctx, stream, false, [&](hipStream_t s) { return fr_launch_binary(ctx, kind, d_a, d_b, d_out, n, s); });
 }
 int fr_binary_host(bn254_ctx *ctx, FrKind kind, const bn_fr *a, const bn_fr *b, bn_fr *out, size_t n) {
     if (n == 0) return BN254_OK;
@@ -134,12 +113,12 @@ int bn254_fr_pow_batch_dev(bn254_ctx *c, const void *a, const void *e, void *o, 
 int bn254_fr_inverse_batch_dev(bn254_ctx *ctx, const void *d_a, void *d_out, void *d_ok, size_t n, void *stream) {
     if (n == 0) return BN254_OK;
     if (n > BN_N_MAX || !d_a || !d_out) return BN254_E_BAD_ARG;                    // before any device lookup
-    return fr_entry(ctx, stream, true, [&](hipStream_t s) { return fr_launch_inverse(ctx, d_a, d_out, d_ok, n, s); });
+    return bn_dev_entry(ctx, stream, true, [&](hipStream_t s) { return fr_launch_inverse(ctx, d_a, d_out, d_ok, n, s); });
 }
 int bn254_fr_interpret_batch_dev(bn254_ctx *ctx, const void *d_in, void *d_out, size_t n, void *stream) {
     if (n == 0) return BN254_OK;
     if (n > BN_N_MAX || !d_in || !d_out) return BN254_E_BAD_ARG;                   // before any device lookup
-    return fr_entry(ctx, stream, false, [&](hipStream_t s) { return fr_launch_interpret(ctx, d_in, d_out, n, s); });
+    return bn_dev_entry(ctx, stream, false, [&](hipStream_t s) { return fr_launch_interpret(ctx, d_in, d_out, n, s); });
 }
 
 // ---------------------------------------------------------------------------------------------- host-buffer API (BnHost: the context's mutex for the call)
@@ -166,20 +145,8 @@ int bn254_fr_interpret_batch(bn254_ctx *ctx, const uint8_t *in, bn_fr *out, size
 // for the sweep only - process-wide overrides of the run length and the width (0 restores the shipped one; same bytes whatever is set)
 unsigned bn254_fr_inverse_run(void) { return FR_INV_RUN; }
 unsigned bn254_fr_pow_window(void) { return FR_POW_WINDOW; }
-int bn254_fr_set_launch_max(size_t elements) {
-    if (elements > BN_LAUNCH_MAX) return BN254_E_BAD_ARG;
-    g_fr_launch_max.store(elements, std::memory_order_relaxed);
-    return BN254_OK;
-}
-int bn254_fr_set_inverse_run(unsigned K) {
-    if (K > 64) return BN254_E_BAD_ARG;
-    g_fr_inverse_run.store(K, std::memory_order_relaxed);
-    return BN254_OK;
-}
-int bn254_fr_set_pow_window(unsigned bits) {
-    if (bits != 0 && bits != 1 && bits != 2 && bits != 4) return BN254_E_BAD_ARG;
-    g_fr_pow_window.store(bits, std::memory_order_relaxed);
-    return BN254_OK;
-}
+int bn254_fr_set_launch_max(size_t elements) { return g_fr_launch_max.set(elements); }
+int bn254_fr_set_inverse_run(unsigned K) { return K > 64 ? BN254_E_BAD_ARG : g_fr_inverse_run.set(K); }
+int bn254_fr_set_pow_window(unsigned bits) { return bits != 0 && bits != 1 && bits != 2 && bits != 4 ? BN254_E_BAD_ARG : g_fr_pow_window.set(bits); }
 
 }  // extern "C"

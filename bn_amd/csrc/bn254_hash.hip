@@ -1,13 +1,13 @@
 // Hash to G1 on the device (include/bn254_hip.h bn254_g1_map_to_curve_batch, bn254_g1_hash_to_curve_uniform_batch, bn254_g1_hash_to_curve_batch
-// and their _dev twins): the kernels - instances of bn254_fr_decode_k<Op> like the other integer kernels, one lane of a body of hash_ops.hpp
-// each - and the six entry points.  One launch per call (and per sub-launch of a large one): a lane reduces its field elements, runs both
+// and their _dev twins): the kernels - Ops of lane_launch.hpp's bn254_fr_decode_k like the other integer kernels, one lane of a body of
+// hash_ops.hpp each - and the six entry points.  One launch per call (and per sub-launch of a large one): a lane reduces its field elements, runs both
 // maps, adds and normalises, so the _dev calls use no scratch and wait on nothing.  Compiled like every unit (bn254_hip.hip: the flags).
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <cstring>
 
 #include "hash_ops.hpp"
 #include "host_ctx.hpp"
+#include "lane_launch.hpp"
 
 using namespace bn254;
 
@@ -38,18 +38,8 @@ struct G1HashMsgOp {
         if (i < n) h2c_hash_msg_body<>(msgs, (size_t)msg_len, dst_prime, dst_prime_len, out, lo + i);
     }
 };
-template <class Op>
-__global__ void __launch_bounds__(H2C_BLOCK) bn254_fr_decode_k(Op op) { op(); }
 
-template <class Op>
-int h2c_launch(const Op &op, size_t lanes, hipStream_t s) {
-    hipLaunchKernelGGL(bn254_fr_decode_k<Op>, dim3((unsigned)((lanes + H2C_BLOCK - 1) / H2C_BLOCK)), dim3(H2C_BLOCK), 0, s, op);
-    return (int)hipGetLastError();
-}
-
-// tests only: the sub-launch size (0 = BN_LAUNCH_MAX)
-std::atomic<size_t> g_hash_launch_max;
-size_t hash_step() { const size_t set = g_hash_launch_max.load(std::memory_order_relaxed); return set ? set : BN_LAUNCH_MAX; }
+BnLaunchMax g_hash_launch_max;      // tests only: the sub-launch size
 
 enum { H2C_MAP = 0, H2C_UNIFORM = 1, H2C_MSG = 2 };
 // arguments only: nothing here touches a device.  1 = nothing to do
@@ -67,20 +57,18 @@ int hash_run(bn254_ctx *ctx, int which, const void *d_in, size_t msg_len, const 
         memcpy(m.dst_prime, dst, dst_len);
         m.dst_prime[dst_len] = (uint8_t)dst_len;
     }
-    return bn_for_parts(n, hash_step(), [&](size_t lo, size_t cnt) -> int {
+    return bn_for_parts(n, g_hash_launch_max.step(), [&](size_t lo, size_t cnt) -> int {
         BnScope sc(ctx, s, which == H2C_MAP ? "g1_map_to_curve" : which == H2C_UNIFORM ? "g1_hash_to_curve" : "g1_hash_to_curve_msg");
-        if (which == H2C_MAP) return h2c_launch(G1MapToCurveOp{(const uint8_t *)d_in, (uint32_t *)d_out, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
-        if (which == H2C_UNIFORM) return h2c_launch(G1HashUniformOp{(const uint8_t *)d_in, (uint32_t *)d_out, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
+        if (which == H2C_MAP) return bn_lane_launch<H2C_BLOCK>(G1MapToCurveOp{(const uint8_t *)d_in, (uint32_t *)d_out, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
+        if (which == H2C_UNIFORM) return bn_lane_launch<H2C_BLOCK>(G1HashUniformOp{(const uint8_t *)d_in, (uint32_t *)d_out, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
         m.lo = lo; m.n = (uint32_t)cnt;
-        return h2c_launch(m, cnt, s);
+        return bn_lane_launch<H2C_BLOCK>(m, cnt, s);
     });
 }
 // order of the checks: arguments, then context and device; nothing waits, nothing is read back
 int hash_dev(bn254_ctx *ctx, int which, const void *d_in, size_t msg_len, const uint8_t *dst, size_t dst_len, void *d_out, size_t n, void *stream) {
     int rc = hash_check(which, d_in, msg_len, dst, dst_len, d_out, n); if (rc) return rc == 1 ? BN254_OK : rc;
-    if ((rc = bn_get_ctx(ctx))) return rc;
-    BnDev d(ctx, stream); if (!d.go) return d.rc;
-    return bn_no_throw([&] { return hash_run(ctx, which, d_in, msg_len, dst, dst_len, d_out, n, d.s); });
+    return bn_dev_entry(ctx, stream, false, [&](hipStream_t s) { return hash_run(ctx, which, d_in, msg_len, dst, dst_len, d_out, n, s); });
 }
 int hash_host(bn254_ctx *ctx, int which, const void *in, size_t msg_len, const uint8_t *dst, size_t dst_len, bn_g1 *out, size_t n) {
     int rc = hash_check(which, in, msg_len, dst, dst_len, out, n); if (rc) return rc == 1 ? BN254_OK : rc;
@@ -108,11 +96,7 @@ int bn254_g1_hash_to_curve_batch_dev(bn254_ctx *ctx, const void *d_msgs, size_t 
 
 // internal (not in the header; tests and tools/time_hash.py): an override of the sub-launch size of the six calls above (0 restores
 // BN_LAUNCH_MAX) so that a test reaches the seam between two sub-launches with a handful of records, and which form of inv0 was built
-int bn254_hash_set_launch_max(size_t lanes) {
-    if (lanes > BN_LAUNCH_MAX) return BN254_E_BAD_ARG;
-    g_hash_launch_max.store(lanes, std::memory_order_relaxed);
-    return BN254_OK;
-}
+int bn254_hash_set_launch_max(size_t lanes) { return g_hash_launch_max.set(lanes); }
 int bn254_hash_inv0_form(void) { return BN254_H2C_INV0; }
 
 }  // extern "C"

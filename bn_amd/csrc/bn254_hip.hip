@@ -12,6 +12,7 @@
 #include <cstring>
 
 #include "host_ctx.hpp"
+#include "lane_launch.hpp"      // BN_LAUNCH_MAX
 
 using namespace bn254;
 
@@ -61,6 +62,21 @@ BnScratchGuard::~BnScratchGuard() {
     if (!c->scratch_ev) hipEventCreateWithFlags(&c->scratch_ev, hipEventDisableTiming);
     if (c->scratch_ev && hipEventRecord(c->scratch_ev, s) == hipSuccess) { c->scratch_used = true; c->scratch_stream = s; }
     c->scratch_mu.unlock();
+}
+
+// The pinned buffer is rewritten while its previous copy may be in flight on another stream: wait for that copy's event first, record
+// the new copy's event last.
+int bn_plan_upload(bn254_ctx *c, const void *a, size_t a_bytes, const void *b, size_t b_bytes, hipStream_t s) {
+    int rc;
+    const size_t bytes = a_bytes + b_bytes;
+    if (c->seg_plan_ev) HIP_TRY(hipEventSynchronize(c->seg_plan_ev));
+    else HIP_TRY(hipEventCreateWithFlags(&c->seg_plan_ev, hipEventDisableTiming));
+    if ((rc = c->seg_plan_host.reserve(bytes)) || (rc = c->seg_plan.reserve(bytes))) return rc;
+    if (a_bytes) memcpy(c->seg_plan_host.p, a, a_bytes);
+    if (b_bytes) memcpy((char *)c->seg_plan_host.p + a_bytes, b, b_bytes);
+    HIP_TRY(hipMemcpyAsync(c->seg_plan.p, c->seg_plan_host.p, bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(c->seg_plan_ev, s));
+    return BN254_OK;
 }
 
 int bn_get_ctx(bn254_ctx *&ctx) {

@@ -35,6 +35,7 @@ __device__ __forceinline__ void bn_g1_tail_policy(int step, int total) {
 }
 #define BN_G1_HOOK(step, total) bn_g1_tail_policy(step, total)
 #include "group_ops.hpp"       // the per-lane bodies of everything below but the chains of curve.hpp: shared with the host simulation
+#include "lane_launch.hpp"     // the shell and the launchers of the integer kernels
 
 using namespace bn254;
 
@@ -156,9 +157,9 @@ __global__ void __launch_bounds__(BLOCK) bn254_g2_add_M(const BnSegPiece *pieces
     if (lp.live) PointIo<G2F>()(r, pc.dst);
 }
 
-// ---- the integer kernels of the bucket method (group_ops.hpp describes the method and holds its point bodies), instances of the name
-// bn254_fr_decode_k beside the wire decoder of bn254_hip.hip (they take the canonical integer of a scalar apart); they need a wave or a
-// workgroup, so they have no twin in the host simulation.
+// ---- the integer kernels of the bucket method (group_ops.hpp describes the method and holds its point bodies), Ops of lane_launch.hpp's
+// bn254_fr_decode_k with workgroups of 256 lanes (they take the canonical integer of a scalar apart); they need a wave or a workgroup, so they
+// have no twin in the host simulation.
 // COUNT: counts[key] += 1 for every non-zero digit of k[0..n); SCATTER: the same walk, (index, key) written at cursor[key]++ (the scanned counts).
 // When every active lane of a wave holds the same digit (equal scalars: the skew case) one lane adds for all of them; large groups of
 // equal digits inside a wave are served the same way.
@@ -231,12 +232,10 @@ struct MsmScanOp {
         for (uint32_t j = 0; j < 4; ++j) { if (4 * t + j < len) v[4 * t + j] = run; run += x[j]; }
     }
 };
-template <class Op>
-__global__ void __launch_bounds__(256) bn254_fr_decode_k(Op op) { op(); }
 
 // The table build of the fixed-base multiplication after the shipped normalising kernel (bn254_g{1,2}_mul_M over the tiled base and the
 // host-known scalars d * 2^(c w)): tile - record j of `out` = the one point at `src`; repack - thread t turns component t % comps of the
-// normalised point t / comps into its 80-byte record.  Instances of bn254_fr_decode_k like the other integer kernels of this unit.
+// normalised point t / comps into its 80-byte record.  Ops of bn254_fr_decode_k like the other integer kernels of this unit.
 struct BaseTileOp {
     const uint32_t *src; uint32_t *out; uint32_t words, n;
     __device__ __forceinline__ void operator()() const {
@@ -313,8 +312,7 @@ int bn254_launch_msm_fold_M(int g, const void *pieces, size_t count, hipStream_t
 // digits: scatter == 0 counts the terms per key into `counts` (zeroed by the caller); scatter != 0 writes (index, key) at the scanned counts
 int bn254_launch_msm_digits_M(const void *k, size_t n, unsigned c, unsigned W, void *counts, void *idx, void *keys, int scatter, hipStream_t s) {
     const MsmDigitsOp op = {(const uint32_t *)k, (uint32_t)n, c, W, (uint32_t *)counts, (uint32_t *)idx, (uint32_t *)keys, scatter};
-    hipLaunchKernelGGL(bn254_fr_decode_k<MsmDigitsOp>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, op);
-    return (int)hipGetLastError();
+    return bn_lane_launch<256>(op, n, s);
 }
 // counts[0..total) -> their exclusive scan in place, the grand total to *n0; total <= 2^20, `tiles`: 1024 words of scratch
 int bn254_launch_msm_scan_M(void *counts, size_t total, void *tiles, void *n0, hipStream_t s) {
@@ -322,9 +320,9 @@ int bn254_launch_msm_scan_M(void *counts, size_t total, void *tiles, void *n0, h
     if (blocks == 0 || blocks > MSM_TILE) return (int)hipErrorInvalidValue;
     for (int mode = 0; mode < 3; ++mode) {
         const MsmScanOp op = {(uint32_t *)counts, (uint32_t)total, (uint32_t *)tiles, (uint32_t *)n0, mode};
-        hipLaunchKernelGGL(bn254_fr_decode_k<MsmScanOp>, dim3(mode == 1 ? 1u : blocks), dim3(256), 0, s, op);
+        if (int rc = bn_block_launch<256>(op, mode == 1 ? 1u : blocks, 0, s)) return rc;
     }
-    return (int)hipGetLastError();
+    return (int)hipSuccess;
 }
 unsigned bn254_msm_piece_M(void) { return MSM_PIECE; }
 // one accumulation level over `lanes` lanes (G2: lane pairs); idx != NULL only at level 0
@@ -351,8 +349,7 @@ int bn254_launch_mul_base_M(int g, const void *table, unsigned c, const void *k,
 int bn254_launch_mul_base_tile_M(int g, const void *d_base, void *d_out, size_t n, hipStream_t s) {
     const uint32_t words = g == 1 ? PointIo<G1F>::WORDS : PointIo<G2F>::WORDS;
     const BaseTileOp op = {(const uint32_t *)d_base, (uint32_t *)d_out, words, (uint32_t)n};
-    hipLaunchKernelGGL(bn254_fr_decode_k<BaseTileOp>, dim3((unsigned)((n * words + 255) / 256)), dim3(256), 0, s, op);
-    return (int)hipGetLastError();
+    return bn_lane_launch<256>(op, n * words, s);
 }
 // bn254_g{1,2}_normalize_batch: n points in runs of bn254_normalize_run_M() per lane (lane pair); `prefix`: bn254_normalize_prefix_bytes_M(g, n)
 // bytes of scratch; d_out may be d_p
@@ -371,7 +368,6 @@ int bn254_launch_eq_M(int g, const void *d_a, const void *d_b, void *d_out, size
 int bn254_launch_mul_base_repack_M(int g, const void *d_pts, void *table, size_t n, hipStream_t s) {
     const uint32_t comps = g == 1 ? 1u : 2u;
     const BaseRepackOp op = {(const uint32_t *)d_pts, (uint4 *)table, comps, (uint32_t)n};
-    hipLaunchKernelGGL(bn254_fr_decode_k<BaseRepackOp>, dim3((unsigned)((n * comps + 255) / 256)), dim3(256), 0, s, op);
-    return (int)hipGetLastError();
+    return bn_lane_launch<256>(op, n * comps, s);
 }
 }

@@ -1,13 +1,13 @@
 // Multilinear tables and sumcheck rounds over Fr on the device (include/bn254_hip.h bn254_fr_mle_eq, bn254_fr_mle_fold, bn254_fr_sumcheck_round,
-// bn254_fr_sumcheck_fold_round, bn254_fr_mle_quotients and their _dev twins): the kernels - instances of bn254_fr_decode_k<Op> like the other
-// integer kernels, one lane of the bodies of mle_ops.hpp each -, the levels host_plan.hpp's bn_sumcheck_plan and the passes its
+// bn254_fr_sumcheck_fold_round, bn254_fr_mle_quotients and their _dev twins): the kernels - Ops of lane_launch.hpp's bn254_fr_decode_k like
+// the other integer kernels, one lane of the bodies of mle_ops.hpp each -, the levels host_plan.hpp's bn_sumcheck_plan and the passes its
 // bn_mle_quotients_plan compute as sub-launches, and the ten entry points.
 #include <algorithm>
-#include <atomic>
 #include <cstring>
 
 #include "mle_ops.hpp"
 #include "host_ctx.hpp"
+#include "lane_launch.hpp"
 
 using namespace bn254;
 
@@ -62,61 +62,49 @@ struct FrMleQuotOp {
         if (i < n) fr_mle_quotients_body<RHO>(src, zz, m, fold_dst, out, lo + i);
     }
 };
-template <class Op>
-__global__ void __launch_bounds__(MLE_BLOCK) bn254_fr_decode_k(Op op) { op(); }
 
-template <class Op>
-int mle_launch(const Op &op, size_t lanes, hipStream_t s) {
-    hipLaunchKernelGGL(bn254_fr_decode_k<Op>, dim3((unsigned)((lanes + MLE_BLOCK - 1) / MLE_BLOCK)), dim3(MLE_BLOCK), 0, s, op);
-    return (int)hipGetLastError();
-}
-
-// tests and tools/time_mle.py, tools/time_mle_open.py, tools/time_fold_round.py only: the sub-launch size (0 = BN_LAUNCH_MAX), the piece
-// lengths and the levels per quotient pass the sweeps time (0 = the shipped constants and, for the fused call, the adaptive choice)
-std::atomic<size_t> g_mle_launch_max;
-std::atomic<unsigned> g_sumcheck_piece, g_sumcheck_fold_piece, g_mle_quot_levels;
-size_t mle_step() { const size_t set = g_mle_launch_max.load(std::memory_order_relaxed); return set ? set : BN_LAUNCH_MAX; }
-unsigned quot_levels() { const unsigned set = g_mle_quot_levels.load(std::memory_order_relaxed); return set ? set : FR_MLE_QUOT_LEVELS; }
-unsigned sumcheck_piece() { const unsigned set = g_sumcheck_piece.load(std::memory_order_relaxed); return set ? set : FR_SUMCHECK_PIECE; }
+// tests and tools/time_mle.py, tools/time_mle_open.py, tools/time_fold_round.py only: the sub-launch size, the piece lengths and the levels
+// per quotient pass the sweeps time (for the fused call 0 = the adaptive choice)
+BnLaunchMax g_mle_launch_max;
+BnOverride<unsigned> g_sumcheck_piece, g_sumcheck_fold_piece, g_mle_quot_levels;
 // an override holds at every size; otherwise the shipped piece, halved while the lanes do not fill a device of `cus` compute units
 unsigned sumcheck_fold_piece(size_t h2, size_t cus) {
-    const unsigned set = g_sumcheck_fold_piece.load(std::memory_order_relaxed);
-    return set ? set : (unsigned)bn_sumcheck_fold_piece(h2, FR_SUMCHECK_FOLD_PIECE, bn_sumcheck_fold_fill(cus));
+    return g_sumcheck_fold_piece.get((unsigned)bn_sumcheck_fold_piece(h2, FR_SUMCHECK_FOLD_PIECE, bn_sumcheck_fold_fill(cus)));
 }
 
 int eq_run(bn254_ctx *c, const void *d_z, int nv, void *d_out, hipStream_t s) {
-    return bn_for_parts((size_t)1 << nv, mle_step(), [&](size_t lo, size_t cnt) -> int {
+    return bn_for_parts((size_t)1 << nv, g_mle_launch_max.step(), [&](size_t lo, size_t cnt) -> int {
         BnScope sc(c, s, "fr_mle_eq");
-        return mle_launch(FrMleEqOp{(const uint32_t *)d_z, (uint32_t)nv, (uint32_t *)d_out, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
+        return bn_lane_launch<MLE_BLOCK>(FrMleEqOp{(const uint32_t *)d_z, (uint32_t)nv, (uint32_t *)d_out, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
     });
 }
 int fold_run(bn254_ctx *c, const void *d_in, size_t len, const bn_fr *r, void *d_out, hipStream_t s) {
     Fr rr;
     memcpy(rr.w, r->l, sizeof rr.w);
-    return bn_for_parts(len / 2, mle_step(), [&](size_t lo, size_t cnt) -> int {
+    return bn_for_parts(len / 2, g_mle_launch_max.step(), [&](size_t lo, size_t cnt) -> int {
         BnScope sc(c, s, "fr_mle_fold");
-        return mle_launch(FrMleFoldOp{(const uint32_t *)d_in, rr, (uint32_t *)d_out, (uint64_t)(len / 2), (uint64_t)lo, (uint32_t)cnt}, cnt, s);
+        return bn_lane_launch<MLE_BLOCK>(FrMleFoldOp{(const uint32_t *)d_in, rr, (uint32_t *)d_out, (uint64_t)(len / 2), (uint64_t)lo, (uint32_t)cnt}, cnt, s);
     });
 }
 template <int D>
 int round_launch(const uint32_t *tables, size_t h, size_t k, const BnSumcheckDesc &desc, size_t lanes, uint32_t *dst, size_t lo, size_t cnt, hipStream_t s) {
-    return mle_launch(FrSumcheckRoundOp<D>{tables, (uint64_t)h, (uint32_t)k, desc, (uint64_t)lanes, dst, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
+    return bn_lane_launch<MLE_BLOCK>(FrSumcheckRoundOp<D>{tables, (uint64_t)h, (uint32_t)k, desc, (uint64_t)lanes, dst, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
 }
 // scratch guard held by the caller.  The lanes of `plan` through launch(dst, lo, cnt) under `scope` - the round kernel or the fused one -,
-// then the sum levels in the plan's order, each as sub-launches of at most mle_step() lanes; the stream orders them.
+// then the sum levels in the plan's order, each as sub-launches of at most g_mle_launch_max.step() lanes; the stream orders them.
 template <class Launch>
 int levels_run(bn254_ctx *c, const BnSumcheckPlan &plan, const char *scope, void *d_out, hipStream_t s, Launch launch) {
     int rc = c->mle_ws.reserve(plan.slots * sizeof(bn_fr)); if (rc) return rc;
     uint32_t *const ws = (uint32_t *)c->mle_ws.p, *const out = (uint32_t *)d_out;
-    rc = bn_for_parts(plan.lanes, mle_step(), [&](size_t lo, size_t cnt) -> int {
+    rc = bn_for_parts(plan.lanes, g_mle_launch_max.step(), [&](size_t lo, size_t cnt) -> int {
         BnScope sc(c, s, scope);
         return launch(plan.levels.empty() ? out : ws, lo, cnt);
     });
     if (rc) return rc;
     for (const BnSumcheckLevel &lv : plan.levels) {
-        rc = bn_for_parts(lv.lanes, mle_step(), [&](size_t lo, size_t cnt) -> int {
+        rc = bn_for_parts(lv.lanes, g_mle_launch_max.step(), [&](size_t lo, size_t cnt) -> int {
             BnScope sc(c, s, "fr_sumcheck_sum");
-            return mle_launch(FrSumcheckSumOp{ws + 8 * lv.src, (uint64_t)lv.cnt, FR_SUMCHECK_FAN, lv.to_out ? out : ws + 8 * lv.dst, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
+            return bn_lane_launch<MLE_BLOCK>(FrSumcheckSumOp{ws + 8 * lv.src, (uint64_t)lv.cnt, FR_SUMCHECK_FAN, lv.to_out ? out : ws + 8 * lv.dst, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
         });
         if (rc) return rc;
     }
@@ -124,7 +112,7 @@ int levels_run(bn254_ctx *c, const BnSumcheckPlan &plan, const char *scope, void
 }
 int round_run(bn254_ctx *c, const void *d_tables, size_t n, size_t k, const BnSumcheckDesc &desc, int degree, void *d_out, hipStream_t s) {
     const size_t h = n / 2;
-    const BnSumcheckPlan plan = bn_sumcheck_plan(h, (unsigned)degree, sumcheck_piece(), FR_SUMCHECK_FAN);
+    const BnSumcheckPlan plan = bn_sumcheck_plan(h, (unsigned)degree, g_sumcheck_piece.get(FR_SUMCHECK_PIECE), FR_SUMCHECK_FAN);
     const uint32_t *tables = (const uint32_t *)d_tables;
     return levels_run(c, plan, "fr_sumcheck_round", d_out, s, [&](uint32_t *dst, size_t lo, size_t cnt) -> int {
         switch (degree) {
@@ -138,7 +126,7 @@ int round_run(bn254_ctx *c, const void *d_tables, size_t n, size_t k, const BnSu
 template <int D>
 int fold_round_launch(const uint32_t *tables, const Fr &r, uint32_t *folded, size_t h2, size_t k, const BnSumcheckDesc &desc, size_t lanes, uint32_t *dst, size_t lo, size_t cnt,
                       hipStream_t s) {
-    return mle_launch(FrSumcheckFoldRoundOp<D>{tables, r, folded, (uint64_t)h2, (uint32_t)k, desc, (uint64_t)lanes, dst, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
+    return bn_lane_launch<MLE_BLOCK>(FrSumcheckFoldRoundOp<D>{tables, r, folded, (uint64_t)h2, (uint32_t)k, desc, (uint64_t)lanes, dst, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
 }
 // scratch guard held by the caller.  The fused kernel over the n / 4 indices of the round that follows the fold, then the round's own sum levels.
 int fold_round_run(bn254_ctx *c, const void *d_tables, size_t n, size_t k, const bn_fr *r, const BnSumcheckDesc &desc, int degree, void *d_folded, void *d_out, hipStream_t s) {
@@ -161,20 +149,20 @@ template <int RHO>
 int quot_launch(const uint32_t *src, const bn_fr *z, unsigned m, uint32_t *fold_dst, uint32_t *out, size_t lo, size_t cnt, hipStream_t s) {
     FrMleQuotOp<RHO> op{src, {}, (uint32_t)m, fold_dst, out, (uint64_t)lo, (uint32_t)cnt};
     for (int k = 0; k < RHO; ++k) memcpy(op.zz[k].w, z[m - 1 - k].l, sizeof op.zz[k].w);
-    return mle_launch(op, cnt, s);
+    return bn_lane_launch<MLE_BLOCK>(op, cnt, s);
 }
-// scratch guard held by the caller.  The passes in the plan's order, each as sub-launches of at most mle_step() lanes; the stream orders
+// scratch guard held by the caller.  The passes in the plan's order, each as sub-launches of at most g_mle_launch_max.step() lanes; the stream orders
 // them.  The first reads a and leaves the folded table in the scratch, the later ones run in place there; a is never written.
 int quotients_run(bn254_ctx *c, const void *d_a, int nv, const bn_fr *z, void *d_out, hipStream_t s) {
     uint32_t *const out = (uint32_t *)d_out;
     if (nv == 0) return (int)hipMemcpyAsync(out, d_a, sizeof(bn_fr), hipMemcpyDeviceToDevice, s);
-    const BnMleQuotPlan plan = bn_mle_quotients_plan((unsigned)nv, quot_levels());
+    const BnMleQuotPlan plan = bn_mle_quotients_plan((unsigned)nv, g_mle_quot_levels.get(FR_MLE_QUOT_LEVELS));
     int rc = c->mle_ws.reserve(plan.slots * sizeof(bn_fr)); if (rc) return rc;
     uint32_t *const ws = (uint32_t *)c->mle_ws.p;
     for (const BnMleQuotPass &ps : plan.passes) {
         const uint32_t *src = ps.first ? (const uint32_t *)d_a : ws;
         uint32_t *fold_dst = ps.last ? out : ws;
-        rc = bn_for_parts(ps.lanes, mle_step(), [&](size_t lo, size_t cnt) -> int {
+        rc = bn_for_parts(ps.lanes, g_mle_launch_max.step(), [&](size_t lo, size_t cnt) -> int {
             BnScope sc(c, s, FR_MLE_QUOT_SCOPE);
             switch (ps.levels) {
             case 1: return quot_launch<1>(src, z, ps.vars, fold_dst, out, lo, cnt, s);
@@ -194,9 +182,7 @@ extern "C" {
 // order of the checks everywhere: arguments (nothing of them touches a device), then context and device; nothing waits, nothing is read back
 int bn254_fr_mle_eq_dev(bn254_ctx *ctx, const void *d_z, int nv, void *d_out, void *stream) {
     int rc = bn_mle_eq_check(d_z, nv, d_out); if (rc) return rc;
-    if ((rc = bn_get_ctx(ctx))) return rc;
-    BnDev d(ctx, stream); if (!d.go) return d.rc;
-    return bn_no_throw([&] { return eq_run(ctx, d_z, nv, d_out, d.s); });
+    return bn_dev_entry(ctx, stream, false, [&](hipStream_t s) { return eq_run(ctx, d_z, nv, d_out, s); });
 }
 int bn254_fr_mle_eq(bn254_ctx *ctx, const bn_fr *z, int nv, bn_fr *out) {
     int rc = bn_mle_eq_check(z, nv, out); if (rc) return rc;
@@ -207,9 +193,7 @@ int bn254_fr_mle_eq(bn254_ctx *ctx, const bn_fr *z, int nv, bn_fr *out) {
 int bn254_fr_mle_fold_dev(bn254_ctx *ctx, const void *d_in, size_t len, const bn_fr *r, void *d_out, void *stream) {
     if (len == 0) return BN254_OK;
     int rc = bn_mle_fold_check(d_in, len, r, d_out); if (rc) return rc;
-    if ((rc = bn_get_ctx(ctx))) return rc;
-    BnDev d(ctx, stream); if (!d.go) return d.rc;
-    return bn_no_throw([&] { return fold_run(ctx, d_in, len, r, d_out, d.s); });
+    return bn_dev_entry(ctx, stream, false, [&](hipStream_t s) { return fold_run(ctx, d_in, len, r, d_out, s); });
 }
 int bn254_fr_mle_fold(bn254_ctx *ctx, const bn_fr *in, size_t len, const bn_fr *r, bn_fr *out) {
     if (len == 0) return BN254_OK;
@@ -222,10 +206,7 @@ int bn254_fr_sumcheck_round_dev(bn254_ctx *ctx, const void *d_tables, size_t n, 
                                 size_t g, int degree, void *d_out, void *stream) {
     BnSumcheckDesc desc;
     int rc = bn_sumcheck_check(d_tables, n, k, group_offsets, group_tables, group_coeff, g, degree, d_out, &desc); if (rc) return rc;      // before any device lookup
-    if ((rc = bn_get_ctx(ctx))) return rc;
-    BnDev d(ctx, stream); if (!d.go) return d.rc;
-    BnScratchGuard guard(ctx, d.s); if (guard.rc) return guard.rc;
-    return bn_no_throw([&] { return round_run(ctx, d_tables, n, k, desc, degree, d_out, d.s); });
+    return bn_dev_entry(ctx, stream, true, [&](hipStream_t s) { return round_run(ctx, d_tables, n, k, desc, degree, d_out, s); });
 }
 int bn254_fr_sumcheck_round(bn254_ctx *ctx, const bn_fr *tables, size_t n, size_t k, const size_t *group_offsets, const uint64_t *group_tables, const bn_fr *group_coeff, size_t g,
                             int degree, bn_fr *out) {
@@ -241,10 +222,7 @@ int bn254_fr_sumcheck_fold_round_dev(bn254_ctx *ctx, const void *d_tables, size_
                                      const bn_fr *group_coeff, size_t g, int degree, void *d_folded, void *d_out, void *stream) {
     BnSumcheckDesc desc;
     int rc = bn_sumcheck_fold_check(d_tables, n, k, r, group_offsets, group_tables, group_coeff, g, degree, d_folded, d_out, &desc); if (rc) return rc;      // before any device lookup
-    if ((rc = bn_get_ctx(ctx))) return rc;
-    BnDev d(ctx, stream); if (!d.go) return d.rc;
-    BnScratchGuard guard(ctx, d.s); if (guard.rc) return guard.rc;
-    return bn_no_throw([&] { return fold_round_run(ctx, d_tables, n, k, r, desc, degree, d_folded, d_out, d.s); });
+    return bn_dev_entry(ctx, stream, true, [&](hipStream_t s) { return fold_round_run(ctx, d_tables, n, k, r, desc, degree, d_folded, d_out, s); });
 }
 // the staged copy is folded out of place on the device; with folded == tables only the lower half of the caller's array is written back
 int bn254_fr_sumcheck_fold_round(bn254_ctx *ctx, const bn_fr *tables, size_t n, size_t k, const bn_fr *r, const size_t *group_offsets, const uint64_t *group_tables,
@@ -259,10 +237,7 @@ int bn254_fr_sumcheck_fold_round(bn254_ctx *ctx, const bn_fr *tables, size_t n, 
 // z is HOST memory in both forms: its records travel as kernel arguments.  out must not overlap a.
 int bn254_fr_mle_quotients_dev(bn254_ctx *ctx, const void *d_a, int nv, const bn_fr *z, void *d_out, void *stream) {
     int rc = bn_mle_quotients_check(d_a, nv, z, d_out); if (rc) return rc;
-    if ((rc = bn_get_ctx(ctx))) return rc;
-    BnDev d(ctx, stream); if (!d.go) return d.rc;
-    BnScratchGuard guard(ctx, d.s); if (guard.rc) return guard.rc;
-    return bn_no_throw([&] { return quotients_run(ctx, d_a, nv, z, d_out, d.s); });
+    return bn_dev_entry(ctx, stream, true, [&](hipStream_t s) { return quotients_run(ctx, d_a, nv, z, d_out, s); });
 }
 int bn254_fr_mle_quotients(bn254_ctx *ctx, const bn_fr *a, int nv, const bn_fr *z, bn_fr *out) {
     int rc = bn_mle_quotients_check(a, nv, z, out); if (rc) return rc;
@@ -276,32 +251,16 @@ int bn254_fr_mle_quotients(bn254_ctx *ctx, const bn_fr *a, int nv, const bn_fr *
 // - for the sweep only - a process-wide override of the piece length (0 restores the shipped one; same bytes whatever is set)
 unsigned bn254_fr_sumcheck_piece(void) { return FR_SUMCHECK_PIECE; }
 unsigned bn254_fr_sumcheck_fan(void) { return FR_SUMCHECK_FAN; }
-int bn254_fr_mle_set_launch_max(size_t lanes) {
-    if (lanes > BN_LAUNCH_MAX) return BN254_E_BAD_ARG;
-    g_mle_launch_max.store(lanes, std::memory_order_relaxed);
-    return BN254_OK;
-}
+int bn254_fr_mle_set_launch_max(size_t lanes) { return g_mle_launch_max.set(lanes); }
 // the shipped levels per quotient pass and - for the sweep of tools/time_mle_open.py only - a process-wide override (0 restores the shipped
 // one; same bytes whatever is set)
 unsigned bn254_fr_mle_quotients_levels(void) { return FR_MLE_QUOT_LEVELS; }
-int bn254_fr_mle_quotients_set_levels(unsigned rho) {
-    if (rho > FR_MLE_QUOT_LEVELS_MAX) return BN254_E_BAD_ARG;
-    g_mle_quot_levels.store(rho, std::memory_order_relaxed);
-    return BN254_OK;
-}
-int bn254_fr_sumcheck_set_piece(unsigned P) {
-    if (P > 64) return BN254_E_BAD_ARG;
-    g_sumcheck_piece.store(P, std::memory_order_relaxed);
-    return BN254_OK;
-}
+int bn254_fr_mle_quotients_set_levels(unsigned rho) { return rho > FR_MLE_QUOT_LEVELS_MAX ? BN254_E_BAD_ARG : g_mle_quot_levels.set(rho); }
+int bn254_fr_sumcheck_set_piece(unsigned P) { return P > 64 ? BN254_E_BAD_ARG : g_sumcheck_piece.set(P); }
 // the shipped piece length of the fused fold-then-round kernel, a process-wide override of it for the sweep of tools/time_fold_round.py and
 // the tests (0 restores the adaptive choice; same bytes whatever is set), and the piece a call over h2 indices runs with on `cus` compute units
 unsigned bn254_fr_sumcheck_fold_piece(void) { return FR_SUMCHECK_FOLD_PIECE; }
-int bn254_fr_sumcheck_fold_set_piece(unsigned P) {
-    if (P > 64) return BN254_E_BAD_ARG;
-    g_sumcheck_fold_piece.store(P, std::memory_order_relaxed);
-    return BN254_OK;
-}
+int bn254_fr_sumcheck_fold_set_piece(unsigned P) { return P > 64 ? BN254_E_BAD_ARG : g_sumcheck_fold_piece.set(P); }
 unsigned bn254_fr_sumcheck_fold_piece_for(size_t h2, size_t cus) { return sumcheck_fold_piece(h2, cus); }
 
 }  // extern "C"

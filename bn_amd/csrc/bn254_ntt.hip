@@ -1,10 +1,10 @@
 // Number-theoretic transforms over Fr on the device (include/bn254_hip.h bn254_fr_ntt_batch, its _dev twin and bn254_fr_root_of_unity): the
-// two kernels - instances of bn254_fr_decode_k<Op> like the other integer kernels, over the bodies of ntt_ops.hpp -, the context-owned
-// twiddle tables, the cut of a call into groups of transforms, passes and sub-launches, and the entry points.
+// two kernels - Ops of lane_launch.hpp's bn254_fr_decode_k like the other integer kernels, launched by workgroup, over the bodies of
+// ntt_ops.hpp -, the context-owned twiddle tables, the cut of a call into groups of transforms, passes and sub-launches, and the entry points.
 #include <algorithm>
-#include <atomic>
 
 #include "host_ctx.hpp"
+#include "lane_launch.hpp"
 #include "ntt_ops.hpp"
 
 using namespace bn254;
@@ -31,25 +31,14 @@ struct NttTableOp {
     uint32_t *out; Fr c0, g0, c1, g1;
     __device__ __forceinline__ void operator()() const { ntt_table_body(out, c0, g0, c1, g1, blockIdx.x * NTT_BLOCK + threadIdx.x); }
 };
-template <class Op>
-__global__ void __launch_bounds__(NTT_BLOCK) bn254_fr_decode_k(Op op) { op(); }
 
 // LDS of a pass, sized at the launch for the tile log in force, so that a smaller tile also gets the occupancy of a smaller tile: 2^T
 // elements and the 2^(t-1) stage twiddles, 48 KiB at T = t = 10
 size_t ntt_lds_bytes(unsigned T, unsigned t) { return ((size_t)sizeof(bn_fr) << T) + (t ? (size_t)sizeof(bn_fr) << (t - 1) : 0); }
-template <class Op>
-int ntt_launch(const Op &op, size_t blocks, size_t lds, hipStream_t s) {
-    if (lds > 64 * 1024)                                                           // only a variant library with a larger tile gets here
-        HIP_TRY(hipFuncSetAttribute((const void *)bn254_fr_decode_k<Op>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(bn254_fr_decode_k<Op>, dim3((unsigned)blocks), dim3(NTT_BLOCK), lds, s, op);
-    return (int)hipGetLastError();
-}
 
-// tests and tools/time_ntt.py only: the tile log in force (0 = the shipped NTT_TILE_LOG) and the sub-launch size (0 = BN_LAUNCH_MAX)
-std::atomic<unsigned> g_ntt_tile_log;
-std::atomic<size_t> g_ntt_launch_max;
-unsigned ntt_tile_log() { const unsigned set = g_ntt_tile_log.load(std::memory_order_relaxed); return set ? set : NTT_TILE_LOG; }
-size_t ntt_step() { const size_t set = g_ntt_launch_max.load(std::memory_order_relaxed); return set ? set : BN_LAUNCH_MAX; }
+// tests and tools/time_ntt.py only: the tile log in force and the sub-launch size
+BnOverride<unsigned> g_ntt_tile_log;
+BnLaunchMax g_ntt_launch_max;
 
 Fr fr_of(const uint64_t *l) {
     Fr r;
@@ -63,7 +52,7 @@ int ntt_build_pair(bn254_ctx *c, uint32_t *out, const uint64_t *c0, const uint64
     bn_fr_one(&one);
     bn_fr_pow(g0, e, g1.l);
     BnScope sc(c, s, "ntt_table");
-    return ntt_launch(NttTableOp{out, fr_of(c0), fr_of(g0), fr_of(one.l), fr_of(g1.l)}, 2 * NTT_TBL / NTT_BLOCK, 0, s);
+    return bn_block_launch<NTT_BLOCK>(NttTableOp{out, fr_of(c0), fr_of(g0), fr_of(one.l), fr_of(g1.l)}, 2 * NTT_TBL / NTT_BLOCK, 0, s);
 }
 // scratch guard held by the caller.  The root pair is built once per context; the shift pair is rebuilt when its key changes: the shift
 // alone for a forward transform (the pair holds s^i, whatever the size), shift and size for an inverse one (n^-1 s^-i).
@@ -92,8 +81,8 @@ int ntt_tables(bn254_ctx *c, int log_n, int inverse, const bn_fr *shift, hipStre
 // scratch guard held by the caller.  Groups, passes, buffers and sub-launches are host_plan.hpp's (bn_ntt_run, bn_ntt_group); here the
 // buffers get their addresses and every step becomes one launch.
 int ntt_run(bn254_ctx *c, const void *d_in, void *d_out, int log_n, size_t count, int inverse, const bn_fr *shift, hipStream_t s) {
-    const unsigned T = ntt_tile_log();
-    const size_t N = (size_t)1 << log_n, step = ntt_step();
+    const unsigned T = g_ntt_tile_log.get(NTT_TILE_LOG);
+    const size_t N = (size_t)1 << log_n, step = g_ntt_launch_max.step();
     const bool in_place = d_in == (const void *)d_out;
     const BnNttRun run = bn_ntt_run((unsigned)log_n, T, count, step, in_place);
     int rc = ntt_tables(c, log_n, inverse, shift, s); if (rc) return rc;
@@ -114,7 +103,7 @@ int ntt_run(bn254_ctx *c, const void *d_in, void *d_out, int log_n, size_t count
             K.pre = st.pre; K.post = st.post;
             K.tile_lo = (uint32_t)st.lo; K.tile_end = (uint32_t)(st.lo + st.n);
             BnScope sc(c, s, "ntt");
-            return ntt_launch(NttPassOp{K}, st.blocks, ntt_lds_bytes(T, K.t), s);
+            return bn_block_launch<NTT_BLOCK>(NttPassOp{K}, st.blocks, ntt_lds_bytes(T, K.t), s);
         });
     });
 }
@@ -135,10 +124,7 @@ int bn254_fr_root_of_unity(int log_n, bn_fr *out) { return bn_fr_root(log_n, out
 int bn254_fr_ntt_batch_dev(bn254_ctx *ctx, const void *d_in, void *d_out, int log_n, size_t count, int inverse, const bn_fr *shift, void *stream) {
     if (count == 0) return BN254_OK;
     int rc = ntt_check(d_in, d_out, log_n, count, shift); if (rc) return rc;      // before any device lookup
-    if ((rc = bn_get_ctx(ctx))) return rc;
-    BnDev d(ctx, stream); if (!d.go) return d.rc;
-    BnScratchGuard g(ctx, d.s); if (g.rc) return g.rc;
-    return bn_no_throw([&] { return ntt_run(ctx, d_in, d_out, log_n, count, inverse, shift, d.s); });
+    return bn_dev_entry(ctx, stream, true, [&](hipStream_t s) { return ntt_run(ctx, d_in, d_out, log_n, count, inverse, shift, s); });
 }
 int bn254_fr_ntt_batch(bn254_ctx *ctx, const bn_fr *in, bn_fr *out, int log_n, size_t count, int inverse, const bn_fr *shift) {
     if (count == 0) return BN254_OK;
@@ -153,15 +139,7 @@ int bn254_fr_ntt_batch(bn254_ctx *ctx, const bn_fr *in, bn_fr *out, int log_n, s
 // one, otherwise 1 .. shipped; same bytes whatever is set), and an override of the sub-launch
 // size (0 restores BN_LAUNCH_MAX) so that a test reaches the seams between groups and sub-launches with a handful of elements
 unsigned bn254_ntt_tile_log(void) { return NTT_TILE_LOG; }
-int bn254_ntt_set_tile_log(unsigned T) {
-    if (T > NTT_TILE_LOG) return BN254_E_BAD_ARG;
-    g_ntt_tile_log.store(T, std::memory_order_relaxed);
-    return BN254_OK;
-}
-int bn254_ntt_set_launch_max(size_t elements) {
-    if (elements > BN_LAUNCH_MAX) return BN254_E_BAD_ARG;
-    g_ntt_launch_max.store(elements, std::memory_order_relaxed);
-    return BN254_OK;
-}
+int bn254_ntt_set_tile_log(unsigned T) { return T > NTT_TILE_LOG ? BN254_E_BAD_ARG : g_ntt_tile_log.set(T); }
+int bn254_ntt_set_launch_max(size_t elements) { return g_ntt_launch_max.set(elements); }
 
 }  // extern "C"

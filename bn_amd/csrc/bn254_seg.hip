@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "host_ctx.hpp"
+#include "lane_launch.hpp"      // BN_LAUNCH_MAX and the overrides; this unit launches through bn254_kernels_{b,w,mul}.hip
 
 // ---- one executor for a segmented plan
 // The values (Fq12 / Jacobian points, V bytes each) are cut into chunks of at most `chunk`; a segment that crosses a cut carries its partial
@@ -15,22 +16,13 @@
 // the values, then the levels of the segmented fold - every piece folds at most `fold` consecutive values; a segment with more values is cut into
 // pieces whose partial results the next level folds, so no lane runs a chain longer than fold - 1 operations and a segment of L values takes
 // ceil(log_fold L) levels - or, `small`, the ragged tail, then the carry copy.  The host builds every level's work list up front.
-// The work lists: ONE copy per call through the context's pinned staging, which is rewritten only after its previous copy completed (so the
-// caller's `offsets` may be freed as soon as the call returns); cut(chunks) may name Miller pieces to place behind the fold's pieces in the
-// same copy (bn254_pairing_product_batch_prepared_native; `extra`: where they are on the device) or return NULL.
+// The work lists: ONE copy per call (bn_plan_upload: the caller's `offsets` may be freed as soon as the call returns); cut(chunks) may name
+// Miller pieces to place behind the fold's pieces in the same copy (bn254_pairing_product_batch_prepared_native; `extra`: where they are on
+// the device) or return NULL.
 namespace {
 struct BnSegSpec { size_t V, fold, chunk; bool snap, small; };
 int bn_seg_upload(bn254_ctx *c, const std::vector<BnSegPiece> &pieces, hipStream_t s, const std::vector<BnMillerPiece> *miller) {
-    int rc;
-    const size_t fold_bytes = pieces.size() * sizeof(BnSegPiece), bytes = fold_bytes + (miller ? miller->size() * sizeof(BnMillerPiece) : 0);
-    if (c->seg_plan_ev) HIP_TRY(hipEventSynchronize(c->seg_plan_ev));
-    else HIP_TRY(hipEventCreateWithFlags(&c->seg_plan_ev, hipEventDisableTiming));
-    if ((rc = c->seg_plan_host.reserve(bytes)) || (rc = c->seg_plan.reserve(bytes))) return rc;
-    if (fold_bytes) memcpy(c->seg_plan_host.p, pieces.data(), fold_bytes);
-    if (bytes > fold_bytes) memcpy((char *)c->seg_plan_host.p + fold_bytes, miller->data(), bytes - fold_bytes);
-    HIP_TRY(hipMemcpyAsync(c->seg_plan.p, c->seg_plan_host.p, bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(c->seg_plan_ev, s));
-    return BN254_OK;
+    return bn_plan_upload(c, pieces.data(), pieces.size() * sizeof(BnSegPiece), miller ? miller->data() : nullptr, miller ? miller->size() * sizeof(BnMillerPiece) : 0, s);
 }
 // fold(tail, pieces, count) enqueues one launch over `count` pieces of the device-side work list; off is HOST memory; scratch guard held by the caller
 template <class Cut, class Produce, class Fold>
@@ -254,11 +246,8 @@ static bool bn_msm_bucket_route(const bn254_ctx *c, int g, size_t n) {
 // and every result (0, 1, 0).  Lookup, build and launches run under the caller's scratch guard, which is what orders a rebuild on one
 // stream behind the readers on another.
 namespace {
-std::atomic<unsigned> g_base_window[2];       // measurement only (bn254_mul_base_set_window): 0 = the shipped width
-unsigned bn_base_window(int g) {
-    const unsigned o = g_base_window[g - 1].load(std::memory_order_relaxed);
-    return o ? o : g == 1 ? BN_BASE_WINDOW_G1 : BN_BASE_WINDOW_G2;
-}
+BnOverride<unsigned> g_base_window[2];        // measurement only (bn254_mul_base_set_window): the window width
+unsigned bn_base_window(int g) { return g_base_window[g - 1].get(g == 1 ? BN_BASE_WINDOW_G1 : BN_BASE_WINDOW_G2); }
 // the scalars of a table build on the device, rebuilt only when the window width changes (as msm_scal)
 int bn_base_scalars(BnBaseCache &bc, unsigned cb, hipStream_t s) {
     if (bc.scal_c == (long)cb) return BN254_OK;
@@ -323,10 +312,10 @@ int bn_launch_mul_base(bn254_ctx *c, int g, const void *base, const void *d_k, v
 // bn254_normalize_run_M() consecutive points with one inversion (group_ops.hpp normalize_body); the last run of a sub-launch is the short
 // one.  The prefix products of a sub-launch - one field element per point - are context-owned scratch, reused by the next sub-launch on the
 // same stream.  eq: one lane (lane pair) per pair of points, no scratch.
-std::atomic<size_t> g_norm_launch_max;        // tests only (bn254_normalize_set_launch_max): 0 = BN_LAUNCH_MAX
+BnLaunchMax g_norm_launch_max;                // tests only (bn254_normalize_set_launch_max): the sub-launch size
 // scratch guard held by the caller
 int bn_launch_normalize(bn254_ctx *c, int g, const void *d_p, void *d_out, size_t n, hipStream_t s) {
-    const size_t V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2), set = g_norm_launch_max.load(std::memory_order_relaxed), step = set ? set : BN_LAUNCH_MAX;
+    const size_t V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2), step = g_norm_launch_max.step();
     int rc = c->norm_prefix.reserve(bn254_normalize_prefix_bytes_M(g, std::min(n, step))); if (rc) return rc;
     return bn_for_parts(n, step, [&](size_t lo, size_t cnt) -> int {
         BnScope sc(c, s, g == 1 ? "g1_normalize" : "g2_normalize");
@@ -355,15 +344,7 @@ static int bn_prep_seg_check(const void *p, const bn254_g2_prepared *prep, bool 
     return BN254_OK;
 }
 
-// the *_dev entry points below, after their argument checks: context, device, scratch guard (workspaces, window tables and work lists are
-// context-owned scratch), then fn(stream) with nothing thrown across the ABI
-template <class Fn>
-static int bn_seg_entry(bn254_ctx *&ctx, void *stream, Fn fn) {
-    int rc = bn_get_ctx(ctx); if (rc) return rc;
-    BnDev d(ctx, stream); if (!d.go) return d.rc;
-    BnScratchGuard g(ctx, d.s); if (g.rc) return g.rc;
-    return bn_no_throw([&] { return fn(d.s); });
-}
+// the *_dev entry points below run under the scratch guard (bn_dev_entry): workspaces, window tables and work lists are context-owned scratch
 
 extern "C" {
 
@@ -371,25 +352,25 @@ extern "C" {
 int bn254_pairing_product_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, const size_t *offsets, size_t m, void *d_out, void *stream) {
     if (m == 0) return BN254_OK;
     if (int e = bn_seg_check(d_p, d_q, offsets, m, d_out)) return e;          // before any device lookup
-    return bn_seg_entry(ctx, stream, [&](hipStream_t s) { return bn_launch_product_batch(ctx, d_p, d_q, offsets, m, d_out, s); });
+    return bn_dev_entry(ctx, stream, true, [&](hipStream_t s) { return bn_launch_product_batch(ctx, d_p, d_q, offsets, m, d_out, s); });
 }
 int bn254_pairing_product_batch_prepared_native_dev(bn254_ctx *ctx, const void *d_p, const bn254_g2_prepared *prep, const void *d_q_index, const size_t *offsets, size_t m, void *d_out, void *stream) {
     if (m == 0) return BN254_OK;
     if (int e = bn_prep_seg_check(d_p, prep, d_q_index != nullptr, nullptr, offsets, m, d_out)) return e;          // before any device lookup
     int rc = bn_get_ctx(ctx); if (rc) return rc;
     if (prep->device != ctx->device) return BN254_E_BAD_ARG;
-    return bn_seg_entry(ctx, stream, [&](hipStream_t s) { return bn_launch_product_batch_prepared(ctx, d_p, prep, d_q_index, offsets, m, d_out, s); });
+    return bn_dev_entry(ctx, stream, true, [&](hipStream_t s) { return bn_launch_product_batch_prepared(ctx, d_p, prep, d_q_index, offsets, m, d_out, s); });
 }
 static int msm_dev(bn254_ctx *ctx, int g, const void *d_p, const void *d_k, const size_t *offsets, size_t m, void *d_out, void *stream) {
     if (m == 0) return BN254_OK;
     if (int e = bn_msm_check(d_p, d_k, offsets, m, d_out)) return e;          // before any device lookup
-    return bn_seg_entry(ctx, stream, [&](hipStream_t s) { return bn_launch_msm(ctx, g, d_p, d_k, offsets, m, d_out, s); });
+    return bn_dev_entry(ctx, stream, true, [&](hipStream_t s) { return bn_launch_msm(ctx, g, d_p, d_k, offsets, m, d_out, s); });
 }
 int bn254_g1_msm_batch_dev(bn254_ctx *c, const void *p, const void *k, const size_t *offsets, size_t m, void *o, void *s) { return msm_dev(c, 1, p, k, offsets, m, o, s); }
 int bn254_g2_msm_batch_dev(bn254_ctx *c, const void *p, const void *k, const size_t *offsets, size_t m, void *o, void *s) { return msm_dev(c, 2, p, k, offsets, m, o, s); }
 static int msm1_dev(bn254_ctx *ctx, int g, const void *d_p, const void *d_k, size_t n, void *d_out, void *stream) {
     if (int e = bn_msm1_check(d_p, d_k, n, d_out)) return e;                   // before any device lookup
-    return bn_seg_entry(ctx, stream, [&](hipStream_t s) -> int {
+    return bn_dev_entry(ctx, stream, true, [&](hipStream_t s) -> int {
         if (bn_msm_bucket_route(ctx, g, n)) return bn_launch_msm_bucket(ctx, g, d_p, d_k, n, d_out, s);
         const size_t off[2] = {0, n};
         return bn_launch_msm(ctx, g, d_p, d_k, off, 1, d_out, s);
@@ -401,7 +382,7 @@ int bn254_g2_msm_dev(bn254_ctx *c, const void *p, const void *k, size_t n, void 
 static int mul_base_dev(bn254_ctx *ctx, int g, const void *base, const void *d_k, void *d_out, size_t n, void *stream) {
     if (n == 0) return BN254_OK;
     if (n > BN_N_MAX || !base || !d_k || !d_out) return BN254_E_BAD_ARG;          // before any device lookup
-    return bn_seg_entry(ctx, stream, [&](hipStream_t s) { return bn_launch_mul_base(ctx, g, base, d_k, d_out, n, s); });
+    return bn_dev_entry(ctx, stream, true, [&](hipStream_t s) { return bn_launch_mul_base(ctx, g, base, d_k, d_out, n, s); });
 }
 int bn254_g1_mul_base_batch_dev(bn254_ctx *c, const bn_g1 *base, const void *k, void *o, size_t n, void *s) { return mul_base_dev(c, 1, base, k, o, n, s); }
 int bn254_g2_mul_base_batch_dev(bn254_ctx *c, const bn_g2 *base, const void *k, void *o, size_t n, void *s) { return mul_base_dev(c, 2, base, k, o, n, s); }
@@ -409,7 +390,7 @@ int bn254_g2_mul_base_batch_dev(bn254_ctx *c, const bn_g2 *base, const void *k, 
 static int normalize_dev(bn254_ctx *ctx, int g, const void *d_p, void *d_out, size_t n, void *stream) {
     if (n == 0) return BN254_OK;
     if (n > BN_N_MAX || !d_p || !d_out) return BN254_E_BAD_ARG;                    // before any device lookup
-    return bn_seg_entry(ctx, stream, [&](hipStream_t s) { return bn_launch_normalize(ctx, g, d_p, d_out, n, s); });
+    return bn_dev_entry(ctx, stream, true, [&](hipStream_t s) { return bn_launch_normalize(ctx, g, d_p, d_out, n, s); });
 }
 int bn254_g1_normalize_batch_dev(bn254_ctx *c, const void *p, void *o, size_t n, void *s) { return normalize_dev(c, 1, p, o, n, s); }
 int bn254_g2_normalize_batch_dev(bn254_ctx *c, const void *p, void *o, size_t n, void *s) { return normalize_dev(c, 2, p, o, n, s); }
@@ -417,20 +398,14 @@ int bn254_g2_normalize_batch_dev(bn254_ctx *c, const void *p, void *o, size_t n,
 static int eq_dev(bn254_ctx *ctx, int g, const void *d_a, const void *d_b, void *d_out, size_t n, void *stream) {
     if (n == 0) return BN254_OK;
     if (n > BN_N_MAX || !d_a || !d_b || !d_out) return BN254_E_BAD_ARG;            // before any device lookup
-    int rc = bn_get_ctx(ctx); if (rc) return rc;
-    BnDev d(ctx, stream); if (!d.go) return d.rc;
-    return bn_no_throw([&] { return bn_launch_eq(ctx, g, d_a, d_b, d_out, n, d.s); });
+    return bn_dev_entry(ctx, stream, false, [&](hipStream_t s) { return bn_launch_eq(ctx, g, d_a, d_b, d_out, n, s); });
 }
 int bn254_g1_eq_batch_dev(bn254_ctx *c, const void *a, const void *b, void *o, size_t n, void *s) { return eq_dev(c, 1, a, b, o, n, s); }
 int bn254_g2_eq_batch_dev(bn254_ctx *c, const void *a, const void *b, void *o, size_t n, void *s) { return eq_dev(c, 2, a, b, o, n, s); }
 // internal (not in the header; tests and tools/time_normalize.py): the shipped run length of the normalisation, and an override of its
 // sub-launch size (0 restores BN_LAUNCH_MAX), so that a test reaches the seam between two sub-launches with a handful of points
 unsigned bn254_normalize_run(void) { return bn254_normalize_run_M(); }
-int bn254_normalize_set_launch_max(size_t points) {
-    if (points > BN_LAUNCH_MAX) return BN254_E_BAD_ARG;
-    g_norm_launch_max.store(points, std::memory_order_relaxed);
-    return BN254_OK;
-}
+int bn254_normalize_set_launch_max(size_t points) { return g_norm_launch_max.set(points); }
 // internal (not in the header; tests and tools/time_mul_base.py): the shipped window width of a group, the device bytes of one table, the
 // slots per group, the scalars a table is built with (returns their count; writes 4 words each when `cap_words` suffices), and - for the
 // width sweep only - a process-wide override of the width (0 restores the shipped one; tables of another width are rebuilt on use)
@@ -449,10 +424,8 @@ size_t bn254_mul_base_table_scalars(unsigned c, uint64_t *out, size_t cap_words)
     });
     return count;
 }
-int bn254_mul_base_set_window(int g, unsigned c) {
-    if ((g != 1 && g != 2) || (c != 0 && (c < 3 || c > 16))) return BN254_E_BAD_ARG;      // c = 2: W c = 254, the top window would carry
-    g_base_window[g - 1].store(c, std::memory_order_relaxed);
-    return BN254_OK;
+int bn254_mul_base_set_window(int g, unsigned c) {      // c = 2: W c = 254, the top window would carry
+    return (g != 1 && g != 2) || (c != 0 && (c < 3 || c > 16)) ? BN254_E_BAD_ARG : g_base_window[g - 1].set(c);
 }
 
 // ---------------------------------------------------------------------------------------------- host-buffer API (BnHost: the context's mutex for the call)

@@ -1,9 +1,8 @@
 // The wire format of the BN254 engine (include/bn254_hip.h; io_wire.hpp): encode / decode kernels, one record per lane, their host-buffer
 // entry points, the byte streams of variable-length records built on them, and the compressed encodings (io_compress.hpp): their kernels are
-// template instances of bn254_fr_decode_k<Op> and - G2 decompression, which carries the subgroup chain - of bn254_g2_decode_k<Op>.
+// Ops of lane_launch.hpp's bn254_fr_decode_k and - G2 decompression, which carries the subgroup chain - of this unit's bn254_g2_decode_k<Op>.
 // Compiled like every unit (bn254_hip.hip: the flags).
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <cstring>
 #include <vector>
 
@@ -12,6 +11,7 @@
 #include "io_wire.hpp"
 #include "io_compress.hpp"
 #include "host_ctx.hpp"
+#include "lane_launch.hpp"
 
 using namespace bn254;
 
@@ -102,8 +102,7 @@ struct G2DecompressOp {
         status[lo + i] = g2_decompress_record(in + BN254_G2_COMPRESSED_BYTES * (lo + i), format, out + 48 * (lo + i));
     }
 };
-template <class Op>
-__global__ void __launch_bounds__(BLOCK) bn254_fr_decode_k(Op op) { op(); }
+// the one Op with a shell of its own name: G2DecompressOp, held under the spill ceiling of bn254_g2_decode_k (the wire decoder above shares the name)
 template <class Op>
 __global__ void __launch_bounds__(BLOCK) bn254_g2_decode_k(Op op) { op(); }
 
@@ -198,9 +197,7 @@ int bn254_g2_decode_stream(bn254_ctx *ctx, const uint8_t *in, size_t len, bn_g2 
 // ---- compressed encodings -------------------------------------------------------------------------------------------------------
 namespace {
 constexpr size_t WIRE_N_MAX = 0x7fffffffu / 129;            // the wire layer's limit on the records of one call
-// tests only: the sub-launch size (0 = BN_LAUNCH_MAX)
-std::atomic<size_t> g_compress_launch_max;
-size_t compress_step() { const size_t set = g_compress_launch_max.load(std::memory_order_relaxed); return set ? set : BN_LAUNCH_MAX; }
+BnLaunchMax g_compress_launch_max;          // tests only: the sub-launch size
 
 // arguments only: nothing here touches a device.  1 = nothing to do
 int compress_check(int format, const void *in, const void *out, const void *status, bool decompress, size_t n) {
@@ -209,22 +206,20 @@ int compress_check(int format, const void *in, const void *out, const void *stat
     return (!in || !out || (decompress && !status) || n > WIRE_N_MAX) ? BN254_E_BAD_ARG : BN254_OK;
 }
 int compress_run(bn254_ctx *ctx, int g, bool decompress, const void *d_in, int format, void *d_out, void *d_status, size_t n, hipStream_t s) {
-    return bn_for_parts(n, compress_step(), [&](size_t lo, size_t cnt) -> int {
+    return bn_for_parts(n, g_compress_launch_max.step(), [&](size_t lo, size_t cnt) -> int {
         BnScope sc(ctx, s, decompress ? (g == 1 ? "g1_decompress" : "g2_decompress") : (g == 1 ? "g1_compress" : "g2_compress"));
-        const dim3 grid((unsigned)((cnt + BLOCK - 1) / BLOCK)), block(BLOCK);
-        if (!decompress && g == 1) hipLaunchKernelGGL(bn254_fr_decode_k<G1CompressOp>, grid, block, 0, s, G1CompressOp{(const uint32_t *)d_in, (uint8_t *)d_out, (uint64_t)lo, (uint32_t)cnt, format});
-        if (!decompress && g == 2) hipLaunchKernelGGL(bn254_fr_decode_k<G2CompressOp>, grid, block, 0, s, G2CompressOp{(const uint32_t *)d_in, (uint8_t *)d_out, (uint64_t)lo, (uint32_t)cnt, format});
-        if (decompress && g == 1) hipLaunchKernelGGL(bn254_fr_decode_k<G1DecompressOp>, grid, block, 0, s, G1DecompressOp{(const uint8_t *)d_in, (uint32_t *)d_out, (int32_t *)d_status, (uint64_t)lo, (uint32_t)cnt, format});
-        if (decompress && g == 2) hipLaunchKernelGGL(bn254_g2_decode_k<G2DecompressOp>, grid, block, 0, s, G2DecompressOp{(const uint8_t *)d_in, (uint32_t *)d_out, (int32_t *)d_status, (uint64_t)lo, (uint32_t)cnt, format});
+        if (!decompress && g == 1) return bn_lane_launch<BLOCK>(G1CompressOp{(const uint32_t *)d_in, (uint8_t *)d_out, (uint64_t)lo, (uint32_t)cnt, format}, cnt, s);
+        if (!decompress) return bn_lane_launch<BLOCK>(G2CompressOp{(const uint32_t *)d_in, (uint8_t *)d_out, (uint64_t)lo, (uint32_t)cnt, format}, cnt, s);
+        if (g == 1) return bn_lane_launch<BLOCK>(G1DecompressOp{(const uint8_t *)d_in, (uint32_t *)d_out, (int32_t *)d_status, (uint64_t)lo, (uint32_t)cnt, format}, cnt, s);
+        hipLaunchKernelGGL(bn254_g2_decode_k<G2DecompressOp>, dim3((unsigned)((cnt + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s,
+                           G2DecompressOp{(const uint8_t *)d_in, (uint32_t *)d_out, (int32_t *)d_status, (uint64_t)lo, (uint32_t)cnt, format});
         return (int)hipGetLastError();
     });
 }
 // order of the checks: arguments, then context and device; nothing waits, nothing is read back
 int compress_dev(bn254_ctx *ctx, int g, bool decompress, const void *d_in, int format, void *d_out, void *d_status, size_t n, void *stream) {
     int rc = compress_check(format, d_in, d_out, d_status, decompress, n); if (rc) return rc == 1 ? BN254_OK : rc;
-    if ((rc = bn_get_ctx(ctx))) return rc;
-    BnDev d(ctx, stream); if (!d.go) return d.rc;
-    return bn_no_throw([&] { return compress_run(ctx, g, decompress, d_in, format, d_out, d_status, n, d.s); });
+    return bn_dev_entry(ctx, stream, false, [&](hipStream_t s) { return compress_run(ctx, g, decompress, d_in, format, d_out, d_status, n, s); });
 }
 int compress_host(bn254_ctx *ctx, int g, bool decompress, const void *in, int format, void *out, int32_t *status, size_t n) {
     int rc = compress_check(format, in, out, status, decompress, n); if (rc) return rc == 1 ? BN254_OK : rc;
@@ -248,11 +243,7 @@ int bn254_g2_decompress_batch_dev(bn254_ctx *ctx, const void *d_in, int format, 
 
 // internal (not in the header; tests and tools/time_compress.py): an override of the sub-launch size of the eight calls above (0 restores
 // BN_LAUNCH_MAX) so that a test reaches the seam between two sub-launches with a handful of records, and which chain form the square roots run
-int bn254_compress_set_launch_max(size_t lanes) {
-    if (lanes > BN_LAUNCH_MAX) return BN254_E_BAD_ARG;
-    g_compress_launch_max.store(lanes, std::memory_order_relaxed);
-    return BN254_OK;
-}
+int bn254_compress_set_launch_max(size_t lanes) { return g_compress_launch_max.set(lanes); }
 int bn254_compress_sqrt_window(void) { return BN254_SQRT_WINDOW; }
 
 }  // extern "C"

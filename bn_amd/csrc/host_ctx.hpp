@@ -1,7 +1,9 @@
 // Host-side internals shared by the translation units that implement include/bn254_hip.h (bn254_hip.hip: contexts, options, launch
 // policy and the single-device entry points of pairing, Miller loop, final exponentiation and products; bn254_seg.hip: the segmented
 // multi-pairings and the multi-scalar multiplications; bn254_wire.hip: the wire format; bn254_multi.hip: pipelined host-buffer path,
-// multi-device fan-out, RCCL exchange).  The host arithmetic that needs no device is host_plan.hpp.  Not part of the ABI.
+// multi-device fan-out, RCCL exchange; bn254_{fr,ntt,dot,scan,mle,poseidon,hash}.hip: the families of integer kernels over Fr and hash-to-curve,
+// each with its Ops and entry points).  The host arithmetic that needs no device is host_plan.hpp; the kernel shell, the launchers and the
+// overrides of the integer kernels are lane_launch.hpp.  Not part of the ABI.
 //
 // Concurrency contract (what the header promises and these structures implement):
 //   * any number of host threads may call the HOST-BUFFER entry points of one context - including the process-wide default
@@ -133,7 +135,7 @@ struct bn254_ctx {
     BnBuf base_stage;                   // the base of a table build on the device ...
     BnBuf base_stage_host{nullptr, 0, true};    // ... and its pinned staging, rewritten only after base_stage_ev (its last copy) completed
     hipEvent_t base_stage_ev = nullptr;
-    BnBuf stage[4];                     // device staging of the small host-buffer entry points (bn_staged: two inputs, two outputs)
+    BnBuf stage[4];                     // device staging of the small host-buffer entry points (bn_staged: two inputs, two outputs; [3] holds a third input instead)
     BnSlot slot[BN_MAX_SLOTS];          // pipelined path (bn254_multi.hip)
     // leases of those slots: a batch of up to one chunk takes ONE of the first two (two callers overlap on the GPU - the number
     // of streams the hardware overlaps without loss), a multi-chunk batch takes all of them
@@ -213,7 +215,6 @@ int bn_launch_product(bn254_ctx *c, const void *in, size_t n, void *out, void *t
 size_t bn_product_tmp_bytes(const bn254_ctx *c, size_t n);
 // table: the caller's own buffer (pipelined path: the slot's) or NULL for the context's (then under a BnScratchGuard)
 int bn_mul_dev(bn254_ctx *ctx, int g, const void *d_p, const void *d_k, void *d_out, size_t n, hipStream_t s, int normalize, BnBuf *table = nullptr);
-constexpr size_t BN_LAUNCH_MAX = (size_t)1 << 22;       // units per launch (32-bit word offsets inside a kernel); also the cap of the size options
 // terms from which bn254_g{1,2}_msm take the bucket route while BN254_OPT_MSM_BUCKET_MIN is not set: the smallest measured size from which
 // the route is faster in kernel time than the one-segment bn254_g{1,2}_msm_batch and stays faster above (profiles/r10_msm_bucket.txt: G1
 // 0.73 x at 2^18, 1.06 x at 2^19, 1.33 x at 2^20; G2 0.77 x at 2^17, 1.14 x at 2^18, 1.55 x at 2^19).  bn254_ctx_get_option reports G1's.
@@ -249,6 +250,20 @@ struct BnDev {
         go = !rc; s = stream;
     }
 };
+// The _dev prologue after the argument checks: context, device, the scratch guard where the call uses context-owned scratch, then
+// fn(stream) with nothing thrown across the ABI (nothing waits, nothing is read back)
+template <class Fn>
+int bn_dev_entry(bn254_ctx *&ctx, void *stream, bool scratch, Fn fn) {
+    int rc = bn_get_ctx(ctx); if (rc) return rc;
+    BnDev d(ctx, stream); if (!d.go) return d.rc;
+    if (!scratch) return bn_no_throw([&] { return fn(d.s); });
+    BnScratchGuard g(ctx, d.s); if (g.rc) return g.rc;
+    return bn_no_throw([&] { return fn(d.s); });
+}
+// Work lists (ctx->seg_plan): ONE copy of a || b per call through the context's pinned staging, which is rewritten only after its previous
+// copy completed - so the caller's host arrays may be freed as soon as the call returns.  Scratch guard held by the caller (bn254_hip.hip;
+// hidden: the library's list of dynamic symbols stays what it was).
+__attribute__((visibility("hidden"))) int bn_plan_upload(bn254_ctx *c, const void *a, size_t a_bytes, const void *b, size_t b_bytes, hipStream_t s);
 // Prologue of the host-buffer entry points that lock the context: looks the context up, holds its mutex for the whole call - concurrent
 // callers of one context (in particular of the default context behind ctx == NULL) are serialised, never interleaved on the staging
 // memory -, makes its device current.  `BnHost h(ctx); if (h.rc) return h.rc;`
@@ -266,24 +281,27 @@ struct BnHost {
 // The body of a host-buffer entry point of the shape copy-in, device calls, copy-out, synchronise, on the context's stream under a BnHost:
 // the inputs (skipped when NULL; nothing copied for zero bytes) are staged in ctx->stage[0..1], body(d) enqueues the work on the staged
 // inputs d.in[] (NULL for a skipped one) and the device buffers d.out / d.out2, then `out` (and `out2` when given) are copied back.
+// A third input takes the place of the second output (ctx->stage[3]): only without an out2.
 // On an error the stream is drained first: copies that read or write the caller's buffers may still be in flight.
 struct BnStageIn { const void *p; size_t bytes; };
-struct BnStaged { void *in[2], *out, *out2; };
+struct BnStaged { void *in[3], *out, *out2; };
 template <class Body>
-int bn_staged(bn254_ctx *ctx, BnStageIn in0, BnStageIn in1, void *out, size_t out_bytes, void *out2, size_t out2_bytes, Body body) {
+int bn_staged(bn254_ctx *ctx, BnStageIn in0, BnStageIn in1, void *out, size_t out_bytes, void *out2, size_t out2_bytes, Body body, BnStageIn in2 = {nullptr, 0}) {
     const hipStream_t s = ctx->stream;
-    const BnStageIn in[2] = {in0, in1};
+    const BnStageIn in[3] = {in0, in1, in2};
+    BnBuf *const in_buf[3] = {&ctx->stage[0], &ctx->stage[1], &ctx->stage[3]};
+    if (in2.p && out2) return BN254_E_INTERNAL;
     auto run = [&]() -> int {
         int rc;
         BnStaged d = {};
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < 3; ++i) {
             if (!in[i].p) continue;
-            if ((rc = ctx->stage[i].reserve(in[i].bytes))) return rc;
-            d.in[i] = ctx->stage[i].p;
+            if ((rc = in_buf[i]->reserve(in[i].bytes))) return rc;
+            d.in[i] = in_buf[i]->p;
         }
         if ((rc = ctx->stage[2].reserve(out_bytes)) || (out2 && (rc = ctx->stage[3].reserve(out2_bytes)))) return rc;
         d.out = ctx->stage[2].p; d.out2 = out2 ? ctx->stage[3].p : nullptr;
-        for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < 3; ++i)
             if (d.in[i] && in[i].bytes) HIP_TRY(hipMemcpyAsync(d.in[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, s));
         if ((rc = body(d))) return rc;
         HIP_TRY(hipMemcpyAsync(out, d.out, out_bytes, hipMemcpyDeviceToHost, s));

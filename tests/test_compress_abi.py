@@ -286,7 +286,8 @@ def test_the_kernels_are_instances_of_existing_names_within_their_ceilings():
     import kernel_meta
     from test_build_quality import SPILL_CEILING
     so = ROOT / "bn_amd" / "libbn254_hip.so"
-    src = (ROOT / "bn_amd" / "csrc" / "bn254_wire.hip").read_text()                            # the unit adds no kernel under a new name
+    import lane_shell
+    src = lane_shell.unit_source("bn254_wire.hip", own_kernels=True)                            # the unit adds no kernel under a new name
     assert set(re.findall(r"__global__[^\n]*?(bn254_\w+)\(", src)) == {"bn254_g1_encode_k", "bn254_g2_encode_k", "bn254_g1_decode_k", "bn254_g2_decode_k", "bn254_fr_encode_k", "bn254_fr_decode_k"}
     if not so.exists() or not (isa_mix.LLVM / "llvm-readelf").exists():
         pytest.skip("library or llvm-readelf not present")

@@ -249,9 +249,9 @@ def test_the_kernels_are_instances_of_fr_decode_k_and_spill_nothing():
     import kernel_meta
     from test_build_quality import SPILL_CEILING
     so = ROOT / "bn_amd" / "libbn254_hip.so"
-    src = (ROOT / "bn_amd" / "csrc" / "bn254_scan.hip").read_text()                            # the unit adds no kernel under any other name
-    assert re.findall(r"__global__[^\n]*?(bn254_\w+)\(", src) == ["bn254_fr_decode_k"] and src.count("__global__") == 1
-    assert "__launch_bounds__(SCAN_BLOCK)" in src and "SCAN_BLOCK = 256" in src
+    import lane_shell
+    src = lane_shell.unit_source("bn254_scan.hip")  # the unit adds no kernel under any other name: the shell is lane_launch.hpp's
+    assert "bn_lane_launch<SCAN_BLOCK>(" in src and "SCAN_BLOCK = 256" in src
     if not so.exists() or not (isa_mix.LLVM / "llvm-readelf").exists():
         pytest.skip("library or llvm-readelf not present")
     assert SPILL_CEILING["bn254_fr_decode_k"] == 0
