@@ -631,7 +631,7 @@ BN_FN void gt_pow_gls_table(const Fq12<F2> &base, Tbl &tbl) {
     for (int e = 2; e <= 8; ++e) {                 // a^e = (a^(e/2))^2 for even e, a^(e-1) * a for odd e
         Fq12<F2> v;
         if ((e & 1) == 0) v = f12_cyclotomic_sqr(Fq12<F2>{tbl.c0(e >> 1), tbl.c1(e >> 1)});
-        else v = f12_mul_src(Fq12<F2>{tbl.c0(e - 1), tbl.c1(e - 1)}, Fq12Slot<F2, Tbl>{tbl, 1}, false);
+        else v = f12_mul_src<false>(Fq12<F2>{tbl.c0(e - 1), tbl.c1(e - 1)}, Fq12Slot<F2, Tbl>{tbl, 1}, false);
         tbl.put(e, v);
     }
 #pragma unroll 1
@@ -666,7 +666,7 @@ BN_FN Fq12<F2> gt_pow_gls_loop(const uint32_t *k_raw, Tbl &tbl) {
             // (forming the Frobenius image when an entry is USED instead of storing 24 images per element - 9 table entries instead of 33, 0.75 GB of
             //  stores less per 2^16 - was built and measured 11 % SLOWER: 54 maps of five Fq2 products by constants per element against 24, and the
             //  stores were never the cost.  profiles/r06_ab_gtpow_mapped_table.txt)
-            res = f12_mul_src(res, Fq12Slot<F2, Tbl>{tbl, ad ? 8 * j + ad : 0}, false);
+            res = f12_mul_src<false>(res, Fq12Slot<F2, Tbl>{tbl, ad ? 8 * j + ad : 0}, false);
             res.c1 = f6_cond_neg(neg, res.c1);
         }
     }

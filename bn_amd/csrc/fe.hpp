@@ -145,6 +145,27 @@ inline void bn_verify_actual(const Fe &f, const char *where) {
 #define BN_VERIFY(x, where) ((void)0)
 #endif
 
+// the double-width value of the lazily reduced tower products (fe_wmul2 / fe_wred below)
+struct FeW {
+    uint32_t l[18];
+#if defined(BN_BOUNDS)
+    uint32_t lb = 1, wb = 0;
+#endif
+};
+#if defined(BN_BOUNDS)
+// the claimed bounds of a wide value against its limbs: limb range, and |value| <= wb q^2 via the top limb (q^2 = 2^507.2, so one unit
+// of the top limb - 2^493 - is q^2 / 2^14.2; compared with 2^15 per unit of wb: the check is a factor 1.7 loose, the claim is not)
+inline void bn_verify_wide(const FeW &f, const char *where) {
+    for (int i = 0; i < 17; ++i)
+        if ((uint64_t)f.l[i] > (uint64_t)f.lb * MASK29) { std::fprintf(stderr, "BN_BOUNDS: wide limb %d = %u exceeds claimed lb %u in %s\n", i, f.l[i], f.lb, where); std::abort(); }
+    const int64_t top = (int64_t)(int32_t)f.l[17];
+    if ((top < 0 ? -top : top) > (int64_t)f.wb * 32768 + 4) { std::fprintf(stderr, "BN_BOUNDS: wide top limb %lld exceeds claimed wb %u in %s\n", (long long)top, f.wb, where); std::abort(); }
+}
+#define BN_VERIFYW(x, where) bn_verify_wide((x), where)
+#else
+#define BN_VERIFYW(x, where) ((void)0)
+#endif
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Leaf calling convention.  A struct argument larger than the 16 registers clang's AMDGPU ABI grants to ALL aggregate
 // arguments together is passed through private memory (scratch), which is HBM traffic (measured: profiles/r01a_*).
@@ -712,6 +733,137 @@ BN_FN Fe fe_mul2s(const Fe &a, const Fe &u, const Fe &c, const Fe &v) {
     BN_VERIFY(r, "fe_mul2s");
     return r;
 }
+// ---------------------------------------------------------------------------------------------------------------------
+// Lazy reduction at double width (Aranha, Karabina, Longa, Gebotys, Lopez 2011) for the Karatsuba products of the lane-pair tower
+// (tower.hpp f6_mul_lazy): the dual products stay UNREDUCED, the Karatsuba recombination and the multiplication by xi run on the
+// unreduced values, and every output coefficient pays ONE Montgomery reduction.
+//
+// FeW: a signed 18-limb integer, sum l[i] 2^(29 i).  Limbs 0..16 are non-negative, the top limb l[17] is an int32 and carries the sign.
+//   limb bound  lb : l[i] <= lb * (2^29 - 1) for i < 17         (a product has lb = 1; limb-wise sums add their bounds, at most 4:
+//                                                               the reduction reads l[i] as a uint32, and as an int32 where lb <= 3)
+//   value bound wb : |value| <= wb * q^2                         (the top limb is below wb * 2^14.3 in magnitude)
+// a*u + c*v as the carry-propagated 18-limb column sum, NO reduction: 162 multiply-adds, and per column the mask and the 64-bit shift that
+// the reducing leaf spends on its upper nine columns.  Operands and column bound as fe_mul2 (la*lu + lc*lv <= 6), value bound
+// wb = A*U + C*V <= 1024 (the top limb stays far inside 32 bits).
+BN_FN FeW fe_wmul2(const Fe &a, const Fe &u, const Fe &c, const Fe &v) {
+#if !defined(BN_HOSTSIM)
+    return fe_wmul2_asm(a, u, c, v);
+#endif
+    BN_COUNT(mul2); BN_COUNT_MACS(162);
+    BN_REQUIRE(!a.sg && !u.sg && !c.sg && !v.sg, "fe_wmul2 on a signed lazy value");
+    BN_REQUIRE(a.lb * u.lb + c.lb * v.lb <= 6, "fe_wmul2 column overflow");
+    BN_REQUIRE(a.vb * u.vb + c.vb * v.vb <= 1024, "fe_wmul2 value bound");
+    uint64_t acc = 0;
+    FeW r;
+#pragma unroll
+    for (int col = 0; col < 17; ++col) {
+        const int lo = col < 9 ? 0 : col - 8, hi = col < 9 ? col : 8;
+#pragma unroll
+        for (int i = lo; i <= hi; ++i) {
+            acc += (uint64_t)a.l[i] * u.l[col - i];
+            acc += (uint64_t)c.l[i] * v.l[col - i];
+        }
+        r.l[col] = (uint32_t)acc & MASK29;
+        acc >>= 29;
+    }
+    r.l[17] = (uint32_t)acc;
+    BN_IFB(r.lb = 1; r.wb = a.vb * u.vb + c.vb * v.vb;)
+    BN_VERIFYW(r, "fe_wmul2");
+    return r;
+}
+// the same over SIGNED operands (fe_sdiff values, |limb| < 2^29; bounds as fe_mul2s: la*lu + lc*lv <= 2): arithmetic column shifts,
+// the sign ends up in the top limb
+BN_FN FeW fe_wmul2s(const Fe &a, const Fe &u, const Fe &c, const Fe &v) {
+#if !defined(BN_HOSTSIM)
+    return fe_wmul2s_asm(a, u, c, v);
+#endif
+    BN_COUNT(mul2); BN_COUNT_MACS(162);
+    BN_REQUIRE(a.lb * u.lb + c.lb * v.lb <= 2, "fe_wmul2s column overflow");
+    BN_REQUIRE(a.vb * u.vb + c.vb * v.vb <= 1024, "fe_wmul2s value bound");
+    int64_t acc = 0;
+    FeW r;
+#pragma unroll
+    for (int col = 0; col < 17; ++col) {
+        const int lo = col < 9 ? 0 : col - 8, hi = col < 9 ? col : 8;
+#pragma unroll
+        for (int i = lo; i <= hi; ++i) {
+            acc += (int64_t)(int32_t)a.l[i] * (int64_t)(int32_t)u.l[col - i];
+            acc += (int64_t)(int32_t)c.l[i] * (int64_t)(int32_t)v.l[col - i];
+        }
+        r.l[col] = (uint32_t)acc & MASK29;
+        acc >>= 29;
+    }
+    r.l[17] = (uint32_t)acc;
+    BN_IFB(r.lb = 1; r.wb = a.vb * u.vb + c.vb * v.vb;)
+    BN_VERIFYW(r, "fe_wmul2s");
+    return r;
+}
+// limb-wise sum of wide values (the Karatsuba sums X_ij = m_ij + v_i + v_j): 18 plain adds, no carries
+BN_FN FeW fe_wadd(const FeW &x, const FeW &y) {
+    BN_COUNT(addsub);
+    BN_REQUIRE(x.lb + y.lb <= 4, "fe_wadd limb overflow (four 29-bit limbs fill a uint32)");
+    FeW r;
+#pragma unroll
+    for (int i = 0; i < 18; ++i) r.l[i] = x.l[i] + y.l[i];
+    BN_IFB(r.lb = x.lb + y.lb; r.wb = x.wb + y.wb;)
+    BN_VERIFYW(r, "fe_wadd");
+    return r;
+}
+// The wide reduction: Montgomery reduction of  n + [XI] (9 x + s px) - [SUB] d R  in ONE signed 64-bit column chain, result in standard
+// form S.  The three combinations of an Fq6 product are
+//     c0 = v0 + xi X12      (n = v0,  x = X12)          c1 = X01 + xi v2      (n = X01, x = v2)          c2 = X02 + v1      (n = X02 + v1, no xi)
+// with px the partner lane's x and s = -1 on the even, +1 on the odd lane (xi W = 9 W -+ pW, as in fe_lc3_par).  d is an element in
+// standard or lazy unsigned form that is subtracted from the RESULT (it enters the upper nine columns): the aa + bb of an Fq12 product's
+// cross term.
+//   columns 0..8:   carry + n_c + 9 x_c + s px_c + sum_{i<c} m_i q_(c-i),  m_c = the Montgomery digit, + m_c q_0, shift
+//   columns 9..17:  carry + n_c + 9 x_c + s px_c + sum m_i q_(c-i) - kq q_(c-9) - d_(c-9)
+// kq is the quotient estimate of the fused reductions (fe_lc4_core), taken from the top limbs BEFORE the chain starts: with T the value of
+// the combination, te <= T / 2^493 (margins: 9 per unit coefficient for what limb 16 holds beyond 29 bits and for the sign of s, 600 for
+// the truncation of FE_MU24), so kq <= T / (R q) and kq > T / (R q) - 1.001.  The result (T + m q) / R - kq q, m < R, lies in [0, 2.001 q).
+// Bounds: n.lb <= 4 (read as uint32 below the top limb), x.lb <= 3 (read as int32), d.lb <= 3;
+//   n.wb + 10 x.wb + 170 d.vb <= 40000  (|te| < 2^31; every column sum: 9 x 2^58 + 11 x 2^31 x 9 + carry < 2^63).
+// Multiply instructions: 9 (digits) + 81 (m q) + 9 (kq q) + 1 (estimate), and per column one per term: 18 for n, 36 for xi x, 9 for d.
+template <bool XI, bool SUB>
+BN_FN Fe fe_wred(const FeW &n, const FeW &x, const FeW &px, bool neg, const Fe &d) {
+    BN_COUNT(reduce); BN_COUNT_MACS(100 + 18 + (XI ? 36 : 0) + (SUB ? 9 : 0));
+    BN_REQUIRE(n.lb <= 4 && (!XI || (x.lb <= 3 && px.lb <= 3)), "fe_wred limb bounds");
+    BN_REQUIRE(!SUB || (d.lb <= 3 && !d.sg), "fe_wred subtrahend limbs");
+    BN_REQUIRE((uint64_t)n.wb + (XI ? 9ull * x.wb + px.wb : 0ull) + (SUB ? 170ull * d.vb : 0ull) <= 40000, "fe_wred value bound");
+    const int32_t s = neg ? -1 : 1;
+    int32_t te = -600 - 9 * (1 + (XI ? 10 : 0) + (SUB ? 1 : 0)) + (int32_t)n.l[17];
+    if (XI) te += 9 * (int32_t)x.l[17] + s * (int32_t)px.l[17];
+    if (SUB) te -= (int32_t)d.l[8];
+    const int64_t kq = ((int64_t)te * (int64_t)k::FE_MU24) >> 45;
+#if !defined(BN_HOSTSIM)
+    return fe_wred_asm<XI, SUB>(n, x, px, s, d, (int32_t)kq);
+#else
+    int64_t acc = 0;
+    uint32_t m[9];
+    Fe r;
+#pragma unroll
+    for (int col = 0; col < 18; ++col) {
+        acc += col < 17 ? (int64_t)n.l[col] : (int64_t)(int32_t)n.l[col];
+        if (XI) acc += 9 * (int64_t)(int32_t)x.l[col] + (int64_t)s * (int64_t)(int32_t)px.l[col];
+        if (col < 9) {
+#pragma unroll
+            for (int i = 0; i < col; ++i) acc += (int64_t)((uint64_t)m[i] * k::Q[col - i]);
+            m[col] = ((uint32_t)acc * k::QINV) & MASK29;
+            acc += (int64_t)((uint64_t)m[col] * k::Q[0]);
+        } else {
+#pragma unroll
+            for (int i = col - 8; i <= 8; ++i) acc += (int64_t)((uint64_t)m[i] * k::Q[col - i]);
+            acc -= kq * (int64_t)k::Q[col - 9];
+            if (SUB) acc -= (int64_t)d.l[col - 9];
+            r.l[col - 9] = col < 17 ? ((uint32_t)acc & MASK29) : (uint32_t)acc;
+        }
+        acc >>= 29;
+    }
+    BN_SETB(r, 1, 3);
+    BN_VERIFY(r, "fe_wred");
+    return r;
+#endif
+}
+
 // (a1 u1 + c1 v1 + a2 u2 + c2 v2 + a3 u3 + c3 v3) / R with ONE reduction: 486 + 81 mads.  Three Fq2 products of the lane-pair mapping summed
 // before they are reduced (tower.hpp f12_mul_by_024: every output coefficient of the sparse line product is such a sum).
 // Column bound: 6 * 9 + 9 = 63 terms of (2^29 - 1)^2 plus a carry stay below 2^64 ONLY for normalized limbs - every operand must have lb = 1.

@@ -255,9 +255,7 @@ BN_FN Fe f2b_sqr_gpu(const Fe &a) {
 #undef BN_SQ
     return fe_mul_body(s, t);
 }
-BN_FN Fe f2b_muls_gpu(const Fe &a, const Fe &b) {        // signed operands: the even lane's negation is a plain 0 - x
-    const Fe a0 = lane_dpp_even(a), a1 = lane_dpp_odd(a);
-    Fe x = lane_partner_x(b);
+BN_FN void fe_sneg_on_even_lanes(Fe &x) {            // x <- 0 - x on the even lanes (signed operands: no bias)
     uint64_t saved;
     asm("s_and_saveexec_b64 %[sv], %[m]\n\t"
         "v_sub_u32 %[x0], 0, %[x0]\n\tv_sub_u32 %[x1], 0, %[x1]\n\tv_sub_u32 %[x2], 0, %[x2]\n\t"
@@ -268,6 +266,11 @@ BN_FN Fe f2b_muls_gpu(const Fe &a, const Fe &b) {        // signed operands: the
           [x7] "+v"(x.l[7]), [x8] "+v"(x.l[8]), [sv] "=&s"(saved)
         : [m] "s"(BN_EVEN_LANES)
         : "scc");
+}
+BN_FN Fe f2b_muls_gpu(const Fe &a, const Fe &b) {        // signed operands: the even lane's negation is a plain 0 - x
+    const Fe a0 = lane_dpp_even(a), a1 = lane_dpp_odd(a);
+    Fe x = lane_partner_x(b);
+    fe_sneg_on_even_lanes(x);
     return fe_mul2s(a0, b, a1, x);
 }
 BN_LEAF_MUL u32x9 f2b_muls_leaf(u32x9 a, u32x9 b) { return bn_tov(f2b_muls_gpu(bn_unv(a), bn_unv(b))); }
@@ -284,6 +287,73 @@ template <class T> BN_FN T f2b_sqr(const T &a) { return f2b_sqr_body(a); }
 template <class T> BN_FN T f2b_mul_inl(const T &a, const T &b) { return f2b_mul_body(a, b); }
 template <class T> BN_FN T f2b_sqr_inl(const T &a) { return f2b_sqr_body(a); }
 template <class T> BN_FN T f2b_muls(const T &a, const T &b) { return f2b_muls_body(a, b); }
+#endif
+
+// The lane-pair product WITHOUT its reduction (fe.hpp FeW): this lane's component of a * b as the 18-limb column sum of the dual product, for
+// the lazily reduced Karatsuba products of tower.hpp (f6_mul_lazy).  Operands as f2b_mul resp. f2b_muls; f2b_wred_xi / f2b_wred take a linear
+// combination of such values back to standard form S with ONE Montgomery reduction:
+//     f2b_wred_xi<SUB>(n, x, d) = reduce(n + xi x) - d          f2b_wred<SUB>(n, d) = reduce(n) - d
+#if !defined(BN_HOSTSIM)
+template <class T> struct Fq2BWide { FeW w; };
+BN_FN Fq2BWide<Fe> f2b_wmul(const Fe &a, const Fe &b) {
+    const Fe a0 = lane_dpp_even(a), a1 = lane_dpp_odd(a);
+    Fe x = lane_partner_x(b);
+    fe_neg_on_even_lanes<1, 9>(x);
+    return {fe_wmul2(a0, b, a1, x)};
+}
+BN_FN Fq2BWide<Fe> f2b_wmuls(const Fe &a, const Fe &b) {
+    const Fe a0 = lane_dpp_even(a), a1 = lane_dpp_odd(a);
+    Fe x = lane_partner_x(b);
+    fe_sneg_on_even_lanes(x);
+    return {fe_wmul2s(a0, b, a1, x)};
+}
+BN_FN Fq2BWide<Fe> f2b_wadd(const Fq2BWide<Fe> &x, const Fq2BWide<Fe> &y) { return {fe_wadd(x.w, y.w)}; }
+template <bool SUB>
+BN_FN Fe f2b_wred_xi(const Fq2BWide<Fe> &n, const Fq2BWide<Fe> &x, const Fe &d) {
+    FeW px;
+#pragma unroll
+    for (int i = 0; i < 18; ++i) px.l[i] = (uint32_t)__builtin_amdgcn_mov_dpp((int)x.w.l[i], 0xB1, 0xF, 0xF, true);
+    return fe_wred<true, SUB>(n.w, x.w, px, !lane_is_odd(), d);
+}
+template <bool SUB>
+BN_FN Fe f2b_wred(const Fq2BWide<Fe> &n, const Fe &d) { return fe_wred<false, SUB>(n.w, n.w, n.w, false, d); }
+#else
+// host simulation: T is a value type of 2 (lanepair.hpp) or 4 (lanequad.hpp) simulated lanes, each an Fe, even lanes first in every pair
+template <class T> struct Fq2BWide { FeW w[sizeof(T) / sizeof(Fe)]; };
+template <class T> BN_FN const Fe &lane_of(const T &x, int i) { return reinterpret_cast<const Fe *>(&x)[i]; }
+template <class T>
+BN_FN Fq2BWide<T> f2b_wmul(const T &a, const T &b) {
+    const T pa = lane_partner(a), pb = lane_partner(b), u = lane_pick(b, pb), v = lane_pick(fe_neg<1, 9>(pb), b);
+    Fq2BWide<T> r;
+    for (int i = 0; i < (int)(sizeof(T) / sizeof(Fe)); ++i) r.w[i] = fe_wmul2(lane_of(a, i), lane_of(u, i), lane_of(pa, i), lane_of(v, i));
+    return r;
+}
+template <class T>
+BN_FN Fq2BWide<T> f2b_wmuls(const T &a, const T &b) {
+    const T pa = lane_partner(a), pb = lane_partner(b), u = lane_pick(b, pb), v = lane_pick(fe_sneg(pb), b);
+    Fq2BWide<T> r;
+    for (int i = 0; i < (int)(sizeof(T) / sizeof(Fe)); ++i) r.w[i] = fe_wmul2s(lane_of(a, i), lane_of(u, i), lane_of(pa, i), lane_of(v, i));
+    return r;
+}
+template <class T>
+BN_FN Fq2BWide<T> f2b_wadd(const Fq2BWide<T> &x, const Fq2BWide<T> &y) {
+    Fq2BWide<T> r;
+    for (int i = 0; i < (int)(sizeof(T) / sizeof(Fe)); ++i) r.w[i] = fe_wadd(x.w[i], y.w[i]);
+    return r;
+}
+template <bool SUB, class T>
+BN_FN T f2b_wred_xi(const Fq2BWide<T> &n, const Fq2BWide<T> &x, const T &d) {
+    T r = d;
+    for (int i = 0; i < (int)(sizeof(T) / sizeof(Fe)); ++i)
+        reinterpret_cast<Fe *>(&r)[i] = fe_wred<true, SUB>(n.w[i], x.w[i], x.w[i ^ 1], (i & 1) == 0, lane_of(d, i));
+    return r;
+}
+template <bool SUB, class T>
+BN_FN T f2b_wred(const Fq2BWide<T> &n, const T &d) {
+    T r = d;
+    for (int i = 0; i < (int)(sizeof(T) / sizeof(Fe)); ++i) reinterpret_cast<Fe *>(&r)[i] = fe_wred<false, SUB>(n.w[i], n.w[i], n.w[i], false, lane_of(d, i));
+    return r;
+}
 #endif
 
 // A multiplier PREPARED for the lane-pair product: (u, v) such that this lane's component of a * b is own_a * u + partner_a * v.  With

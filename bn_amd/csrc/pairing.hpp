@@ -492,6 +492,8 @@ BN_FN Fq12<F2> final_exponentiation(const Fq12<F2> &f) {
 // form).  The power is a unique field element, so any addition chain returns the reference's bytes: fixed 4-bit windows, MSB first -
 // 256 squarings + 64 table products + a 14-operation table.  General Fq12 squarings (not cyclotomic ones): correct for ANY Fq12.
 // `tbl`: 16 Fq12 entries with put(e, v) / c0(e) / c1(e) (per-lane global memory in the kernel, plain variables in the host simulation).
+// Products and squarings of the Gt::pow chains keep the EAGER form (f12_mul_src<false>, f12_sqr<true, false>): with the wide values of the
+// lazily reduced form the window loops of bn254_gt_pow_B spill.
 template <class F2, class Tbl>
 BN_FN Fq12<F2> gt_pow_windowed(const Fq12<F2> &base, const uint32_t *k_raw, Tbl &tbl) {
     tbl.put(0, f12_one<F2>());
@@ -499,8 +501,8 @@ BN_FN Fq12<F2> gt_pow_windowed(const Fq12<F2> &base, const uint32_t *k_raw, Tbl 
 #pragma unroll 1
     for (int e = 2; e < 16; ++e) {                 // a^e = (a^(e/2))^2 for even e, a^(e-1) * a for odd e
         Fq12<F2> v;
-        if ((e & 1) == 0) v = f12_sqr<true>(Fq12<F2>{tbl.c0(e >> 1), tbl.c1(e >> 1)});
-        else v = f12_mul_src(Fq12<F2>{tbl.c0(e - 1), tbl.c1(e - 1)}, Fq12Slot<F2, Tbl>{tbl, 1}, false);
+        if ((e & 1) == 0) v = f12_sqr<true, false>(Fq12<F2>{tbl.c0(e >> 1), tbl.c1(e >> 1)});
+        else v = f12_mul_src<false>(Fq12<F2>{tbl.c0(e - 1), tbl.c1(e - 1)}, Fq12Slot<F2, Tbl>{tbl, 1}, false);
         tbl.put(e, v);
     }
     Fq12<F2> res = f12_one<F2>();
@@ -508,9 +510,9 @@ BN_FN Fq12<F2> gt_pow_windowed(const Fq12<F2> &base, const uint32_t *k_raw, Tbl 
     for (int w = 63; w >= 0; --w) {
         BN_EXP_HOOK(63 - w, 64);
 #pragma unroll 1
-        for (int d = 0; d < 4; ++d) res = f12_sqr<true>(res);
+        for (int d = 0; d < 4; ++d) res = f12_sqr<true, false>(res);
         const int digit = (int)((k_raw[w >> 3] >> ((w & 7) * 4)) & 15u);          // per lane pair: both lanes hold the same scalar
-        res = f12_mul_src(res, Fq12Slot<F2, Tbl>{tbl, digit}, false);
+        res = f12_mul_src<false>(res, Fq12Slot<F2, Tbl>{tbl, digit}, false);
     }
     return res;
 }
@@ -545,7 +547,7 @@ BN_FN Fq12<F2> gt_pow_cyclotomic(const Fq12<F2> &base, const uint32_t *k_raw, Tb
     for (int e = 2; e <= 8; ++e) {                 // a^e = (a^(e/2))^2 for even e, a^(e-1) * a for odd e
         Fq12<F2> v;
         if ((e & 1) == 0) v = f12_cyclotomic_sqr(Fq12<F2>{tbl.c0(e >> 1), tbl.c1(e >> 1)});
-        else v = f12_mul_src(Fq12<F2>{tbl.c0(e - 1), tbl.c1(e - 1)}, Fq12Slot<F2, Tbl>{tbl, 1}, false);
+        else v = f12_mul_src<false>(Fq12<F2>{tbl.c0(e - 1), tbl.c1(e - 1)}, Fq12Slot<F2, Tbl>{tbl, 1}, false);
         tbl.put(e, v);
     }
     Fq12<F2> res = f12_one<F2>();
@@ -560,7 +562,7 @@ BN_FN Fq12<F2> gt_pow_cyclotomic(const Fq12<F2> &base, const uint32_t *k_raw, Tb
         // res * conj(t) = conj(conj(res) * t): the sign is applied to the running value (in registers anyway), so the table operand
         // takes the same path as in the exponentiation machine (conjugating the operand on load cost 97 spilled VGPRs)
         res.c1 = f6_cond_neg(digit < 0, res.c1);
-        res = f12_mul_src(res, Fq12Slot<F2, Tbl>{tbl, digit < 0 ? -digit : digit}, false);
+        res = f12_mul_src<false>(res, Fq12Slot<F2, Tbl>{tbl, digit < 0 ? -digit : digit}, false);
         res.c1 = f6_cond_neg(digit < 0, res.c1);
     }
     return res;

@@ -55,6 +55,29 @@ BN_COARSE Fq6Raw<F2> f6_mul_raw(const Fq6<F2> &a, const Fq6<F2> &b) {
     r.x02 = f2_cross(a.c0, a.c2, b.c0, b.c2, r.v0, r.v2);
     return r;
 }
+// The same product in the lane-pair mapping by LAZY REDUCTION at double width (fe.hpp FeW): the six Karatsuba products stay unreduced
+// (6 x 162 multiply-adds), the recombination and the multiplication by xi run on the unreduced 18-limb values, and each output coefficient
+// pays ONE Montgomery reduction (fe_wred) - three per product where f6_mul pays six inside its dual products and three fused range
+// reductions after them.  With SUB the element d is subtracted from the result inside the same reductions (the aa + bb of an Fq12
+// product's cross term, ab + v ab of a square's).  1398 (+ 27 with SUB) multiply instructions per lane against 1605 (1632 for f6_mul_raw and
+// its recombination).  Order: every wide value dies at the reduction that consumes it; v0, v1, v2 and one cross product are alive together.
+//     X_ij = (a_i - a_j)(b_j - b_i) + v_i + v_j = a_i b_j + a_j b_i       c1 = X01 + xi v2,   c2 = X02 + v1,   c0 = v0 + xi X12
+template <bool SUB, class T>
+BN_COARSE Fq6<Fq2B<T>> f6_mul_lazy(const Fq6<Fq2B<T>> &a, const Fq6<Fq2B<T>> &b, const Fq6<Fq2B<T>> &d) {
+    typedef Fq2BWide<T> W;
+    Fq6<Fq2B<T>> r;
+    const W v0 = f2b_wmul(a.c0.v, b.c0.v), v1 = f2b_wmul(a.c1.v, b.c1.v);
+    const W x01 = f2b_wadd(f2b_wadd(f2b_wmuls(fe_sdiff(a.c0.v, a.c1.v), fe_sdiff(b.c1.v, b.c0.v)), v0), v1);
+    const W v2 = f2b_wmul(a.c2.v, b.c2.v);
+    r.c1.v = f2b_wred_xi<SUB>(x01, v2, d.c1.v);
+    const W x02 = f2b_wadd(f2b_wadd(f2b_wadd(f2b_wmuls(fe_sdiff(a.c0.v, a.c2.v), fe_sdiff(b.c2.v, b.c0.v)), v0), v2), v1);
+    r.c2.v = f2b_wred<SUB>(x02, d.c2.v);
+    const W x12 = f2b_wadd(f2b_wadd(f2b_wmuls(fe_sdiff(a.c1.v, a.c2.v), fe_sdiff(b.c2.v, b.c1.v)), v1), v2);
+    r.c0.v = f2b_wred_xi<SUB>(v0, x12, d.c0.v);
+    return r;
+}
+template <class T>
+BN_FN Fq6<Fq2B<T>> f6_mul_lazy(const Fq6<Fq2B<T>> &a, const Fq6<Fq2B<T>> &b) { return f6_mul_lazy<false>(a, b, a); }
 // fq6.rs:113-127 (CH-SQR2)
 template <class F2>
 BN_COARSE Fq6<F2> f6_sqr(const Fq6<F2> &a) {
@@ -100,7 +123,7 @@ struct Fq12Ref {
     BN_FN Fq6<F2> c1() const { return x.c1; }
 };
 template <class F2, class BSrc>
-BN_FN Fq12<F2> f12_mul_src(const Fq12<F2> &a, const BSrc &b, bool conj_b) {
+BN_FN Fq12<F2> f12_mul_src_eager(const Fq12<F2> &a, const BSrc &b, bool conj_b) {
     // the Karatsuba cross term first: it is the only product that needs both halves of a and of b at once
     Fq6<F2> b1 = b.c1();
     if (conj_b) b1 = f6_neg(b1);
@@ -117,6 +140,30 @@ BN_FN Fq12<F2> f12_mul_src(const Fq12<F2> &a, const BSrc &b, bool conj_b) {
     r.c0.c2 = f2_lc3<1, 1, 0>(aa.c2, bb.c1, bb.c1);
     return r;
 }
+// WIDE: a caller's choice between the form above and the lazily reduced one of the lane-pair mapping below (the other mappings have one form);
+// a kernel whose register allocation does not hold the wide values keeps the eager form by naming f12_mul_src<false> / f12_sqr<.., false>
+template <bool WIDE = true, class F2, class BSrc>
+BN_FN Fq12<F2> f12_mul_src(const Fq12<F2> &a, const BSrc &b, bool conj_b) { return f12_mul_src_eager(a, b, conj_b); }
+// The lane-pair mapping with lazily reduced Fq6 products (f6_mul_lazy).  The cross term comes LAST here: its reductions subtract aa + bb
+// themselves, so nothing of it has to wait in registers while aa and bb are computed.
+template <bool WIDE = true, class T, class BSrc>
+BN_FN Fq12<Fq2B<T>> f12_mul_src(const Fq12<Fq2B<T>> &a, const BSrc &b, bool conj_b) {
+    typedef Fq2B<T> F2;
+    if constexpr (!WIDE) return f12_mul_src_eager(a, b, conj_b);
+    else {
+        Fq6<F2> b1 = b.c1();
+        if (conj_b) b1 = f6_neg(b1);
+        const Fq6<F2> bb = f6_mul_lazy(a.c1, b1);
+        const Fq6<F2> aa = f6_mul_lazy(a.c0, b.c0());
+        Fq12<F2> r;
+        r.c0.c0 = f2_lc_xi<1, 1>(bb.c2, aa.c0);                  // aa + v*bb
+        r.c0.c1 = f2_lc3<1, 1, 0>(aa.c1, bb.c0, bb.c0);
+        r.c0.c2 = f2_lc3<1, 1, 0>(aa.c2, bb.c1, bb.c1);
+        const Fq6<F2> d = {f2_add(aa.c0, bb.c0), f2_add(aa.c1, bb.c1), f2_add(aa.c2, bb.c2)};
+        r.c1 = f6_mul_lazy<true>(f6_add_norm(a.c0, a.c1), f6_add_norm(b.c0(), b1), d);      // s t - aa - bb
+        return r;
+    }
+}
 template <class F2>
 BN_COARSE Fq12<F2> f12_mul(const Fq12<F2> &a, const Fq12<F2> &b) { return f12_mul_src(a, Fq12Ref<F2>{b}, false); }
 // fq12.rs:275-282 (complex squaring over Fq6)
@@ -125,7 +172,7 @@ BN_COARSE Fq12<F2> f12_mul(const Fq12<F2> &a, const Fq12<F2> &b) { return f12_mu
 // with c1 < 4q the Karatsuba sums of the NEXT squaring can exceed the 9q bias of the lane-pair product (found by the host
 // simulation's bound checks; actual values stay far below, but the bound must hold by construction).
 template <bool REDUCED_C1 = false, class F2>
-BN_COARSE Fq12<F2> f12_sqr(const Fq12<F2> &a) {
+BN_COARSE Fq12<F2> f12_sqr_eager(const Fq12<F2> &a) {
     Fq6<F2> ab = f6_mul(a.c0, a.c1);
     Fq6<F2> u;                                                // v*c1 + c0
     u.c0 = f2_lc_xi<1, 1>(a.c1.c2, a.c0.c0);
@@ -140,6 +187,27 @@ BN_COARSE Fq12<F2> f12_sqr(const Fq12<F2> &a) {
     if constexpr (REDUCED_C1) r.c1 = f6_lc3<2, 0, 0>(ab, ab, ab);
     else r.c1 = f6_add_norm(ab, ab);                           // 2ab as a plain sum (carries propagated)
     return r;
+}
+template <bool REDUCED_C1 = false, bool WIDE = true, class F2>
+BN_FN Fq12<F2> f12_sqr(const Fq12<F2> &a) { return f12_sqr_eager<REDUCED_C1>(a); }
+// The lane-pair mapping with lazily reduced Fq6 products: t - (ab + v ab) leaves the reductions of t finished.
+template <bool REDUCED_C1 = false, bool WIDE = true, class T>
+BN_COARSE Fq12<Fq2B<T>> f12_sqr(const Fq12<Fq2B<T>> &a) {
+    typedef Fq2B<T> F2;
+    if constexpr (!WIDE) return f12_sqr_eager<REDUCED_C1>(a);
+    else {
+        const Fq6<F2> ab = f6_mul_lazy(a.c0, a.c1);
+        Fq6<F2> u;                                                // v*c1 + c0
+        u.c0 = f2_lc_xi<1, 1>(a.c1.c2, a.c0.c0);
+        u.c1 = f2_sum_for_mul(a.c1.c0, a.c0.c1);
+        u.c2 = f2_sum_for_mul(a.c1.c1, a.c0.c2);
+        const Fq6<F2> d = {f2_lc_xi<1, 1>(ab.c2, ab.c0), f2_add(ab.c1, ab.c0), f2_add(ab.c2, ab.c1)};      // ab + v ab
+        Fq12<F2> r;
+        r.c0 = f6_mul_lazy<true>(f6_add_norm(a.c0, a.c1), u, d);
+        if constexpr (REDUCED_C1) r.c1 = f6_lc3<2, 0, 0>(ab, ab, ab);
+        else r.c1 = f6_add_norm(ab, ab);
+        return r;
+    }
 }
 // fq12.rs:103-105
 template <class F2> BN_OUTER Fq12<F2> f12_conj(const Fq12<F2> &a) { return {a.c0, f6_neg(a.c1)}; }
@@ -338,7 +406,9 @@ BN_COARSE Fq12<F2> f12_cyclotomic_sqr(const Fq12<F2> &f) {
 }
 
 // out-of-line twins for the straight-line (non-loop) callers
-template <class F2> BN_OUTER Fq12<F2> f12_mul_o(const Fq12<F2> &a, const Fq12<F2> &b) { return f12_mul(a, b); }
+// (the eager form: both operands are in registers here, and the wide values on top of them do not fit - bn254_gt_mul_B and the product
+// kernels would spill)
+template <class F2> BN_OUTER Fq12<F2> f12_mul_o(const Fq12<F2> &a, const Fq12<F2> &b) { return f12_mul_src<false>(a, Fq12Ref<F2>{b}, false); }
 
 #undef F2P
 }  // namespace bn254
