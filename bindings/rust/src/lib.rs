@@ -37,6 +37,14 @@ extern "C" {
     fn bn254_g1_map_to_curve_batch_dev(ctx: *mut c_void, d_u: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_g1_hash_to_curve_uniform_batch_dev(ctx: *mut c_void, d_uniform: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_g1_hash_to_curve_batch_dev(ctx: *mut c_void, d_msgs: *const c_void, msg_len: usize, dst: *const u8, dst_len: usize, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_g2_map_to_curve_batch(ctx: *mut c_void, u: *const u8, out: *mut G2, n: usize) -> c_int;
+    fn bn254_g2_clear_cofactor_batch(ctx: *mut c_void, p: *const G2, out: *mut G2, n: usize) -> c_int;
+    fn bn254_g2_hash_to_curve_uniform_batch(ctx: *mut c_void, uniform: *const u8, out: *mut G2, n: usize) -> c_int;
+    fn bn254_g2_hash_to_curve_batch(ctx: *mut c_void, msgs: *const u8, msg_len: usize, dst: *const u8, dst_len: usize, out: *mut G2, n: usize) -> c_int;
+    fn bn254_g2_map_to_curve_batch_dev(ctx: *mut c_void, d_u: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_g2_clear_cofactor_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_g2_hash_to_curve_uniform_batch_dev(ctx: *mut c_void, d_uniform: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_g2_hash_to_curve_batch_dev(ctx: *mut c_void, d_msgs: *const c_void, msg_len: usize, dst: *const u8, dst_len: usize, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     // prepared-G2 mode (the crate's internal G2Precomp, src/groups/mod.rs:472-483): 102 line coefficients per Q, then many P against them
     fn bn254_g2_precompute(ctx: *mut c_void, q: *const G2, coeffs: *mut EllCoeffs, n: usize) -> c_int;
     fn bn254_pairing_prepared_batch(ctx: *mut c_void, p: *const G1, coeffs: *const EllCoeffs, shared: c_int, out: *mut Gt, n: usize) -> c_int;
@@ -619,6 +627,45 @@ pub fn g1_hash_to_curve_batch(msgs: &[u8], msg_len: usize, n: usize, dst: &[u8])
     assert_eq!(msgs.len(), n * msg_len);
     let mut out = vec![G1::zero(); n];
     check(unsafe { bn254_g1_hash_to_curve_batch(std::ptr::null_mut(), msgs.as_ptr(), msg_len, dst.as_ptr(), dst.len(), out.as_mut_ptr(), n) })?;
+    Ok(out)
+}
+
+// the same for G2: an Fq2 element is c0 then c1 (BN254_H2C_G2_FIELD_BYTES), a uniform record u0.c0 | u0.c1 | u1.c0 | u1.c1 (BN254_H2C_G2_UNIFORM_BYTES)
+const H2C_G2_FIELD_BYTES: usize = 96;
+const H2C_G2_UNIFORM_BYTES: usize = 192;
+
+/// map_to_curve of RFC 9380 over Fq2 (Shallue-van de Woestijne, Z = 1) on every 96-byte element of `u`: (x, y, 1) on the twist, never infinity
+/// and NOT in G2 - clear the cofactor before any other use.  The map's constants are derived from the RFC's formulas; neither they nor the
+/// outputs are checked against gnark-crypto or any other library.
+pub fn g2_map_to_curve_batch(u: &[u8]) -> Result<Vec<G2>, GpuError> {
+    assert_eq!(u.len() % H2C_G2_FIELD_BYTES, 0);
+    let mut out = vec![G2::zero(); u.len() / H2C_G2_FIELD_BYTES];
+    check(unsafe { bn254_g2_map_to_curve_batch(std::ptr::null_mut(), u.as_ptr(), out.as_mut_ptr(), out.len()) })?;
+    Ok(out)
+}
+
+/// clear(P) = [u]P + psi([3u]P) + psi^2([u]P) + psi^3(P), normalised, for any Jacobian point of the twist (on the curve: the caller's
+/// responsibility): a point of G2, G2::zero() for infinity.  Not [2q - r]P; not checked against gnark-crypto or any other library.
+pub fn g2_clear_cofactor_batch(p: &[G2]) -> Result<Vec<G2>, GpuError> {
+    let mut out = vec![G2::zero(); p.len()];
+    check(unsafe { bn254_g2_clear_cofactor_batch(std::ptr::null_mut(), p.as_ptr(), out.as_mut_ptr(), p.len()) })?;
+    Ok(out)
+}
+
+/// hash_to_curve from 192 uniform bytes per record: clear(map(u0) + map(u1)), normalised (G2::zero() when the two maps cancel)
+pub fn g2_hash_to_curve_uniform_batch(uniform: &[u8]) -> Result<Vec<G2>, GpuError> {
+    assert_eq!(uniform.len() % H2C_G2_UNIFORM_BYTES, 0);
+    let mut out = vec![G2::zero(); uniform.len() / H2C_G2_UNIFORM_BYTES];
+    check(unsafe { bn254_g2_hash_to_curve_uniform_batch(std::ptr::null_mut(), uniform.as_ptr(), out.as_mut_ptr(), out.len()) })?;
+    Ok(out)
+}
+
+/// hash_to_curve into G2 of `n` messages of `msg_len` bytes each, back to back in `msgs` (`msg_len` may be 0), with expand_message_xmd over
+/// SHA-256 on the device; `dst` holds 1 .. 255 bytes
+pub fn g2_hash_to_curve_batch(msgs: &[u8], msg_len: usize, n: usize, dst: &[u8]) -> Result<Vec<G2>, GpuError> {
+    assert_eq!(msgs.len(), n * msg_len);
+    let mut out = vec![G2::zero(); n];
+    check(unsafe { bn254_g2_hash_to_curve_batch(std::ptr::null_mut(), msgs.as_ptr(), msg_len, dst.as_ptr(), dst.len(), out.as_mut_ptr(), n) })?;
     Ok(out)
 }
 

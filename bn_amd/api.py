@@ -170,6 +170,9 @@ class G2(_Point):
         return g2_msm(points, scalars)
     def mul_base(self, scalars):
         return g2_mul_base(self, scalars)
+    @staticmethod
+    def hash(msg, dst):                   # hash_to_curve of RFC 9380 over Fq2 (SvdW, SHA-256 XMD) and the psi-based cofactor clearing
+        return g2_hash_to_curve_batch([msg], dst)[0]
     def to_compressed(self, format="ark"):    # 64 bytes
         return g2_compress_batch([self], format)[0]
     @staticmethod
@@ -415,6 +418,41 @@ def g1_hash_to_curve_batch(msgs, dst, engine=None):
     """[hash_to_curve(m) for m in msgs] (RFC 9380, random-oracle variant: SHA-256 XMD, two SvdW maps, one sum) under the domain separation
     tag dst (1 .. 255 bytes).  msgs: a sequence of bytes or an (n, msg_len) uint8 array."""
     return [G1(r) for r in _hash_to_curve_limbs(msgs, dst, engine)]
+
+
+def g2_map_to_curve_batch(us, engine=None):
+    """[map_to_curve(u) for u in us] over Fq2: points (x, y, 1) of the twist, never at infinity and NOT in G2 (g2_clear_cofactor_batch takes
+    them there).  us: a sequence of (c0, c1) pairs of integers below 2^384 (taken mod q) or an (n,96) uint8 array, c0 then c1, big endian."""
+    if not isinstance(us, np.ndarray):
+        us = list(us)
+        us = np.stack([np.frombuffer(int(c0).to_bytes(48, "big") + int(c1).to_bytes(48, "big"), np.uint8) for c0, c1 in us]) if us else np.zeros((0, 96), np.uint8)
+    return [G2(r) for r in (engine or default_engine()).g2_map_to_curve_batch(us)]
+
+
+def g2_clear_cofactor_batch(points, engine=None):
+    """[clear(p) for p in points], clear(P) = [u]P + psi([3u]P) + psi^2([u]P) + psi^3(P), normalised: a point of G2 for every point of the twist
+    (being on the curve is the caller's responsibility).  Not [2q - r]P; on G2 it is a fixed scalar.  Neither the constants nor the outputs are checked against gnark-crypto or any other
+    library."""
+    return [G2(r) for r in (engine or default_engine()).g2_clear_cofactor_batch(_point_array(G2, points))]
+
+
+def _g2_hash_to_curve_limbs(msgs, dst, engine):
+    """(n,24) uint64: messages of one length take the device's SHA-256, mixed lengths are expanded with hashlib and take the uniform call"""
+    from . import hash_to_curve as h2c
+    dst = h2c.h2c_dst(dst)
+    if not isinstance(msgs, np.ndarray):
+        msgs = [bytes(m) for m in msgs]
+    e = engine or default_engine()
+    arr = h2c.message_array(msgs)
+    if arr is not None:
+        return e.g2_hash_to_curve_batch(arr, dst)
+    return e.g2_hash_to_curve_uniform_batch(h2c.uniform_bytes_g2(msgs, dst))
+
+
+def g2_hash_to_curve_batch(msgs, dst, engine=None):
+    """[hash_to_curve(m) for m in msgs] into G2 (RFC 9380, random-oracle variant over Fq2: SHA-256 XMD to 192 bytes, two SvdW maps, one sum,
+    the cofactor clearing) under the domain separation tag dst (1 .. 255 bytes).  msgs: a sequence of bytes or an (n, msg_len) uint8 array."""
+    return [G2(r) for r in _g2_hash_to_curve_limbs(msgs, dst, engine)]
 
 
 def g1_normalize_batch(points, engine=None):

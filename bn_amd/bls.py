@@ -6,7 +6,7 @@ H is hash_to_curve of RFC 9380 for G1 (Shallue-van de Woestijne map, SHA-256 XMD
 were derived from the RFC's formulas and are not checked against gnark-crypto or any other library, so signatures made here are not promised to
 verify elsewhere.  Every function is a fixed, small number of engine calls whatever the batch size: hashing is one call (on the device for
 messages of one length), the pairings one call.  Points travel as bn_amd.G1 / G2 or as (n,12) / (n,24) uint64 arrays; messages as a sequence of
-bytes or an (n, msg_len) uint8 array.  Not built: hash to G2 (the min-pubkey layout), proofs of possession themselves, multi-GPU forms."""
+bytes or an (n, msg_len) uint8 array.  The min-pubkey layout (keys in G1, hash to G2) is bn_amd.bls_minpk.  Not built: proofs of possession themselves, multi-GPU forms."""
 import numpy as np
 
 from . import api

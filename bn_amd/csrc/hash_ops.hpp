@@ -167,20 +167,23 @@ BN_FN void sha256_finish(Sha256 &s) {
     s.w[14] = (uint32_t)(bits >> 32); s.w[15] = (uint32_t)bits;
     sha256_block(s);
 }
-// expand_message_xmd(msg, DST, 96) as 24 words.  dst_prime = DST || len(DST), dst_prime_len = len(DST) + 1 <= 256
-BN_FN void h2c_expand_xmd96(const uint8_t *msg, size_t msg_len, const uint8_t *dst_prime, uint32_t dst_prime_len, uint32_t *out) {
+// expand_message_xmd(msg, DST, 32 ELL) as 8 ELL words, ELL <= 7 blocks (the length fits l_i_b_str's low byte: 96 for G1, 192 for G2).
+// dst_prime = DST || len(DST), dst_prime_len = len(DST) + 1 <= 256
+template <uint32_t ELL>
+BN_FN void h2c_expand_xmd(const uint8_t *msg, size_t msg_len, const uint8_t *dst_prime, uint32_t dst_prime_len, uint32_t *out) {
+    static_assert(ELL >= 1 && 32 * ELL <= 255, "h2c_expand_xmd length");
     Sha256 s;
     sha256_init(s);
     sha256_block(s);                                      // Z_pad: 64 zero bytes are one block
     s.total = 64;
     sha256_bytes(s, msg, msg_len);
-    sha256_byte(s, 0); sha256_byte(s, H2C_UNIFORM_BYTES); sha256_byte(s, 0);      // l_i_b_str, then the index 0
+    sha256_byte(s, 0); sha256_byte(s, 32 * ELL); sha256_byte(s, 0);               // l_i_b_str, then the index 0
     sha256_bytes(s, dst_prime, dst_prime_len);
     sha256_finish(s);
     uint32_t b0[8], prev[8];
     for (int i = 0; i < 8; ++i) { b0[i] = s.h[i]; prev[i] = 0; }
 #pragma unroll 1
-    for (uint32_t j = 1; j <= 3; ++j) {
+    for (uint32_t j = 1; j <= ELL; ++j) {
         sha256_init(s);
 #pragma unroll 1
         for (int i = 0; i < 8; ++i) sha256_word(s, b0[i] ^ prev[i]);
@@ -189,6 +192,9 @@ BN_FN void h2c_expand_xmd96(const uint8_t *msg, size_t msg_len, const uint8_t *d
         sha256_finish(s);
         for (int i = 0; i < 8; ++i) { prev[i] = s.h[i]; out[8 * (j - 1) + i] = s.h[i]; }
     }
+}
+BN_FN void h2c_expand_xmd96(const uint8_t *msg, size_t msg_len, const uint8_t *dst_prime, uint32_t dst_prime_len, uint32_t *out) {
+    h2c_expand_xmd<H2C_UNIFORM_BYTES / 32>(msg, msg_len, dst_prime, dst_prime_len, out);
 }
 // message i of msg_len bytes -> hash_to_curve
 template <int INV0 = BN254_H2C_INV0>

@@ -36,6 +36,7 @@ def compressed_format(fmt):
 
 
 H2C_FIELD_BYTES, H2C_UNIFORM_BYTES, H2C_DST_MAX = 48, 96, 255       # BN254_H2C_* of include/bn254_hip.h
+H2C_G2_FIELD_BYTES, H2C_G2_UNIFORM_BYTES = 96, 192                  # BN254_H2C_G2_*
 
 
 def h2c_dst(dst):
@@ -765,6 +766,47 @@ class Engine:
         """device pointers for messages and points; `dst` is host bytes (it travels as a kernel argument)"""
         dst = h2c_dst(dst)
         _native.check(self._lib.bn254_g1_hash_to_curve_batch_dev(self._h, d_msgs, msg_len, dst, len(dst), d_out, n, stream))
+
+    # ---- hash to G2 (RFC 9380 over Fq2 and the cofactor clearing [u]P + psi([3u]P) + psi^2([u]P) + psi^3(P); neither the constants nor the
+    # outputs are checked against gnark-crypto or any other library)
+    def g2_map_to_curve_batch(self, u):
+        """(n,96) uint8: c0 then c1, big-endian integers (taken mod q) -> (n,24) uint64 points (x, y, 1) of the twist, NOT in G2"""
+        u = np.ascontiguousarray(u, np.uint8).reshape(-1, H2C_G2_FIELD_BYTES); out = np.empty((u.shape[0], G2_WORDS), np.uint64)
+        _native.check(self._lib.bn254_g2_map_to_curve_batch(self._h, _p(u), _p(out), u.shape[0])); return out
+
+    def g2_clear_cofactor_batch(self, p):
+        """(n,24) uint64 Jacobian points of the twist (on the curve: the caller's responsibility) -> (n,24) uint64 points of G2, normalised"""
+        p = np.ascontiguousarray(p, np.uint64).reshape(-1, G2_WORDS); out = np.empty_like(p)
+        _native.check(self._lib.bn254_g2_clear_cofactor_batch(self._h, _p(p), _p(out), p.shape[0])); return out
+
+    def g2_hash_to_curve_uniform_batch(self, uniform):
+        """(n,192) uint8 uniform bytes u0.c0 | u0.c1 | u1.c0 | u1.c1 -> (n,24) uint64: clear(map(u0) + map(u1)), normalised"""
+        b = np.ascontiguousarray(uniform, np.uint8).reshape(-1, H2C_G2_UNIFORM_BYTES); out = np.empty((b.shape[0], G2_WORDS), np.uint64)
+        _native.check(self._lib.bn254_g2_hash_to_curve_uniform_batch(self._h, _p(b), _p(out), b.shape[0])); return out
+
+    def g2_hash_to_curve_batch(self, msgs, dst):
+        """(n,msg_len) uint8 messages of one length and a tag of 1 .. 255 bytes -> (n,24) uint64: hash_to_curve with SHA-256 XMD on the device"""
+        msgs = np.ascontiguousarray(msgs, np.uint8)
+        if msgs.ndim != 2:
+            raise ValueError(f"msgs must be an (n, msg_len) uint8 array, got shape {msgs.shape}")
+        dst = h2c_dst(dst); n, ml = msgs.shape
+        out = np.empty((n, G2_WORDS), np.uint64)
+        _native.check(self._lib.bn254_g2_hash_to_curve_batch(self._h, _p(msgs) if msgs.size else None, ml, dst, len(dst), _p(out), n)); return out
+
+    def g2_map_to_curve_batch_dev(self, d_u, d_out, n, stream=0):
+        _native.check(self._lib.bn254_g2_map_to_curve_batch_dev(self._h, d_u, d_out, n, stream))
+
+    def g2_clear_cofactor_batch_dev(self, d_p, d_out, n, stream=0):
+        """d_out may be exactly d_p"""
+        _native.check(self._lib.bn254_g2_clear_cofactor_batch_dev(self._h, d_p, d_out, n, stream))
+
+    def g2_hash_to_curve_uniform_batch_dev(self, d_uniform, d_out, n, stream=0):
+        _native.check(self._lib.bn254_g2_hash_to_curve_uniform_batch_dev(self._h, d_uniform, d_out, n, stream))
+
+    def g2_hash_to_curve_batch_dev(self, d_msgs, msg_len, dst, d_out, n, stream=0):
+        """device pointers for messages and points; `dst` is host bytes (it travels as a kernel argument)"""
+        dst = h2c_dst(dst)
+        _native.check(self._lib.bn254_g2_hash_to_curve_batch_dev(self._h, d_msgs, msg_len, dst, len(dst), d_out, n, stream))
 
     # ---- the crate's variable-length byte stream (infinity = the lone byte 0)
     def _encode_stream(self, fn, p, rec):

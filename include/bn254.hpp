@@ -350,6 +350,33 @@ inline std::vector<G1> g1_hash_to_curve(const std::vector<uint8_t> &msgs, size_t
     check(bn254_g1_hash_to_curve_batch(nullptr, msgs.data(), msg_len, dst.data(), dst.size(), reinterpret_cast<bn_g1 *>(out.data()), n));
     return out;
 }
+// Hash to G2 (RFC 9380 over Fq2): the map on 96-byte elements (c0 then c1) gives points of the twist that are NOT in G2; g2_clear_cofactor takes
+// any point of the twist to G2 by [u]P + psi([3u]P) + psi^2([u]P) + psi^3(P), normalised; hash_to_curve = clear(map(u0) + map(u1)) from 192
+// uniform bytes per record, and the same behind expand_message_xmd over SHA-256 on the device.  The constants are derived from the RFC's
+// formulas and the clearing is the one step the RFC defines no suite for; not checked against gnark-crypto or any other library.
+inline std::vector<G2> g2_map_to_curve(const std::vector<uint8_t> &u) {
+    if (u.size() % BN254_H2C_G2_FIELD_BYTES) throw std::invalid_argument("g2_map_to_curve: not whole elements of 96 bytes");
+    std::vector<G2> out(u.size() / BN254_H2C_G2_FIELD_BYTES);
+    check(bn254_g2_map_to_curve_batch(nullptr, u.data(), reinterpret_cast<bn_g2 *>(out.data()), out.size()));
+    return out;
+}
+inline std::vector<G2> g2_clear_cofactor(const std::vector<G2> &p) {
+    std::vector<G2> out(p.size());
+    check(bn254_g2_clear_cofactor_batch(nullptr, reinterpret_cast<const bn_g2 *>(p.data()), reinterpret_cast<bn_g2 *>(out.data()), p.size()));
+    return out;
+}
+inline std::vector<G2> g2_hash_to_curve_uniform(const std::vector<uint8_t> &uniform) {
+    if (uniform.size() % BN254_H2C_G2_UNIFORM_BYTES) throw std::invalid_argument("g2_hash_to_curve_uniform: not whole records of 192 bytes");
+    std::vector<G2> out(uniform.size() / BN254_H2C_G2_UNIFORM_BYTES);
+    check(bn254_g2_hash_to_curve_uniform_batch(nullptr, uniform.data(), reinterpret_cast<bn_g2 *>(out.data()), out.size()));
+    return out;
+}
+inline std::vector<G2> g2_hash_to_curve(const std::vector<uint8_t> &msgs, size_t msg_len, size_t n, const std::vector<uint8_t> &dst) {
+    if (msgs.size() != n * msg_len) throw std::invalid_argument("g2_hash_to_curve: msgs is not n messages of msg_len bytes");
+    std::vector<G2> out(n);
+    check(bn254_g2_hash_to_curve_batch(nullptr, msgs.data(), msg_len, dst.data(), dst.size(), reinterpret_cast<bn_g2 *>(out.data()), n));
+    return out;
+}
 // out[i] = (a[i] == b[i]) as group elements, whatever their Jacobian representations (groups/mod.rs:83-109): nothing is normalized
 inline std::vector<bool> g1_eq(const std::vector<G1> &a, const std::vector<G1> &b) {
     if (a.size() != b.size()) throw std::invalid_argument("g1_eq: length mismatch");

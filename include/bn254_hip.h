@@ -69,6 +69,13 @@
  *                          counterpart in the reference
  *   bn254_g1_map_to_curve_batch_dev / bn254_g1_hash_to_curve_uniform_batch_dev / bn254_g1_hash_to_curve_batch_dev  the same three on device-resident records,
  *                          asynchronous on the caller's stream
+ *   bn254_g2_map_to_curve_batch  out[i] = map_to_curve(u[i]), the same map over Fq2 for the twist y^2 = x^3 + b' (Z = 1); the result is on the twist
+ *                          and NOT in G2;  bn254_g2_clear_cofactor_batch  out[i] = [u]P + psi([3u]P) + psi^2([u]P) + psi^3(P), normalised: a point of G2 for
+ *                          any point P of the twist;  bn254_g2_hash_to_curve_uniform_batch  out[i] = clear(map(u0) + map(u1)) over 192 uniform bytes;
+ *                          bn254_g2_hash_to_curve_batch  the same behind expand_message_xmd over SHA-256 on the device, one message per lane; none has a
+ *                          counterpart in the reference, and neither the constants nor the outputs are checked against gnark-crypto or any other library
+ *   bn254_g2_map_to_curve_batch_dev / bn254_g2_clear_cofactor_batch_dev / bn254_g2_hash_to_curve_uniform_batch_dev / bn254_g2_hash_to_curve_batch_dev  the same
+ *                          four on device-resident records, asynchronous on the caller's stream
  *   bn254_g2_precompute    coeffs[i][0..102) = q[i].to_affine().precompute().coeffs   groups/mod.rs:557-588 (Q != infinity)
  *   bn254_pairing_prepared_batch  out[i] = final_exponentiation(prepared.miller_loop(p[i]))   groups/mod.rs:486-519,768
  *   bn254_gt_mul_batch     out[i] = a[i] * b[i]                                     lib.rs:175-179, fields/fq12.rs:295-307
@@ -115,6 +122,8 @@
      bn254_g{1,2}_compress_batch and bn254_g{1,2}_decompress_batch serialise on the context in the same way (its mutex for the whole call).
      bn254_g1_map_to_curve_batch, bn254_g1_hash_to_curve_uniform_batch and bn254_g1_hash_to_curve_batch serialise on the context in the same way (its
      mutex for the whole call).
+     bn254_g2_map_to_curve_batch, bn254_g2_clear_cofactor_batch, bn254_g2_hash_to_curve_uniform_batch and bn254_g2_hash_to_curve_batch serialise on the
+     context in the same way (its mutex for the whole call).
  *     bn254_pairing_product_batch_prepared_native serialises on the context like them; its handle is immutable and shared freely.
  *     Use one context per thread (or bn254_multi_*) for more overlap;
  *     bn254_ctx_set_option is atomic, but set options before concurrent use: a call in flight may run some
@@ -164,6 +173,10 @@
      per sub-launch does the field reduction, both maps, the sum and the normalisation.  bn254_g1_hash_to_curve_batch_dev reads its HOST `dst`
      before it returns (the tag travels as a kernel argument: nothing is uploaded).  None of the three waits on anything or reads anything
      back, so any number of threads may issue them on one context, each on its own stream and buffers.
+     bn254_g2_map_to_curve_batch_dev, bn254_g2_clear_cofactor_batch_dev, bn254_g2_hash_to_curve_uniform_batch_dev and bn254_g2_hash_to_curve_batch_dev
+     use no scratch either: one launch per sub-launch does the field reduction, both maps, the sum, the cofactor clearing and the
+     normalisation.  bn254_g2_hash_to_curve_batch_dev reads its HOST `dst` before it returns.  None of the four waits on anything or reads
+     anything back, so any number of threads may issue them on one context, each on its own stream and buffers.
  */
 #ifndef BN254_HIP_H
 #define BN254_HIP_H
@@ -801,6 +814,42 @@ int bn254_g1_map_to_curve_batch_dev(bn254_ctx *ctx, const void *d_u, void *d_out
 int bn254_g1_hash_to_curve_uniform_batch_dev(bn254_ctx *ctx, const void *d_uniform, void *d_out, size_t n, void *stream);
 int bn254_g1_hash_to_curve_batch_dev(bn254_ctx *ctx, const void *d_msgs, size_t msg_len, const uint8_t *dst, size_t dst_len, void *d_out, size_t n, void *stream);
 
+/* Hash to G2 (RFC 9380) and cofactor clearing, one record per lane.  The constants were derived from the RFC's formulas (Z by its find_z_svdw
+   search over Fq2, which gives Z = 1 as for G1) and the clearing is the one step the RFC defines no suite for: NEITHER THE CONSTANTS NOR THE
+   OUTPUTS ARE CHECKED AGAINST gnark-crypto OR ANY OTHER LIBRARY.
+     map_to_curve   the Shallue-van de Woestijne map over Fq2 for the twist y^2 = x^3 + b', b' = 3 / (9 + i): Z = 1, c1 = g(Z) = 1 + b', c2 = -1 / 2,
+                    c3 = sqrt(-g(Z) 3 Z^2) with sgn0(c3) = 0, c4 = -4 g(Z) / (3 Z^2), in the RFC's order.  sgn0(a) = sign_0 | (zero_0 & sign_1) on the
+                    canonical integers of (c0, c1); inv0(0) = 0; is_square is the character of the norm and zero counts as a square.  u[i] is 96
+                    bytes: c0 then c1, each 48 big-endian bytes, any value below 2^384, taken mod q.  out[i] = (x, y, 1) in canonical Montgomery
+                    words, never the point at infinity.
+                    *** THE RESULT IS ON THE TWIST BUT NOT IN G2 ***: the twist has the 254-bit cofactor 2q - r.  Do not hand it to a pairing, to
+                    bn254_g2_mul_batch (GLS, valid on the order-r subgroup only) or to an encoder; clear the cofactor first.
+     clear_cofactor p[i] is any Jacobian point of the twist - being on the curve is the CALLER's responsibility, Z = 0 counts as infinity.
+                    out[i] = clear(P) = [u]P + psi([3u]P) + psi^2([u]P) + psi^3(P), u = 4965661367192848881,
+                    psi(X, Y, Z) = (conj(X) gx, conj(Y) gy, conj(Z)) (Fuentes-Castaneda, Knapp, Rodriguez-Henriquez, section 6.1), normalised:
+                    (x, y, 1) in G2, or G2::zero() = (0, 1, 0) for infinity.  This is NOT [2q - r]P - the formula is part of the interface; on a point
+                    Q of G2 it is [k]Q with k = u + 3u lambda + u lambda^2 + lambda^3 mod r, lambda = 6u^2.  [u]P is plain double-and-add with the
+                    complete addition, never the GLS multiplication.  out may be exactly p.
+     uniform        record i is 192 bytes: u0.c0 | u0.c1 | u1.c0 | u1.c1 (hash_to_field with L = 48, m = 2).  out[i] = clear(map(u0) + map(u1)),
+                    normalised; G2::zero() when the two maps cancel.
+     messages       n messages of msg_len bytes each, back to back; record i is hash_to_curve(msg i) with the 192 uniform bytes from
+                    expand_message_xmd(msg, dst, 192) over SHA-256, computed on the device.  msg_len == 0 is allowed (msgs may then be NULL).
+                    Messages of different lengths go through the uniform call after a host-side expansion.  `dst` is a HOST pointer in both forms
+                    (1 .. BN254_H2C_DST_MAX bytes).
+   Argument rules and error codes as for G1: a NULL pointer with work to do, dst_len == 0 or dst_len > BN254_H2C_DST_MAX, msg_len > 2^20, n > 2^40
+   or n * msg_len > 2^40 is BN254_E_BAD_ARG before any device is touched; n == 0 succeeds.  Calls run as sub-launches of at most 2^22 records.
+   The _dev forms take device pointers (dst excepted) and enqueue on `stream`.  Threading: see above. */
+#define BN254_H2C_G2_FIELD_BYTES 96
+#define BN254_H2C_G2_UNIFORM_BYTES 192
+int bn254_g2_map_to_curve_batch(bn254_ctx *ctx, const uint8_t *u, bn_g2 *out, size_t n);
+int bn254_g2_clear_cofactor_batch(bn254_ctx *ctx, const bn_g2 *p, bn_g2 *out, size_t n);
+int bn254_g2_hash_to_curve_uniform_batch(bn254_ctx *ctx, const uint8_t *uniform, bn_g2 *out, size_t n);
+int bn254_g2_hash_to_curve_batch(bn254_ctx *ctx, const uint8_t *msgs, size_t msg_len, const uint8_t *dst, size_t dst_len, bn_g2 *out, size_t n);
+int bn254_g2_map_to_curve_batch_dev(bn254_ctx *ctx, const void *d_u, void *d_out, size_t n, void *stream);
+int bn254_g2_clear_cofactor_batch_dev(bn254_ctx *ctx, const void *d_p, void *d_out, size_t n, void *stream);
+int bn254_g2_hash_to_curve_uniform_batch_dev(bn254_ctx *ctx, const void *d_uniform, void *d_out, size_t n, void *stream);
+int bn254_g2_hash_to_curve_batch_dev(bn254_ctx *ctx, const void *d_msgs, size_t msg_len, const uint8_t *dst, size_t dst_len, void *d_out, size_t n, void *stream);
+
 /* ---- device-resident entry points (inputs/outputs already in HBM; `stream` is a hipStream_t or NULL) ------------------ */
 /* Same layouts (array of structs) in device memory.  Asynchronous on `stream`; the caller synchronises. */
 int bn254_pairing_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, void *d_out, size_t n, void *stream);
@@ -931,6 +980,7 @@ int bn254_profile_reset(bn254_ctx *ctx);
    of bn254_fr_poseidon_batch, bn254_fr_poseidon_permute_batch and bn254_fr_merkle_tree: "fr_poseidon", "fr_poseidon_permute", "fr_merkle_level" (one scope per level, or per sub-launch of it);
    of bn254_g{1,2}_compress_batch and bn254_g{1,2}_decompress_batch: "g1_compress", "g2_compress", "g1_decompress", "g2_decompress" (one scope per sub-launch);
    of bn254_g1_map_to_curve_batch, bn254_g1_hash_to_curve_uniform_batch and bn254_g1_hash_to_curve_batch: "g1_map_to_curve", "g1_hash_to_curve", "g1_hash_to_curve_msg" (one scope per sub-launch);
+   of bn254_g2_map_to_curve_batch, bn254_g2_clear_cofactor_batch, bn254_g2_hash_to_curve_uniform_batch and bn254_g2_hash_to_curve_batch: "g2_map_to_curve", "g2_clear_cofactor", "g2_hash_to_curve", "g2_hash_to_curve_msg" (one scope per sub-launch);
    and, of bn254_fr_ntt_batch: "ntt" (the passes), "ntt_table" (the builds of the twiddle tables).
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);
