@@ -72,7 +72,9 @@
 #endif
 #include "bn254_constants.hpp"
 // GPU builds run the multiplier leaves and the 64-bit chains of the fused reductions as inline-asm instruction chains (fe_asm.hpp: same
-// arithmetic, fixed instruction order); the host simulation runs the C++ bodies, which also carry the bound checks
+// arithmetic, fixed instruction order); the host simulation runs the C++ bodies, which also carry the bound checks.  The asm side is held to
+// the C++ bodies by tests/test_gpu_leaf.py: every leaf and every chain of the reductions on raw limbs at the stated operand bounds, limb for limb
+// against the bodies (tests/hostsim/hostsim_leaf.cpp; both call the list tests/leafprobe/leaf_list.hpp - a new leaf or chain belongs on it)
 
 #if defined(BN_BOUNDS)
 #include <cstdio>

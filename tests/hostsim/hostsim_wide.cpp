@@ -7,28 +7,11 @@
 #include "lanepair.hpp"
 #include "lanequad.hpp"                    // two lane pairs side by side: the even and the odd SLOT of a batch
 #include "../../bn_amd/csrc/io.hpp"
+#include "rawleaf.hpp"                     // fe_raw / few_raw and the two wide leaves on raw limbs
 
 using namespace bn254;
 #define EXPORT extern "C" __attribute__((visibility("default")))
 typedef Fq2B<FeP> F2B;
-
-static Fe fe_raw(const uint32_t *l, unsigned lb, unsigned vb, int sg) {
-    Fe r;
-    for (int i = 0; i < 9; ++i) r.l[i] = l[i];
-    BN_SETB(r, lb, vb);
-    BN_IFB(r.sg = sg != 0;)
-    (void)lb; (void)vb; (void)sg;
-    BN_VERIFY(r, "hostsim_wide operand");
-    return r;
-}
-static FeW few_raw(const uint32_t *l, unsigned lb, unsigned wb) {
-    FeW r;
-    for (int i = 0; i < 18; ++i) r.l[i] = l[i];
-    BN_IFB(r.lb = lb; r.wb = wb;)
-    (void)lb; (void)wb;
-    BN_VERIFYW(r, "hostsim_wide operand");
-    return r;
-}
 
 EXPORT int hsw_bounds_enabled() {
 #ifdef BN_BOUNDS
@@ -37,21 +20,10 @@ EXPORT int hsw_bounds_enabled() {
     return 0;
 #endif
 }
-// a*u + c*v on raw limbs -> 18 limbs.  bounds: (lb, vb) of a, u, c, v in this order
-EXPORT void hsw_wmul2(int is_signed, const uint32_t *a, const uint32_t *u, const uint32_t *c, const uint32_t *v, const uint32_t *bounds, uint32_t *o) {
-    const Fe A = fe_raw(a, bounds[0], bounds[1], is_signed), U = fe_raw(u, bounds[2], bounds[3], is_signed);
-    const Fe Cc = fe_raw(c, bounds[4], bounds[5], is_signed), V = fe_raw(v, bounds[6], bounds[7], is_signed);
-    const FeW r = is_signed ? fe_wmul2s(A, U, Cc, V) : fe_wmul2(A, U, Cc, V);
-    for (int i = 0; i < 18; ++i) o[i] = r.l[i];
-}
+// a*u + c*v on raw limbs -> 18 limbs.  bounds: (lb, vb) of a, u, c, v in this order  (rawleaf.hpp, shared with hostsim_leaf.cpp)
+EXPORT void hsw_wmul2(int is_signed, const uint32_t *a, const uint32_t *u, const uint32_t *c, const uint32_t *v, const uint32_t *bounds, uint32_t *o) { raw_wmul2(is_signed, a, u, c, v, bounds, o); }
 // reduce(n + [xi] (9 x + s px)) - [sub] d on raw limbs -> 9 limbs.  bounds: (lb, wb) of n, x, px, then (lb, vb) of d
-EXPORT void hsw_wred(int xi, int sub, const uint32_t *n, const uint32_t *x, const uint32_t *px, int neg, const uint32_t *d, const uint32_t *bounds, uint32_t *o) {
-    const FeW N = few_raw(n, bounds[0], bounds[1]), X = few_raw(x, bounds[2], bounds[3]), PX = few_raw(px, bounds[4], bounds[5]);
-    const Fe D = fe_raw(d, bounds[6], bounds[7], 0);
-    const Fe r = xi ? (sub ? fe_wred<true, true>(N, X, PX, neg != 0, D) : fe_wred<true, false>(N, X, PX, neg != 0, D))
-                    : (sub ? fe_wred<false, true>(N, X, PX, neg != 0, D) : fe_wred<false, false>(N, X, PX, neg != 0, D));
-    for (int i = 0; i < 9; ++i) o[i] = r.l[i];
-}
+EXPORT void hsw_wred(int xi, int sub, const uint32_t *n, const uint32_t *x, const uint32_t *px, int neg, const uint32_t *d, const uint32_t *bounds, uint32_t *o) { raw_wred(xi, sub, n, x, px, neg, d, bounds, o); }
 // wide values of the limb-wise sums the tower forms: o = x + y
 EXPORT void hsw_wadd(const uint32_t *x, const uint32_t *y, const uint32_t *bounds, uint32_t *o) {
     const FeW r = fe_wadd(few_raw(x, bounds[0], bounds[1]), few_raw(y, bounds[2], bounds[3]));

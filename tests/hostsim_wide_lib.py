@@ -18,7 +18,7 @@ def lib():
     global _lib
     if _lib is None:
         out = HERE / "libhostsim_wide.so"
-        srcs = [HERE / "hostsim_wide.cpp", HERE / "lanepair.hpp", HERE / "lanequad.hpp"] + sorted(CSRC.glob("*.hpp"))
+        srcs = [HERE / "hostsim_wide.cpp", HERE / "rawleaf.hpp", HERE / "lanepair.hpp", HERE / "lanequad.hpp"] + sorted(CSRC.glob("*.hpp"))
         if (not out.exists()) or out.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
             subprocess.check_call(["g++", "-DBN_BOUNDS", "-std=c++17", "-O1", "-fPIC", "-shared", "-fvisibility=hidden", "-o", str(out), str(HERE / "hostsim_wide.cpp")])
         _lib = C.CDLL(str(out))

@@ -16,27 +16,15 @@ import pytest
 import bn_model as M
 import edge_inputs as E
 import hostsim_wide_lib as W
+from leaf_cases import COMBOS, D_BOUND, at_bound, sdiff, wide_raw          # the case makers shared with the leaf tests
 
 Q = M.Q
 R261 = 1 << 261
 MASK29 = W.MASK29
 
 
-def at_bound(lb, vb):
-    """nine limbs with limbs 0..7 at lb (2^29 - 1) and the value just below vb q"""
-    low = sum((lb * MASK29) << (29 * i) for i in range(8))
-    top = (vb * Q - low) >> 232
-    assert top >= 0
-    return np.array([lb * MASK29] * 8 + [top], np.uint32)
-
-
 def norm9(v):
     return W.limbs9(v)
-
-
-def sdiff(x, y):
-    """limb-wise difference of two normalized nine-limb values: every limb an int32 of magnitude below 2^29 (fe_sdiff)"""
-    return ((x.astype(np.int64) - y.astype(np.int64)) & 0xffffffff).astype(np.uint32)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the wide product
@@ -94,18 +82,6 @@ def test_signed_wide_product_is_the_integer():
 
 
 # ---------------------------------------------------------------------------------------------------------------- the wide reduction
-def wide_raw(lb, wb, sign):
-    """18 limbs at the claimed bounds: limbs 0..16 at lb (2^29 - 1), the top limb at +- wb q^2 / 2^493"""
-    top = sign * ((wb * Q * Q) >> (29 * 17))
-    return np.array([lb * MASK29] * 17 + [top & 0xffffffff], np.uint32)
-
-
-# (xi, sub, bounds of n, bounds of x) of the combinations the tower forms; the value bounds are those of the cross term of f12_mul_src, whose
-# operands are carry-propagated sums below 6q:  v_i <= 6*6 + 6*9 = 90 q^2,  m_ij <= 72,  X_ij = m_ij + v_i + v_j <= 252
-COMBOS = [("c0 = v0 + xi X12", True, (1, 90), (3, 252)), ("c1 = X01 + xi v2", True, (3, 252), (1, 90)), ("c2 = X02 + v1", False, (4, 342), (1, 0))]
-D_BOUND = (2, 6)                # aa + bb, each in standard form
-
-
 def _check_wred(name, xi, sub, n, x, px, neg, d, bounds):
     got = W.wred(xi, sub, n, x, px, neg, d, bounds)
     T = W.limbs_value(n, top_signed=True)

@@ -15,8 +15,12 @@ DPP in hand-written or generated asm (none is emitted here - the lane exchanges 
 permutation attached to a REVERSED opcode lands on the other source (v_subrev_u32 + DPP16 computes dpp(S1) - S0, not S1 - dpp(S0):
 profiles/r06_dpp_subrev_encoding.txt - the assembler encodes what the ISA says, the silicon swaps the operands before the permutation stage).
 Safe forms: v_mov_b32_dpp; DPP on commutative VOP2 opcodes; DPP on the non-reversed v_sub_u32 with the permuted value as src0.  Never *rev + DPP.
+
+usage: tools/gen_asm_leaf.py [--check] [path]       --check writes nothing: "up to date" and status 0, or "stale" and status 1
+(tests/test_hostsim_leaf.py runs the check; tests/test_gpu_leaf.py runs every generated leaf against its C++ twin on the GPU)
 """
 import pathlib
+import sys
 
 def chain(col, pairs, red, signed=False):
     """asm text + operand lists for one column: pairs = [(xname, yname)] product operand arrays (or "sqr": the squaring's 45 products
@@ -124,8 +128,13 @@ text = "\n".join(["// GENERATED by tools/gen_asm_leaf.py - do not edit.  The GPU
                   wide("fe_wmul2_asm"), wide("fe_wmul2s_asm", signed=True),
                   "template <bool XI, bool SUB> BN_FN Fe fe_wred_asm(const FeW &n, const FeW &x, const FeW &px, int32_t s, const Fe &d, int32_t kq);",
                   wred(False, False), wred(False, True), wred(True, False), wred(True, True), "}  // namespace bn254", ""])
-p = pathlib.Path(__file__).resolve().parents[1] / "bn_amd" / "csrc" / "fe_asm.hpp"
-if not p.exists() or p.read_text() != text:
-    p.write_text(text); print("wrote", p)
-else:
-    print("up to date:", p)
+if __name__ == "__main__":
+    args = [a for a in sys.argv[1:] if a != "--check"]
+    p = pathlib.Path(args[0]) if args else pathlib.Path(__file__).resolve().parents[1] / "bn_amd" / "csrc" / "fe_asm.hpp"
+    if p.exists() and p.read_text() == text:
+        print("up to date:", p)
+    elif "--check" in sys.argv[1:]:
+        print("stale:", p)
+        sys.exit(1)
+    else:
+        p.write_text(text); print("wrote", p)
