@@ -45,6 +45,11 @@ extern "C" {
     fn bn254_g2_clear_cofactor_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_g2_hash_to_curve_uniform_batch_dev(ctx: *mut c_void, d_uniform: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_g2_hash_to_curve_batch_dev(ctx: *mut c_void, d_msgs: *const c_void, msg_len: usize, dst: *const u8, dst_len: usize, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    // validation of raw points: one status per record (0 valid, 1 range, 4 not on the curve, 5 not in the subgroup)
+    fn bn254_g1_validate_batch(ctx: *mut c_void, p: *const G1, status: *mut i32, n: usize) -> c_int;
+    fn bn254_g2_validate_batch(ctx: *mut c_void, p: *const G2, status: *mut i32, n: usize) -> c_int;
+    fn bn254_g1_validate_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_status: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_g2_validate_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_status: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     // prepared-G2 mode (the crate's internal G2Precomp, src/groups/mod.rs:472-483): 102 line coefficients per Q, then many P against them
     fn bn254_g2_precompute(ctx: *mut c_void, q: *const G2, coeffs: *mut EllCoeffs, n: usize) -> c_int;
     fn bn254_pairing_prepared_batch(ctx: *mut c_void, p: *const G1, coeffs: *const EllCoeffs, shared: c_int, out: *mut Gt, n: usize) -> c_int;
@@ -667,6 +672,22 @@ pub fn g2_hash_to_curve_batch(msgs: &[u8], msg_len: usize, n: usize, dst: &[u8])
     let mut out = vec![G2::zero(); n];
     check(unsafe { bn254_g2_hash_to_curve_batch(std::ptr::null_mut(), msgs.as_ptr(), msg_len, dst.as_ptr(), dst.len(), out.as_mut_ptr(), n) })?;
     Ok(out)
+}
+
+/// One status per raw point, checked in this order: 1 a coordinate is not below the modulus, 0 for z == 0 (infinity), 4 not on the curve, else 0.
+/// G1 has cofactor 1: a point on the curve is in the group.
+pub fn g1_validate_batch(p: &[G1]) -> Result<Vec<i32>, GpuError> {
+    let mut status = vec![0i32; p.len()];
+    check(unsafe { bn254_g1_validate_batch(std::ptr::null_mut(), p.as_ptr(), status.as_mut_ptr(), p.len()) })?;
+    Ok(status)
+}
+
+/// The same for G2, and 5 for a point of the twist outside the order-r subgroup (the endomorphism subgroup test
+/// [u + 1]P + psi([u]P) + psi^2([u]P) == psi^3([2u]P)): the check every pairing, multiplication and verifier here leaves to its caller.
+pub fn g2_validate_batch(p: &[G2]) -> Result<Vec<i32>, GpuError> {
+    let mut status = vec![0i32; p.len()];
+    check(unsafe { bn254_g2_validate_batch(std::ptr::null_mut(), p.as_ptr(), status.as_mut_ptr(), p.len()) })?;
+    Ok(status)
 }
 
 /// `q.to_affine().precompute()` for every q (src/groups/mod.rs:557-588; q must not be infinity): 102 coefficients per point, in schedule order

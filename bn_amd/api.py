@@ -129,6 +129,8 @@ class G1(_Point):
     @staticmethod
     def hash(msg, dst):                   # hash_to_curve of RFC 9380 (SvdW, SHA-256 XMD) under the tag dst
         return g1_hash_to_curve_batch([msg], dst)[0]
+    def is_valid(self):                   # the limbs are below q and on the curve (or z == 0): one check on the GPU
+        return int(g1_validate_batch([self])[0]) == 0
     def to_compressed(self, format="ark"):    # 32 bytes: x and the sign of y
         return g1_compress_batch([self], format)[0]
     @staticmethod
@@ -173,6 +175,8 @@ class G2(_Point):
     @staticmethod
     def hash(msg, dst):                   # hash_to_curve of RFC 9380 over Fq2 (SvdW, SHA-256 XMD) and the psi-based cofactor clearing
         return g2_hash_to_curve_batch([msg], dst)[0]
+    def is_valid(self):                   # below q, on the twist AND in the order-r subgroup (or z == 0): one check on the GPU
+        return int(g2_validate_batch([self])[0]) == 0
     def to_compressed(self, format="ark"):    # 64 bytes
         return g2_compress_batch([self], format)[0]
     @staticmethod
@@ -453,6 +457,26 @@ def g2_hash_to_curve_batch(msgs, dst, engine=None):
     """[hash_to_curve(m) for m in msgs] into G2 (RFC 9380, random-oracle variant over Fq2: SHA-256 XMD to 192 bytes, two SvdW maps, one sum,
     the cofactor clearing) under the domain separation tag dst (1 .. 255 bytes).  msgs: a sequence of bytes or an (n, msg_len) uint8 array."""
     return [G2(r) for r in _g2_hash_to_curve_limbs(msgs, dst, engine)]
+
+
+def g1_validate_batch(points, engine=None):
+    """int32 status per point, for raw limbs from anywhere: 0 valid (the point at infinity, z == 0, included), 1 a coordinate is not below q,
+    4 not on the curve y^2 = x^3 + 3 (in Jacobian form, any z).  G1 has cofactor 1.  points: a sequence of G1 or an (n,12) uint64 array."""
+    return (engine or default_engine()).g1_validate_batch(_point_array(G1, points))
+
+
+def g2_validate_batch(points, engine=None):
+    """the same over G2, and 5 for a point of the twist outside the order-r subgroup: the twist has the 254-bit cofactor 2q - r, and every
+    pairing, multiplication and verifier of this package trusts its G2 inputs to be in the subgroup.  The test is the endomorphism subgroup
+    test [u + 1]P + psi([u]P) + psi^2([u]P) == psi^3([2u]P), exact on the twist."""
+    return (engine or default_engine()).g2_validate_batch(_point_array(G2, points))
+
+
+def _valid_rows(engine, g1, g2, keys):
+    """bool per row of a signature batch (bn_amd.bls, bn_amd.bls_minpk with validate=True): the G1 and the G2 point of the row are valid - one
+    validation call per group - and the public key (`keys`: whichever of the two arrays holds them) is not the point at infinity"""
+    ok = (np.asarray(engine.g1_validate_batch(g1)) == 0) & (np.asarray(engine.g2_validate_batch(g2)) == 0)
+    return ok & keys[:, 2 * keys.shape[1] // 3:].any(axis=1)
 
 
 def g1_normalize_batch(points, engine=None):

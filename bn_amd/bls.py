@@ -55,9 +55,12 @@ def sign(sk, msg, dst=DST, engine=None):
     return sign_batch([sk], [msg], dst, engine)[0]
 
 
-def verify_batch(pks, msgs, sigs, dst=DST, engine=None):
+def verify_batch(pks, msgs, sigs, dst=DST, engine=None, validate=False):
     """numpy bool array: entry i holds iff e(H(msgs[i]), pks[i]) e(-sigs[i], G2::one()) == 1.  One hash call, one addition call (the negated
-    signatures) and one batched pairing check of two-pair segments."""
+    signatures) and one batched pairing check of two-pair segments.  Keys and signatures are TRUSTED to be valid points - a key outside the
+    order-r subgroup of the twist makes the check meaningless - unless validate=True: then one validation call per group comes first, and a
+    row whose key or signature is not a valid point, or whose key is the point at infinity, is False (its points are replaced by the
+    generators for the pairing call; the other rows are unaffected)."""
     pk = api._point_array(G2, pks); sg = api._point_array(G1, sigs)
     n = _count(msgs)
     if pk.shape[0] != n or sg.shape[0] != n:
@@ -65,11 +68,16 @@ def verify_batch(pks, msgs, sigs, dst=DST, engine=None):
     if n == 0:
         return np.zeros(0, bool)
     e = _engine(engine)
+    valid = None
+    if validate:
+        valid = api._valid_rows(e, sg, pk, pk)
+        pk = np.where(valid[:, None], pk, G2.one().limbs); sg = np.where(valid[:, None], sg, G1.one().limbs)
     h = api._hash_to_curve_limbs(msgs, dst, e)
     neg = e.g1_add_batch(np.tile(G1.zero().limbs, (n, 1)), sg, negate_b=True)
     P = np.empty((2 * n, G1.WORDS), np.uint64); P[0::2] = h; P[1::2] = neg
     Q = np.empty((2 * n, G2.WORDS), np.uint64); Q[0::2] = pk; Q[1::2] = G2.one().limbs
-    return api.pairing_check_batch(P, Q, np.arange(0, 2 * n + 1, 2, dtype=np.uint64), engine=e)
+    ok = api.pairing_check_batch(P, Q, np.arange(0, 2 * n + 1, 2, dtype=np.uint64), engine=e)
+    return ok if valid is None else ok & valid
 
 
 def verify(pk, msg, sig, dst=DST, engine=None):

@@ -62,9 +62,12 @@ def sign(sk, msg, dst=DST, engine=None):
     return sign_batch([sk], [msg], dst, engine)[0]
 
 
-def verify_batch(pks, msgs, sigs, dst=DST, engine=None):
+def verify_batch(pks, msgs, sigs, dst=DST, engine=None, validate=False):
     """numpy bool array: entry i holds iff e(pks[i], H(msgs[i])) e(-G1::one(), sigs[i]) == 1.  One hash call and one batched pairing check of
-    two-pair segments (the negated generator is a constant)."""
+    two-pair segments (the negated generator is a constant).  Keys and signatures are TRUSTED to be valid points - a signature outside the
+    order-r subgroup of the twist makes the check meaningless - unless validate=True: then one validation call per group comes first, and a
+    row whose key or signature is not a valid point, or whose key is the point at infinity, is False (its points are replaced by the
+    generators for the pairing call; the other rows are unaffected)."""
     pk = api._point_array(G1, pks); sg = api._point_array(G2, sigs)
     n = _count(msgs)
     if pk.shape[0] != n or sg.shape[0] != n:
@@ -72,10 +75,15 @@ def verify_batch(pks, msgs, sigs, dst=DST, engine=None):
     if n == 0:
         return np.zeros(0, bool)
     e = _engine(engine)
+    valid = None
+    if validate:
+        valid = api._valid_rows(e, pk, sg, pk)
+        pk = np.where(valid[:, None], pk, G1.one().limbs); sg = np.where(valid[:, None], sg, G2.one().limbs)
     h = api._g2_hash_to_curve_limbs(msgs, dst, e)
     P = np.empty((2 * n, G1.WORDS), np.uint64); P[0::2] = pk; P[1::2] = _neg_g1_one()
     Q = np.empty((2 * n, G2.WORDS), np.uint64); Q[0::2] = h; Q[1::2] = sg
-    return api.pairing_check_batch(P, Q, np.arange(0, 2 * n + 1, 2, dtype=np.uint64), engine=e)
+    ok = api.pairing_check_batch(P, Q, np.arange(0, 2 * n + 1, 2, dtype=np.uint64), engine=e)
+    return ok if valid is None else ok & valid
 
 
 def verify(pk, msg, sig, dst=DST, engine=None):

@@ -1,6 +1,7 @@
 // The wire format of the BN254 engine (include/bn254_hip.h; io_wire.hpp): encode / decode kernels, one record per lane, their host-buffer
 // entry points, the byte streams of variable-length records built on them, and the compressed encodings (io_compress.hpp): their kernels are
-// Ops of lane_launch.hpp's bn254_fr_decode_k and - G2 decompression, which carries the subgroup chain - of this unit's bn254_g2_decode_k<Op>.
+// Ops of lane_launch.hpp's bn254_fr_decode_k and - G2 decompression, which carries the subgroup test (io_wire.hpp BN254_G2_SUBGROUP_ENDO) - of this
+// unit's bn254_g2_decode_k<Op>.
 // Compiled like every unit (bn254_hip.hip: the flags).
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -245,5 +246,7 @@ int bn254_g2_decompress_batch_dev(bn254_ctx *ctx, const void *d_in, int format, 
 // BN_LAUNCH_MAX) so that a test reaches the seam between two sub-launches with a handful of records, and which chain form the square roots run
 int bn254_compress_set_launch_max(size_t lanes) { return g_compress_launch_max.set(lanes); }
 int bn254_compress_sqrt_window(void) { return BN254_SQRT_WINDOW; }
+// internal (tools/time_validate.py): which membership test the G2 decoders of this library run - 1 the endomorphism test, 0 the r - 1 chain
+int bn254_wire_subgroup_endo(void) { return BN254_G2_SUBGROUP_ENDO; }
 
 }  // extern "C"

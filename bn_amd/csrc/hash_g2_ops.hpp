@@ -17,12 +17,11 @@
 // Everything here is pure and takes plain pointers and a lane index (tests/hostsim/hostsim_hash_g2.cpp runs the very same bodies over host arrays).
 #pragma once
 #include "hash_ops.hpp"
+#include "subgroup_ops.hpp"
 
 namespace bn254 {
 
 constexpr uint32_t H2C_G2_FIELD_BYTES = 96, H2C_G2_UNIFORM_BYTES = 192;
-using H2cF2 = Fq2Field<Fq2A>;
-using H2cJac2 = Jac<H2cF2>;
 
 // 24 words of a big-endian byte string: c0 then c1
 BN_FN Fq2A h2c_f2_from_be_words(const uint32_t *w) { return {h2c_fe_from_be_words(w), h2c_fe_from_be_words(w + 12)}; }
@@ -62,24 +61,8 @@ BN_FN void h2c_g2_map(const Fq2A &u, Fq2A &x, Fq2A &y) {
     y = f2_select(h2c_sgn0(r) != h2c_sgn0(u), r, f2_neg(r));
 }
 
-// ---- psi and its powers on Jacobian coordinates (psi^2 = (w X, -Y, Z), psi^3 = (conj(X) w gx, -conj(Y) gy, conj(Z)): the constants of GLS)
-BN_FN H2cJac2 h2c_psi(const H2cJac2 &p) {
-    return {f2_mul_const(f2_conj_lazy(p.x), k::TWIST_MUL_BY_Q_X), f2_mul_const(f2_conj_lazy(p.y), k::TWIST_MUL_BY_Q_Y), f2_conj(p.z)};
-}
-BN_FN H2cJac2 h2c_psi2(const H2cJac2 &p) { return {f2_scale(p.x, fe_const(k::GLS_W)), f2_neg(p.y), p.z}; }
-BN_FN H2cJac2 h2c_psi3(const H2cJac2 &p) {
-    return {f2_mul_const(f2_conj_lazy(p.x), k::GLS_WGX), f2_neg(f2_mul_const(f2_conj_lazy(p.y), k::TWIST_MUL_BY_Q_Y)), f2_conj(p.z)};
-}
-// [u]P for any point of the twist, infinity (Z = 0) included: 62 doublings and the additions of the set bits of u below its top one
-BN_FN H2cJac2 h2c_mul_u(const H2cJac2 &p) {
-    H2cJac2 acc = p;
-#pragma unroll 1
-    for (int i = 61; i >= 0; --i) {                                              // u has 63 bits; the top one is consumed by acc = p
-        acc = jac_double(acc);
-        if ((k::BN_U >> i) & 1) acc = add_body<H2cF2>(acc, p, 0);
-    }
-    return acc;
-}
+// ---- psi, psi^2, psi^3 on Jacobian coordinates (the constants k::TWIST_MUL_BY_Q_X, k::TWIST_MUL_BY_Q_Y, k::GLS_W, k::GLS_WGX) and [u]P over the
+// bits of k::BN_U, h2c_mul_u, live in subgroup_ops.hpp: the membership test of G2 runs the same chain
 // clear(P), not normalised.  Out of line with P handed over by reference, so that P lives in private memory through the 62 steps of the
 // chain: inlined into the clearing kernel, the allocation kept P, the running point and an addition's values in registers and spilled 45 of them
 BN_OUTER H2cJac2 h2c_clear(const H2cJac2 &p) {

@@ -71,5 +71,12 @@ BN_FN bool words_all_zero(const uint32_t *w, int n) {
     for (int i = 0; i < n; ++i) o |= w[i];
     return o == 0;
 }
+// a raw 256-bit integer (8 words, little-endian word order) below q
+BN_FN bool words_lt_q(const uint32_t *w) {
+    int64_t br = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { int64_t s = (int64_t)w[i] - (int64_t)k::Q32[i] + br; br = s >> 32; }
+    return br != 0;
+}
 #undef F2P
 }  // namespace bn254

@@ -7,6 +7,11 @@
 // Fr records move into and out of Montgomery form with the shared arithmetic of fr.hpp (through curve.hpp); this file has none of its own.
 #pragma once
 #include "curve.hpp"
+#include "subgroup_ops.hpp"
+
+#ifndef BN254_G2_SUBGROUP_ENDO
+#define BN254_G2_SUBGROUP_ENDO 1       // which membership test the G2 decoders run: 1 the endomorphism test (subgroup_ops.hpp), 0 the r - 1 chain below; 0 stays buildable: tools/build_variant.sh
+#endif
 
 namespace bn254 {
 
@@ -33,12 +38,6 @@ BN_FN Fe fe_from_raw_words(const uint32_t *w) {
     Fe u = fe_unpack_u32x8(w);
     BN_IFB(u.vb = 6;)                       // a raw 256-bit integer is below 2^256 < 6q
     return fe_mul(u, fe_const(k::C_RAW_IN));
-}
-BN_FN bool words_lt_q(const uint32_t *w) {
-    int64_t br = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { int64_t s = (int64_t)w[i] - (int64_t)k::Q32[i] + br; br = s >> 32; }
-    return br != 0;
 }
 // r[0..16) = a[0..8) * q + c[0..8)      (U512::from, arith.rs:21-44)
 BN_FN void mul_q_add(const uint32_t *a, const uint32_t *c, uint32_t *r) {
@@ -136,7 +135,7 @@ BN_FN void g2_encode_record(const uint32_t *p, uint8_t *out) {
     for (int i = 0; i < 129; ++i) out[i] = (inf && i > 0) ? 0 : buf[i];
 }
 // p * (-1) + p == 0   (groups/mod.rs:183-194): the scalar r - 1 is the same for every lane, so its bits drive uniform branches
-BN_FN bool g2_in_subgroup(const Fq2A &x, const Fq2A &y) {
+BN_FN bool g2_in_subgroup_chain(const Fq2A &x, const Fq2A &y) {
     using F = Fq2Field<Fq2A>;
     Jac<F> p = {x, y, F::one()};
     Jac<F> acc = p;
@@ -147,6 +146,16 @@ BN_FN bool g2_in_subgroup(const Fq2A &x, const Fq2A &y) {
     }
     Jac<F> sum = jac_add_flags(acc, p, false, false);
     return F::is_zero(sum.z);
+}
+// the membership test of the decoders (here and io_compress.hpp g2_decompress_record) for an affine point of the twist - or any pair (x, y):
+// every lane runs it, its result counts only where the earlier checks passed.  Both forms give the same answer on every point of the twist.
+BN_FN bool g2_in_subgroup(const Fq2A &x, const Fq2A &y) {
+#if BN254_G2_SUBGROUP_ENDO
+    const H2cJac2 p = {x, y, H2cF2::one()};
+    return g2_in_subgroup_endo(p);
+#else
+    return g2_in_subgroup_chain(x, y);
+#endif
 }
 BN_FN int g2_decode_record(const uint8_t *in, uint32_t *out) {
     uint8_t tag = in[0];

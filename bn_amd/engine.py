@@ -808,6 +808,26 @@ class Engine:
         dst = h2c_dst(dst)
         _native.check(self._lib.bn254_g2_hash_to_curve_batch_dev(self._h, d_msgs, msg_len, dst, len(dst), d_out, n, stream))
 
+    # ---- validation of raw points: what every other call trusts its caller to have done
+    def g1_validate_batch(self, p):
+        """(n,12) uint64 raw records (x, y, z), any z -> (n,) int32 status: 0 valid (infinity, z == 0, included), 1 a coordinate is not below q,
+        4 not on the curve"""
+        p = np.ascontiguousarray(p, np.uint64).reshape(-1, G1_WORDS); st = np.empty(p.shape[0], np.int32)
+        _native.check(self._lib.bn254_g1_validate_batch(self._h, _p(p), _p(st), p.shape[0])); return st
+
+    def g2_validate_batch(self, p):
+        """(n,24) uint64 raw records -> (n,) int32 status: as for G1, and 5 for a point of the twist outside the order-r subgroup (the
+        endomorphism subgroup test [u + 1]P + psi([u]P) + psi^2([u]P) == psi^3([2u]P))"""
+        p = np.ascontiguousarray(p, np.uint64).reshape(-1, G2_WORDS); st = np.empty(p.shape[0], np.int32)
+        _native.check(self._lib.bn254_g2_validate_batch(self._h, _p(p), _p(st), p.shape[0])); return st
+
+    def g1_validate_batch_dev(self, d_p, d_status, n, stream=0):
+        """device pointers: records and n int32 statuses"""
+        _native.check(self._lib.bn254_g1_validate_batch_dev(self._h, d_p, d_status, n, stream))
+
+    def g2_validate_batch_dev(self, d_p, d_status, n, stream=0):
+        _native.check(self._lib.bn254_g2_validate_batch_dev(self._h, d_p, d_status, n, stream))
+
     # ---- the crate's variable-length byte stream (infinity = the lone byte 0)
     def _encode_stream(self, fn, p, rec):
         out = np.empty(p.shape[0] * rec, np.uint8); w = C.c_size_t()

@@ -377,6 +377,18 @@ inline std::vector<G2> g2_hash_to_curve(const std::vector<uint8_t> &msgs, size_t
     check(bn254_g2_hash_to_curve_batch(nullptr, msgs.data(), msg_len, dst.data(), dst.size(), reinterpret_cast<bn_g2 *>(out.data()), n));
     return out;
 }
+// Validation of raw points: one status per record with the wire format's numbers (0 valid - infinity, z == 0, included -, 1 a coordinate is not
+// below q, 4 not on the curve, 5 on the twist but not in G2: the endomorphism subgroup test).  Every other call trusts its inputs
+inline std::vector<int32_t> g1_validate(const std::vector<G1> &p) {
+    std::vector<int32_t> status(p.size());
+    check(bn254_g1_validate_batch(nullptr, reinterpret_cast<const bn_g1 *>(p.data()), status.data(), p.size()));
+    return status;
+}
+inline std::vector<int32_t> g2_validate(const std::vector<G2> &p) {
+    std::vector<int32_t> status(p.size());
+    check(bn254_g2_validate_batch(nullptr, reinterpret_cast<const bn_g2 *>(p.data()), status.data(), p.size()));
+    return status;
+}
 // out[i] = (a[i] == b[i]) as group elements, whatever their Jacobian representations (groups/mod.rs:83-109): nothing is normalized
 inline std::vector<bool> g1_eq(const std::vector<G1> &a, const std::vector<G1> &b) {
     if (a.size() != b.size()) throw std::invalid_argument("g1_eq: length mismatch");

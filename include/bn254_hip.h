@@ -76,6 +76,10 @@
  *                          counterpart in the reference, and neither the constants nor the outputs are checked against gnark-crypto or any other library
  *   bn254_g2_map_to_curve_batch_dev / bn254_g2_clear_cofactor_batch_dev / bn254_g2_hash_to_curve_uniform_batch_dev / bn254_g2_hash_to_curve_batch_dev  the same
  *                          four on device-resident records, asynchronous on the caller's stream
+ *   bn254_g1_validate_batch / bn254_g2_validate_batch  status[i] = 0 when the raw record p[i] is a valid point (on the curve and, for G2, in the order-r
+ *                          subgroup, by the endomorphism subgroup test), else the wire format's error number; what the Rust type system guarantees for the
+ *                          reference's G1 / G2 values and a caller holding raw structs cannot know; no counterpart in the reference
+ *   bn254_g1_validate_batch_dev / bn254_g2_validate_batch_dev  the same two on device-resident records, asynchronous on the caller's stream
  *   bn254_g2_precompute    coeffs[i][0..102) = q[i].to_affine().precompute().coeffs   groups/mod.rs:557-588 (Q != infinity)
  *   bn254_pairing_prepared_batch  out[i] = final_exponentiation(prepared.miller_loop(p[i]))   groups/mod.rs:486-519,768
  *   bn254_gt_mul_batch     out[i] = a[i] * b[i]                                     lib.rs:175-179, fields/fq12.rs:295-307
@@ -87,7 +91,7 @@
  * a point at infinity in either argument gives Gt::one() (groups/mod.rs:766).  So the only failures are device failures:
  * every function returns 0 on success or a negative BN254_E_* / positive hipError_t code; nothing panics, throws or
  * aborts across this boundary.  Inputs are trusted to be valid subgroup points exactly as the Rust type system guarantees
- * for G1/G2 values; behaviour on other limb patterns is unspecified (but memory safe).
+ * for G1/G2 values; behaviour on other limb patterns is unspecified (but memory safe).  bn254_g{1,2}_validate_batch check raw structs.
  *
  * Sizes: n is limited by device memory only.  Batches are cut internally into sub-launches of at most one machine round, and the
  * context-owned tables (final exponentiation: 4 KB, Gt::pow: 14.8 KB per pairing) are sized for ONE round - 264 MB / 970 MB on an
@@ -124,6 +128,7 @@
      mutex for the whole call).
      bn254_g2_map_to_curve_batch, bn254_g2_clear_cofactor_batch, bn254_g2_hash_to_curve_uniform_batch and bn254_g2_hash_to_curve_batch serialise on the
      context in the same way (its mutex for the whole call).
+     bn254_g1_validate_batch and bn254_g2_validate_batch serialise on the context in the same way (its mutex for the whole call).
  *     bn254_pairing_product_batch_prepared_native serialises on the context like them; its handle is immutable and shared freely.
  *     Use one context per thread (or bn254_multi_*) for more overlap;
  *     bn254_ctx_set_option is atomic, but set options before concurrent use: a call in flight may run some
@@ -177,6 +182,9 @@
      use no scratch either: one launch per sub-launch does the field reduction, both maps, the sum, the cofactor clearing and the
      normalisation.  bn254_g2_hash_to_curve_batch_dev reads its HOST `dst` before it returns.  None of the four waits on anything or reads
      anything back, so any number of threads may issue them on one context, each on its own stream and buffers.
+     bn254_g1_validate_batch_dev and bn254_g2_validate_batch_dev use no scratch and no host operand either: one launch per sub-launch compares
+     the words with q, checks the curve equation and (G2) runs the subgroup test.  Neither waits on anything or reads anything back (d_status
+     stays on the device), so any number of threads may issue them on one context, each on its own stream and buffers.
  */
 #ifndef BN254_HIP_H
 #define BN254_HIP_H
@@ -850,6 +858,27 @@ int bn254_g2_clear_cofactor_batch_dev(bn254_ctx *ctx, const void *d_p, void *d_o
 int bn254_g2_hash_to_curve_uniform_batch_dev(bn254_ctx *ctx, const void *d_uniform, void *d_out, size_t n, void *stream);
 int bn254_g2_hash_to_curve_batch_dev(bn254_ctx *ctx, const void *d_msgs, size_t msg_len, const uint8_t *dst, size_t dst_len, void *d_out, size_t n, void *stream);
 
+/* Validation of raw points, one record per lane: what every other entry point TRUSTS its caller to have done.  p[i] is any 96 / 192 bytes:
+   (x, y, z) as canonical Montgomery words, any z.  status[i] takes the numbers of the wire format above, checked in the order of the
+   compressed decoders:
+     1   a coordinate (G2: a component of one) is not below q - the words are compared as they stand, before any field arithmetic
+     0   z == 0: the point at infinity, whatever x and y hold
+     4   Y^2 != X^3 + b Z^6 (b = 3 for G1, b' = 3 / (9 + i) for G2): not on the curve
+     5   (G2 only) on the twist but not in the order-r subgroup.  The twist has the 254-bit cofactor 2q - r, and a pairing check against a point
+         outside the subgroup means nothing.  G1 has cofactor 1: on the curve is in the group.
+     0   otherwise: a valid point
+   Membership of G2 is the endomorphism subgroup test [u + 1]P + psi([u]P) + psi^2([u]P) == psi^3([2u]P), u = 4965661367192848881,
+   psi(X, Y, Z) = (conj(X) gx, conj(Y) gy, conj(Z)) - the criterion gnark-crypto's bn254 uses; exact: it accepts a point of the twist if and only
+   if [r]P == 0.  [u]P is plain double-and-add with the complete addition, never the GLS multiplication (bn254_g2_mul_batch by r is WRONG off
+   the subgroup, where psi is not the scalar lambda).  The decoders of the wire format and of the compressed encodings run the same test.
+   Nothing is written but status; a record is never changed.  A NULL pointer with work to do or n > 2^40 is BN254_E_BAD_ARG before any device
+   is touched; n == 0 succeeds.  Calls run as sub-launches of at most 2^22 records.  The _dev forms take device pointers (d_status too: int32_t
+   per record) and enqueue on `stream`.  Threading: see above. */
+int bn254_g1_validate_batch(bn254_ctx *ctx, const bn_g1 *p, int32_t *status, size_t n);
+int bn254_g2_validate_batch(bn254_ctx *ctx, const bn_g2 *p, int32_t *status, size_t n);
+int bn254_g1_validate_batch_dev(bn254_ctx *ctx, const void *d_p, void *d_status, size_t n, void *stream);
+int bn254_g2_validate_batch_dev(bn254_ctx *ctx, const void *d_p, void *d_status, size_t n, void *stream);
+
 /* ---- device-resident entry points (inputs/outputs already in HBM; `stream` is a hipStream_t or NULL) ------------------ */
 /* Same layouts (array of structs) in device memory.  Asynchronous on `stream`; the caller synchronises. */
 int bn254_pairing_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, void *d_out, size_t n, void *stream);
@@ -981,6 +1010,7 @@ int bn254_profile_reset(bn254_ctx *ctx);
    of bn254_g{1,2}_compress_batch and bn254_g{1,2}_decompress_batch: "g1_compress", "g2_compress", "g1_decompress", "g2_decompress" (one scope per sub-launch);
    of bn254_g1_map_to_curve_batch, bn254_g1_hash_to_curve_uniform_batch and bn254_g1_hash_to_curve_batch: "g1_map_to_curve", "g1_hash_to_curve", "g1_hash_to_curve_msg" (one scope per sub-launch);
    of bn254_g2_map_to_curve_batch, bn254_g2_clear_cofactor_batch, bn254_g2_hash_to_curve_uniform_batch and bn254_g2_hash_to_curve_batch: "g2_map_to_curve", "g2_clear_cofactor", "g2_hash_to_curve", "g2_hash_to_curve_msg" (one scope per sub-launch);
+   of bn254_g1_validate_batch and bn254_g2_validate_batch: "g1_validate", "g2_validate" (one scope per sub-launch);
    and, of bn254_fr_ntt_batch: "ntt" (the passes), "ntt_table" (the builds of the twiddle tables).
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);

@@ -200,7 +200,7 @@ def main():
         wins = statistics.median(times[1]) < statistics.median(times[0])
         say("the rule (fixed before measuring): the form with the smaller median of %d ships -> %s (the library measured above carries %s)"
             % (a.repeats, forms[int(wins)], forms[window]))
-    say("   not built: compressed Gt, the endomorphism subgroup test instead of the r - 1 chain, compressed stream forms, multi-GPU forms, gnark's or snarkjs' own proof-file framing")
+    say("   not built: compressed Gt, compressed stream forms, multi-GPU forms, gnark's or snarkjs' own proof-file framing")
 
 
 if __name__ == "__main__":

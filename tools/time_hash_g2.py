@@ -3,7 +3,7 @@
 bn254_g2_hash_to_curve_batch) on one GPU, one process; every figure is the median [min max] of --repeats runs after --warmup.  Kernel ms come
 from bn254_kernel_stats around the _dev call.
   - the map and the two hash calls at n = 1, 2^15, 2^18 (32-byte messages), each beside bn254_g2_decompress_batch_dev on as many records: that
-    call proves membership with the r - 1 chain, the chain that clearing the cofactor by psi avoids
+    call proves membership (the r - 1 chain when profiles/r23_hash_g2.txt was written, the endomorphism subgroup test since), which clearing the cofactor by psi avoids
   - bn254_g2_clear_cofactor_batch_dev on points of G2 beside bn254_g2_mul_batch_dev by k = u + 3u lambda + u lambda^2 + lambda^3 on the same
     points: on the subgroup the two give equal bytes (asserted)
   - the VGPRs, spills and private bytes of the four kernel instances (tools/kernel_meta.py) and the launch shape that shipped
@@ -111,7 +111,7 @@ def main():
             v = repeat(lambda: kernel_ms((scope,), lambda: call(n)), a.repeats, a.warmup)
             d = repeat(lambda: kernel_ms(("g2_decompress",), lambda: eng.g2_decompress_batch_dev(B2.data_ptr(), D2.data_ptr(), ST.data_ptr(), n, "ark", s0)), a.repeats, a.warmup)
             ms = statistics.median(v)
-            say("n = %-7d | kernel ms %s | %9.3f M points/s | g2_decompress_batch_dev on %d records (two root chains and the r - 1 chain) %s, this call takes %.2f x"
+            say("n = %-7d | kernel ms %s | %9.3f M points/s | g2_decompress_batch_dev on %d records (two root chains and the subgroup test) %s, this call takes %.2f x"
                 % (n, fmt(v), n / ms / 1e3, n, fmt(d), ms / statistics.median(d)))
 
     say("-- clear_cofactor on points of G2, beside g2_mul_batch_dev (GLS) by k on the same points: equal bytes on the subgroup")
@@ -144,7 +144,7 @@ def main():
         hashing = repeat(lambda: wall(hash_call), a.repeats, a.warmup)
         say("%s.verify_batch %s | hashing (host buffers in and out) %s | the rest, by difference of the medians %9.4f | %.1f k signatures/s"
             % (name, fmt(whole), fmt(hashing), statistics.median(whole) - statistics.median(hashing), m / statistics.median(whole)))
-    say("   not built: encode_to_curve, mixed lengths on the device, an endomorphism subgroup test for the decoders from the same psi, a hash with a shorter addition chain for u, multi-GPU forms")
+    say("   not built: encode_to_curve, mixed lengths on the device, a hash with a shorter addition chain for u, multi-GPU forms")
 
 
 if __name__ == "__main__":
