@@ -50,6 +50,16 @@ extern "C" {
     fn bn254_g2_validate_batch(ctx: *mut c_void, p: *const G2, status: *mut i32, n: usize) -> c_int;
     fn bn254_g1_validate_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_status: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_g2_validate_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_status: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_bjj_validate_batch(ctx: *mut c_void, p: *const Fr, status: *mut i32, n: usize) -> c_int;
+    fn bn254_bjj_add_batch(ctx: *mut c_void, p: *const Fr, q: *const Fr, out: *mut Fr, n: usize) -> c_int;
+    fn bn254_bjj_mul_batch(ctx: *mut c_void, p: *const Fr, k: *const Fr, out: *mut Fr, n: usize) -> c_int;
+    fn bn254_eddsa_poseidon_challenge_batch(ctx: *mut c_void, a: *const Fr, r8: *const Fr, msg: *const Fr, out: *mut Fr, n: usize) -> c_int;
+    fn bn254_eddsa_poseidon_verify_batch(ctx: *mut c_void, a: *const Fr, r8: *const Fr, s: *const Fr, msg: *const Fr, status: *mut i32, n: usize) -> c_int;
+    fn bn254_bjj_validate_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_status: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_bjj_add_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_q: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_bjj_mul_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_k: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_eddsa_poseidon_challenge_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_r8: *const c_void, d_msg: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_eddsa_poseidon_verify_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_r8: *const c_void, d_s: *const c_void, d_msg: *const c_void, d_status: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     // prepared-G2 mode (the crate's internal G2Precomp, src/groups/mod.rs:472-483): 102 line coefficients per Q, then many P against them
     fn bn254_g2_precompute(ctx: *mut c_void, q: *const G2, coeffs: *mut EllCoeffs, n: usize) -> c_int;
     fn bn254_pairing_prepared_batch(ctx: *mut c_void, p: *const G1, coeffs: *const EllCoeffs, shared: c_int, out: *mut Gt, n: usize) -> c_int;
@@ -687,6 +697,49 @@ pub fn g1_validate_batch(p: &[G1]) -> Result<Vec<i32>, GpuError> {
 pub fn g2_validate_batch(p: &[G2]) -> Result<Vec<i32>, GpuError> {
     let mut status = vec![0i32; p.len()];
     check(unsafe { bn254_g2_validate_batch(std::ptr::null_mut(), p.as_ptr(), status.as_mut_ptr(), p.len()) })?;
+    Ok(status)
+}
+
+/// Baby Jubjub, the twisted Edwards curve `a x^2 + y^2 = 1 + d x^2 y^2` over `Fr` (a = 168700, d = 168696): a point is two consecutive `Fr`, x then
+/// y, affine, so `p` holds `2 n` elements.  One status per raw point, checked in this order: 1 a coordinate is not below r, 4 not on the curve,
+/// 5 on the curve but `[l]P != O`, else 0 (the identity `(0, 1)` is valid).
+pub fn bjj_validate_batch(p: &[Fr]) -> Result<Vec<i32>, GpuError> {
+    assert_eq!(p.len() % 2, 0);
+    let mut status = vec![0i32; p.len() / 2];
+    check(unsafe { bn254_bjj_validate_batch(std::ptr::null_mut(), p.as_ptr(), status.as_mut_ptr(), p.len() / 2) })?;
+    Ok(status)
+}
+
+/// `out[i] = p[i] + q[i]`: the complete affine sum, for points of the curve (not checked).
+pub fn bjj_add_batch(p: &[Fr], q: &[Fr]) -> Result<Vec<Fr>, GpuError> {
+    assert!(p.len() % 2 == 0 && p.len() == q.len());
+    let mut out = vec![Fr::zero(); p.len()];
+    check(unsafe { bn254_bjj_add_batch(std::ptr::null_mut(), p.as_ptr(), q.as_ptr(), out.as_mut_ptr(), p.len() / 2) })?;
+    Ok(out)
+}
+
+/// `out[i] = [k[i]] p[i]` for any point of the curve, cofactor components included; the scalar is the canonical integer of `k[i]`.
+pub fn bjj_mul_batch(p: &[Fr], k: &[Fr]) -> Result<Vec<Fr>, GpuError> {
+    assert_eq!(p.len(), 2 * k.len());
+    let mut out = vec![Fr::zero(); p.len()];
+    check(unsafe { bn254_bjj_mul_batch(std::ptr::null_mut(), p.as_ptr(), k.as_ptr(), out.as_mut_ptr(), k.len()) })?;
+    Ok(out)
+}
+
+/// `out[i] = Poseidon5(r8[i].x, r8[i].y, a[i].x, a[i].y, msg[i])`: the challenge of EdDSA-Poseidon (circomlib's Poseidon at width 6); no curve check.
+pub fn eddsa_poseidon_challenge_batch(a: &[Fr], r8: &[Fr], msg: &[Fr]) -> Result<Vec<Fr>, GpuError> {
+    assert!(a.len() == 2 * msg.len() && r8.len() == 2 * msg.len());
+    let mut out = vec![Fr::zero(); msg.len()];
+    check(unsafe { bn254_eddsa_poseidon_challenge_batch(std::ptr::null_mut(), a.as_ptr(), r8.as_ptr(), msg.as_ptr(), out.as_mut_ptr(), msg.len()) })?;
+    Ok(out)
+}
+
+/// circomlib's `verifyPoseidon` per row: 1 a word array is not below r or `s` is not below l, 4 `R8` or `A` is not on the curve,
+/// 6 `[S]B8 != R8 + [8 hm]A`, 0 valid.  There is no subgroup check: `A = O` with `R8 = [S]B8` verifies, as in circomlib.
+pub fn eddsa_poseidon_verify_batch(a: &[Fr], r8: &[Fr], s: &[Fr], msg: &[Fr]) -> Result<Vec<i32>, GpuError> {
+    assert!(a.len() == 2 * msg.len() && r8.len() == 2 * msg.len() && s.len() == msg.len());
+    let mut status = vec![0i32; msg.len()];
+    check(unsafe { bn254_eddsa_poseidon_verify_batch(std::ptr::null_mut(), a.as_ptr(), r8.as_ptr(), s.as_ptr(), msg.as_ptr(), status.as_mut_ptr(), msg.len()) })?;
     Ok(status)
 }
 

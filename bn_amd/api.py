@@ -705,6 +705,56 @@ def fr_ntt(values, inverse=False, shift=None, engine=None):
     return fr_ntt_batch(A.reshape(1, -1, 4), inverse, shift, engine)[0]
 
 
+def _bjj_points(points):
+    from . import babyjub
+    return babyjub._point_array(points)
+
+
+def bjj_validate_batch(points, engine=None):
+    """(n,) int32 per Baby Jubjub point (bn_amd.babyjub): 0 a valid point ([l]P == O; O itself included), 1 a coordinate's words are not below
+    r, 4 not on the curve, 5 on the curve but [l]P != O.  points: a sequence of babyjub.Point or (x, y) integer pairs, or an (n, 2, 4) uint64
+    array of raw records"""
+    return (engine or default_engine()).bjj_validate_batch(_bjj_points(points))
+
+
+def bjj_add_batch(p, q, engine=None):
+    """[p_i + q_i] -> list of babyjub.Point: the complete sum, for points of the curve (not checked)"""
+    from .babyjub import Point
+    P, Q = _bjj_points(p), _bjj_points(q)
+    if P.shape != Q.shape:
+        raise ValueError(f"{P.shape[0]} points, {Q.shape[0]} points")
+    return [Point.from_limbs(r) for r in (engine or default_engine()).bjj_add_batch(P, Q)]
+
+
+def bjj_mul_batch(p, k, engine=None):
+    """[[k_i] p_i] -> list of babyjub.Point, for any point of the curve (cofactor components included; not checked) and any Fr k: the scalar is
+    the canonical integer of the element"""
+    from .babyjub import Point
+    P, K = _bjj_points(p), _scalar_array(k)
+    if P.shape[0] != K.shape[0]:
+        raise ValueError(f"{P.shape[0]} points, {K.shape[0]} scalars")
+    return [Point.from_limbs(r) for r in (engine or default_engine()).bjj_mul_batch(P, K)]
+
+
+def eddsa_poseidon_challenge_batch(a, r8, msg, engine=None):
+    """[Poseidon5(r8.x, r8.y, a.x, a.y, msg)] -> list of Fr: the challenge of EdDSA-Poseidon (circomlib's Poseidon at width 6), plain field
+    elements in, no curve check.  a, r8: points as for bjj_add_batch; msg: a sequence of Fr or an (n,4) uint64 array"""
+    A, R8, M = _bjj_points(a), _bjj_points(r8), _scalar_array(msg)
+    if not A.shape[0] == R8.shape[0] == M.shape[0]:
+        raise ValueError(f"{A.shape[0]} keys, {R8.shape[0]} points, {M.shape[0]} messages")
+    return [Fr.from_limbs(r) for r in (engine or default_engine()).eddsa_poseidon_challenge_batch(A, R8, M)]
+
+
+def eddsa_poseidon_verify_batch(a, r8, s, msg, engine=None):
+    """(n,) int32 per signature (R8, S) on msg under the key A, circomlib's verifyPoseidon: 1 a word array of a, r8, s or msg is not below r or the
+    integer of s is not below l, 4 R8 or A is not on the curve, 6 [S]B8 != R8 + [8 hm]A, 0 valid - checked in that order, every row on its own.
+    There is no subgroup check: A = O with R8 = [S]B8 verifies, as it does in circomlib"""
+    A, R8, S, M = _bjj_points(a), _bjj_points(r8), _scalar_array(s), _scalar_array(msg)
+    if not A.shape[0] == R8.shape[0] == S.shape[0] == M.shape[0]:
+        raise ValueError(f"{A.shape[0]} keys, {R8.shape[0]} points, {S.shape[0]} scalars, {M.shape[0]} messages")
+    return (engine or default_engine()).eddsa_poseidon_verify_batch(A, R8, S, M)
+
+
 class PreparedG2:
     """G2 points prepared once for many pairings (the crate's internal G2Precomp, groups/mod.rs:472-483,557-588, as a device-resident
     native table: Engine.g2_prepare).  One point: shared by every P; several: point i is paired with ps[i]."""

@@ -1,6 +1,6 @@
 // The per-lane bodies of the Poseidon kernels over Fr (bn254_poseidon.hip): bn254_fr_poseidon_batch, bn254_fr_poseidon_permute_batch,
-// bn254_fr_merkle_tree and their _dev twins.  The circomlib / iden3 instance: S-box x^5, width T = arity + 1 = 2 .. 5, R_F = 8 full rounds (four in
-// front, four behind) around R_P = 56 / 57 / 56 / 60 partial ones; the constants are poseidon_constants.hpp (generated from bn_amd/poseidon.py).
+// bn254_fr_merkle_tree and their _dev twins.  The circomlib / iden3 instance: S-box x^5, width T = arity + 1 = 2 .. 5 (and the width 6 of babyjub_ops.hpp), R_F = 8 full rounds (four in
+// front, four behind) around R_P = 56 / 57 / 56 / 60 (/ 60) partial ones; the constants are poseidon_constants.hpp (generated from bn_amd/poseidon.py).
 //   round    s[i] += C[round * T + i];  s[i] = s[i]^5 for every i (full) or for i = 0 (partial);  s = M s
 //   permute  the R_F + R_P rounds over a state of T records
 //   hash     element 0 of permute([0, x_1 .. x_arity]); a Merkle node is hash(left, right), so a tree level is the hash of arity 2 over the
@@ -60,11 +60,29 @@ BN_FN Fr fr_poseidon_row_tail(const Fr (&s)[T], const Fr &acc) {
     if constexpr (J < T) return fr_poseidon_row_tail<T, I, J + 1>(s, fr_add(acc, fr_mul(s[J], fr_const(psd::K<T>::M[I * T + J]))));
     else return acc;
 }
+// Width 6 (the challenge of EdDSA-Poseidon, babyjub_ops.hpp; no public Poseidon call reaches it): fr_dot stops at five pairs because
+// 5 r < 2^256 < 6 r, so a fused row is fr_dot<5> plus one product and one sum (BN254_POSEIDON_ROW6_SPLIT=0, shipped) or two fr_dot<3> and a
+// sum (=1): 64 multiply-add rows per word either way, both canonical, the same bytes.  The host simulation runs both.
+#ifndef BN254_POSEIDON_ROW6_SPLIT
+#define BN254_POSEIDON_ROW6_SPLIT 0
+#endif
+template <int I>
+BN_FN Fr fr_poseidon_row6(const Fr (&s)[6]) {
+    const uint32_t (*m)[8] = psd::K<6>::M + I * 6;
+#if BN254_POSEIDON_ROW6_SPLIT
+    const Fr lo[3] = {s[0], s[1], s[2]}, hi[3] = {s[3], s[4], s[5]};
+    return fr_add(fr_dot<3>(lo, m), fr_dot<3>(hi, m + 3));
+#else
+    const Fr lo[5] = {s[0], s[1], s[2], s[3], s[4]};
+    return fr_add(fr_dot<5>(lo, m), fr_mul(s[5], fr_const(m[5])));
+#endif
+}
 template <int T, int I = 0>
 BN_FN void fr_poseidon_rows(const Fr (&s)[T], Fr (&n)[T]) {
     if constexpr (I < T) {
 #if BN254_POSEIDON_FUSED_ROW
-        n[I] = fr_dot<T>(s, psd::K<T>::M + I * T);
+        if constexpr (T == 6) n[I] = fr_poseidon_row6<I>(s);
+        else n[I] = fr_dot<T>(s, psd::K<T>::M + I * T);
 #else
         n[I] = fr_poseidon_row_tail<T, I>(s, fr_mul(s[0], fr_const(psd::K<T>::M[I * T])));
 #endif

@@ -828,6 +828,66 @@ class Engine:
     def g2_validate_batch_dev(self, d_p, d_status, n, stream=0):
         _native.check(self._lib.bn254_g2_validate_batch_dev(self._h, d_p, d_status, n, stream))
 
+    # ---- Baby Jubjub (the twisted Edwards curve over Fr; a point is two Fr, x then y, affine) and EdDSA-Poseidon on it
+    def bjj_validate_batch(self, p):
+        """(n,2,4) uint64 raw records -> (n,) int32 status: 0 valid (O included), 1 a coordinate's words are not below r, 4 not on the curve,
+        5 on the curve but [l]P != O"""
+        p = np.ascontiguousarray(p, np.uint64).reshape(-1, 2, 4); st = np.empty(p.shape[0], np.int32)
+        _native.check(self._lib.bn254_bjj_validate_batch(self._h, _p(p), _p(st), p.shape[0])); return st
+
+    def bjj_add_batch(self, p, q):
+        """(n,2,4) + (n,2,4) uint64 points of the curve -> (n,2,4): the complete affine sum"""
+        p = np.ascontiguousarray(p, np.uint64).reshape(-1, 2, 4); q = np.ascontiguousarray(q, np.uint64).reshape(-1, 2, 4)
+        if p.shape != q.shape:
+            raise ValueError(f"{p.shape[0]} points, {q.shape[0]} points")
+        out = np.empty_like(p)
+        _native.check(self._lib.bn254_bjj_add_batch(self._h, _p(p), _p(q), _p(out), p.shape[0])); return out
+
+    def bjj_mul_batch(self, p, k):
+        """(n,2,4) uint64 points of the curve, (n,4) uint64 Fr -> (n,2,4): [canonical integer of k] p, affine"""
+        p = np.ascontiguousarray(p, np.uint64).reshape(-1, 2, 4); k = np.ascontiguousarray(k, np.uint64).reshape(-1, 4)
+        if p.shape[0] != k.shape[0]:
+            raise ValueError(f"{p.shape[0]} points, {k.shape[0]} scalars")
+        out = np.empty_like(p)
+        _native.check(self._lib.bn254_bjj_mul_batch(self._h, _p(p), _p(k), _p(out), p.shape[0])); return out
+
+    def eddsa_poseidon_challenge_batch(self, a, r8, msg):
+        """(n,2,4) keys, (n,2,4) points R8, (n,4) messages -> (n,4) uint64: Poseidon5(r8.x, r8.y, a.x, a.y, msg), no curve check"""
+        a = np.ascontiguousarray(a, np.uint64).reshape(-1, 2, 4); r8 = np.ascontiguousarray(r8, np.uint64).reshape(-1, 2, 4)
+        msg = np.ascontiguousarray(msg, np.uint64).reshape(-1, 4)
+        if not a.shape[0] == r8.shape[0] == msg.shape[0]:
+            raise ValueError(f"{a.shape[0]} keys, {r8.shape[0]} points, {msg.shape[0]} messages")
+        out = np.empty_like(msg)
+        _native.check(self._lib.bn254_eddsa_poseidon_challenge_batch(self._h, _p(a), _p(r8), _p(msg), _p(out), a.shape[0])); return out
+
+    def eddsa_poseidon_verify_batch(self, a, r8, s, msg):
+        """keys, points R8, scalars S, messages -> (n,) int32 status: 1 a word array is not below r or S >= l, 4 R8 or A is not on the curve,
+        6 [S]B8 != R8 + [8 hm]A, 0 valid"""
+        a = np.ascontiguousarray(a, np.uint64).reshape(-1, 2, 4); r8 = np.ascontiguousarray(r8, np.uint64).reshape(-1, 2, 4)
+        s = np.ascontiguousarray(s, np.uint64).reshape(-1, 4); msg = np.ascontiguousarray(msg, np.uint64).reshape(-1, 4)
+        if not a.shape[0] == r8.shape[0] == s.shape[0] == msg.shape[0]:
+            raise ValueError(f"{a.shape[0]} keys, {r8.shape[0]} points, {s.shape[0]} scalars, {msg.shape[0]} messages")
+        st = np.empty(a.shape[0], np.int32)
+        _native.check(self._lib.bn254_eddsa_poseidon_verify_batch(self._h, _p(a), _p(r8), _p(s), _p(msg), _p(st), a.shape[0])); return st
+
+    def bjj_validate_batch_dev(self, d_p, d_status, n, stream=0):
+        """device pointers: records and n int32 statuses"""
+        _native.check(self._lib.bn254_bjj_validate_batch_dev(self._h, d_p, d_status, n, stream))
+
+    def bjj_add_batch_dev(self, d_p, d_q, d_out, n, stream=0):
+        """d_out may be exactly d_p or d_q"""
+        _native.check(self._lib.bn254_bjj_add_batch_dev(self._h, d_p, d_q, d_out, n, stream))
+
+    def bjj_mul_batch_dev(self, d_p, d_k, d_out, n, stream=0):
+        """d_out may be exactly d_p"""
+        _native.check(self._lib.bn254_bjj_mul_batch_dev(self._h, d_p, d_k, d_out, n, stream))
+
+    def eddsa_poseidon_challenge_batch_dev(self, d_a, d_r8, d_msg, d_out, n, stream=0):
+        _native.check(self._lib.bn254_eddsa_poseidon_challenge_batch_dev(self._h, d_a, d_r8, d_msg, d_out, n, stream))
+
+    def eddsa_poseidon_verify_batch_dev(self, d_a, d_r8, d_s, d_msg, d_status, n, stream=0):
+        _native.check(self._lib.bn254_eddsa_poseidon_verify_batch_dev(self._h, d_a, d_r8, d_s, d_msg, d_status, n, stream))
+
     # ---- the crate's variable-length byte stream (infinity = the lone byte 0)
     def _encode_stream(self, fn, p, rec):
         out = np.empty(p.shape[0] * rec, np.uint8); w = C.c_size_t()

@@ -14,7 +14,7 @@ import functools
 from .api import R_MOD, Fr, _scalar_array, default_engine
 
 R_F = 8
-R_P = {2: 56, 3: 57, 4: 56, 5: 60}
+R_P = {2: 56, 3: 57, 4: 56, 5: 60, 6: 60}      # width 6 is the challenge of EdDSA-Poseidon (bn_amd.eddsa): host functions and its own device calls only
 ARITY_MAX = 4
 
 
@@ -53,10 +53,10 @@ class _Grain:
 
 @functools.lru_cache(maxsize=None)
 def constants(t):
-    """(C, M) of width t = 2 .. 5 as Python integers: C the (R_F + R_P) * t round constants in round order, M the t x t Cauchy matrix as a
+    """(C, M) of width t = 2 .. 6 as Python integers: C the (R_F + R_P) * t round constants in round order, M the t x t Cauchy matrix as a
     tuple of rows, M[i][j] = 1 / (xs[i] + ys[j])"""
     if t not in R_P:
-        raise ValueError(f"Poseidon width t = {t}: 2 .. 5 are defined")
+        raise ValueError(f"Poseidon width t = {t}: 2 .. 6 are defined")
     g = _Grain(t, R_F, R_P[t])
     C = []
     while len(C) < (R_F + R_P[t]) * t:
@@ -65,14 +65,14 @@ def constants(t):
             C.append(v)
     xy = [g.draw() % R_MOD for _ in range(2 * t)]          # the matrix draws are reduced, not rejected
     xs, ys = xy[:t], xy[t:]
-    # the first attempt is good at all four widths (distinct values, no zero sum): there is no retry
+    # the first attempt is good at all five widths (distinct values, no zero sum): there is no retry
     assert len(set(xy)) == 2 * t and all((x + y) % R_MOD for x in xs for y in ys), "the Cauchy draw of this width needs the retry this module does not have"
     M = tuple(tuple(pow(x + y, -1, R_MOD) for y in ys) for x in xs)
     return tuple(C), M
 
 
 def permute_host(state):
-    """the permutation of a list of t = 2 .. 5 integers mod r, in host integers -> list of t integers"""
+    """the permutation of a list of t = 2 .. 6 integers mod r, in host integers -> list of t integers"""
     s = [int(x) % R_MOD for x in state]
     t = len(s)
     C, M = constants(t)

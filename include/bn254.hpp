@@ -389,6 +389,42 @@ inline std::vector<int32_t> g2_validate(const std::vector<G2> &p) {
     check(bn254_g2_validate_batch(nullptr, reinterpret_cast<const bn_g2 *>(p.data()), status.data(), p.size()));
     return status;
 }
+// Baby Jubjub (the twisted Edwards curve a x^2 + y^2 = 1 + d x^2 y^2 over Fr, a = 168700, d = 168696) and EdDSA-Poseidon on it.  A point is two
+// consecutive Fr, x then y, affine: a vector of 2 n elements holds n points.  bjj_validate: 0 valid (O = (0, 1) included), 1 a coordinate is not
+// below r, 4 not on the curve, 5 on the curve but [l]P != O.  eddsa_poseidon_verify is circomlib's verifyPoseidon: 1 range (S below l included),
+// 4 R8 or A not on the curve, 6 [S]B8 != R8 + [8 hm]A, 0 valid; there is NO subgroup check
+inline std::vector<int32_t> bjj_validate(const std::vector<Fr> &p) {
+    if (p.size() % 2) throw std::invalid_argument("bjj_validate: a point is two Fr");
+    std::vector<int32_t> status(p.size() / 2);
+    check(bn254_bjj_validate_batch(nullptr, reinterpret_cast<const bn_fr *>(p.data()), status.data(), status.size()));
+    return status;
+}
+inline std::vector<Fr> bjj_add(const std::vector<Fr> &p, const std::vector<Fr> &q) {
+    if (p.size() % 2 || p.size() != q.size()) throw std::invalid_argument("bjj_add: length mismatch");
+    std::vector<Fr> out(p.size());
+    check(bn254_bjj_add_batch(nullptr, reinterpret_cast<const bn_fr *>(p.data()), reinterpret_cast<const bn_fr *>(q.data()), reinterpret_cast<bn_fr *>(out.data()), p.size() / 2));
+    return out;
+}
+inline std::vector<Fr> bjj_mul(const std::vector<Fr> &p, const std::vector<Fr> &k) {
+    if (p.size() != 2 * k.size()) throw std::invalid_argument("bjj_mul: length mismatch");
+    std::vector<Fr> out(p.size());
+    check(bn254_bjj_mul_batch(nullptr, reinterpret_cast<const bn_fr *>(p.data()), reinterpret_cast<const bn_fr *>(k.data()), reinterpret_cast<bn_fr *>(out.data()), k.size()));
+    return out;
+}
+inline std::vector<Fr> eddsa_poseidon_challenge(const std::vector<Fr> &a, const std::vector<Fr> &r8, const std::vector<Fr> &msg) {
+    if (a.size() != 2 * msg.size() || r8.size() != 2 * msg.size()) throw std::invalid_argument("eddsa_poseidon_challenge: length mismatch");
+    std::vector<Fr> out(msg.size());
+    check(bn254_eddsa_poseidon_challenge_batch(nullptr, reinterpret_cast<const bn_fr *>(a.data()), reinterpret_cast<const bn_fr *>(r8.data()), reinterpret_cast<const bn_fr *>(msg.data()),
+                                               reinterpret_cast<bn_fr *>(out.data()), msg.size()));
+    return out;
+}
+inline std::vector<int32_t> eddsa_poseidon_verify(const std::vector<Fr> &a, const std::vector<Fr> &r8, const std::vector<Fr> &s, const std::vector<Fr> &msg) {
+    if (a.size() != 2 * msg.size() || r8.size() != 2 * msg.size() || s.size() != msg.size()) throw std::invalid_argument("eddsa_poseidon_verify: length mismatch");
+    std::vector<int32_t> status(msg.size());
+    check(bn254_eddsa_poseidon_verify_batch(nullptr, reinterpret_cast<const bn_fr *>(a.data()), reinterpret_cast<const bn_fr *>(r8.data()), reinterpret_cast<const bn_fr *>(s.data()),
+                                            reinterpret_cast<const bn_fr *>(msg.data()), status.data(), msg.size()));
+    return status;
+}
 // out[i] = (a[i] == b[i]) as group elements, whatever their Jacobian representations (groups/mod.rs:83-109): nothing is normalized
 inline std::vector<bool> g1_eq(const std::vector<G1> &a, const std::vector<G1> &b) {
     if (a.size() != b.size()) throw std::invalid_argument("g1_eq: length mismatch");

@@ -80,6 +80,11 @@
  *                          subgroup, by the endomorphism subgroup test), else the wire format's error number; what the Rust type system guarantees for the
  *                          reference's G1 / G2 values and a caller holding raw structs cannot know; no counterpart in the reference
  *   bn254_g1_validate_batch_dev / bn254_g2_validate_batch_dev  the same two on device-resident records, asynchronous on the caller's stream
+ *   bn254_bjj_validate_batch / bn254_bjj_add_batch / bn254_bjj_mul_batch  Baby Jubjub, the twisted Edwards curve over Fr: validation of raw points,
+ *                          the complete affine sum, out[i] = [k[i]] p[i];  bn254_eddsa_poseidon_challenge_batch  out[i] = Poseidon5(r8.x, r8.y, a.x, a.y,
+ *                          msg);  bn254_eddsa_poseidon_verify_batch  circomlib's verifyPoseidon per row; none has a counterpart in the reference
+ *   bn254_bjj_validate_batch_dev / bn254_bjj_add_batch_dev / bn254_bjj_mul_batch_dev / bn254_eddsa_poseidon_challenge_batch_dev /
+ *   bn254_eddsa_poseidon_verify_batch_dev  the same five on device-resident records, asynchronous on the caller's stream
  *   bn254_g2_precompute    coeffs[i][0..102) = q[i].to_affine().precompute().coeffs   groups/mod.rs:557-588 (Q != infinity)
  *   bn254_pairing_prepared_batch  out[i] = final_exponentiation(prepared.miller_loop(p[i]))   groups/mod.rs:486-519,768
  *   bn254_gt_mul_batch     out[i] = a[i] * b[i]                                     lib.rs:175-179, fields/fq12.rs:295-307
@@ -129,6 +134,8 @@
      bn254_g2_map_to_curve_batch, bn254_g2_clear_cofactor_batch, bn254_g2_hash_to_curve_uniform_batch and bn254_g2_hash_to_curve_batch serialise on the
      context in the same way (its mutex for the whole call).
      bn254_g1_validate_batch and bn254_g2_validate_batch serialise on the context in the same way (its mutex for the whole call).
+     bn254_bjj_validate_batch, bn254_bjj_add_batch, bn254_bjj_mul_batch, bn254_eddsa_poseidon_challenge_batch and bn254_eddsa_poseidon_verify_batch
+     serialise on the context in the same way (its mutex for the whole call).
  *     bn254_pairing_product_batch_prepared_native serialises on the context like them; its handle is immutable and shared freely.
  *     Use one context per thread (or bn254_multi_*) for more overlap;
  *     bn254_ctx_set_option is atomic, but set options before concurrent use: a call in flight may run some
@@ -185,6 +192,10 @@
      bn254_g1_validate_batch_dev and bn254_g2_validate_batch_dev use no scratch and no host operand either: one launch per sub-launch compares
      the words with q, checks the curve equation and (G2) runs the subgroup test.  Neither waits on anything or reads anything back (d_status
      stays on the device), so any number of threads may issue them on one context, each on its own stream and buffers.
+     bn254_bjj_validate_batch_dev, bn254_bjj_add_batch_dev, bn254_bjj_mul_batch_dev, bn254_eddsa_poseidon_challenge_batch_dev and
+     bn254_eddsa_poseidon_verify_batch_dev use no scratch and no host operand either: one launch per sub-launch does all of a record's work - the
+     verifier hashes, runs its joint chain and compares in one lane (each lane's window table is its own private memory).  None of the five waits
+     on anything or reads anything back, so any number of threads may issue them on one context, each on its own stream and buffers.
  */
 #ifndef BN254_HIP_H
 #define BN254_HIP_H
@@ -879,6 +890,50 @@ int bn254_g2_validate_batch(bn254_ctx *ctx, const bn_g2 *p, int32_t *status, siz
 int bn254_g1_validate_batch_dev(bn254_ctx *ctx, const void *d_p, void *d_status, size_t n, void *stream);
 int bn254_g2_validate_batch_dev(bn254_ctx *ctx, const void *d_p, void *d_status, size_t n, void *stream);
 
+/* Baby Jubjub and EdDSA-Poseidon, one record per lane.  Baby Jubjub is the twisted Edwards curve a x^2 + y^2 = 1 + d x^2 y^2 over Fr - THIS
+   library's scalar field - with a = 168700 and d = 168696: the curve circomlib, iden3 and the Hermez-style rollups sign on.  Identity O = (0, 1),
+   -(x, y) = (-x, y), order 8 l with l = 2736030358979909402780800718157159386076813972158567259200215660948447373041 (251 bits); the base point
+   B8 = (5299619240641551281634865583518297030282874472190772894086521144482721001553,
+   16950150798460657717958625567821834550301663161624707787222815936182638968203) has order l.  a is a square mod r and d is not, so the unified
+   addition law is complete: no exceptional inputs, doubling is the same formula.  A POINT is two consecutive bn_fr, x then y, canonical
+   Montgomery words, affine: p[2 i] and p[2 i + 1].  Scalars and messages are bn_fr like everywhere else; a scalar's value is the canonical
+   integer of the element.
+   bn254_bjj_validate_batch: status[i] for the raw record p[i], any 64 bytes, checked in this order:
+     1   a coordinate is not below r - the words are compared as they stand, before any field arithmetic
+     4   a x^2 + y^2 != 1 + d x^2 y^2: not on the curve
+     5   on the curve but [l]P != O: a component in the cofactor-8 part
+     0   otherwise: a valid point; O is one
+   Nothing is written but status; a record is never changed.
+   bn254_bjj_add_batch: out[i] = p[i] + q[i], the complete affine sum, defined for points of the curve - like the G1 calls it trusts its caller.
+   out may be p or q.
+   bn254_bjj_mul_batch: out[i] = [k[i]] p[i] for ANY point of the curve, cofactor components included, and any k in [0, r); affine; out may be p.
+   (8 l is above r: [8 l]P is [8]([l]P).)  One fixed-window chain of complete additions over the bits of the integer k, one inversion per lane.
+   bn254_eddsa_poseidon_challenge_batch: out[i] = Poseidon5(r8[i].x, r8[i].y, a[i].x, a[i].y, msg[i]) - circomlib's Poseidon at width t = 6
+   (R_F = 8, R_P = 60), element 0 of permute([0, ...]); plain field elements in, one bn_fr out, NO curve check.  The hash half of the verifier,
+   for signers and witness generators.  The public Poseidon calls above still stop at arity BN254_POSEIDON_ARITY_MAX.
+   bn254_eddsa_poseidon_verify_batch: circomlib's verifyPoseidon for the signature (r8[i], s[i]) on msg[i] under the key a[i]; status[i], checked
+   in this order, every row on its own:
+     1   a word array of a, r8, s or msg is not below r, or the integer of s is not below l
+     4   R8 or A is not on the curve
+     6   [S]B8 != R8 + [8 hm]A with hm the challenge above.  The scalar is the INTEGER 8 hm, not its value reduced mod l
+     0   valid
+   There is NO subgroup check, as there is none in circomlib: A = O, or A of small order, with R8 = [S]B8 verifies.  Check keys with
+   bn254_bjj_validate_batch where that matters.  One lane hashes, forms [8]A and runs one joint doubling chain for [S]B8 - [hm]([8]A), compared
+   with R8 without an inversion.
+   All five: a NULL pointer with work to do or n > 2^40 is BN254_E_BAD_ARG before any device is touched; n == 0 succeeds.  Calls run as
+   sub-launches of at most 2^22 records.  The _dev forms take device pointers (d_status too: int32_t per record), enqueue on `stream`, use no
+   host round trip and read nothing back.  Threading: see above. */
+int bn254_bjj_validate_batch(bn254_ctx *ctx, const bn_fr *p, int32_t *status, size_t n);
+int bn254_bjj_add_batch(bn254_ctx *ctx, const bn_fr *p, const bn_fr *q, bn_fr *out, size_t n);
+int bn254_bjj_mul_batch(bn254_ctx *ctx, const bn_fr *p, const bn_fr *k, bn_fr *out, size_t n);
+int bn254_eddsa_poseidon_challenge_batch(bn254_ctx *ctx, const bn_fr *a, const bn_fr *r8, const bn_fr *msg, bn_fr *out, size_t n);
+int bn254_eddsa_poseidon_verify_batch(bn254_ctx *ctx, const bn_fr *a, const bn_fr *r8, const bn_fr *s, const bn_fr *msg, int32_t *status, size_t n);
+int bn254_bjj_validate_batch_dev(bn254_ctx *ctx, const void *d_p, void *d_status, size_t n, void *stream);
+int bn254_bjj_add_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, void *d_out, size_t n, void *stream);
+int bn254_bjj_mul_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, void *d_out, size_t n, void *stream);
+int bn254_eddsa_poseidon_challenge_batch_dev(bn254_ctx *ctx, const void *d_a, const void *d_r8, const void *d_msg, void *d_out, size_t n, void *stream);
+int bn254_eddsa_poseidon_verify_batch_dev(bn254_ctx *ctx, const void *d_a, const void *d_r8, const void *d_s, const void *d_msg, void *d_status, size_t n, void *stream);
+
 /* ---- device-resident entry points (inputs/outputs already in HBM; `stream` is a hipStream_t or NULL) ------------------ */
 /* Same layouts (array of structs) in device memory.  Asynchronous on `stream`; the caller synchronises. */
 int bn254_pairing_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, void *d_out, size_t n, void *stream);
@@ -1011,6 +1066,7 @@ int bn254_profile_reset(bn254_ctx *ctx);
    of bn254_g1_map_to_curve_batch, bn254_g1_hash_to_curve_uniform_batch and bn254_g1_hash_to_curve_batch: "g1_map_to_curve", "g1_hash_to_curve", "g1_hash_to_curve_msg" (one scope per sub-launch);
    of bn254_g2_map_to_curve_batch, bn254_g2_clear_cofactor_batch, bn254_g2_hash_to_curve_uniform_batch and bn254_g2_hash_to_curve_batch: "g2_map_to_curve", "g2_clear_cofactor", "g2_hash_to_curve", "g2_hash_to_curve_msg" (one scope per sub-launch);
    of bn254_g1_validate_batch and bn254_g2_validate_batch: "g1_validate", "g2_validate" (one scope per sub-launch);
+   of bn254_bjj_{validate,add,mul}_batch and bn254_eddsa_poseidon_{challenge,verify}_batch: "bjj_validate", "bjj_add", "bjj_mul", "eddsa_poseidon_challenge", "eddsa_poseidon_verify" (one scope per sub-launch);
    and, of bn254_fr_ntt_batch: "ntt" (the passes), "ntt_table" (the builds of the twiddle tables).
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);
