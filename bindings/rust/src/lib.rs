@@ -60,6 +60,12 @@ extern "C" {
     fn bn254_bjj_mul_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_k: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_eddsa_poseidon_challenge_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_r8: *const c_void, d_msg: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_eddsa_poseidon_verify_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_r8: *const c_void, d_s: *const c_void, d_msg: *const c_void, d_status: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_bjj_pack_batch(ctx: *mut c_void, p: *const Fr, out32: *mut u8, n: usize) -> c_int;
+    fn bn254_bjj_unpack_batch(ctx: *mut c_void, in32: *const u8, out: *mut Fr, status: *mut i32, n: usize) -> c_int;
+    fn bn254_eddsa_poseidon_verify_packed_batch(ctx: *mut c_void, a32: *const u8, sig64: *const u8, msg: *const Fr, status: *mut i32, n: usize) -> c_int;
+    fn bn254_bjj_pack_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_out32: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_bjj_unpack_batch_dev(ctx: *mut c_void, d_in32: *const c_void, d_out: *mut c_void, d_status: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_eddsa_poseidon_verify_packed_batch_dev(ctx: *mut c_void, d_a32: *const c_void, d_sig64: *const c_void, d_msg: *const c_void, d_status: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     // prepared-G2 mode (the crate's internal G2Precomp, src/groups/mod.rs:472-483): 102 line coefficients per Q, then many P against them
     fn bn254_g2_precompute(ctx: *mut c_void, q: *const G2, coeffs: *mut EllCoeffs, n: usize) -> c_int;
     fn bn254_pairing_prepared_batch(ctx: *mut c_void, p: *const G1, coeffs: *const EllCoeffs, shared: c_int, out: *mut Gt, n: usize) -> c_int;
@@ -130,6 +136,7 @@ extern "C" {
     fn bn254_fr_inverse_batch(ctx: *mut c_void, a: *const Fr, out: *mut Fr, ok: *mut i32, n: usize) -> c_int;
     fn bn254_fr_pow_batch(ctx: *mut c_void, a: *const Fr, e: *const Fr, out: *mut Fr, n: usize) -> c_int;
     fn bn254_fr_interpret_batch(ctx: *mut c_void, bytes: *const u8, out: *mut Fr, n: usize) -> c_int;
+    fn bn254_fr_sqrt_batch(ctx: *mut c_void, a: *const Fr, out: *mut Fr, ok: *mut i32, n: usize) -> c_int;
     fn bn254_fr_root_of_unity(log_n: c_int, out: *mut Fr) -> c_int;
     fn bn254_fr_ntt_batch(ctx: *mut c_void, input: *const Fr, out: *mut Fr, log_n: c_int, count: usize, inverse: c_int, shift: *const Fr) -> c_int;
     fn bn254_fr_dot_batch(ctx: *mut c_void, coeff: *const Fr, index: *const u64, x: *const Fr, nx: usize, offsets: *const usize, m: usize, out: *mut Fr) -> c_int;
@@ -147,6 +154,7 @@ extern "C" {
     fn bn254_fr_inverse_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_out: *mut c_void, d_ok: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_pow_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_e: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_interpret_batch_dev(ctx: *mut c_void, d_in: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_fr_sqrt_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_out: *mut c_void, d_ok: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_ntt_batch_dev(ctx: *mut c_void, d_in: *const c_void, d_out: *mut c_void, log_n: c_int, count: usize, inverse: c_int, shift: *const Fr, stream: *mut c_void) -> c_int;
     fn bn254_fr_dot_batch_dev(ctx: *mut c_void, d_coeff: *const c_void, d_index: *const c_void, d_x: *const c_void, nx: usize, offsets: *const usize, m: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn bn254_fr_scan_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_init: *const c_void, offsets: *const usize, m: usize, flags: c_int, d_out: *mut c_void, stream: *mut c_void) -> c_int;
@@ -697,6 +705,42 @@ pub fn g1_validate_batch(p: &[G1]) -> Result<Vec<i32>, GpuError> {
 pub fn g2_validate_batch(p: &[G2]) -> Result<Vec<i32>, GpuError> {
     let mut status = vec![0i32; p.len()];
     check(unsafe { bn254_g2_validate_batch(std::ptr::null_mut(), p.as_ptr(), status.as_mut_ptr(), p.len()) })?;
+    Ok(status)
+}
+
+/// `Option<Fr>` square roots: the root whose canonical integer is not above `(r - 1) / 2`, `None` for a non-residue.
+pub fn fr_sqrt(a: &[Fr]) -> Result<Vec<Option<Fr>>, GpuError> {
+    let mut out = vec![Fr::zero(); a.len()];
+    let mut ok = vec![0i32; a.len()];
+    check(unsafe { bn254_fr_sqrt_batch(std::ptr::null_mut(), a.as_ptr(), out.as_mut_ptr(), ok.as_mut_ptr(), a.len()) })?;
+    Ok(out.into_iter().zip(ok).map(|(x, k)| if k != 0 { Some(x) } else { None }).collect())
+}
+
+/// Baby Jubjub points (`2 n` elements) to circomlib's 32-byte records: `y` little endian, the sign of `x` in the top bit.  No validation.
+pub fn bjj_pack_batch(p: &[Fr]) -> Result<Vec<u8>, GpuError> {
+    assert_eq!(p.len() % 2, 0);
+    let mut out = vec![0u8; 16 * p.len()];
+    check(unsafe { bn254_bjj_pack_batch(std::ptr::null_mut(), p.as_ptr(), out.as_mut_ptr(), p.len() / 2) })?;
+    Ok(out)
+}
+
+/// 32-byte records to points and one status each: 1 `y` is not below r, 4 no point has this `y`, 3 `x == 0` with the sign bit set, else 0.
+/// A rejected record gives the identity `(0, 1)`.  No subgroup check.
+pub fn bjj_unpack_batch(in32: &[u8]) -> Result<(Vec<Fr>, Vec<i32>), GpuError> {
+    assert_eq!(in32.len() % 32, 0);
+    let n = in32.len() / 32;
+    let mut out = vec![Fr::zero(); 2 * n];
+    let mut status = vec![0i32; n];
+    check(unsafe { bn254_bjj_unpack_batch(std::ptr::null_mut(), in32.as_ptr(), out.as_mut_ptr(), status.as_mut_ptr(), n) })?;
+    Ok((out, status))
+}
+
+/// `eddsa_poseidon_verify_batch` on packed keys (32 bytes) and packed signatures (64 bytes: packed `R8`, then `S` little endian): 1 range,
+/// 4 a point has no `x`, 3 a non-canonical sign, 6 the equation fails, 0 valid.
+pub fn eddsa_poseidon_verify_packed_batch(a32: &[u8], sig64: &[u8], msg: &[Fr]) -> Result<Vec<i32>, GpuError> {
+    assert!(a32.len() == 32 * msg.len() && sig64.len() == 64 * msg.len());
+    let mut status = vec![0i32; msg.len()];
+    check(unsafe { bn254_eddsa_poseidon_verify_packed_batch(std::ptr::null_mut(), a32.as_ptr(), sig64.as_ptr(), msg.as_ptr(), status.as_mut_ptr(), msg.len()) })?;
     Ok(status)
 }
 

@@ -69,6 +69,9 @@ class Fr:
     @property
     def limbs(self): return _mont(self.v, R_MOD)
     def inverse(self): return None if self.v == 0 else Fr(pow(self.v, -1, R_MOD))
+    def sqrt(self):
+        """the square root whose integer is not above (r - 1) / 2, None for a non-residue (on the GPU: fr_sqrt_batch)"""
+        return fr_sqrt_batch([self])[0]
     def is_zero(self): return self.v == 0
     def pow(self, e): return Fr(pow(self.v, e.v, R_MOD))
     def __add__(self, o): return Fr(self.v + o.v)
@@ -532,6 +535,13 @@ def fr_inverse_batch(a, engine=None):
     return [Fr.from_limbs(r) if k else None for r, k in zip(out, ok)]
 
 
+def fr_sqrt_batch(a, engine=None):
+    """[x.sqrt() for x in a]: a list of Fr, None where x is a non-residue.  Of the two roots the one whose canonical integer is not above
+    (r - 1) / 2 comes out; 0 has the root 0.  No counterpart in the reference crate"""
+    out, ok = (engine or default_engine()).fr_sqrt_batch(_scalar_array(a))
+    return [Fr.from_limbs(r) if k else None for r, k in zip(out, ok)]
+
+
 def fr_interpret_batch(bufs, engine=None):
     """[Fr.interpret(b) for b in bufs] (lib.rs:27-29): a sequence of 64-byte buffers, or an (n,64) uint8 array"""
     if not isinstance(bufs, np.ndarray):
@@ -753,6 +763,40 @@ def eddsa_poseidon_verify_batch(a, r8, s, msg, engine=None):
     if not A.shape[0] == R8.shape[0] == S.shape[0] == M.shape[0]:
         raise ValueError(f"{A.shape[0]} keys, {R8.shape[0]} points, {S.shape[0]} scalars, {M.shape[0]} messages")
     return (engine or default_engine()).eddsa_poseidon_verify_batch(A, R8, S, M)
+
+
+def _byte_records(records, size):
+    if isinstance(records, np.ndarray):
+        return np.ascontiguousarray(records, np.uint8).reshape(-1, size)
+    records = [bytes(b) for b in records]
+    if any(len(b) != size for b in records):
+        raise ValueError(f"every record is {size} bytes")
+    return np.frombuffer(b"".join(records), np.uint8).reshape(-1, size)
+
+
+def bjj_pack_batch(points, engine=None):
+    """[32 bytes per Baby Jubjub point] (circomlib's packPoint as bn_amd.babyjub describes it): y little endian, bit 7 of the last byte set iff
+    the integer of x is above (r - 1) / 2.  No validation.  points as for bjj_add_batch"""
+    return [r.tobytes() for r in (engine or default_engine()).bjj_pack_batch(_bjj_points(points))]
+
+
+def bjj_unpack_batch(records, engine=None):
+    """(list of babyjub.Point, (n,) int32 status) per 32-byte record: 1 y is not below r, 4 no point has this y, 3 x == 0 with the sign bit set
+    (this project's choice), 0 otherwise; a rejected record gives the identity.  No subgroup check, as in circomlib: bjj_validate_batch is there
+    for that.  records: a sequence of 32-byte strings or an (n,32) uint8 array"""
+    from .babyjub import Point
+    out, st = (engine or default_engine()).bjj_unpack_batch(_byte_records(records, 32))
+    return [Point.from_limbs(r) for r in out], st
+
+
+def eddsa_poseidon_verify_packed_batch(a32, sig64, msg, engine=None):
+    """(n,) int32 per packed signature (64 bytes: the packed R8, then S little endian) on msg under the packed key (32 bytes): 1 a y, S or msg is
+    out of range, 4 a point has no x, 3 a non-canonical sign, 6 [S]B8 != R8 + [8 hm]A, 0 valid - checked in that order, every row on its own,
+    in one launch.  No subgroup check"""
+    A, S, M = _byte_records(a32, 32), _byte_records(sig64, 64), _scalar_array(msg)
+    if not A.shape[0] == S.shape[0] == M.shape[0]:
+        raise ValueError(f"{A.shape[0]} keys, {S.shape[0]} signatures, {M.shape[0]} messages")
+    return (engine or default_engine()).eddsa_poseidon_verify_packed_batch(A, S, M)
 
 
 class PreparedG2:

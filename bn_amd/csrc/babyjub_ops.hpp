@@ -26,6 +26,7 @@
 #pragma once
 #include <stddef.h>
 #include "poseidon_ops.hpp"
+#include "fr_sqrt_ops.hpp"
 #include "babyjub_constants.hpp"
 
 // The joint window of the verifier, 1 or 2 bits per scalar.  The rule was fixed before measuring: the smaller median of five
@@ -49,12 +50,6 @@ BN_FN BjjExt bjj_from_affine(const Fr &x, const Fr &y) { return {x, y, fr_one(),
 BN_FN BjjExt bjj_neg(const BjjExt &p) { return {fr_sub(fr_zero(), p.x), p.y, p.z, fr_sub(fr_zero(), p.t)}; }
 BN_FN BjjExt bjj_select(bool take_b, const BjjExt &a, const BjjExt &b) {
     return {fr_select(take_b, a.x, b.x), fr_select(take_b, a.y, b.y), fr_select(take_b, a.z, b.z), fr_select(take_b, a.t, b.t)};
-}
-BN_FN bool fr_eq(const Fr &a, const Fr &b) {
-    uint32_t o = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o |= a.w[i] ^ b.w[i];
-    return o == 0;
 }
 BN_FN BjjExt bjj_add(const BjjExt &p, const BjjExt &q) {
     const Fr a = fr_mul(p.x, q.x), b = fr_mul(p.y, q.y);
@@ -170,6 +165,16 @@ BN_FN void eddsa_challenge_body(const uint32_t *a, const uint32_t *r8, const uin
 // statuses in the order of the checks: 1 range (a word array of a, r8, s or msg is not below r, or the integer of s is not below l), 4 R8 or A
 // is not on the curve, 6 the equation fails, 0 valid.  A row that fails a check computes on O and zeros from there on: every lane runs the
 // whole chain, every case is a select
+// the core both verifiers share, on inputs that passed (or were replaced by O and zeros after) every check: hash, [8]A, the joint chain, the
+// projective comparison.  sr is the integer S, m a Montgomery image
+template <int W>
+BN_FN bool eddsa_verify_core(const Fr &ax, const Fr &ay, const Fr &rx, const Fr &ry, const Fr &sr, const Fr &m) {
+    const Fr hr = fr_raw(eddsa_challenge(ax, ay, rx, ry, m));
+    const BjjExt na8 = bjj_neg(bjj_double(bjj_double(bjj_double(bjj_from_affine(ax, ay)))));
+    BjjExt v;
+    bjj_joint_chain<W>(na8, sr, hr, v);                                           // [S]B8 - [hm][8]A, to be R8
+    return fr_eq(v.x, fr_mul(rx, v.z)) & fr_eq(v.y, fr_mul(ry, v.z));
+}
 template <int W>
 BN_FN void eddsa_verify_body(const uint32_t *a, const uint32_t *r8, const uint32_t *s, const uint32_t *msg, int32_t *status, size_t i) {
     Fr ax = fr_load(a, 2 * i), ay = fr_load(a, 2 * i + 1), rx = fr_load(r8, 2 * i), ry = fr_load(r8, 2 * i + 1), sm = fr_load(s, i), m = fr_load(msg, i);
@@ -183,12 +188,61 @@ BN_FN void eddsa_verify_body(const uint32_t *a, const uint32_t *r8, const uint32
     const bool on_curve = bjj_on_curve(rx, ry) & bjj_on_curve(ax, ay);
     ax = fr_select(on_curve, fr_zero(), ax); ay = fr_select(on_curve, fr_one(), ay);
     rx = fr_select(on_curve, fr_zero(), rx); ry = fr_select(on_curve, fr_one(), ry);
-    const Fr hr = fr_raw(eddsa_challenge(ax, ay, rx, ry, m));
-    const BjjExt na8 = bjj_neg(bjj_double(bjj_double(bjj_double(bjj_from_affine(ax, ay)))));
-    BjjExt v;
-    bjj_joint_chain<W>(na8, sr, hr, v);                                           // [S]B8 - [hm][8]A, to be R8
-    const bool eq = fr_eq(v.x, fr_mul(rx, v.z)) & fr_eq(v.y, fr_mul(ry, v.z));
+    const bool eq = eddsa_verify_core<W>(ax, ay, rx, ry, sr, m);
     status[i] = !in_range ? 1 : !on_curve ? 4 : !eq ? 6 : 0;
+}
+
+// ---- packed points (circomlib's packPoint): 32 bytes, the canonical integer of y little endian, bit 7 of byte 31 set iff the canonical
+// integer of x is above (r - 1) / 2.  On a little-endian device the record is the eight words of that integer
+BN_FN void bjj_pack_body(const uint32_t *p, uint32_t *out32, size_t i) {
+    const Fr xr = fr_raw(fr_load(p, 2 * i));
+    Fr yr = fr_raw(fr_load(p, 2 * i + 1));
+    yr.w[7] |= fr_raw_above_half(xr) ? 0x80000000u : 0u;
+    fr_store(yr, out32, i);
+}
+// what a record holds: in_range the integer of y (the sign bit cleared) is below r; has_x some point has this y:
+// x^2 = (1 - y^2) / (a - d y^2) is a square (the denominator is never zero: a / d is a non-residue); canonical not (x == 0 and the sign bit
+// set).  (x, y) is the point when all three hold and O = (0, 1) otherwise.  The flags are computed in that order, each on O once one failed
+struct BjjUnpacked { Fr x, y; bool in_range, has_x, canonical; };
+template <int FORM>
+BN_FN BjjUnpacked bjj_unpack_point(Fr rec) {
+    BjjUnpacked o;
+    const bool sign = (rec.w[7] >> 31) != 0;
+    rec.w[7] &= 0x7fffffffu;
+    o.in_range = fr_lt_r(rec.w);
+    const Fr y = fr_select(o.in_range, fr_one(), fr_mul(rec, fr_const(k::FR_R2_32)));        // R^2 is the canonical operand
+    const Fr yy = fr_mul(y, y);
+    FrSqrt r;
+    fr_sqrt_ratio<FORM>(fr_sub(fr_one(), yy), fr_sub(fr_const(bjj::A_M), fr_mul(yy, fr_const(bjj::D_M))), r);
+    o.has_x = r.is_square;
+    o.canonical = !(fr_is_zero(r.root) & sign);
+    const bool ok = o.in_range & o.has_x & o.canonical;
+    o.x = fr_select(ok, fr_zero(), fr_select(sign, r.root, fr_sub(fr_zero(), r.root)));
+    o.y = fr_select(ok, fr_one(), y);
+    return o;
+}
+// statuses in the order of the checks: 1 range, 4 no point has this y, 3 a non-canonical sign, 0 otherwise; a rejected record is O.
+// out may not be in32 (the records differ in size)
+template <int FORM>
+BN_FN void bjj_unpack_body(const uint32_t *in32, uint32_t *out, int32_t *status, size_t i) {
+    const BjjUnpacked u = bjj_unpack_point<FORM>(fr_load(in32, i));
+    fr_store(u.x, out, 2 * i);
+    fr_store(u.y, out, 2 * i + 1);
+    status[i] = !u.in_range ? 1 : !u.has_x ? 4 : !u.canonical ? 3 : 0;
+}
+// The verifier on the wire bytes: a32 the packed key, sig64 the packed R8 followed by the integer S as 32 little-endian bytes (its top bit
+// is no flag), msg as in eddsa_verify_body.  Statuses in the order of the checks: 1 a y, S or msg out of range, 4 a point has no x, 3 a
+// non-canonical sign in either point, 6 the equation fails, 0 valid.  A row that fails computes on O and zeros from there on
+template <int W, int FORM>
+BN_FN void eddsa_verify_packed_body(const uint32_t *a32, const uint32_t *sig64, const uint32_t *msg, int32_t *status, size_t i) {
+    const BjjUnpacked a = bjj_unpack_point<FORM>(fr_load(a32, i)), r8 = bjj_unpack_point<FORM>(fr_load(sig64, 2 * i));
+    Fr sr = fr_load(sig64, 2 * i + 1), m = fr_load(msg, i);
+    const bool in_range = a.in_range & r8.in_range & bjj_lt(sr.w, bjj::L_RAW) & fr_lt_r(m.w);
+    const bool has_x = a.has_x & r8.has_x, canonical = a.canonical & r8.canonical, ok = in_range & has_x & canonical;
+    sr = fr_select(ok, fr_zero(), sr); m = fr_select(ok, fr_zero(), m);
+    const Fr ax = fr_select(ok, fr_zero(), a.x), ay = fr_select(ok, fr_one(), a.y), rx = fr_select(ok, fr_zero(), r8.x), ry = fr_select(ok, fr_one(), r8.y);
+    const bool eq = eddsa_verify_core<W>(ax, ay, rx, ry, sr, m);
+    status[i] = !in_range ? 1 : !has_x ? 4 : !canonical ? 3 : !eq ? 6 : 0;
 }
 
 }  // namespace bn254

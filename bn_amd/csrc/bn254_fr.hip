@@ -146,6 +146,7 @@ int bn254_fr_interpret_batch(bn254_ctx *ctx, const uint8_t *in, bn_fr *out, size
 unsigned bn254_fr_inverse_run(void) { return FR_INV_RUN; }
 unsigned bn254_fr_pow_window(void) { return FR_POW_WINDOW; }
 int bn254_fr_set_launch_max(size_t elements) { return g_fr_launch_max.set(elements); }
+size_t bn254_fr_launch_step(void) { return g_fr_launch_max.step(); }          // bn254_fr_sqrt.hip: the square roots cut their sub-launches by the same override
 int bn254_fr_set_inverse_run(unsigned K) { return K > 64 ? BN254_E_BAD_ARG : g_fr_inverse_run.set(K); }
 int bn254_fr_set_pow_window(unsigned bits) { return bits != 0 && bits != 1 && bits != 2 && bits != 4 ? BN254_E_BAD_ARG : g_fr_pow_window.set(bits); }
 

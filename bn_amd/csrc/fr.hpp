@@ -32,6 +32,12 @@ BN_FN bool fr_is_zero(const Fr &a) {
     for (int i = 0; i < 8; ++i) o |= a.w[i];
     return o == 0;
 }
+BN_FN bool fr_eq(const Fr &a, const Fr &b) {
+    uint32_t o = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o |= a.w[i] ^ b.w[i];
+    return o == 0;
+}
 BN_FN Fr fr_select(bool take_b, const Fr &a, const Fr &b) {
     Fr r;
 #pragma unroll

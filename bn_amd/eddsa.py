@@ -9,14 +9,20 @@ and the Hermez-style rollups, with the point arithmetic and the hash on the GPU.
 circomlib's A is [key >> 3]B8 with S = rho + hm * key: the same equation with s = key >> 3 (key is a multiple of 8).  circomlib derives key and
 rho with BLAKE-512, which Python's hashlib does not have: KEY AND NONCE DERIVATION HERE ARE NOT circomlib's - the default nonce is SHA-512 of
 secret and message reduced mod l, a secret is whatever integer the caller brings.  Only the signatures (and what verifies) are circomlib's; one
-published circomlibjs vector is checked by the tests, nothing beyond it."""
+published circomlibjs vector is checked by the tests, nothing beyond it.
+
+Packed forms (pack_signature / unpack_signature, verify_packed*, sign_batch(packed=True)): a key is babyjub's 32-byte packed point, a
+signature is 64 bytes - the packed R8, then S as 32 little-endian bytes - the layout of circomlibjs' packSignature as its documentation
+describes it, written from memory: NO packed vector of circomlibjs has been checked (the one published vector is affine).  verify_packed* run
+ONE launch on the wire bytes: a lane unpacks both points (a square root in Fr each) and then runs the hash and the chain of the unpacked
+verifier.  A point with x == 0 and the sign bit set is rejected (status 3): this project's decision, which may differ from circomlibjs."""
 import hashlib
 
 import numpy as np
 
 from . import babyjub as BJ
 from . import poseidon
-from .api import R_MOD, Fr, eddsa_poseidon_challenge_batch, eddsa_poseidon_verify_batch
+from .api import R_MOD, Fr, eddsa_poseidon_challenge_batch, eddsa_poseidon_verify_batch, eddsa_poseidon_verify_packed_batch
 
 
 def _int(v):
@@ -34,9 +40,9 @@ def default_nonce(secret, msg):
     return int.from_bytes(h, "little") % BJ.L
 
 
-def sign_batch(secrets, msgs, nonces=None, engine=None):
+def sign_batch(secrets, msgs, nonces=None, engine=None, packed=False):
     """[(R8, S)] for messages (Fr or integers mod r) under integer secrets: one bjj_mul_batch for the keys and the R8 together, one challenge
-    call, S in host integers.  nonces: integers, None for default_nonce"""
+    call, S in host integers.  nonces: integers, None for default_nonce.  packed: 64-byte signatures instead (one bjj_pack_batch more)"""
     secrets = [_int(s) for s in secrets]; msgs = [_int(m) % R_MOD for m in msgs]
     if len(secrets) != len(msgs):
         raise ValueError(f"{len(secrets)} secrets, {len(msgs)} messages")
@@ -48,11 +54,28 @@ def sign_batch(secrets, msgs, nonces=None, engine=None):
     pts = BJ.mul_base([Fr(k) for k in secrets + [x % BJ.L for x in nonces]], engine=engine)
     A, R8 = pts[:len(msgs)], pts[len(msgs):]
     hm = eddsa_poseidon_challenge_batch(A, R8, [Fr(m) for m in msgs], engine=engine)
-    return [(r8, (rho + 8 * h.v * s) % BJ.L) for r8, rho, h, s in zip(R8, nonces, hm, secrets)]
+    ss = [(rho + 8 * h.v * s) % BJ.L for rho, h, s in zip(nonces, hm, secrets)]
+    if packed:
+        return [r + s.to_bytes(32, "little") for r, s in zip(BJ.pack_batch(R8, engine=engine), ss)]
+    return list(zip(R8, ss))
 
 
-def sign(secret, msg, nonce=None, engine=None):
-    return sign_batch([secret], [msg], None if nonce is None else [nonce], engine=engine)[0]
+def sign(secret, msg, nonce=None, engine=None, packed=False):
+    return sign_batch([secret], [msg], None if nonce is None else [nonce], engine=engine, packed=packed)[0]
+
+
+def pack_signature(sig):
+    """(R8, S) -> 64 bytes: the packed R8 (babyjub.pack_host), then S as 32 little-endian bytes; S must fit 256 bits"""
+    return BJ.pack_host(sig[0]) + _int(sig[1]).to_bytes(32, "little")
+
+
+def unpack_signature(b):
+    """64 bytes -> ((R8 as an (x, y) pair, S), status of the point) in host integers; nothing about S is checked"""
+    b = bytes(b)
+    if len(b) != 64:
+        raise ValueError("a packed signature is 64 bytes")
+    r8, st = BJ.unpack_host(b[:32])
+    return (r8, int.from_bytes(b[32:], "little")), st
 
 
 def _sig_arrays(pks, msgs, sigs):
@@ -82,6 +105,41 @@ def verify_batch(pks, msgs, sigs, engine=None):
 
 def verify(pk, msg, sig, engine=None):
     return verify_batch([pk], [msg], [sig], engine=engine)[0]
+
+
+def _msg_array(msgs):
+    return np.stack([Fr(_int(m)).limbs for m in msgs]) if len(msgs) else np.zeros((0, 4), np.uint64)
+
+
+def verify_packed_status_batch(pks32, msgs, sigs64, engine=None):
+    """(n,) int32 per (packed key, message, packed signature): the statuses of eddsa_poseidon_verify_packed_batch (0 valid, 1 range, 4 a point
+    has no x, 3 a non-canonical sign, 6 equation).  Keys and signatures: sequences of 32- and 64-byte strings, or uint8 arrays"""
+    msgs = list(msgs)
+    if not len(pks32) == len(msgs) == len(sigs64):
+        raise ValueError(f"{len(pks32)} keys, {len(msgs)} messages, {len(sigs64)} signatures")
+    return eddsa_poseidon_verify_packed_batch(pks32, sigs64, _msg_array(msgs), engine=engine)
+
+
+def verify_packed_batch(pks32, msgs, sigs64, engine=None):
+    """list of bool: packed signature i is valid for message i under packed key i (one call, one lane per signature)"""
+    return [int(s) == 0 for s in verify_packed_status_batch(pks32, msgs, sigs64, engine=engine)]
+
+
+def verify_packed(pk32, msg, sig64, engine=None):
+    return verify_packed_batch([pk32], [msg], [sig64], engine=engine)[0]
+
+
+def verify_packed_status_host(pk32, msg, sig64):
+    """the status of one packed signature in host integers, in the order of the device's checks"""
+    (r8, s), st_r = unpack_signature(sig64)
+    a, st_a = BJ.unpack_host(pk32)
+    m = _int(msg)
+    if 1 in (st_a, st_r) or not (0 <= s < BJ.L and 0 <= m < R_MOD):
+        return 1
+    for st in (4, 3):
+        if st in (st_a, st_r):
+            return st
+    return verify_status_host(a, m, (r8, s))
 
 
 def challenge_host(a, r8, msg):

@@ -447,6 +447,14 @@ class Engine:
         _native.check(self._lib.bn254_fr_inverse_batch(self._h, _p(a), _p(out), _p(ok), a.shape[0]))
         return out, ok != 0
 
+    def fr_sqrt_batch(self, a):
+        """(out, ok): out[i] = the square root of a[i] whose canonical integer is not above (r - 1) / 2 and ok[i] True, or Fr::zero() and False
+        where a[i] is a non-residue -> (n, 4) uint64, (n,) bool (include/bn254_hip.h bn254_fr_sqrt_batch)"""
+        a = _arr(a, 4) if len(a) else np.zeros((0, 4), np.uint64)
+        out = np.empty_like(a); ok = np.empty(a.shape[0], np.int32)
+        _native.check(self._lib.bn254_fr_sqrt_batch(self._h, _p(a), _p(out), _p(ok), a.shape[0]))
+        return out, ok != 0
+
     def fr_interpret_batch(self, buf):
         """out[i] = the 64-byte record i of `buf` as a big-endian 512-bit integer, mod r (Fr::interpret, lib.rs:27-29) -> (n, 4) uint64"""
         b = np.ascontiguousarray(buf, np.uint8).reshape(-1, 64)
@@ -870,6 +878,39 @@ class Engine:
         st = np.empty(a.shape[0], np.int32)
         _native.check(self._lib.bn254_eddsa_poseidon_verify_batch(self._h, _p(a), _p(r8), _p(s), _p(msg), _p(st), a.shape[0])); return st
 
+    def bjj_pack_batch(self, p):
+        """(n,2,4) uint64 points -> (n,32) uint8: y little endian, bit 7 of byte 31 set iff the integer of x is above (r - 1) / 2; no validation"""
+        p = np.ascontiguousarray(p, np.uint64).reshape(-1, 2, 4); out = np.empty((p.shape[0], 32), np.uint8)
+        _native.check(self._lib.bn254_bjj_pack_batch(self._h, _p(p), _p(out), p.shape[0])); return out
+
+    def bjj_unpack_batch(self, in32):
+        """(n,32) uint8 -> ((n,2,4) uint64 points, (n,) int32 status): 1 y is not below r, 4 no point has this y, 3 x == 0 with the sign bit
+        set, 0 otherwise; a rejected record gives O = (0, 1).  No subgroup check"""
+        b = np.ascontiguousarray(in32, np.uint8).reshape(-1, 32)
+        out = np.empty((b.shape[0], 2, 4), np.uint64); st = np.empty(b.shape[0], np.int32)
+        _native.check(self._lib.bn254_bjj_unpack_batch(self._h, _p(b), _p(out), _p(st), b.shape[0])); return out, st
+
+    def eddsa_poseidon_verify_packed_batch(self, a32, sig64, msg):
+        """(n,32) uint8 packed keys, (n,64) uint8 packed signatures, (n,4) messages -> (n,) int32 status: 1 a y, S or msg is out of range, 4 a
+        point has no x, 3 a non-canonical sign, 6 [S]B8 != R8 + [8 hm]A, 0 valid.  One launch: a lane unpacks its two points and verifies"""
+        a32 = np.ascontiguousarray(a32, np.uint8).reshape(-1, 32); sig64 = np.ascontiguousarray(sig64, np.uint8).reshape(-1, 64)
+        msg = np.ascontiguousarray(msg, np.uint64).reshape(-1, 4)
+        if not a32.shape[0] == sig64.shape[0] == msg.shape[0]:
+            raise ValueError(f"{a32.shape[0]} keys, {sig64.shape[0]} signatures, {msg.shape[0]} messages")
+        st = np.empty(msg.shape[0], np.int32)
+        _native.check(self._lib.bn254_eddsa_poseidon_verify_packed_batch(self._h, _p(a32), _p(sig64), _p(msg), _p(st), msg.shape[0])); return st
+
+    def bjj_pack_batch_dev(self, d_p, d_out32, n, stream=0):
+        """device pointers: n points and 32 n bytes"""
+        _native.check(self._lib.bn254_bjj_pack_batch_dev(self._h, d_p, d_out32, n, stream))
+
+    def bjj_unpack_batch_dev(self, d_in32, d_out, d_status, n, stream=0):
+        """device pointers: 32 n bytes, n points and n int32 statuses"""
+        _native.check(self._lib.bn254_bjj_unpack_batch_dev(self._h, d_in32, d_out, d_status, n, stream))
+
+    def eddsa_poseidon_verify_packed_batch_dev(self, d_a32, d_sig64, d_msg, d_status, n, stream=0):
+        _native.check(self._lib.bn254_eddsa_poseidon_verify_packed_batch_dev(self._h, d_a32, d_sig64, d_msg, d_status, n, stream))
+
     def bjj_validate_batch_dev(self, d_p, d_status, n, stream=0):
         """device pointers: records and n int32 statuses"""
         _native.check(self._lib.bn254_bjj_validate_batch_dev(self._h, d_p, d_status, n, stream))
@@ -998,6 +1039,10 @@ class Engine:
     def fr_inverse_batch_dev(self, d_a, d_out, d_ok, n, stream=0):
         """d_ok: n int32 (1 / 0), or None"""
         _native.check(self._lib.bn254_fr_inverse_batch_dev(self._h, d_a, d_out, d_ok, n, stream))
+
+    def fr_sqrt_batch_dev(self, d_a, d_out, d_ok, n, stream=0):
+        """d_ok: n int32 (1 / 0), or None; d_out may be exactly d_a"""
+        _native.check(self._lib.bn254_fr_sqrt_batch_dev(self._h, d_a, d_out, d_ok, n, stream))
 
     def fr_interpret_batch_dev(self, d_in, d_out, n, stream=0):
         """d_in: 64 n bytes, d_out: n records"""

@@ -184,6 +184,13 @@ inline std::pair<std::vector<Fr>, std::vector<bool>> fr_inverse(const std::vecto
     check(bn254_fr_inverse_batch(nullptr, reinterpret_cast<const bn_fr *>(a.data()), reinterpret_cast<bn_fr *>(out.data()), ok.data(), a.size()));
     return {out, std::vector<bool>(ok.begin(), ok.end())};
 }
+// Option<Fr> square roots: the root whose canonical integer is not above (r - 1) / 2; false and Fr::zero() for a non-residue
+inline std::pair<std::vector<Fr>, std::vector<bool>> fr_sqrt(const std::vector<Fr> &a) {
+    std::vector<Fr> out(a.size());
+    std::vector<int32_t> ok(a.size());
+    check(bn254_fr_sqrt_batch(nullptr, reinterpret_cast<const bn_fr *>(a.data()), reinterpret_cast<bn_fr *>(out.data()), ok.data(), a.size()));
+    return {out, std::vector<bool>(ok.begin(), ok.end())};
+}
 inline std::vector<Fr> fr_interpret(const std::vector<std::array<uint8_t, 64>> &bufs) {
     std::vector<Fr> out(bufs.size());
     check(bn254_fr_interpret_batch(nullptr, reinterpret_cast<const uint8_t *>(bufs.data()), reinterpret_cast<bn_fr *>(out.data()), bufs.size()));
@@ -423,6 +430,28 @@ inline std::vector<int32_t> eddsa_poseidon_verify(const std::vector<Fr> &a, cons
     std::vector<int32_t> status(msg.size());
     check(bn254_eddsa_poseidon_verify_batch(nullptr, reinterpret_cast<const bn_fr *>(a.data()), reinterpret_cast<const bn_fr *>(r8.data()), reinterpret_cast<const bn_fr *>(s.data()),
                                             reinterpret_cast<const bn_fr *>(msg.data()), status.data(), msg.size()));
+    return status;
+}
+// Packed points and signatures (circomlib's packPoint / packSignature): 32 bytes per point - y little endian, the sign of x in the top bit -
+// and 64 per signature - the packed R8, then S little endian.  bjj_unpack: 1 y not below r, 4 no point has this y, 3 x == 0 with the sign bit
+// set, 0 otherwise; a rejected record gives O.  eddsa_poseidon_verify_packed: 1 range, 4 a point has no x, 3 a non-canonical sign, 6, 0
+inline std::vector<uint8_t> bjj_pack(const std::vector<Fr> &p) {
+    if (p.size() % 2) throw std::invalid_argument("bjj_pack: a point is two Fr");
+    std::vector<uint8_t> out(16 * p.size());
+    check(bn254_bjj_pack_batch(nullptr, reinterpret_cast<const bn_fr *>(p.data()), out.data(), p.size() / 2));
+    return out;
+}
+inline std::pair<std::vector<Fr>, std::vector<int32_t>> bjj_unpack(const std::vector<uint8_t> &in32) {
+    if (in32.size() % 32) throw std::invalid_argument("bjj_unpack: a record is 32 bytes");
+    std::vector<Fr> out(in32.size() / 16);
+    std::vector<int32_t> status(in32.size() / 32);
+    check(bn254_bjj_unpack_batch(nullptr, in32.data(), reinterpret_cast<bn_fr *>(out.data()), status.data(), status.size()));
+    return {out, status};
+}
+inline std::vector<int32_t> eddsa_poseidon_verify_packed(const std::vector<uint8_t> &a32, const std::vector<uint8_t> &sig64, const std::vector<Fr> &msg) {
+    if (a32.size() != 32 * msg.size() || sig64.size() != 64 * msg.size()) throw std::invalid_argument("eddsa_poseidon_verify_packed: length mismatch");
+    std::vector<int32_t> status(msg.size());
+    check(bn254_eddsa_poseidon_verify_packed_batch(nullptr, a32.data(), sig64.data(), reinterpret_cast<const bn_fr *>(msg.data()), status.data(), msg.size()));
     return status;
 }
 // out[i] = (a[i] == b[i]) as group elements, whatever their Jacobian representations (groups/mod.rs:83-109): nothing is normalized

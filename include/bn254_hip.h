@@ -35,8 +35,9 @@
  *   bn254_fr_inverse_batch out[i] = a[i].inverse(): Option<Fr> as ok[i] = 1, or 0 with Fr::zero()   lib.rs:25, fields/fp.rs:107-115
  *   bn254_fr_pow_batch     out[i] = a[i].pow(e[i])                                       lib.rs:23, fields/mod.rs:35-46
  *   bn254_fr_interpret_batch  out[i] = Fr::interpret(&in[64 i .. 64 i + 64])             lib.rs:27-29, fields/fp.rs:72-74, arith.rs:90-97
- *   bn254_fr_add_batch_dev / bn254_fr_mul_batch_dev / bn254_fr_inverse_batch_dev / bn254_fr_pow_batch_dev / bn254_fr_interpret_batch_dev
- *                          the same five on device-resident arrays, asynchronous on the caller's stream
+ *   bn254_fr_sqrt_batch    out[i] = the square root of a[i] that is not above (r - 1) / 2: Option<Fr> as ok[i] = 1, or 0 with Fr::zero()   no counterpart in the reference
+ *   bn254_fr_add_batch_dev / bn254_fr_mul_batch_dev / bn254_fr_inverse_batch_dev / bn254_fr_pow_batch_dev / bn254_fr_interpret_batch_dev /
+ *   bn254_fr_sqrt_batch_dev  the same six on device-resident arrays, asynchronous on the caller's stream
  *   bn254_fr_ntt_batch     out[t n + k] = sum_j in[t n + j] s^j w_n^(j k), or the inverse map: the polynomial <-> its evaluations over the subgroup of
  *                          order n = 2^log_n (on the coset s H); no counterpart in the reference - the convention is ark-bn254's root of unity
  *   bn254_fr_ntt_batch_dev the same on device-resident arrays, asynchronous on the caller's stream; bn254_fr_root_of_unity  w_n, on the host
@@ -85,6 +86,11 @@
  *                          msg);  bn254_eddsa_poseidon_verify_batch  circomlib's verifyPoseidon per row; none has a counterpart in the reference
  *   bn254_bjj_validate_batch_dev / bn254_bjj_add_batch_dev / bn254_bjj_mul_batch_dev / bn254_eddsa_poseidon_challenge_batch_dev /
  *   bn254_eddsa_poseidon_verify_batch_dev  the same five on device-resident records, asynchronous on the caller's stream
+ *   bn254_bjj_pack_batch / bn254_bjj_unpack_batch  Baby Jubjub points to and from circomlib's 32-byte records (y, and the sign of x in the top bit);
+ *                          bn254_eddsa_poseidon_verify_packed_batch  verifyPoseidon on a packed key and a packed 64-byte signature; none has a
+ *                          counterpart in the reference
+ *   bn254_bjj_pack_batch_dev / bn254_bjj_unpack_batch_dev / bn254_eddsa_poseidon_verify_packed_batch_dev  the same three on device-resident
+ *                          records, asynchronous on the caller's stream
  *   bn254_g2_precompute    coeffs[i][0..102) = q[i].to_affine().precompute().coeffs   groups/mod.rs:557-588 (Q != infinity)
  *   bn254_pairing_prepared_batch  out[i] = final_exponentiation(prepared.miller_loop(p[i]))   groups/mod.rs:486-519,768
  *   bn254_gt_mul_batch     out[i] = a[i] * b[i]                                     lib.rs:175-179, fields/fq12.rs:295-307
@@ -136,6 +142,8 @@
      bn254_g1_validate_batch and bn254_g2_validate_batch serialise on the context in the same way (its mutex for the whole call).
      bn254_bjj_validate_batch, bn254_bjj_add_batch, bn254_bjj_mul_batch, bn254_eddsa_poseidon_challenge_batch and bn254_eddsa_poseidon_verify_batch
      serialise on the context in the same way (its mutex for the whole call).
+     bn254_fr_sqrt_batch, bn254_bjj_pack_batch, bn254_bjj_unpack_batch and bn254_eddsa_poseidon_verify_packed_batch serialise on the context in
+     the same way (its mutex for the whole call).
  *     bn254_pairing_product_batch_prepared_native serialises on the context like them; its handle is immutable and shared freely.
  *     Use one context per thread (or bn254_multi_*) for more overlap;
  *     bn254_ctx_set_option is atomic, but set options before concurrent use: a call in flight may run some
@@ -196,6 +204,9 @@
      bn254_eddsa_poseidon_verify_batch_dev use no scratch and no host operand either: one launch per sub-launch does all of a record's work - the
      verifier hashes, runs its joint chain and compares in one lane (each lane's window table is its own private memory).  None of the five waits
      on anything or reads anything back, so any number of threads may issue them on one context, each on its own stream and buffers.
+     bn254_fr_sqrt_batch_dev, bn254_bjj_pack_batch_dev, bn254_bjj_unpack_batch_dev and bn254_eddsa_poseidon_verify_packed_batch_dev are of the same
+     kind: no scratch, no host operand, one launch per sub-launch (the packed verifier unpacks its two points in the lane that verifies), nothing
+     waited on or read back, so any number of threads may issue them on one context, each on its own stream and buffers.
  */
 #ifndef BN254_HIP_H
 #define BN254_HIP_H
@@ -486,6 +497,11 @@ int bn254_fr_mul_batch(bn254_ctx *ctx, const bn_fr *a, const bn_fr *b, bn_fr *ou
 int bn254_fr_inverse_batch(bn254_ctx *ctx, const bn_fr *a, bn_fr *out, int32_t *ok, size_t n);
 int bn254_fr_pow_batch(bn254_ctx *ctx, const bn_fr *a, const bn_fr *e, bn_fr *out, size_t n);
 int bn254_fr_interpret_batch(bn254_ctx *ctx, const uint8_t *in, bn_fr *out, size_t n);
+/* Option<Fr> square roots: ok[i] = 1 and out[i] the root of a[i] whose canonical integer is not above (r - 1) / 2, or ok[i] = 0 and
+   out[i] = Fr::zero() for a non-residue; 0 has the root 0.  ok may be NULL and out may be a, as for bn254_fr_inverse_batch.  r - 1 = 2^28 t:
+   one exponentiation by (t - 1) / 2 and a correction by a power of a fixed element of order 2^28, found digit by digit; every lane runs the
+   same instruction stream whatever its element holds.  Elements are taken as canonical Montgomery images like everywhere in this family. */
+int bn254_fr_sqrt_batch(bn254_ctx *ctx, const bn_fr *a, bn_fr *out, int32_t *ok, size_t n);
 /* Number-theoretic transforms over Fr: `count` transforms of n = 2^log_n elements each (log_n 0 .. BN254_NTT_LOG_MAX), transform t in
    records [t n, (t + 1) n), natural order in and out - what moves a polynomial between its coefficients and its evaluations over the
    subgroup H of order n of Fr*, plain and on a coset: the quotient (a b - c) / Z_H of a Groth16 prover, the inverse transform in front of
@@ -933,6 +949,34 @@ int bn254_bjj_add_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, vo
 int bn254_bjj_mul_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, void *d_out, size_t n, void *stream);
 int bn254_eddsa_poseidon_challenge_batch_dev(bn254_ctx *ctx, const void *d_a, const void *d_r8, const void *d_msg, void *d_out, size_t n, void *stream);
 int bn254_eddsa_poseidon_verify_batch_dev(bn254_ctx *ctx, const void *d_a, const void *d_r8, const void *d_s, const void *d_msg, void *d_status, size_t n, void *stream);
+/* Packed points and signatures, the form keys and signatures travel in (circomlib's packPoint / packSignature).  A packed point is 32 bytes:
+   the canonical integer of y, little endian, with bit 7 of byte 31 set iff the canonical integer of x is above (r - 1) / 2.  A packed
+   signature is 64 bytes: the packed R8, then the integer S as 32 little-endian bytes (its top bit is no flag).
+   bn254_bjj_pack_batch: out32[32 i ..] = the record of p[i].  No validation: words not below r give unspecified bytes, never a fault.
+   bn254_bjj_unpack_batch: out[i] and status[i] for the record in32[32 i ..], any 32 bytes, checked in this order:
+     1   the integer of y (the sign bit cleared) is not below r
+     4   x^2 = (1 - y^2) / (a - d y^2) is not a square: no point has this y
+     3   x == 0 and the sign bit is set: a non-canonical encoding of (0, 1) or (0, -1)
+     0   otherwise: out[i] is the point with this y whose x has this sign
+   A rejected record gives O = (0, 1).  There is NO subgroup check, as there is none in circomlib: bn254_bjj_validate_batch is there for that.
+   One square root of a ratio per record and no inversion (bn254_fr_sqrt_batch's).
+   bn254_eddsa_poseidon_verify_packed_batch: bn254_eddsa_poseidon_verify_batch on the packed key a32[32 i ..] and the packed signature
+   sig64[64 i ..], msg as there; status[i], checked in this order, every row on its own:
+     1   a y is not below r, the integer S is not below l, or the words of msg are not below r
+     4   a point has no x
+     3   a non-canonical sign, in either point
+     6   [S]B8 != R8 + [8 hm]A
+     0   valid
+   One launch: a lane unpacks its two points and runs the hash and the joint chain of the unpacked verifier.
+   All three: a NULL pointer with work to do or n > 2^40 is BN254_E_BAD_ARG before any device is touched; n == 0 succeeds; sub-launches of at
+   most 2^22 records.  The _dev forms take device pointers (16-byte aligned; d_status int32_t per record), enqueue on `stream`, use no host
+   round trip and read nothing back.  Threading: see above. */
+int bn254_bjj_pack_batch(bn254_ctx *ctx, const bn_fr *p, uint8_t *out32, size_t n);
+int bn254_bjj_unpack_batch(bn254_ctx *ctx, const uint8_t *in32, bn_fr *out, int32_t *status, size_t n);
+int bn254_eddsa_poseidon_verify_packed_batch(bn254_ctx *ctx, const uint8_t *a32, const uint8_t *sig64, const bn_fr *msg, int32_t *status, size_t n);
+int bn254_bjj_pack_batch_dev(bn254_ctx *ctx, const void *d_p, void *d_out32, size_t n, void *stream);
+int bn254_bjj_unpack_batch_dev(bn254_ctx *ctx, const void *d_in32, void *d_out, void *d_status, size_t n, void *stream);
+int bn254_eddsa_poseidon_verify_packed_batch_dev(bn254_ctx *ctx, const void *d_a32, const void *d_sig64, const void *d_msg, void *d_status, size_t n, void *stream);
 
 /* ---- device-resident entry points (inputs/outputs already in HBM; `stream` is a hipStream_t or NULL) ------------------ */
 /* Same layouts (array of structs) in device memory.  Asynchronous on `stream`; the caller synchronises. */
@@ -999,6 +1043,7 @@ int bn254_fr_mul_batch_dev(bn254_ctx *ctx, const void *d_a, const void *d_b, voi
 int bn254_fr_inverse_batch_dev(bn254_ctx *ctx, const void *d_a, void *d_out, void *d_ok, size_t n, void *stream);
 int bn254_fr_pow_batch_dev(bn254_ctx *ctx, const void *d_a, const void *d_e, void *d_out, size_t n, void *stream);
 int bn254_fr_interpret_batch_dev(bn254_ctx *ctx, const void *d_in, void *d_out, size_t n, void *stream);
+int bn254_fr_sqrt_batch_dev(bn254_ctx *ctx, const void *d_a, void *d_out, void *d_ok, size_t n, void *stream);
 /* bn254_fr_ntt_batch on device-resident arrays (count 2^log_n records of 32 bytes, 16-byte aligned), asynchronous on `stream`; d_out may
    be exactly d_in; `shift` is HOST memory (one element or NULL), read before the call returns.  Tables and the arrays between the passes
    are context-owned scratch (see Threading). */
@@ -1067,6 +1112,7 @@ int bn254_profile_reset(bn254_ctx *ctx);
    of bn254_g2_map_to_curve_batch, bn254_g2_clear_cofactor_batch, bn254_g2_hash_to_curve_uniform_batch and bn254_g2_hash_to_curve_batch: "g2_map_to_curve", "g2_clear_cofactor", "g2_hash_to_curve", "g2_hash_to_curve_msg" (one scope per sub-launch);
    of bn254_g1_validate_batch and bn254_g2_validate_batch: "g1_validate", "g2_validate" (one scope per sub-launch);
    of bn254_bjj_{validate,add,mul}_batch and bn254_eddsa_poseidon_{challenge,verify}_batch: "bjj_validate", "bjj_add", "bjj_mul", "eddsa_poseidon_challenge", "eddsa_poseidon_verify" (one scope per sub-launch);
+   of bn254_fr_sqrt_batch, bn254_bjj_{pack,unpack}_batch and bn254_eddsa_poseidon_verify_packed_batch: "fr_sqrt", "bjj_pack", "bjj_unpack", "eddsa_poseidon_verify_packed" (one scope per sub-launch);
    and, of bn254_fr_ntt_batch: "ntt" (the passes), "ntt_table" (the builds of the twiddle tables).
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);
