@@ -149,6 +149,8 @@ extern "C" {
     fn bn254_fr_poseidon_batch(ctx: *mut c_void, input: *const Fr, arity: c_int, out: *mut Fr, n: usize) -> c_int;
     fn bn254_fr_poseidon_permute_batch(ctx: *mut c_void, input: *const Fr, t: c_int, out: *mut Fr, n: usize) -> c_int;
     fn bn254_fr_merkle_tree(ctx: *mut c_void, leaves: *const Fr, log_n: c_int, nodes: *mut Fr) -> c_int;
+    fn bn254_fr_poseidon_ex_batch(ctx: *mut c_void, input: *const Fr, n_inputs: c_int, init: *const Fr, n_outs: c_int, out: *mut Fr, n: usize) -> c_int;
+    fn bn254_fr_poseidon_chain_batch(ctx: *mut c_void, input: *const Fr, offsets: *const usize, m: usize, rate: c_int, out: *mut Fr) -> c_int;
     fn bn254_fr_add_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_out: *mut c_void, n: usize, negate_b: c_int, stream: *mut c_void) -> c_int;
     fn bn254_fr_mul_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_inverse_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_out: *mut c_void, d_ok: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
@@ -166,6 +168,8 @@ extern "C" {
     fn bn254_fr_poseidon_batch_dev(ctx: *mut c_void, d_in: *const c_void, arity: c_int, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_poseidon_permute_batch_dev(ctx: *mut c_void, d_in: *const c_void, t: c_int, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_merkle_tree_dev(ctx: *mut c_void, d_leaves: *const c_void, log_n: c_int, d_nodes: *mut c_void, stream: *mut c_void) -> c_int;
+    fn bn254_fr_poseidon_ex_batch_dev(ctx: *mut c_void, d_in: *const c_void, n_inputs: c_int, d_init: *const c_void, n_outs: c_int, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_fr_poseidon_chain_batch_dev(ctx: *mut c_void, d_in: *const c_void, offsets: *const usize, m: usize, rate: c_int, d_out: *mut c_void, stream: *mut c_void) -> c_int;
 }
 
 /// One line-function coefficient of a prepared G2 point: the crate's `EllCoeffs { ell_0, ell_vw, ell_vv: Fq2 }` (src/groups/mod.rs:472-476) as the
@@ -525,6 +529,26 @@ pub fn fr_merkle_tree(leaves: &[Fr]) -> Result<Vec<Fr>, GpuError> {
     let mut nodes = vec![Fr::zero(); leaves.len() - 1];
     check(unsafe { bn254_fr_merkle_tree(std::ptr::null_mut(), leaves.as_ptr(), leaves.len().trailing_zeros() as c_int, nodes.as_mut_ptr()) })?;
     Ok(nodes)
+}
+
+/// circomlib's `PoseidonEx(n_inputs, n_outs)` on `input.len() / n_inputs` rows of 1 to 16 inputs: the first `n_outs` elements of the permutation of
+/// `[init[i], row..]` at width `n_inputs + 1` (`init`: `None` for zeros, else one element per row), `n_outs` consecutive outputs per row.
+pub fn fr_poseidon_ex(input: &[Fr], n_inputs: usize, init: Option<&[Fr]>, n_outs: usize) -> Result<Vec<Fr>, GpuError> {
+    assert!((1..=16).contains(&n_inputs) && input.len() % n_inputs == 0 && (1..=n_inputs + 1).contains(&n_outs));
+    let n = input.len() / n_inputs;
+    assert!(init.map_or(true, |i| i.len() == n));
+    let mut out = vec![Fr::zero(); n * n_outs];
+    check(unsafe { bn254_fr_poseidon_ex_batch(std::ptr::null_mut(), input.as_ptr(), n_inputs as c_int, init.map_or(std::ptr::null(), |i| i.as_ptr()), n_outs as c_int, out.as_mut_ptr(), n) })?;
+    Ok(out)
+}
+
+/// One digest per variable-length record `input[offsets[j]..offsets[j + 1]]`: `c = len`, then per block of `rate` elements (the last padded with
+/// zeros, an empty record is one block of zeros) `c = permute([c, block..])[0]` at width `rate + 1`.  The framing is this library's own.
+pub fn fr_poseidon_chain(input: &[Fr], offsets: &[usize], rate: usize) -> Result<Vec<Fr>, GpuError> {
+    assert!((1..=16).contains(&rate) && !offsets.is_empty() && offsets[0] == 0 && *offsets.last().unwrap() == input.len());
+    let mut out = vec![Fr::zero(); offsets.len() - 1];
+    check(unsafe { bn254_fr_poseidon_chain_batch(std::ptr::null_mut(), input.as_ptr(), offsets.as_ptr(), out.len(), rate as c_int, out.as_mut_ptr()) })?;
+    Ok(out)
 }
 
 /// `out[i] = a[i] * b[i]` (src/lib.rs:175-179)

@@ -665,6 +665,36 @@ def fr_poseidon_permute_batch(states, engine=None):
     return [[Fr.from_limbs(r) for r in st] for st in (engine or default_engine()).fr_poseidon_permute_batch(x)]
 
 
+def fr_poseidon_ex_batch(inputs, init=None, n_outs=1, engine=None):
+    """[PoseidonEx(*row)] -> list of lists of n_outs Fr: circomlib's PoseidonEx(n_inputs, n_outs), the first n_outs elements of the permutation
+    of [init_i, *row] at width n_inputs + 1; several GPU lanes share one permutation.  inputs: rows of 1 .. 16 Fr each, all of one length, or
+    an (n, n_inputs, 4) uint64 array; init: None (zeros), one Fr for every row, or a sequence of one Fr per row; 1 <= n_outs <= n_inputs + 1.
+    fr_poseidon_ex_batch(rows)[i][0] is fr_poseidon_batch(rows)[i] for 1 .. 4 inputs.  ValueError for another shape."""
+    from .engine import _poseidon_ex_args
+    if isinstance(init, Fr):
+        init = [init]
+    x, init = _poseidon_ex_args(_poseidon_rows(inputs), None if init is None else _scalar_array(init), n_outs, "inputs")
+    return [[Fr.from_limbs(r) for r in row] for row in (engine or default_engine()).fr_poseidon_ex_batch(x, init, n_outs)]
+
+
+def fr_poseidon_chain_batch(records, rate=16, engine=None):
+    """[hash_chain(record)] -> list of Fr, one digest per record of any length (bn_amd.poseidon.hash_chain_host): c = len(record); the record is cut
+    into max(1, ceil(len / rate)) blocks of `rate` Fr, the last padded with zeros; per block c = permute([c, *block])[0] at width rate + 1.  The
+    framing is this package's own - not an additive sponge, not another library's format.  records: a list of sequences of Fr of any lengths,
+    or a pair (flat, offsets) of a sequence of Fr (or an (n, 4) uint64 array) and m + 1 CSR offsets.  ValueError for rate outside 1 .. 16."""
+    from .engine import _poseidon_chain_args
+    if isinstance(records, tuple) and len(records) == 2:
+        flat, offsets = _scalar_array(records[0]), records[1]
+    else:
+        rows = [_scalar_array(r) for r in records]
+        offsets = np.concatenate([[0], np.cumsum([r.shape[0] for r in rows])]).astype(np.uint64)
+        flat = np.concatenate(rows) if rows else np.zeros((0, 4), np.uint64)
+    x, o = _poseidon_chain_args(flat, offsets, rate)
+    if o.size == 1:
+        return []
+    return [Fr.from_limbs(r) for r in (engine or default_engine()).fr_poseidon_chain_batch(x, o, rate)]
+
+
 def fr_merkle_tree(leaves, engine=None):
     """the n - 1 inner nodes of the binary Poseidon tree over n = 2^k leaves -> list of Fr, level by level: the n / 2 parents of the leaves
     first, the root last; parent i of a level is hash(child[2 i], child[2 i + 1]).  One call, one launch per level.  leaves: a sequence of Fr

@@ -361,6 +361,7 @@ void bn254_ctx_destroy(bn254_ctx *c) {
         for (auto &sl : bc.slot) sl.table.release();
         bc.scal.release();
     }
+    for (auto &b : c->psd_wide_tbl) b.release();
     c->base_stage.release(); c->base_stage_host.release();
     if (c->base_stage_ev) hipEventDestroy(c->base_stage_ev);
     for (auto &b : c->stage) b.release();

@@ -132,6 +132,9 @@ struct bn254_ctx {
     BnBuf dot_ws;                       // bn254_fr_dot_batch: the partial sums of the segments longer than one piece (32 bytes each; its work list travels through seg_plan)
     BnBuf scan_ws;                      // bn254_fr_scan_batch: per scratch slot of its plan a map (A, B) and a carry, three arrays of 32-byte records (its work list travels through seg_plan)
     BnBuf mle_ws;                       // bn254_fr_sumcheck_round: the partial sums of the round kernel's lanes and of the sum levels, [t][lane] per level (32 bytes each)
+    BnBuf psd_wide_tbl[16];             // bn254_fr_poseidon_ex_batch / _chain_batch: the constants of width t = 2 .. 17 ([t - 2]; poseidon_wide_table.hpp), derived and
+    bool psd_wide_ready[16] = {};       // ... uploaded with a blocking copy at the first use of the width, under psd_wide_mu; read-only afterwards
+    std::mutex psd_wide_mu;             // (its own mutex: the host-buffer forms hold `mu` while they call their _dev twins)
     BnBuf base_stage;                   // the base of a table build on the device ...
     BnBuf base_stage_host{nullptr, 0, true};    // ... and its pinned staging, rewritten only after base_stage_ev (its last copy) completed
     hipEvent_t base_stage_ev = nullptr;

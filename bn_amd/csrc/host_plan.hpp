@@ -619,3 +619,28 @@ inline std::vector<BnMerkleLevel> bn_merkle_plan(int log_n, size_t step) {
     }
     return levels;
 }
+
+// ---- the wide Poseidon calls (bn254_fr_poseidon_ex_batch, bn254_fr_poseidon_chain_batch): the argument checks.  The ranges of n_inputs, n_outs and
+// rate are answered even for an empty call; with work to do, pointers and sizes follow.
+inline int bn_poseidon_ex_range(int n_inputs, int n_outs) {
+    return (n_inputs < 1 || n_inputs > BN254_POSEIDON_EX_INPUTS_MAX || n_outs < 1 || n_outs > n_inputs + 1) ? BN254_E_BAD_ARG : BN254_OK;
+}
+// n > 0 rows: `init` may be NULL; host_buffers: `out` (n * n_outs records) must overlap neither `in` (n * n_inputs) nor `init` (n)
+inline int bn_poseidon_ex_check(const void *in, int n_inputs, const void *init, int n_outs, const void *out, size_t n, bool host_buffers) {
+    const int rc = bn_poseidon_ex_range(n_inputs, n_outs); if (rc) return rc;
+    if (!in || !out || n > BN_N_MAX / (size_t)(n_inputs + 1)) return BN254_E_BAD_ARG;
+    if (!host_buffers) return BN254_OK;
+    const size_t rec = 32, out_bytes = n * (size_t)n_outs * rec;
+    if (bn_ranges_overlap(in, n * (size_t)n_inputs * rec, out, out_bytes) || (init && bn_ranges_overlap(init, n * rec, out, out_bytes))) return BN254_E_BAD_ARG;
+    return BN254_OK;
+}
+// m > 0 records: CSR offsets in host memory (m + 1 entries from 0, non-decreasing), at most 2^40 records and 2^40 elements
+inline int bn_poseidon_chain_check(const void *in, const size_t *offsets, size_t m, int rate, const void *out, bool host_buffers) {
+    if (rate < 1 || rate > BN254_POSEIDON_EX_INPUTS_MAX) return BN254_E_BAD_ARG;
+    if (!offsets || !out || m > BN_N_MAX || offsets[0] != 0) return BN254_E_BAD_ARG;
+    for (size_t j = 0; j < m; ++j)
+        if (offsets[j + 1] < offsets[j]) return BN254_E_BAD_ARG;
+    const size_t n = offsets[m];
+    if (n > BN_N_MAX || (n && !in)) return BN254_E_BAD_ARG;
+    return (host_buffers && n && bn_ranges_overlap(in, n * 32, out, m * 32)) ? BN254_E_BAD_ARG : BN254_OK;
+}

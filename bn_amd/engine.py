@@ -159,6 +159,36 @@ def _merkle_args(leaves):
     return x, n.bit_length() - 1
 
 
+POSEIDON_EX_INPUTS_MAX = 16                                 # BN254_POSEIDON_EX_INPUTS_MAX of include/bn254_hip.h
+
+
+def _poseidon_ex_args(x, init, n_outs, name="x"):
+    """the operands of fr_poseidon_ex_batch, checked the way the C ABI checks them: (x as (n, n_inputs, 4), init as (n, 4) or None)"""
+    x = _poseidon_args(x, name, 1, POSEIDON_EX_INPUTS_MAX, "n_inputs")
+    if not 1 <= n_outs <= x.shape[1] + 1:
+        raise ValueError(f"n_outs = {n_outs}: 1..{x.shape[1] + 1} for {x.shape[1]} inputs per row")
+    if init is not None:
+        init = np.ascontiguousarray(init, dtype=np.uint64).reshape(-1, 4)
+        if init.shape[0] == 1 and x.shape[0] != 1:                 # one initial state for every row
+            init = np.ascontiguousarray(np.broadcast_to(init, (x.shape[0], 4)))
+        if init.shape[0] != x.shape[0]:
+            raise ValueError(f"init holds {init.shape[0]} records but x has {x.shape[0]} rows")
+    return x, init
+
+
+def _poseidon_chain_args(x, offsets, rate):
+    """the operands of fr_poseidon_chain_batch: (x as (n, 4), offsets as size_t words)"""
+    if not 1 <= rate <= POSEIDON_EX_INPUTS_MAX:
+        raise ValueError(f"rate = {rate}: 1..{POSEIDON_EX_INPUTS_MAX} are supported")
+    x = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4)
+    o = _offsets(offsets)
+    if int(o[0]) != 0 or (o.size > 1 and bool((o[1:] < o[:-1]).any())):
+        raise ValueError("offsets must start at 0 and never decrease")
+    if int(o[-1]) != x.shape[0]:
+        raise ValueError(f"x holds {x.shape[0]} records but offsets[m] = {int(o[-1])}")
+    return x, o
+
+
 def _fr_point(v, name):
     """one field element (anything with .limbs, or four uint64 words) as a C-contiguous array of 4 words"""
     v = np.ascontiguousarray(getattr(v, "limbs", v), dtype=np.uint64).reshape(-1)
@@ -565,6 +595,24 @@ class Engine:
         x, log_n = _merkle_args(leaves)
         out = np.empty((x.shape[0] - 1, 4), np.uint64)
         _native.check(self._lib.bn254_fr_merkle_tree(self._h, _p(x), log_n, _p(out) if log_n else None))
+        return out
+
+    def fr_poseidon_ex_batch(self, x, init=None, n_outs=1):
+        """circomlib's PoseidonEx per row -> (n, n_outs, 4) uint64: out[i, j] = permute([init[i] or 0, x[i, 0], .., x[i, n_inputs - 1]])[j].
+        x: (n, n_inputs, 4), n_inputs 1 .. 16; init: None, (n, 4), or one record for every row; 1 <= n_outs <= n_inputs + 1
+        (include/bn254_hip.h bn254_fr_poseidon_ex_batch)"""
+        x, init = _poseidon_ex_args(x, init, n_outs)
+        out = np.empty((x.shape[0], n_outs, 4), np.uint64)
+        _native.check(self._lib.bn254_fr_poseidon_ex_batch(self._h, _p(x), x.shape[1], _p(init) if init is not None else None, n_outs, _p(out), x.shape[0]))
+        return out
+
+    def fr_poseidon_chain_batch(self, x, offsets, rate=16):
+        """one digest per variable-length record -> (m, 4) uint64: record j is x[offsets[j]:offsets[j + 1]]; c = len, then per block of `rate`
+        elements (the last padded with zeros, an empty record is one block of zeros) c = permute([c, block..])[0].  This framing is this
+        library's own (include/bn254_hip.h bn254_fr_poseidon_chain_batch)"""
+        x, o = _poseidon_chain_args(x, offsets, rate)
+        out = np.empty((o.size - 1, 4), np.uint64)
+        _native.check(self._lib.bn254_fr_poseidon_chain_batch(self._h, _p(x) if x.shape[0] else None, _p(o), o.size - 1, rate, _p(out) if o.size > 1 else None))
         return out
 
     def g1_msm_batch(self, p, k, offsets):
@@ -1127,6 +1175,17 @@ class Engine:
         """device pointers leaves (2^log_n records of 32 bytes) and nodes (2^log_n - 1 records, level by level, the root last; must not overlap
         leaves), ordered on `stream`: one launch per level"""
         _native.check(self._lib.bn254_fr_merkle_tree_dev(self._h, d_leaves, log_n, d_nodes, stream))
+
+    def fr_poseidon_ex_batch_dev(self, d_in, n_inputs, d_init, n_outs, d_out, n, stream=0):
+        """device pointers in (n * n_inputs records of 32 bytes, row-major), init (n records, or None / 0 for zeros) and out (n * n_outs records;
+        must overlap no input), ordered on `stream`.  The first call of a width on the engine blocks while its constants go to the device"""
+        _native.check(self._lib.bn254_fr_poseidon_ex_batch_dev(self._h, d_in, n_inputs, d_init or None, n_outs, d_out, n, stream))
+
+    def fr_poseidon_chain_batch_dev(self, d_in, offsets, rate, d_out, stream=0):
+        """device pointers in (offsets[m] records of 32 bytes) and out (m records; must not overlap in), ordered on `stream`; `offsets` is a HOST
+        array of m + 1 entries, read before the call returns"""
+        o = _offsets(offsets)                                      # held here until the call has returned
+        _native.check(self._lib.bn254_fr_poseidon_chain_batch_dev(self._h, d_in, _p(o), o.size - 1, rate, d_out, stream))
 
     def g1_mul_base_batch_dev(self, base, d_k, d_out, n, stream=0):
         """`base` is a HOST point (12 uint64 words), read before the call returns; d_k, d_out device pointers (n records), ordered on `stream`"""

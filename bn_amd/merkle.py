@@ -3,7 +3,8 @@ circomlib / iden3 hash of arity 2 (bn_amd.poseidon).
 
 Tree(leaves) builds every node with ONE bn_amd.fr_merkle_tree call (one launch per level); open(i) reads a path out of the nodes, which stay
 on the host as integers; verify walks one path in host integers (bn_amd.poseidon.hash_host: no device); verify_batch checks m openings of one
-depth with ONE fr_poseidon_batch of m hashes per level - left and right are chosen by the index bit on the host.
+depth with ONE fr_poseidon_batch of m hashes per level - left and right are chosen by the index bit on the host.  Tree.from_records hashes
+variable-length records into the leaves with ONE bn_amd.fr_poseidon_chain_batch call first.
 
 Not built: trees of arity 4, a several-lanes-per-hash kernel for the top levels (a level of one node is one lane's chain of about 830 dependent
 products), sparse trees, updates in place."""
@@ -22,6 +23,15 @@ class Tree:
         x, self.depth = _merkle_args(_scalar_array(leaves))
         self.leaves = [Fr.from_limbs(r) for r in x]
         self.nodes = [Fr.from_limbs(r) for r in (engine or default_engine()).fr_merkle_tree(x)]
+
+    @classmethod
+    def from_records(cls, rows, rate=16, engine=None):
+        """the tree whose leaf i is the digest of the variable-length record rows[i] (bn_amd.poseidon.hash_chain_host: this package's own
+        framing): ONE fr_poseidon_chain_batch call for the leaves, then the tree as above.  rows: a power of two of sequences of Fr, of any
+        lengths"""
+        from .api import fr_poseidon_chain_batch
+        e = engine or default_engine()
+        return cls(fr_poseidon_chain_batch(rows, rate=rate, engine=e), engine=e)
 
     @property
     def root(self):

@@ -307,6 +307,26 @@ inline std::vector<Fr> fr_merkle_tree(const std::vector<Fr> &leaves) {
     check(bn254_fr_merkle_tree(nullptr, reinterpret_cast<const bn_fr *>(leaves.data()), log_n, reinterpret_cast<bn_fr *>(nodes.data())));
     return nodes;
 }
+// circomlib's PoseidonEx(n_inputs, n_outs) on in.size() / n_inputs rows of 1 .. 16 inputs: the first n_outs elements of the permutation of
+// [init[i], row..] at width n_inputs + 1 (init: nullptr for zeros, else one element per row), n_outs consecutive outputs per row
+inline std::vector<Fr> fr_poseidon_ex(const std::vector<Fr> &in, int n_inputs, const std::vector<Fr> *init = nullptr, int n_outs = 1) {
+    if (n_inputs < 1 || n_inputs > BN254_POSEIDON_EX_INPUTS_MAX || n_outs < 1 || n_outs > n_inputs + 1 || in.size() % size_t(n_inputs) ||
+        (init && init->size() != in.size() / size_t(n_inputs)))
+        throw std::invalid_argument("fr_poseidon_ex: n_inputs, n_outs, init and the inputs disagree");
+    const size_t n = in.size() / size_t(n_inputs);
+    std::vector<Fr> out(n * size_t(n_outs));
+    check(bn254_fr_poseidon_ex_batch(nullptr, reinterpret_cast<const bn_fr *>(in.data()), n_inputs, init ? reinterpret_cast<const bn_fr *>(init->data()) : nullptr, n_outs,
+                                     reinterpret_cast<bn_fr *>(out.data()), n));
+    return out;
+}
+// one digest per variable-length record in[offsets[j] .. offsets[j + 1]): c = len, then per block of `rate` elements (the last padded with zeros, an
+// empty record is one block of zeros) c = permute([c, block..])[0] at width rate + 1.  The framing is this library's own.
+inline std::vector<Fr> fr_poseidon_chain(const std::vector<Fr> &in, const std::vector<size_t> &offsets, int rate = 16) {
+    if (rate < 1 || rate > BN254_POSEIDON_EX_INPUTS_MAX || offsets.empty() || offsets.back() != in.size()) throw std::invalid_argument("fr_poseidon_chain: rate, offsets and the inputs disagree");
+    std::vector<Fr> out(offsets.size() - 1);
+    check(bn254_fr_poseidon_chain_batch(nullptr, reinterpret_cast<const bn_fr *>(in.data()), offsets.data(), out.size(), rate, reinterpret_cast<bn_fr *>(out.data())));
+    return out;
+}
 // Compressed encodings: x and one sign bit, 32 bytes per G1 and 64 per G2 point, in the layout `format` (BN254_COMPRESSED_ARK or
 // BN254_COMPRESSED_GNARK: laid out as ark-serialize / gnark-crypto describe; not checked against those libraries here).  compress takes any
 // Jacobian form and writes canonical bytes; decompress returns (x, y, 1) and one status per record (0 ok, 3 flags, 1 range, 4 no such point,

@@ -61,6 +61,10 @@
  *                          bn254_fr_poseidon_permute_batch  the permutation itself on n states of t records;  bn254_fr_merkle_tree  every node of the binary
  *                          tree of hash(left, right) over 2^log_n leaves; none has a counterpart in the reference
  *   bn254_fr_poseidon_batch_dev / bn254_fr_poseidon_permute_batch_dev / bn254_fr_merkle_tree_dev  the same three on device-resident records, asynchronous on the caller's stream
+ *   bn254_fr_poseidon_ex_batch  circomlib's PoseidonEx(n_inputs, n_outs) with an initialState for 1 .. 16 inputs (t = 2 .. 17): the first n_outs elements
+ *                          of permute([init, x_1 .. x_n]);  bn254_fr_poseidon_chain_batch  one digest per variable-length record (CSR offsets), PoseidonEx(rate, 1)
+ *                          chained through its initialState under this project's own framing; neither has a counterpart in the reference
+ *   bn254_fr_poseidon_ex_batch_dev / bn254_fr_poseidon_chain_batch_dev  the same two on device-resident records, asynchronous on the caller's stream
  *   bn254_g{1,2}_compress_batch / bn254_g{1,2}_decompress_batch  points <-> x and one sign bit (32 / 64 bytes) in the byte layouts ark-serialize and gnark-crypto
  *                          describe; decompression recovers y by a square root on the device and checks curve and subgroup; no counterpart in the reference
  *   bn254_g{1,2}_compress_batch_dev / bn254_g{1,2}_decompress_batch_dev  the same four on device-resident records, asynchronous on the caller's stream
@@ -134,6 +138,7 @@
      bn254_fr_sumcheck_fold_round serialises on the context in the same way (its mutex for the whole call).
      bn254_fr_mle_quotients serialises on the context in the same way (its mutex for the whole call).
      bn254_fr_poseidon_batch, bn254_fr_poseidon_permute_batch and bn254_fr_merkle_tree serialise on the context in the same way (its mutex for the whole call).
+     bn254_fr_poseidon_ex_batch and bn254_fr_poseidon_chain_batch serialise on the context in the same way (its mutex for the whole call).
      bn254_g{1,2}_compress_batch and bn254_g{1,2}_decompress_batch serialise on the context in the same way (its mutex for the whole call).
      bn254_g1_map_to_curve_batch, bn254_g1_hash_to_curve_uniform_batch and bn254_g1_hash_to_curve_batch serialise on the context in the same way (its
      mutex for the whole call).
@@ -187,6 +192,12 @@
      bn254_fr_poseidon_batch_dev, bn254_fr_poseidon_permute_batch_dev and bn254_fr_merkle_tree_dev use no scratch and no host operand: the levels of a
      tree are launches in stream order that read what the level before wrote into the caller's `nodes`.  None of the three waits on anything
      or reads anything back, so any number of threads may issue them on one context, each on its own stream and buffers.
+     bn254_fr_poseidon_ex_batch_dev and bn254_fr_poseidon_chain_batch_dev read the constants of their width from a context-owned table that is derived on
+     the host and uploaded with a BLOCKING copy at the first use of the width on the context, under a mutex of its own, and never written again:
+     a launch enqueued after that call returned - on any stream, by any thread - finds it in place.  That first call of a width therefore blocks
+     for the derivation and the copy (milliseconds); every later call waits on nothing.  bn254_fr_poseidon_ex_batch_dev uses no scratch and no host
+     operand.  bn254_fr_poseidon_chain_batch_dev reads its HOST `offsets` before it returns and uploads them through the work-list staging the
+     segmented calls share, under the same event ordering, so it serialises with them across streams.  Neither reads anything back.
      bn254_g{1,2}_compress_batch_dev and bn254_g{1,2}_decompress_batch_dev use no scratch and no host operand either, wait on nothing and read
      nothing back (d_status stays on the device): any number of threads may issue them on one context, each on its own stream and buffers.
      bn254_g1_map_to_curve_batch_dev, bn254_g1_hash_to_curve_uniform_batch_dev and bn254_g1_hash_to_curve_batch_dev use no scratch either: one launch
@@ -714,6 +725,48 @@ int bn254_fr_mle_quotients(bn254_ctx *ctx, const bn_fr *a, int nv, const bn_fr *
 int bn254_fr_poseidon_batch(bn254_ctx *ctx, const bn_fr *in, int arity, bn_fr *out, size_t n);
 int bn254_fr_poseidon_permute_batch(bn254_ctx *ctx, const bn_fr *in, int t, bn_fr *out, size_t n);
 int bn254_fr_merkle_tree(bn254_ctx *ctx, const bn_fr *leaves, int log_n, bn_fr *nodes);
+/* Wide Poseidon over Fr: the same circomlib instance at every width circomlib's poseidon.circom and circomlibjs define, 1 .. 16 inputs, t = 2 .. 17
+   - what iden3 claims, wide record leaves and circuit witness generators call.  R_F = 8; R_P for t = 2 .. 17 is 56, 57, 56, 60, 60, 63, 64, 63, 60, 66,
+   60, 65, 70, 60, 64, 68; round constants and the Cauchy matrix from the Grain LFSR exactly as above (bn_amd/csrc/poseidon_wide_table.hpp restates the
+   derivation of bn_amd/poseidon.py on the host: the 12 638 constants are derived per width at its first use, not shipped).  Known answers,
+   permute([0, 1, .., n])[0]: n = 6 gives 20400040500897583745843009878988256314335038853985262692600694741116813247201 and n = 16 gives
+   9989051620750914585850546081941653841776809718687451684622678807385399211877 - the values circomlibjs publishes in its own tests, the external anchor
+   of the R_P list and the wide matrix; n = 1 and n = 2 are the answers pinned above; the rows for every other n in tests/poseidon_wide_cases.py are
+   this project's own output, regression anchors and not external vectors.  Inputs are canonical Montgomery images; outputs are canonical, hence
+   the bytes are those of the integer model.
+   bn254_fr_poseidon_ex_batch: circomlib's PoseidonEx(n_inputs, n_outs).  `in` holds n * n_inputs records, row-major; the state of row i is
+   [init ? init[i] : 0, in[i * n_inputs], .., in[i * n_inputs + n_inputs - 1]] (t = n_inputs + 1; `init` may be NULL), and out[i * n_outs + j] =
+   permute(state)[j] for j < n_outs, 1 <= n_outs <= t.  With init NULL and n_outs 1 this is bn254_fr_poseidon_batch where that is defined.  `out`
+   must not overlap `in` or `init`.
+   bn254_fr_poseidon_chain_batch: m variable-length records as CSR `offsets` (m + 1 entries, offsets[0] == 0, non-decreasing, HOST memory as for
+   bn254_fr_dot_batch); record j is in[offsets[j] .. offsets[j + 1]).  For a record of L elements: c = Fr(L); the record is cut into
+   max(1, ceil(L / rate)) blocks of `rate` elements, the last padded with zeros (an empty record is one block of zeros); for each block in order
+   c = permute([c, block..])[0] at width rate + 1; out[j] = c.  That is PoseidonEx(rate, 1) chained through its initialState, the way circom code
+   hashes long inputs, with the length in the first capacity element.  THIS FRAMING IS THIS PROJECT'S OWN DEFINITION: it is not an additive sponge
+   and it is not a format of any other library.  rate = 1 .. 16.  `out` must not overlap `in`.
+   How: BN254_POSEIDON_WIDE_LANES lanes (shipped: see below; 4 / 8 / 16 build) share one permutation and never straddle a wave.  Lane g owns the state
+   elements g, g + G, ..; the state lives in LDS; a round is add + S-box + publish on the owned elements, then the lane's rows of M s, each row
+   ceil(t / 5) product-sums of at most five pairs (fr.hpp fr_dot) joined by additions - every partial result canonical, so the bytes depend neither
+   on G nor on the cut.  t is a run-time argument: one kernel per call kind, not per width.  Constants and matrix rows are vector loads from
+   the width's device table (a matrix is at most 9 KB and stays in cache; an LDS copy would need a workgroup barrier and the LDS of more
+   resident waves).  The phases are ordered with wave-scope means only - no workgroup barrier, no workgroup waits for another, no atomics, no
+   scratch: the groups of a wave run different numbers of blocks in the chain call and leave when their record ends.  Sub-launches of at most
+   2^22 lanes.
+   Measured on an MI355X (tools/time_poseidon_wide.py, kernel ms, medians of 5; profiles/r27_poseidon_wide.txt): the lanes per
+   permutation were chosen by a rule fixed before measuring - the smallest median of five interleaved runs of bn254_fr_poseidon_ex_batch_dev on 2^16
+   rows of 16 inputs, equal bytes asserted: 4 / 8 / 16 lanes take 16.5068 / 15.4797 / 20.4012 ms, so 8 ship.  2^20 rows of 2 / 4 / 8 / 16 inputs take
+   29.4410 / 35.9782 / 88.5153 / 231.2080 ms - 1.84 / 0.93 / 0.75 / 0.53 x bn254_fr_mul_batch_dev on as many products, and 4.11 / 2.37 x
+   bn254_fr_poseidon_batch_dev at 2 / 4 inputs (one lane per hash); ONE row takes 0.4445 / 0.5298 / 1.2953 / 3.4050 ms (one lane: 0.8449 / 1.7638 ms at 2 / 4
+   inputs).  The chain on 2^16 records of 1 .. 40 elements at rate 16 takes 37.7600 ms.  132 / 140 VGPRs, no spill, 17 408 B of LDS per workgroup.  The
+   small calls and the top of a tree are NOT rerouted onto these kernels.
+   n == 0 and m == 0 return BN254_OK and write nothing.
+   Errors (BN254_E_BAD_ARG, checked before any device is touched): n_inputs or rate outside 1 .. BN254_POSEIDON_EX_INPUTS_MAX; n_outs outside
+   1 .. n_inputs + 1; a NULL pointer with work to do (`init` may be NULL); offsets[0] != 0 or offsets decreasing; n * t or the number of elements
+   above 2^40; `out` overlapping an input (host-buffer forms).  Threading: see above - the host-buffer entry points hold the context's mutex for
+   the whole call. */
+#define BN254_POSEIDON_EX_INPUTS_MAX 16
+int bn254_fr_poseidon_ex_batch(bn254_ctx *ctx, const bn_fr *in, int n_inputs, const bn_fr *init, int n_outs, bn_fr *out, size_t n);
+int bn254_fr_poseidon_chain_batch(bn254_ctx *ctx, const bn_fr *in, const size_t *offsets, size_t m, int rate, bn_fr *out);
 
 /* ---- one node, several GPUs (north_star: independent batches shard across the GPUs; ONE exchange for the multi-pairing) --- */
 /* `devices[0..ndev)`: HIP device index of every rank (NULL = 0..ndev-1).  One context and one host thread per rank.  A device may
@@ -1083,6 +1136,13 @@ int bn254_fr_mle_quotients_dev(bn254_ctx *ctx, const void *d_a, int nv, const bn
 int bn254_fr_poseidon_batch_dev(bn254_ctx *ctx, const void *d_in, int arity, void *d_out, size_t n, void *stream);
 int bn254_fr_poseidon_permute_batch_dev(bn254_ctx *ctx, const void *d_in, int t, void *d_out, size_t n, void *stream);
 int bn254_fr_merkle_tree_dev(bn254_ctx *ctx, const void *d_leaves, int log_n, void *d_nodes, void *stream);
+/* bn254_fr_poseidon_ex_batch / bn254_fr_poseidon_chain_batch on device-resident records of 32 bytes, 16-byte aligned, asynchronous on `stream`: d_in
+   (n * n_inputs records), d_init (n, or NULL) and d_out (n * n_outs); d_in (offsets[m] records) and d_out (m).  d_out must overlap no input (not
+   checked).  `offsets` (m + 1 entries) is HOST memory, read before the call returns, and may be freed then.  The first call of a width on a
+   context blocks while the width's constants are derived and copied to the device (see Threading); otherwise neither waits for anything or
+   reads anything back. */
+int bn254_fr_poseidon_ex_batch_dev(bn254_ctx *ctx, const void *d_in, int n_inputs, const void *d_init, int n_outs, void *d_out, size_t n, void *stream);
+int bn254_fr_poseidon_chain_batch_dev(bn254_ctx *ctx, const void *d_in, const size_t *offsets, size_t m, int rate, void *d_out, void *stream);
 /* raw Jacobian result of the reference's MSB-first double-and-add (what G::random produces, groups/mod.rs:220-222):
    used to generate benchmark inputs with z != 1 on the device */
 int bn254_g1_mul_jacobian_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, void *d_out, size_t n, void *stream);
@@ -1107,6 +1167,7 @@ int bn254_profile_reset(bn254_ctx *ctx);
    of bn254_fr_mle_quotients: "fr_mle_quotients" (one scope per pass, or per sub-launch of it);
    of bn254_fr_sumcheck_fold_round: "fr_sumcheck_fold_round" (the lanes over the indices; the levels over its partial sums run under the round's scope for them);
    of bn254_fr_poseidon_batch, bn254_fr_poseidon_permute_batch and bn254_fr_merkle_tree: "fr_poseidon", "fr_poseidon_permute", "fr_merkle_level" (one scope per level, or per sub-launch of it);
+   of bn254_fr_poseidon_ex_batch and bn254_fr_poseidon_chain_batch: "fr_poseidon_ex", "fr_poseidon_chain" (one scope per sub-launch);
    of bn254_g{1,2}_compress_batch and bn254_g{1,2}_decompress_batch: "g1_compress", "g2_compress", "g1_decompress", "g2_decompress" (one scope per sub-launch);
    of bn254_g1_map_to_curve_batch, bn254_g1_hash_to_curve_uniform_batch and bn254_g1_hash_to_curve_batch: "g1_map_to_curve", "g1_hash_to_curve", "g1_hash_to_curve_msg" (one scope per sub-launch);
    of bn254_g2_map_to_curve_batch, bn254_g2_clear_cofactor_batch, bn254_g2_hash_to_curve_uniform_batch and bn254_g2_hash_to_curve_batch: "g2_map_to_curve", "g2_clear_cofactor", "g2_hash_to_curve", "g2_hash_to_curve_msg" (one scope per sub-launch);
