@@ -158,6 +158,10 @@ extern "C" {
     fn bn254_fr_interpret_batch_dev(ctx: *mut c_void, d_in: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_sqrt_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_out: *mut c_void, d_ok: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_fr_ntt_batch_dev(ctx: *mut c_void, d_in: *const c_void, d_out: *mut c_void, log_n: c_int, count: usize, inverse: c_int, shift: *const Fr, stream: *mut c_void) -> c_int;
+    fn bn254_g1_ntt_batch(ctx: *mut c_void, input: *const G1, out: *mut G1, log_n: c_int, count: usize, inverse: c_int, shift: *const Fr) -> c_int;
+    fn bn254_g2_ntt_batch(ctx: *mut c_void, input: *const G2, out: *mut G2, log_n: c_int, count: usize, inverse: c_int, shift: *const Fr) -> c_int;
+    fn bn254_g1_ntt_batch_dev(ctx: *mut c_void, d_in: *const c_void, d_out: *mut c_void, log_n: c_int, count: usize, inverse: c_int, shift: *const Fr, stream: *mut c_void) -> c_int;
+    fn bn254_g2_ntt_batch_dev(ctx: *mut c_void, d_in: *const c_void, d_out: *mut c_void, log_n: c_int, count: usize, inverse: c_int, shift: *const Fr, stream: *mut c_void) -> c_int;
     fn bn254_fr_dot_batch_dev(ctx: *mut c_void, d_coeff: *const c_void, d_index: *const c_void, d_x: *const c_void, nx: usize, offsets: *const usize, m: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn bn254_fr_scan_batch_dev(ctx: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_init: *const c_void, offsets: *const usize, m: usize, flags: c_int, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn bn254_fr_mle_eq_dev(ctx: *mut c_void, d_z: *const c_void, nv: c_int, d_out: *mut c_void, stream: *mut c_void) -> c_int;
@@ -410,6 +414,25 @@ pub fn fr_ntt(values: &[Fr], log_n: u32, inverse: bool, shift: Option<&Fr>) -> R
     let mut out = vec![Fr::zero(); values.len()];
     let sh = shift.map_or(std::ptr::null(), |s| s as *const Fr);
     check(unsafe { bn254_fr_ntt_batch(std::ptr::null_mut(), values.as_ptr(), out.as_mut_ptr(), log_n as c_int, values.len() >> log_n, inverse as c_int, sh) })?;
+    Ok(out)
+}
+
+/// The same transforms with points for data and scalar multiplication for the product: `points.len() / 2^log_n` transforms of `2^log_n`
+/// points each, natural order in and out, every output normalised.  The inverse transform of the powers `tau^i G` of a reference string
+/// gives its Lagrange points.
+pub fn g1_ntt(points: &[G1], log_n: u32, inverse: bool, shift: Option<&Fr>) -> Result<Vec<G1>, GpuError> {
+    assert!(log_n <= 22 && points.len() % (1usize << log_n) == 0);
+    let mut out = vec![G1::zero(); points.len()];
+    let sh = shift.map_or(std::ptr::null(), |s| s as *const Fr);
+    check(unsafe { bn254_g1_ntt_batch(std::ptr::null_mut(), points.as_ptr(), out.as_mut_ptr(), log_n as c_int, points.len() >> log_n, inverse as c_int, sh) })?;
+    Ok(out)
+}
+
+pub fn g2_ntt(points: &[G2], log_n: u32, inverse: bool, shift: Option<&Fr>) -> Result<Vec<G2>, GpuError> {
+    assert!(log_n <= 22 && points.len() % (1usize << log_n) == 0);
+    let mut out = vec![G2::zero(); points.len()];
+    let sh = shift.map_or(std::ptr::null(), |s| s as *const Fr);
+    check(unsafe { bn254_g2_ntt_batch(std::ptr::null_mut(), points.as_ptr(), out.as_mut_ptr(), log_n as c_int, points.len() >> log_n, inverse as c_int, sh) })?;
     Ok(out)
 }
 

@@ -7,7 +7,7 @@ import subprocess
 
 HERE = pathlib.Path(__file__).resolve().parent
 LIB_PATH = pathlib.Path(os.environ.get("BN254_LIB_PATH", HERE / "libbn254_hip.so"))     # override: kernel experiments only
-SOURCES = [HERE / "csrc" / f for f in ("bn254_hip.hip", "bn254_seg.hip", "bn254_wire.hip", "bn254_kernels_b.hip", "bn254_kernels_mul.hip", "bn254_kernels_w.hip", "bn254_kernels_q.hip", "bn254_multi.hip", "bn254_measure.hip", "bn254_fr.hip", "bn254_fr_sqrt.hip", "bn254_ntt.hip", "bn254_dot.hip", "bn254_scan.hip", "bn254_mle.hip", "bn254_poseidon.hip", "bn254_poseidon_wide.hip", "bn254_hash.hip", "bn254_hash_g2.hip", "bn254_validate.hip", "bn254_babyjub.hip")]
+SOURCES = [HERE / "csrc" / f for f in ("bn254_hip.hip", "bn254_seg.hip", "bn254_wire.hip", "bn254_kernels_b.hip", "bn254_kernels_mul.hip", "bn254_kernels_w.hip", "bn254_kernels_q.hip", "bn254_multi.hip", "bn254_measure.hip", "bn254_fr.hip", "bn254_fr_sqrt.hip", "bn254_ntt.hip", "bn254_group_ntt.hip", "bn254_dot.hip", "bn254_scan.hip", "bn254_mle.hip", "bn254_poseidon.hip", "bn254_poseidon_wide.hip", "bn254_hash.hip", "bn254_hash_g2.hip", "bn254_validate.hip", "bn254_babyjub.hip")]
 OBJ_DIR = HERE / "csrc" / "build"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # EVERY unit is compiled with LLVM's DPP combiner off: with it on, the quad_perm move of a neighbour lane's limb is folded into the
@@ -74,6 +74,10 @@ SIGNATURES = {   # name -> argtypes  (every function returns int unless noted)
     "bn254_fr_root_of_unity": [C.c_int, _VP],
     "bn254_fr_ntt_batch": [_VP, _VP, _VP, C.c_int, _SZ, C.c_int, _VP],
     "bn254_fr_ntt_batch_dev": [_VP, _VP, _VP, C.c_int, _SZ, C.c_int, _VP, _VP],
+    "bn254_g1_ntt_batch": [_VP, _VP, _VP, C.c_int, _SZ, C.c_int, _VP],
+    "bn254_g2_ntt_batch": [_VP, _VP, _VP, C.c_int, _SZ, C.c_int, _VP],
+    "bn254_g1_ntt_batch_dev": [_VP, _VP, _VP, C.c_int, _SZ, C.c_int, _VP, _VP],
+    "bn254_g2_ntt_batch_dev": [_VP, _VP, _VP, C.c_int, _SZ, C.c_int, _VP, _VP],
     "bn254_fr_dot_batch": [_VP, _VP, _VP, _VP, _SZ, _VP, _SZ, _VP],
     "bn254_fr_dot_batch_dev": [_VP, _VP, _VP, _VP, _SZ, _VP, _SZ, _VP, _VP],
     "bn254_fr_scan_batch": [_VP, _VP, _VP, _VP, _VP, _SZ, C.c_int, _VP],

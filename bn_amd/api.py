@@ -745,6 +745,50 @@ def fr_ntt(values, inverse=False, shift=None, engine=None):
     return fr_ntt_batch(A.reshape(1, -1, 4), inverse, shift, engine)[0]
 
 
+def _group_ntt_batch(cls, method, points, log_n, inverse, shift, engine):
+    A = _point_array(cls, points)
+    if not 0 <= log_n <= 22:
+        raise ValueError(f"log_n must be 0..22, got {log_n}")
+    if A.shape[0] % (1 << log_n):
+        raise ValueError(f"{A.shape[0]} points are not whole transforms of 2^{log_n}")
+    sh = _shift_limbs(shift)
+    if A.shape[0] == 0:
+        return []
+    return [cls(r) for r in getattr(engine or default_engine(), method)(A, log_n, inverse, sh)]
+
+
+def _group_ntt_log(n):
+    if n < 1 or n & (n - 1):
+        raise ValueError(f"the length of a transform must be a power of two, got {n}")
+    return n.bit_length() - 1
+
+
+def g1_ntt_batch(points, log_n, inverse=False, shift=None, engine=None):
+    """len(points) / 2^log_n transforms over G1 in ONE call, transform t in points [t n, (t + 1) n): see g1_ntt.  points: a sequence of G1 or
+    an (N, 12) uint64 array; N a multiple of n = 2^log_n, else ValueError."""
+    return _group_ntt_batch(G1, "g1_ntt_batch", points, log_n, inverse, shift, engine)
+
+
+def g2_ntt_batch(points, log_n, inverse=False, shift=None, engine=None):
+    """the same over G2: a sequence of G2 or an (N, 24) uint64 array"""
+    return _group_ntt_batch(G2, "g2_ntt_batch", points, log_n, inverse, shift, engine)
+
+
+def g1_ntt(points, inverse=False, shift=None, engine=None):
+    """The transform of fr_ntt with G1 points for data (n = 2^log_n of them, else ValueError) and scalar multiplication for the product,
+    natural order in and out -> list of normalised G1.  Forward: out[k] = sum_j [shift^j w^(j k)] points[j] with w = Fr.root_of_unity(log_n);
+    inverse: out[j] = [n^-1 shift^-j] sum_k [w^(-j k)] points[k].  The inverse transform of the powers tau^i G of a reference string gives
+    its Lagrange points (bn_amd.kzg.lagrange_srs).  shift: an Fr or an integer, None for 1."""
+    A = _point_array(G1, points)
+    return g1_ntt_batch(A, _group_ntt_log(A.shape[0]), inverse, shift, engine)
+
+
+def g2_ntt(points, inverse=False, shift=None, engine=None):
+    """the same over G2"""
+    A = _point_array(G2, points)
+    return g2_ntt_batch(A, _group_ntt_log(A.shape[0]), inverse, shift, engine)
+
+
 def _bjj_points(points):
     from . import babyjub
     return babyjub._point_array(points)

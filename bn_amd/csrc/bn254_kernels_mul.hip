@@ -35,6 +35,7 @@ __device__ __forceinline__ void bn_g1_tail_policy(int step, int total) {
 }
 #define BN_G1_HOOK(step, total) bn_g1_tail_policy(step, total)
 #include "group_ops.hpp"       // the per-lane bodies of everything below but the chains of curve.hpp: shared with the host simulation
+#include "group_ntt_ops.hpp"   // ... and those of the transforms over G1 / G2
 #include "lane_launch.hpp"     // the shell and the launchers of the integer kernels
 
 using namespace bn254;
@@ -285,6 +286,23 @@ __global__ void __launch_bounds__(BLOCK) bn254_g2_add_M(Args g, uint32_t n) {
     if (pair < n) msm_point_op<G2F>(g, pair);
 }
 
+// ---- the transforms over G1 / G2 (bn254_g{1,2}_ntt_batch, group_ntt_ops.hpp): lane (G2: lane pair) i < n of a launch is butterfly lo + i of a
+// stage, or point lo + i of a shift / inverse pass - further instances of the generic point kernels bn254_g{1,2}_add_M<Args> below (a lane
+// pair past n retires as a whole).  What runs a chain keeps its window table in the launch's scratch like the term kernels
+// (`table`: bn254_mul_table_bytes_M(g, n) bytes, one table per lane); the hand-over hooks of the chains are those of this unit.
+template <class F> __device__ __forceinline__ AffTableMem<F> group_ntt_table(uint4 *table, uint32_t i) {
+    const uint32_t lane = std::is_same<F, G1F>::value ? i : 2u * i + (threadIdx.x & 1u);
+    return {table + (size_t)lane * AFF_LANE_U4};
+}
+template <class F> __device__ __forceinline__ void msm_point_op(const GroupNttStageArgs &g, uint32_t i) { group_ntt_stage0_body<F>(g, i, PointIo<F>()); }
+template <class F> __device__ __forceinline__ void msm_point_op(const GroupNttChainArgs &g, uint32_t i) {
+    AffTableMem<F> tab = group_ntt_table<F>(g.table, i);
+    group_ntt_stage_body<F>(g.st, i, tab, PointIo<F>());
+}
+template <class F> __device__ __forceinline__ void msm_point_op(const GroupNttPassArgs &g, uint32_t i) {
+    AffTableMem<F> tab = group_ntt_table<F>(g.table, i);
+    group_ntt_scale_body<F>(g.sc, i, tab, PointIo<F>());
+}
 // Every launch of a group kernel: one lane per G1 element, one lane pair per G2 element, BLOCK lanes per workgroup
 unsigned group_grid(int g, size_t n) { return (unsigned)(((g == 1 ? n : 2 * n) + BLOCK - 1) / BLOCK); }
 template <class... A>
@@ -364,6 +382,22 @@ int bn254_launch_normalize_M(int g, const void *d_p, void *d_out, size_t n, void
 int bn254_launch_eq_M(int g, const void *d_a, const void *d_b, void *d_out, size_t n, hipStream_t s) {
     const EqArgs a = {(const uint32_t *)d_a, (const uint32_t *)d_b, (int32_t *)d_out};
     return launch_group(g, n, s, bn254_g1_add_M<EqArgs>, bn254_g2_add_M<EqArgs>, a, (uint32_t)n);
+}
+// bn254_g{1,2}_ntt_batch.  A stage: butterflies [lo, lo + n) of stage `stage` of transforms of 2^log_n points laid back to back from d_src, written
+// to d_dst (another array); wtbl: the root table pair of bn254_fr_ntt_batch; `table` (stage > 0): bn254_mul_table_bytes_M(g, n) bytes
+int bn254_launch_group_ntt_stage_M(int g, const void *d_src, void *d_dst, const void *wtbl, unsigned log_n, unsigned stage, int inverse, size_t lo, size_t n, void *table, hipStream_t s) {
+    const GroupNttStageArgs a = {(const uint32_t *)d_src, (uint32_t *)d_dst, (const uint32_t *)wtbl, log_n, stage, inverse ? 1u : 0u, (uint32_t)lo};
+    if (stage == 0) return launch_group(g, n, s, bn254_g1_add_M<GroupNttStageArgs>, bn254_g2_add_M<GroupNttStageArgs>, a, (uint32_t)n);
+    const GroupNttChainArgs c = {a, (uint4 *)table};
+    return launch_group(g, n, s, bn254_g1_add_M<GroupNttChainArgs>, bn254_g2_add_M<GroupNttChainArgs>, c, (uint32_t)n);
+}
+// a pass: d_dst[j] = [c_j] d_src[j] (Jacobian; d_dst may be d_src) for the points j in [lo, lo + n): c_j = the shift table pair's power for
+// j mod 2^log_n (scale == NULL), or the one Montgomery image at `scale`
+int bn254_launch_group_ntt_scale_M(int g, const void *d_src, void *d_dst, const void *stbl, unsigned log_n, const uint64_t *scale, size_t lo, size_t n, void *table, hipStream_t s) {
+    GroupNttScaleArgs a = {(const uint32_t *)d_src, (uint32_t *)d_dst, (const uint32_t *)stbl, log_n, scale ? 0u : 1u, (uint32_t)lo, {}};
+    for (int i = 0; scale && i < 4; ++i) { a.scale.w[2 * i] = (uint32_t)scale[i]; a.scale.w[2 * i + 1] = (uint32_t)(scale[i] >> 32); }
+    const GroupNttPassArgs c = {a, (uint4 *)table};
+    return launch_group(g, n, s, bn254_g1_add_M<GroupNttPassArgs>, bn254_g2_add_M<GroupNttPassArgs>, c, (uint32_t)n);
 }
 int bn254_launch_mul_base_repack_M(int g, const void *d_pts, void *table, size_t n, hipStream_t s) {
     const uint32_t comps = g == 1 ? 1u : 2u;

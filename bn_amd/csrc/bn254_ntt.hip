@@ -117,6 +117,9 @@ int ntt_check(const void *in, const void *out, int log_n, size_t count, const bn
 }
 }  // namespace
 
+// the tables for bn254_group_ntt.hip (host_ctx.hpp): the same pairs under the same keys, so the two families share them
+int bn_ntt_tables(bn254_ctx *c, int log_n, int inverse, const bn_fr *shift, hipStream_t s) { return ntt_tables(c, log_n, inverse, shift, s); }
+
 extern "C" {
 
 int bn254_fr_root_of_unity(int log_n, bn_fr *out) { return bn_fr_root(log_n, out); }

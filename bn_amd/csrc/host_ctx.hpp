@@ -129,6 +129,7 @@ struct bn254_ctx {
     uint64_t ntt_shift_key[5] = {};     // ... and the powers of the coset shift the second pair was built for (forward: the shift; inverse: shift and size)
     bool ntt_shift_valid = false;
     BnBuf ntt_ws;                       // the arrays between the passes of one group of transforms (one, or two for an odd number of passes in place)
+    BnBuf gntt_ws;                      // bn254_g{1,2}_ntt_batch: the array of Jacobian points between the stages of one group of transforms
     BnBuf dot_ws;                       // bn254_fr_dot_batch: the partial sums of the segments longer than one piece (32 bytes each; its work list travels through seg_plan)
     BnBuf scan_ws;                      // bn254_fr_scan_batch: per scratch slot of its plan a map (A, B) and a carry, three arrays of 32-byte records (its work list travels through seg_plan)
     BnBuf mle_ws;                       // bn254_fr_sumcheck_round: the partial sums of the round kernel's lanes and of the sum levels, [t][lane] per level (32 bytes each)
@@ -267,6 +268,10 @@ int bn_dev_entry(bn254_ctx *&ctx, void *stream, bool scratch, Fn fn) {
 // copy completed - so the caller's host arrays may be freed as soon as the call returns.  Scratch guard held by the caller (bn254_hip.hip;
 // hidden: the library's list of dynamic symbols stays what it was).
 __attribute__((visibility("hidden"))) int bn_plan_upload(bn254_ctx *c, const void *a, size_t a_bytes, const void *b, size_t b_bytes, hipStream_t s);
+// The twiddle tables of bn254_fr_ntt_batch for the transforms over G1 / G2 (bn254_ntt.hip; hidden like bn_plan_upload): builds the root pair
+// on first use and, for a shift, the shift pair when its key changed.  ctx->ntt_tbl holds the root pair, then the shift pair, of
+// 2 * 2^12 records each (ntt_ops.hpp).  Scratch guard held by the caller.
+__attribute__((visibility("hidden"))) int bn_ntt_tables(bn254_ctx *c, int log_n, int inverse, const bn_fr *shift, hipStream_t s);
 // Prologue of the host-buffer entry points that lock the context: looks the context up, holds its mutex for the whole call - concurrent
 // callers of one context (in particular of the default context behind ctx == NULL) are serialised, never interleaved on the staging
 // memory -, makes its device current.  `BnHost h(ctx); if (h.rc) return h.rc;`
@@ -371,6 +376,8 @@ unsigned bn254_normalize_run_M(void);
 size_t bn254_normalize_prefix_bytes_M(int g, size_t n);
 int bn254_launch_normalize_M(int g, const void *d_p, void *d_out, size_t n, void *prefix, hipStream_t s);
 int bn254_launch_eq_M(int g, const void *d_a, const void *d_b, void *d_out, size_t n, hipStream_t s);
+int bn254_launch_group_ntt_stage_M(int g, const void *d_src, void *d_dst, const void *wtbl, unsigned log_n, unsigned stage, int inverse, size_t lo, size_t n, void *table, hipStream_t s);
+int bn254_launch_group_ntt_scale_M(int g, const void *d_src, void *d_dst, const void *stbl, unsigned log_n, const uint64_t *scale, size_t lo, size_t n, void *table, hipStream_t s);
 // bn254_measure.hip
 int bn254_launch_gather_K(const void *d_records, size_t records, size_t record_bytes, const void *d_index, size_t n, void *d_out, hipStream_t s);
 }

@@ -363,6 +363,63 @@ int bn_ntt_group(const BnNttRun &r, unsigned log_n, unsigned T, size_t cnt, size
     return BN254_OK;
 }
 
+// ---- transforms over G1 / G2 (bn254_g{1,2}_ntt_batch): the argument check and the steps of a call
+// in the order of ntt_check (the empty call is answered before): range of log_n, pointers, size, a zero shift
+inline int bn_group_ntt_check(const void *in, const void *out, int log_n, size_t count, const bn_fr *shift) {
+    if (log_n < 0 || log_n > BN254_GROUP_NTT_LOG_MAX || !in || !out) return BN254_E_BAD_ARG;
+    if (count > (BN_N_MAX >> log_n)) return BN254_E_BAD_ARG;
+    if (shift && bn_fr_is_zero(shift->l)) return BN254_E_BAD_ARG;
+    return BN254_OK;
+}
+// A call runs in groups of whole transforms of at most `cap` points (a larger transform is a group of its own).  The steps of a group, each
+// over all of its transforms:
+//   SCALE      (forward with a shift, first)  point j times s^j, IN -> OUT: lane-local, so OUT may be IN
+//   STAGE i    i < log_n, group_ntt_ops.hpp: reads one array and writes ANOTHER - the first one writes WS, then OUT and WS alternate
+//   SCALE      (inverse, after the last stage) point j times n^-1 s^-j, or every point times n^-1: in place, wherever the last stage wrote
+//   NORMALIZE  from there to OUT (in place when that is OUT)
+// IN is never written and OUT only once IN has been read completely, so OUT may be IN; one workspace array of `most` Jacobian points serves
+// every call with log_n >= 1.  At log_n == 0 every factor is one: the call is the normalisation.  A step is cut into sub-launches of at
+// most `cap` units - butterflies for a stage, points otherwise -, and what runs chains (every step but stage 0 and the normalisation) of at
+// most `chain_cap` besides: a lane's window table is scratch of the launch.
+enum BnGroupNttKind { BN_GNTT_SCALE, BN_GNTT_STAGE, BN_GNTT_NORMALIZE };
+struct BnGroupNttRun {
+    unsigned stages;                    // log_n
+    bool pre, post;                     // the two passes
+    size_t per_group;                   // transforms per group
+    size_t most;                        // points of the largest group: the size of the workspace array
+    unsigned ws_bufs;                   // 0 or 1
+};
+inline BnGroupNttRun bn_group_ntt_run(unsigned log_n, size_t count, size_t cap, bool shift, bool inverse) {
+    BnGroupNttRun r;
+    r.stages = log_n;
+    r.pre = log_n > 0 && shift && !inverse;
+    r.post = log_n > 0 && inverse;
+    r.per_group = std::max<size_t>(1, cap >> log_n);
+    r.most = std::min(count, r.per_group) << log_n;
+    r.ws_bufs = log_n ? 1u : 0u;
+    return r;
+}
+// one sub-launch: units [lo, lo + n) of the step, counted from the group's first transform
+struct BnGroupNttStep { BnGroupNttKind kind; unsigned stage; BnNttBuf src, dst; bool chain; size_t lo, n; };
+// the sub-launches of one group of `cnt` transforms, in order: fn(step) enqueues one
+template <class Fn>
+int bn_group_ntt_group(const BnGroupNttRun &r, unsigned log_n, size_t cnt, size_t cap, size_t chain_cap, Fn fn) {
+    const size_t points = cnt << log_n, chain_step = std::min(cap, chain_cap);
+    BnNttBuf cur = BN_NTT_IN;
+    auto step = [&](BnGroupNttKind kind, unsigned stage, BnNttBuf dst, bool chain, size_t units) -> int {
+        BnGroupNttStep s = {kind, stage, cur, dst, chain, 0, 0};
+        const int rc = bn_for_parts(units, chain ? chain_step : cap, [&](size_t lo, size_t n) -> int { s.lo = lo; s.n = n; return fn(s); });
+        cur = dst;
+        return rc;
+    };
+    int rc;
+    if (r.pre && (rc = step(BN_GNTT_SCALE, 0, BN_NTT_OUT, true, points))) return rc;
+    for (unsigned i = 0; i < r.stages; ++i)
+        if ((rc = step(BN_GNTT_STAGE, i, cur == BN_NTT_WS0 ? BN_NTT_OUT : BN_NTT_WS0, i != 0, points / 2))) return rc;
+    if (r.post && (rc = step(BN_GNTT_SCALE, 0, cur, true, points))) return rc;
+    return step(BN_GNTT_NORMALIZE, 0, BN_NTT_OUT, false, points);
+}
+
 // ---- sparse linear maps over Fr (bn254_fr_dot_batch): the argument checks and the work list
 // CSR offsets, sizes and pointers as for the other segmented calls; without an index the terms meet x one to one, so nx must be n
 inline int bn_dot_check(const void *coeff, bool has_index, const void *x, size_t nx, const size_t *offsets, size_t m, const void *out) {

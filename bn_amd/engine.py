@@ -61,6 +61,15 @@ def _ntt_count(rows, log_n):
     return rows >> log_n
 
 
+def _group_ntt_count(rows, log_n):
+    """transforms over G1 / G2 in an array of `rows` points"""
+    if not 0 <= log_n <= 22:
+        raise ValueError(f"log_n must be 0..22, got {log_n}")
+    if rows % (1 << log_n):
+        raise ValueError(f"{rows} points are not whole transforms of 2^{log_n}")
+    return rows >> log_n
+
+
 def _ntt_shift(shift):
     """the coset shift as one C-contiguous scalar of 4 uint64 words, or None (NULL).  The CALLER keeps the returned array alive for the length
     of the C call and takes its address there: a converted copy (a list, another dtype, a strided view) belongs to nobody else"""
@@ -502,6 +511,24 @@ class Engine:
         shift = _ntt_shift(shift)                                  # held here until the call has returned
         _native.check(self._lib.bn254_fr_ntt_batch(self._h, _p(a), _p(out), log_n, count, 1 if inverse else 0, None if shift is None else _p(shift)))
         return out
+
+    def _group_ntt(self, fn, p, words, log_n, inverse, shift):
+        p = _arr(p, words) if len(p) else np.zeros((0, words), np.uint64)
+        count = _group_ntt_count(p.shape[0], log_n)
+        out = np.empty_like(p)
+        shift = _ntt_shift(shift)                                  # held here until the call has returned
+        _native.check(fn(self._h, _p(p), _p(out), log_n, count, 1 if inverse else 0, None if shift is None else _p(shift)))
+        return out
+
+    def g1_ntt_batch(self, p, log_n, inverse=False, shift=None):
+        """len(p) / 2^log_n transforms of 2^log_n G1 points each, natural order in and out -> (len(p), 12) uint64, normalised.  Forward:
+        out[k] = sum_j [shift^j w^(j k)] p[j]; inverse: out[j] = [n^-1 shift^-j] sum_k [w^(-j k)] p[k].  shift: ONE scalar (4 uint64 words,
+        non-zero) or None for 1 (include/bn254_hip.h bn254_g1_ntt_batch)"""
+        return self._group_ntt(self._lib.bn254_g1_ntt_batch, p, G1_WORDS, log_n, inverse, shift)
+
+    def g2_ntt_batch(self, p, log_n, inverse=False, shift=None):
+        """the same over G2 -> (len(p), 24) uint64"""
+        return self._group_ntt(self._lib.bn254_g2_ntt_batch, p, G2_WORDS, log_n, inverse, shift)
 
     def fr_dot_batch(self, coeff, x, offsets, index=None):
         """out[j] = sum of coeff[t] * x[index[t]] over t in [offsets[j], offsets[j+1]) -> (m, 4) uint64: a sparse matrix in CSR form times the
@@ -1101,6 +1128,17 @@ class Engine:
         words) or None, read before the call returns"""
         shift = _ntt_shift(shift)                                  # held here until the call has returned (it reads the shift before it does)
         _native.check(self._lib.bn254_fr_ntt_batch_dev(self._h, d_in, d_out, log_n, count, 1 if inverse else 0, None if shift is None else _p(shift), stream))
+
+    def g1_ntt_batch_dev(self, d_in, d_out, log_n, count, inverse=False, shift=None, stream=0):
+        """device pointers in, out (count * 2^log_n records of 96 bytes; out may be in), ordered on `stream`; `shift` is a HOST scalar (4 uint64
+        words) or None, read before the call returns"""
+        shift = _ntt_shift(shift)                                  # held here until the call has returned (it reads the shift before it does)
+        _native.check(self._lib.bn254_g1_ntt_batch_dev(self._h, d_in, d_out, log_n, count, 1 if inverse else 0, None if shift is None else _p(shift), stream))
+
+    def g2_ntt_batch_dev(self, d_in, d_out, log_n, count, inverse=False, shift=None, stream=0):
+        """the same over G2: records of 192 bytes"""
+        shift = _ntt_shift(shift)                                  # held here until the call has returned (it reads the shift before it does)
+        _native.check(self._lib.bn254_g2_ntt_batch_dev(self._h, d_in, d_out, log_n, count, 1 if inverse else 0, None if shift is None else _p(shift), stream))
 
     def fr_dot_batch_dev(self, d_coeff, d_index, d_x, nx, offsets, m, d_out, stream=0):
         """device pointers coeff (offsets[m] records of 32 bytes), index (as many 64-bit words, or None), x (nx records), out (m records),

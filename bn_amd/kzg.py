@@ -7,7 +7,11 @@ With a structured reference string (tau^i G)_{i<n}, H, tau H for a secret tau (G
                 e(C - y G + z pi, H) * e(-pi, tau H) == 1                       so that nothing is computed in G2
 verify_batch answers for m openings from ONE call sequence: one segmented multi-scalar multiplication of m three-term segments
 (C_j * 1 + G * (-y_j) + pi_j * z_j), one batched subtraction for the negations, one batched multi-pairing check of two pairs per opening.
-A random linear combination of the checks into one multi-pairing is not built."""
+A random linear combination of the checks into one multi-pairing is not built.
+Over the transforms on G1 (bn254_g1_ntt_batch), none of which needs tau:
+    lagrange_srs    the points L_j(tau) G of the domain {w^j}: one inverse transform of the powers
+    commit_evals    C from the n evaluations of p over the domain: one multi-scalar multiplication against those points
+    open_all        every opening of p over the domain (FK20): three transforms over G1, two over Fr, one batched multiplication"""
 import collections
 
 import numpy as np
@@ -66,6 +70,56 @@ def open(srs, p, z, engine=None):
     if P.shape[0] == 1:
         return y, G1.zero()
     return y, G1(e.g1_msm(srs.g1_powers[:P.shape[0] - 1], out[1:]))
+
+
+LagrangeSRS = collections.namedtuple("LagrangeSRS", "g1_lagrange log_n g2_one tau_g2")
+LagrangeSRS.__doc__ = "g1_lagrange: (2^log_n, 12) uint64, the normalized points L_j(tau) G over the domain {w^j}; g2_one: H; tau_g2: tau H"
+
+
+def lagrange_srs(srs, log_n, engine=None):
+    """The reference string in the Lagrange basis of the domain {w^j}, w = Fr.root_of_unity(log_n), WITHOUT tau: ONE inverse transform over
+    G1 of the first n = 2^log_n powers, L_j(tau) G = n^-1 sum_k w^(-j k) (tau^k G).  ValueError when the string holds fewer than n powers."""
+    n = 1 << log_n
+    if srs.g1_powers.shape[0] < n:
+        raise ValueError(f"a Lagrange basis of 2^{log_n} points needs {n} powers but the reference string holds {srs.g1_powers.shape[0]}")
+    return LagrangeSRS((engine or default_engine()).g1_ntt_batch(srs.g1_powers[:n], log_n, True), log_n, srs.g2_one, srs.tau_g2)
+
+
+def commit_evals(lsrs, evals, engine=None):
+    """C = p(tau) G -> G1 for the polynomial of degree < n given by its n evaluations over the domain (Fr values or an (n,4) uint64 array):
+    one multi-scalar multiplication against the Lagrange points - the commitment commit() gives for the inverse transform of evals.
+    ValueError unless there are exactly n evaluations."""
+    E = _scalar_array(evals)
+    if E.shape[0] != lsrs.g1_lagrange.shape[0]:
+        raise ValueError(f"{E.shape[0]} evaluations against a Lagrange basis of {lsrs.g1_lagrange.shape[0]} points")
+    return G1((engine or default_engine()).g1_msm(lsrs.g1_lagrange, E))
+
+
+def open_all(srs, p, log_n, engine=None):
+    """(ys, proofs): every opening of p on the domain {w^m}, w = Fr.root_of_unity(log_n) - ys[m] = p(w^m) and proofs[m] the proof
+    open(srs, p, w^m) gives - from a few transforms instead of n multi-scalar multiplications (Feist and Khovratovich's FK20).  With
+    d = len(p) - 1 the proofs are the forward transform over G1 of (h_0 .. h_(d-1), O, ..), h_k = sum_(i <= d-1-k) p_(i+k+1) (tau^i G), and
+    the h_k are a convolution of the coefficients with the reversed powers: entries d-1 .. 2d-2 of the inverse transform of size 2n of the
+    entry-wise product (one g1_mul_batch) of the transformed coefficients and the transformed points.  The transform of the points depends
+    on the reference string and d only; it is not kept between calls.  A constant or empty polynomial has all-infinity proofs.
+    ValueError when len(p) > n or len(p) > the powers of the string, or 2n is above the largest transform over G1."""
+    P = _coefficients(srs, p)
+    n, L = 1 << log_n, P.shape[0]
+    if L > n:
+        raise ValueError(f"the polynomial has {L} coefficients but the domain holds {n} points")
+    e = engine or default_engine()
+    zero_fr = np.zeros((1, 4), np.uint64)
+    ys = e.fr_ntt_batch(np.concatenate([P, np.tile(zero_fr, (n - L, 1))]), log_n)
+    inf = G1.zero().limbs
+    d = L - 1
+    if d <= 0:
+        return [Fr.from_limbs(r) for r in ys], [G1.zero() for _ in range(n)]
+    s_hat = np.concatenate([srs.g1_powers[:d][::-1], np.tile(inf, (2 * n - d, 1))])
+    c = np.concatenate([P[1:], np.tile(zero_fr, (2 * n - d, 1))])
+    prod = e.g1_mul_batch(e.g1_ntt_batch(s_hat, log_n + 1), e.fr_ntt_batch(c, log_n + 1))
+    h = e.g1_ntt_batch(prod, log_n + 1, True)[d - 1:2 * d - 1]
+    proofs = e.g1_ntt_batch(np.concatenate([h, np.tile(inf, (n - d, 1))]), log_n)
+    return [Fr.from_limbs(r) for r in ys], [G1(r) for r in proofs]
 
 
 def verify_batch(srs, cs, zs, ys, proofs, engine=None):

@@ -211,6 +211,23 @@ inline std::vector<Fr> fr_ntt(const std::vector<Fr> &values, int log_n, bool inv
                              reinterpret_cast<const bn_fr *>(shift)));
     return out;
 }
+// The same transforms with points for data and scalar multiplication for the product: points.size() / 2^log_n transforms of 2^log_n
+// points each, natural order in and out, every output normalised.  The inverse transform of the powers tau^i G of a reference string
+// gives its Lagrange points.
+inline std::vector<G1> g1_ntt(const std::vector<G1> &points, int log_n, bool inverse = false, const Fr *shift = nullptr) {
+    if (log_n < 0 || log_n > BN254_GROUP_NTT_LOG_MAX || points.size() % (size_t(1) << log_n)) throw std::invalid_argument("g1_ntt: not whole transforms of 2^log_n");
+    std::vector<G1> out(points.size());
+    check(bn254_g1_ntt_batch(nullptr, reinterpret_cast<const bn_g1 *>(points.data()), reinterpret_cast<bn_g1 *>(out.data()), log_n, points.size() >> log_n, inverse ? 1 : 0,
+                             reinterpret_cast<const bn_fr *>(shift)));
+    return out;
+}
+inline std::vector<G2> g2_ntt(const std::vector<G2> &points, int log_n, bool inverse = false, const Fr *shift = nullptr) {
+    if (log_n < 0 || log_n > BN254_GROUP_NTT_LOG_MAX || points.size() % (size_t(1) << log_n)) throw std::invalid_argument("g2_ntt: not whole transforms of 2^log_n");
+    std::vector<G2> out(points.size());
+    check(bn254_g2_ntt_batch(nullptr, reinterpret_cast<const bn_g2 *>(points.data()), reinterpret_cast<bn_g2 *>(out.data()), log_n, points.size() >> log_n, inverse ? 1 : 0,
+                             reinterpret_cast<const bn_fr *>(shift)));
+    return out;
+}
 // out[j] = sum of coeff[t] * x[index[t]] over t in [offsets[j], offsets[j+1]): a sparse matrix in CSR form times the vector x - the witness
 // map of an R1CS.  index: nullptr for x[t], a plain segmented inner product (x.size() == coeff.size()).  An empty segment gives Fr::zero().
 inline std::vector<Fr> fr_dot(const std::vector<Fr> &coeff, const std::vector<uint64_t> *index, const std::vector<Fr> &x, const std::vector<size_t> &offsets) {

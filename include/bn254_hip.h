@@ -95,6 +95,9 @@
  *                          counterpart in the reference
  *   bn254_bjj_pack_batch_dev / bn254_bjj_unpack_batch_dev / bn254_eddsa_poseidon_verify_packed_batch_dev  the same three on device-resident
  *                          records, asynchronous on the caller's stream
+ *   bn254_g1_ntt_batch / bn254_g2_ntt_batch  the transform of bn254_fr_ntt_batch with points for data and scalar multiplication for the product:
+ *                          out[k] = normalize(sum_j [s^j w_n^(j k)] in[j]), and its inverse; no counterpart in the reference
+ *   bn254_g1_ntt_batch_dev / bn254_g2_ntt_batch_dev  the same two on device-resident records, asynchronous on the caller's stream
  *   bn254_g2_precompute    coeffs[i][0..102) = q[i].to_affine().precompute().coeffs   groups/mod.rs:557-588 (Q != infinity)
  *   bn254_pairing_prepared_batch  out[i] = final_exponentiation(prepared.miller_loop(p[i]))   groups/mod.rs:486-519,768
  *   bn254_gt_mul_batch     out[i] = a[i] * b[i]                                     lib.rs:175-179, fields/fq12.rs:295-307
@@ -132,6 +135,8 @@
      bn254_fr_{add,mul,inverse,pow,interpret}_batch serialise on the context in the same way (its mutex for the whole call).
      bn254_fr_ntt_batch serialises on the context in the same way (its mutex for the whole call); bn254_fr_root_of_unity touches no
      context and no device.
+     bn254_g{1,2}_ntt_batch serialise on the context in the same way (its mutex for the whole call); bn254_g{1,2}_ntt_batch_dev run under
+     the scratch guard like the other _dev entry points that use context-owned scratch.
      bn254_fr_dot_batch serialises on the context in the same way (its mutex for the whole call).
      bn254_fr_scan_batch serialises on the context in the same way (its mutex for the whole call).
      bn254_fr_mle_eq, bn254_fr_mle_fold and bn254_fr_sumcheck_round serialise on the context in the same way (its mutex for the whole call).
@@ -547,6 +552,31 @@ int bn254_fr_sqrt_batch(bn254_ctx *ctx, const bn_fr *a, bn_fr *out, int32_t *ok,
 #define BN254_NTT_LOG_MAX 24
 int bn254_fr_root_of_unity(int log_n, bn_fr *out);
 int bn254_fr_ntt_batch(bn254_ctx *ctx, const bn_fr *in, bn_fr *out, int log_n, size_t count, int inverse, const bn_fr *shift);
+/* The same transforms over G1 and G2: points for data, scalar multiplication for the product - what turns the powers tau^i G of a
+   reference string into the Lagrange points L_j(tau) G without tau (one inverse transform), and what computes all n openings of a
+   polynomial over the domain with a few transforms instead of n multi-scalar multiplications (FK20; bn_amd.kzg.lagrange_srs, open_all).
+   `count` transforms of n = 2^log_n points each (log_n 0 .. BN254_GROUP_NTT_LOG_MAX), transform t in records [t n, (t + 1) n), natural
+   order in and out, w_n the root of bn254_fr_root_of_unity(log_n):
+   forward (inverse == 0):  out[t n + k] = sum_j [s^j w_n^(j k)] in[t n + j]
+   inverse (inverse != 0):  out[t n + j] = [n^-1 s^-j] sum_k [w_n^(-j k)] in[t n + k]
+   `shift` as for bn254_fr_ntt_batch: ONE element in HOST memory, read before the call returns, NULL for s = 1.
+   Inputs are raw points as bn254_g{1,2}_mul_batch take them: any z, z == 0 is the point at infinity whatever x and y hold; the caller
+   vouches for curve and subgroup membership.  Outputs are NORMALISED: every record holds the bytes bn254_g{1,2}_normalize_batch give for
+   that group element (infinity: (0, 1, 0)), so the bytes do not depend on how the transform is scheduled.  `out` may be exactly `in`
+   (partial overlap is outside the contract).
+   How: log_n radix-2 Stockham stages in global memory (no bit reversal), one lane per butterfly for G1 and one lane pair for G2: the
+   twiddle from the factored root tables of bn254_fr_ntt_batch, ONE GLV / GLS chain left Jacobian, then the sum and the difference by the
+   complete addition (equal and opposite operands are ordinary here: a constant input doubles at every stage).  The stage whose twiddles
+   are all one runs no chain: n / 2 (log_n - 1) chains per transform.  A shift, or the n^-1 of an inverse, is one further pass of n chains
+   with the scalars of the shift tables.  Points stay Jacobian between the stages; the last step is the shared-inversion normalisation.
+   Scratch per context: the tables of bn254_fr_ntt_batch, one array of Jacobian points of the size of a group of transforms (up to 2^22
+   points: 384 MB for G1, 768 MB for G2), the window tables of one sub-launch (640 B per lane, at most 2^20 lanes) and the prefix products
+   of the normalisation.  Measurements: tools/time_group_ntt.py.
+   Errors (BN254_E_BAD_ARG, checked before any device is touched, in this order): log_n < 0 or > BN254_GROUP_NTT_LOG_MAX, a NULL `in` or
+   `out`, count 2^log_n > 2^40, a `shift` that is Fr::zero().  count == 0 returns BN254_OK and writes nothing. */
+#define BN254_GROUP_NTT_LOG_MAX 22
+int bn254_g1_ntt_batch(bn254_ctx *ctx, const bn_g1 *in, bn_g1 *out, int log_n, size_t count, int inverse, const bn_fr *shift);
+int bn254_g2_ntt_batch(bn254_ctx *ctx, const bn_g2 *in, bn_g2 *out, int log_n, size_t count, int inverse, const bn_fr *shift);
 /* Sparse linear maps over Fr: m dot products in one call - a sparse matrix in CSR form times a vector.  The witness map of an R1CS (the rows
    of A, B, C against the assignment z, in front of the quotient of bn254_fr_ntt_batch), the same transposed for a setup
    (u_i(tau) = sum_j A[j,i] L_j(tau)), and, without an index, segmented inner products: a polynomial against a vector of powers, plain sums
@@ -1101,6 +1131,11 @@ int bn254_fr_sqrt_batch_dev(bn254_ctx *ctx, const void *d_a, void *d_out, void *
    be exactly d_in; `shift` is HOST memory (one element or NULL), read before the call returns.  Tables and the arrays between the passes
    are context-owned scratch (see Threading). */
 int bn254_fr_ntt_batch_dev(bn254_ctx *ctx, const void *d_in, void *d_out, int log_n, size_t count, int inverse, const bn_fr *shift, void *stream);
+/* bn254_g{1,2}_ntt_batch on device-resident arrays (count 2^log_n records of 96 / 192 bytes, 16-byte aligned), asynchronous on `stream`;
+   d_out may be exactly d_in; `shift` is HOST memory (one element or NULL), read before the call returns.  Tables, the array between the
+   stages, window tables and prefix products are context-owned scratch (see Threading). */
+int bn254_g1_ntt_batch_dev(bn254_ctx *ctx, const void *d_in, void *d_out, int log_n, size_t count, int inverse, const bn_fr *shift, void *stream);
+int bn254_g2_ntt_batch_dev(bn254_ctx *ctx, const void *d_in, void *d_out, int log_n, size_t count, int inverse, const bn_fr *shift, void *stream);
 /* bn254_fr_dot_batch on device-resident coeff (n records of 32 bytes, 16-byte aligned), d_index (n 64-bit words, or NULL), x (nx records) and
    out (m records); `offsets` (m+1 entries) is HOST memory (the launches are planned from it) and may be freed on return.  d_index cannot be
    read on the host, so it is NOT checked: an index >= nx is outside the contract, but memory safe - the kernel compares it before it loads
@@ -1174,6 +1209,7 @@ int bn254_profile_reset(bn254_ctx *ctx);
    of bn254_g1_validate_batch and bn254_g2_validate_batch: "g1_validate", "g2_validate" (one scope per sub-launch);
    of bn254_bjj_{validate,add,mul}_batch and bn254_eddsa_poseidon_{challenge,verify}_batch: "bjj_validate", "bjj_add", "bjj_mul", "eddsa_poseidon_challenge", "eddsa_poseidon_verify" (one scope per sub-launch);
    of bn254_fr_sqrt_batch, bn254_bjj_{pack,unpack}_batch and bn254_eddsa_poseidon_verify_packed_batch: "fr_sqrt", "bjj_pack", "bjj_unpack", "eddsa_poseidon_verify_packed" (one scope per sub-launch);
+   of bn254_g{1,2}_ntt_batch: "g1_ntt", "g2_ntt" (the stages, one scope per sub-launch), "g1_ntt_scale", "g2_ntt_scale" (the pass of a shift or of an inverse), "g1_ntt_normalize", "g2_ntt_normalize" (the normalisation that ends a call);
    and, of bn254_fr_ntt_batch: "ntt" (the passes), "ntt_table" (the builds of the twiddle tables).
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);

@@ -17,7 +17,7 @@ name=$1; shift
 B=bn_amd/csrc/build
 UNITS=${UNITS:-bn254_kernels_b}
 objs=""
-for u in bn254_hip bn254_seg bn254_wire bn254_kernels_b bn254_kernels_mul bn254_kernels_w bn254_kernels_q bn254_multi bn254_measure bn254_fr bn254_fr_sqrt bn254_ntt bn254_dot bn254_scan bn254_mle bn254_poseidon bn254_poseidon_wide bn254_hash bn254_hash_g2 bn254_validate bn254_babyjub; do
+for u in bn254_hip bn254_seg bn254_wire bn254_kernels_b bn254_kernels_mul bn254_kernels_w bn254_kernels_q bn254_multi bn254_measure bn254_fr bn254_fr_sqrt bn254_ntt bn254_group_ntt bn254_dot bn254_scan bn254_mle bn254_poseidon bn254_poseidon_wide bn254_hash bn254_hash_g2 bn254_validate bn254_babyjub; do
   if [[ " $UNITS " == *" $u "* ]]; then
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value -mllvm -amdgpu-dpp-combine=false "$@" -c bn_amd/csrc/$u.hip -o build_variants/${u}_$name.o &
     objs="$objs build_variants/${u}_$name.o"
