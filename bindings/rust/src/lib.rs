@@ -117,6 +117,20 @@ extern "C" {
     fn bn254_g2_msm(ctx: *mut c_void, p: *const G2, k: *const Fr, n: usize, out: *mut G2) -> c_int;
     fn bn254_g1_msm_dev(ctx: *mut c_void, d_p: *const c_void, d_k: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn bn254_g2_msm_dev(ctx: *mut c_void, d_p: *const c_void, d_k: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn bn254_g1_msm_prepare(ctx: *mut c_void, p: *const G1, n: usize, window_bits: c_int, out: *mut *mut c_void) -> c_int;
+    fn bn254_g2_msm_prepare(ctx: *mut c_void, p: *const G2, n: usize, window_bits: c_int, out: *mut *mut c_void) -> c_int;
+    fn bn254_g1_msm_prepare_dev(ctx: *mut c_void, d_p: *const c_void, n: usize, window_bits: c_int, out: *mut *mut c_void, stream: *mut c_void) -> c_int;
+    fn bn254_g2_msm_prepare_dev(ctx: *mut c_void, d_p: *const c_void, n: usize, window_bits: c_int, out: *mut *mut c_void, stream: *mut c_void) -> c_int;
+    fn bn254_msm_prepared_destroy(prep: *mut c_void);
+    fn bn254_msm_prepared_count(prep: *const c_void) -> usize;
+    fn bn254_msm_prepared_bytes(prep: *const c_void) -> usize;
+    fn bn254_msm_prepared_group(prep: *const c_void) -> c_int;
+    fn bn254_msm_prepared_window_bits(prep: *const c_void) -> c_int;
+    fn bn254_msm_prepared_export(ctx: *mut c_void, prep: *const c_void, host_table: *mut c_void, bytes: usize) -> c_int;
+    fn bn254_g1_msm_prepared(ctx: *mut c_void, prep: *const c_void, first: usize, k: *const Fr, n: usize, out: *mut G1) -> c_int;
+    fn bn254_g2_msm_prepared(ctx: *mut c_void, prep: *const c_void, first: usize, k: *const Fr, n: usize, out: *mut G2) -> c_int;
+    fn bn254_g1_msm_prepared_dev(ctx: *mut c_void, prep: *const c_void, first: usize, d_k: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn bn254_g2_msm_prepared_dev(ctx: *mut c_void, prep: *const c_void, first: usize, d_k: *const c_void, n: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn bn254_g1_msm_multi(mh: *mut c_void, p: *const G1, k: *const Fr, n: usize, out: *mut G1) -> c_int;
     fn bn254_g2_msm_multi(mh: *mut c_void, p: *const G2, k: *const Fr, n: usize, out: *mut G2) -> c_int;
     fn bn254_g1_mul_base_batch(ctx: *mut c_void, base: *const G1, k: *const Fr, out: *mut G1, n: usize) -> c_int;
@@ -306,6 +320,52 @@ pub fn g2_msm(p: &[G2], k: &[Fr]) -> Result<G2, GpuError> {
     let mut out = G2::zero();
     check(unsafe { bn254_g2_msm(std::ptr::null_mut(), p.as_ptr(), k.as_ptr(), p.len(), &mut out) })?;
     Ok(out)
+}
+
+/// Points a prover multiplies fresh scalars against, call after call (a proving key, an SRS), prepared once: the handle keeps the affine
+/// multiples `2^(c w) P_i` in device memory, and `msm(first, k)` is `normalize(sum P[first + i] * k[i])` - the bytes of `g1_msm` / `g2_msm`
+/// on the same points and scalars.  `window_bits`: 0 for the default of the size, or 3..=16.
+pub struct PreparedMsmG1(*mut c_void);
+unsafe impl Send for PreparedMsmG1 {}
+unsafe impl Sync for PreparedMsmG1 {}
+impl PreparedMsmG1 {
+    pub fn new(p: &[G1], window_bits: i32) -> Result<PreparedMsmG1, GpuError> {
+        let mut h = std::ptr::null_mut();
+        check(unsafe { bn254_g1_msm_prepare(std::ptr::null_mut(), p.as_ptr(), p.len(), window_bits, &mut h) })?;
+        Ok(PreparedMsmG1(h))
+    }
+    pub fn len(&self) -> usize { unsafe { bn254_msm_prepared_count(self.0) } }
+    pub fn device_bytes(&self) -> usize { unsafe { bn254_msm_prepared_bytes(self.0) } }
+    pub fn window_bits(&self) -> i32 { unsafe { bn254_msm_prepared_window_bits(self.0) } }
+    pub fn msm(&self, first: usize, k: &[Fr]) -> Result<G1, GpuError> {
+        let mut out = G1::zero();
+        check(unsafe { bn254_g1_msm_prepared(std::ptr::null_mut(), self.0, first, k.as_ptr(), k.len(), &mut out) })?;
+        Ok(out)
+    }
+}
+impl Drop for PreparedMsmG1 {
+    fn drop(&mut self) { unsafe { bn254_msm_prepared_destroy(self.0) } }
+}
+pub struct PreparedMsmG2(*mut c_void);
+unsafe impl Send for PreparedMsmG2 {}
+unsafe impl Sync for PreparedMsmG2 {}
+impl PreparedMsmG2 {
+    pub fn new(p: &[G2], window_bits: i32) -> Result<PreparedMsmG2, GpuError> {
+        let mut h = std::ptr::null_mut();
+        check(unsafe { bn254_g2_msm_prepare(std::ptr::null_mut(), p.as_ptr(), p.len(), window_bits, &mut h) })?;
+        Ok(PreparedMsmG2(h))
+    }
+    pub fn len(&self) -> usize { unsafe { bn254_msm_prepared_count(self.0) } }
+    pub fn device_bytes(&self) -> usize { unsafe { bn254_msm_prepared_bytes(self.0) } }
+    pub fn window_bits(&self) -> i32 { unsafe { bn254_msm_prepared_window_bits(self.0) } }
+    pub fn msm(&self, first: usize, k: &[Fr]) -> Result<G2, GpuError> {
+        let mut out = G2::zero();
+        check(unsafe { bn254_g2_msm_prepared(std::ptr::null_mut(), self.0, first, k.as_ptr(), k.len(), &mut out) })?;
+        Ok(out)
+    }
+}
+impl Drop for PreparedMsmG2 {
+    fn drop(&mut self) { unsafe { bn254_msm_prepared_destroy(self.0) } }
 }
 
 /// `out[i] = (base * k[i]).normalize()`: fixed-base scalar multiplication - many scalars against ONE point (key and SRS generation,

@@ -43,6 +43,20 @@ SIGNATURES = {   # name -> argtypes  (every function returns int unless noted)
     "bn254_g2_msm": [_VP, _VP, _VP, _SZ, _VP],
     "bn254_g1_msm_dev": [_VP, _VP, _VP, _SZ, _VP, _VP],
     "bn254_g2_msm_dev": [_VP, _VP, _VP, _SZ, _VP, _VP],
+    "bn254_g1_msm_prepare": [_VP, _VP, _SZ, C.c_int, C.POINTER(_VP)],
+    "bn254_g2_msm_prepare": [_VP, _VP, _SZ, C.c_int, C.POINTER(_VP)],
+    "bn254_g1_msm_prepare_dev": [_VP, _VP, _SZ, C.c_int, C.POINTER(_VP), _VP],
+    "bn254_g2_msm_prepare_dev": [_VP, _VP, _SZ, C.c_int, C.POINTER(_VP), _VP],
+    "bn254_msm_prepared_destroy": [_VP],
+    "bn254_msm_prepared_count": [_VP],
+    "bn254_msm_prepared_bytes": [_VP],
+    "bn254_msm_prepared_group": [_VP],
+    "bn254_msm_prepared_window_bits": [_VP],
+    "bn254_msm_prepared_export": [_VP, _VP, _VP, _SZ],
+    "bn254_g1_msm_prepared": [_VP, _VP, _SZ, _VP, _SZ, _VP],
+    "bn254_g2_msm_prepared": [_VP, _VP, _SZ, _VP, _SZ, _VP],
+    "bn254_g1_msm_prepared_dev": [_VP, _VP, _SZ, _VP, _SZ, _VP, _VP],
+    "bn254_g2_msm_prepared_dev": [_VP, _VP, _SZ, _VP, _SZ, _VP, _VP],
     "bn254_g1_msm_multi": [_VP, _VP, _VP, _SZ, _VP],
     "bn254_g2_msm_multi": [_VP, _VP, _VP, _SZ, _VP],
     "bn254_g1_mul_batch": [_VP, _VP, _VP, _VP, _SZ],
@@ -302,6 +316,9 @@ def lib():
         l.bn254_g2_prepared_count.restype = C.c_size_t
         l.bn254_g2_prepared_bytes.restype = C.c_size_t
         l.bn254_multi_ctx.restype = C.c_void_p
+        l.bn254_msm_prepared_destroy.restype = None
+        l.bn254_msm_prepared_count.restype = C.c_size_t
+        l.bn254_msm_prepared_bytes.restype = C.c_size_t
         _lib = l
     return _lib
 

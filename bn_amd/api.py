@@ -312,6 +312,25 @@ def g2_msm(points, scalars, engine=None):
     return G2((engine or default_engine()).g2_msm(P, K))
 
 
+def _point_array(group, points):
+    if isinstance(points, np.ndarray):
+        return np.asarray(points, np.uint64).reshape(-1, group.WORDS)
+    points = list(points)
+    return np.stack([p.limbs for p in points]) if points else np.zeros((0, group.WORDS), np.uint64)
+
+
+def g1_msm_prepare(points, window_bits=None, engine=None):
+    """PreparedMSM of the G1 points: prepare once what g1_msm redoes per call against the same points (a proving key, an SRS), then
+    `.msm(scalars, first=0)` == g1_msm(points[first:first + len(scalars)], scalars), the same bytes.  points: a sequence of G1 or an (n,12)
+    uint64 array, raw (any z); window_bits: None for the default of the size, or 3 .. 16."""
+    return (engine or default_engine()).g1_msm_prepare(_point_array(G1, points), window_bits)
+
+
+def g2_msm_prepare(points, window_bits=None, engine=None):
+    """the same over G2: a sequence of G2 or an (n,24) uint64 array"""
+    return (engine or default_engine()).g2_msm_prepare(_point_array(G2, points), window_bits)
+
+
 def _scalar_array(scalars):
     if isinstance(scalars, np.ndarray):
         return np.asarray(scalars, np.uint64).reshape(-1, 4)

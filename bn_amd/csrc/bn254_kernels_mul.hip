@@ -206,6 +206,50 @@ struct MsmDigitsOp {
         }
     }
 };
+// The same walk over the signed digits of a call against prepared bases (group_ops.hpp msm_signed_digit): ONE set of 2^(c-1) buckets for all
+// windows, key = |d| - 1; the entry written for term i and window w is the table index w * count + first + i, MSM_NEG set for d < 0.
+struct MsmSignedDigitsOp {
+    const uint32_t *k; uint32_t n, c, W, count, first; uint32_t *counts; uint32_t *idx, *keys; int scatter;
+    __device__ __forceinline__ void operator()() const {
+        const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+        if (i >= n) return;
+        uint32_t raw[8];
+        fr_load_raw(k + 8u * i, raw);
+        const uint64_t active = __ballot(1);
+        const uint32_t lane = __lane_id(), leader = (uint32_t)__ffsll((unsigned long long)active) - 1u;
+        const uint32_t rank = (uint32_t)__popcll(active & ((1ull << lane) - 1ull)), total = (uint32_t)__popcll(active);
+        uint32_t carry = 0;
+#pragma unroll 1
+        for (uint32_t w = 0; w < W; ++w) {
+            bool neg;
+            const uint32_t d = msm_signed_digit(raw, w, c, carry, neg), first_d = (uint32_t)__shfl((int)d, (int)leader);
+            const uint32_t key = d - 1u;                               // used for d != 0 only
+            uint32_t pos = 0;
+            if (__all(d == first_d)) {                                 // wave-uniform
+                if (d && lane == leader) pos = atomicAdd(&counts[key], total);
+                pos = (uint32_t)__shfl((int)pos, (int)leader) + rank;
+            } else {
+                // groups of equal digits inside a wave add through ONE atomic, as in MsmDigitsOp
+                bool done = d == 0;
+                uint64_t rem = __ballot(!done);
+                for (int small = 0; rem && small < 2;) {
+                    const uint32_t lead = (uint32_t)__ffsll((unsigned long long)rem) - 1u, dl = (uint32_t)__shfl((int)d, (int)lead);
+                    const bool mine = !done && d == dl;
+                    const uint64_t m = __ballot(mine);
+                    rem &= ~m;
+                    const uint32_t cnt = (uint32_t)__popcll(m);
+                    if (cnt < 3) { ++small; continue; }
+                    uint32_t base = 0;
+                    if (lane == lead) base = atomicAdd(&counts[dl - 1u], cnt);
+                    base = (uint32_t)__shfl((int)base, (int)lead);
+                    if (mine) { pos = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)); done = true; }
+                }
+                if (!done) pos = atomicAdd(&counts[key], 1u);
+            }
+            if (scatter && d) { idx[pos] = (w * count + first + i) | (neg ? MSM_NEG : 0u); keys[pos] = key; }
+        }
+    }
+};
 // exclusive scan of `total` counts in place, three launches: mode 0 - the sum of every tile; 1 - ONE workgroup scans the (at most 1024) tile
 // sums and writes the grand total to *n0; 2 - every tile scans its counts from its base
 struct MsmScanOp {
@@ -262,6 +306,10 @@ struct BaseRepackOp {
 // whole - the bodies return early themselves (a lane past a level's entries), both lanes of a pair alike, so nothing here is clamped.
 template <class F> __device__ __forceinline__ void msm_point_op(const MsmAccArgs &g, uint32_t i) { msm_acc_body<F>(g, i); }
 template <class F> __device__ __forceinline__ void msm_point_op(const MsmReduceArgs &g, uint32_t i) { msm_reduce_body<F>(g, i); }
+template <class F> __device__ __forceinline__ void msm_point_op(const MsmAccPrepArgs &g, uint32_t i) {
+    msm_acc_prep_body<F>(g, i, BaseTableMem<F>{g.table, std::is_same<F, G1F>::value ? 0u : threadIdx.x & 1u});
+}
+template <class F> __device__ __forceinline__ void msm_point_op(const MsmPrepDoubleArgs &g, uint32_t i) { msm_prep_double_body<F>(g, i, PointIo<F>()); }
 template <class F> __device__ __forceinline__ void msm_point_op(const BaseMulArgs &g, uint32_t i) {
     base_mul_body<F>(g, i, BaseTableMem<F>{g.table, std::is_same<F, G1F>::value ? 0u : threadIdx.x & 1u}, PointIo<F>());
 }
@@ -354,6 +402,23 @@ int bn254_launch_msm_reduce_M(int g, const void *buckets, unsigned G, unsigned g
     const MsmReduceArgs a = {(const uint32_t *)buckets, G, groups, c, (uint32_t)count, (uint32_t *)terms};
     return launch_group(g, count, s, bn254_g1_add_M<MsmReduceArgs>, bn254_g2_add_M<MsmReduceArgs>, a, (uint32_t)count);
 }
+// bn254_g{1,2}_msm_prepared.  digits: as above over the signed digits - `count` points in the handle, term i of this launch is point first + i;
+// counts: 2^(c-1) words
+int bn254_launch_msmp_digits_M(const void *k, size_t n, unsigned c, unsigned W, size_t count, size_t first, void *counts, void *idx, void *keys, int scatter, hipStream_t s) {
+    const MsmSignedDigitsOp op = {(const uint32_t *)k, (uint32_t)n, c, W, (uint32_t)count, (uint32_t)first, (uint32_t *)counts, (uint32_t *)idx, (uint32_t *)keys, scatter};
+    return bn_lane_launch<256>(op, n, s);
+}
+// level 0 of the accumulation over the handle's table, `lanes` lanes (G2: lane pairs)
+int bn254_launch_msmp_bucket_M(int g, const void *table, const void *idx, const void *keys, const void *n0, void *out_pts, void *out_keys, void *buckets, size_t lanes, hipStream_t s) {
+    const MsmAccPrepArgs a = {(const uint4 *)table, (const uint32_t *)idx, (const uint32_t *)keys, (const uint32_t *)n0, (uint32_t *)out_pts, (uint32_t *)out_keys, (uint32_t *)buckets};
+    return launch_group(g, lanes, s, bn254_g1_add_M<MsmAccPrepArgs>, bn254_g2_add_M<MsmAccPrepArgs>, a, (uint32_t)lanes);
+}
+// a table build's window step: the n Jacobian points at d_pts doubled c times in place
+int bn254_launch_msmp_double_M(int g, void *d_pts, unsigned c, size_t n, hipStream_t s) {
+    const MsmPrepDoubleArgs a = {(uint32_t *)d_pts, c};
+    return launch_group(g, n, s, bn254_g1_add_M<MsmPrepDoubleArgs>, bn254_g2_add_M<MsmPrepDoubleArgs>, a, (uint32_t)n);
+}
+size_t bn254_msmp_entry_bytes_M(int g) { return (size_t)(g == 1 ? 1 : 2) * AFF_ENTRY_U4 * sizeof(uint4); }
 // bn254_g{1,2}_mul_base_batch.  A table: W * 2^(c-1) entries of 80 (G1) / 160 (G2) bytes for c-bit windows, 3 <= c <= 16 (c W > 254).
 size_t bn254_mul_base_table_bytes_M(int g, unsigned c) {
     return (size_t)((254 + c - 1) / c) * ((size_t)1 << (c - 1)) * (g == 1 ? 1 : 2) * AFF_ENTRY_U4 * sizeof(uint4);

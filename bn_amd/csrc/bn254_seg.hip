@@ -331,6 +331,155 @@ int bn_launch_eq(bn254_ctx *c, int g, const void *d_a, const void *d_b, void *d_
 }
 }  // namespace
 
+// ---- multi-scalar multiplication against prepared bases (bn254_g{1,2}_msm_prepare*, bn254_g{1,2}_msm_prepared*)
+// Everything bn254_g{1,2}_msm redoes per call that depends on the points alone is in the handle: the affine multiples 2^(c w) P_i
+// (group_ops.hpp: records, layout, bodies).
+// The build (scope g*_msmp_table), window by window over scratch of two count-sized arrays in the context's workspace: a running Jacobian
+// copy of the points is normalised (bn_launch_normalize: one inversion per NORM_RUN points) into the second array, whose points are repacked
+// into the window's records (window 0: and kept as the handle's points); the running copy is then doubled c times in place.  The entries
+// are normalised, so the table does not depend on how it was built.
+// scratch guard held by the caller
+static int bn_msmp_build(bn254_ctx *c, bn254_msm_prepared *h, const void *d_p, hipStream_t s) {
+    const int g = h->group;
+    const size_t V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2), n = h->count, E = bn254_msmp_entry_bytes_M(g);
+    if (n == 0) return BN254_OK;
+    int rc = c->ws.reserve(2 * n * V); if (rc) return rc;
+    char *run = (char *)c->ws.p, *norm = run + n * V;
+    HIP_TRY(hipMemcpyAsync(run, d_p, n * V, hipMemcpyDeviceToDevice, s));
+    for (unsigned w = 0; w < h->W; ++w) {
+        if ((rc = bn_launch_normalize(c, g, run, norm, n, s))) return rc;
+        BnScope sc(c, s, g == 1 ? "g1_msmp_table" : "g2_msmp_table");
+        if (w == 0) HIP_TRY(hipMemcpyAsync(h->pts, norm, n * V, hipMemcpyDeviceToDevice, s));
+        rc = bn_for_parts(n, BN_LAUNCH_MAX / 2, [&](size_t lo, size_t cnt) -> int {
+            if (int e = bn254_launch_mul_base_repack_M(g, norm + lo * V, (char *)h->table + ((size_t)w * n + lo) * E, cnt, s)) return e;
+            return w + 1 < h->W ? bn254_launch_msmp_double_M(g, run + lo * V, h->c, cnt, s) : BN254_OK;
+        });
+        if (rc) return rc;
+    }
+    return BN254_OK;
+}
+static void bn_msmp_free(bn254_msm_prepared *h) {
+    if (h->table) hipFree(h->table);
+    if (h->pts) hipFree(h->pts);
+    delete h;
+}
+// d_p: device memory; the checks that need no device are the caller's
+static int bn_msmp_prepare_dev(bn254_ctx *ctx, int g, const void *d_p, size_t n, int window_bits, void **out, void *stream) {
+    *out = nullptr;
+    return bn_dev_entry(ctx, stream, true, [&](hipStream_t s) -> int {
+        bn254_msm_prepared *h = new (std::nothrow) bn254_msm_prepared();
+        if (!h) return BN254_E_ALLOC;
+        h->device = ctx->device; h->group = g; h->count = n;
+        h->c = window_bits ? (unsigned)window_bits : bn_msm_prepared_window_bits(n);
+        h->W = bn_msm_prepared_windows(h->c);
+        h->table_bytes = (size_t)h->W * n * bn254_msmp_entry_bytes_M(g);
+        if (n && (hipMalloc(&h->table, h->table_bytes) != hipSuccess || hipMalloc(&h->pts, n * (g == 1 ? sizeof(bn_g1) : sizeof(bn_g2))) != hipSuccess)) {
+            (void)hipGetLastError();
+            bn_msmp_free(h);
+            return BN254_E_ALLOC;
+        }
+        if (int rc = bn_msmp_build(ctx, h, d_p, s)) { (void)hipStreamSynchronize(s); bn_msmp_free(h); return rc; }
+        *out = h;
+        return BN254_OK;
+    });
+}
+// The call from the crossover on, per chunk of at most BN254_OPT_MSM_CHUNK terms (all chunks into the same buckets):
+//   digits   count the terms per |digit| (MsmSignedDigitsOp), scan the 2^(c-1) counts, scatter (table index | sign, key)     scope g*_msmp_digits
+//   bucket   level 0 from the records (msm_acc_prep_body), levels 1 .. of Jacobian partial sums (msm_acc_body), launched for the
+//            upper bound W * terms of the entry count: nothing is read back                                                  scope g*_msmp_bucket
+// then ONE reduction over the one window of 2^(c-1) buckets (scope g*_msmp_reduce) and the one-segment bn_launch_msm over its
+// 2 * 2^(c-1) / 16 terms with the scalars base + 1 and 1.  Workspace: msm_ws (host_plan.hpp msm_prepared_plan).
+// scratch guard held by the caller
+static int bn_launch_msmp_bucket(bn254_ctx *c, const bn254_msm_prepared *h, size_t first, const void *d_k, size_t n, void *d_out, hipStream_t s) {
+    const int g = h->group;
+    const size_t V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2), L = bn254_msm_piece_M();
+    const unsigned cb = h->c;
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, (size_t)bn_opt(c, BN254_OPT_MSM_CHUNK)));
+    const MsmBucketPlan bp = msm_prepared_plan(cb, chunk, V, L);
+    int rc;
+    if ((rc = c->msm_ws.reserve(bp.bytes))) return rc;
+    char *ws = (char *)c->msm_ws.p;
+    if (c->msmp_scal_c != (long)cb) {
+        std::vector<uint64_t> &hs = c->msmp_scal_host;
+        HIP_TRY(hipStreamSynchronize(s));                    // the previous image may still be on its way
+        msm_prepared_tail_scalars(cb, hs);
+        if ((rc = c->msmp_scal.reserve(hs.size() * 8))) return rc;
+        c->msmp_scal_c = -1;
+        HIP_TRY(hipMemcpyAsync(c->msmp_scal.p, hs.data(), hs.size() * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        c->msmp_scal_c = (long)cb;
+    }
+    HIP_TRY(hipMemsetAsync(ws + bp.o_buckets, 0, bp.K * V, s));   // z = 0: every bucket starts as the point at infinity
+    rc = bn_for_parts(n, chunk, [&](size_t lo, size_t len) -> int {
+        const char *pk = (const char *)d_k + lo * sizeof(bn_fr);
+        {
+            BnScope sc(c, s, g == 1 ? "g1_msmp_digits" : "g2_msmp_digits");
+            HIP_TRY(hipMemsetAsync(ws + bp.o_counts, 0, bp.K * 4, s));
+            if ((rc = bn254_launch_msmp_digits_M(pk, len, cb, bp.W, h->count, first + lo, ws + bp.o_counts, nullptr, nullptr, 0, s))) return rc;
+            if ((rc = bn254_launch_msm_scan_M(ws + bp.o_counts, bp.K, ws + bp.o_tiles, ws + bp.o_n0, s))) return rc;
+            if ((rc = bn254_launch_msmp_digits_M(pk, len, cb, bp.W, h->count, first + lo, ws + bp.o_counts, ws + bp.o_idx, ws + bp.o_keys, 1, s))) return rc;
+        }
+        BnScope sc(c, s, g == 1 ? "g1_msmp_bucket" : "g2_msmp_bucket");
+        const char *pts = nullptr, *keys = ws + bp.o_keys;
+        size_t N = (size_t)bp.W * len;
+        for (unsigned level = 0;; ++level) {
+            if (level >= bp.o_level.size()) return BN254_E_INTERNAL;
+            char *opts = ws + bp.o_level[level].first, *okeys = ws + bp.o_level[level].second;
+            const size_t lanes = (N + L - 1) / L;
+            if (level == 0) rc = bn254_launch_msmp_bucket_M(g, h->table, ws + bp.o_idx, keys, ws + bp.o_n0, opts, okeys, ws + bp.o_buckets, lanes, s);
+            else rc = bn254_launch_msm_bucket_M(g, pts, nullptr, keys, ws + bp.o_n0, level, opts, okeys, ws + bp.o_buckets, lanes, s);
+            if (rc) return rc;
+            if (N <= L) return BN254_OK;
+            N = 2 * lanes; pts = opts; keys = okeys;
+        }
+    });
+    if (rc) return rc;
+    {
+        BnScope sc(c, s, g == 1 ? "g1_msmp_reduce" : "g2_msmp_reduce");
+        if ((rc = bn254_launch_msm_reduce_M(g, ws + bp.o_buckets, bp.G, bp.groups, cb - 1, bp.count, ws + bp.o_terms, s))) return rc;
+    }
+    const size_t off[2] = {0, 2 * bp.count};
+    return bn_launch_msm(c, g, ws + bp.o_terms, c->msmp_scal.p, off, 1, d_out, s);
+}
+// the route of one call: below the crossover the one-segment launch sequence of bn254_g{1,2}_msm_batch on the handle's points
+static bool bn_msmp_bucket_route(const bn254_ctx *c, int g, size_t n) {
+    const long set = c->opt[BN254_OPT_MSM_BUCKET_MIN].load(std::memory_order_relaxed);
+    return n >= (size_t)(set >= 0 ? set : g == 1 ? BN_MSMP_BUCKET_MIN_DEFAULT : BN_MSMP_BUCKET_MIN_DEFAULT_G2);
+}
+static int msmp_dev(bn254_ctx *ctx, int g, const void *prep, size_t first, const void *d_k, size_t n, void *d_out, void *stream) {
+    const bn254_msm_prepared *h = (const bn254_msm_prepared *)prep;
+    if (int e = bn_msm_prepared_check(h != nullptr, h ? h->group : 0, g, h ? h->count : 0, first, d_k, n, d_out)) return e;      // before any device lookup
+    int rc = bn_get_ctx(ctx); if (rc) return rc;
+    if (h->device != ctx->device) return BN254_E_BAD_ARG;
+    return bn_dev_entry(ctx, stream, true, [&](hipStream_t s) -> int {
+        if (bn_msmp_bucket_route(ctx, g, n)) return bn_launch_msmp_bucket(ctx, h, first, d_k, n, d_out, s);
+        const size_t off[2] = {0, n}, V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2);
+        return bn_launch_msm(ctx, g, (const char *)h->pts + first * V, d_k, off, 1, d_out, s);
+    });
+}
+static int msmp_prepare_host(bn254_ctx *ctx, int g, const void *p, size_t n, int window_bits, void **out) {
+    if (int e = bn_msm_prepare_check(p, n, window_bits, out)) return e;          // before any device lookup
+    *out = nullptr;
+    const size_t V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2);
+    BnHost h(ctx); if (h.rc) return h.rc;
+    BnBuf &dp = ctx->stage[0];
+    int rc;
+    if ((rc = dp.reserve(n * V))) return rc;
+    if (n) HIP_TRY(hipMemcpyAsync(dp.p, p, n * V, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = bn_msmp_prepare_dev(ctx, g, dp.p, n, window_bits, out, ctx->stream))) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { bn254_msm_prepared_destroy(*out); *out = nullptr; return (int)e; }
+    return BN254_OK;
+}
+static int msmp_host(bn254_ctx *ctx, int g, const void *prep, size_t first, const bn_fr *k, size_t n, void *out) {
+    const bn254_msm_prepared *hp = (const bn254_msm_prepared *)prep;
+    if (int e = bn_msm_prepared_check(hp != nullptr, hp ? hp->group : 0, g, hp ? hp->count : 0, first, k, n, out)) return e;     // before any device lookup
+    const size_t V = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2);
+    BnHost h(ctx); if (h.rc) return h.rc;
+    return bn_staged(ctx, {k, n * sizeof(bn_fr)}, {nullptr, 0}, out, V, nullptr, 0,
+                     [&](const BnStaged &d) { return msmp_dev(ctx, g, prep, first, d.in[0], n, d.out, ctx->stream); });
+}
+
 // argument checks of bn254_pairing_product_batch_prepared_native* for m > 0 that need no device: the CSR rules, the handle, and - where the
 // indices are host memory - every index
 // (`indexed`: the pairs carry indices; `q_index`: those indices where the host can read them)
@@ -378,6 +527,34 @@ static int msm1_dev(bn254_ctx *ctx, int g, const void *d_p, const void *d_k, siz
 }
 int bn254_g1_msm_dev(bn254_ctx *c, const void *p, const void *k, size_t n, void *o, void *s) { return msm1_dev(c, 1, p, k, n, o, s); }
 int bn254_g2_msm_dev(bn254_ctx *c, const void *p, const void *k, size_t n, void *o, void *s) { return msm1_dev(c, 2, p, k, n, o, s); }
+int bn254_g1_msm_prepare_dev(bn254_ctx *ctx, const void *d_p, size_t n, int window_bits, void **out, void *stream) {
+    if (int e = bn_msm_prepare_check(d_p, n, window_bits, out)) return e;        // before any device lookup
+    return bn_msmp_prepare_dev(ctx, 1, d_p, n, window_bits, out, stream);
+}
+int bn254_g2_msm_prepare_dev(bn254_ctx *ctx, const void *d_p, size_t n, int window_bits, void **out, void *stream) {
+    if (int e = bn_msm_prepare_check(d_p, n, window_bits, out)) return e;        // before any device lookup
+    return bn_msmp_prepare_dev(ctx, 2, d_p, n, window_bits, out, stream);
+}
+void bn254_msm_prepared_destroy(void *prep) {
+    bn254_msm_prepared *h = (bn254_msm_prepared *)prep;
+    if (!h) return;
+    BnDeviceGuard dev_guard;
+    hipSetDevice(h->device);
+    bn_msmp_free(h);
+}
+size_t bn254_msm_prepared_count(const void *prep) { return prep ? ((const bn254_msm_prepared *)prep)->count : 0; }
+size_t bn254_msm_prepared_bytes(const void *prep) {
+    const bn254_msm_prepared *h = (const bn254_msm_prepared *)prep;
+    return h ? h->table_bytes + h->count * (h->group == 1 ? sizeof(bn_g1) : sizeof(bn_g2)) : 0;
+}
+int bn254_msm_prepared_group(const void *prep) { return prep ? ((const bn254_msm_prepared *)prep)->group : 0; }
+int bn254_msm_prepared_window_bits(const void *prep) { return prep ? (int)((const bn254_msm_prepared *)prep)->c : 0; }
+int bn254_g1_msm_prepared_dev(bn254_ctx *c, const void *prep, size_t first, const void *k, size_t n, void *o, void *s) { return msmp_dev(c, 1, prep, first, k, n, o, s); }
+int bn254_g2_msm_prepared_dev(bn254_ctx *c, const void *prep, size_t first, const void *k, size_t n, void *o, void *s) { return msmp_dev(c, 2, prep, first, k, n, o, s); }
+// internal (not in the header; tests and tools/time_msm_prepared.py): the default window width of a handle of n points and the default
+// crossover of a group
+unsigned bn254_msm_prepared_default_window_bits(size_t n) { return bn_msm_prepared_window_bits(n); }
+long bn254_msm_prepared_default_min(int g) { return g == 1 ? BN_MSMP_BUCKET_MIN_DEFAULT : BN_MSMP_BUCKET_MIN_DEFAULT_G2; }
 // order of the checks: empty batch, arguments, then context and device
 static int mul_base_dev(bn254_ctx *ctx, int g, const void *base, const void *d_k, void *d_out, size_t n, void *stream) {
     if (n == 0) return BN254_OK;
@@ -473,6 +650,20 @@ static int msm1_host(bn254_ctx *ctx, int g, const void *p, const bn_fr *k, size_
 }
 int bn254_g1_msm(bn254_ctx *ctx, const bn_g1 *p, const bn_fr *k, size_t n, bn_g1 *out) { return msm1_host(ctx, 1, p, k, n, out); }
 int bn254_g2_msm(bn254_ctx *ctx, const bn_g2 *p, const bn_fr *k, size_t n, bn_g2 *out) { return msm1_host(ctx, 2, p, k, n, out); }
+int bn254_g1_msm_prepare(bn254_ctx *ctx, const bn_g1 *p, size_t n, int window_bits, void **out) { return msmp_prepare_host(ctx, 1, p, n, window_bits, out); }
+int bn254_g2_msm_prepare(bn254_ctx *ctx, const bn_g2 *p, size_t n, int window_bits, void **out) { return msmp_prepare_host(ctx, 2, p, n, window_bits, out); }
+int bn254_g1_msm_prepared(bn254_ctx *ctx, const void *prep, size_t first, const bn_fr *k, size_t n, bn_g1 *out) { return msmp_host(ctx, 1, prep, first, k, n, out); }
+int bn254_g2_msm_prepared(bn254_ctx *ctx, const void *prep, size_t first, const bn_fr *k, size_t n, bn_g2 *out) { return msmp_host(ctx, 2, prep, first, k, n, out); }
+// (not bn_staged: one copy out of the handle's table, nothing staged)
+int bn254_msm_prepared_export(bn254_ctx *ctx, const void *prep, void *host_table, size_t bytes) {
+    const bn254_msm_prepared *hp = (const bn254_msm_prepared *)prep;
+    if (!hp || bytes != hp->table_bytes || (bytes && !host_table)) return BN254_E_BAD_ARG;
+    BnHost h(ctx); if (h.rc) return h.rc;
+    if (hp->device != ctx->device) return BN254_E_BAD_ARG;
+    if (bytes) HIP_TRY(hipMemcpyAsync(host_table, hp->table, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return BN254_OK;
+}
 static int mul_base_host(bn254_ctx *ctx, int g, const void *base, const bn_fr *k, void *out, size_t n) {
     if (n == 0) return BN254_OK;
     if (n > BN_N_MAX || !base || !k || !out) return BN254_E_BAD_ARG;              // before any device lookup

@@ -1,6 +1,6 @@
 // The per-lane bodies of the group kernels (bn254_kernels_mul.hip): point I/O, the 80-byte table record, the complete addition, the segmented
 // fold of bn254_g{1,2}_msm_batch, the accumulation levels and the reduction of the bucket method (bn254_g{1,2}_msm), the fixed-base chain
-// (bn254_g{1,2}_mul_base_batch), the shared-inversion normalisation (bn254_g{1,2}_normalize_batch) and the projective comparison
+// (bn254_g{1,2}_mul_base_batch), the table build and level 0 of the prepared bases (bn254_g{1,2}_msm_prepared), the shared-inversion normalisation (bn254_g{1,2}_normalize_batch) and the projective comparison
 // (bn254_g{1,2}_eq_batch).  Everything here is pure and takes plain pointers and a lane (G2: lane pair) index, so the host simulation
 // (tests/hostsim/hostsim.cpp) runs the very same bodies over host arrays; what needs a wave, a workgroup or a launch stays in the .hip.
 #pragma once
@@ -22,6 +22,12 @@ struct MsmAccArgs {          // one accumulation level of the bucket method (msm
 };
 struct MsmReduceArgs {       // the bucket reduction (msm_reduce_body)
     const uint32_t *buckets; uint32_t G, groups, log2B, count; uint32_t *terms;       // terms: S of every lane, then T of every lane
+};
+struct MsmAccPrepArgs {      // level 0 of the accumulation over a prepared table (msm_acc_prep_body)
+    const uint4 *table; const uint32_t *idx, *keys, *n0; uint32_t *out_pts, *out_keys, *buckets;
+};
+struct MsmPrepDoubleArgs {   // one window step of a prepared table's build (msm_prep_double_body)
+    uint32_t *pts; uint32_t c;
 };
 struct BaseMulArgs {         // the fixed-base chain (base_mul_body)
     const uint32_t *k; uint32_t *out; const uint4 *table; uint32_t c, W;
@@ -272,6 +278,91 @@ BN_FN void base_mul_body(const BaseMulArgs &g, uint32_t i, Tab tab, PointIo<F> i
         }
     }
     io(jac_normalize<F>(acc), g.out + (size_t)i * io.WORDS);
+}
+// ---- multi-scalar multiplication against prepared bases: bn254_g{1,2}_msm_prepare / bn254_g{1,2}_msm_prepared (bn254_seg.hip keeps the handle
+// and plans the launches).  The handle's table holds the AFFINE points 2^(c w) P_i for w < W = ceil(254 / c), entry (w, i) at index
+// w * count + i, as the records of the fixed-base tables (G2 two per entry, BaseTableMem reads them).  A scalar is recoded into the W signed
+// digits of base_mul_body; digit d != 0 of window w puts entry (w, i), y negated for d < 0, into bucket |d| - 1 - ONE set of 2^(c-1) buckets
+// for all windows, since the weights 2^(c w) are in the entries - and the sum is sum_b (b + 1) B_b.
+// Digit w of the recoding, low window first: returns |d| <= 2^(c-1), `neg` for d < 0; `carry` (0 before window 0) goes from window to
+// window: v > 2^(c-1) carries.  The top window of a scalar below r < 2^254 <= 2^(c W - 1) leaves no carry.
+BN_FN uint32_t msm_signed_digit(const uint32_t *raw, uint32_t w, uint32_t c, uint32_t &carry, bool &neg) {
+    const uint32_t half = 1u << (c - 1), v = msm_digit(raw, w, c) + carry;
+    carry = v > half ? 1u : 0u;
+    neg = carry != 0;
+    return carry ? 2u * half - v : v;
+}
+constexpr uint32_t MSM_NEG = 0x80000000u;         // index flag of a sorted entry: the table entry is subtracted
+// The build of a table, window by window: lane (G2: lane pair) i doubles the running Jacobian point i c times in place,
+// 2^(c w) P_i -> 2^(c (w + 1)) P_i (infinity stays infinity: z3 = 2 y z); the host normalises and repacks every window's points.
+template <class F>
+BN_FN void msm_prep_double_body(const MsmPrepDoubleArgs &g, uint32_t i, PointIo<F> io) {
+    uint32_t *w = g.pts + (size_t)i * io.WORDS;
+    Jac<F> p = io(w);
+#pragma unroll 1
+    for (uint32_t j = 0; j < g.c; ++j) p = jac_double(p);
+    io(p, w);
+}
+// Level 0 of the accumulation over a prepared table: the runs, slots and MSM_SKIP markers of msm_acc_body (N = *n0 entries in key order,
+// MSM_PIECE per lane), but entry j is ONE record - table entry idx[j] & ~MSM_NEG, subtracted when idx[j] & MSM_NEG - and joins its run by
+// the COMPLETE mixed addition: the same point twice in a bucket doubles, P and -P cancel, a flagged record (a base at infinity) is skipped.
+// A complete run joins its bucket by the full Jacobian addition; the pieces of longer runs are Jacobian entries of level 1, which is
+// msm_acc_body.  `tab`: where a lane finds a record (BaseTableMem; a simulated lane pair fetches both components).
+template <class F, class Tab>
+BN_FN void msm_acc_prep_body(const MsmAccPrepArgs &g, uint32_t i, Tab tab) {
+    constexpr uint32_t WORDS = PointIo<F>::WORDS;
+    const PointIo<F> io;
+    const uint32_t N = *g.n0, a = i * MSM_PIECE;
+    if (a >= N) return;
+    const uint32_t b = min(a + MSM_PIECE, N);
+    const uint32_t prev = a ? g.keys[a - 1] & ~MSM_SKIP : 0xffffffffu, next = b < N ? g.keys[b] & ~MSM_SKIP : 0xffffffffu;
+    g.out_keys[2 * i] = MSM_NONE; g.out_keys[2 * i + 1] = MSM_NONE;
+    Jac<F> acc = {F::zero(), F::one(), F::zero()};
+    bool acc_inf = true;
+    uint32_t cur = g.keys[a] & ~MSM_SKIP, j = a;
+    bool first_run = true;
+#pragma unroll 1
+    for (;;) {
+        // one step = at most one addition: an entry joins the run, or a complete run joins its bucket
+        const bool at_end = j >= b;
+        const uint32_t kj = at_end ? 0u : g.keys[j], key = kj & ~MSM_SKIP;
+        const bool flush = at_end || key != cur;
+        const uint32_t *src = nullptr;
+        uint32_t *dst = nullptr;
+        if (flush) {
+            const bool began_earlier = first_run && prev == cur, goes_on = at_end && next == cur;
+            if (cur != MSM_NONE) {
+                if (!began_earlier && !goes_on) { dst = g.buckets + (size_t)cur * WORDS; src = dst; }
+                else {
+                    const uint32_t slot = began_earlier ? 2 * i : 2 * i + 1;
+                    dst = g.out_pts + (size_t)slot * WORDS;
+                    g.out_keys[slot] = cur;
+                    if (began_earlier && goes_on) g.out_keys[2 * i + 1] = cur | MSM_SKIP;
+                }
+            }
+            if (src) {
+                const Jac<F> q = io(src);
+                acc = jac_add_flags<F>(acc, q, F::is_zero(acc.z), F::is_zero(q.z));
+            }
+            if (dst) io(acc, dst);
+        } else if (!(kj & MSM_SKIP) && key != MSM_NONE) {
+            const uint32_t e = g.idx[j];
+            const bool neg = (e & MSM_NEG) != 0;
+            bool e_inf;
+            const Aff<F> q = tab.get(e & ~MSM_NEG, e_inf);
+            if constexpr (std::is_same<F, FqField>::value) {
+                acc = jac_madd_signed(acc, q, neg, acc_inf, e_inf);
+            } else {
+                Aff<F> qs = q;
+                qs.y = F::select(neg, q.y, F::template lc3<-1, 0, 0>(q.y, q.y, q.y));
+                acc = jac_madd_flags<F>(acc, qs, acc_inf, e_inf);
+                acc_inf = F::is_zero_std(acc.z);
+            }
+        }
+        if (at_end) break;
+        if (flush) { first_run = false; acc = {F::zero(), F::one(), F::zero()}; acc_inf = true; cur = key; }
+        else ++j;
+    }
 }
 // ---- normalisation of bn254_g{1,2}_normalize_batch: out[i] = (x / z^2, y / z^3, 1), the point at infinity (z == 0, whatever x and y hold)
 // as G::zero() = (0, 1, 0) - jac_normalize (curve.hpp) with ONE inversion per run of points (Montgomery's trick) instead of one per point.

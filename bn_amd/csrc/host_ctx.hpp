@@ -121,6 +121,9 @@ struct bn254_ctx {
     BnBuf msm_scal;                     // ... and the tail's scalars (Montgomery images of 2^(c w) and base * 2^(c w)) for window width msm_scal_c
     std::vector<uint64_t> msm_scal_host;    // their host image (kept while the copy may be in flight; rebuilt only when the width changes)
     long msm_scal_c = -1;
+    BnBuf msmp_scal;                    // bn254_g{1,2}_msm_prepared: the tail's scalars (base + 1 and 1) for window width msmp_scal_c, kept like msm_scal
+    std::vector<uint64_t> msmp_scal_host;
+    long msmp_scal_c = -1;
     BnBaseCache base_cache[2];          // bn254_g{1,2}_mul_base_batch: [0] G1, [1] G2
     BnBuf norm_prefix;                  // bn254_g{1,2}_normalize_batch: the prefix products of one sub-launch (48 / 96 bytes per point)
     BnBuf fr_prefix;                    // bn254_fr_inverse_batch: the prefix products of one sub-launch (32 bytes per element)
@@ -166,6 +169,23 @@ struct bn254_g2_prepared {
     void *q = nullptr;
     size_t small_max = 0;
 };
+
+// bn254_g{1,2}_msm_prepare: the affine multiples 2^(c w) P_i of `count` points (entry (w, i) at index w * count + i, the records of
+// group_ops.hpp) and the normalised points themselves, in device memory.  Behind the header's `void *`.
+struct bn254_msm_prepared {
+    int device = 0;
+    int group = 0;                      // 1 or 2
+    unsigned c = 0, W = 0;              // window width, windows
+    size_t count = 0;
+    void *table = nullptr;              // W * count entries
+    void *pts = nullptr;                // count points of 96 / 192 bytes: the small route's
+    size_t table_bytes = 0;
+};
+// terms from which bn254_g{1,2}_msm_prepared take their bucket route while BN254_OPT_MSM_BUCKET_MIN is not set: the smallest measured size
+// from which the route's [min, max] of kernel time lies wholly below the small route's at that size and at every larger one
+// (tools/time_msm_prepared.py --crossover, profiles/r29_msm_prepared.txt, every power of two from 2^10 to 2^20 at the default width:
+// G1 bucket / small 1.08 at 2^18, 0.72 at 2^19, 0.54 at 2^20; G2 1.00 at 2^17 - the two ranges overlap -, 0.66 at 2^18, 0.35 at 2^20)
+constexpr long BN_MSMP_BUCKET_MIN_DEFAULT = (long)1 << 19, BN_MSMP_BUCKET_MIN_DEFAULT_G2 = (long)1 << 18;
 
 // lease of pipeline slots for one host-buffer call (see bn254_ctx::slot_busy)
 struct BnSlotLease {
@@ -368,6 +388,10 @@ unsigned bn254_msm_piece_M(void);
 int bn254_launch_msm_bucket_M(int g, const void *pts, const void *idx, const void *keys, const void *n0, unsigned level, void *out_pts, void *out_keys, void *buckets,
                               size_t lanes, hipStream_t s);
 int bn254_launch_msm_reduce_M(int g, const void *buckets, unsigned G, unsigned groups, unsigned c, size_t count, void *terms, hipStream_t s);
+int bn254_launch_msmp_digits_M(const void *k, size_t n, unsigned c, unsigned W, size_t count, size_t first, void *counts, void *idx, void *keys, int scatter, hipStream_t s);
+int bn254_launch_msmp_bucket_M(int g, const void *table, const void *idx, const void *keys, const void *n0, void *out_pts, void *out_keys, void *buckets, size_t lanes, hipStream_t s);
+int bn254_launch_msmp_double_M(int g, void *d_pts, unsigned c, size_t n, hipStream_t s);
+size_t bn254_msmp_entry_bytes_M(int g);
 size_t bn254_mul_base_table_bytes_M(int g, unsigned c);
 int bn254_launch_mul_base_M(int g, const void *table, unsigned c, const void *k, void *out, size_t n, hipStream_t s);
 int bn254_launch_mul_base_tile_M(int g, const void *d_base, void *d_out, size_t n, hipStream_t s);

@@ -231,6 +231,71 @@ inline void msm_tail_scalars(unsigned cb, std::vector<uint64_t> &h) {
     }
 }
 
+// ---- multi-scalar multiplication against prepared bases (bn254_g{1,2}_msm_prepare / bn254_g{1,2}_msm_prepared): the handle's table holds the
+// affine points 2^(c w) P_i, so every (term, window) pair falls into ONE set of 2^(c-1) buckets by its signed digit, bucket b weighs b + 1
+inline unsigned bn_msm_prepared_windows(unsigned cb) { return (254 + cb - 1) / cb; }
+// Window width of a handle of n points when the caller passes 0: the width with the smallest median kernel time of the sweep over
+// c = 10 .. 16 (tools/time_msm_prepared.py --widths, profiles/r29_msm_prepared.txt: G1 2^16 / 2^18 / 2^20 / 2^22 and G2 2^15 / 2^18 / 2^20), a
+// size in between or outside taking the width of the nearest measured one.  The table has ONE entry: 16 won at all seven sizes, for both
+// groups (G1 2^20: 7.27 ms against 7.41 at 15 and 7.59 at 14; G2 2^20: 11.53 against 12.04 and 12.57) - the counting sort's atomics meet in
+// 2^(c-1) counters for ALL windows, so its time falls with every bit (G1 2^20: 18.3 ms at c = 10, 2.1 ms at 16), and 16 has the fewest
+// windows, hence the fewest entries and the smallest table.  Total on every n.
+inline unsigned bn_msm_prepared_window_bits(size_t n) {
+    (void)n;
+    return 16;
+}
+// what bn254_g{1,2}_msm_prepare* can refuse without a device: window_bits is 0 (default) or 3 .. 16 (c W > 254 rules out 1 and 2: the top
+// window must not carry); a table index w * count + i must leave bit 31 to the sign
+inline int bn_msm_prepare_check(const void *p, size_t n, int window_bits, const void *out) {
+    if (!out || (n && !p) || n > BN_N_MAX) return BN254_E_BAD_ARG;
+    if (window_bits != 0 && (window_bits < 3 || window_bits > 16)) return BN254_E_BAD_ARG;
+    const unsigned cb = window_bits ? (unsigned)window_bits : bn_msm_prepared_window_bits(n);
+    return (unsigned __int128)bn_msm_prepared_windows(cb) * n >= ((unsigned __int128)1 << 31) ? BN254_E_BAD_ARG : BN254_OK;
+}
+// ... and a call over a handle of `count` points of group `group`: the range [first, first + n) lies in the handle
+inline int bn_msm_prepared_check(bool have_handle, int group, int g, size_t count, size_t first, const void *k, size_t n, const void *out) {
+    if (!have_handle || group != g || !out || (n && !k)) return BN254_E_BAD_ARG;
+    return first > count || n > count - first ? BN254_E_BAD_ARG : BN254_OK;
+}
+// The workspace of a call with cb-bit windows over chunks of at most `chunk` terms: msm_bucket_plan's layout with ONE window of
+// K = 2^(cb-1) buckets for the reduction (count = groups lanes, 2 * count tail terms) and up to W * chunk sorted entries per chunk.
+inline MsmBucketPlan msm_prepared_plan(unsigned cb, size_t chunk, size_t V, size_t L) {
+    MsmBucketPlan p;
+    p.W = bn_msm_prepared_windows(cb);
+    p.K = (size_t)1 << (cb - 1);
+    p.G = (unsigned)std::min<size_t>(BN_MSM_GROUP, p.K); p.groups = (unsigned)(p.K / p.G);
+    p.count = p.groups;
+    p.n0max = (size_t)p.W * chunk;                 // < 86 * 2^22 < 2^32: positions are 32-bit
+    for (size_t N = p.n0max;;) {
+        const size_t M = 2 * ((N + L - 1) / L);
+        p.out_slots.push_back(M);
+        if (N <= L) break;
+        N = M;
+    }
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += bn_align256(bytes); return o; };
+    p.o_counts = take(p.K * 4); p.o_tiles = take(1024 * 4); p.o_n0 = take(4); p.o_idx = take(p.n0max * 4); p.o_keys = take(p.n0max * 4); p.o_buckets = take(p.K * V);
+    for (size_t M : p.out_slots) { const size_t a = take(M * V), b = take(M * 4); p.o_level.push_back({a, b}); }
+    p.o_terms = take(2 * p.count * V);
+    p.bytes = at;
+    return p;
+}
+// the scalars of the tail's 2 * groups terms as Montgomery images: base + 1 for the S term of the group whose first bucket is `base`
+// (bucket b weighs b + 1), then 1 for every T term
+inline void msm_prepared_tail_scalars(unsigned cb, std::vector<uint64_t> &h) {
+    const size_t K = (size_t)1 << (cb - 1), G = std::min<size_t>(BN_MSM_GROUP, K), groups = K / G;
+    h.assign(2 * groups * 4, 0);
+    bn_fr one; bn_fr_one(&one);
+    uint64_t step[4] = {0, 0, 0, 0}, acc[4];
+    memcpy(acc, one.l, sizeof acc);
+    for (size_t b = 0; b < G; ++b) bn_fr_add(step, one.l, step);                           // G
+    for (size_t q = 0; q < groups; ++q) {
+        memcpy(&h[q * 4], acc, sizeof acc);
+        memcpy(&h[(groups + q) * 4], one.l, sizeof acc);
+        bn_fr_add(acc, step, acc);
+    }
+}
+
 // ---- fixed-base scalar multiplication (bn254_g{1,2}_mul_base_batch): the table of a base for signed c-bit windows holds d * 2^(c w) * B for
 // w < W = ceil(254 / c) and d = 1 .. 2^(c-1), entry (w, d) at index w * 2^(c-1) + d - 1
 inline unsigned bn_base_windows(unsigned cb) { return (254 + cb - 1) / cb; }

@@ -668,6 +668,39 @@ class Engine:
         _native.check(self._lib.bn254_g2_msm(self._h, _p(p), _p(k), p.shape[0], _p(out)))
         return out
 
+    # ---- multi-scalar multiplication against prepared bases (include/bn254_hip.h bn254_g1_msm_prepare ...)
+    def _msm_prepare(self, g, points, window_bits):
+        words = G1_WORDS if g == 1 else G2_WORDS
+        p = _arr(points, words) if len(points) else np.zeros((0, words), np.uint64)
+        h = C.c_void_p()
+        fn = self._lib.bn254_g1_msm_prepare if g == 1 else self._lib.bn254_g2_msm_prepare
+        _native.check(fn(self._h, _p(p) if p.shape[0] else None, p.shape[0], 0 if window_bits is None else int(window_bits), C.byref(h)))
+        return PreparedMSM(self, h)
+
+    def g1_msm_prepare(self, points, window_bits=None):
+        """(n,12) raw G1 points (any z) -> PreparedMSM: the affine multiples 2^(c w) P_i of every window in device memory, for many
+        g1_msm_prepared calls against the same points.  window_bits: None for the default of the size, or 3 .. 16"""
+        return self._msm_prepare(1, points, window_bits)
+
+    def g2_msm_prepare(self, points, window_bits=None):
+        """the same over (n,24) G2 points"""
+        return self._msm_prepare(2, points, window_bits)
+
+    def _msm_prepared(self, g, prep, k, first):
+        k = _arr(k, 4) if len(k) else np.zeros((0, 4), np.uint64)
+        out = np.empty(G1_WORDS if g == 1 else G2_WORDS, np.uint64)
+        fn = self._lib.bn254_g1_msm_prepared if g == 1 else self._lib.bn254_g2_msm_prepared
+        _native.check(fn(self._h, prep._h, int(first), _p(k) if k.shape[0] else None, k.shape[0], _p(out)))
+        return out
+
+    def g1_msm_prepared(self, prep, k, first=0):
+        """normalize(sum of P[first + i] * k[i]) over the points of `prep` -> (12,) uint64: the bytes of g1_msm on those points and scalars"""
+        return self._msm_prepared(1, prep, k, first)
+
+    def g2_msm_prepared(self, prep, k, first=0):
+        """the same over a G2 handle -> (24,) uint64"""
+        return self._msm_prepared(2, prep, k, first)
+
     def g1_add_batch(self, a, b, negate_b=False):
         """a + b (a - b): the reference's Jacobian limbs (groups/mod.rs:275-347)"""
         a = _arr(a, G1_WORDS); b = _arr(b, G1_WORDS); _same_len(a, b); out = np.empty_like(a)
@@ -1254,6 +1287,24 @@ class Engine:
     def g2_msm_dev(self, d_p, d_k, n, d_out, stream=0):
         _native.check(self._lib.bn254_g2_msm_dev(self._h, d_p, d_k, n, d_out, stream))
 
+    def g1_msm_prepare_dev(self, d_p, n, window_bits=None, stream=0):
+        """device pointer to n raw G1 points -> PreparedMSM; the build is ordered on `stream`"""
+        h = C.c_void_p()
+        _native.check(self._lib.bn254_g1_msm_prepare_dev(self._h, d_p, n, 0 if window_bits is None else int(window_bits), C.byref(h), stream))
+        return PreparedMSM(self, h)
+
+    def g2_msm_prepare_dev(self, d_p, n, window_bits=None, stream=0):
+        h = C.c_void_p()
+        _native.check(self._lib.bn254_g2_msm_prepare_dev(self._h, d_p, n, 0 if window_bits is None else int(window_bits), C.byref(h), stream))
+        return PreparedMSM(self, h)
+
+    def g1_msm_prepared_dev(self, prep, first, d_k, n, d_out, stream=0):
+        """device pointers k (n scalars) and out (ONE point) against points [first, first + n) of `prep`, ordered on `stream`"""
+        _native.check(self._lib.bn254_g1_msm_prepared_dev(self._h, prep._h, int(first), d_k, n, d_out, stream))
+
+    def g2_msm_prepared_dev(self, prep, first, d_k, n, d_out, stream=0):
+        _native.check(self._lib.bn254_g2_msm_prepared_dev(self._h, prep._h, int(first), d_k, n, d_out, stream))
+
     def gt_mul_dev(self, d_a, d_b, d_out, n, stream=0):
         _native.check(self._lib.bn254_gt_mul_batch_dev(self._h, d_a, d_b, d_out, n, stream))
 
@@ -1327,6 +1378,71 @@ class PreparedG2:
     def close(self):
         if getattr(self, "_p", None) and getattr(self._eng, "_ctx", None):
             self._eng._lib.bn254_g2_prepared_destroy(self._p)
+        self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PreparedMSM:
+    """opaque handle of bn254_g{1,2}_msm_prepare: the affine multiples 2^(c w) P_i of `count` points of G1 or G2 in device memory"""
+
+    def __init__(self, engine, handle):
+        self._eng = engine
+        self._p = handle
+
+    @property
+    def _h(self):
+        if self._p is None:
+            raise _native.Bn254Error("this PreparedMSM is closed")
+        return self._p
+
+    @property
+    def count(self):
+        h = self._h
+        return int(self._eng._lib.bn254_msm_prepared_count(h))
+
+    @property
+    def group(self):
+        h = self._h
+        return int(self._eng._lib.bn254_msm_prepared_group(h))
+
+    @property
+    def window_bits(self):
+        h = self._h
+        return int(self._eng._lib.bn254_msm_prepared_window_bits(h))
+
+    @property
+    def windows(self):
+        c = self.window_bits
+        return (254 + c - 1) // c
+
+    @property
+    def device_bytes(self):
+        h = self._h
+        return int(self._eng._lib.bn254_msm_prepared_bytes(h))
+
+    def export(self):
+        """the table as (windows, count, group, 20) uint32: entry (w, i) is one 80-byte record per component - 9 + 9 limbs of (x, y), the
+        flag word (not zero: the point at infinity), a zero word - for tests"""
+        out = np.empty((self.windows, self.count, self.group, 20), np.uint32)
+        _native.check(self._eng._lib.bn254_msm_prepared_export(self._eng._h, self._h, _p(out) if out.size else None, out.nbytes))
+        return out
+
+    def msm(self, scalars, first=0):
+        """normalize(sum of P[first + i] * scalars[i]) -> G1 or G2; scalars: a sequence of Fr or an (n,4) uint64 array"""
+        from . import api
+        k = api._scalar_array(scalars)
+        if self.group == 1:
+            return api.G1(self._eng.g1_msm_prepared(self, k, first))
+        return api.G2(self._eng.g2_msm_prepared(self, k, first))
+
+    def close(self):
+        if getattr(self, "_p", None) and getattr(self._eng, "_ctx", None):
+            self._eng._lib.bn254_msm_prepared_destroy(self._p)
         self._p = None
 
     def __del__(self):

@@ -280,6 +280,26 @@ def setup(r1cs, rng, engine=None):
     return pk, vk
 
 
+PreparedProvingKey = collections.namedtuple("PreparedProvingKey", ProvingKey._fields + ("prepared",))
+PreparedProvingKey.__doc__ = """a ProvingKey and `prepared`: the PreparedMSM handles of its five queries, a dict with the keys a_query,
+b_g1_query, l_query, h_query (G1) and b_g2_query (G2).  prove() takes it wherever it takes the plain key and returns the same proof."""
+
+
+def prepare_proving_key(pk, window_bits=None, engine=None):
+    """ProvingKey -> PreparedProvingKey: the five queries go to the device once (Engine.g1_msm_prepare / g2_msm_prepare); every later
+    prove() sends the scalars only.  The prepared key is used with the engine that prepared it."""
+    e = engine or default_engine()
+    prepared = {name: e.g1_msm_prepare(getattr(pk, name), window_bits) for name in ("a_query", "b_g1_query", "l_query", "h_query")}
+    prepared["b_g2_query"] = e.g2_msm_prepare(pk.b_g2_query, window_bits)
+    return PreparedProvingKey(*pk[:len(ProvingKey._fields)], prepared)
+
+
+def _prepared_sums(e, prepared, Z, l, H):
+    """the five sums of prove() against the handles of a prepared key: (sum_a, sum_b1, sum_l, sum_h, sum_b2)"""
+    return (e.g1_msm_prepared(prepared["a_query"], Z), e.g1_msm_prepared(prepared["b_g1_query"], Z), e.g1_msm_prepared(prepared["l_query"], Z[l + 1:]),
+            e.g1_msm_prepared(prepared["h_query"], H), e.g2_msm_prepared(prepared["b_g2_query"], Z))
+
+
 def prove(pk, r1cs, z, rng, engine=None):
     """The proof (A: G1, B: G2, C: G1) that the prover knows an assignment z = (1, public_1 .. public_l, private ...) of the system, for the
     keys of setup(); verify_batch(vk, [proof], [z[1:l + 1]]) accepts it.  With h = poly.quotient(*witness_map(r1cs, z)) and r, s drawn from
@@ -287,7 +307,7 @@ def prove(pk, r1cs, z, rng, engine=None):
         A = alpha + sum z_i a_query_i + r delta
         B = beta + sum z_i b_g2_query_i + s delta                          (in G2; the same sum in G1 is B1)
         C = sum_{i>l} z_i l_query_i + sum_k h_k h_query_k + s A + r B1 - r s delta
-    The five sums are multi-scalar multiplications, four in G1 and one in G2; what remains - a handful of terms per output - is one segmented
+    The five sums are multi-scalar multiplications, four in G1 and one in G2 (pk may be a PreparedProvingKey: they then run against its handles); what remains - a handful of terms per output - is one segmented
     multi-scalar multiplication per group.  It is NOT checked that z satisfies the system: an assignment that does not yields a proof that
     does not verify (the quotient is then the quotient of nothing).  ValueError, before any device call, when len(z) != num_variables or
     z[0] != 1."""
@@ -298,9 +318,12 @@ def prove(pk, r1cs, z, rng, engine=None):
     h = poly.quotient(a_evals, b_evals, c_evals, engine=e)
     H = np.stack([x.limbs for x in h[:-1]])
     r, s = _draw(rng), _draw(rng)
-    sum_a, sum_b1 = e.g1_msm(pk.a_query, Z), e.g1_msm(pk.b_g1_query, Z)
-    sum_l, sum_h = e.g1_msm(pk.l_query, Z[l + 1:]), e.g1_msm(pk.h_query, H)
-    sum_b2 = e.g2_msm(pk.b_g2_query, Z)
+    if getattr(pk, "prepared", None) is not None:
+        sum_a, sum_b1, sum_l, sum_h, sum_b2 = _prepared_sums(e, pk.prepared, Z, l, H)
+    else:
+        sum_a, sum_b1 = e.g1_msm(pk.a_query, Z), e.g1_msm(pk.b_g1_query, Z)
+        sum_l, sum_h = e.g1_msm(pk.l_query, Z[l + 1:]), e.g1_msm(pk.h_query, H)
+        sum_b2 = e.g2_msm(pk.b_g2_query, Z)
     # s A + r B1 - r s delta = s alpha + s sum_a + r beta + r sum_b1 + r s delta
     points = np.stack([pk.alpha_g1.limbs, sum_a, pk.delta_g1.limbs,
                        sum_l, sum_h, pk.alpha_g1.limbs, sum_a, pk.beta_g1.limbs, sum_b1, pk.delta_g1.limbs])

@@ -11,7 +11,9 @@ A random linear combination of the checks into one multi-pairing is not built.
 Over the transforms on G1 (bn254_g1_ntt_batch), none of which needs tau:
     lagrange_srs    the points L_j(tau) G of the domain {w^j}: one inverse transform of the powers
     commit_evals    C from the n evaluations of p over the domain: one multi-scalar multiplication against those points
-    open_all        every opening of p over the domain (FK20): three transforms over G1, two over Fr, one batched multiplication"""
+    open_all        every opening of p over the domain (FK20): three transforms over G1, two over Fr, one batched multiplication
+prepare(srs) / prepare(lsrs) take the points of a reference string once (Engine.g1_msm_prepare); commit, open and commit_evals accept the
+prepared string wherever they accept the plain one and return the same bytes."""
 import collections
 
 import numpy as np
@@ -42,6 +44,28 @@ def setup(n, rng, engine=None):
     return SRS(g1, G2(g2[0]), G2(g2[1]))
 
 
+PreparedSRS = collections.namedtuple("PreparedSRS", "g1_powers g2_one tau_g2 prepared")
+PreparedSRS.__doc__ = "an SRS and `prepared`, the PreparedMSM of its g1_powers: commit and open run their multi-scalar multiplications against it"
+PreparedLagrangeSRS = collections.namedtuple("PreparedLagrangeSRS", "g1_lagrange log_n g2_one tau_g2 prepared")
+PreparedLagrangeSRS.__doc__ = "a LagrangeSRS and `prepared`, the PreparedMSM of its g1_lagrange: commit_evals runs against it"
+
+
+def prepare(srs, window_bits=None, engine=None):
+    """SRS -> PreparedSRS, LagrangeSRS -> PreparedLagrangeSRS: the points of the string go to the device once, as the affine multiples of
+    every window (Engine.g1_msm_prepare); every later commit / open / commit_evals sends the scalars only.  The prepared string is used
+    with the engine that prepared it."""
+    e = engine or default_engine()
+    if hasattr(srs, "g1_lagrange"):
+        return PreparedLagrangeSRS(srs.g1_lagrange, srs.log_n, srs.g2_one, srs.tau_g2, e.g1_msm_prepare(srs.g1_lagrange, window_bits))
+    return PreparedSRS(srs.g1_powers, srs.g2_one, srs.tau_g2, e.g1_msm_prepare(srs.g1_powers, window_bits))
+
+
+def _msm(e, srs, points, k):
+    """normalize(sum points[i] * k[i]) over the first len(k) points of the string: against the handle of a prepared string"""
+    prep = getattr(srs, "prepared", None)
+    return e.g1_msm_prepared(prep, k, 0) if prep is not None else e.g1_msm(points[:k.shape[0]], k)
+
+
 def _coefficients(srs, p):
     P = _scalar_array(p)
     if P.shape[0] > srs.g1_powers.shape[0]:
@@ -55,7 +79,7 @@ def commit(srs, p, engine=None):
     P = _coefficients(srs, p)
     if P.shape[0] == 0:
         return G1.zero()
-    return G1((engine or default_engine()).g1_msm(srs.g1_powers[:P.shape[0]], P))
+    return G1(_msm(engine or default_engine(), srs, srs.g1_powers, P))
 
 
 def open(srs, p, z, engine=None):
@@ -69,7 +93,7 @@ def open(srs, p, z, engine=None):
     y = Fr.from_limbs(out[0])
     if P.shape[0] == 1:
         return y, G1.zero()
-    return y, G1(e.g1_msm(srs.g1_powers[:P.shape[0] - 1], out[1:]))
+    return y, G1(_msm(e, srs, srs.g1_powers, out[1:]))
 
 
 LagrangeSRS = collections.namedtuple("LagrangeSRS", "g1_lagrange log_n g2_one tau_g2")
@@ -92,7 +116,7 @@ def commit_evals(lsrs, evals, engine=None):
     E = _scalar_array(evals)
     if E.shape[0] != lsrs.g1_lagrange.shape[0]:
         raise ValueError(f"{E.shape[0]} evaluations against a Lagrange basis of {lsrs.g1_lagrange.shape[0]} points")
-    return G1((engine or default_engine()).g1_msm(lsrs.g1_lagrange, E))
+    return G1(_msm(engine or default_engine(), lsrs, lsrs.g1_lagrange, E))
 
 
 def open_all(srs, p, log_n, engine=None):

@@ -49,6 +49,16 @@ def setup(nv, rng, engine=None):
     return SRS(nv, g1, G2(g2[0]), [G2(q) for q in g2[1:]])
 
 
+PreparedSRS = collections.namedtuple("PreparedSRS", "nv g1_levels g2_one tau_g2 prepared")
+PreparedSRS.__doc__ = "an SRS and `prepared`, the PreparedMSM of its g1_levels: commit runs level m as the range from 2^m of that handle"
+
+
+def prepare(srs, window_bits=None, engine=None):
+    """SRS -> PreparedSRS: the levels go to the device once (Engine.g1_msm_prepare); commit accepts either and returns the same bytes.
+    The prepared string is used with the engine that prepared it."""
+    return PreparedSRS(srs.nv, srs.g1_levels, srs.g2_one, srs.tau_g2, (engine or default_engine()).g1_msm_prepare(srs.g1_levels, window_bits))
+
+
 def _table(srs, table):
     """(the (2^m, 4) array, m)"""
     T = _scalar_array(table)
@@ -64,7 +74,11 @@ def commit(srs, table, engine=None):
     """C = f(tau) G -> G1 for the multilinear f with these 2^m values (Fr values or an (n,4) uint64 array), m <= nv: one multi-scalar
     multiplication against level m of the reference string.  ValueError for a length that is not a power of two or is too long."""
     T, m = _table(srs, table)
-    return G1((engine or default_engine()).g1_msm(srs.g1_levels[1 << m:2 << m], T))
+    e = engine or default_engine()
+    prep = getattr(srs, "prepared", None)
+    if prep is not None:
+        return G1(e.g1_msm_prepared(prep, T, first=1 << m))
+    return G1(e.g1_msm(srs.g1_levels[1 << m:2 << m], T))
 
 
 def open(srs, table, point, engine=None):

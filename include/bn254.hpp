@@ -556,6 +556,50 @@ public:
     }
 };
 
+// Points prepared ONCE for many multi-scalar multiplications (a proving key, an SRS): the handle keeps the affine multiples 2^(c w) P_i in
+// device memory.  msm(k, first) == bn::g1_msm / bn::g2_msm over the points [first, first + k.size()) - the same bytes.
+// window_bits: 0 for the default of the size, or 3 .. 16.
+template <class G>
+class PreparedMsm {
+    static constexpr bool IS_G1 = sizeof(G) == sizeof(bn_g1);
+    void *h_ = nullptr;
+public:
+    explicit PreparedMsm(const std::vector<G> &p, int window_bits = 0) {
+        if constexpr (IS_G1) check(bn254_g1_msm_prepare(nullptr, reinterpret_cast<const bn_g1 *>(p.data()), p.size(), window_bits, &h_));
+        else check(bn254_g2_msm_prepare(nullptr, reinterpret_cast<const bn_g2 *>(p.data()), p.size(), window_bits, &h_));
+    }
+    ~PreparedMsm() { bn254_msm_prepared_destroy(h_); }
+    PreparedMsm(const PreparedMsm &) = delete;
+    PreparedMsm &operator=(const PreparedMsm &) = delete;
+    size_t size() const { return bn254_msm_prepared_count(h_); }
+    size_t device_bytes() const { return bn254_msm_prepared_bytes(h_); }
+    int group() const { return bn254_msm_prepared_group(h_); }
+    int window_bits() const { return bn254_msm_prepared_window_bits(h_); }
+    G msm(const std::vector<Fr> &k, size_t first = 0) const {
+        G out;
+        if constexpr (IS_G1) check(bn254_g1_msm_prepared(nullptr, h_, first, reinterpret_cast<const bn_fr *>(k.data()), k.size(), reinterpret_cast<bn_g1 *>(&out)));
+        else check(bn254_g2_msm_prepared(nullptr, h_, first, reinterpret_cast<const bn_fr *>(k.data()), k.size(), reinterpret_cast<bn_g2 *>(&out)));
+        return out;
+    }
+    // device-resident forms, asynchronous on `stream` (bn254_g{1,2}_msm_prepared_dev)
+    void msm_dev(size_t first, const void *d_k, size_t n, void *d_out, void *stream = nullptr) const {
+        check(IS_G1 ? bn254_g1_msm_prepared_dev(nullptr, h_, first, d_k, n, d_out, stream) : bn254_g2_msm_prepared_dev(nullptr, h_, first, d_k, n, d_out, stream));
+    }
+    static void *prepare_dev(const void *d_p, size_t n, int window_bits = 0, void *stream = nullptr) {
+        void *h = nullptr;
+        check(IS_G1 ? bn254_g1_msm_prepare_dev(nullptr, d_p, n, window_bits, &h, stream) : bn254_g2_msm_prepare_dev(nullptr, d_p, n, window_bits, &h, stream));
+        return h;
+    }
+    // the table as W * size() entries of 80 (G1) / 160 (G2) bytes, for tests
+    std::vector<unsigned char> export_table() const {
+        std::vector<unsigned char> t((size_t)((254 + window_bits() - 1) / window_bits()) * size() * (IS_G1 ? 80 : 160));
+        check(bn254_msm_prepared_export(nullptr, h_, t.data(), t.size()));
+        return t;
+    }
+};
+typedef PreparedMsm<G1> PreparedMsmG1;
+typedef PreparedMsm<G2> PreparedMsmG2;
+
 // tunables of the default context (BN254_OPT_* of bn254_hip.h; value < 0 restores the default derived from the device)
 inline void set_option(int key, long value) { check(bn254_ctx_set_option(nullptr, key, value)); }
 inline long get_option(int key) { long v = 0; check(bn254_ctx_get_option(nullptr, key, &v)); return v; }

@@ -167,6 +167,9 @@
  *     bn254_g{1,2}_msm_dev keeps (sorted indices, counts, buckets, partial sums, tail terms).  bn254_g{1,2}_msm_dev plans its launches from
  *     upper bounds and reads nothing back; it synchronises the caller's stream only in a call that changes the window width (the tail's
  *     scalars are rebuilt and uploaded then), and briefly on the upload of the tail's work list like bn254_g{1,2}_msm_batch_dev.
+ *     bn254_g{1,2}_msm_prepared_dev is bn254_g{1,2}_msm_dev in all of this (the same workspace, its own tail scalars per window width); the
+ *     handle it reads is not scratch: it must outlive the work enqueued against it.  bn254_g{1,2}_msm_prepare_dev builds in the context's
+ *     workspace under the same ordering.  The host-buffer forms serialise on the context (its mutex for the call).
      The fixed-base tables of bn254_g{1,2}_mul_base_batch_dev are context-owned scratch of the same kind: a table is looked up, built and read
      under the same event ordering, so a slot is never rebuilt while a launch on another stream may still read it.  The call reads its HOST
      `base` before it returns (compared with the cached keys; copied to pinned staging on a miss).  It waits on the host only for the copy of
@@ -1086,6 +1089,35 @@ int bn254_g2_msm_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, con
    count is read back; the call synchronises `stream` only when it changes the window width (see Threading above) */
 int bn254_g1_msm_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, size_t n, void *d_out, void *stream);
 int bn254_g2_msm_dev(bn254_ctx *ctx, const void *d_p, const void *d_k, size_t n, void *d_out, void *stream);
+/* ---- multi-scalar multiplication against PREPARED bases: a prover multiplies fresh scalars against the same points, proof after proof (a
+   proving key, an SRS).  bn254_g{1,2}_msm_prepare takes n raw points (any z; z == 0 is infinity) once and returns a handle that owns, in
+   device memory, the affine multiples 2^(c w) P_i for w < W = ceil(254 / c) - entry (w, i) at index w * n + i, one 80-byte record for G1
+   (9 + 9 limbs of x and y, a flag word that is not zero for the point at infinity, a zero word) and two for G2 (component c0, then c1) -
+   and the n normalised points.  window_bits: 0 for the default of the size, or 3 .. 16.  A handle of zero points is legal.
+   bn254_g{1,2}_msm_prepared: out[0] = normalize(sum over i < n of P[first + i] * k[i]) - THE BYTES bn254_g{1,2}_msm returns for the same
+   points and scalars; n == 0 gives G::zero() = (0, 1, 0).  Below the crossover (BN254_OPT_MSM_BUCKET_MIN when it is set - 0 forces the
+   bucket route -, else this route's own default per group) the call is the one-segment bn254_g{1,2}_msm_batch on the handle's points; from
+   there on every (term, window) pair falls into ONE set of 2^(c-1) buckets by its signed digit, level 0 of the accumulation is a mixed
+   addition from a record, and the reduction and its tail shrink by 2 W against bn254_g{1,2}_msm.  Chunks of BN254_OPT_MSM_CHUNK terms.
+   BN254_E_BAD_ARG, before any device work and whatever `ctx` is: NULL pointers with n > 0 (out: always), first + n > count, a handle of
+   the other group, window_bits out of range, W * n >= 2^31.  The handle is a plain pointer here; its layout is private to the library.
+   The _dev forms take device-resident points / scalars / out and are asynchronous on `stream` like bn254_g{1,2}_msm_dev (prepare_dev
+   allocates the handle's memory, which synchronises with the device).  A handle belongs to the device of the context that made it. */
+int bn254_g1_msm_prepare(bn254_ctx *ctx, const bn_g1 *p, size_t n, int window_bits, void **out);
+int bn254_g2_msm_prepare(bn254_ctx *ctx, const bn_g2 *p, size_t n, int window_bits, void **out);
+int bn254_g1_msm_prepare_dev(bn254_ctx *ctx, const void *d_p, size_t n, int window_bits, void **out, void *stream);
+int bn254_g2_msm_prepare_dev(bn254_ctx *ctx, const void *d_p, size_t n, int window_bits, void **out, void *stream);
+void bn254_msm_prepared_destroy(void *prep);
+size_t bn254_msm_prepared_count(const void *prep);
+size_t bn254_msm_prepared_bytes(const void *prep);            /* device memory: table and points */
+int bn254_msm_prepared_group(const void *prep);               /* 1 or 2 (0 for NULL) */
+int bn254_msm_prepared_window_bits(const void *prep);
+/* for tests: the table as W * count entries of 80 (G1) / 160 (G2) bytes; `bytes` must be exactly that */
+int bn254_msm_prepared_export(bn254_ctx *ctx, const void *prep, void *host_table, size_t bytes);
+int bn254_g1_msm_prepared(bn254_ctx *ctx, const void *prep, size_t first, const bn_fr *k, size_t n, bn_g1 *out);
+int bn254_g2_msm_prepared(bn254_ctx *ctx, const void *prep, size_t first, const bn_fr *k, size_t n, bn_g2 *out);
+int bn254_g1_msm_prepared_dev(bn254_ctx *ctx, const void *prep, size_t first, const void *d_k, size_t n, void *d_out, void *stream);
+int bn254_g2_msm_prepared_dev(bn254_ctx *ctx, const void *prep, size_t first, const void *d_k, size_t n, void *d_out, void *stream);
 int bn254_g2_precompute_dev(bn254_ctx *ctx, const void *d_q, void *d_coeffs, size_t n, void *stream);
 int bn254_miller_prepared_dev(bn254_ctx *ctx, const void *d_p, const void *d_coeffs, int shared, void *d_f, size_t n, void *stream);
 /* native prepared-G2 mode on device-resident inputs.  bn254_g2_prepare_dev allocates the handle's table (that part synchronises with the
@@ -1210,6 +1242,7 @@ int bn254_profile_reset(bn254_ctx *ctx);
    of bn254_bjj_{validate,add,mul}_batch and bn254_eddsa_poseidon_{challenge,verify}_batch: "bjj_validate", "bjj_add", "bjj_mul", "eddsa_poseidon_challenge", "eddsa_poseidon_verify" (one scope per sub-launch);
    of bn254_fr_sqrt_batch, bn254_bjj_{pack,unpack}_batch and bn254_eddsa_poseidon_verify_packed_batch: "fr_sqrt", "bjj_pack", "bjj_unpack", "eddsa_poseidon_verify_packed" (one scope per sub-launch);
    of bn254_g{1,2}_ntt_batch: "g1_ntt", "g2_ntt" (the stages, one scope per sub-launch), "g1_ntt_scale", "g2_ntt_scale" (the pass of a shift or of an inverse), "g1_ntt_normalize", "g2_ntt_normalize" (the normalisation that ends a call);
+   of bn254_g{1,2}_msm_prepare and bn254_g{1,2}_msm_prepared: "g1_msmp_table", "g2_msmp_table" (a handle's build: one scope per window; its normalisations run under "g*_normalize"), "g1_msmp_digits", "g1_msmp_bucket", "g1_msmp_reduce", "g2_msmp_digits", "g2_msmp_bucket", "g2_msmp_reduce" (the bucket route of a call; its tail and the small route run under "g*_msm_mul" and "g*_msm_fold");
    and, of bn254_fr_ntt_batch: "ntt" (the passes), "ntt_table" (the builds of the twiddle tables).
    Synchronises and consumes the recorded events (totals accumulate until bn254_profile_reset). */
 int bn254_kernel_stats(bn254_ctx *ctx, const char *kernel, double *total_ms, uint64_t *launches);
