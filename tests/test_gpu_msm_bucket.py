@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 R = M.R_ORD
 SIZES = [0, 1, 2, 3, 63, 64, 65, 257]
-WIDTHS = [1, 2, 5, 8, 13, 16]
+WIDTHS = [1, 2, 5, 8, 9, 11, 12, 13, 14, 16]                # 9, 11, 12, 14: what bn_msm_window_bits picks from 2^15 terms on
 BUCKET_SCOPES = ("digits", "bucket", "reduce")
 
 
@@ -108,7 +108,8 @@ def prefix(oracle, points):
 @pytest.mark.parametrize("c", WIDTHS)
 @pytest.mark.parametrize("g", [1, 2])
 def test_sizes_and_window_widths(eng, prefix, g, c):
-    """digits inside a word (1, 2, 8, 16), across word seams (5, 13), a short top window (5, 8, 13, 16), the largest bucket table (16)"""
+    """digits inside a word (1, 2, 8, 16), across word seams (5, 9, 11, 12, 13, 14), a short top window (5, 8, 13, 16; one bit at 11, two bits
+    at 9, 12 and 14), the largest bucket table (16)"""
     P, K, want = prefix[g]
     with eng.options(msm_bucket_min=0, msm_window_bits=c):
         for n in SIZES:
@@ -148,11 +149,12 @@ def _crafted(c):
     return [0, 1, R - 1, (1 << (c * (W - 1))) - 1, 1, 1 << (c * (W // 2)), 1 << (c * (W - 1)), 1 << 253]
 
 
-@pytest.mark.parametrize("c", [5, 13])
+@pytest.mark.parametrize("c", [5, 11, 13, 14])
 @pytest.mark.parametrize("g", [1, 2])
 def test_crafted_scalars(oracle, eng, points, g, c):
     """0, 1, r - 1, every window but the top one full, one set bit in the first / a middle / the top window, 2^253: each alone, each beside
-    a random term, and all in one call; an all-zero scalar vector gives (0, 1, 0)"""
+    a random term, and all in one call; an all-zero scalar vector gives (0, 1, 0).  c = 11 has a top window of one bit and c = 14 one of
+    two bits: the default widths of 2^16, 2^17 and 2^19 terms and of 2^20 terms and more"""
     rng = np.random.default_rng(1020 + g + c)
     ks = _crafted(c)
     P = points[g][rng.integers(0, 512, len(ks) + 1)]
@@ -205,7 +207,7 @@ def test_collisions_inside_a_bucket(oracle, eng, points, g):
 def test_chunk_seams(eng, prefix, oracle, g, n):
     """msm_chunk = 64: one full pass, a pass of one term behind it, four passes - all into the same buckets and the one tail"""
     P, K, want = prefix[g]
-    for c in (5, 13):
+    for c in (5, 11, 13, 14):
         with eng.options(msm_bucket_min=0, msm_window_bits=c, msm_chunk=64):
             eng.profile(True); eng.profile_reset()
             try:

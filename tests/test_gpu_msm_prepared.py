@@ -15,7 +15,7 @@ from test_gpu_msm_bucket import SIZES, _batch, _dev, _host, _want, _zero, eng, p
 pytestmark = pytest.mark.gpu
 
 R = M.R_ORD
-WIDTHS = [3, 5, 8, 13, 16]
+WIDTHS = [3, 5, 8, 11, 13, 14, 16]
 NEW = ("digits", "bucket", "reduce")
 
 
@@ -46,7 +46,7 @@ def _profiled(eng, g, fn):
 @pytest.mark.parametrize("c", WIDTHS)
 @pytest.mark.parametrize("g", [1, 2])
 def test_sizes_and_window_widths(eng, prefix, g, c):
-    """digits inside a word (8, 16) and across word seams (3, 5, 13), a short top window, 4 to 32768 buckets; the prepared scopes ran (no
+    """digits inside a word (8, 16) and across word seams (3, 5, 11, 13, 14), a short top window, 4 to 32768 buckets; the prepared scopes ran (no
     terms: nothing to sort or accumulate, the reduction and the tail still run) and the scopes of bn254_g{1,2}_msm's bucket route did not"""
     P, K, want = prefix[g]
     W = (254 + c - 1) // c
@@ -157,11 +157,12 @@ def _crafted(c):
     return [0, 1, R - 1, 1 << 253, below_r(half), below_r(half + 1), (1 << (c * (W - 1))) - 1]
 
 
-@pytest.mark.parametrize("c", [5, 13])
+@pytest.mark.parametrize("c", [5, 13, 16])
 @pytest.mark.parametrize("g", [1, 2])
 def test_crafted_scalars(oracle, eng, points, g, c):
     """0, 1, r - 1, 2^253, every digit exactly 2^(c-1) (kept, no carry), every digit 2^(c-1) + 1 (every window carries), every window but
-    the top one full: each alone, each beside a random term, and all in one call; an all-zero scalar vector gives (0, 1, 0)"""
+    the top one full: each alone, each beside a random term, and all in one call; an all-zero scalar vector gives (0, 1, 0).  c = 16 is
+    the width every handle of the default width has"""
     rng = np.random.default_rng(2920 + g + c)
     ks = _crafted(c)
     P = points[g][rng.integers(0, 512, len(ks) + 1)]

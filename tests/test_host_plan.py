@@ -195,3 +195,5 @@ def test_tail_scalar_table(lib, cb):
 def test_window_width_by_size(lib):
     assert [lib.hs_msm_window_bits(C.c_long(-1), C.c_size_t(1 << lg)) for lg in (0, 14, 15, 17, 18, 19, 20, 24)] == [8, 8, 9, 11, 12, 11, 14, 14]
     assert lib.hs_msm_window_bits(C.c_long(5), C.c_size_t(1 << 20)) == 5
+    # the sizes of tests/test_gpu_msm_default_route.py, which reads the widths it ran from this rule
+    assert [lib.hs_msm_window_bits(C.c_long(-1), C.c_size_t(n)) for n in (1 << 16, (1 << 18) - 1, (1 << 19) - 1, (1 << 20) + 1000)] == [11, 11, 12, 14]
