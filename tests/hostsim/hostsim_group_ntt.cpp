@@ -28,6 +28,25 @@ void build_pair(uint32_t *out, const uint64_t *c0, const uint64_t *g0) {
     bn_fr_pow(g0, e, g1.l);
     for (uint32_t i = 0; i < 2 * NTT_TBL; ++i) ntt_table_body(out, fr_of(c0), fr_of(g0), fr_of(one.l), fr_of(g1.l), i);
 }
+// the root table pair of every call: the powers of w_24
+const uint32_t *root_pair() {
+    static std::vector<uint32_t> tbl;
+    if (tbl.empty()) {
+        tbl.assign((size_t)8 * 2 * NTT_TBL, 0xffffffffu);
+        bn_fr one, w;
+        bn_fr_one(&one); bn_fr_root((int)NTT_LOG_MAX, &w);
+        build_pair(tbl.data(), one.l, w.l);
+    }
+    return tbl.data();
+}
+// the shift table pair of a call: s^j forward, n^-1 s^-j inverse
+void shift_pair(uint32_t *out, uint32_t log_n, int inverse, const uint64_t *shift) {
+    bn_fr one, n_inv, g0;
+    bn_fr_one(&one); bn_fr_inv_pow2(log_n, &n_inv);
+    memcpy(g0.l, shift, sizeof g0.l);
+    if (inverse) bn_fr_inverse(shift, g0.l);
+    build_pair(out, inverse ? n_inv.l : one.l, g0.l);
+}
 // a simulated lane pair holds both components of a prefix product: it keeps both records (tests/hostsim/hostsim_normalize.cpp)
 struct PrefixPair {
     uint4 *base;
@@ -99,23 +118,46 @@ EXPORT void hsg_index(uint32_t log_n, uint32_t stage, uint32_t g, uint32_t *out)
     const GroupNttIdx x = group_ntt_index(log_n, stage, g);
     out[0] = x.a; out[1] = x.b; out[2] = x.o0; out[3] = x.o1; out[4] = x.e;
 }
+// the twiddle group_ntt_stage_body multiplies record b of butterfly g with, by its own calls over the root table pair: eight Montgomery words
+EXPORT void hsg_twiddle(uint32_t log_n, uint32_t stage, uint32_t g, int inverse, uint32_t *out) {
+    const GroupNttIdx x = group_ntt_index(log_n, stage, g);
+    NttPass P = {};
+    P.wtbl = root_pair(); P.inverse = inverse ? 1u : 0u;
+    const Fr w = ntt_root_power(P, x.e);
+    memcpy(out, w.w, sizeof w.w);
+}
+// the factor group_ntt_scale_body multiplies point j of the arrays with, by its own calls over the shift table pair hsg_ntt builds (kept
+// until another log_n, direction or shift is asked for); shift == nullptr: the `scale` of an inverse, n^-1.  Eight Montgomery words.
+EXPORT void hsg_scale_factor(uint32_t log_n, uint32_t j, int inverse, const uint64_t *shift, uint32_t *out) {
+    static std::vector<uint32_t> stbl;
+    static uint64_t key[6] = {~0ull, 0, 0, 0, 0, 0};
+    bn_fr n_inv;
+    bn_fr_inv_pow2(log_n, &n_inv);
+    Fr c = fr_of(n_inv.l);
+    if (shift) {
+        const uint64_t want[6] = {log_n, inverse ? 1u : 0u, shift[0], shift[1], shift[2], shift[3]};
+        if (stbl.empty() || memcmp(key, want, sizeof key)) {
+            stbl.assign((size_t)8 * 2 * NTT_TBL, 0xffffffffu);
+            shift_pair(stbl.data(), log_n, inverse, shift);
+            memcpy(key, want, sizeof key);
+        }
+        NttPass P = {};
+        P.stbl = stbl.data(); P.log_n = log_n;
+        c = ntt_shift_power(P, j & ((1u << log_n) - 1u));
+    }
+    memcpy(out, c.w, sizeof c.w);
+}
 // bn254_g{1,2}_ntt_batch_dev over host arrays with sub-launches of `cap` units and chain launches of at most `chain_cap`; d_out may be d_in.
 // The workspace is filled with a pattern that is no point, and IN is compared with a copy afterwards unless it is OUT.  Returns 0, -1 when a
 // step breaks the buffer rules of the plan, -2 when IN was written.
 EXPORT int hsg_ntt(int g, const uint32_t *d_in, uint32_t *d_out, uint32_t log_n, size_t count, int inverse, const uint64_t *shift, size_t cap, size_t chain_cap) {
     g_chains = 0;
     const size_t W = g == 1 ? PointIo<G1S>::WORDS : PointIo<G2S>::WORDS, N = (size_t)1 << log_n;
-    std::vector<uint32_t> tbl((size_t)8 * 4 * NTT_TBL, 0xffffffffu);
-    bn_fr one, w, n_inv;
-    bn_fr_one(&one); bn_fr_root((int)NTT_LOG_MAX, &w);
-    build_pair(tbl.data(), one.l, w.l);
+    const uint32_t *const wtbl = root_pair();
+    std::vector<uint32_t> stbl((size_t)8 * 2 * NTT_TBL, 0xffffffffu);
+    bn_fr n_inv;
     bn_fr_inv_pow2(log_n, &n_inv);
-    if (shift) {
-        bn_fr g0;
-        memcpy(g0.l, shift, sizeof g0.l);
-        if (inverse) bn_fr_inverse(shift, g0.l);
-        build_pair(tbl.data() + 8 * 2 * NTT_TBL, inverse ? n_inv.l : one.l, g0.l);
-    }
+    if (shift) shift_pair(stbl.data(), log_n, inverse, shift);
     const bool in_place = d_in == d_out;
     const std::vector<uint32_t> in_copy(d_in, d_in + count * N * W);
     const BnGroupNttRun run = bn_group_ntt_run(log_n, count, cap, shift != nullptr, inverse != 0);
@@ -130,10 +172,10 @@ EXPORT int hsg_ntt(int g, const uint32_t *d_in, uint32_t *d_out, uint32_t log_n,
             if (st.kind == BN_GNTT_STAGE && (st.src == st.dst || (in_place && st.src == BN_NTT_IN && st.dst == BN_NTT_OUT))) return -1;
             if (st.n > (st.chain ? std::min(cap, chain_cap) : cap)) return -1;
             if (st.kind == BN_GNTT_STAGE) {
-                const GroupNttStageArgs a = {buf[st.src], buf[st.dst], tbl.data(), log_n, st.stage, inverse ? 1u : 0u, (uint32_t)st.lo};
+                const GroupNttStageArgs a = {buf[st.src], buf[st.dst], wtbl, log_n, st.stage, inverse ? 1u : 0u, (uint32_t)st.lo};
                 if (g == 1) stage<G1S>(a, st.n); else stage<G2S>(a, st.n);
             } else if (st.kind == BN_GNTT_SCALE) {
-                const GroupNttScaleArgs a = {buf[st.src], buf[st.dst], tbl.data() + 8 * 2 * NTT_TBL, log_n, shift ? 1u : 0u, (uint32_t)st.lo, fr_of(n_inv.l)};
+                const GroupNttScaleArgs a = {buf[st.src], buf[st.dst], stbl.data(), log_n, shift ? 1u : 0u, (uint32_t)st.lo, fr_of(n_inv.l)};
                 if (g == 1) scale<G1S>(a, st.n); else scale<G2S>(a, st.n);
             } else {
                 normalize(g, buf[st.src] + st.lo * W, buf[st.dst] + st.lo * W, (uint32_t)st.n);

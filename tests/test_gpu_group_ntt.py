@@ -1,6 +1,8 @@
 """Transforms over G1 and G2 on an MI355X (run with -m gpu): bn254_g{1,2}_ntt_batch, their _dev entry points and the Python faces.  The
 model is the O(n^2) sum of the definition with the oracle's chains (tests/group_ntt_cases.py); a second, independent check needs no model
-of the new code at all: for in[j] = [a_j] G the output is [fr_ntt(a)_k] G.  Expected bytes are exact: every output is normalised."""
+of the new code at all: for in[j] = [a_j] G the output is [fr_ntt(a)_k] G - up to 2^10 with the device's Fr transform, at 2^13 (the
+smallest size at which both halves of the root and shift table pairs take part) with the transform on Python integers.  Expected bytes are
+exact: every output is normalised."""
 import ctypes as C
 
 import numpy as np
@@ -86,6 +88,81 @@ def test_the_transform_of_multiples_of_the_generator_is_the_transform_of_their_s
             got = _ntt(eng, g, P, log_n, inverse, sh)
             want = _base_multiples(eng, g, eng.fr_ntt_batch(a, log_n, inverse, _shift(sh)))
             assert got.tobytes() == want.tobytes(), (g, log_n, inverse, sh, _diff(got, want))
+
+
+BIG_LOG = 13                                                # the smallest size whose twiddle exponents have a low part and whose shift powers a high one
+BIG_MODES = ((False, None), (True, None), (False, NC.SHIFT_RANDOM), (True, 5))
+_big = {}
+
+
+def _big_scalars():
+    """8192 scalars: zero at 3 and 4096 (and at 5000, where the record is made garbage with z == 0), equal ones at 4 and 5, a and r - a at 6 and 7"""
+    if "scalars" not in _big:
+        vals = FC.values(1 << BIG_LOG, seed=213)
+        vals[3] = vals[4096] = vals[5000] = 0
+        vals[5] = vals[4]
+        vals[7] = (FC.R - vals[6]) % FC.R
+        assert vals[4] and vals[6]
+        _big["scalars"] = vals
+    return _big["scalars"]
+
+
+def _big_transform(inverse, sh):
+    """the transform of the scalars on Python integers, once per mode for both groups"""
+    key = ("ntt", inverse, sh)
+    if key not in _big:
+        _big[key] = FC.rows(NC.ntt(_big_scalars(), inverse, sh))
+    return _big[key]
+
+
+def _big_input(eng, g):
+    """[a_j] G; every eighth point (and those at 4 and 6) moved to (x l^2, y l^3, l) with l random or q - 1 on host integers; garbage with z == 0 at 5000"""
+    if ("in", g) not in _big:
+        P = _base_multiples(eng, g, FC.rows(_big_scalars())).copy()
+        rng = np.random.default_rng(130 + g)
+        comps = GC.WORDS[g] // 4
+        moved = 0
+        for i in [4, 6] + list(range(1, len(P), 8)):
+            c = [GC.M.from_mont_limbs([int(w) for w in P[i, 4 * k:4 * k + 4]]) for k in range(comps)]
+            x, y, z = c if g == 1 else ((c[0], c[1]), (c[2], c[3]), (c[4], c[5]))
+            if z == GC.ZC.OPS[g].zero:
+                continue
+            assert z == GC.ZC.OPS[g].one                                        # the fixed-base call normalises
+            P[i] = GC.ZC.rows(g, [GC.ZC.rep(g, (x, y), GC.ZC.lam_of(rng, 2 * (i // 8 % 2)))])[0]
+            moved += 1
+        assert moved >= len(P) // 8
+        P[5000] = GC.ZC.rows(g, [GC.ZC.garbage(g, rng)])[0]
+        _big["in", g] = P
+    return _big["in", g]
+
+
+@pytest.mark.parametrize("inverse, sh", BIG_MODES, ids=("forward", "inverse", "forward coset", "inverse coset"))
+@pytest.mark.parametrize("g", GROUPS)
+def test_all_8192_outputs_of_a_transform_of_multiples_of_the_generator(eng, g, inverse, sh):
+    """in[j] = [a_j] G  =>  out = [ntt(a)] G at 2^13, where stage 12 takes twiddles with a low part of the exponent and the pass takes shift
+    powers with a high one; the transform of the scalars is done on Python integers, so no device transform takes part in the expectation"""
+    got = _ntt(eng, g, _big_input(eng, g), BIG_LOG, inverse, sh)
+    want = _base_multiples(eng, g, _big_transform(inverse, sh))
+    assert got.tobytes() == want.tobytes(), (g, inverse, sh, _diff(got, want))
+
+
+@pytest.mark.parametrize("g", GROUPS)
+def test_a_transform_of_8192_in_sub_launches_of_a_thousand(eng, lib, g):
+    """the inverse coset transform again under a cap of 1000 units: sub-launches that are no whole waves, with offsets above a wave, in every
+    stage, in the pass and in the normalisation"""
+    inverse, sh = BIG_MODES[3]
+    with capped(lib, 1000):
+        got = _ntt(eng, g, _big_input(eng, g), BIG_LOG, inverse, sh)
+    want = _base_multiples(eng, g, _big_transform(inverse, sh))
+    assert got.tobytes() == want.tobytes(), (g, _diff(got, want))
+
+
+@pytest.mark.parametrize("g", GROUPS)
+def test_round_trip_of_8192_on_a_coset(eng, g):
+    P = GC.batch(g, BIG_LOG, 1, seed=6)                                         # the set with points at infinity between the others
+    back = _ntt(eng, g, _ntt(eng, g, P, BIG_LOG, False, NC.SHIFT_RANDOM), BIG_LOG, True, NC.SHIFT_RANDOM)
+    want = GC.normalize(g, P)
+    assert back.tobytes() == want.tobytes(), (g, _diff(back, want))
 
 
 @pytest.mark.parametrize("g", GROUPS)
