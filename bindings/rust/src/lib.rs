@@ -66,6 +66,14 @@ extern "C" {
     fn bn254_bjj_pack_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_out32: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_bjj_unpack_batch_dev(ctx: *mut c_void, d_in32: *const c_void, d_out: *mut c_void, d_status: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
     fn bn254_eddsa_poseidon_verify_packed_batch_dev(ctx: *mut c_void, d_a32: *const c_void, d_sig64: *const c_void, d_msg: *const c_void, d_status: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_grumpkin_validate_batch(ctx: *mut c_void, p: *const Fr, status: *mut i32, n: usize) -> c_int;
+    fn bn254_grumpkin_add_batch(ctx: *mut c_void, p: *const Fr, q: *const Fr, out: *mut Fr, n: usize) -> c_int;
+    fn bn254_grumpkin_mul_batch(ctx: *mut c_void, p: *const Fr, k32: *const u8, out: *mut Fr, n: usize) -> c_int;
+    fn bn254_grumpkin_msm_batch(ctx: *mut c_void, p: *const Fr, k32: *const u8, offsets: *const usize, m: usize, out: *mut Fr) -> c_int;
+    fn bn254_grumpkin_validate_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_status: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_grumpkin_add_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_q: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_grumpkin_mul_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_k32: *const c_void, d_out: *mut c_void, n: usize, stream: *mut c_void) -> c_int;
+    fn bn254_grumpkin_msm_batch_dev(ctx: *mut c_void, d_p: *const c_void, d_k32: *const c_void, offsets: *const usize, m: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     // prepared-G2 mode (the crate's internal G2Precomp, src/groups/mod.rs:472-483): 102 line coefficients per Q, then many P against them
     fn bn254_g2_precompute(ctx: *mut c_void, q: *const G2, coeffs: *mut EllCoeffs, n: usize) -> c_int;
     fn bn254_pairing_prepared_batch(ctx: *mut c_void, p: *const G1, coeffs: *const EllCoeffs, shared: c_int, out: *mut Gt, n: usize) -> c_int;
@@ -849,6 +857,42 @@ pub fn eddsa_poseidon_verify_packed_batch(a32: &[u8], sig64: &[u8], msg: &[Fr]) 
     let mut status = vec![0i32; msg.len()];
     check(unsafe { bn254_eddsa_poseidon_verify_packed_batch(std::ptr::null_mut(), a32.as_ptr(), sig64.as_ptr(), msg.as_ptr(), status.as_mut_ptr(), msg.len()) })?;
     Ok(status)
+}
+
+/// Grumpkin, `y^2 = x^3 - 17` over `Fr`, the other half of the BN254 curve cycle (prime order q, cofactor 1): a point is two consecutive `Fr`, x
+/// then y, affine, infinity `(0, 0)`, so `p` holds `2 n` elements.  One status per raw point, checked in this order: 1 a coordinate is not
+/// below r, 4 not on the curve, else 0 (`(0, 0)` is valid).  There is no subgroup status.
+pub fn grumpkin_validate_batch(p: &[Fr]) -> Result<Vec<i32>, GpuError> {
+    assert_eq!(p.len() % 2, 0);
+    let mut status = vec![0i32; p.len() / 2];
+    check(unsafe { bn254_grumpkin_validate_batch(std::ptr::null_mut(), p.as_ptr(), status.as_mut_ptr(), p.len() / 2) })?;
+    Ok(status)
+}
+
+/// `out[i] = p[i] + q[i]`: the complete sum, for points of the curve (not checked).
+pub fn grumpkin_add_batch(p: &[Fr], q: &[Fr]) -> Result<Vec<Fr>, GpuError> {
+    assert!(p.len() % 2 == 0 && p.len() == q.len());
+    let mut out = vec![Fr::zero(); p.len()];
+    check(unsafe { bn254_grumpkin_add_batch(std::ptr::null_mut(), p.as_ptr(), q.as_ptr(), out.as_mut_ptr(), p.len() / 2) })?;
+    Ok(out)
+}
+
+/// `out[i] = [k[i]] p[i]`; a scalar is 32 bytes, the little-endian integer (any value below 2^256; NOT a Montgomery image), so `k32` holds `32 n` bytes.
+pub fn grumpkin_mul_batch(p: &[Fr], k32: &[u8]) -> Result<Vec<Fr>, GpuError> {
+    assert!(k32.len() % 32 == 0 && p.len() == 2 * (k32.len() / 32));
+    let mut out = vec![Fr::zero(); p.len()];
+    check(unsafe { bn254_grumpkin_mul_batch(std::ptr::null_mut(), p.as_ptr(), k32.as_ptr(), out.as_mut_ptr(), k32.len() / 32) })?;
+    Ok(out)
+}
+
+/// `out[j] = sum of [k[t]] p[t]` over `t` in `[offsets[j], offsets[j+1])`: many independent multi-scalar multiplications in one call.  An
+/// empty or cancelling segment gives `(0, 0)`.
+pub fn grumpkin_msm_batch(p: &[Fr], k32: &[u8], offsets: &[usize]) -> Result<Vec<Fr>, GpuError> {
+    assert!(!offsets.is_empty() && k32.len() == 32 * offsets[offsets.len() - 1] && p.len() == 2 * offsets[offsets.len() - 1]);
+    let m = offsets.len() - 1;
+    let mut out = vec![Fr::zero(); 2 * m];
+    check(unsafe { bn254_grumpkin_msm_batch(std::ptr::null_mut(), p.as_ptr(), k32.as_ptr(), offsets.as_ptr(), m, out.as_mut_ptr()) })?;
+    Ok(out)
 }
 
 /// Baby Jubjub, the twisted Edwards curve `a x^2 + y^2 = 1 + d x^2 y^2` over `Fr` (a = 168700, d = 168696): a point is two consecutive `Fr`, x then

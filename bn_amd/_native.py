@@ -7,7 +7,7 @@ import subprocess
 
 HERE = pathlib.Path(__file__).resolve().parent
 LIB_PATH = pathlib.Path(os.environ.get("BN254_LIB_PATH", HERE / "libbn254_hip.so"))     # override: kernel experiments only
-SOURCES = [HERE / "csrc" / f for f in ("bn254_hip.hip", "bn254_seg.hip", "bn254_wire.hip", "bn254_kernels_b.hip", "bn254_kernels_mul.hip", "bn254_kernels_w.hip", "bn254_kernels_q.hip", "bn254_multi.hip", "bn254_measure.hip", "bn254_fr.hip", "bn254_fr_sqrt.hip", "bn254_ntt.hip", "bn254_group_ntt.hip", "bn254_dot.hip", "bn254_scan.hip", "bn254_mle.hip", "bn254_poseidon.hip", "bn254_poseidon_wide.hip", "bn254_hash.hip", "bn254_hash_g2.hip", "bn254_validate.hip", "bn254_babyjub.hip")]
+SOURCES = [HERE / "csrc" / f for f in ("bn254_hip.hip", "bn254_seg.hip", "bn254_wire.hip", "bn254_kernels_b.hip", "bn254_kernels_mul.hip", "bn254_kernels_w.hip", "bn254_kernels_q.hip", "bn254_multi.hip", "bn254_measure.hip", "bn254_fr.hip", "bn254_fr_sqrt.hip", "bn254_ntt.hip", "bn254_group_ntt.hip", "bn254_dot.hip", "bn254_scan.hip", "bn254_mle.hip", "bn254_poseidon.hip", "bn254_poseidon_wide.hip", "bn254_hash.hip", "bn254_hash_g2.hip", "bn254_validate.hip", "bn254_babyjub.hip", "bn254_grumpkin.hip")]
 OBJ_DIR = HERE / "csrc" / "build"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # EVERY unit is compiled with LLVM's DPP combiner off: with it on, the quad_perm move of a neighbour lane's limb is folded into the
@@ -170,6 +170,14 @@ SIGNATURES = {   # name -> argtypes  (every function returns int unless noted)
     "bn254_bjj_pack_batch_dev": [_VP, _VP, _VP, _SZ, _VP],
     "bn254_bjj_unpack_batch_dev": [_VP, _VP, _VP, _VP, _SZ, _VP],
     "bn254_eddsa_poseidon_verify_packed_batch_dev": [_VP, _VP, _VP, _VP, _VP, _SZ, _VP],
+    "bn254_grumpkin_validate_batch": [_VP, _VP, _VP, _SZ],
+    "bn254_grumpkin_add_batch": [_VP, _VP, _VP, _VP, _SZ],
+    "bn254_grumpkin_mul_batch": [_VP, _VP, _VP, _VP, _SZ],
+    "bn254_grumpkin_msm_batch": [_VP, _VP, _VP, _VP, _SZ, _VP],
+    "bn254_grumpkin_validate_batch_dev": [_VP, _VP, _VP, _SZ, _VP],
+    "bn254_grumpkin_add_batch_dev": [_VP, _VP, _VP, _VP, _SZ, _VP],
+    "bn254_grumpkin_mul_batch_dev": [_VP, _VP, _VP, _VP, _SZ, _VP],
+    "bn254_grumpkin_msm_batch_dev": [_VP, _VP, _VP, _VP, _SZ, _VP, _VP],
     "bn254_g2_precompute": [_VP, _VP, _VP, _SZ],
     "bn254_pairing_prepared_batch": [_VP, _VP, _VP, C.c_int, _VP, _SZ],
     "bn254_g2_precompute_dev": [_VP, _VP, _VP, _SZ, _VP],

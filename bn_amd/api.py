@@ -892,6 +892,52 @@ def eddsa_poseidon_verify_packed_batch(a32, sig64, msg, engine=None):
     return (engine or default_engine()).eddsa_poseidon_verify_packed_batch(A, S, M)
 
 
+def _grumpkin_points(points):
+    from . import grumpkin
+    return grumpkin._point_array(points)
+
+
+def _grumpkin_scalars(scalars):
+    from . import grumpkin
+    return grumpkin._scalar_array(scalars)
+
+
+def grumpkin_validate_batch(points, engine=None):
+    """(n,) int32 per Grumpkin point (bn_amd.grumpkin): 0 a point of the curve (O = (0, 0) included), 1 a coordinate's words are not below r,
+    4 not on the curve.  The cofactor is 1: there is no subgroup status.  points: a sequence of grumpkin.Point or (x, y) integer pairs, or an
+    (n, 2, 4) uint64 array of raw records"""
+    return (engine or default_engine()).grumpkin_validate_batch(_grumpkin_points(points))
+
+
+def grumpkin_add_batch(p, q, engine=None):
+    """[p_i + q_i] -> list of grumpkin.Point: the complete sum, for points of the curve (not checked)"""
+    from .grumpkin import Point
+    P, Q = _grumpkin_points(p), _grumpkin_points(q)
+    if P.shape != Q.shape:
+        raise ValueError(f"{P.shape[0]} points, {Q.shape[0]} points")
+    return [Point.from_limbs(r) for r in (engine or default_engine()).grumpkin_add_batch(P, Q)]
+
+
+def grumpkin_mul_batch(p, k, engine=None):
+    """[[k_i] p_i] -> list of grumpkin.Point, for points of the curve (not checked).  k: a sequence of integers in [0, 2^256) (an Fr counts as
+    its canonical integer), or an (n, 4) uint64 array of plain little-endian words - NOT Montgomery images; the result is [k mod q]p"""
+    from .grumpkin import Point
+    P, K = _grumpkin_points(p), _grumpkin_scalars(k)
+    if P.shape[0] != K.shape[0]:
+        raise ValueError(f"{P.shape[0]} points, {K.shape[0]} scalars")
+    return [Point.from_limbs(r) for r in (engine or default_engine()).grumpkin_mul_batch(P, K)]
+
+
+def grumpkin_msm_batch(p, k, offsets, engine=None):
+    """[sum of [k_t] p_t over t in [offsets[j], offsets[j+1])] -> list of grumpkin.Point: many independent multi-scalar multiplications in
+    one call; an empty or cancelling segment gives O.  p, k as for grumpkin_mul_batch; offsets: m + 1 CSR offsets"""
+    from .grumpkin import Point
+    P, K = _grumpkin_points(p), _grumpkin_scalars(k)
+    if P.shape[0] != K.shape[0]:
+        raise ValueError(f"{P.shape[0]} points, {K.shape[0]} scalars")
+    return [Point.from_limbs(r) for r in (engine or default_engine()).grumpkin_msm_batch(P, K, offsets)]
+
+
 class PreparedG2:
     """G2 points prepared once for many pairings (the crate's internal G2Precomp, groups/mod.rs:472-483,557-588, as a device-resident
     native table: Engine.g2_prepare).  One point: shared by every P; several: point i is paired with ps[i]."""

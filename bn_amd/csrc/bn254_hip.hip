@@ -355,7 +355,7 @@ void bn254_ctx_destroy(bn254_ctx *c) {
     hipDeviceSynchronize();
     for (auto &r : c->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     c->ws.release(); c->exp_tbl.release(); c->pow_tbl.release(); c->miller_state.release(); c->mul_tbl.release();
-    c->seg_plan.release(); c->seg_plan_host.release(); c->msm_ws.release(); c->msm_scal.release(); c->msmp_scal.release(); c->norm_prefix.release(); c->fr_prefix.release(); c->ntt_tbl.release(); c->ntt_ws.release(); c->gntt_ws.release(); c->dot_ws.release(); c->scan_ws.release(); c->mle_ws.release();
+    c->seg_plan.release(); c->seg_plan_host.release(); c->msm_ws.release(); c->msm_scal.release(); c->msmp_scal.release(); c->norm_prefix.release(); c->fr_prefix.release(); c->ntt_tbl.release(); c->ntt_ws.release(); c->gntt_ws.release(); c->dot_ws.release(); c->scan_ws.release(); c->mle_ws.release(); c->grk_ws.release();
     if (c->seg_plan_ev) hipEventDestroy(c->seg_plan_ev);
     for (auto &bc : c->base_cache) {
         for (auto &sl : bc.slot) sl.table.release();

@@ -1,7 +1,7 @@
 // Host-side internals shared by the translation units that implement include/bn254_hip.h (bn254_hip.hip: contexts, options, launch
 // policy and the single-device entry points of pairing, Miller loop, final exponentiation and products; bn254_seg.hip: the segmented
 // multi-pairings and the multi-scalar multiplications; bn254_wire.hip: the wire format; bn254_multi.hip: pipelined host-buffer path,
-// multi-device fan-out, RCCL exchange; bn254_{fr,ntt,dot,scan,mle,poseidon,hash}.hip: the families of integer kernels over Fr and hash-to-curve,
+// multi-device fan-out, RCCL exchange; bn254_{fr,ntt,dot,scan,mle,poseidon,hash,babyjub,grumpkin}.hip: the families of integer kernels over Fr, hash-to-curve and the curves over Fr,
 // each with its Ops and entry points).  The host arithmetic that needs no device is host_plan.hpp; the kernel shell, the launchers and the
 // overrides of the integer kernels are lane_launch.hpp.  Not part of the ABI.
 //
@@ -135,6 +135,7 @@ struct bn254_ctx {
     BnBuf gntt_ws;                      // bn254_g{1,2}_ntt_batch: the array of Jacobian points between the stages of one group of transforms
     BnBuf dot_ws;                       // bn254_fr_dot_batch: the partial sums of the segments longer than one piece (32 bytes each; its work list travels through seg_plan)
     BnBuf scan_ws;                      // bn254_fr_scan_batch: per scratch slot of its plan a map (A, B) and a carry, three arrays of 32-byte records (its work list travels through seg_plan)
+    BnBuf grk_ws;                       // bn254_grumpkin_msm_batch: the projective partial sums of the segments of more than one term (96 bytes each; its work list travels through seg_plan)
     BnBuf mle_ws;                       // bn254_fr_sumcheck_round: the partial sums of the round kernel's lanes and of the sum levels, [t][lane] per level (32 bytes each)
     BnBuf psd_wide_tbl[16];             // bn254_fr_poseidon_ex_batch / _chain_batch: the constants of width t = 2 .. 17 ([t - 2]; poseidon_wide_table.hpp), derived and
     bool psd_wide_ready[16] = {};       // ... uploaded with a blocking copy at the first use of the width, under psd_wide_mu; read-only afterwards

@@ -1037,6 +1037,61 @@ class Engine:
     def eddsa_poseidon_verify_batch_dev(self, d_a, d_r8, d_s, d_msg, d_status, n, stream=0):
         _native.check(self._lib.bn254_eddsa_poseidon_verify_batch_dev(self._h, d_a, d_r8, d_s, d_msg, d_status, n, stream))
 
+    # ---- Grumpkin (y^2 = x^3 - 17 over Fr, of prime order q; a point is two Fr, x then y, affine, O = (0, 0); a scalar is 32 little-endian bytes)
+    def grumpkin_validate_batch(self, p):
+        """(n,2,4) uint64 raw records -> (n,) int32 status: 0 a point of the curve (O = (0, 0) included), 1 a coordinate's words are not below r,
+        4 not on the curve"""
+        p = np.ascontiguousarray(p, np.uint64).reshape(-1, 2, 4); st = np.empty(p.shape[0], np.int32)
+        _native.check(self._lib.bn254_grumpkin_validate_batch(self._h, _p(p), _p(st), p.shape[0])); return st
+
+    def grumpkin_add_batch(self, p, q):
+        """(n,2,4) + (n,2,4) uint64 points of the curve -> (n,2,4): the complete sum, affine"""
+        p = np.ascontiguousarray(p, np.uint64).reshape(-1, 2, 4); q = np.ascontiguousarray(q, np.uint64).reshape(-1, 2, 4)
+        if p.shape != q.shape:
+            raise ValueError(f"{p.shape[0]} points, {q.shape[0]} points")
+        out = np.empty_like(p)
+        _native.check(self._lib.bn254_grumpkin_add_batch(self._h, _p(p), _p(q), _p(out), p.shape[0])); return out
+
+    def grumpkin_mul_batch(self, p, k):
+        """(n,2,4) uint64 points of the curve, (n,4) uint64 plain 256-bit integers (not Montgomery images) -> (n,2,4): [k] p, affine"""
+        p = np.ascontiguousarray(p, np.uint64).reshape(-1, 2, 4); k = np.ascontiguousarray(k, np.uint64).reshape(-1, 4)
+        if p.shape[0] != k.shape[0]:
+            raise ValueError(f"{p.shape[0]} points, {k.shape[0]} scalars")
+        out = np.empty_like(p)
+        _native.check(self._lib.bn254_grumpkin_mul_batch(self._h, _p(p), _p(k), _p(out), p.shape[0])); return out
+
+    def grumpkin_msm_batch(self, p, k, offsets):
+        """out[j] = sum of [k[t]] p[t] over t in [offsets[j], offsets[j+1]) -> (m,2,4) uint64; an empty or cancelling segment gives O = (0, 0)
+        (include/bn254_hip.h bn254_grumpkin_msm_batch)"""
+        p = np.ascontiguousarray(p, np.uint64).reshape(-1, 2, 4); k = np.ascontiguousarray(k, np.uint64).reshape(-1, 4)
+        if p.shape[0] != k.shape[0]:
+            raise ValueError(f"{p.shape[0]} points, {k.shape[0]} scalars")
+        o = _offsets(offsets)
+        if int(o[-1]) != p.shape[0]:
+            raise ValueError(f"offsets[m] = {int(o[-1])} but {p.shape[0]} terms were given")
+        out = np.empty((o.size - 1, 2, 4), np.uint64)
+        _native.check(self._lib.bn254_grumpkin_msm_batch(self._h, _p(p), _p(k), _p(o), o.size - 1, _p(out))); return out
+
+    def grumpkin_validate_batch_dev(self, d_p, d_status, n, stream=0):
+        """device pointers: records and n int32 statuses"""
+        _native.check(self._lib.bn254_grumpkin_validate_batch_dev(self._h, d_p, d_status, n, stream))
+
+    def grumpkin_add_batch_dev(self, d_p, d_q, d_out, n, stream=0):
+        """d_out may be exactly d_p or d_q"""
+        _native.check(self._lib.bn254_grumpkin_add_batch_dev(self._h, d_p, d_q, d_out, n, stream))
+
+    def grumpkin_mul_batch_dev(self, d_p, d_k, d_out, n, stream=0):
+        """d_out may be exactly d_p"""
+        _native.check(self._lib.bn254_grumpkin_mul_batch_dev(self._h, d_p, d_k, d_out, n, stream))
+
+    def grumpkin_msm_batch_dev(self, d_p, d_k, offsets, m, d_out, stream=0):
+        """device pointers p (offsets[m] points), k (as many 32-byte scalars) and out (m points; must not overlap the inputs), ordered on
+        `stream`; `offsets` is a HOST sequence of m + 1 CSR offsets, read before the call returns"""
+        o = _offsets(offsets)
+        if o.size != m + 1:
+            raise ValueError(f"{m} segments need {m + 1} offsets, got {o.size}")
+        _native.check(self._lib.bn254_grumpkin_msm_batch_dev(self._h, d_p, d_k, _p(o), m, d_out, stream))
+
     # ---- the crate's variable-length byte stream (infinity = the lone byte 0)
     def _encode_stream(self, fn, p, rec):
         out = np.empty(p.shape[0] * rec, np.uint8); w = C.c_size_t()

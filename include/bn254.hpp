@@ -491,6 +491,35 @@ inline std::vector<int32_t> eddsa_poseidon_verify_packed(const std::vector<uint8
     check(bn254_eddsa_poseidon_verify_packed_batch(nullptr, a32.data(), sig64.data(), reinterpret_cast<const bn_fr *>(msg.data()), status.data(), msg.size()));
     return status;
 }
+// Grumpkin (y^2 = x^3 - 17 over Fr, the other half of the BN254 curve cycle: prime order q, cofactor 1).  A point is two consecutive Fr, x then
+// y, affine, infinity (0, 0): a vector of 2 n elements holds n points.  A scalar is 32 bytes, the little-endian integer (any value below 2^256,
+// NOT a Montgomery image): a vector of 32 n bytes.  grumpkin_validate: 0 a point of the curve ((0, 0) included), 1 a coordinate is not below r,
+// 4 not on the curve; there is no subgroup status
+inline std::vector<int32_t> grumpkin_validate(const std::vector<Fr> &p) {
+    if (p.size() % 2) throw std::invalid_argument("grumpkin_validate: a point is two Fr");
+    std::vector<int32_t> status(p.size() / 2);
+    check(bn254_grumpkin_validate_batch(nullptr, reinterpret_cast<const bn_fr *>(p.data()), status.data(), status.size()));
+    return status;
+}
+inline std::vector<Fr> grumpkin_add(const std::vector<Fr> &p, const std::vector<Fr> &q) {
+    if (p.size() % 2 || p.size() != q.size()) throw std::invalid_argument("grumpkin_add: length mismatch");
+    std::vector<Fr> out(p.size());
+    check(bn254_grumpkin_add_batch(nullptr, reinterpret_cast<const bn_fr *>(p.data()), reinterpret_cast<const bn_fr *>(q.data()), reinterpret_cast<bn_fr *>(out.data()), p.size() / 2));
+    return out;
+}
+inline std::vector<Fr> grumpkin_mul(const std::vector<Fr> &p, const std::vector<uint8_t> &k32) {
+    if (k32.size() % 32 || p.size() != 2 * (k32.size() / 32)) throw std::invalid_argument("grumpkin_mul: length mismatch");
+    std::vector<Fr> out(p.size());
+    check(bn254_grumpkin_mul_batch(nullptr, reinterpret_cast<const bn_fr *>(p.data()), k32.data(), reinterpret_cast<bn_fr *>(out.data()), k32.size() / 32));
+    return out;
+}
+// out[j] = sum of [k[t]] p[t] over t in [offsets[j], offsets[j+1]); an empty or cancelling segment gives (0, 0)
+inline std::vector<Fr> grumpkin_msm(const std::vector<Fr> &p, const std::vector<uint8_t> &k32, const std::vector<size_t> &offsets) {
+    if (offsets.empty() || k32.size() != 32 * offsets.back() || p.size() != 2 * offsets.back()) throw std::invalid_argument("grumpkin_msm: offsets, points and scalars disagree in length");
+    std::vector<Fr> out(2 * (offsets.size() - 1));
+    check(bn254_grumpkin_msm_batch(nullptr, reinterpret_cast<const bn_fr *>(p.data()), k32.data(), offsets.data(), offsets.size() - 1, reinterpret_cast<bn_fr *>(out.data())));
+    return out;
+}
 // out[i] = (a[i] == b[i]) as group elements, whatever their Jacobian representations (groups/mod.rs:83-109): nothing is normalized
 inline std::vector<bool> g1_eq(const std::vector<G1> &a, const std::vector<G1> &b) {
     if (a.size() != b.size()) throw std::invalid_argument("g1_eq: length mismatch");

@@ -95,6 +95,12 @@
  *                          counterpart in the reference
  *   bn254_bjj_pack_batch_dev / bn254_bjj_unpack_batch_dev / bn254_eddsa_poseidon_verify_packed_batch_dev  the same three on device-resident
  *                          records, asynchronous on the caller's stream
+ *   bn254_grumpkin_validate_batch / bn254_grumpkin_add_batch / bn254_grumpkin_mul_batch / bn254_grumpkin_msm_batch  Grumpkin, y^2 = x^3 - 17 over Fr, the
+ *                          other half of the BN254 curve cycle (order q): validation of raw points, the complete sum, out[i] = [k[i]] p[i] for
+ *                          256-bit integers k, and the segmented sum out[j] = sum of [k[t]] p[t] over segment j; none has a counterpart in the
+ *                          reference
+ *   bn254_grumpkin_validate_batch_dev / bn254_grumpkin_add_batch_dev / bn254_grumpkin_mul_batch_dev / bn254_grumpkin_msm_batch_dev  the same four on
+ *                          device-resident records, asynchronous on the caller's stream
  *   bn254_g1_ntt_batch / bn254_g2_ntt_batch  the transform of bn254_fr_ntt_batch with points for data and scalar multiplication for the product:
  *                          out[k] = normalize(sum_j [s^j w_n^(j k)] in[j]), and its inverse; no counterpart in the reference
  *   bn254_g1_ntt_batch_dev / bn254_g2_ntt_batch_dev  the same two on device-resident records, asynchronous on the caller's stream
@@ -154,6 +160,8 @@
      serialise on the context in the same way (its mutex for the whole call).
      bn254_fr_sqrt_batch, bn254_bjj_pack_batch, bn254_bjj_unpack_batch and bn254_eddsa_poseidon_verify_packed_batch serialise on the context in
      the same way (its mutex for the whole call).
+     bn254_grumpkin_validate_batch, bn254_grumpkin_add_batch, bn254_grumpkin_mul_batch and bn254_grumpkin_msm_batch serialise on the context in the
+     same way (its mutex for the whole call).
  *     bn254_pairing_product_batch_prepared_native serialises on the context like them; its handle is immutable and shared freely.
  *     Use one context per thread (or bn254_multi_*) for more overlap;
  *     bn254_ctx_set_option is atomic, but set options before concurrent use: a call in flight may run some
@@ -226,6 +234,11 @@
      bn254_fr_sqrt_batch_dev, bn254_bjj_pack_batch_dev, bn254_bjj_unpack_batch_dev and bn254_eddsa_poseidon_verify_packed_batch_dev are of the same
      kind: no scratch, no host operand, one launch per sub-launch (the packed verifier unpacks its two points in the lane that verifies), nothing
      waited on or read back, so any number of threads may issue them on one context, each on its own stream and buffers.
+     bn254_grumpkin_validate_batch_dev, bn254_grumpkin_add_batch_dev and bn254_grumpkin_mul_batch_dev are of the same kind: no scratch, no host
+     operand, one launch per sub-launch (each lane's window table is its own private memory), nothing waited on or read back, so any number of
+     threads may issue them on one context, each on its own stream and buffers.  bn254_grumpkin_msm_batch_dev reads its HOST `offsets` before
+     it returns and keeps its partial sums in context-owned scratch, bracketed by the scratch event like bn254_fr_dot_batch_dev's: two streams
+     on one context serialise on it instead of racing.  It waits on nothing and reads nothing back.
  */
 #ifndef BN254_HIP_H
 #define BN254_HIP_H
@@ -1064,6 +1077,40 @@ int bn254_bjj_pack_batch_dev(bn254_ctx *ctx, const void *d_p, void *d_out32, siz
 int bn254_bjj_unpack_batch_dev(bn254_ctx *ctx, const void *d_in32, void *d_out, void *d_status, size_t n, void *stream);
 int bn254_eddsa_poseidon_verify_packed_batch_dev(bn254_ctx *ctx, const void *d_a32, const void *d_sig64, const void *d_msg, void *d_status, size_t n, void *stream);
 
+/* Grumpkin, one record per lane.  Grumpkin is the curve y^2 = x^3 - 17 over Fr - THIS library's scalar field - whose order is q, the base field
+   modulus of BN254: the two curves form a cycle.  q is prime, so the cofactor is 1 and there is no subgroup to check.  The generator is
+   G = (1, 17631683881184975370165255887551781615748388533673675138860), the square root of -16 that is not above (r - 1) / 2.
+   A POINT is two consecutive bn_fr, x then y, canonical Montgomery words, affine: p[2 i] and p[2 i + 1], 64 bytes, the layout of the Baby
+   Jubjub calls.  Infinity is (0, 0): -17 is a non-residue mod r, so no point of the curve has x = 0.  -(x, y) = (x, -y).
+   A SCALAR is 32 bytes, the little-endian integer k: k32[32 i ..].  Any value below 2^256 is accepted and the result is [k]P for that integer,
+   which equals [k mod q]P.  It is NOT a Montgomery image and not a bn_fr: the scalar field of this curve is Fq, and this header has no Fq type.
+   bn254_grumpkin_validate_batch: status[i] for the raw record p[i], any 64 bytes, checked in this order:
+     1   a coordinate is not below r - the words are compared as they stand, before any field arithmetic
+     4   y^2 != x^3 - 17 and the record is not (0, 0): not on the curve
+     0   otherwise: a point of the curve; O = (0, 0) is one
+   Nothing is written but status; a record is never changed.  There is no subgroup status: the cofactor is 1.
+   bn254_grumpkin_add_batch: out[i] = p[i] + q[i] by the complete projective formulas of Renes-Costello-Batina for a = 0: no exceptional inputs,
+   p[i] == q[i], O and p[i] == -q[i] included.  Defined for points of the curve - like the G1 calls it trusts its caller; an off-curve record gives
+   garbage, never a fault.  out may be p or q.
+   bn254_grumpkin_mul_batch: out[i] = [k32[i]] p[i]; out may be p.  One fixed-window chain (4 bits a window) of complete additions over all 256
+   bits of k, the same instruction stream whatever the scalar, and one inversion per lane.
+   bn254_grumpkin_msm_batch: out[j] = sum over t in [offsets[j], offsets[j+1]) of [k32[t]] p[t], affine.  offsets: a HOST array of m + 1 size_t in
+   both forms, as for bn254_fr_dot_batch: offsets[0] == 0, never decreasing, offsets[m] terms in all.  An empty segment and a sum that cancels
+   give (0, 0).  out must not overlap the inputs.  One lane per term runs the chain; segments of more than one term are then added in fold
+   levels of at most 16 partial sums per lane, one inversion per segment.
+   All four: a NULL pointer with work to do or n > 2^40 (offsets[m] > 2^40) is BN254_E_BAD_ARG before any device is touched, and so are offsets
+   that do not start at 0 or that decrease; n == 0 (m == 0) succeeds.  Calls run as sub-launches of at most 2^22 records.  The _dev forms take
+   device pointers (16-byte aligned; d_status int32_t per record), enqueue on `stream`, use no host round trip and read nothing back.
+   Threading: see above. */
+int bn254_grumpkin_validate_batch(bn254_ctx *ctx, const bn_fr *p, int32_t *status, size_t n);
+int bn254_grumpkin_add_batch(bn254_ctx *ctx, const bn_fr *p, const bn_fr *q, bn_fr *out, size_t n);
+int bn254_grumpkin_mul_batch(bn254_ctx *ctx, const bn_fr *p, const uint8_t *k32, bn_fr *out, size_t n);
+int bn254_grumpkin_msm_batch(bn254_ctx *ctx, const bn_fr *p, const uint8_t *k32, const size_t *offsets, size_t m, bn_fr *out);
+int bn254_grumpkin_validate_batch_dev(bn254_ctx *ctx, const void *d_p, void *d_status, size_t n, void *stream);
+int bn254_grumpkin_add_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, void *d_out, size_t n, void *stream);
+int bn254_grumpkin_mul_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_k32, void *d_out, size_t n, void *stream);
+int bn254_grumpkin_msm_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_k32, const size_t *offsets, size_t m, void *d_out, void *stream);
+
 /* ---- device-resident entry points (inputs/outputs already in HBM; `stream` is a hipStream_t or NULL) ------------------ */
 /* Same layouts (array of structs) in device memory.  Asynchronous on `stream`; the caller synchronises. */
 int bn254_pairing_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, void *d_out, size_t n, void *stream);
@@ -1241,6 +1288,7 @@ int bn254_profile_reset(bn254_ctx *ctx);
    of bn254_g1_validate_batch and bn254_g2_validate_batch: "g1_validate", "g2_validate" (one scope per sub-launch);
    of bn254_bjj_{validate,add,mul}_batch and bn254_eddsa_poseidon_{challenge,verify}_batch: "bjj_validate", "bjj_add", "bjj_mul", "eddsa_poseidon_challenge", "eddsa_poseidon_verify" (one scope per sub-launch);
    of bn254_fr_sqrt_batch, bn254_bjj_{pack,unpack}_batch and bn254_eddsa_poseidon_verify_packed_batch: "fr_sqrt", "bjj_pack", "bjj_unpack", "eddsa_poseidon_verify_packed" (one scope per sub-launch);
+   of bn254_grumpkin_{validate,add,mul,msm}_batch: "grumpkin_validate", "grumpkin_add", "grumpkin_mul", "grumpkin_msm", "grumpkin_msm_fold" (one scope per sub-launch; the segmented sum: per sub-launch of a level);
    of bn254_g{1,2}_ntt_batch: "g1_ntt", "g2_ntt" (the stages, one scope per sub-launch), "g1_ntt_scale", "g2_ntt_scale" (the pass of a shift or of an inverse), "g1_ntt_normalize", "g2_ntt_normalize" (the normalisation that ends a call);
    of bn254_g{1,2}_msm_prepare and bn254_g{1,2}_msm_prepared: "g1_msmp_table", "g2_msmp_table" (a handle's build: one scope per window; its normalisations run under "g*_normalize"), "g1_msmp_digits", "g1_msmp_bucket", "g1_msmp_reduce", "g2_msmp_digits", "g2_msmp_bucket", "g2_msmp_reduce" (the bucket route of a call; its tail and the small route run under "g*_msm_mul" and "g*_msm_fold");
    and, of bn254_fr_ntt_batch: "ntt" (the passes), "ntt_table" (the builds of the twiddle tables).
