@@ -882,7 +882,8 @@ int bn254_g1_decode_batch(bn254_ctx *ctx, const uint8_t *in, bn_g1 *out, int32_t
 int bn254_g2_decode_batch(bn254_ctx *ctx, const uint8_t *in, bn_g2 *out, int32_t *status, size_t n);
 /* the crate's own byte stream (what bincode/rustc_serialize produce for a sequence of points, groups/mod.rs:143-205): a point at
    infinity is the lone byte 0, a finite point is 4 + coordinates, so records have variable length.  encode: `written` bytes are
-   produced (BN254_E_BAD_ARG if `cap` is too small).  decode: up to `max_points` points are parsed from `len` bytes; `count` points
+   produced (BN254_E_BAD_ARG if `cap` is too small: `*written` is left as it was, `out` holds the leading whole records that fit in
+   `cap` and nothing behind them is written; `cap` equal to the length of the stream is enough).  decode: up to `max_points` points are parsed from `len` bytes; `count` points
    and `consumed` bytes are reported (a truncated trailing record is left unconsumed); status[i] as for the batch decoders.
    DIFFERENCE from the crate: its Decodable returns Err at the first bad record and the caller's stream stops there
    (groups/mod.rs:165-175); this decoder records the status (a bad tag consumes its one byte, a record that fails a check consumes

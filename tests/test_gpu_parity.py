@@ -934,6 +934,13 @@ def test_wire_stream_format_on_gpu(oracle, eng):
             assert np.array_equal(out[i], zero if not pts[i][2 * len(zero) // 3:].any() else norm(pts[i]))
         # truncated tail: the last complete record boundary is reported; a bad tag costs one byte and status 3
         cut = got[:-5] if got[-1] != 0 or got.size < 2 else got
+        outc, stc, usedc = decs(cut)
+        whole = cut.size == got.size                               # a last byte 0 leaves the stream as it is: all n records
+        assert outc.shape[0] == (n if whole else n - 1) and not stc.any() and np.array_equal(outc, out[:outc.shape[0]])
+        assert usedc == (got.size if whole else got.size - len(enc1(pts[1])))
+        short = got[:-6]                                           # the closing infinity and five bytes of the finite record in front of it
+        outs, sts, useds = decs(short)
+        assert outs.shape[0] == n - 2 and not sts.any() and useds == got.size - 1 - len(enc1(pts[1])) and np.array_equal(outs, out[:n - 2])
         out2, st2, used2 = decs(np.concatenate([np.array([9], np.uint8), got[:200]]))
         assert st2[0] == 3 and used2 <= 201 and out2.shape[0] >= 2 and not st2[1:].any()
         assert np.array_equal(out2[1:], out[:out2.shape[0] - 1])
