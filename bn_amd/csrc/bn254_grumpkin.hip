@@ -1,7 +1,7 @@
 // Grumpkin on the device (include/bn254_hip.h bn254_grumpkin_validate_batch, bn254_grumpkin_add_batch, bn254_grumpkin_mul_batch,
 // bn254_grumpkin_msm_batch and their _dev twins): the kernels - Ops of lane_launch.hpp's bn254_fr_decode_k like the other integer kernels, one
-// lane of a body of grumpkin_ops.hpp each - and the eight entry points.  validate / add / mul: one launch per call (and per sub-launch of a
-// large one), no scratch, nothing waits.  The segmented sum: the work list of host_plan.hpp's bn_dot_plan with one term per lane goes up through
+// lane of a body of grumpkin_ops.hpp each - and the eight entry points.  validate / add / mul: a kind table and a launch switch on
+// record_call.hpp's one path - one launch per call (and per sub-launch of a large one), no scratch, nothing waits.  The segmented sum: the work list of host_plan.hpp's bn_dot_plan with one term per lane goes up through
 // the context's work-list staging, level 0 runs the chains, the fold levels add scratch slots of 96 bytes (ctx->grk_ws, under the scratch guard).
 // Compiled like every unit (bn254_hip.hip: the flags).
 #include <hip/hip_runtime.h>
@@ -9,6 +9,7 @@
 #include "grumpkin_ops.hpp"
 #include "host_ctx.hpp"
 #include "lane_launch.hpp"
+#include "record_call.hpp"
 
 using namespace bn254;
 
@@ -20,7 +21,6 @@ using namespace bn254;
 
 namespace {
 constexpr unsigned GRK_BLOCK = BN254_GRUMPKIN_BLOCK;
-constexpr size_t GRK_N_MAX = (size_t)1 << 40;
 constexpr size_t GRK_SLOT_BYTES = 3 * sizeof(bn_fr);
 
 // lanes [lo, lo + n) of a call: a sub-launch, one record per lane
@@ -63,46 +63,23 @@ struct GrkMsmFoldOp {
 
 BnLaunchMax g_grk_launch_max;          // tests only: the sub-launch size
 
+// validate / add / mul are a record family (record_call.hpp): scope, inputs and the bytes of one record of each, of the output, of a second output
 enum { GRK_VALIDATE, GRK_ADD, GRK_MUL, GRK_KINDS };
-const char *const GRK_SCOPE[] = {"grumpkin_validate", "grumpkin_add", "grumpkin_mul"};
-// inputs of a call (device or host pointers) and the bytes of one record of each; the output
-struct GrkArgs { const void *in[2]; int n_in; void *out; };
-constexpr size_t GRK_IN_BYTES[GRK_KINDS][2] = {{64, 0}, {64, 64}, {64, 32}};
-constexpr size_t GRK_OUT_BYTES[GRK_KINDS] = {sizeof(int32_t), 64, 64};
-
-// arguments only: nothing here touches a device.  1 = nothing to do
-int grk_check(const GrkArgs &a, size_t n) {
-    if (n == 0) return 1;
-    if (!a.out || n > GRK_N_MAX) return BN254_E_BAD_ARG;
-    for (int j = 0; j < a.n_in; ++j)
-        if (!a.in[j]) return BN254_E_BAD_ARG;
-    return BN254_OK;
-}
-int grk_run(bn254_ctx *ctx, int what, const GrkArgs &a, size_t n, hipStream_t s) {
-    const uint32_t *const i0 = (const uint32_t *)a.in[0], *const i1 = (const uint32_t *)a.in[1];
-    return bn_for_parts(n, g_grk_launch_max.step(), [&](size_t lo, size_t cnt) -> int {
-        BnScope sc(ctx, s, GRK_SCOPE[what]);
+constexpr BnRecordKind GRK_KIND[GRK_KINDS] = {{"grumpkin_validate", 1, {64}, sizeof(int32_t), 0}, {"grumpkin_add", 2, {64, 64}, 64, 0}, {"grumpkin_mul", 2, {64, 32}, 64, 0}};
+struct GrkLaunch {
+    int what;
+    int operator()(const BnRecordArgs &a, size_t lo, size_t cnt, hipStream_t s) const {
+        const uint32_t *const i0 = (const uint32_t *)a.in[0], *const i1 = (const uint32_t *)a.in[1];
         switch (what) {
         case GRK_VALIDATE: return bn_lane_launch<GRK_BLOCK>(GrkValidateOp{i0, (int32_t *)a.out, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
         case GRK_ADD: return bn_lane_launch<GRK_BLOCK>(GrkAddOp{i0, i1, (uint32_t *)a.out, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
         default: return bn_lane_launch<GRK_BLOCK>(GrkMulOp{i0, i1, (uint32_t *)a.out, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
         }
-    });
-}
-// order of the checks: arguments, then context and device; nothing waits, nothing is read back
-int grk_dev(bn254_ctx *ctx, int what, const GrkArgs &a, size_t n, void *stream) {
-    int rc = grk_check(a, n); if (rc) return rc == 1 ? BN254_OK : rc;
-    return bn_dev_entry(ctx, stream, false, [&](hipStream_t s) { return grk_run(ctx, what, a, n, s); });
-}
-// the host-buffer form: at most two inputs and one output, bn_staged's shape
-int grk_host(bn254_ctx *ctx, int what, const GrkArgs &a, size_t n) {
-    int rc = grk_check(a, n); if (rc) return rc == 1 ? BN254_OK : rc;
-    BnHost h(ctx); if (h.rc) return h.rc;
-    return bn_no_throw([&] {
-        return bn_staged(ctx, {a.in[0], n * GRK_IN_BYTES[what][0]}, {a.n_in > 1 ? a.in[1] : nullptr, n * GRK_IN_BYTES[what][1]}, a.out, n * GRK_OUT_BYTES[what], nullptr, 0,
-                         [&](const BnStaged &d) { return grk_run(ctx, what, {{d.in[0], d.in[1]}, a.n_in, d.out}, n, ctx->stream); });
-    });
-}
+    }
+};
+// the two forms of a call of kind `what`: checks, sub-launches, staging
+int grk_host(bn254_ctx *ctx, int what, const BnRecordArgs &a, size_t n) { return bn_record_host(ctx, GRK_KIND[what], g_grk_launch_max, a, n, GrkLaunch{what}); }
+int grk_dev(bn254_ctx *ctx, int what, const BnRecordArgs &a, size_t n, void *stream) { return bn_record_dev(ctx, GRK_KIND[what], g_grk_launch_max, a, n, stream, GrkLaunch{what}); }
 
 // scratch guard held by the caller.  The work list goes up in one copy (bn_plan_upload: `off` may be freed as soon as the call returns).
 // Then level 0 and the fold levels, each as sub-launches of at most g_grk_launch_max.step() pieces.
@@ -128,12 +105,12 @@ int grk_msm_run(bn254_ctx *c, const void *d_p, const void *d_k, const size_t *of
 
 extern "C" {
 
-int bn254_grumpkin_validate_batch(bn254_ctx *ctx, const bn_fr *p, int32_t *status, size_t n) { return grk_host(ctx, GRK_VALIDATE, {{p}, 1, status}, n); }
-int bn254_grumpkin_add_batch(bn254_ctx *ctx, const bn_fr *p, const bn_fr *q, bn_fr *out, size_t n) { return grk_host(ctx, GRK_ADD, {{p, q}, 2, out}, n); }
-int bn254_grumpkin_mul_batch(bn254_ctx *ctx, const bn_fr *p, const uint8_t *k32, bn_fr *out, size_t n) { return grk_host(ctx, GRK_MUL, {{p, k32}, 2, out}, n); }
-int bn254_grumpkin_validate_batch_dev(bn254_ctx *ctx, const void *d_p, void *d_status, size_t n, void *stream) { return grk_dev(ctx, GRK_VALIDATE, {{d_p}, 1, d_status}, n, stream); }
-int bn254_grumpkin_add_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, void *d_out, size_t n, void *stream) { return grk_dev(ctx, GRK_ADD, {{d_p, d_q}, 2, d_out}, n, stream); }
-int bn254_grumpkin_mul_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_k32, void *d_out, size_t n, void *stream) { return grk_dev(ctx, GRK_MUL, {{d_p, d_k32}, 2, d_out}, n, stream); }
+int bn254_grumpkin_validate_batch(bn254_ctx *ctx, const bn_fr *p, int32_t *status, size_t n) { return grk_host(ctx, GRK_VALIDATE, {{p}, status}, n); }
+int bn254_grumpkin_add_batch(bn254_ctx *ctx, const bn_fr *p, const bn_fr *q, bn_fr *out, size_t n) { return grk_host(ctx, GRK_ADD, {{p, q}, out}, n); }
+int bn254_grumpkin_mul_batch(bn254_ctx *ctx, const bn_fr *p, const uint8_t *k32, bn_fr *out, size_t n) { return grk_host(ctx, GRK_MUL, {{p, k32}, out}, n); }
+int bn254_grumpkin_validate_batch_dev(bn254_ctx *ctx, const void *d_p, void *d_status, size_t n, void *stream) { return grk_dev(ctx, GRK_VALIDATE, {{d_p}, d_status}, n, stream); }
+int bn254_grumpkin_add_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_q, void *d_out, size_t n, void *stream) { return grk_dev(ctx, GRK_ADD, {{d_p, d_q}, d_out}, n, stream); }
+int bn254_grumpkin_mul_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_k32, void *d_out, size_t n, void *stream) { return grk_dev(ctx, GRK_MUL, {{d_p, d_k32}, d_out}, n, stream); }
 
 // order of the checks: empty call, arguments (nothing of them touches a device), then context and device; nothing waits, nothing is read back
 int bn254_grumpkin_msm_batch_dev(bn254_ctx *ctx, const void *d_p, const void *d_k32, const size_t *offsets, size_t m, void *d_out, void *stream) {

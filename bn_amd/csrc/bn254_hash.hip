@@ -1,19 +1,19 @@
 // Hash to G1 on the device (include/bn254_hip.h bn254_g1_map_to_curve_batch, bn254_g1_hash_to_curve_uniform_batch, bn254_g1_hash_to_curve_batch
 // and their _dev twins): the kernels - Ops of lane_launch.hpp's bn254_fr_decode_k like the other integer kernels, one lane of a body of
-// hash_ops.hpp each - and the six entry points.  One launch per call (and per sub-launch of a large one): a lane reduces its field elements, runs both
-// maps, adds and normalises, so the _dev calls use no scratch and wait on nothing.  Compiled like every unit (bn254_hip.hip: the flags).
+// hash_ops.hpp each -, the family's kind table and launch switch, and the six entry points on record_call.hpp's one path.  One launch per call
+// (and per sub-launch of a large one): a lane reduces its field elements, runs both maps, adds and normalises, so the _dev calls use no
+// scratch and wait on nothing.  Compiled like every unit (bn254_hip.hip: the flags).
 #include <hip/hip_runtime.h>
-#include <cstring>
 
 #include "hash_ops.hpp"
 #include "host_ctx.hpp"
 #include "lane_launch.hpp"
+#include "record_call.hpp"
 
 using namespace bn254;
 
 namespace {
 constexpr unsigned H2C_BLOCK = 64;
-constexpr size_t H2C_N_MAX = (size_t)1 << 40, H2C_MSG_MAX = (size_t)1 << 20;
 
 // lanes [lo, lo + n) of a call: a sub-launch, one record per lane
 struct G1MapToCurveOp {
@@ -30,7 +30,7 @@ struct G1HashUniformOp {
         if (i < n) h2c_hash_uniform_body<>(uniform, out, lo + i);
     }
 };
-// the tag travels in the argument record: DST || len(DST), the same for every lane
+// the tag travels in the argument record: DST || len(DST), the same for every lane (record_call.hpp bn_h2c_call fills it in)
 struct G1HashMsgOp {
     const uint8_t *msgs; uint64_t msg_len; uint32_t *out; uint64_t lo; uint32_t n; uint32_t dst_prime_len; uint8_t dst_prime[H2C_DST_MAX + 1];
     __device__ __forceinline__ void operator()() const {
@@ -41,41 +41,25 @@ struct G1HashMsgOp {
 
 BnLaunchMax g_hash_launch_max;      // tests only: the sub-launch size
 
-enum { H2C_MAP = 0, H2C_UNIFORM = 1, H2C_MSG = 2 };
-// arguments only: nothing here touches a device.  1 = nothing to do
-int hash_check(int which, const void *in, size_t msg_len, const void *dst, size_t dst_len, const void *out, size_t n) {
-    if (which == H2C_MSG && (dst_len == 0 || dst_len > BN254_H2C_DST_MAX || msg_len > H2C_MSG_MAX)) return BN254_E_BAD_ARG;
-    if (n == 0) return 1;
-    if (n > H2C_N_MAX || (which == H2C_MSG && n * msg_len > H2C_N_MAX)) return BN254_E_BAD_ARG;        // (no overflow: both factors were bounded above)
-    if (!out || (which == H2C_MSG && !dst) || (!in && !(which == H2C_MSG && msg_len == 0))) return BN254_E_BAD_ARG;
-    return BN254_OK;
-}
-int hash_run(bn254_ctx *ctx, int which, const void *d_in, size_t msg_len, const uint8_t *dst, size_t dst_len, void *d_out, size_t n, hipStream_t s) {
-    G1HashMsgOp m = {};
-    if (which == H2C_MSG) {
-        m.msgs = (const uint8_t *)d_in; m.msg_len = msg_len; m.out = (uint32_t *)d_out; m.dst_prime_len = (uint32_t)dst_len + 1;
-        memcpy(m.dst_prime, dst, dst_len);
-        m.dst_prime[dst_len] = (uint8_t)dst_len;
+// the family's kinds (record_call.hpp): scope, the input and the bytes of one record of it, of the output.  The message kind's record is msg_len, a per-call value
+enum { H2C_MAP, H2C_UNIFORM, H2C_MSG, H2C_KINDS };
+constexpr BnRecordKind H2C_KIND[H2C_KINDS] = {{"g1_map_to_curve", 1, {BN254_H2C_FIELD_BYTES}, sizeof(bn_g1), 0}, {"g1_hash_to_curve", 1, {BN254_H2C_UNIFORM_BYTES}, sizeof(bn_g1), 0}, {"g1_hash_to_curve_msg", 1, {0}, sizeof(bn_g1), 0}};
+struct HashLaunch {
+    int which; G1HashMsgOp m;      // m: the message kind's Op with its tag filled in (bn_h2c_call)
+    int operator()(const BnRecordArgs &a, size_t lo, size_t cnt, hipStream_t s) const {
+        if (which == H2C_MAP) return bn_lane_launch<H2C_BLOCK>(G1MapToCurveOp{(const uint8_t *)a.in[0], (uint32_t *)a.out, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
+        if (which == H2C_UNIFORM) return bn_lane_launch<H2C_BLOCK>(G1HashUniformOp{(const uint8_t *)a.in[0], (uint32_t *)a.out, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
+        G1HashMsgOp op = m;
+        op.msgs = (const uint8_t *)a.in[0]; op.out = (uint32_t *)a.out; op.lo = lo; op.n = (uint32_t)cnt;
+        return bn_lane_launch<H2C_BLOCK>(op, cnt, s);
     }
-    return bn_for_parts(n, g_hash_launch_max.step(), [&](size_t lo, size_t cnt) -> int {
-        BnScope sc(ctx, s, which == H2C_MAP ? "g1_map_to_curve" : which == H2C_UNIFORM ? "g1_hash_to_curve" : "g1_hash_to_curve_msg");
-        if (which == H2C_MAP) return bn_lane_launch<H2C_BLOCK>(G1MapToCurveOp{(const uint8_t *)d_in, (uint32_t *)d_out, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
-        if (which == H2C_UNIFORM) return bn_lane_launch<H2C_BLOCK>(G1HashUniformOp{(const uint8_t *)d_in, (uint32_t *)d_out, (uint64_t)lo, (uint32_t)cnt}, cnt, s);
-        m.lo = lo; m.n = (uint32_t)cnt;
-        return bn_lane_launch<H2C_BLOCK>(m, cnt, s);
-    });
-}
-// order of the checks: arguments, then context and device; nothing waits, nothing is read back
+};
+// the two forms of a call of kind `which`; the message kind's rules, record size and tag are record_call.hpp's bn_h2c_call
 int hash_dev(bn254_ctx *ctx, int which, const void *d_in, size_t msg_len, const uint8_t *dst, size_t dst_len, void *d_out, size_t n, void *stream) {
-    int rc = hash_check(which, d_in, msg_len, dst, dst_len, d_out, n); if (rc) return rc == 1 ? BN254_OK : rc;
-    return bn_dev_entry(ctx, stream, false, [&](hipStream_t s) { return hash_run(ctx, which, d_in, msg_len, dst, dst_len, d_out, n, s); });
+    return bn_h2c_call(H2C_KIND[which], HashLaunch{which, {}}, which == H2C_MSG, msg_len, dst, dst_len, n, [&](const BnRecordKind &k, const HashLaunch &l) { return bn_record_dev(ctx, k, g_hash_launch_max, {{d_in}, d_out}, n, stream, l); });
 }
 int hash_host(bn254_ctx *ctx, int which, const void *in, size_t msg_len, const uint8_t *dst, size_t dst_len, bn_g1 *out, size_t n) {
-    int rc = hash_check(which, in, msg_len, dst, dst_len, out, n); if (rc) return rc == 1 ? BN254_OK : rc;
-    BnHost h(ctx); if (h.rc) return h.rc;
-    const size_t rec = which == H2C_MAP ? BN254_H2C_FIELD_BYTES : which == H2C_UNIFORM ? BN254_H2C_UNIFORM_BYTES : msg_len;
-    return bn_staged(ctx, {rec ? in : nullptr, n * rec}, {nullptr, 0}, out, n * sizeof(bn_g1), nullptr, 0,
-                     [&](const BnStaged &d) { return hash_run(ctx, which, d.in[0], msg_len, dst, dst_len, d.out, n, ctx->stream); });
+    return bn_h2c_call(H2C_KIND[which], HashLaunch{which, {}}, which == H2C_MSG, msg_len, dst, dst_len, n, [&](const BnRecordKind &k, const HashLaunch &l) { return bn_record_host(ctx, k, g_hash_launch_max, {{in}, out}, n, l); });
 }
 }  // namespace
 

@@ -1,7 +1,7 @@
 // The wire format of the BN254 engine (include/bn254_hip.h; io_wire.hpp): encode / decode kernels, one record per lane, their host-buffer
 // entry points, the byte streams of variable-length records built on them, and the compressed encodings (io_compress.hpp): their kernels are
 // Ops of lane_launch.hpp's bn254_fr_decode_k and - G2 decompression, which carries the subgroup test (io_wire.hpp BN254_G2_SUBGROUP_ENDO) - of this
-// unit's bn254_g2_decode_k<Op>.
+// unit's bn254_g2_decode_k<Op>; their eight entry points are a kind table and a launch switch on record_call.hpp's one path.
 // Compiled like every unit (bn254_hip.hip: the flags).
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -13,6 +13,7 @@
 #include "io_compress.hpp"
 #include "host_ctx.hpp"
 #include "lane_launch.hpp"
+#include "record_call.hpp"
 
 using namespace bn254;
 
@@ -200,47 +201,44 @@ namespace {
 constexpr size_t WIRE_N_MAX = 0x7fffffffu / 129;            // the wire layer's limit on the records of one call
 BnLaunchMax g_compress_launch_max;          // tests only: the sub-launch size
 
-// arguments only: nothing here touches a device.  1 = nothing to do
-int compress_check(int format, const void *in, const void *out, const void *status, bool decompress, size_t n) {
-    if (format != BN254_COMPRESSED_ARK && format != BN254_COMPRESSED_GNARK) return BN254_E_BAD_ARG;
-    if (n == 0) return 1;
-    return (!in || !out || (decompress && !status) || n > WIRE_N_MAX) ? BN254_E_BAD_ARG : BN254_OK;
+// the family's kinds (record_call.hpp): scope, the input and the bytes of one record of it, of the output, of the decoders' status
+enum { CMP_G1_COMPRESS, CMP_G2_COMPRESS, CMP_G1_DECOMPRESS, CMP_G2_DECOMPRESS, CMP_KINDS };
+constexpr BnRecordKind CMP_KIND[CMP_KINDS] = {{"g1_compress", 1, {sizeof(bn_g1)}, BN254_G1_COMPRESSED_BYTES, 0}, {"g2_compress", 1, {sizeof(bn_g2)}, BN254_G2_COMPRESSED_BYTES, 0},
+                                              {"g1_decompress", 1, {BN254_G1_COMPRESSED_BYTES}, sizeof(bn_g1), sizeof(int32_t)}, {"g2_decompress", 1, {BN254_G2_COMPRESSED_BYTES}, sizeof(bn_g2), sizeof(int32_t)}};
+struct CompressLaunch {
+    int what, format;
+    int operator()(const BnRecordArgs &a, size_t lo, size_t cnt, hipStream_t s) const {
+        switch (what) {
+        case CMP_G1_COMPRESS: return bn_lane_launch<BLOCK>(G1CompressOp{(const uint32_t *)a.in[0], (uint8_t *)a.out, (uint64_t)lo, (uint32_t)cnt, format}, cnt, s);
+        case CMP_G2_COMPRESS: return bn_lane_launch<BLOCK>(G2CompressOp{(const uint32_t *)a.in[0], (uint8_t *)a.out, (uint64_t)lo, (uint32_t)cnt, format}, cnt, s);
+        case CMP_G1_DECOMPRESS: return bn_lane_launch<BLOCK>(G1DecompressOp{(const uint8_t *)a.in[0], (uint32_t *)a.out, (int32_t *)a.out2, (uint64_t)lo, (uint32_t)cnt, format}, cnt, s);
+        default:
+            hipLaunchKernelGGL(bn254_g2_decode_k<G2DecompressOp>, dim3((unsigned)((cnt + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s,
+                               G2DecompressOp{(const uint8_t *)a.in[0], (uint32_t *)a.out, (int32_t *)a.out2, (uint64_t)lo, (uint32_t)cnt, format});
+            return (int)hipGetLastError();
+        }
+    }
+};
+// the two forms of a call of kind `what`: the format first, then the shared checks (up to the wire layer's limit), sub-launches and staging
+bool compress_format_ok(int format) { return format == BN254_COMPRESSED_ARK || format == BN254_COMPRESSED_GNARK; }
+int compress_host(bn254_ctx *ctx, int what, int format, const BnRecordArgs &a, size_t n) {
+    return compress_format_ok(format) ? bn_record_host(ctx, CMP_KIND[what], g_compress_launch_max, a, n, CompressLaunch{what, format}, WIRE_N_MAX) : BN254_E_BAD_ARG;
 }
-int compress_run(bn254_ctx *ctx, int g, bool decompress, const void *d_in, int format, void *d_out, void *d_status, size_t n, hipStream_t s) {
-    return bn_for_parts(n, g_compress_launch_max.step(), [&](size_t lo, size_t cnt) -> int {
-        BnScope sc(ctx, s, decompress ? (g == 1 ? "g1_decompress" : "g2_decompress") : (g == 1 ? "g1_compress" : "g2_compress"));
-        if (!decompress && g == 1) return bn_lane_launch<BLOCK>(G1CompressOp{(const uint32_t *)d_in, (uint8_t *)d_out, (uint64_t)lo, (uint32_t)cnt, format}, cnt, s);
-        if (!decompress) return bn_lane_launch<BLOCK>(G2CompressOp{(const uint32_t *)d_in, (uint8_t *)d_out, (uint64_t)lo, (uint32_t)cnt, format}, cnt, s);
-        if (g == 1) return bn_lane_launch<BLOCK>(G1DecompressOp{(const uint8_t *)d_in, (uint32_t *)d_out, (int32_t *)d_status, (uint64_t)lo, (uint32_t)cnt, format}, cnt, s);
-        hipLaunchKernelGGL(bn254_g2_decode_k<G2DecompressOp>, dim3((unsigned)((cnt + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s,
-                           G2DecompressOp{(const uint8_t *)d_in, (uint32_t *)d_out, (int32_t *)d_status, (uint64_t)lo, (uint32_t)cnt, format});
-        return (int)hipGetLastError();
-    });
-}
-// order of the checks: arguments, then context and device; nothing waits, nothing is read back
-int compress_dev(bn254_ctx *ctx, int g, bool decompress, const void *d_in, int format, void *d_out, void *d_status, size_t n, void *stream) {
-    int rc = compress_check(format, d_in, d_out, d_status, decompress, n); if (rc) return rc == 1 ? BN254_OK : rc;
-    return bn_dev_entry(ctx, stream, false, [&](hipStream_t s) { return compress_run(ctx, g, decompress, d_in, format, d_out, d_status, n, s); });
-}
-int compress_host(bn254_ctx *ctx, int g, bool decompress, const void *in, int format, void *out, int32_t *status, size_t n) {
-    int rc = compress_check(format, in, out, status, decompress, n); if (rc) return rc == 1 ? BN254_OK : rc;
-    BnHost h(ctx); if (h.rc) return h.rc;
-    const size_t ps = g == 1 ? sizeof(bn_g1) : sizeof(bn_g2), rs = g == 1 ? BN254_G1_COMPRESSED_BYTES : BN254_G2_COMPRESSED_BYTES;
-    return bn_staged(ctx, {in, n * (decompress ? rs : ps)}, {nullptr, 0}, out, n * (decompress ? ps : rs), decompress ? status : nullptr, n * sizeof(int32_t),
-                     [&](const BnStaged &d) { return compress_run(ctx, g, decompress, d.in[0], format, d.out, d.out2, n, ctx->stream); });
+int compress_dev(bn254_ctx *ctx, int what, int format, const BnRecordArgs &a, size_t n, void *stream) {
+    return compress_format_ok(format) ? bn_record_dev(ctx, CMP_KIND[what], g_compress_launch_max, a, n, stream, CompressLaunch{what, format}, WIRE_N_MAX) : BN254_E_BAD_ARG;
 }
 }  // namespace
 
 extern "C" {
 
-int bn254_g1_compress_batch(bn254_ctx *ctx, const bn_g1 *p, int format, uint8_t *out, size_t n) { return compress_host(ctx, 1, false, p, format, out, nullptr, n); }
-int bn254_g2_compress_batch(bn254_ctx *ctx, const bn_g2 *p, int format, uint8_t *out, size_t n) { return compress_host(ctx, 2, false, p, format, out, nullptr, n); }
-int bn254_g1_decompress_batch(bn254_ctx *ctx, const uint8_t *in, int format, bn_g1 *out, int32_t *status, size_t n) { return compress_host(ctx, 1, true, in, format, out, status, n); }
-int bn254_g2_decompress_batch(bn254_ctx *ctx, const uint8_t *in, int format, bn_g2 *out, int32_t *status, size_t n) { return compress_host(ctx, 2, true, in, format, out, status, n); }
-int bn254_g1_compress_batch_dev(bn254_ctx *ctx, const void *d_p, int format, void *d_out, size_t n, void *stream) { return compress_dev(ctx, 1, false, d_p, format, d_out, nullptr, n, stream); }
-int bn254_g2_compress_batch_dev(bn254_ctx *ctx, const void *d_p, int format, void *d_out, size_t n, void *stream) { return compress_dev(ctx, 2, false, d_p, format, d_out, nullptr, n, stream); }
-int bn254_g1_decompress_batch_dev(bn254_ctx *ctx, const void *d_in, int format, void *d_out, void *d_status, size_t n, void *stream) { return compress_dev(ctx, 1, true, d_in, format, d_out, d_status, n, stream); }
-int bn254_g2_decompress_batch_dev(bn254_ctx *ctx, const void *d_in, int format, void *d_out, void *d_status, size_t n, void *stream) { return compress_dev(ctx, 2, true, d_in, format, d_out, d_status, n, stream); }
+int bn254_g1_compress_batch(bn254_ctx *ctx, const bn_g1 *p, int format, uint8_t *out, size_t n) { return compress_host(ctx, CMP_G1_COMPRESS, format, {{p}, out}, n); }
+int bn254_g2_compress_batch(bn254_ctx *ctx, const bn_g2 *p, int format, uint8_t *out, size_t n) { return compress_host(ctx, CMP_G2_COMPRESS, format, {{p}, out}, n); }
+int bn254_g1_decompress_batch(bn254_ctx *ctx, const uint8_t *in, int format, bn_g1 *out, int32_t *status, size_t n) { return compress_host(ctx, CMP_G1_DECOMPRESS, format, {{in}, out, status}, n); }
+int bn254_g2_decompress_batch(bn254_ctx *ctx, const uint8_t *in, int format, bn_g2 *out, int32_t *status, size_t n) { return compress_host(ctx, CMP_G2_DECOMPRESS, format, {{in}, out, status}, n); }
+int bn254_g1_compress_batch_dev(bn254_ctx *ctx, const void *d_p, int format, void *d_out, size_t n, void *stream) { return compress_dev(ctx, CMP_G1_COMPRESS, format, {{d_p}, d_out}, n, stream); }
+int bn254_g2_compress_batch_dev(bn254_ctx *ctx, const void *d_p, int format, void *d_out, size_t n, void *stream) { return compress_dev(ctx, CMP_G2_COMPRESS, format, {{d_p}, d_out}, n, stream); }
+int bn254_g1_decompress_batch_dev(bn254_ctx *ctx, const void *d_in, int format, void *d_out, void *d_status, size_t n, void *stream) { return compress_dev(ctx, CMP_G1_DECOMPRESS, format, {{d_in}, d_out, d_status}, n, stream); }
+int bn254_g2_decompress_batch_dev(bn254_ctx *ctx, const void *d_in, int format, void *d_out, void *d_status, size_t n, void *stream) { return compress_dev(ctx, CMP_G2_DECOMPRESS, format, {{d_in}, d_out, d_status}, n, stream); }
 
 // internal (not in the header; tests and tools/time_compress.py): an override of the sub-launch size of the eight calls above (0 restores
 // BN_LAUNCH_MAX) so that a test reaches the seam between two sub-launches with a handful of records, and which chain form the square roots run

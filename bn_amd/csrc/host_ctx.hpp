@@ -3,7 +3,7 @@
 // multi-pairings and the multi-scalar multiplications; bn254_wire.hip: the wire format; bn254_multi.hip: pipelined host-buffer path,
 // multi-device fan-out, RCCL exchange; bn254_{fr,ntt,dot,scan,mle,poseidon,hash,babyjub,grumpkin}.hip: the families of integer kernels over Fr, hash-to-curve and the curves over Fr,
 // each with its Ops and entry points).  The host arithmetic that needs no device is host_plan.hpp; the kernel shell, the launchers and the
-// overrides of the integer kernels are lane_launch.hpp.  Not part of the ABI.
+// overrides of the integer kernels are lane_launch.hpp; the one call path of the record-per-lane families is record_call.hpp.  Not part of the ABI.
 //
 // Concurrency contract (what the header promises and these structures implement):
 //   * any number of host threads may call the HOST-BUFFER entry points of one context - including the process-wide default
@@ -143,7 +143,7 @@ struct bn254_ctx {
     BnBuf base_stage;                   // the base of a table build on the device ...
     BnBuf base_stage_host{nullptr, 0, true};    // ... and its pinned staging, rewritten only after base_stage_ev (its last copy) completed
     hipEvent_t base_stage_ev = nullptr;
-    BnBuf stage[4];                     // device staging of the small host-buffer entry points (bn_staged: two inputs, two outputs; [3] holds a third input instead)
+    BnBuf stage[4];                     // device staging of the small host-buffer entry points (bn_staged_n: [0] the inputs, [2] and [3] the outputs; [0] and [1] also serve the calls that stage by hand)
     BnSlot slot[BN_MAX_SLOTS];          // pipelined path (bn254_multi.hip)
     // leases of those slots: a batch of up to one chunk takes ONE of the first two (two callers overlap on the GPU - the number
     // of streams the hardware overlaps without loss), a multi-chunk batch takes all of them
@@ -308,30 +308,35 @@ struct BnHost {
     }
 };
 // The body of a host-buffer entry point of the shape copy-in, device calls, copy-out, synchronise, on the context's stream under a BnHost:
-// the inputs (skipped when NULL; nothing copied for zero bytes) are staged in ctx->stage[0..1], body(d) enqueues the work on the staged
-// inputs d.in[] (NULL for a skipped one) and the device buffers d.out / d.out2, then `out` (and `out2` when given) are copied back.
-// A third input takes the place of the second output (ctx->stage[3]): only without an out2.
+// the inputs (skipped when NULL; nothing copied for zero bytes) are staged one after the other in ctx->stage[0], each at a multiple of
+// BN_STAGE_ALIGN bytes - an allocation's own alignment, so an input of any size leaves the next one as aligned as a buffer of its own -,
+// body(d) enqueues the work on the staged inputs d.in[] (NULL for a skipped one) and the device buffers d.out / d.out2 (ctx->stage[2],
+// ctx->stage[3]), then `out` (and `out2` when given) are copied back.
 // On an error the stream is drained first: copies that read or write the caller's buffers may still be in flight.
+// bn_staged_n is the one implementation of that sequence; bn_staged is its form for up to three inputs written out as arguments.
+constexpr int BN_STAGE_INS = 4;
+constexpr size_t BN_STAGE_ALIGN = 256;
 struct BnStageIn { const void *p; size_t bytes; };
-struct BnStaged { void *in[3], *out, *out2; };
+struct BnStaged { void *in[BN_STAGE_INS], *out, *out2; };
 template <class Body>
-int bn_staged(bn254_ctx *ctx, BnStageIn in0, BnStageIn in1, void *out, size_t out_bytes, void *out2, size_t out2_bytes, Body body, BnStageIn in2 = {nullptr, 0}) {
+int bn_staged_n(bn254_ctx *ctx, const BnStageIn *in, int n_in, void *out, size_t out_bytes, void *out2, size_t out2_bytes, Body body) {
     const hipStream_t s = ctx->stream;
-    const BnStageIn in[3] = {in0, in1, in2};
-    BnBuf *const in_buf[3] = {&ctx->stage[0], &ctx->stage[1], &ctx->stage[3]};
-    if (in2.p && out2) return BN254_E_INTERNAL;
+    if (n_in > BN_STAGE_INS) return BN254_E_INTERNAL;
     auto run = [&]() -> int {
         int rc;
-        BnStaged d = {};
-        for (int i = 0; i < 3; ++i) {
-            if (!in[i].p) continue;
-            if ((rc = in_buf[i]->reserve(in[i].bytes))) return rc;
-            d.in[i] = in_buf[i]->p;
+        size_t at[BN_STAGE_INS], total = 0;
+        for (int i = 0; i < n_in; ++i) {
+            at[i] = total;
+            if (in[i].p) total += (in[i].bytes + BN_STAGE_ALIGN - 1) / BN_STAGE_ALIGN * BN_STAGE_ALIGN;
         }
-        if ((rc = ctx->stage[2].reserve(out_bytes)) || (out2 && (rc = ctx->stage[3].reserve(out2_bytes)))) return rc;
+        if ((rc = ctx->stage[0].reserve(total)) || (rc = ctx->stage[2].reserve(out_bytes)) || (out2 && (rc = ctx->stage[3].reserve(out2_bytes)))) return rc;
+        BnStaged d = {};
         d.out = ctx->stage[2].p; d.out2 = out2 ? ctx->stage[3].p : nullptr;
-        for (int i = 0; i < 3; ++i)
-            if (d.in[i] && in[i].bytes) HIP_TRY(hipMemcpyAsync(d.in[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, s));
+        for (int i = 0; i < n_in; ++i) {
+            if (!in[i].p) continue;
+            d.in[i] = (char *)ctx->stage[0].p + at[i];
+            if (in[i].bytes) HIP_TRY(hipMemcpyAsync(d.in[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, s));
+        }
         if ((rc = body(d))) return rc;
         HIP_TRY(hipMemcpyAsync(out, d.out, out_bytes, hipMemcpyDeviceToHost, s));
         if (out2) HIP_TRY(hipMemcpyAsync(out2, d.out2, out2_bytes, hipMemcpyDeviceToHost, s));
@@ -340,6 +345,11 @@ int bn_staged(bn254_ctx *ctx, BnStageIn in0, BnStageIn in1, void *out, size_t ou
     const int rc = run();
     if (rc) (void)hipStreamSynchronize(s);
     return rc;
+}
+template <class Body>
+int bn_staged(bn254_ctx *ctx, BnStageIn in0, BnStageIn in1, void *out, size_t out_bytes, void *out2, size_t out2_bytes, Body body, BnStageIn in2 = {nullptr, 0}) {
+    const BnStageIn in[3] = {in0, in1, in2};
+    return bn_staged_n(ctx, in, 3, out, out_bytes, out2, out2_bytes, body);
 }
 
 extern "C" {

@@ -49,10 +49,16 @@ def _verify_both(eng, rows, stream=None):
     return host, dev
 
 
-def test_the_challenge_gives_the_published_answers(eng):
+@pytest.fixture(scope="module")
+def challenges():
+    """(A, R8, M, the model's challenges): the published inputs, the edge elements and 63 random rows"""
     ins = list(BC.KNOWN_POSEIDON5) + [(BC.R - 1,) * 5, (0,) * 5] + [tuple(FC.rand(np.random.default_rng(i)) for _ in range(5)) for i in range(63)]
     A = BC.point_rows([(i[2], i[3]) for i in ins]); R8 = BC.point_rows([(i[0], i[1]) for i in ins]); M = FC.rows([i[4] for i in ins])
-    want = FC.rows([BC.KNOWN_POSEIDON5.get(i) or BC.poseidon5(i) for i in ins])
+    return A, R8, M, FC.rows([BC.KNOWN_POSEIDON5.get(i) or BC.poseidon5(i) for i in ins])
+
+
+def test_the_challenge_gives_the_published_answers(eng, challenges):
+    A, R8, M, want = challenges
     assert np.array_equal(eng.eddsa_poseidon_challenge_batch(A, R8, M), want)
     assert np.array_equal(dev_call(eng.eddsa_poseidon_challenge_batch_dev, [A, R8, M], np.zeros_like(M)), want)
     assert np.array_equal(eng.eddsa_poseidon_challenge_batch(A[:1], R8[:1], M[:1]), want[:1])
@@ -77,15 +83,21 @@ def test_every_failing_class_among_valid_rows(eng, mixed):
     assert np.array_equal(dev, want), np.flatnonzero(dev != want)
 
 
-def test_the_same_batch_through_the_seam_and_on_a_stream(eng, lib, mixed):
+def test_the_same_batch_through_the_seam_and_on_a_stream(eng, lib, mixed, challenges):
     import torch
     rows, want = mixed
+    A, R8, M, ch_want = (x[:5] for x in challenges)
     try:
         assert lib.bn254_bjj_set_launch_max(64) == 0
         host, dev = _verify_both(eng, rows, torch.cuda.Stream())
+        assert lib.bn254_bjj_set_launch_max(2) == 0                # 5 records: 2, 2 and 1 - an odd count, where a wrong staging offset or `lo` shows
+        host5, dev5 = _verify_both(eng, rows[10:15])
+        ch_host, ch_dev = eng.eddsa_poseidon_challenge_batch(A, R8, M), dev_call(eng.eddsa_poseidon_challenge_batch_dev, [A, R8, M], np.zeros_like(M))
     finally:
         assert lib.bn254_bjj_set_launch_max(0) == 0
     assert np.array_equal(host, want) and np.array_equal(dev, want)
+    assert want[10:15].tolist() == [0, 0, 6, 0, 0] and np.array_equal(host5, want[10:15]) and np.array_equal(dev5, want[10:15])
+    assert np.array_equal(ch_host, ch_want) and np.array_equal(ch_dev, ch_want)
 
 
 def test_sign_then_verify_and_the_host_verifier(eng):

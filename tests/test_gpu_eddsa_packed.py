@@ -64,9 +64,12 @@ def test_the_same_batch_across_two_seams_on_a_stream(eng, lib, mixed):
     try:
         assert lib.bn254_bjj_set_launch_max(64) == 0
         host, dev = _both(eng, A32, SIG, M, torch.cuda.Stream())
+        assert lib.bn254_bjj_set_launch_max(2) == 0                # 5 records: 2, 2 and 1 - an odd count, where a wrong staging offset or `lo` shows
+        host5, dev5 = _both(eng, A32[26:31], SIG[26:31], M[26:31])
     finally:
         assert lib.bn254_bjj_set_launch_max(0) == 0
     assert np.array_equal(host, want) and np.array_equal(dev, want)
+    assert want[26:31].tolist() == [0, 6, 0, 0, 1] and np.array_equal(host5, want[26:31]) and np.array_equal(dev5, want[26:31])
 
 
 def test_it_agrees_with_the_unpacked_verifier_where_the_points_unpack(eng, mixed):

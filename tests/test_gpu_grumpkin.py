@@ -145,9 +145,12 @@ def test_the_seam_between_sub_launches(eng, lib, ref):
     try:
         assert lib.bn254_grumpkin_set_launch_max(64) == 0               # 130 records: sub-launches of 64, 64 and 2
         forms = _all_forms(eng, ref, 130)
+        assert lib.bn254_grumpkin_set_launch_max(2) == 0                # 5 records: 2, 2 and 1 - an odd count, where a wrong staging offset or `lo` shows
+        odd = _all_forms(eng, ref, 5)
     finally:
         assert lib.bn254_grumpkin_set_launch_max(0) == 0
     _check(forms, "seam")
+    _check(odd, "seam, 5 records in sub-launches of 2")
 
 
 def test_in_place(eng, ref):
